@@ -4,6 +4,11 @@
 Contract: ``python bench.py --gpus N --steps K --warmup W`` (N>1 under torch.distributed.run, one
 rank per GPU over RCCL).  W untimed warm-up steps, then exactly K steps timed between
 barrier + torch.cuda.synchronize() on both sides; MAX over ranks; rank 0 prints ONE JSON line.
+A plain run does only that.  ``--full`` adds everything else the line can carry, measured after the timed region:
+200 more steps, the exposed all-reduce (several ranks), the two kernel rooflines, the student and generation legs
+and the CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step computed (loss, parameters after its
+Adam update, the gradients it applied) as DIR/<name>.npy; inputs and initial weights are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 Workload = BASELINE.json configs[1]: 3x[1..512] dilations, 64 residual / 256 skip channels,
 256-way mu-law softmax, batch 8 x 16000 samples per GPU, bf16 MFMA with fp32 accumulation,
@@ -34,6 +39,14 @@ def synthetic_audio(B, T, seed=0):
     f = 110.0 * (1 + np.arange(B, dtype=np.float64))[:, None]
     x = 0.5 * np.sin(2.0 * np.pi * f * t / 16000.0) + 0.05 * rng.standard_normal((B, T))
     return np.clip(x, -1.0, 1.0).astype(np.float32)
+
+
+def dump_outputs(eng, out_dir):
+    """What the last step left its caller, as fp32 .npy files: the loss it returned, the flat parameter buffer after its
+    Adam update and the flat gradient it applied (engine.py's section layout; 4 MB each for the 30-layer stack)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("loss", eng.loss), ("params", eng.params), ("grads", eng.grads)):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def profiled_traffic(kernel_substr, config_key):
@@ -148,10 +161,16 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--length", type=int, default=16000)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the student (config 4) and generation (config 5) legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: 200 more steps, the "
+                         "exposed all-reduce, the rooflines, the student and generation legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's loss, parameters and gradients to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="(--full) skip the 200 more steps and the student (config 4) and generation (config 5) legs")
     ap.add_argument("--no-graph-launch-timing", action="store_true",
-                    help="time the dominant kernel's launches from the eager span events only")
+                    help="(--full) time the dominant kernel's launches from the eager span events only")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("SRWN_GRAPH", "1")))
     args = ap.parse_args()
 
@@ -233,12 +252,14 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt_s = float(tt.item())
     loss = float(eng.loss.item())
+    if args.dump_outputs and rank == 0:     # before --full runs more steps on the same buffers
+        dump_outputs(eng, args.dump_outputs)
 
     # ---- outside the timed region, not `value`: the same step over a longer window.  The K timed steps (33 ms at K = 20)
     # start a few ms after the card was idle (graph capture, barrier); A/Bs on one box (tools/ab_step.py: 200-step
     # windows after 20 warm-up replays) read 3-4 % lower than a 20-step window there, so both are reported.
     ms_steady = None
-    if use_graph and not args.no_extras:
+    if args.full and use_graph and not args.no_extras:
         nst = 200
         sync()
         t1 = time.perf_counter()
@@ -254,7 +275,7 @@ def main():
     graphs_per_step, allreduce_exposed_us, allreduce_bytes = None, None, None
     if use_graph:
         graphs_per_step = 1 + (eng._g_b2 is not None) + (eng._g_opt is not None)
-    if dist is not None and use_graph and eng._g_opt is not None:
+    if args.full and dist is not None and use_graph and eng._g_opt is not None:
         ts = []
         for _ in range(5):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -278,133 +299,135 @@ def main():
         allreduce_bytes = {"bucket_a_overlapped": 4 * (eng.nparams - eng.bucket_off) if eng._g_b2 is not None else 0,
                            "bucket_b_exposed": 4 * (eng.bucket_off if eng._g_b2 is not None else eng.nparams)}
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream, eager launches
-    eng.timing = True
-    eng.spans.clear()
-    npass = max(min(args.steps, 5), 1)
-    for _ in range(npass):
-        eng.train_step()
-    torch.cuda.synchronize()
-    eng.timing = False
-    # second timing pass: the same spans with the side-stream overlap of the real schedule left on (only where the
-    # schedule has one: with the group kernels the default schedule runs one kernel at a time, SRWN_OVERLAP)
-    spans_serial = dict(eng.spans)
-    spans_ov_raw = spans_serial
-    if eng.overlap:
-        eng.spans = {}
-        eng.timing_overlap = True
+    roofline = roofline_gemm = None
+    if args.full:
+        # ---- roofline of the dominant kernel: HIP events on the launch stream, eager launches
+        eng.timing = True
+        eng.spans.clear()
+        npass = max(min(args.steps, 5), 1)
         for _ in range(npass):
             eng.train_step()
         torch.cuda.synchronize()
-        eng.timing_overlap = False
-        spans_ov_raw, eng.spans = dict(eng.spans), spans_serial
-    # median over the timing passes (a mean lets one stray pass -- a first-touch allocation, a late module load --
-    # stand for the kernel: round 1's driver record carried a 25x outlier that way), summed over the launches of a span
-    def _span_ms(v):
-        per_pass = len(v) // npass if len(v) >= npass else 1
-        tot = [sum(s.elapsed_time(e) for s, e in v[i * per_pass:(i + 1) * per_pass]) for i in range(len(v) // per_pass)]
-        return float(np.median(tot))
-    spans = {k: _span_ms(v) for k, v in eng.spans.items()}   # ms per step
-    spans_ov = {k: _span_ms(v) for k, v in spans_ov_raw.items()}
-    fl = algorithmic_flops(N, L, R, S, C, Kw)
-    kflops = {"skip_sum": 2.0 * N * L * R * S, "wgrad_skip": 2.0 * N * L * R * S}
-    es = 2 if args.dtype == "bf16" else 4
-    step_ms = 1e3 * dt_s / args.steps
-    # Dominant kernel by time = the backward chain of the residual stack, HBM-bound.
-    #  default path (fused_wt): group_bwd_kernel in its weight-gradient-tile instantiation, one launch per layer group.
-    #    Algorithmic bytes per launch: per sample and layer it reads z, dcs and the transposed x and c tiles (4 x R x es
-    #    bytes), reads the group's top gradient (where there is one) and writes its bottom gradient once (R x es each);
-    #    the fp32 partial sums it leaves (one 3 R R + 2 R block per workgroup and layer) are in the measured traffic.
-    #  SRWN_FUSE_WT=0: the same kernel without the weight gradients: reads z, dcs, writes df, G (4 x R x es) + top gradient;
-    #  SRWN_FUSE=0: layer_bwd_kernel, one launch per layer: reads G_{l+2}, df_{l+1}, dcs_l, z_l, writes G_{l+1}, df_l.
-    fused = eng.fused_bwd
-    cfg_key = "config: %s B=%d T=%d L=%d R=%d S=%d" % (args.dtype, B, T, L, R, S)
-    # The operand list behind bytes_per_launch is stated in the line (roofline.operands), and the same figure over the
-    # MINIMAL operand set beside it (frac_min_operands): c^T is z sigmoid(z) stored a second time in another layout, so
-    # counting it raises the algorithmic bytes without being information the kernel could not have derived.
-    if fused:
-        ngr = len(eng.groups)
-        extra = 1.0 if eng.fused_wt else 0.0      # (the bottom gradient; without the weight gradients it is one of the 4)
-        bwd_bytes_step = sum((4.0 * (l1 - l0) + extra + (1.0 if l1 < L else 0.0)) * R * es * N for l0, l1 in eng.groups)
-        nlaunch, kname = ngr, "group_bwd_kernel"
-        traffic, traffic_src = profiled_traffic("group_bwd_kernel", cfg_key + (" wt=1" if eng.fused_wt else " wt=0"))
-        if eng.fused_wt:
-            operands = ("per layer and sample row: z, dcs, x^T tile, c^T tile read (4 x R x %d B); per launch: the group's "
-                        "top gradient read (where there is one), its bottom gradient written (R x %d B each); the fp32 "
-                        "weight-gradient partials it leaves are in `traffic`, not here" % (es, es))
-            min_bytes_step = sum((3.0 * (l1 - l0) + 1.0 + (1.0 if l1 < L else 0.0)) * R * es * N for l0, l1 in eng.groups)
-            operands_min = "x, z, dcs per layer (c^T = z sigmoid(z) is derivable from z) + top gradient in + bottom gradient out"
+        eng.timing = False
+        # second timing pass: the same spans with the side-stream overlap of the real schedule left on (only where the
+        # schedule has one: with the group kernels the default schedule runs one kernel at a time, SRWN_OVERLAP)
+        spans_serial = dict(eng.spans)
+        spans_ov_raw = spans_serial
+        if eng.overlap:
+            eng.spans = {}
+            eng.timing_overlap = True
+            for _ in range(npass):
+                eng.train_step()
+            torch.cuda.synchronize()
+            eng.timing_overlap = False
+            spans_ov_raw, eng.spans = dict(eng.spans), spans_serial
+        # median over the timing passes (a mean lets one stray pass -- a first-touch allocation, a late module load --
+        # stand for the kernel: round 1's driver record carried a 25x outlier that way), summed over the launches of a span
+        def _span_ms(v):
+            per_pass = len(v) // npass if len(v) >= npass else 1
+            tot = [sum(s.elapsed_time(e) for s, e in v[i * per_pass:(i + 1) * per_pass]) for i in range(len(v) // per_pass)]
+            return float(np.median(tot))
+        spans = {k: _span_ms(v) for k, v in eng.spans.items()}   # ms per step
+        spans_ov = {k: _span_ms(v) for k, v in spans_ov_raw.items()}
+        fl = algorithmic_flops(N, L, R, S, C, Kw)
+        kflops = {"skip_sum": 2.0 * N * L * R * S, "wgrad_skip": 2.0 * N * L * R * S}
+        es = 2 if args.dtype == "bf16" else 4
+        step_ms = 1e3 * dt_s / args.steps
+        # Dominant kernel by time = the backward chain of the residual stack, HBM-bound.
+        #  default path (fused_wt): group_bwd_kernel in its weight-gradient-tile instantiation, one launch per layer group.
+        #    Algorithmic bytes per launch: per sample and layer it reads z, dcs and the transposed x and c tiles (4 x R x es
+        #    bytes), reads the group's top gradient (where there is one) and writes its bottom gradient once (R x es each);
+        #    the fp32 partial sums it leaves (one 3 R R + 2 R block per workgroup and layer) are in the measured traffic.
+        #  SRWN_FUSE_WT=0: the same kernel without the weight gradients: reads z, dcs, writes df, G (4 x R x es) + top gradient;
+        #  SRWN_FUSE=0: layer_bwd_kernel, one launch per layer: reads G_{l+2}, df_{l+1}, dcs_l, z_l, writes G_{l+1}, df_l.
+        fused = eng.fused_bwd
+        cfg_key = "config: %s B=%d T=%d L=%d R=%d S=%d" % (args.dtype, B, T, L, R, S)
+        # The operand list behind bytes_per_launch is stated in the line (roofline.operands), and the same figure over the
+        # MINIMAL operand set beside it (frac_min_operands): c^T is z sigmoid(z) stored a second time in another layout, so
+        # counting it raises the algorithmic bytes without being information the kernel could not have derived.
+        if fused:
+            ngr = len(eng.groups)
+            extra = 1.0 if eng.fused_wt else 0.0      # (the bottom gradient; without the weight gradients it is one of the 4)
+            bwd_bytes_step = sum((4.0 * (l1 - l0) + extra + (1.0 if l1 < L else 0.0)) * R * es * N for l0, l1 in eng.groups)
+            nlaunch, kname = ngr, "group_bwd_kernel"
+            traffic, traffic_src = profiled_traffic("group_bwd_kernel", cfg_key + (" wt=1" if eng.fused_wt else " wt=0"))
+            if eng.fused_wt:
+                operands = ("per layer and sample row: z, dcs, x^T tile, c^T tile read (4 x R x %d B); per launch: the group's "
+                            "top gradient read (where there is one), its bottom gradient written (R x %d B each); the fp32 "
+                            "weight-gradient partials it leaves are in `traffic`, not here" % (es, es))
+                min_bytes_step = sum((3.0 * (l1 - l0) + 1.0 + (1.0 if l1 < L else 0.0)) * R * es * N for l0, l1 in eng.groups)
+                operands_min = "x, z, dcs per layer (c^T = z sigmoid(z) is derivable from z) + top gradient in + bottom gradient out"
+            else:
+                operands = "per layer and sample row: z, dcs read, df, G written (4 x R x %d B); per launch: the top gradient read" % es
+                min_bytes_step, operands_min = bwd_bytes_step, "the same"
         else:
-            operands = "per layer and sample row: z, dcs read, df, G written (4 x R x %d B); per launch: the top gradient read" % es
+            bwd_bytes_step = 6.0 * R * es * N * (L + 1)
+            nlaunch, kname = L + 1, "layer_bwd_kernel"
+            traffic, traffic_src = profiled_traffic("layer_bwd_kernel", cfg_key + " fuse=0")
+            operands = "per launch and sample row: G_{l+2}, df_{l+1}, dcs_l, z_l read, G_{l+1}, df_l written (6 x R x %d B)" % es
             min_bytes_step, operands_min = bwd_bytes_step, "the same"
-    else:
-        bwd_bytes_step = 6.0 * R * es * N * (L + 1)
-        nlaunch, kname = L + 1, "layer_bwd_kernel"
-        traffic, traffic_src = profiled_traffic("layer_bwd_kernel", cfg_key + " fuse=0")
-        operands = "per launch and sample row: G_{l+2}, df_{l+1}, dcs_l, z_l read, G_{l+1}, df_l written (6 x R x %d B)" % es
-        min_bytes_step, operands_min = bwd_bytes_step, "the same"
-    bwd_launch_ms = spans["bwd_layers"] / nlaunch
-    eager_launch_us = 1e3 * bwd_launch_ms
-    # The eager passes above put an event pair around every launch (the per-kernel spans), and each event is a packet
-    # between two kernels: the launches of the dominant kernel come out 15-20 % longer than the profiler's durations.
-    # So the figure the roofline uses is taken the way the timed region runs them: the step's backward launches captured
-    # into a hipGraph (four times over: they only read the forward's buffers), replayed between two events on the
-    # launch stream.
-    if fused and eng.fused_wt and not args.no_graph_launch_timing:
-        reps = 4
-        cs = torch.cuda.Stream()
-        cs.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(cs):
-            def chain():
-                for l0, l1 in reversed(eng.groups):
-                    eng._group_bwd_wt(l0, l1)
-            chain()
-            cs.synchronize()
-            cg = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(cg, stream=cs):
-                for _ in range(reps):
-                    chain()
-            for _ in range(4):      # (untimed: a replay is 2.4 ms, and the first ones after the idle capture run 10 % long)
-                cg.replay()
-            ts = []
-            for _ in range(11):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(cs)
-                cg.replay()
-                e1.record(cs)
-                e1.synchronize()
-                ts.append(e0.elapsed_time(e1))
-        torch.cuda.current_stream().wait_stream(cs)
-        bwd_launch_ms = float(np.median(ts)) / (reps * nlaunch)
-    ach_bw = bwd_bytes_step / nlaunch / (bwd_launch_ms * 1e-3) / 1e9
-    roofline = {"kernel": kname, "bound": "hbm", "achieved": ach_bw, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                "frac": ach_bw / PEAK_HBM_GBS,
-                # HBM bytes per launch from the rocprofv3 PMC passes of the same command (FETCH_SIZE x 2 + WRITE_SIZE,
-                # MI355X_MICROARCH.md), read at run time from the tracked profile named in traffic_source (null when
-                # no tracked profile covers this configuration); not measured in this run
-                "traffic": traffic, "traffic_source": traffic_src,
-                "bytes_per_launch": bwd_bytes_step / nlaunch, "operands": operands,
-                "bytes_per_launch_min_operands": min_bytes_step / nlaunch, "operands_min": operands_min,
-                "frac_min_operands": min_bytes_step / nlaunch / (bwd_launch_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                # what a streaming kernel with this kernel's mix of directions (87 % reads) reaches on this chip
-                # (tools/micro/cuingest.hip, profiles/r04_q_cu_ingest.txt: 1 KB written per 4 KB read); not a peak
-                "stream_rate_same_mix_GBs": 5370.0,
-                "launch_us": 1e3 * bwd_launch_ms,
-                "launch_us_eager_with_span_events": eager_launch_us,
-                # the same launches timed inside the schedule the timed region replays (weight-gradient passes running
-                # beside them on the side stream): what the kernel costs in the step, vs. alone on the chip above
-                "launch_us_in_schedule": 1e3 * spans_ov["bwd_layers"] / nlaunch if "bwd_layers" in spans_ov else None,
-                "launches_per_step": nlaunch, "share_of_step": nlaunch * bwd_launch_ms / step_ms,
-                "whole_step_mfma_frac": fl["per_step"] / (dt_s / args.steps) / 1e12 / PEAK_BF16_TFLOPS,
-                "spans_ms": spans}
-    # the largest single kernel by FLOPs: the skip sum as one K = L*R contraction (row-streaming MFMA GEMM)
-    dom = max((k for k in spans if k in ("skip_sum", "wgrad_skip")), key=lambda k: spans[k])
-    achieved = kflops[dom] / (spans[dom] * 1e-3) / 1e12
-    roofline_gemm = {"kernel": dom, "bound": "mfma", "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / PEAK_BF16_TFLOPS,
-                     }
-    roofline_gemm["traffic"], roofline_gemm["traffic_source"] = profiled_traffic(
-        {"skip_sum": "rowgemm_kernel", "wgrad_skip": "wgrad256_kernelIDF16bLi1"}[dom], cfg_key)
+        bwd_launch_ms = spans["bwd_layers"] / nlaunch
+        eager_launch_us = 1e3 * bwd_launch_ms
+        # The eager passes above put an event pair around every launch (the per-kernel spans), and each event is a packet
+        # between two kernels: the launches of the dominant kernel come out 15-20 % longer than the profiler's durations.
+        # So the figure the roofline uses is taken the way the timed region runs them: the step's backward launches captured
+        # into a hipGraph (four times over: they only read the forward's buffers), replayed between two events on the
+        # launch stream.
+        if fused and eng.fused_wt and not args.no_graph_launch_timing:
+            reps = 4
+            cs = torch.cuda.Stream()
+            cs.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(cs):
+                def chain():
+                    for l0, l1 in reversed(eng.groups):
+                        eng._group_bwd_wt(l0, l1)
+                chain()
+                cs.synchronize()
+                cg = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(cg, stream=cs):
+                    for _ in range(reps):
+                        chain()
+                for _ in range(4):      # (untimed: a replay is 2.4 ms, and the first ones after the idle capture run 10 % long)
+                    cg.replay()
+                ts = []
+                for _ in range(11):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(cs)
+                    cg.replay()
+                    e1.record(cs)
+                    e1.synchronize()
+                    ts.append(e0.elapsed_time(e1))
+            torch.cuda.current_stream().wait_stream(cs)
+            bwd_launch_ms = float(np.median(ts)) / (reps * nlaunch)
+        ach_bw = bwd_bytes_step / nlaunch / (bwd_launch_ms * 1e-3) / 1e9
+        roofline = {"kernel": kname, "bound": "hbm", "achieved": ach_bw, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": ach_bw / PEAK_HBM_GBS,
+                    # HBM bytes per launch from the rocprofv3 PMC passes of the same command (FETCH_SIZE x 2 + WRITE_SIZE,
+                    # MI355X_MICROARCH.md), read at run time from the tracked profile named in traffic_source (null when
+                    # no tracked profile covers this configuration); not measured in this run
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "bytes_per_launch": bwd_bytes_step / nlaunch, "operands": operands,
+                    "bytes_per_launch_min_operands": min_bytes_step / nlaunch, "operands_min": operands_min,
+                    "frac_min_operands": min_bytes_step / nlaunch / (bwd_launch_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                    # what a streaming kernel with this kernel's mix of directions (87 % reads) reaches on this chip
+                    # (tools/micro/cuingest.hip, profiles/r04_q_cu_ingest.txt: 1 KB written per 4 KB read); not a peak
+                    "stream_rate_same_mix_GBs": 5370.0,
+                    "launch_us": 1e3 * bwd_launch_ms,
+                    "launch_us_eager_with_span_events": eager_launch_us,
+                    # the same launches timed inside the schedule the timed region replays (weight-gradient passes running
+                    # beside them on the side stream): what the kernel costs in the step, vs. alone on the chip above
+                    "launch_us_in_schedule": 1e3 * spans_ov["bwd_layers"] / nlaunch if "bwd_layers" in spans_ov else None,
+                    "launches_per_step": nlaunch, "share_of_step": nlaunch * bwd_launch_ms / step_ms,
+                    "whole_step_mfma_frac": fl["per_step"] / (dt_s / args.steps) / 1e12 / PEAK_BF16_TFLOPS,
+                    "spans_ms": spans}
+        # the largest single kernel by FLOPs: the skip sum as one K = L*R contraction (row-streaming MFMA GEMM)
+        dom = max((k for k in spans if k in ("skip_sum", "wgrad_skip")), key=lambda k: spans[k])
+        achieved = kflops[dom] / (spans[dom] * 1e-3) / 1e12
+        roofline_gemm = {"kernel": dom, "bound": "mfma", "achieved": achieved, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                         "frac": achieved / PEAK_BF16_TFLOPS,
+                         }
+        roofline_gemm["traffic"], roofline_gemm["traffic_source"] = profiled_traffic(
+            {"skip_sum": "rowgemm_kernel", "wgrad_skip": "wgrad256_kernelIDF16bLi1"}[dom], cfg_key)
 
     if rank == 0:
         out = {
@@ -425,7 +448,7 @@ def main():
             out["allreduce_exposed_us"] = allreduce_exposed_us
             out["allreduce_bytes"] = allreduce_bytes
             out["dist_backend"] = dist.get_backend()
-        if not args.no_extras and world == 1 and args.dtype == "bf16":
+        if args.full and not args.no_extras and world == 1 and args.dtype == "bf16":
             # after (and outside) the timed region: BASELINE configs[3] and [4] at their one-GPU shapes
             del eng
             torch.cuda.empty_cache()
@@ -446,7 +469,7 @@ def main():
             except Exception as e:
                 extra["gen_error"] = repr(e)
             out["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the CPU restatement on the box's host cores, and the same on ONE thread (half the time budget)
             out["cpu_baseline"] = cpu_baseline(dil, R, S, C, threads=min(os.cpu_count() or 1, 16), seconds_budget=16.0)
             out["cpu_baseline_1thread"] = cpu_baseline(dil, R, S, C, threads=1, seconds_budget=8.0)
