@@ -370,6 +370,19 @@ int srwn_pooled_head(const float* mean, const float* w2, const float* b2, const 
 int srwn_bcast_mask(const float* dmean, const void* r1, void* out, int32_t B, int32_t T, int32_t S, float scale,
                     int32_t dtype, void* stream);
 
+/* ---- contrastive head of class SiameseWaveNet (model.py:660-797; since srwn_version() 101).  The two towers share
+ * their weights, so they run as ONE batch of rows = 2P clips: rows 0..P-1 the left clips, P..2P-1 the right ones.  On
+ * the time-mean of srwn_time_mean (the pool commutes with the last 1x1):
+ *   emb[r,k] = b2[k] + sum_s mean[r,s]*w2[s,k]                        [rows,D]   (w2 [S,ldw], columns >= D ignored)
+ *   dist[p]  = sqrt(1e-8 + |emb[p] - emb[P+p]|^2)                      [P]        (model.py:736)
+ *   loss     = mean_p y_p*d_p^2/2 + (1-y_p)*max(0, margin-d_p)^2/2                (model.py:747-749; y = 1: "same")
+ * with labels [P] (plain floats) also gw2/gb2 (written, [S,ldw]/[ldw]; gb2 is exactly 0) and dmean = d loss / d mean
+ * [rows,S] (needs an even row count, loss and the gradient outputs).  labels == NULL: emb only, and dist when `dist` is
+ * given (even row count).  One workgroup: rows*D + 2P floats must fit 64 KiB of LDS (else SRWN_E_SHAPE). */
+int srwn_contrastive_head(const float* mean, const float* w2, const float* b2, const float* labels, float margin,
+                          float* emb, float* dist, float* loss, float* gw2, float* gb2, float* dmean, int32_t rows,
+                          int32_t S, int32_t D, int32_t ldw, void* stream);
+
 /* ---- weight gradient of 256-wide products as ONE time-contraction GEMM (tf.gradients of ops.py:44,
  * model.py:53,56 kernels):  partials[slab][m][n] = sum_{rows of slab} pro(A[row][m]) * D[row][n], n < 256.
  * A is addressed in chunks of 64 channels: a + (m/64)*a_chunk_stride + row*a_row_stride + m%64

@@ -19,14 +19,16 @@ PYB_SRC = os.path.join(CSRC, "srwn_pybind.cpp")   # generated from _lib.SIGNATUR
 PYB_NAME = "_srwn_pyb"
 IO_SOURCES = ["srwn_tfrecord.cpp"]
 CXX = os.environ.get("CXX", "g++")
-SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip"]
+SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed", "-ffp-contract=on"]
 # Kernels that fetch REGISTER operands with loads the compiler does not see (inline asm, hand-counted waits) must not
 # spill: the compiler takes such a load's destination for written when the statement ends, so under register pressure
 # it may spill or move it while the data is still in flight -- garbage operands, or a wild address once the register has
 # been reused for a pointer (seen on a prototype: HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION).  The build refuses them.
-NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"]}
+# Kernels listed here are also held to zero scratch: the contrastive head (csrc/srwn_siamese.hip) keeps every value in
+# registers or LDS, and the build refuses an object in which it does not.
+NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"], "srwn_siamese.hip": ["contrastive_head_kernel"]}
 
 
 def _deps():
@@ -64,7 +66,8 @@ def _sha(paths, extra=""):
 
 
 def _check_no_spill(src, obj, remarks, kernels):
-    """Parses hipcc's kernel-resource-usage remarks: every kernel of `kernels` must report `VGPRs Spill: 0`."""
+    """Parses hipcc's kernel-resource-usage remarks: every kernel of `kernels` must report `VGPRs Spill: 0`,
+    `SGPRs Spill: 0` and `ScratchSize [bytes/lane]: 0`."""
     import re
     seen = {}
     name = None
@@ -72,15 +75,15 @@ def _check_no_spill(src, obj, remarks, kernels):
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             name = m.group(1)
-        m = re.search(r"VGPRs Spill: (\d+)", line)
+        m = re.search(r"(?:[VS]GPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
         if m and name:
-            seen[name] = int(m.group(1))
+            seen[name] = seen.get(name, 0) + int(m.group(1))
     for k in kernels:
         hit = [(n, v) for n, v in seen.items() if k in n]
         if not hit or any(v for _, v in hit):
             if os.path.exists(obj):
                 os.remove(obj)
-            raise RuntimeError("%s: kernel %s must not spill registers (untracked register loads): %s" % (src, k, hit or "not found"))
+            raise RuntimeError("%s: kernel %s must not spill registers or use scratch: %s" % (src, k, hit or "not found"))
 
 
 def _check_inflight(src, obj, flags, kernels):

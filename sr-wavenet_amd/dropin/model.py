@@ -12,3 +12,4 @@ WaveNet = _m.WaveNet
 WaveNetTeacher = _m.WaveNetTeacher
 WaveNetAutoEncoder = _m.WaveNetAutoEncoder
 ParallelWaveNet = _m.ParallelWaveNet
+SiameseWaveNet = _m.SiameseWaveNet

@@ -1,4 +1,4 @@
-"""``from simple_audio import generate_wave_batch`` shim (generator.py:10)."""
+"""``from simple_audio import generate_wave_batch`` / ``generate_random_wave`` shim (generator.py:10, siamese.py:9)."""
 import importlib as _il
 import os as _os
 import sys as _sys
@@ -9,4 +9,5 @@ if _root not in _sys.path:
 _m = _il.import_module("sr-wavenet_amd.simple_audio")
 generate_wave_batch = _m.generate_wave_batch
 generate_random_wave_f = _m.generate_random_wave_f
+generate_random_wave = _m.generate_random_wave
 Sine, Square, Sawtooth, Triangle, Normalize, CreateTicks = _m.Sine, _m.Square, _m.Sawtooth, _m.Triangle, _m.Normalize, _m.CreateTicks

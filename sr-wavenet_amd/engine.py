@@ -48,8 +48,12 @@ class StackConfig:
     #                                         loss SUMMED over batch and time
     #                                  "flow": no skip path, head relu -> 1x1 R->2 + affine transform: one flow of
     #                                         ParallelWaveNet (model.py:415-487), see student.FlowStack
+    #                                  "contrastive": class SiameseWaveNet's twin towers (model.py:660-797) as ONE
+    #                                         batch of B = 2P clips (left rows, then right): time-mean -> last 1x1 =
+    #                                         embedding [B, output_channels], contrastive loss over the P pairs
     dtype: torch.dtype = torch.bfloat16
     learning_rate: float = 1e-3
+    margin: float = 5.0           # contrastive head: the margin m of the loss (model.py:660, 747-749)
 
 
 class Section:
@@ -98,7 +102,7 @@ class WaveNetEngine:
             raise NotImplementedError("output_channels must be in [1, 256]")
         if cfg.head_mode == "mol" and (cfg.output_channels % 4 or not 4 <= cfg.output_channels <= 64):
             raise ValueError("mol head: output_channels = 4 * num_mixtures (<= 16 mixtures)")
-        if cfg.head_mode not in ("per_timestep", "pooled", "mol", "flow"):
+        if cfg.head_mode not in ("per_timestep", "pooled", "mol", "flow", "contrastive"):
             raise ValueError("head_mode %r" % cfg.head_mode)
         if cfg.cond_channels and (length % cfg.pool_stride):
             raise ValueError("length %d is not a multiple of pool_stride %d" % (length, cfg.pool_stride))
@@ -504,9 +508,14 @@ class WaveNetEngine:
         if self.mol:
             self.logits32 = z(N, Cp, dt=torch.float32)
         if self.pooled:
-            from . import _lib as _l
             self.labels = z(B, self.C, dt=torch.float32)
             self.probs = z(B, self.C, dt=torch.float32)
+        if self.contrastive:      # B = 2P rows: the left clips, then the right ones
+            self.labels = z(B // 2, dt=torch.float32)
+            self.emb = z(B, self.C, dt=torch.float32)
+            self.dist = z(B // 2, dt=torch.float32)
+        if self.clip_head:
+            from . import _lib as _l
             self.mean_r1 = z(B, S, dt=torch.float32)
             self.dmean = z(B, S, dt=torch.float32)
             self.tm_parts = z(B * int(_l.load().srwn_time_mean_slabs(T)) * S, dt=torch.float32)
@@ -529,7 +538,7 @@ class WaveNetEngine:
         self.wg_parts = z(self.nslabs * big, dt=torch.float32)
         self.wg_bparts = z(max(self.nslabs * max(L * S, Cp), 256 * 256), dt=torch.float32)
         # the two head products keep partials of their own, so that skip + head finish in ONE reduction launch
-        self.batch_reduce = self.use_w256 and not self.pooled and Cp == 256 and _os_environ_flag("SRWN_BATCH_REDUCE", True)
+        self.batch_reduce = self.use_w256 and not self.clip_head and Cp == 256 and _os_environ_flag("SRWN_BATCH_REDUCE", True)
         if self.batch_reduce:
             self.hd_parts = [z(self.ns_head * S * 256, dt=torch.float32) for _ in range(2)]
             self.hd_bparts = [z(self.ns_head * 256, dt=torch.float32) for _ in range(2)]
@@ -543,6 +552,10 @@ class WaveNetEngine:
         if targets is not None:
             if self.pooled:
                 self.labels.copy_(targets.reshape(self.B, self.C))
+            elif self.contrastive:
+                if self.B % 2:
+                    raise ValueError("contrastive head: labels need B = 2P rows (left clips, then right), got B=%d" % self.B)
+                self.labels.copy_(targets.reshape(self.B // 2))
             else:
                 self.targets.copy_(targets.reshape(self.N))
         if self.E:
@@ -592,7 +605,7 @@ class WaveNetEngine:
         with _Span(self, "head_1x1"):
             K.pw_linear(self.r0.data_ptr(), S, 0, S, S, self.wptr(self.o_w1), v("head_b1"), self.r1, S, S, N,
                         epi=K.EPI_RELU)                                               # model.py:53-54
-        if self.pooled:
+        if self.clip_head:
             return self._forward_pooled_head(with_loss)
         if self.mol:
             # last 1x1 in fp32 (the mixture parameters need it), then the mixture-of-logistics NLL on the
@@ -616,13 +629,22 @@ class WaveNetEngine:
 
     def _forward_pooled_head(self, with_labels: bool):
         """model.py:56-60: last 1x1, average pool over the clip, softmax -- computed as the 1x1 of the
-        time-mean (the pool commutes with it); leaves probs [B,C], loss, and dmean for backward."""
+        time-mean (the pool commutes with it); leaves probs [B,C], loss, and dmean for backward.
+        Contrastive head (model.py:708-750): the same pooled 1x1 is the embedding; leaves emb [B,C], dist [P] (B even),
+        loss and dmean.  Either head writes the head_w2 / head_b2 gradients itself when it has labels."""
         from ._lib import call
         st = torch.cuda.current_stream().cuda_stream
         B, T, S, C, Cp = self.B, self.T, self.S, self.C, self.Cp
         g = self.grads
         call("srwn_time_mean", self.r1.data_ptr(), self.tm_parts.data_ptr(), self.mean_r1.data_ptr(), B, T, S,
              K.abi_dtype(self.dt), st)
+        if self.contrastive:
+            call("srwn_contrastive_head", self.mean_r1.data_ptr(), self.view("head_w2").data_ptr(),
+                 self.view("head_b2").data_ptr(), self.labels.data_ptr() if with_labels else None, float(self.cfg.margin),
+                 self.emb.data_ptr(), None if B % 2 else self.dist.data_ptr(), self.loss.data_ptr(),
+                 self.view("head_w2", g).data_ptr(), self.view("head_b2", g).data_ptr(), self.dmean.data_ptr(), B, S,
+                 C, Cp, st)
+            return None
         call("srwn_pooled_head", self.mean_r1.data_ptr(), self.view("head_w2").data_ptr(),
              self.view("head_b2").data_ptr(), self.labels.data_ptr() if with_labels else None, self.probs.data_ptr(),
              self.loss.data_ptr(), self.view("head_w2", g).data_ptr(), self.view("head_b2", g).data_ptr(),
@@ -871,6 +893,16 @@ class WaveNetEngine:
         return min(los, key=lambda v: abs(v - 0.4 * self.L)) if los else 0
 
     @property
+    def contrastive(self) -> bool:
+        return self.cfg.head_mode == "contrastive"
+
+    @property
+    def clip_head(self) -> bool:
+        """One output row per clip (the pooled softmax or the contrastive embedding): the head runs on the time-mean of
+        r1, writes the last 1x1's gradients itself, and its backward broadcasts one row over time."""
+        return self.cfg.head_mode in ("pooled", "contrastive")
+
+    @property
     def bucket_off(self) -> int:
         return self.sections["WS"].offset
 
@@ -881,7 +913,7 @@ class WaveNetEngine:
         import os as _os
         forced = _os.environ.get("SRWN_FORCE_DIST") == "1"
         mode = _os.environ.get("SRWN_BUCKETS", "auto")   # "0" off, "1" on, "auto": on for RCCL only (gloo's
-        if mode == "0" or not ((self.world > 1 or forced) and self.use_wl and self.split_layer > 0 and not self.pooled):
+        if mode == "0" or not ((self.world > 1 or forced) and self.use_wl and self.split_layer > 0 and not self.clip_head):
             return False                                 # asynchronous CUDA all-reduce stalls for tens of ms)
         if mode == "1":
             return True
@@ -893,7 +925,7 @@ class WaveNetEngine:
         if self._head_bwd_done:     # da1, dtotal came out of the forward's head launch
             return
         with _Span(self, "bwd_head"):   # relu masks against the saved activations
-            if self.pooled:
+            if self.clip_head:
                 from ._lib import call
                 call("srwn_bcast_mask", self.dmean.data_ptr(), self.r1.data_ptr(), self.da1.data_ptr(), B, T, S,
                      1.0 / T, K.abi_dtype(self.dt), torch.cuda.current_stream().cuda_stream)
@@ -1015,12 +1047,12 @@ class WaveNetEngine:
                     ns, dt)                                                           # head 1x1 (S->S)
             K.reduce_partials(self.wg_parts, ns, S * S, 1, True, 1.0, gp + 4 * sec["head_w1"].offset, 0)
             K.reduce_partials(self.wg_bparts, ns, S, 1, True, 1.0, gp + 4 * sec["head_b1"].offset, 0)
-        if self.use_w256 and not self.pooled and Cp == 256:
+        if self.use_w256 and not self.clip_head and Cp == 256:
             K.wgrad256(self.r1.data_ptr(), 64, S, S // 64, self.dlogits, self.wg_parts, self.wg_bparts, N,
                        self.ns_head)                                                  # last 1x1 (S->C)
             K.reduce_partials(self.wg_parts, self.ns_head, S * Cp, 1, True, 1.0, gp + 4 * sec["head_w2"].offset, 0)
             K.reduce_partials(self.wg_bparts, self.ns_head, Cp, 1, True, 1.0, gp + 4 * sec["head_b2"].offset, 0)
-        elif not self.pooled:   # (the pooled head wrote its own kernel/bias gradients in forward)
+        elif not self.clip_head:   # (the pooled and contrastive heads wrote their own kernel/bias gradients in forward)
             K.wgrad(self.r1.data_ptr(), 0, S, self.dlogits.data_ptr(), 0, Cp, None, 1, self.wg_parts, self.wg_bparts,
                     N, T, ns, dt)                                                     # last 1x1 (S->C)
             K.reduce_partials(self.wg_parts, ns, S * Cp, 1, True, 1.0, gp + 4 * sec["head_w2"].offset, 0)
@@ -1105,7 +1137,7 @@ class WaveNetEngine:
         stack is conditioned): returns (audio, selected mixture, logits [B,nsteps,4M])."""
         import ctypes as C
         from . import _lib
-        if self.o_gen is None or self.pooled:
+        if self.o_gen is None or self.clip_head:
             raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
         B = int(batch or self.B)
         self._repack_generation()      # (the generation-only images follow the parameters lazily: not part of a training step)

@@ -11,6 +11,8 @@ wrappers, but no TensorFlow: the graph body is the fixed kernel sequence of ``en
                             (encoder.AutoEncoderEngine), the teacher teacher.py trains.
 * ``ParallelWaveNet``    -- model.py:290-656: the IAF student distilled against that frozen teacher
                             (student.StudentEngine).
+* ``SiameseWaveNet``     -- model.py:660-797: two weight-sharing WaveNet towers trained on pairs with the contrastive
+                            loss (engine head_mode "contrastive": both towers run as one batch).
 """
 from __future__ import annotations
 
@@ -661,3 +663,78 @@ class ParallelWaveNet(object):
     def reconstruct(self, sess, inputs, conditions=None):
         """The teacher's own reconstruction (``teacher_out``, model.py:651-656)."""
         return self._ae_teacher(inputs).reconstruct(inputs, conditions)
+
+
+class SiameseWaveNet(_EngineOwner):
+    """model.py:660-797: two towers of class ``WaveNet``'s network (input conv, residual stack, skip sum, relu -> 1x1
+    -> relu -> 1x1, average pool over the whole clip) that share one set of weights, trained on pairs with the
+    Hadsell-Chopra-LeCun contrastive loss under the reference's label convention (y = 1: "same", model.py:747-749).
+
+    The towers share their weights, so a pair batch runs as ONE engine batch of 2P clips (the left clips, then the
+    right ones) and the weight gradients come out summed over both towers.  The ``sess`` argument of every method is
+    accepted for call compatibility with siamese.py and ignored (there is no session).
+    ``train(sess, left[P,T], right[P,T], labels[P]) -> (loss, distance[P])``; ``get_embedding -> [B,1,D]``;
+    ``get_distance -> [P]``.  Checkpoint names are those of the left tower, ``{name}/siamese/...`` (model.py:689)."""
+
+    def __init__(self, input_size, output_dimensions, dilations, margin=5.0, filter_width=2, dilation_channels=32,
+                 skip_channels=256, name="SiameseWaveNet", learning_rate=0.001, dtype=None, seed=0):
+        self.input_size = input_size
+        self.output_dimensions = output_dimensions
+        self.dilations = dilations
+        self.margin = margin
+        self.filter_width = filter_width
+        self.dilation_channels = dilation_channels
+        self.skip_channels = skip_channels
+        self._scope, self._decoder_names, self._default_length = name + "/siamese", False, int(input_size)
+        self._setup(StackConfig(dilations=list(dilations), filter_width=filter_width,
+                                dilation_channels=dilation_channels, skip_channels=skip_channels,
+                                output_channels=output_dimensions, shift_input=False, head_mode="contrastive",
+                                margin=float(margin), dtype=dtype or _default_dtype(), learning_rate=learning_rate),
+                    seed)
+
+    def _clips(self, inputs, what="inputs"):
+        x = np.asarray(inputs, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("%s must be [batch, samples]" % what)
+        if x.shape[1] != self.input_size:
+            # tf.nn.pool window = input_size, VALID, then squeezed (model.py:710, 731): other lengths do not embed
+            raise ValueError("%s have %d samples, the model was built for input_size=%d" % (what, x.shape[1], self.input_size))
+        return x
+
+    def _pair(self, inputs_left, inputs_right):
+        left, right = self._clips(inputs_left, "inputs_left"), self._clips(inputs_right, "inputs_right")
+        if left.shape[0] != right.shape[0]:
+            raise ValueError("inputs_left and inputs_right must hold the same number of clips (%d vs %d)"
+                             % (left.shape[0], right.shape[0]))
+        return np.concatenate([left, right], axis=0)
+
+    def _stage(self, x, labels=None):
+        eng = self._engine(x.shape[0], x.shape[1])
+        eng.set_inputs(torch.as_tensor(x, device="cuda"),
+                       None if labels is None else torch.as_tensor(labels, device="cuda"))
+        return eng
+
+    def load(self, sess, logdir):
+        return super().load(logdir)
+
+    def save(self, sess, logdir, global_step, force=False, fmt=None):
+        return super().save(logdir, global_step, force, fmt)
+
+    def train(self, sess, inputs_left, inputs_right, labels):
+        x = self._pair(inputs_left, inputs_right)
+        y = np.asarray(labels, dtype=np.float32).reshape(-1)
+        if y.shape[0] != x.shape[0] // 2:
+            raise ValueError("labels must hold one value per pair (%d), got %d" % (x.shape[0] // 2, y.shape[0]))
+        eng = self._stage(x, y)
+        _train_step(eng)
+        return np.float32(eng.loss.item()), eng.dist.cpu().numpy()
+
+    def get_embedding(self, sess, inputs):
+        eng = self._stage(self._clips(inputs))
+        eng.forward(with_loss=False)
+        return eng.emb.cpu().numpy()[:, None, :]
+
+    def get_distance(self, sess, inputs_left, inputs_right):
+        eng = self._stage(self._pair(inputs_left, inputs_right))
+        eng.forward(with_loss=False)
+        return eng.dist.cpu().numpy()

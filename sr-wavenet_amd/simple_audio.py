@@ -6,6 +6,9 @@
   generate_wave_batch(batch_size, length, combos=False) -> (x [B, length], y [B, 10])
       per clip: a frequency f in 22..39, one of the four shapes at `length` samples per second for one second,
       N(0, 0.05) noise, normalised to [-1, 1]; label = one-hot of int(f/2 - 1) - 10   (simple_audio.py:40-61)
+  generate_random_wave(length, combos=False) -> (x [length], y [4])                     (siamese.py:9, 56-57)
+      20 periods over the clip (one second at `length` samples per second) of one of the four shapes -- with combos
+      the sum of 1..4 distinct ones --, N(0, 0.1) noise, normalised to [-1, 1]; y = multi-hot of the shapes used
 """
 from __future__ import annotations
 
@@ -46,6 +49,18 @@ def Normalize(t, min_val=0, max_val=1):
 
 
 _FUNCS = (Sine, Square, Sawtooth, Triangle)
+
+
+def generate_random_wave(length, combos=False, rng=None):
+    rng = np.random if rng is None else rng
+    count = int(rng.randint(1, len(_FUNCS) + 1)) if combos else 1
+    labels = np.zeros(len(_FUNCS))
+    wave = 0.0
+    for i in rng.choice(len(_FUNCS), count, replace=False):
+        wave = wave + _FUNCS[int(i)](frequency=20, duration=1, sample_rate=length)
+        labels[int(i)] = 1
+    wave = wave + rng.normal(0, 0.1, wave.shape)
+    return Normalize(wave, min_val=-1, max_val=1), labels
 
 
 def generate_random_wave_f(length, combos=False, rng=None):
