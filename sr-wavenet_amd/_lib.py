@@ -87,6 +87,10 @@ SIGNATURES = {
     "srwn_pooled_head": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
     "srwn_bcast_mask": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _f32, _i32, _p]),
     "srwn_contrastive_head": (C.c_int, [_p, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p]),
+    "srwn_wavenet_layer_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32,
+                                         _i32, _i32, _i32, _p]),
+    "srwn_wavenet_layer_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32,
+                                         _i32, _i32, _i32, _p]),
     "srwn_skip_dgrad_all": (C.c_int, [_p, _p, _p, _i64, _i32, _i64, _i32, _i32, _i32, _p]),
     "srwn_wgrad_layers": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i64,
                                     _i32, _i32, _i32, _i32, _i32, _p]),

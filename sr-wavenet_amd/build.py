@@ -19,16 +19,18 @@ PYB_SRC = os.path.join(CSRC, "srwn_pybind.cpp")   # generated from _lib.SIGNATUR
 PYB_NAME = "_srwn_pyb"
 IO_SOURCES = ["srwn_tfrecord.cpp"]
 CXX = os.environ.get("CXX", "g++")
-SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip"]
+SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip", "srwn_wngate.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed", "-ffp-contract=on"]
 # Kernels that fetch REGISTER operands with loads the compiler does not see (inline asm, hand-counted waits) must not
 # spill: the compiler takes such a load's destination for written when the statement ends, so under register pressure
 # it may spill or move it while the data is still in flight -- garbage operands, or a wild address once the register has
 # been reused for a pointer (seen on a prototype: HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION).  The build refuses them.
-# Kernels listed here are also held to zero scratch: the contrastive head (csrc/srwn_siamese.hip) keeps every value in
-# registers or LDS, and the build refuses an object in which it does not.
-NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"], "srwn_siamese.hip": ["contrastive_head_kernel"]}
+# Kernels listed here are also held to zero scratch: the contrastive head (csrc/srwn_siamese.hip) and the canonical-gate
+# layer kernels (csrc/srwn_wngate.hip) keep every value in registers or LDS, and the build refuses an object in which they
+# do not.
+NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"], "srwn_siamese.hip": ["contrastive_head_kernel"],
+            "srwn_wngate.hip": ["wavenet_layer_fwd_kernel", "wavenet_layer_bwd_kernel"]}
 
 
 def _deps():

@@ -54,6 +54,9 @@ class StackConfig:
     dtype: torch.dtype = torch.bfloat16
     learning_rate: float = 1e-3
     margin: float = 5.0           # contrastive head: the margin m of the loss (model.py:660, 747-749)
+    gate_mode: str = "reference"  # "reference": c = z*sigmoid(z), the graph the reference runs (ops.py:33 discards the gate
+    #                               conv); "wavenet": the canonical c = tanh(Wf*x + bf) * sigmoid(Wg*x + bg), trained with
+    #                               one launch per layer (csrc/srwn_wngate.hip); the `_gate` variables are then trained too
 
 
 class Section:
@@ -92,6 +95,10 @@ class _Span:
 class WaveNetEngine:
     def __init__(self, cfg: StackConfig, batch: int, length: int, device="cuda", seed: int = 0,
                  process_group=None, share_from: Optional["WaveNetEngine"] = None, frozen: bool = False):
+        if cfg.gate_mode not in ("reference", "wavenet"):
+            raise ValueError("gate_mode %r: 'reference' or 'wavenet'" % (cfg.gate_mode,))
+        if cfg.gate_mode == "wavenet" and cfg.head_mode == "flow":
+            raise NotImplementedError("gate_mode 'wavenet' is not built for the flows of ParallelWaveNet")
         if cfg.filter_width != 2:
             raise NotImplementedError("filter_width %d: only 2 is built (reference default, model.py:9)" % cfg.filter_width)
         if cfg.dilation_channels not in (32, 64):
@@ -107,14 +114,17 @@ class WaveNetEngine:
         if cfg.cond_channels and (length % cfg.pool_stride):
             raise ValueError("length %d is not a multiple of pool_stride %d" % (length, cfg.pool_stride))
         self.cfg = cfg
+        # canonical gate: always the per-layer path (the group kernels, their weight-gradient tiles and the layer
+        # weight-gradient kernel srwn_wgrad_layers all build c = z*sigmoid(z))
+        self.wavenet = cfg.gate_mode == "wavenet"
         self.timing = False           # HIP-event spans with every launch alone on the chip (no side stream)
         self.timing_overlap = False   # the same spans inside the real schedule (side-stream work left running)
         self.spans: Dict[str, list] = {}
         import os as _os
         # multi-layer kernels (csrc/srwn_group.hip): SRWN_FUSE=0 keeps one launch per layer (the parity twin)
         fuse = _os.environ.get("SRWN_FUSE", "1")
-        self.fuse_fwd = fuse not in ("0", "bwd")
-        self.fuse_bwd = fuse not in ("0", "fwd")
+        self.fuse_fwd = fuse not in ("0", "bwd") and not self.wavenet
+        self.fuse_bwd = fuse not in ("0", "fwd") and not self.wavenet
         # SRWN_FUSE_WT=1 (default): layer weight gradients inside the 8-wave backward group kernel, split by output over
         # the waves; the forward group kernel writes the transposed operands ("weight-gradient tiles") they need
         # (csrc/srwn_group.hip, _wt entry points).  0: chain kernel + separate weight-gradient pass (the parity twin)
@@ -200,6 +210,8 @@ class WaveNetEngine:
 
         add("init_w", (Kw, 1, R)); add("init_b", (R,))
         add("WF", (L, Kw, R, R)); add("BF", (L, R))
+        if self.wavenet:      # (before WS: the gate's gradients join the second all-reduce bucket with the other layer ones)
+            add("WG", (L, Kw, R, R)); add("BG", (L, R))
         add("WR", (L, R, R)); add("BR", (L, R))
         if E:
             add("WC", (L, E, R)); add("BC", (L, R))
@@ -218,8 +230,10 @@ class WaveNetEngine:
         self.bs_sum = torch.zeros(S, dtype=torch.float32, device=self.dev)      # sum_l BS[l] (kept current by repack())
         # the dead gate conv variables of ops.py:31-33 exist in reference checkpoints; they take no
         # part in the graph (TF reports None gradients) so they live outside the trained buffer.
-        self.dead_gate = {"WG": torch.zeros((L, Kw, R, R), dtype=torch.float32, device=self.dev),
-                          "BG": torch.zeros((L, R), dtype=torch.float32, device=self.dev)}
+        # (gate_mode "wavenet": they are the trained sections WG / BG)
+        self.dead_gate = None if self.wavenet else {
+            "WG": torch.zeros((L, Kw, R, R), dtype=torch.float32, device=self.dev),
+            "BG": torch.zeros((L, R), dtype=torch.float32, device=self.dev)}
         self.init_parameters(seed)
 
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -252,8 +266,12 @@ class WaveNetEngine:
         w2 = torch.zeros((S, self.Cp))
         w2[:, :C] = xav((S, C), S, C)
         put("head_w2", w2)
+        wg = xav((L, Kw, R, R), Kw * R, Kw * R)      # (last in the RNG stream: every other draw is the same in both modes)
+        if self.wavenet:
+            put("WG", wg)
         self.params.copy_(host)
-        self.dead_gate["WG"].copy_(xav((L, Kw, R, R), Kw * R, Kw * R))
+        if not self.wavenet:
+            self.dead_gate["WG"].copy_(wg)
         self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
 
     def load_oracle_params(self, sp):
@@ -266,6 +284,8 @@ class WaveNetEngine:
 
         put("init_w", sp.init_w); put("init_b", sp.init_b)
         put("WF", np.stack([l.wf for l in sp.layers])); put("BF", np.stack([l.bf for l in sp.layers]))
+        if self.wavenet:
+            put("WG", np.stack([l.wg for l in sp.layers])); put("BG", np.stack([l.bg for l in sp.layers]))
         put("WR", np.stack([l.wr for l in sp.layers])); put("BR", np.stack([l.br for l in sp.layers]))
         put("WS", np.stack([l.ws for l in sp.layers])); put("BS", np.stack([l.bs for l in sp.layers]))
         if self.E:
@@ -283,6 +303,8 @@ class WaveNetEngine:
         out = {"init_w": self.view("init_w", buf), "init_b": self.view("init_b", buf)}
         for i in range(self.L):
             out[f"l{i}.wf"] = self.view("WF", buf)[i]; out[f"l{i}.bf"] = self.view("BF", buf)[i]
+            if self.wavenet:
+                out[f"l{i}.wg"] = self.view("WG", buf)[i]; out[f"l{i}.bg"] = self.view("BG", buf)[i]
             out[f"l{i}.wr"] = self.view("WR", buf)[i]; out[f"l{i}.br"] = self.view("BR", buf)[i]
             out[f"l{i}.ws"] = self.view("WS", buf)[i]; out[f"l{i}.bs"] = self.view("BS", buf)[i]
             if self.E:
@@ -304,8 +326,9 @@ class WaveNetEngine:
             nm = f"dilated_conv_{i}"
             out[f"{scope}/{nm}_filter/{nm}_Kernel"] = n[f"l{i}.wf"]
             out[f"{scope}/{nm}_filter/{nm}_Bias"] = n[f"l{i}.bf"].view(1, 1, -1)
-            out[f"{scope}/{nm}_gate/{nm}_Kernel"] = self.dead_gate["WG"][i]
-            out[f"{scope}/{nm}_gate/{nm}_Bias"] = self.dead_gate["BG"][i].view(1, 1, -1)
+            gate = self.dead_gate if not self.wavenet else {"WG": self.view("WG"), "BG": self.view("BG")}
+            out[f"{scope}/{nm}_gate/{nm}_Kernel"] = gate["WG"][i]
+            out[f"{scope}/{nm}_gate/{nm}_Bias"] = gate["BG"][i].view(1, 1, -1)
             j = per * i
             if decoder:
                 out[f"{scope}/{cname(j)}/kernel"] = n[f"l{i}.wc"].unsqueeze(0)
@@ -344,8 +367,14 @@ class WaveNetEngine:
         self.o_conv, self.o_res, self.o_convT, self.o_resT = [], [], [], []
         for l in range(L):
             self.o_conv.append(P.pack_conv(pk, sec["WF"].offset + l * Kw * R * R, Kw, R))
+            if self.wavenet:      # [Wf | Wg]: the gate conv's image right behind the filter's (one 2R-row product)
+                o = P.pack_conv(pk, sec["WG"].offset + l * Kw * R * R, Kw, R)
+                assert o == self.o_conv[l] + Kw * R * R
             self.o_res.append(P.pack_res(pk, sec["WR"].offset + l * R * R, R))
             self.o_convT.append(P.pack_conv_T(pk, sec["WF"].offset + l * Kw * R * R, Kw, R))
+            if self.wavenet:      # [WfT | WgT] likewise (the data gradient contracts over both halves of D)
+                o = P.pack_conv_T(pk, sec["WG"].offset + l * Kw * R * R, Kw, R)
+                assert o == self.o_convT[l] + Kw * R * R
             self.o_resT.append(P.pack_linear_T(pk, sec["WR"].offset + l * R * R, R, R, R, perm=True))
         if E:
             # conditioning 1x1 of every layer as one [Ep] -> [L*R] product (model.py:180)
@@ -434,10 +463,16 @@ class WaveNetEngine:
         self.audio = z(B, T, dt=torch.float32)
         self.xs = z(L + 1, B, T, R)
         self.zs = z(L, B, T, R)
-        self.dfs = z(L, B, T, R)
+        self.dfs = z(L, B, T, 2 * R if self.wavenet else R)   # (wavenet: D = [d f | d g] of both convs)
+        if self.wavenet:
+            self.ss = z(L, B, T, R)      # sigmoid(Wg*x + bg)
+            self.cs = z(L, B, T, R)      # c = z*s: the skip sum and the 1x1 weight gradients read it as it is
+            # both convs' weight / bias gradients as srwn_wgrad leaves them ([in, 2R] per tap), split into WF|WG, BF|BG
+            self.wn_wgrad = z(L, self.Kw, R, 2 * R, dt=torch.float32)
+            self.wn_bgrad = z(L, 2 * R, dt=torch.float32)
         self.gs = z(L + 1, B, T, R)   # gs[L] is never written by the teacher: its last dense output is unused
         self.nslabs = K.wgrad_slabs(N)
-        self.use_wl = (R in (32, 64) and self.Kw == 2)
+        self.use_wl = (R in (32, 64) and self.Kw == 2) and not self.wavenet
         self.use_dcs = (R, self.S) in ((64, 256), (32, 128))
         import os as _os
         # decided ONCE, before anything is sized (the tiles, the partial slabs and the skip weight-gradient path follow it)
@@ -536,7 +571,7 @@ class WaveNetEngine:
             else:
                 big = max(big, -(-self.ns_skip_wt * L * R * S // self.nslabs))
         self.wg_parts = z(self.nslabs * big, dt=torch.float32)
-        self.wg_bparts = z(max(self.nslabs * max(L * S, Cp), 256 * 256), dt=torch.float32)
+        self.wg_bparts = z(max(self.nslabs * max(L * S, Cp, 2 * L * R if self.wavenet else 0), 256 * 256), dt=torch.float32)
         # the two head products keep partials of their own, so that skip + head finish in ONE reduction launch
         self.batch_reduce = self.use_w256 and not self.clip_head and Cp == 256 and _os_environ_flag("SRWN_BATCH_REDUCE", True)
         if self.batch_reduce:
@@ -587,8 +622,8 @@ class WaveNetEngine:
         with _Span(self, "fwd_layers"):
             self._stack_fwd(self.cond_all if self.E else None, wt=self._tiles_valid)
         with _Span(self, "skip_sum"):      # model.py:50-51 (bs_sum = the sum of the layers' skip biases: formed by repack())
-            K.pw_linear(self.zs.data_ptr(), R, N * R, R, L * R, self.wptr(self.o_skip), self.bs_sum, self.r0, S, S,
-                        N, pro=K.PRO_GATE, epi=K.EPI_RELU)
+            K.pw_linear(self._gate_out.data_ptr(), R, N * R, R, L * R, self.wptr(self.o_skip), self.bs_sum, self.r0, S, S,
+                        N, pro=self._gate_pro, epi=K.EPI_RELU)
         self._head_bwd_done = False
         if self.head_chain and self.o_w2p is not None and not want_logits and with_loss:
             # model.py:53-56 + softmax CE + the two head data gradients: rows never leave the registers in between
@@ -714,6 +749,11 @@ class WaveNetEngine:
         v = self.view
         nxt = cond_all is not None and l + 1 < self.L      # the NEXT layer's conditioning bias goes onto the output
         cond3 = cond_all[l + 1].view(self.B, self.frames, self.R) if nxt else None
+        if self.wavenet:
+            K.wavenet_layer_fwd(self.xs[l], cond3, self.wptr(self.o_conv[l]), self.wptr(self.o_res[l]), v("BF")[l],
+                                v("BG")[l], v("BR")[l], self.xs[l + 1], self.zs[l], self.ss[l], self.cs[l], self.Kw,
+                                self.dil[l], self.cfg.pool_stride)
+            return
         K.residual_layer_fwd(self.xs[l], cond3, self.wptr(self.o_conv[l]), self.wptr(self.o_res[l]), v("BF")[l],
                              v("BR")[l], self.xs[l + 1], self.zs[l], self.Kw, self.dil[l], self.cfg.pool_stride)
 
@@ -793,14 +833,17 @@ class WaveNetEngine:
         for l in range(l_hi, l_lo - 1, -1):
             has_up = l < L - 1
             g_in = self.gs[l + 2] if (has_up and l + 2 < L) else None
-            K.residual_layer_bwd(g_in, self.dfs[l + 1] if has_up else None,
-                                 self.wptr(self.o_convT[l + 1]) if has_up else None,
-                                 self.gs[l + 1] if has_up else None,
-                                 self.wptr(self.o_resT[l]) if has_up else None,
-                                 None if self.use_dcs else self.wptr(self.o_skipT[l]),
-                                 None if self.use_dcs else self.dtotal, self.zs[l], self.dfs[l], B, T, R, S, Kw,
-                                 self.dil[l + 1] if has_up else 1, has_up, True, dt,
-                                 dcs=self.dcs[l] if self.use_dcs else None)
+            if self.wavenet:
+                self._wavenet_layer_bwd(l, g_in, has_up)
+            else:
+                K.residual_layer_bwd(g_in, self.dfs[l + 1] if has_up else None,
+                                     self.wptr(self.o_convT[l + 1]) if has_up else None,
+                                     self.gs[l + 1] if has_up else None,
+                                     self.wptr(self.o_resT[l]) if has_up else None,
+                                     None if self.use_dcs else self.wptr(self.o_skipT[l]),
+                                     None if self.use_dcs else self.dtotal, self.zs[l], self.dfs[l], B, T, R, S, Kw,
+                                     self.dil[l + 1] if has_up else 1, has_up, True, dt,
+                                     dcs=self.dcs[l] if self.use_dcs else None)
             if l in group_lo and not self.timing:   # df_l.. and G_{l+1}.. of this group are complete
                 if overlap:
                     ev = torch.cuda.Event()
@@ -813,14 +856,18 @@ class WaveNetEngine:
             if overlap:
                 main.wait_stream(side)   # skip/head gradients (and the layer groups launched so far) are in
             return
-        K.residual_layer_bwd(self.gs[1] if L > 1 else None, self.dfs[0], self.wptr(self.o_convT[0]), self.gs[0],
-                             None, None, None, None, None, B, T, R, S, Kw, self.dil[0], True, False, dt)
+        if self.wavenet:
+            K.wavenet_layer_bwd(self.gs[1] if L > 1 else None, self.dfs[0], self.wptr(self.o_convT[0]), self.gs[0],
+                                None, None, None, None, None, None, None, B, T, R, S, Kw, self.dil[0], True, False, dt)
+        else:
+            K.residual_layer_bwd(self.gs[1] if L > 1 else None, self.dfs[0], self.wptr(self.o_convT[0]), self.gs[0],
+                                 None, None, None, None, None, B, T, R, S, Kw, self.dil[0], True, False, dt)
         span.__exit__()
         if self.timing:   # (timed runs keep the dgrad chain's span free of the weight-gradient passes)
             for g in groups:
                 self._wgrad_layers_group(*g)
         merged = self.use_wl      # (as in the grouped path: the same sums in the same order)
-        if merged and overlap:
+        if overlap:       # (the canonical gate's conv weight gradients read every D_l of the chain: no group events)
             side.wait_stream(main)
         with torch.cuda.stream(side):
             if merged:
@@ -829,6 +876,25 @@ class WaveNetEngine:
         self._wgrad_input_and_cond(input_conv=not merged)
         if overlap and join:
             main.wait_stream(side)
+
+    def _wavenet_layer_bwd(self, l: int, g_in: Optional[torch.Tensor], has_up: bool):
+        """Canonical gate: G_{l+1} from D_{l+1} (has_up) and D_l = [d f | d g] of layer l (csrc/srwn_wngate.hip)."""
+        B, T, R, S = self.B, self.T, self.R, self.S
+        K.wavenet_layer_bwd(g_in, self.dfs[l + 1] if has_up else None,
+                            self.wptr(self.o_convT[l + 1]) if has_up else None, self.gs[l + 1] if has_up else None,
+                            self.wptr(self.o_resT[l]) if has_up else None,
+                            None if self.use_dcs else self.wptr(self.o_skipT[l]), None if self.use_dcs else self.dtotal,
+                            self.dcs[l] if self.use_dcs else None, self.zs[l], self.ss[l], self.dfs[l], B, T, R, S,
+                            self.Kw, self.dil[l + 1] if has_up else 1, has_up, True, self.dt)
+
+    @property
+    def _gate_out(self) -> torch.Tensor:
+        """What the skip sum and the 1x1 weight gradients read: z (c rebuilt as z*sigmoid(z) on load), or c (wavenet)."""
+        return self.cs if self.wavenet else self.zs
+
+    @property
+    def _gate_pro(self) -> int:
+        return K.PRO_NONE if self.wavenet else K.PRO_GATE
 
     def join_side(self):
         if self.side is not None and self.overlap and not self.timing:
@@ -952,7 +1018,7 @@ class WaveNetEngine:
         gp, sec, ns, dt = self.grads.data_ptr(), self.sections, self.nslabs, self.dt
         es = self.xs.element_size()
         NR = N * R
-        xs_p, zs_p, dfs_p, gs_p = self.xs.data_ptr(), self.zs.data_ptr(), self.dfs.data_ptr(), self.gs.data_ptr()
+        xs_p, dfs_p, gs_p = self.xs.data_ptr(), self.dfs.data_ptr(), self.gs.data_ptr()
         if self.use_wl:
             blk = (R,) if self.part16 else ()      # (bf16 partial blocks in lane order: SRWN_PARTIALS_BLK16, R columns)
             jobs = [(self.pl_f, ns, Kw * R * R, L, True, 1.0, gp + 4 * sec["WF"].offset, Kw * R * R) + blk,
@@ -964,26 +1030,46 @@ class WaveNetEngine:
                 self._ic_job = None
             K.reduce_partials_multi(jobs)
             return
-        for k in range(Kw):                                                          # dilated conv taps (legacy)
-            shifts = [(Kw - 1 - k) * d for d in self.dil]
-            last = k == Kw - 1
-            K.wgrad(xs_p, NR, R, dfs_p, NR, R, shifts, L, self.wg_parts, self.wg_bparts if last else None, N, T, ns,
-                    dt)                                  # (xs holds the conditioned conv inputs, model.py:183)
-            K.reduce_partials(self.wg_parts, ns, R * R, L, True, 1.0, gp + 4 * (sec["WF"].offset + k * R * R),
-                              Kw * R * R)
-            if last:
-                K.reduce_partials(self.wg_bparts, ns, R, L, True, 1.0, gp + 4 * sec["BF"].offset, R)
-        K.wgrad(zs_p, NR, R, gs_p + NR * es, NR, R, None, L, self.wg_parts, self.wg_bparts, N, T, ns, dt,
-                pro=K.PRO_GATE)                                                       # 1x1 residual
+        if self.wavenet:
+            self._wgrad_wavenet_convs()
+        else:
+            for k in range(Kw):                              # dilated conv taps (legacy)
+                shifts = [(Kw - 1 - k) * d for d in self.dil]
+                last = k == Kw - 1
+                K.wgrad(xs_p, NR, R, dfs_p, NR, R, shifts, L, self.wg_parts, self.wg_bparts if last else None, N, T, ns,
+                        dt)                                  # (xs holds the conditioned conv inputs, model.py:183)
+                K.reduce_partials(self.wg_parts, ns, R * R, L, True, 1.0, gp + 4 * (sec["WF"].offset + k * R * R),
+                                  Kw * R * R)
+                if last:
+                    K.reduce_partials(self.wg_bparts, ns, R, L, True, 1.0, gp + 4 * sec["BF"].offset, R)
+        K.wgrad(self._gate_out.data_ptr(), NR, R, gs_p + NR * es, NR, R, None, L, self.wg_parts, self.wg_bparts, N, T,
+                ns, dt, pro=self._gate_pro)                                           # 1x1 residual
         K.reduce_partials(self.wg_parts, ns, R * R, L, True, SQRT_HALF, gp + 4 * sec["WR"].offset, R * R)
         K.reduce_partials(self.wg_bparts, ns, R, L, True, SQRT_HALF, gp + 4 * sec["BR"].offset, R)
+
+    def _wgrad_wavenet_convs(self):
+        """Both dilated convs of every layer (canonical gate): per tap one srwn_wgrad over (x_l, D_l) with cin = R,
+        cout = 2R, reduced into [L, K, R, 2R] / [L, 2R] and split into the WF | WG and BF | BG sections."""
+        L, R, Kw, N, T, ns = self.L, self.R, self.Kw, self.N, self.T, self.nslabs
+        NR = N * R
+        for k in range(Kw):
+            last = k == Kw - 1
+            K.wgrad(self.xs.data_ptr(), NR, R, self.dfs.data_ptr(), 2 * NR, 2 * R, [(Kw - 1 - k) * d for d in self.dil], L,
+                    self.wg_parts, self.wg_bparts if last else None, N, T, ns, self.dt)
+            K.reduce_partials(self.wg_parts, ns, R * 2 * R, L, True, 1.0,
+                              self.wn_wgrad.data_ptr() + 4 * k * R * 2 * R, Kw * R * 2 * R)
+            if last:
+                K.reduce_partials(self.wg_bparts, ns, 2 * R, L, True, 1.0, self.wn_bgrad.data_ptr(), 2 * R)
+        g = self.grads
+        self.view("WF", g).copy_(self.wn_wgrad[..., :R]); self.view("WG", g).copy_(self.wn_wgrad[..., R:])
+        self.view("BF", g).copy_(self.wn_bgrad[:, :R]); self.view("BG", g).copy_(self.wn_bgrad[:, R:])
 
     def _wgrad_skip_and_head(self):
         """Gradients of the skip 1x1s and the two head 1x1s: need only z, r0, r1, da1, dtotal, dlogits."""
         N, T, L, R, S, Cp = self.N, self.T, self.L, self.R, self.S, self.Cp
         gp, sec, ns, dt = self.grads.data_ptr(), self.sections, self.nslabs, self.dt
         NR = N * R
-        zs_p = self.zs.data_ptr()
+        zs_p = self._gate_out.data_ptr()      # (z, gated on load, or the canonical gate's c)
         if self.batch_reduce:
             ns_skip = self.ns_skip
             with _Span(self, "wgrad_skip"):
@@ -994,7 +1080,7 @@ class WaveNetEngine:
                                     self.wg_bparts, ns_skip, self.B, T, R)
                 else:
                     K.wgrad256(zs_p, NR, R, L, self.dtotal, self.wg_parts, self.wg_bparts, N, self.ns_skip,
-                               pro=K.PRO_GATE, chunk_width=R)
+                               pro=self._gate_pro, chunk_width=R)
             if S == Cp:   # both head 1x1s (S->S, S->C) as one launch
                 K.wgrad256_pair(self.r0.data_ptr(), self.da1, self.hd_parts[0], self.hd_bparts[0],
                                 self.r1.data_ptr(), self.dlogits, self.hd_parts[1], self.hd_bparts[1], 64, S, S // 64, N,
@@ -1028,7 +1114,7 @@ class WaveNetEngine:
                                     self.wg_bparts, ns_skip, self.B, T, R)
                 else:
                     K.wgrad256(zs_p, NR, R, L, self.dtotal, self.wg_parts, self.wg_bparts, N, self.ns_skip,
-                               pro=K.PRO_GATE, chunk_width=R)
+                               pro=self._gate_pro, chunk_width=R)
             if self.skip_wt and self.fused_wt and self.skip_parts16 is not None:
                 K.reduce_partials_multi([(self.skip_parts16, ns_skip, L * R * S, 1, True, 1.0, gp + 4 * sec["WS"].offset, 0, S)])
             else:
@@ -1040,7 +1126,7 @@ class WaveNetEngine:
         else:
             with _Span(self, "wgrad_skip"):
                 K.wgrad(zs_p, NR, R, self.dtotal.data_ptr(), 0, S, None, L, self.wg_parts, self.wg_bparts, N, T, ns,
-                        dt, pro=K.PRO_GATE)                                           # 1x1 skip
+                        dt, pro=self._gate_pro)                                       # 1x1 skip
             K.reduce_partials(self.wg_parts, ns, R * S, L, True, 1.0, gp + 4 * sec["WS"].offset, R * S)
             K.reduce_partials(self.wg_bparts, ns, S, L, True, 1.0, gp + 4 * sec["BS"].offset, S)
             K.wgrad(self.r0.data_ptr(), 0, S, self.da1.data_ptr(), 0, S, None, 1, self.wg_parts, self.wg_bparts, N, T,
@@ -1137,6 +1223,9 @@ class WaveNetEngine:
         stack is conditioned): returns (audio, selected mixture, logits [B,nsteps,4M])."""
         import ctypes as C
         from . import _lib
+        if self.wavenet:
+            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
+                                      "the reference gate (canonical generation is not built)")
         if self.o_gen is None or self.clip_head:
             raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
         B = int(batch or self.B)

@@ -520,6 +520,43 @@ def residual_layer_bwd(g_in: Optional[torch.Tensor], df_up: Optional[torch.Tenso
          int(dilation_up), int(has_up), int(has_down), abi_dtype(dtype), _stream())
 
 
+def wavenet_layer_fwd(x: torch.Tensor, cond: Optional[torch.Tensor], wconv_ptr: int, wres_ptr: int, bias_f: torch.Tensor,
+                      bias_g: torch.Tensor, bias_r: torch.Tensor, h_out: torch.Tensor, z_out: torch.Tensor,
+                      s_out: torch.Tensor, c_out: torch.Tensor, K: int, dilation: int, pool_stride: int = 1):
+    """Canonical-gate residual layer (csrc/srwn_wngate.hip): x [B,T,R] -> h_out, z_out, s_out, c_out (all [B,T,R]).
+    wconv_ptr: the [Wf | Wg] image (pack_conv of Wf, then of Wg); cond: the NEXT layer's frame bias [B, frames, >=R]."""
+    B, T, R = x.shape
+    px = _chk(x, "x")
+    frames, cstride, pc = 1, R, None
+    if cond is not None:
+        _chk(cond, "cond", x.dtype)
+        if cond.dim() != 3 or cond.shape[0] != B or cond.shape[2] < R:
+            raise ValueError("cond: shape %s for B=%d R=%d" % (tuple(cond.shape), B, R))
+        frames, cstride, pc = cond.shape[1], cond.shape[2], cond.data_ptr()
+    pb = [_chk(t, n, torch.float32, (R,)) for t, n in ((bias_f, "bias_f"), (bias_g, "bias_g"), (bias_r, "bias_r"))]
+    po = [_chk(t, n, x.dtype, (B, T, R)) for t, n in ((h_out, "h_out"), (z_out, "z_out"), (s_out, "s_out"), (c_out, "c_out"))]
+    call("srwn_wavenet_layer_fwd", px, pc, wconv_ptr, wres_ptr, *pb, *po, B, T, R, K, int(dilation), frames,
+         int(pool_stride), int(cstride), abi_dtype(x.dtype), _stream())
+
+
+def wavenet_layer_bwd(g_in: Optional[torch.Tensor], d_up: Optional[torch.Tensor], wconvT_up_ptr: Optional[int],
+                      g_out: Optional[torch.Tensor], wresT_ptr: Optional[int], wskipT_ptr: Optional[int],
+                      dtotal: Optional[torch.Tensor], dcs: Optional[torch.Tensor], z: Optional[torch.Tensor],
+                      s: Optional[torch.Tensor], d_out: Optional[torch.Tensor], B: int, T: int, R: int, S: int, K: int,
+                      dilation_up: int, has_up: bool, has_down: bool, dtype: torch.dtype):
+    """Canonical-gate layer data gradient (csrc/srwn_wngate.hip); D tensors are [B,T,2R] = [d f | d g]."""
+    shp, shp2 = (B, T, R), (B, T, 2 * R)
+    pdt = None
+    if dtotal is not None:
+        pdt = _chk(dtotal, "dtotal", dtype)
+        if dtotal.numel() != B * T * S:
+            raise ValueError("dtotal: %d elements, expected %d" % (dtotal.numel(), B * T * S))
+    call("srwn_wavenet_layer_bwd", _opt(g_in, "g_in", dtype, shp), _opt(d_up, "d_up", dtype, shp2), wconvT_up_ptr,
+         _opt(g_out, "g_out", dtype, shp), wresT_ptr, wskipT_ptr, pdt, _opt(dcs, "dcs", dtype, shp),
+         _opt(z, "z", dtype, shp), _opt(s, "s", dtype, shp), _opt(d_out, "d_out", dtype, shp2), B, T, R, S, K,
+         int(dilation_up), int(has_up), int(has_down), abi_dtype(dtype), _stream())
+
+
 def skip_dgrad_all(dtotal: torch.Tensor, wskipT_all_ptr: int, dcs: torch.Tensor, R: int, S: int):
     """dcs[l] = dtotal @ Ws_l^T for every layer (dcs: [L, rows, R])."""
     L, rows, R2 = dcs.shape

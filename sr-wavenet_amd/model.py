@@ -145,7 +145,7 @@ class WaveNet(_EngineOwner):
     """model.py:8-72.  ``train(inputs[B,T], targets[B,output_size]) -> loss``; ``predict -> [B,1,C]``."""
 
     def __init__(self, input_size, output_size, dilations, filter_width=2, dilation_channels=32, skip_channels=256,
-                 output_channels=256, name="WaveNet", learning_rate=0.001, dtype=None, seed=0):
+                 output_channels=256, name="WaveNet", learning_rate=0.001, dtype=None, seed=0, *, gate_mode="reference"):
         self.input_size = input_size
         self.output_size = output_size
         self.dilations = dilations
@@ -160,7 +160,8 @@ class WaveNet(_EngineOwner):
         self._setup(StackConfig(dilations=list(dilations), filter_width=filter_width,
                                 dilation_channels=dilation_channels, skip_channels=skip_channels,
                                 output_channels=output_channels, shift_input=False, head_mode="pooled",
-                                dtype=dtype or _default_dtype(), learning_rate=learning_rate), seed)
+                                dtype=dtype or _default_dtype(), learning_rate=learning_rate, gate_mode=gate_mode), seed)
+        self.gate_mode = gate_mode
 
     def _stage(self, inputs, targets=None):
         x = np.asarray(inputs, dtype=np.float32)
@@ -202,13 +203,19 @@ class WaveNetTeacher(_EngineOwner):
     def __init__(self, input_size, condition_size, dilations, filter_width=2, dilation_channels=32,
                  skip_channels=256, quantization_channels=256, latent_channels=16, pool_stride=512,
                  name="WaveNetTeacher", learning_rate=0.001, use_encoding=False, dtype=None, seed=0,
-                 head="softmax", num_mixtures=5):
+                 head="softmax", num_mixtures=5, *, gate_mode="reference"):
+        """gate_mode: "reference" (default) = the gate the reference runs, c = z*sigmoid(z) (ops.py:33); "wavenet" = the
+        canonical tanh(Wf*x) * sigmoid(Wg*x), which also trains the `_gate` variables (generation is not built for it)."""
+        if gate_mode not in ("reference", "wavenet"):
+            raise ValueError("gate_mode %r: 'reference' or 'wavenet'" % (gate_mode,))
         self._ctor = dict(input_size=int(input_size), condition_size=int(condition_size),
                           dilations=[int(d) for d in dilations], filter_width=int(filter_width),
                           dilation_channels=int(dilation_channels), skip_channels=int(skip_channels),
                           quantization_channels=int(quantization_channels), latent_channels=int(latent_channels),
                           pool_stride=int(pool_stride), name=name, learning_rate=float(learning_rate),
-                          use_encoding=bool(use_encoding), seed=int(seed), head=head, num_mixtures=int(num_mixtures))
+                          use_encoding=bool(use_encoding), seed=int(seed), head=head, num_mixtures=int(num_mixtures),
+                          gate_mode=gate_mode)
+        self.gate_mode = gate_mode
         self.input_size = input_size
         self.condition_size = condition_size
         self.dilations = dilations
@@ -228,7 +235,7 @@ class WaveNetTeacher(_EngineOwner):
                                 cond_channels=cond_ch, pool_stride=pool_stride if cond_ch else 1, shift_input=True,
                                 head_mode="per_timestep" if head == "softmax" else "mol",
                                 dtype=dtype or _default_dtype(),
-                                learning_rate=learning_rate), seed)
+                                learning_rate=learning_rate, gate_mode=gate_mode), seed)
 
     def save(self, logdir, global_step, force=False, fmt=None):
         """Checkpoint + ``config.json`` (the constructor arguments; the reference gets them from the meta graph
@@ -292,6 +299,9 @@ class WaveNetTeacher(_EngineOwner):
         samples; the mixture-of-logistics teacher (optionally conditioned on `encoding`) emits logistic samples."""
         if self.head == "softmax" and self.use_encoding:
             raise NotImplementedError("generation: the conditioned softmax teacher is not built")
+        if self.gate_mode == "wavenet":
+            raise NotImplementedError("generation: gate_mode 'wavenet' is trained only (the generation kernels implement "
+                                      "the reference gate)")
         eng = self._primary or self._engine(1, self._default_length)
         f = None if forced is None else torch.as_tensor(np.asarray(forced, dtype=np.float32), device="cuda")
         cond = None
@@ -529,6 +539,9 @@ class ParallelWaveNet(object):
         else:
             self._teacher = teacher
         t = self._teacher
+        if isinstance(t, WaveNetTeacher) and t.gate_mode != "reference":
+            raise ValueError("ParallelWaveNet: the teacher was built with gate_mode=%r; distillation runs the reference "
+                             "gate only (the teacher's generation and the flows implement it)" % t.gate_mode)
         if t is None:
             tc = self._teacher_cfg
             tl, tcs, tp, tdt = tc["latent_channels"], tc["condition_size"], tc["pool_stride"], None
