@@ -360,7 +360,9 @@ int srwn_adam_step(float* params, const float* grads, float* m, float* v, int64_
  *   srwn_time_mean   : out[b,c] = mean_t x[b,t,c]   (partials: B*srwn_time_mean_slabs(T)*C floats)
  *   srwn_pooled_head : logits = mean @ w2 + b2; probs = softmax (model.py:60); with labels also
  *                      loss = mean_b softmax_cross_entropy_with_logits_v2 (soft labels, model.py:29),
- *                      gw2/gb2 (written, [S,ldw]/[ldw]) and dmean = d loss / d mean  [B,S]
+ *                      gw2/gb2 (written, [S,ldw]/[ldw]) and dmean = d loss / d mean  [B,S].  Any B (since
+ *                      srwn_version() 103: the rows go through one workgroup's LDS in chunks, same bits for any
+ *                      chunk size); C <= 16128
  *   srwn_bcast_mask  : da1[b,t,s] = (r1[b,t,s] > 0) ? dmean[b,s]*scale : 0  (scale = 1/T) */
 int32_t srwn_time_mean_slabs(int32_t T);
 int srwn_time_mean(const void* x, float* partials, float* out, int32_t B, int32_t T, int32_t C, int32_t dtype,

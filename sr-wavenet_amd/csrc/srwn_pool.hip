@@ -50,94 +50,107 @@ extern "C" int srwn_time_mean(const void* x, float* partials, float* out, int32_
 //   logits = mean @ w2 + b2; probs = softmax(logits); loss = mean_b( -sum_c labels*log_softmax )
 //   dl = (probs*sum_c(labels) - labels) / B
 //   gw2[s][c] = sum_b mean[b][s]*dl[b][c];  gb2[c] = sum_b dl[b][c];  dmean[b][s] = sum_c dl[b][c]*w2[s][c]
+// LDS holds the logits/dl of one chunk of `chunk` rows, so any B runs: the rows go through in chunks, and the sums over
+// b of gw2 and gb2 continue from the value the previous chunk left in global memory -- the same thread owns the same
+// element in every chunk and adds the rows in the same order, so the result is the same bits for any chunk size.
+constexpr int kPhLdsFloats = 65536 / 4;   // the LDS budget of one block: chunk*C + 256 floats
+
 __global__ __launch_bounds__(256) void pooled_head_kernel(const float* __restrict__ mean, const float* __restrict__ w2,
                                                           const float* __restrict__ b2, const float* __restrict__ labels,
                                                           float* __restrict__ probs, float* __restrict__ loss,
                                                           float* __restrict__ gw2, float* __restrict__ gb2,
-                                                          float* __restrict__ dmean, int B, int S, int C, int ldw) {
-  extern __shared__ float sh[];  // logits/dl [B*C], red[256]
+                                                          float* __restrict__ dmean, int B, int S, int C, int ldw,
+                                                          int chunk) {
+  extern __shared__ float sh[];  // logits/dl [chunk*C], red[256]
   float* dl = sh;
-  float* red = sh + B * C;
-  for (int i = threadIdx.x; i < B * C; i += 256) {
-    const int b = i / C, c = i % C;
-    float acc = b2[c];
-    for (int s = 0; s < S; ++s) acc = fmaf(mean[b * S + s], w2[(int64_t)s * ldw + c], acc);
-    dl[i] = acc;
-  }
-  __syncthreads();
+  float* red = sh + chunk * C;
   float lsum = 0.0f;
-  for (int b = 0; b < B; ++b) {  // rows are few; every thread walks every row, columns split over threads
-    float m = -INFINITY;
-    for (int c = threadIdx.x; c < C; c += 256) m = fmaxf(m, dl[b * C + c]);
-    red[threadIdx.x] = m;
+  for (int b0 = 0; b0 < B; b0 += chunk) {
+    const int nb = min(chunk, B - b0);
+    const float* mc = mean + (int64_t)b0 * S;
+    const float* lc = labels ? labels + (int64_t)b0 * C : nullptr;
+    float* pc = probs ? probs + (int64_t)b0 * C : nullptr;
+    for (int i = threadIdx.x; i < nb * C; i += 256) {
+      const int b = i / C, c = i % C;
+      float acc = b2[c];
+      for (int s = 0; s < S; ++s) acc = fmaf(mc[b * S + s], w2[(int64_t)s * ldw + c], acc);
+      dl[i] = acc;
+    }
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+    for (int b = 0; b < nb; ++b) {  // rows are few; every thread walks every row, columns split over threads
+      float m = -INFINITY;
+      for (int c = threadIdx.x; c < C; c += 256) m = fmaxf(m, dl[b * C + c]);
+      red[threadIdx.x] = m;
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + w]);
+        __syncthreads();
+      }
+      m = red[0];
+      __syncthreads();
+      float se = 0.0f, sl = 0.0f;
+      for (int c = threadIdx.x; c < C; c += 256) {
+        se += expf(dl[b * C + c] - m);
+        sl += lc ? lc[b * C + c] : 0.0f;
+      }
+      red[threadIdx.x] = se;
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+      }
+      se = red[0];
+      __syncthreads();
+      red[threadIdx.x] = sl;
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+      }
+      sl = red[0];
+      __syncthreads();
+      const float lse = m + logf(se);
+      float part = 0.0f;
+      for (int c = threadIdx.x; c < C; c += 256) {
+        const float lg = dl[b * C + c];
+        const float p = expf(lg - lse);
+        const float y = lc ? lc[b * C + c] : 0.0f;
+        if (pc) pc[b * C + c] = p;
+        part += -y * (lg - lse);
+        dl[b * C + c] = (p * sl - y) / (float)B;
+      }
+      red[threadIdx.x] = part;
+      __syncthreads();
+      for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+      }
+      lsum += red[0];
       __syncthreads();
     }
-    m = red[0];
-    __syncthreads();
-    float se = 0.0f, sl = 0.0f;
-    for (int c = threadIdx.x; c < C; c += 256) {
-      se += expf(dl[b * C + c] - m);
-      sl += labels ? labels[b * C + c] : 0.0f;
+    if (!labels) continue;
+    for (int i = threadIdx.x; i < S * ldw; i += 256) {
+      const int s = i / ldw, c = i % ldw;
+      float acc = (b0 > 0 && c < C) ? gw2[i] : 0.0f;
+      if (c < C)
+        for (int b = 0; b < nb; ++b) acc = fmaf(mc[b * S + s], dl[b * C + c], acc);
+      gw2[i] = acc;
     }
-    red[threadIdx.x] = se;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
+    for (int c = threadIdx.x; c < ldw; c += 256) {
+      float acc = (b0 > 0 && c < C) ? gb2[c] : 0.0f;
+      if (c < C)
+        for (int b = 0; b < nb; ++b) acc += dl[b * C + c];
+      gb2[c] = acc;
     }
-    se = red[0];
-    __syncthreads();
-    red[threadIdx.x] = sl;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
+    for (int i = threadIdx.x; i < nb * S; i += 256) {
+      const int b = i / S, s = i % S;
+      float acc = 0.0f;
+      for (int c = 0; c < C; ++c) acc = fmaf(dl[b * C + c], w2[(int64_t)s * ldw + c], acc);
+      dmean[(int64_t)b0 * S + i] = acc;
     }
-    sl = red[0];
-    __syncthreads();
-    const float lse = m + logf(se);
-    float part = 0.0f;
-    for (int c = threadIdx.x; c < C; c += 256) {
-      const float lg = dl[b * C + c];
-      const float p = expf(lg - lse);
-      const float y = labels ? labels[b * C + c] : 0.0f;
-      if (probs) probs[b * C + c] = p;
-      part += -y * (lg - lse);
-      dl[b * C + c] = (p * sl - y) / (float)B;
-    }
-    red[threadIdx.x] = part;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    lsum += red[0];
-    __syncthreads();
+    __syncthreads();   // the next chunk overwrites dl
   }
   if (threadIdx.x == 0 && loss) loss[0] = lsum / (float)B;
-  if (!labels) return;
-  for (int i = threadIdx.x; i < S * ldw; i += 256) {
-    const int s = i / ldw, c = i % ldw;
-    float acc = 0.0f;
-    if (c < C)
-      for (int b = 0; b < B; ++b) acc = fmaf(mean[b * S + s], dl[b * C + c], acc);
-    gw2[i] = acc;
-  }
-  for (int c = threadIdx.x; c < ldw; c += 256) {
-    float acc = 0.0f;
-    if (c < C)
-      for (int b = 0; b < B; ++b) acc += dl[b * C + c];
-    gb2[c] = acc;
-  }
-  for (int i = threadIdx.x; i < B * S; i += 256) {
-    const int b = i / S, s = i % S;
-    float acc = 0.0f;
-    for (int c = 0; c < C; ++c) acc = fmaf(dl[b * C + c], w2[(int64_t)s * ldw + c], acc);
-    dmean[i] = acc;
-  }
 }
 
 extern "C" int srwn_pooled_head(const float* mean, const float* w2, const float* b2, const float* labels,
@@ -146,11 +159,12 @@ extern "C" int srwn_pooled_head(const float* mean, const float* w2, const float*
   if (B == 0) return 0;
   if (!mean || !w2 || !b2) return set_error(SRWN_E_NULL, "pooled_head: null pointer");
   if (labels && (!gw2 || !gb2 || !dmean)) return set_error(SRWN_E_NULL, "pooled_head: labels given but gradient outputs missing");
-  if (B < 0 || S < 1 || C < 1 || ldw < C) return set_error(SRWN_E_SHAPE, "pooled_head: B=%d S=%d C=%d ldw=%d", B, S, C, ldw);
-  const size_t sh = ((size_t)B * C + 256) * sizeof(float);
-  if (sh > 65536) return set_error(SRWN_E_SHAPE, "pooled_head: B*C=%d too large for one block", B * C);
+  if (B < 0 || S < 1 || C < 1 || C > kPhLdsFloats - 256 || ldw < C)
+    return set_error(SRWN_E_SHAPE, "pooled_head: B=%d S=%d C=%d ldw=%d", B, S, C, ldw);
+  const int chunk = min((int)B, (kPhLdsFloats - 256) / (int)C);
+  const size_t sh = ((size_t)chunk * C + 256) * sizeof(float);
   hipLaunchKernelGGL(pooled_head_kernel, dim3(1), dim3(256), sh, (hipStream_t)stream, mean, w2, b2, labels, probs,
-                     loss, gw2, gb2, dmean, B, S, C, ldw);
+                     loss, gw2, gb2, dmean, (int)B, (int)S, (int)C, (int)ldw, chunk);
   return check_launch("pooled_head");
 }
 

@@ -92,6 +92,9 @@ class _Span:
         return False
 
 
+CONTRASTIVE_LDS_FLOATS = 65536 // 4   # srwn_contrastive_head: rows*D + 2P floats in one workgroup (csrc/srwn_siamese.hip)
+
+
 class WaveNetEngine:
     def __init__(self, cfg: StackConfig, batch: int, length: int, device="cuda", seed: int = 0,
                  process_group=None, share_from: Optional["WaveNetEngine"] = None, frozen: bool = False):
@@ -111,6 +114,14 @@ class WaveNetEngine:
             raise ValueError("mol head: output_channels = 4 * num_mixtures (<= 16 mixtures)")
         if cfg.head_mode not in ("per_timestep", "pooled", "mol", "flow", "contrastive"):
             raise ValueError("head_mode %r" % cfg.head_mode)
+        if cfg.head_mode == "contrastive":
+            # srwn_contrastive_head is one workgroup: the embeddings of all rows (and two floats per pair) live in its
+            # 64 KiB of LDS.  Refused here, not on the first forward (the engine scores pairs when B is even)
+            need = batch * cfg.output_channels + (batch if batch % 2 == 0 else 0)
+            if need > CONTRASTIVE_LDS_FLOATS:
+                raise ValueError("contrastive head: B=%d clips x D=%d dimensions (+ 2 per pair) need %d floats, over the "
+                                 "head kernel's limit of %d (64 KiB of LDS)"
+                                 % (batch, cfg.output_channels, need, CONTRASTIVE_LDS_FLOATS))
         if cfg.cond_channels and (length % cfg.pool_stride):
             raise ValueError("length %d is not a multiple of pool_stride %d" % (length, cfg.pool_stride))
         self.cfg = cfg

@@ -1,9 +1,12 @@
 """One rank of the data-parallel GPU test (tests/test_gpu_dp2.py): a fresh process that shards a fixed global batch,
 runs one eager and two graph-replayed training steps of the ENGINE's own data-parallel schedule (gradient all-reduce
 in one bucket or two, the first overlapped with the lower backward pass), and saves its parameters.
-usage: dp_worker.py <mode: softmax|mol|student|deep> <out.pt>     (RANK / WORLD_SIZE / MASTER_* from the environment)
+usage: dp_worker.py <mode: softmax|mol|student|deep|pooled|contrastive> <out.pt>     (RANK / WORLD_SIZE / MASTER_* from
+the environment)
 "deep" is the benchmark's own stack (30 layers 3 x [1..512], bf16) on clips longer than the receptive field, so that the
-two-bucket schedule cuts where the benchmark cuts (split_layer = 10, three hipGraphs)."""
+two-bucket schedule cuts where the benchmark cuts (split_layer = 10, three hipGraphs).  "pooled" and "contrastive" are
+the clip-level heads (class WaveNet, class SiameseWaveNet), whose head_w2 / head_b2 gradients are written in forward;
+in "contrastive" a rank's shard is its own pairs: its left clips, then their right partners."""
 import importlib
 import os
 import sys
@@ -37,19 +40,35 @@ def main():
     sl = slice(rank * b, (rank + 1) * b)
     audio = O.synthetic_audio(GB, T, seed=5)
     dev = lambda a, dt=torch.float32: torch.tensor(np.asarray(a), dtype=dt, device="cuda")
-    if mode in ("softmax", "mol", "deep"):
-        C = 20 if mode == "mol" else 256
+    if mode in ("softmax", "mol", "deep", "pooled", "contrastive"):
+        C = {"mol": 20, "pooled": 10, "contrastive": 2}.get(mode, 256)
         sp = O.init_stack_params(7, dil, 2, R, S, C, bias_scale=0.05)
-        cfg = EG.StackConfig(dilations=dil, dilation_channels=R, skip_channels=S, output_channels=C, shift_input=True,
-                             dtype=dtype, learning_rate=1e-3,
-                             head_mode="mol" if mode == "mol" else "per_timestep")
-        eng = EG.WaveNetEngine(cfg, b, T, "cuda")
-        eng.load_oracle_params(sp)
-        codes = O.mu_law_encode(audio, 256).astype(np.int32)
-        eng.set_inputs(dev(audio[sl]), dev(codes[sl], torch.int32))
+        head = {"mol": "mol", "pooled": "pooled", "contrastive": "contrastive"}.get(mode, "per_timestep")
+        clip = head in ("pooled", "contrastive")
+        cfg = EG.StackConfig(dilations=dil, dilation_channels=R, skip_channels=S, output_channels=C,
+                             shift_input=not clip, dtype=dtype, learning_rate=1e-3, head_mode=head, margin=0.05)
+        if mode == "contrastive":      # GB pairs = 2 GB clips: left clips, then right ones; a rank takes its own pairs
+            audio = O.synthetic_audio(2 * GB, T, seed=5)
+            labels = np.array([1.0, 0.0, 0.25, 0.0], np.float32)
+            rows = np.concatenate([np.arange(GB)[sl], GB + np.arange(GB)[sl]])
+            eng = EG.WaveNetEngine(cfg, 2 * b, T, "cuda")
+            eng.load_oracle_params(sp)
+            eng.set_inputs(dev(audio[rows]), dev(labels[sl]))
+        elif mode == "pooled":
+            y = np.random.default_rng(3).random((GB, C)).astype(np.float32)
+            y /= y.sum(-1, keepdims=True)
+            eng = EG.WaveNetEngine(cfg, b, T, "cuda")
+            eng.load_oracle_params(sp)
+            eng.set_inputs(dev(audio[sl]), dev(y[sl]))
+        else:
+            eng = EG.WaveNetEngine(cfg, b, T, "cuda")
+            eng.load_oracle_params(sp)
+            codes = O.mu_law_encode(audio, 256).astype(np.int32)
+            eng.set_inputs(dev(audio[sl]), dev(codes[sl], torch.int32))
         info = {"bucketed": bool(eng.bucketed), "world": eng.world, "fused": bool(eng.fused_bwd),
                 "split_layer": int(eng.split_layer), "layers": eng.L,
-                "backend": dist.get_backend() if grouped else "none"}
+                "backend": dist.get_backend() if grouped else "none",
+                "sections": {n: (s.offset, s.numel) for n, s in eng.sections.items()}}
         eng.train_step()
         torch.cuda.synchronize()
         grads1, params1 = eng.grads.cpu().clone(), eng.params.cpu().clone()

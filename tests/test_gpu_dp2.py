@@ -45,13 +45,19 @@ def _run(mode, world, tmp_path, tag, buckets, port, backend="gloo", force_dist=F
     return [torch.load(o, weights_only=True) for o in outs]
 
 
-@pytest.mark.parametrize("mode,buckets", [("softmax", "0"), ("softmax", "1"), ("mol", "1"), ("student", "0"), ("deep", "1")])
+@pytest.mark.parametrize("mode,buckets", [("softmax", "0"), ("softmax", "1"), ("mol", "1"), ("student", "0"), ("deep", "1"),
+                                          ("pooled", "0"), ("contrastive", "0")])
 def test_two_ranks_equal_one_process_on_the_global_batch(tmp_path, mode, buckets):
     """"deep": BASELINE config 3's stack and dtype (30 layers, bf16) with two ranks through the schedule the scaling bench
     replays: backward cut at layer 10, first bucket all-reduced beside the lower part, three hipGraphs.  The shards are
     whole clips, every kernel works clip by clip, so even in bf16 two ranks and one process form the same per-clip
-    gradients: only the order of the fp32 sums differs."""
-    port = 29600 + (os.getpid() % 200) + {"softmax": 0, "mol": 1, "student": 2, "deep": 3}[mode] * 3 + int(buckets)
+    gradients: only the order of the fp32 sums differs.
+    "pooled" / "contrastive": the clip-level heads (class WaveNet, class SiameseWaveNet) write their head_w2 / head_b2
+    gradients during forward, outside the backward chain the buckets follow; those must be all-reduced too.  A
+    contrastive rank holds its own pairs (its left clips, then their right partners).  (The engine keeps one bucket for
+    the clip-level heads.)"""
+    port = 29600 + (os.getpid() % 200) + {"softmax": 0, "mol": 1, "student": 2, "deep": 3, "pooled": 4,
+                                          "contrastive": 5}[mode] * 3 + int(buckets)
     ref = _run(mode, 1, tmp_path, "ref", "0", port)[0]
     r0, r1 = _run(mode, 2, tmp_path, "dp" + buckets, buckets, port + 400)
     assert r0["info"]["world"] == 2 and r1["info"]["world"] == 2
@@ -69,6 +75,16 @@ def test_two_ranks_equal_one_process_on_the_global_batch(tmp_path, mode, buckets
     scale = 1.0 if mode == "mol" else 0.5
     gerr = float((g * scale - gref).abs().max() / gref.abs().max())
     assert gerr < (1e-4 if mode == "deep" else 1e-5), gerr
+    if mode in ("pooled", "contrastive"):     # the head gradients written in forward, on their own scale
+        for n in ("head_w2", "head_b2"):
+            off, num = r0["info"]["sections"][n]
+            h, href = g[off:off + num] * scale, gref[off:off + num]
+            if mode == "contrastive" and n == "head_b2":
+                assert not h.any() and not href.any(), "the contrastive loss is translation-invariant: head_b2 is 0"
+                continue
+            assert href.abs().max() > 0, n
+            herr = float((h - href).abs().max() / href.abs().max())
+            assert herr < 1e-5, (n, herr)
     # parameters after the first Adam step and after the two graph-replayed ones, where the gradient is not numerically
     # zero (Adam turns the sign of a ~1e-9 gradient entry into a 1e-3 step, and later steps amplify that)
     # ("deep": the bf16 gradients of two ranks and one process may differ by 1e-4 of the largest entry -- the bound

@@ -184,6 +184,11 @@ def test_stack_conditioned_decoder(monkeypatch, dt, tol, E):
     _check_grads(eng, grads, tol, with_cond=True)
 
 
+# bf16 gradients of test_pooled_classifier_head: 2x the worst per-tensor relative L2 error measured on one MI355X
+# (SRWN_PRINT_ERR=1 pytest -s prints it): C = 30 1.37e-2 (init_w), C = 256 1.91e-2 (init_w)
+POOLED_BF16_GRAD = {30: 2.8e-2, 256: 3.9e-2}
+
+
 @pytest.mark.parametrize("dt,tol", [(torch.float32, 1e-3), (torch.bfloat16, 5e-2)])
 @pytest.mark.parametrize("C", [30, 256])
 def test_pooled_classifier_head(dt, tol, C):
@@ -208,6 +213,19 @@ def test_pooled_classifier_head(dt, tol, C):
     eng.backward()
     if dt == torch.float32:
         _check_grads(eng, grads, tol)
+    else:   # bf16: every gradient tensor in relative L2 (bound: 2x the worst measured on one MI355X, see POOLED_BF16_GRAD)
+        got = eng.named_tensors(eng.grads)
+        errs = {}
+        for n, ref in dict(O.flatten_named(grads, False)).items():
+            g = got[n].float().cpu().numpy()
+            if np.abs(ref).max() < 1e-12:
+                assert not g.any(), n       # the top layer's residual 1x1: exactly zero
+                continue
+            errs[n] = float(np.linalg.norm(g - ref) / np.linalg.norm(ref))
+        worst = max((v, k) for k, v in errs.items())
+        if os.environ.get("SRWN_PRINT_ERR"):
+            print("MEASURED pooled head C=%d bf16 worst gradient rel L2 %.3e (%s)" % (C, worst[0], worst[1]))
+        assert worst[0] < POOLED_BF16_GRAD[C], worst
     l0 = float(eng.loss.item())
     for _ in range(5):
         eng.train_step()

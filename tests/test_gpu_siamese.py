@@ -36,11 +36,26 @@ def _np_head(mean, w2, b2, labels, margin, D):
 @pytest.mark.parametrize("P", [1, 3, 33])
 @pytest.mark.parametrize("D", [2, 16, 30])
 def test_contrastive_head_kernel(P, D):
+    _contrastive_head_case(P, D)
+
+
+@pytest.mark.parametrize("P,D", [(65, 2), (65, 30), (65, 65), (200, 2), (200, 30), (1, 65), (33, 65), (1, 256),
+                                 (3, 256), (31, 256)])
+def test_contrastive_head_kernel_many_pairs_and_wide_embeddings(P, D):
+    """More pairs than the 64 lanes of the loss sum (65, 200) and embeddings wider than a wave (65, 256: the lane loop
+    over k wraps).  The last pair is two identical clips (d = 1e-4, the 1e-8 floor: finite gradients, equal to the
+    oracle's), and one margin is set to a pair's own fp32 distance (the hinge exactly at zero)."""
+    _contrastive_head_case(P, D, identical_last=True)
+
+
+def _contrastive_head_case(P, D, identical_last=False):
     L = sub("_lib")
     S = 96
     ldw = (D + 31) // 32 * 32
     rng = np.random.default_rng(100 * P + D)
     mean = rng.normal(0, 1, (2 * P, S)).astype(np.float32)
+    if identical_last:
+        mean[2 * P - 1] = mean[P - 1]
     w2 = rng.normal(0, 0.3, (S, ldw)).astype(np.float32)
     w2[:, D:] = 7.0                        # padding columns: never read
     b2 = rng.normal(0, 0.1, ldw).astype(np.float32)
@@ -49,6 +64,14 @@ def test_contrastive_head_kernel(P, D):
     margins = [0.5 * d0.min(), 2.0 * d0.max()] + ([float(np.median(d0))] if P > 1 else [])
     st = torch.cuda.current_stream().cuda_stream
     g_mean, g_w2, g_b2, g_lab = dev(mean), dev(w2), dev(b2), dev(labels)
+    if identical_last:
+        assert abs(d0[-1] - 1e-4) < 1e-12
+        dist = torch.full((P,), np.nan, device=DEV)
+        emb = torch.full((2 * P, D), np.nan, device=DEV)
+        L.call("srwn_contrastive_head", g_mean.data_ptr(), g_w2.data_ptr(), g_b2.data_ptr(), None, 1.0,
+               emb.data_ptr(), dist.data_ptr(), None, None, None, None, 2 * P, S, D, ldw, st)
+        torch.cuda.synchronize()
+        margins.append(float(dist[0].item()))          # the kernel's own fp32 distance of pair 0: max(0, m - d) == 0
     for margin in margins:
         emb = torch.full((2 * P, D), np.nan, device=DEV)
         dist = torch.full((P,), np.nan, device=DEV)

@@ -154,3 +154,15 @@ def test_contrastive_loss_restatement_matches_finite_differences():
     gp = (labels * d - (1 - labels) * torch.clamp(margin - d, min=0.0)) / P
     closed = gp[:, None] * (emb[:P] - emb[P:]) / d[:, None]
     assert torch.allclose(e.grad[:P], closed, rtol=1e-12, atol=1e-15)
+
+
+def test_contrastive_batch_over_the_head_limit_is_refused_when_built():
+    """srwn_contrastive_head holds rows*D + 2P floats in one workgroup's 64 KiB of LDS: the engine refuses a batch past
+    that when it is built, naming B, D and the limit, not on its first forward."""
+    EG = sub("engine")
+    cfg = EG.StackConfig(dilations=[1, 2], dilation_channels=32, skip_channels=128, output_channels=63,
+                         head_mode="contrastive")
+    with pytest.raises(ValueError, match=r"B=258 .*D=63.*16384"):      # 258*63 + 258 floats
+        EG.WaveNetEngine(cfg, 258, 64, "cpu")
+    with pytest.raises(ValueError, match=r"B=261 .*D=63.*16384"):      # 261*63 floats (odd: embedding only)
+        EG.WaveNetEngine(cfg, 261, 64, "cpu")
