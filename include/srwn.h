@@ -529,6 +529,56 @@ int srwn_generate_mol(const void* wcr, const void* wskip, const void* w1, const 
                       int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed,
                       int32_t dtype, void* stream);
 
+/* ---- resumable generation (since srwn_version() 104): the four generators above as one call of a longer run, so that a
+ * stream is produced chunk by chunk, stopped and continued, or continued from a prompt (the loop of teacher.py:140-171 /
+ * generator.py:150-170 runs from t = 0 to the end in one go; these split it anywhere).  Each *_resume entry point takes
+ * the arguments of the call it extends, plus:
+ *   t0     the absolute step of the launch's first sample: step j of the launch is step t = t0 + j for the ring slots
+ *          (t mod (d_l+1)), the delayed-tap test t - d_l >= 0, the conditioning frame t / pool_stride and both samplers'
+ *          counters (softmax: (seed, u, t); mixture: (seed, u, t*(M+1)+m)).  Rows j of audio_out / codes_out / logits_out
+ *          and of forced are the launch's own ([B, Tout] with nsteps <= Tout, as before).
+ *   carry  float [B][2] = (a[t0-1], a[t0-2]), the two audio samples the input conv with RightShift (model.py:172-173)
+ *          reads at step t0; read at the start, and on return it holds (a[t0+n-1], a[t0+n-2]) for the next launch: the
+ *          forced samples where the launch was teacher-forced (step j reads forced[j-1] for j >= 1, else carry[0], and
+ *          forced[j-2] for j >= 2, carry[0] for j = 1, carry[1] for j = 0), the emitted samples where it ran free.
+ *          NULL = zeros in, nothing written back (only with t0 = 0: a NULL carry with t0 > 0 is SRWN_E_NULL).
+ * The ring must hold the state after step t0 - 1: what the previous launch of the run left, srwn_generate_ring_fill, or
+ * zeros for t0 = 0.  The one-shot entry points are these with t0 = 0, carry = NULL, and return the same bits. */
+int srwn_generate_resume(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
+                         const float* bias_r, const float* bs_sum, const float* b1, const float* b2, const float* init_w,
+                         const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float* logits_out,
+                         const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                         int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, uint64_t seed,
+                         int32_t dtype, void* stream, int32_t t0, float* carry);
+int srwn_generate_mol_resume(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
+                             const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                             const float* init_w, const float* init_b, void* ring, float* audio_out, int32_t* codes_out,
+                             float* logits_out, const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B,
+                             int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                             const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                             uint64_t seed, int32_t dtype, void* stream, int32_t t0, float* carry);
+int srwn_generate16_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const float* bias_r,
+                           const float* bs_sum, const float* b1, const float* b2, const float* init_w, const float* init_b,
+                           void* ring, float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                           const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R,
+                           int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream, int32_t t0, float* carry);
+int srwn_generate16_mol_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const float* bias_r,
+                               const float* bs_sum, const float* b1, const float* b2, const float* init_w,
+                               const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float* logits_out,
+                               const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                               int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                               int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed,
+                               void* stream, int32_t t0, float* carry);
+/* The rings after a prompt of P samples, from ONE parallel forward pass over it instead of P generation steps (the
+ * teacher-forced loop of teacher.py:140-171 over the prompt): xs = the stored layer inputs of that pass, layer l at
+ * xs + l * layer_stride elements, [B, T_src, R] rows (T_src >= P; for a conditioned stack they already hold cb_l, as the
+ * rings do).  Writes every slot of every layer ring of all ceil(B/32) groups (layout of srwn_generate_ring_elems): slot s
+ * of layer l <- x_l[t] for the single t in [P-1-d_l, P-1] with t = s (mod d_l+1); zero where t < 0 or the utterance is
+ * >= B (the causal padding both bodies rely on).  Then a *_resume launch with t0 = P continues the prompt.  dtype bf16
+ * or fp32, R in {32, 64}; xs 16-byte aligned, layer_stride a multiple of 16 bytes; xs may be NULL when P = 0. */
+int srwn_generate_ring_fill(const void* xs, int64_t layer_stride, int32_t T_src, int32_t P, const int32_t* dilations,
+                            int32_t nlayers, int32_t B, int32_t R, void* ring, int32_t dtype, void* stream);
+
 /* ---- discretised mixture-of-logistics loss of the reference's live teacher:
  * discretized_mix_logistic_loss (ops.py:124-175, sum_all=True) on logits [rows, ldl] fp32 whose first 4*M
  * columns are (logit_probs, means, log_scales, coeffs) and targets x [rows] in [-1,1]:

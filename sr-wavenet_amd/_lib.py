@@ -106,6 +106,17 @@ SIGNATURES = {
                                       _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, C.c_uint64, _p]),
     "srwn_generate_mol": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32,
                                     _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, C.c_uint64, _i32, _p]),
+    "srwn_generate_resume": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                       _i32, _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _i32, _p, _i32, _p]),
+    "srwn_generate_mol_resume": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                           _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, C.c_uint64,
+                                           _i32, _p, _i32, _p]),
+    "srwn_generate16_resume": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                         _i32, _i32, _i32, _i32, _i32, _i32, C.c_uint64, _p, _i32, _p]),
+    "srwn_generate16_mol_resume": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                             _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, C.c_uint64, _p,
+                                             _i32, _p]),
+    "srwn_generate_ring_fill": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
     "srwn_mol_loss": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _i64, _i64, _f32, _i32, _p]),
     "srwn_wgrad256_slabs": (_i32, [_i64, _i32]),
     "srwn_wgrad256": (C.c_int, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p]),

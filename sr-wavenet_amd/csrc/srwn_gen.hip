@@ -38,6 +38,12 @@ struct GenArgs {
   // layer l adds row (u, t / pool) to its input, rounded to T like the training kernel.  NULL = unconditioned.
   const void* cond; int cond_frames; int pool; long long cond_ld;
   int M;                // > 0: mixture-of-logistics head with M mixtures (C = 4M logits) instead of the softmax
+  // resume form: the launch runs the absolute steps t0 <= t < nsteps (here: the END step t0 + n) -- ring slots, the
+  // delayed-tap test, the conditioning frame and the RNG counters see t; audio_out / codes_out / logits_out / forced arrive
+  // shifted back by t0 rows, so that row t of them is the launch's row t - t0 and the step loop keeps no second counter
+  // (one more live scalar spilled SGPRs to scratch).  carry [B][2] = (a[t0-1], a[t0-2]) in, (a[t0+n-1], a[t0+n-2]) out --
+  // the input samples the next step reads: forced ones where forced, else emitted ones.  t0 = 0 / NULL: the one-shot call
+  int t0; float* carry;
   long long ring_group_elems;
   unsigned long long seed;
   int dil[kGenMaxLayers];
@@ -59,6 +65,21 @@ __device__ __forceinline__ float gen_uniform(unsigned long long seed, unsigned u
   return (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f);   // (0,1)
 }
 
+// the carry a launch leaves for the next one (its last __syncthreads ordered prev): the samples step t_end reads, i.e. the
+// emitted ones of a free-running launch, the forced ones of a forced launch (prev[] holds the emitted ones there; after a
+// single step its older entry is still the carried a[t0-1]).  `forced` is shifted back by t0 rows like the outputs.
+__device__ __forceinline__ void gen_carry_out(float* carry, const float* forced, const float* prev, int u, int ul, int B,
+                                              int Tout, int t0, int t_end) {
+  if (u >= B) return;
+  float c0 = prev[ul], c1 = prev[32 + ul];
+  if (forced) {
+    c0 = forced[(size_t)u * Tout + t_end - 1];
+    if (t_end - t0 >= 2) c1 = forced[(size_t)u * Tout + t_end - 2];
+  }
+  carry[2 * u] = c0;
+  carry[2 * u + 1] = c1;
+}
+
 template <typename T, int RT> struct GenCond { f32x4 cc[RT][4]; };
 struct GenNoCond {};
 
@@ -74,7 +95,7 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
   char* wbuf = smem;                                             // [NBUF][LAYER_B]
   T* xch = reinterpret_cast<T*>(smem + NBUF * LAYER_B);          // [32][S] activation exchange (r0 / r1)
   float* lgl = reinterpret_cast<float*>(xch + 32 * S);           // [32][LGS] logits
-  float* prev = lgl + 32 * LGS;                                  // [2][32] last two samples
+  float* prev = lgl + 32 * LGS;                                  // [2][32] last two samples (starting as the carry)
   float* cst = prev + 64;                                        // constants: biases of every layer + head + input conv
   float* c_bf = cst;                 // [L][R]
   float* c_br = c_bf + a.L * R;      // [L][R]
@@ -104,7 +125,10 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
     c_b2[i] = (i < (a.C + 31) / 32 * 32) ? a.b2[i] : 0.0f;     // the last 1x1 has ceil(C/32)*32 rows
   if (threadIdx.x < 2 * R) c_iw[threadIdx.x] = a.init_w[threadIdx.x];
   if (threadIdx.x < R) c_ib[threadIdx.x] = a.init_b[threadIdx.x];
-  if (threadIdx.x < 64) prev[threadIdx.x] = 0.0f;
+  if (threadIdx.x < 64) {
+    const int u = u0 + (threadIdx.x & 31);
+    prev[threadIdx.x] = (a.carry && u < a.B) ? a.carry[2 * u + (threadIdx.x >> 5)] : 0.0f;
+  }
   if (a.Q >= 2) c_dec[threadIdx.x] = gen_mu_law_decode(threadIdx.x < a.Q ? threadIdx.x : a.Q - 1, a.Q);
   lds_dma_copy(wcr, wbuf, LAYER_B, wave, lane, 4);
   __syncthreads();
@@ -138,13 +162,15 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
       for (int ks = 0; ks < KS; ++ks) p.ws[m][ks] = wskip[((size_t)(MQ * wave + m) * ks_skip + l * KS + ks) * 64 + lane];
   };
 
-  for (int t = 0; t < a.nsteps; ++t) {
+  for (int t = a.t0; t < a.nsteps; ++t) {
     // ---- input conv with RightShift (model.py:172-173): h0[t] = w[0]*audio[t-2] + w[1]*audio[t-1] + b
+    // (prev[] starts as the carry, so a forced launch's first two steps read it there: shifted, the carried a[t0-1]
+    // is prev[32 + col] at step t0 + 1)
     float a1 = 0.0f, a2 = 0.0f;
     if (uok) {
       if (a.forced) {
-        if (t >= 1) a1 = a.forced[(size_t)ug * a.Tout + t - 1];
-        if (t >= 2) a2 = a.forced[(size_t)ug * a.Tout + t - 2];
+        a1 = (t >= a.t0 + 1) ? a.forced[(size_t)ug * a.Tout + t - 1] : prev[col];
+        a2 = (t >= a.t0 + 2) ? a.forced[(size_t)ug * a.Tout + t - 2] : prev[32 + col];
       } else {
         a1 = prev[col];
         a2 = prev[32 + col];
@@ -406,6 +432,8 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
     }
     __syncthreads();
   }
+  if (a.carry && threadIdx.x < 32) gen_carry_out(a.carry, a.forced, prev, u0 + threadIdx.x, threadIdx.x, a.B, a.Tout,
+                                                  a.t0, a.nsteps);
 }
 
 extern "C" int64_t srwn_generate_ring_elems(const int32_t* dilations, int32_t nlayers, int32_t R) {
@@ -420,8 +448,10 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
                          float* logits_out, const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B,
                          int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode,
                          uint64_t seed, int32_t dtype, void* stream, const void* cond, int32_t cond_frames,
-                         int32_t pool, int64_t cond_ld, int32_t M) {
+                         int32_t pool, int64_t cond_ld, int32_t M, int32_t t0, float* carry) {
   if (B == 0 || nsteps == 0) return 0;
+  if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate: t0=%d", t0);
+  if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate: a launch that resumes at t0=%d needs the carry", t0);
   if (!wcr || !wskip || !w1 || !w2 || !bias_f || !bias_r || !bs_sum || !b1 || !b2 || !init_w || !init_b || !ring ||
       !audio_out || !codes_out || !dilations)
     return set_error(SRWN_E_NULL, "generate: null pointer");
@@ -435,6 +465,11 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
   a.codes_out = codes_out; a.logits_out = logits_out; a.forced = forced;
   a.B = B; a.Tout = Tout; a.nsteps = nsteps; a.L = nlayers; a.C = C; a.mode = mode; a.Q = C; a.seed = seed;
   a.cond = cond; a.cond_frames = cond_frames; a.pool = pool; a.cond_ld = cond_ld; a.M = M;
+  // the shifted row pointers of the resume form (never dereferenced below row t0)
+  const ptrdiff_t sh = (ptrdiff_t)t0;
+  a.audio_out = audio_out - sh; a.codes_out = codes_out - sh;
+  a.logits_out = logits_out ? logits_out - sh * C : nullptr; a.forced = forced ? forced - sh : nullptr;
+  a.nsteps = t0 + nsteps; a.t0 = t0; a.carry = carry;
   long long off = 0;
   for (int l = 0; l < kGenMaxLayers; ++l) {
     a.dil[l] = (l < nlayers) ? dilations[l] : 1;
@@ -474,21 +509,53 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
   return check_launch("generate");
 }
 
+extern "C" int srwn_generate_resume(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                    const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                    const float* b2, const float* init_w, const float* init_b, void* ring,
+                                    float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                    const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
+                                    int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, uint64_t seed,
+                                    int32_t dtype, void* stream, int32_t t0, float* carry) {
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, seed, dtype, stream,
+                       nullptr, 1, 1, 0, 0, t0, carry);
+}
+
 extern "C" int srwn_generate(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
                              const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                              const float* init_w, const float* init_b, void* ring, float* audio_out,
                              int32_t* codes_out, float* logits_out, const float* forced, const int32_t* dilations,
                              int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
                              int32_t C, int32_t K, int32_t mode, uint64_t seed, int32_t dtype, void* stream) {
-  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, seed, dtype, stream,
-                       nullptr, 1, 1, 0, 0);
+  return srwn_generate_resume(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out,
+                              codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, seed,
+                              dtype, stream, 0, nullptr);
 }
 
 // The conditioned mixture-of-logistics decoder (WaveNetAutoEncoder.createDecoder, model.py:158-200): cond
 // [B*cond_frames, cond_ld] = the per-layer conditioning biases cb_l at columns [l*R, (l+1)*R) (srwn_pw_linear of
 // encoding_w_condition, model.py:180); head = 4*num_mixtures logits, sampled as ops.py:178-201.  b2 and the w2
 // image cover ceil(4M/32)*32 rows.  codes_out receives the selected mixture index.
+extern "C" int srwn_generate_mol_resume(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                        const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                        const float* b2, const float* init_w, const float* init_b, void* ring,
+                                        float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                        const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                        int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                                        const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                                        int32_t mode, uint64_t seed, int32_t dtype, void* stream, int32_t t0,
+                                        float* carry) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate_mol: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
+    return set_error(SRWN_E_SHAPE, "generate_mol: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames, pool_stride,
+                     (long long)cond_ld);
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, seed,
+                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, t0,
+                       carry);
+}
+
 extern "C" int srwn_generate_mol(const void* wcr, const void* wskip, const void* w1, const void* w2,
                                  const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
                                  const float* b2, const float* init_w, const float* init_b, void* ring,
@@ -497,12 +564,76 @@ extern "C" int srwn_generate_mol(const void* wcr, const void* wskip, const void*
                                  int32_t R, int32_t S, int32_t K, int32_t num_mixtures, const void* cond,
                                  int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed,
                                  int32_t dtype, void* stream) {
-  if (num_mixtures < 1 || num_mixtures > 16)
-    return set_error(SRWN_E_SHAPE, "generate_mol: num_mixtures=%d (1..16)", num_mixtures);
-  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
-    return set_error(SRWN_E_SHAPE, "generate_mol: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames, pool_stride,
-                     (long long)cond_ld);
-  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, seed,
-                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures);
+  return srwn_generate_mol_resume(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out,
+                                  codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, K,
+                                  num_mixtures, cond, cond_frames, pool_stride, cond_ld, mode, seed, dtype, stream, 0,
+                                  nullptr);
+}
+
+// ---- the rings after a prompt of P samples, from the layer inputs of ONE parallel forward pass over it (what the loop of
+// teacher.py:140-171 would have left after P steps): slot s of layer l <- x_l[t], the t in [P-1-d_l, P-1] with
+// t = s (mod d_l+1); zero where t < 0 or the utterance is past B (the causal padding the bodies rely on).  Memory-bound:
+// one 16-byte vector per thread, consecutive threads along the R channels of a row, then rows, then slots.
+struct RingFillArgs {
+  const void* xs; void* ring;
+  long long layer_stride, ring_group_elems;
+  int T_src, P, B, R;
+  int dil[kGenMaxLayers];
+  long long ring_off[kGenMaxLayers];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void ring_fill_kernel(RingFillArgs a) {
+  constexpr int V = 16 / sizeof(T);
+  const int l = blockIdx.y, g = blockIdx.z;
+  const int d = a.dil[l], depth = d + 1, vpr = a.R / V;
+  const int nvec = depth * 32 * vpr;
+  const int base = a.P - 1 - d;                                  // oldest step the ring still holds (may be < 0)
+  const T* xp = reinterpret_cast<const T*>(a.xs) + (size_t)l * a.layer_stride;
+  T* rp = reinterpret_cast<T*>(a.ring) + (size_t)g * a.ring_group_elems + a.ring_off[l];
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nvec; i += gridDim.x * 256) {
+    const int cv = i % vpr, r = i / vpr;                         // r = slot * 32 + row
+    const int row = r & 31, s = r >> 5, u = 32 * g + row;
+    int off = (s - base) % depth;
+    if (off < 0) off += depth;
+    const int t = base + off;
+    uint4 v = {0u, 0u, 0u, 0u};
+    if (t >= 0 && u < a.B) v = *reinterpret_cast<const uint4*>(xp + ((size_t)u * a.T_src + t) * a.R + cv * V);
+    *reinterpret_cast<uint4*>(rp + (size_t)r * a.R + cv * V) = v;
+  }
+}
+
+extern "C" int srwn_generate_ring_fill(const void* xs, int64_t layer_stride, int32_t T_src, int32_t P,
+                                       const int32_t* dilations, int32_t nlayers, int32_t B, int32_t R, void* ring,
+                                       int32_t dtype, void* stream) {
+  if (B == 0) return 0;
+  if (!ring || !dilations || (P > 0 && !xs)) return set_error(SRWN_E_NULL, "generate_ring_fill: null pointer");
+  if (R != 64 && R != 32) return set_error(SRWN_E_UNSUPPORTED, "generate_ring_fill: built for R=64 or 32 (got R=%d)", R);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "generate_ring_fill: dtype %d", dtype);
+  const int V = dtype == SRWN_BF16 ? 8 : 4;
+  if (B < 0 || P < 0 || T_src < P || nlayers < 1 || nlayers > kGenMaxLayers || layer_stride < 0 ||
+      (P > 0 && (layer_stride % V || (reinterpret_cast<uintptr_t>(xs) & 15) || (nlayers > 1 && layer_stride < (int64_t)B * T_src * R))))
+    return set_error(SRWN_E_SHAPE, "generate_ring_fill: B=%d P=%d T_src=%d layers=%d layer_stride=%lld", B, P, T_src,
+                     nlayers, (long long)layer_stride);
+  RingFillArgs a;
+  a.xs = xs; a.ring = ring; a.layer_stride = layer_stride; a.T_src = T_src; a.P = P; a.B = B; a.R = R;
+  long long off = 0;
+  int maxvec = 0;
+  for (int l = 0; l < kGenMaxLayers; ++l) {
+    a.dil[l] = (l < nlayers) ? dilations[l] : 1;
+    a.ring_off[l] = off;
+    if (l < nlayers) {
+      if (dilations[l] < 1 || dilations[l] > (1 << 20))
+        return set_error(SRWN_E_SHAPE, "generate_ring_fill: dilation %d", dilations[l]);
+      off += (long long)(dilations[l] + 1) * 32 * R;
+      maxvec = max(maxvec, (dilations[l] + 1) * 32 * (R / V));
+    }
+  }
+  if ((reinterpret_cast<uintptr_t>(ring) & 15)) return set_error(SRWN_E_SHAPE, "generate_ring_fill: ring not 16-byte aligned");
+  a.ring_group_elems = off;
+  const dim3 grid((unsigned)min((maxvec + 255) / 256, 1024), (unsigned)nlayers, (unsigned)((B + 31) / 32));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_fill_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(ring_fill_kernel<float>, grid, dim3(256), 0, st, a);
+  return check_launch("generate_ring_fill");
 }

@@ -39,6 +39,7 @@ struct Gen16Args {
   int B, Tout, nsteps, L, C, Cp, mode, Q;       // Cp: entries of b2 / rows of the last 1x1 (ceil(C/32)*32)
   int M;                                        // > 0: mixture-of-logistics head with M mixtures (C = 4M)
   const void* cond; int cond_frames, pool; long long cond_ld;   // conditioning biases cb_l (COND instantiation)
+  int t0; float* carry;                         // resume form (as generate_kernel's GenArgs): absolute first step, carry [B][2]
   long long ring_group_elems;
   unsigned long long seed;
   int dil[kG16MaxLayers];
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
   T* cb = xb + 32 * LSX;                                      // [32][LSX] the gate output c_l[t]
   T* hx = cb + 32 * LSX;                                      // [32][LSH] head activations (r0 / r1)
   float* lgl = reinterpret_cast<float*>(hx + 32 * LSH);       // [32][LGS] logits
-  float* prev = lgl + 32 * LGS;                               // [2][32] last two samples
+  float* prev = lgl + 32 * LGS;                               // [2][32] last two samples (starting as the carry)
   float* c_bf = prev + 64;                                    // [L][R]
   float* c_br = c_bf + a.L * R;                               // [L][R]
   float* c_bs = c_br + a.L * R;                               // [S]
@@ -121,7 +122,10 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
   for (int i = threadIdx.x; i < 256; i += 256) c_b2[i] = i < a.Cp ? a.b2[i] : 0.0f;
   if (threadIdx.x < 2 * R) c_iw[threadIdx.x] = a.init_w[threadIdx.x];
   if (threadIdx.x < R) c_ib[threadIdx.x] = a.init_b[threadIdx.x];
-  if (threadIdx.x < 64) prev[threadIdx.x] = 0.0f;
+  if (threadIdx.x < 64) {
+    const int ul = threadIdx.x & 31, u = u0 + ul;
+    prev[threadIdx.x] = (a.carry && ul < NU && u < a.B) ? a.carry[2 * u + (threadIdx.x >> 5)] : 0.0f;
+  }
   c_dec[threadIdx.x] = g16_mu_law_decode((int)threadIdx.x < a.Q ? (int)threadIdx.x : a.Q - 1, a.Q);
   __syncthreads();
 
@@ -130,7 +134,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
   const int lyr = lane < a.L ? lane : a.L - 1;
   const int depthv = a.dil[lyr] + 1;
   const int roffv = (int)a.ring_off[lyr];
-  int curv = 0;
+  int curv = a.t0 % depthv;                                   // (a resumed launch: the slot of absolute step t0)
   auto wrap = [](int x, int depth) { return x >= depth ? x - depth : x; };
 
   // the operands of layer l at the step whose write slots are curv + ahead: the delayed tap x_l[t - d] sits in slot
@@ -171,19 +175,20 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
   };
 
   Pre pa, pb;
-  for (int t = 0; t < a.nsteps; ++t) {
+  for (int j = 0; j < a.nsteps; ++j) {
+    const int t = a.t0 + j;   // absolute step (ring slots, conditioning frame, RNG); j indexes outputs and `forced`
     // (layer 0's operands were requested by the top layer of the step before: its ring slot is at least one step old)
-    if (t == 0) preload(0, 0, 0, pa);
+    if (j == 0) preload(0, 0, t, pa);
     // ---- input conv with RightShift (model.py:172-173): h0[t] = w[0] audio[t-2] + w[1] audio[t-1] + b; this wave's 16 channels
     float xs[NCB][4];                              // the wave's slice of the current layer input (as stored: rounded)
 #pragma unroll
     for (int c2 = 0; c2 < NCB; ++c2) {
       const int ug = u0 + 16 * c2 + col;
       float a1 = 0.0f, a2 = 0.0f;
-      if (ug < a.B) {
+      if (ug < a.B) {   // (prev[] starts as the carry: a forced launch's first two steps read it there, as generate_kernel)
         if (a.forced) {
-          if (t >= 1) a1 = a.forced[(size_t)ug * a.Tout + t - 1];
-          if (t >= 2) a2 = a.forced[(size_t)ug * a.Tout + t - 2];
+          a1 = (j >= 1) ? a.forced[(size_t)ug * a.Tout + j - 1] : prev[16 * c2 + col];
+          a2 = (j >= 2) ? a.forced[(size_t)ug * a.Tout + j - 2] : prev[32 + 16 * c2 + col];
         } else {
           a1 = prev[16 * c2 + col];
           a2 = prev[32 + 16 * c2 + col];
@@ -405,8 +410,8 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
           }
           smp = fminf(fmaxf(smp, -1.0f), 1.0f);
           if (u < a.B) {
-            a.audio_out[(size_t)u * a.Tout + t] = smp;
-            a.codes_out[(size_t)u * a.Tout + t] = sel;
+            a.audio_out[(size_t)u * a.Tout + j] = smp;
+            a.codes_out[(size_t)u * a.Tout + j] = sel;
           }
           prev[32 + ul] = prev[ul];
           prev[ul] = smp;
@@ -415,7 +420,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
       if (a.logits_out) {
         for (int i = threadIdx.x; i < NU * a.C; i += 256) {
           const int ul = i / a.C, c = i - ul * a.C;
-          if (u0 + ul < a.B) a.logits_out[((size_t)(u0 + ul) * a.Tout + t) * a.C + c] = lgl[ul * LGS + c];
+          if (u0 + ul < a.B) a.logits_out[((size_t)(u0 + ul) * a.Tout + j) * a.C + c] = lgl[ul * LGS + c];
         }
       }
       wg_barrier();
@@ -493,8 +498,8 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
         const int ul = NI * wave + lane, u = u0 + ul;
         const float smp = c_dec[cd];
         if (u < a.B) {
-          a.audio_out[(size_t)u * a.Tout + t] = smp;
-          a.codes_out[(size_t)u * a.Tout + t] = cd;
+          a.audio_out[(size_t)u * a.Tout + j] = smp;
+          a.codes_out[(size_t)u * a.Tout + j] = cd;
         }
         prev[32 + ul] = prev[ul];
         prev[ul] = smp;
@@ -504,7 +509,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
         for (int i = 0; i < NI; ++i) {
           const int u = u0 + NI * wave + i;
           if (u < a.B && 4 * lane < a.C) {
-            float* lo = a.logits_out + ((size_t)u * a.Tout + t) * a.C + 4 * lane;
+            float* lo = a.logits_out + ((size_t)u * a.Tout + j) * a.C + 4 * lane;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
               if (4 * lane + e < a.C) lo[e] = v[i][e];
@@ -513,6 +518,19 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
       }
     }
     wg_barrier();
+  }
+  // the carry for the next launch (the step's last barrier ordered prev): emitted samples, or forced ones where forced
+  if (a.carry && threadIdx.x < NU) {
+    const int ul = threadIdx.x, u = u0 + ul;
+    if (u < a.B) {
+      float c0 = prev[ul], c1 = prev[32 + ul];
+      if (a.forced) {
+        c0 = a.forced[(size_t)u * a.Tout + a.nsteps - 1];
+        if (a.nsteps >= 2) c1 = a.forced[(size_t)u * a.Tout + a.nsteps - 2];
+      }
+      a.carry[2 * u] = c0;
+      a.carry[2 * u + 1] = c1;
+    }
   }
 }
 
@@ -561,8 +579,11 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
                            const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float* logits_out,
                            const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
                            int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
-                           int32_t M, const void* cond, int32_t cond_frames, int32_t pool, int64_t cond_ld) {
+                           int32_t M, const void* cond, int32_t cond_frames, int32_t pool, int64_t cond_ld, int32_t t0,
+                           float* carry) {
   if (B == 0 || nsteps == 0) return 0;
+  if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate16: t0=%d", t0);
+  if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate16: a launch that resumes at t0=%d needs the carry", t0);
   if (!wl || !wh1 || !wh2 || !bias_f || !bias_r || !bs_sum || !b1 || !b2 || !init_w || !init_b || !ring || !audio_out ||
       !codes_out || !dilations)
     return set_error(SRWN_E_NULL, "generate16: null pointer");
@@ -579,10 +600,23 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
   a.logits_out = logits_out; a.forced = forced;
   a.B = B; a.Tout = Tout; a.nsteps = nsteps; a.L = nlayers; a.C = C; a.Cp = (C + 31) / 32 * 32; a.mode = mode; a.Q = C; a.seed = seed;
   a.M = M; a.cond = cond; a.cond_frames = cond_frames; a.pool = pool; a.cond_ld = cond_ld;
+  a.t0 = t0; a.carry = carry;
   if (R == 64 && S == 256) return generate16_launch<64, 256>(a, dilations, nlayers, B, cond != nullptr, M, stream);
   if (R == 64) return generate16_launch<64, 128>(a, dilations, nlayers, B, cond != nullptr, M, stream);
   if (S == 256) return generate16_launch<32, 256>(a, dilations, nlayers, B, cond != nullptr, M, stream);
   return generate16_launch<32, 128>(a, dilations, nlayers, B, cond != nullptr, M, stream);
+}
+
+extern "C" int srwn_generate16_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                      const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                      const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                      int32_t* codes_out, float* logits_out, const float* forced,
+                                      const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
+                                      int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
+                                      int32_t t0, float* carry) {
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, seed, stream, 0, nullptr, 1,
+                         1, 0, t0, carry);
 }
 
 extern "C" int srwn_generate16(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
@@ -591,13 +625,28 @@ extern "C" int srwn_generate16(const void* wl, const void* wh1, const void* wh2,
                                int32_t* codes_out, float* logits_out, const float* forced, const int32_t* dilations,
                                int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
                                int32_t C, int32_t mode, uint64_t seed, void* stream) {
-  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, seed, stream, 0, nullptr, 1,
-                         1, 0);
+  return srwn_generate16_resume(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                                logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, seed, stream, 0,
+                                nullptr);
 }
 
 // the same body for the conditioned mixture-of-logistics decoder (srwn_generate_mol's arguments; wh2 / b2 cover
 // ceil(4M/32)*32 rows)
+extern "C" int srwn_generate16_mol_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                          const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                          const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                          int32_t* codes_out, float* logits_out, const float* forced,
+                                          const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                          int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                                          int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                                          uint64_t seed, void* stream, int32_t t0, float* carry) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate16_mol: num_mixtures=%d (1..16)", num_mixtures);
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, seed, stream,
+                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, t0, carry);
+}
+
 extern "C" int srwn_generate16_mol(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
                                    const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                                    const float* init_w, const float* init_b, void* ring, float* audio_out,
@@ -605,9 +654,7 @@ extern "C" int srwn_generate16_mol(const void* wl, const void* wh1, const void* 
                                    const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
                                    int32_t R, int32_t S, int32_t num_mixtures, const void* cond, int32_t cond_frames,
                                    int32_t pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed, void* stream) {
-  if (num_mixtures < 1 || num_mixtures > 16)
-    return set_error(SRWN_E_SHAPE, "generate16_mol: num_mixtures=%d (1..16)", num_mixtures);
-  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, seed, stream,
-                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld);
+  return srwn_generate16_mol_resume(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out,
+                                    codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, num_mixtures,
+                                    cond, cond_frames, pool_stride, cond_ld, mode, seed, stream, 0, nullptr);
 }

@@ -92,6 +92,18 @@ class _Span:
         return False
 
 
+class GenerationState:
+    """One resumable generation run (WaveNetEngine.generation_state): the per-layer rings of the queue-cached generator,
+    the carry [B, 2] fp32 = (a[t-1], a[t-2]) the next step's input conv reads, the absolute step t of the next sample, the
+    seed of the samplers' counters, and for a conditioned decoder the encoding `cond`, its per-layer conditioning
+    `cond_all` [B*frames, L*R] and `limit` = frames * pool_stride (the last step it covers)."""
+
+    def __init__(self, batch, ring, carry, seed, cond=None, cond_all=None, frames=0, limit=None):
+        self.batch, self.ring, self.carry, self.seed = int(batch), ring, carry, int(seed)
+        self.cond, self.cond_all, self.frames, self.limit = cond, cond_all, int(frames), limit
+        self.t = 0
+
+
 CONTRASTIVE_LDS_FLOATS = 65536 // 4   # srwn_contrastive_head: rows*D + 2P floats in one workgroup (csrc/srwn_siamese.hip)
 
 
@@ -611,11 +623,13 @@ class WaveNetEngine:
             self.cond_in[:, :self.E].copy_(cond.reshape(self.B * self.frames, self.E))
 
     def forward(self, want_logits: bool = False, with_loss: bool = True, train: bool = True,
-                defer_loss: bool = False) -> Optional[torch.Tensor]:
+                defer_loss: bool = False, stack_only: bool = False) -> Optional[torch.Tensor]:
         """Runs the stack on the staged inputs; leaves loss in self.loss and dlogits for backward.
         Returns fp32 per-time-step logits [B,T,C] when want_logits.  train=False: forward only (no weight-gradient tiles
         are written; backward() refuses to follow such a pass).  defer_loss (the training step): the final sum of the loss
-        partials is left to the backward pass, where it is one more job of the skip / head reduction launch."""
+        partials is left to the backward pass, where it is one more job of the skip / head reduction launch.
+        stack_only (internal: priming a generation state): the input conv and the residual layers only -- xs holds every
+        layer's input afterwards -- no skip sum, no head, no loss."""
         B, T, N, L, R, S = self.B, self.T, self.N, self.L, self.R, self.S
         es = self.packed.element_size()
         v = self.view
@@ -632,6 +646,8 @@ class WaveNetEngine:
             self._cond_bias_to_input()
         with _Span(self, "fwd_layers"):
             self._stack_fwd(self.cond_all if self.E else None, wt=self._tiles_valid)
+        if stack_only:
+            return None
         with _Span(self, "skip_sum"):      # model.py:50-51 (bs_sum = the sum of the layers' skip biases: formed by repack())
             K.pw_linear(self._gate_out.data_ptr(), R, N * R, R, L * R, self.wptr(self.o_skip), self.bs_sum, self.r0, S, S,
                         N, pro=self._gate_pro, epi=K.EPI_RELU)
@@ -1296,6 +1312,149 @@ class WaveNetEngine:
                           *common[4:21], self.R, self.S, self.C, md, int(seed), st)
             else:
                 _lib.call("srwn_generate", *common, self.C, self.Kw, md, int(seed), K.abi_dtype(self.dt), st)
+        return audio, codes, logits
+
+    # ------------------------------------------------------------------------------------------
+    # resumable generation: streaming, chunks, prompts
+    # ------------------------------------------------------------------------------------------
+    def generation_state(self, batch: int, cond: Optional[torch.Tensor] = None, seed: int = 0) -> "GenerationState":
+        """A generation run of `batch` utterances that `generate_chunk` advances chunk by chunk and `prime` can start from a
+        prompt: the layer rings, the carry (the last two input samples, [B, 2] fp32), the absolute step t, the seed and,
+        for a conditioned decoder, the per-layer conditioning (`cond` = encoding_w_condition [B, frames, cond_channels]).
+        The generation weight images are gathered here: train between chunks and the run keeps the weights it started
+        with (make a new state to pick up new ones)."""
+        import ctypes as C
+        from . import _lib
+        if self.wavenet:
+            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
+                                      "the reference gate (canonical generation is not built)")
+        if self.o_gen is None or self.clip_head:
+            raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
+        B = int(batch)
+        if B < 1:
+            raise ValueError("generation_state: batch %d" % B)
+        cond_all, frames = None, 0
+        if self.mol and self.E:
+            if cond is None:
+                raise ValueError("this decoder is conditioned: pass cond [batch, frames, cond_channels]")
+            cond = cond.to(device=self.dev, dtype=torch.float32).contiguous()
+            frames = int(cond.shape[1]) if cond.dim() == 3 else 0
+            if cond.dim() != 3 or tuple(cond.shape) != (B, frames, self.E) or frames < 1:
+                raise ValueError("cond must be [batch, frames, %d]" % self.E)
+            cin = torch.zeros((B * frames, self.Ep), dtype=self.dt, device=self.dev)
+            cin[:, :self.E].copy_(cond.reshape(B * frames, self.E))
+            cond_all = torch.empty((B * frames, self.L * self.R), dtype=self.dt, device=self.dev)
+            K.pw_linear(cin.data_ptr(), self.Ep, 0, self.Ep, self.Ep, self.wptr(self.o_wc), self.view("BC").reshape(-1),
+                        cond_all, self.L * self.R, self.L * self.R, B * frames)          # model.py:180
+        elif self.mol:
+            if cond is not None:
+                raise ValueError("this decoder is not conditioned")
+        elif self.E or cond is not None:
+            raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
+                                      "decoder of the reference has the mixture-of-logistics head)")
+        self._repack_generation()
+        dl = (C.c_int32 * self.L)(*self.dil)
+        relems = int(_lib.load().srwn_generate_ring_elems(dl, self.L, self.R))
+        ring = torch.zeros(relems * ((B + 31) // 32), dtype=self.dt, device=self.dev)
+        carry = torch.zeros((B, 2), dtype=torch.float32, device=self.dev)
+        return GenerationState(B, ring, carry, int(seed), cond if frames else None, cond_all, frames,
+                               frames * self.cfg.pool_stride if frames else None)
+
+    def _prime_view(self, B: int, T: int) -> "WaveNetEngine":
+        """A forward-only (frozen) view of this stack at (B, T), kept for the next prompt of the same shape."""
+        v = getattr(self, "_gen_prime_view", None)
+        if v is None or (v.B, v.T) != (B, T):
+            self._gen_prime_view = None
+            v = WaveNetEngine(self.cfg, B, T, self.dev, share_from=self, frozen=True)
+            self._gen_prime_view = v
+        return v
+
+    def prime(self, state: "GenerationState", prompt: torch.Tensor) -> None:
+        """Continues `state` (at t = 0) from a prompt [B, P]: ONE parallel forward pass of the stack over the prompt
+        (rounded up to a whole conditioning frame; the causal convs keep the padding out of every x_l[t < P]), its stored
+        layer inputs into the rings (srwn_generate_ring_fill), the carry from the prompt's last two samples, t = P.  The
+        next chunk's first sample is the one after the prompt."""
+        import ctypes as C
+        from . import _lib
+        prompt = torch.as_tensor(prompt).to(device=self.dev, dtype=torch.float32)
+        if prompt.dim() != 2 or prompt.shape[0] != state.batch:
+            raise ValueError("prompt must be [batch=%d, P], got %s" % (state.batch, tuple(prompt.shape)))
+        if state.t != 0:
+            raise ValueError("prime: the state is at step %d; a prompt starts a run (t = 0)" % state.t)
+        B, P = state.batch, int(prompt.shape[1])
+        if state.limit is not None and P > state.limit:
+            raise ValueError("prompt of %d samples exceeds frames * pool_stride = %d" % (P, state.limit))
+        if P == 0:
+            return
+        pool = self.cfg.pool_stride if self.E else 1
+        P_pad = -(-P // pool) * pool
+        view = self._prime_view(B, P_pad)
+        audio = torch.zeros((B, P_pad), dtype=torch.float32, device=self.dev)
+        audio[:, :P].copy_(prompt)
+        view.set_inputs(audio, None, state.cond[:, :P_pad // pool] if self.E else None)
+        view.forward(want_logits=False, with_loss=False, train=False, stack_only=True)
+        dl = (C.c_int32 * self.L)(*self.dil)
+        _lib.call("srwn_generate_ring_fill", view.xs.data_ptr(), B * P_pad * self.R, P_pad, P, dl, self.L, B, self.R,
+                  state.ring.data_ptr(), K.abi_dtype(self.dt), torch.cuda.current_stream().cuda_stream)
+        state.carry[:, 0].copy_(prompt[:, P - 1])
+        if P >= 2:
+            state.carry[:, 1].copy_(prompt[:, P - 2])
+        state.t = P
+
+    def generate_chunk(self, state: "GenerationState", nsteps: int, mode: str = "sample",
+                       forced: Optional[torch.Tensor] = None, want_logits: bool = False):
+        """The next `nsteps` samples of the run `state` (see `generate`: the same kernels, chosen by the same rule, and the
+        same outputs): (audio [B, nsteps] f32, codes [B, nsteps] i32, logits [B, nsteps, C] f32 or None); advances
+        state.t.  Chunks of any lengths give the bits of one `generate` call over their sum.  `forced` [B, nsteps]:
+        teacher forcing for this chunk only."""
+        import ctypes as C
+        import os as _os
+        from . import _lib
+        B, nsteps = state.batch, int(nsteps)
+        if nsteps < 0:
+            raise ValueError("generate_chunk: nsteps %d" % nsteps)
+        if state.limit is not None and state.t + nsteps > state.limit:
+            raise ValueError("generate_chunk: steps %d..%d run past the encoding's frames * pool_stride = %d"
+                             % (state.t, state.t + nsteps, state.limit))
+        audio = torch.zeros((B, nsteps), dtype=torch.float32, device=self.dev)
+        codes = torch.zeros((B, nsteps), dtype=torch.int32, device=self.dev)
+        logits = torch.zeros((B, nsteps, self.C), dtype=torch.float32, device=self.dev) if want_logits else None
+        fp = None
+        if forced is not None:
+            forced = torch.as_tensor(forced).to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(forced.shape) != (B, nsteps):
+                raise ValueError("forced must be [batch, nsteps]")
+            fp = forced.data_ptr()
+        if nsteps == 0:
+            return audio, codes, logits
+        md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
+        st = torch.cuda.current_stream().cuda_stream
+        dl = (C.c_int32 * self.L)(*self.dil)
+        v = self.view
+        common = (v("BF").data_ptr(), v("BR").data_ptr(), self.bs_sum.data_ptr(), v("head_b1").data_ptr(),
+                  v("head_b2").data_ptr(), v("init_w").data_ptr(), v("init_b").data_ptr(), state.ring.data_ptr(),
+                  audio.data_ptr(), codes.data_ptr(), None if logits is None else logits.data_ptr(), fp, dl, self.L, B,
+                  nsteps, nsteps, self.R, self.S)
+        thr = (self.wptr(self.o_gen), self.wptr(self.o_skip_gen), self.wptr(self.o_w1), self.wptr(self.o_w2))
+        resume = (state.t, state.carry.data_ptr())
+        g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
+        if g16:
+            lat = (self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2))
+        if self.mol:
+            cptr = None if state.cond_all is None else state.cond_all.data_ptr()
+            frames = state.frames if state.cond_all is not None else 1
+            if g16:
+                _lib.call("srwn_generate16_mol_resume", *lat, *common, self.C // 4, cptr, frames, self.cfg.pool_stride,
+                          self.L * self.R, md, int(state.seed), st, *resume)
+            else:
+                _lib.call("srwn_generate_mol_resume", *thr, *common, self.Kw, self.C // 4, cptr, frames,
+                          self.cfg.pool_stride, self.L * self.R, md, int(state.seed), K.abi_dtype(self.dt), st, *resume)
+        elif g16:
+            _lib.call("srwn_generate16_resume", *lat, *common, self.C, md, int(state.seed), st, *resume)
+        else:
+            _lib.call("srwn_generate_resume", *thr, *common, self.C, self.Kw, md, int(state.seed), K.abi_dtype(self.dt),
+                      st, *resume)
+        state.t += nsteps
         return audio, codes, logits
 
     def capture_graphs(self):

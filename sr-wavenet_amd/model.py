@@ -292,11 +292,22 @@ class WaveNetTeacher(_EngineOwner):
         return np.float32(eng.loss.item())
 
     def generate(self, batch_size, num_samples, mode="sample", seed=0, forced=None, return_logits=False,
-                 encoding=None, conditions=None):
+                 encoding=None, conditions=None, prompt=None):
         """Queue-cached autoregressive generation (the O(T L) replacement of the reference's O(T^2 L)
         loop, teacher.py:140-171): returns audio [B, num_samples] float32, or (audio, codes, logits) when
         return_logits.  `forced` [B, num_samples] = teacher forcing.  The softmax teacher emits mu-law decoded
-        samples; the mixture-of-logistics teacher (optionally conditioned on `encoding`) emits logistic samples."""
+        samples; the mixture-of-logistics teacher (optionally conditioned on `encoding`) emits logistic samples.
+        `prompt` [B, P]: the num_samples that FOLLOW the prompt (one parallel pass over it primes the generator)."""
+        if prompt is not None:
+            p = self._check_generation(batch_size, prompt)
+            eng = self._primary or self._engine(1, self._default_length)
+            st = eng.generation_state(int(batch_size), self._generation_cond(encoding, conditions), seed)
+            eng.prime(st, p)
+            f = None if forced is None else torch.as_tensor(np.asarray(forced, dtype=np.float32), device="cuda")
+            a, c, lg = eng.generate_chunk(st, int(num_samples), mode=mode, forced=f, want_logits=return_logits)
+            if return_logits:
+                return a.cpu().numpy(), c.cpu().numpy(), lg.cpu().numpy()
+            return a.cpu().numpy()
         if self.head == "softmax" and self.use_encoding:
             raise NotImplementedError("generation: the conditioned softmax teacher is not built")
         if self.gate_mode == "wavenet":
@@ -318,6 +329,66 @@ class WaveNetTeacher(_EngineOwner):
         if return_logits:
             return a.cpu().numpy(), c.cpu().numpy(), lg.cpu().numpy()
         return a.cpu().numpy()
+
+    def stream(self, batch_size, chunk_size, mode="sample", seed=0, prompt=None, encoding=None, conditions=None,
+               max_samples=None):
+        """Real-time generation: an iterator of NumPy [B, chunk_size] blocks (the last one shorter where max_samples or
+        the encoding ends), each back as soon as its samples exist.  The blocks put together are generate(..., seed) bit
+        for bit.  prompt [B, P]: continue from it.  A conditioned decoder stops where the encoding's frames run out
+        (frames * pool_stride samples in all, the prompt included); otherwise the stream ends only at max_samples."""
+        p = self._check_generation(batch_size, prompt)
+        if int(chunk_size) < 1:
+            raise ValueError("chunk_size must be >= 1")
+        eng = self._primary or self._engine(1, self._default_length)
+        st = eng.generation_state(int(batch_size), self._generation_cond(encoding, conditions), seed)
+        if p is not None:
+            eng.prime(st, p)
+        return _stream_chunks(eng, st, int(chunk_size), mode, max_samples)
+
+    def _check_generation(self, batch_size, prompt):
+        """What generation refuses before any device work; returns the prompt as float32 [B, P] (or None)."""
+        if self.head == "softmax" and self.use_encoding:
+            raise NotImplementedError("generation: the conditioned softmax teacher is not built")
+        if self.gate_mode == "wavenet":
+            raise NotImplementedError("generation: gate_mode 'wavenet' is trained only (the generation kernels implement "
+                                      "the reference gate)")
+        return _check_prompt(batch_size, prompt)
+
+    def _generation_cond(self, encoding, conditions):
+        if not self.use_encoding:
+            return None
+        if encoding is None:
+            raise ValueError("this teacher was built with use_encoding=True; pass encoding [B, frames, latent]")
+        cond = torch.as_tensor(np.asarray(encoding, dtype=np.float32), device="cuda")
+        if self.condition_size > 0:
+            c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
+            cond = torch.cat([cond, c[:, None, :].expand(-1, cond.shape[1], -1)], dim=2)
+        return cond.contiguous()
+
+
+def _check_prompt(batch_size, prompt):
+    if prompt is None:
+        return None
+    p = np.asarray(prompt, dtype=np.float32)
+    if p.ndim != 2 or p.shape[0] != int(batch_size):
+        raise ValueError("prompt must be [batch=%d, P], got shape %s" % (int(batch_size), p.shape))
+    return p
+
+
+def _stream_chunks(eng, st, chunk, mode, max_samples):
+    """The blocks of a primed generation state (WaveNetEngine.generate_chunk) until max_samples or the encoding ends."""
+    made = 0
+    while True:
+        n = chunk
+        if max_samples is not None:
+            n = min(n, int(max_samples) - made)
+        if st.limit is not None:
+            n = min(n, st.limit - st.t)
+        if n <= 0:
+            return
+        a, _, _ = eng.generate_chunk(st, n, mode=mode)
+        made += n
+        yield a.cpu().numpy()
 
 
 class WaveNetAutoEncoder(object):
@@ -469,10 +540,19 @@ class WaveNetAutoEncoder(object):
         self._put_encoding(eng, encoding)
         return eng.dec.forward(want_logits=True, with_loss=False).cpu().numpy()
 
-    def generate(self, encoding, conditions=None, num_samples=None, mode="sample", seed=0):
+    def generate(self, encoding, conditions=None, num_samples=None, mode="sample", seed=0, prompt=None):
         """Queue-cached autoregressive sampling from the decoder given an encoding (the O(T L) replacement of the
         reference's sample-by-sample loop over ``reconstruct_with_encoding``, generator.py:150-170 /
-        teacher.py:140-171): audio [B, num_samples] in [-1, 1]."""
+        teacher.py:140-171): audio [B, num_samples] in [-1, 1].  prompt [B, P]: the num_samples (default: the rest of
+        the encoding) that follow the prompt's P samples."""
+        if prompt is not None:
+            eng, st, p = self._prompted_state(encoding, conditions, seed, prompt)
+            rest = st.limit - p.shape[1]
+            T = int(num_samples) if num_samples is not None else rest
+            if T > rest:
+                raise ValueError("prompt %d + num_samples %d exceeds frames * pool_stride = %d" % (p.shape[1], T, st.limit))
+            a, _, _ = eng.dec.generate_chunk(st, T, mode=mode)
+            return a.cpu().numpy()
         e = torch.as_tensor(np.asarray(encoding, dtype=np.float32), device="cuda")
         if e.ndim != 3 or e.shape[2] != self.latent_channels:
             raise ValueError("encoding must be [batch, frames, latent_channels]")
@@ -488,6 +568,35 @@ class WaveNetAutoEncoder(object):
         eng = self._eng or self._engine(B, frames * self.pool_stride)
         a, _, _ = eng.dec.generate(T, mode=mode, seed=seed, batch=B, cond=e.contiguous())
         return a.cpu().numpy()
+
+    def stream(self, encoding, conditions=None, chunk_size=160, mode="sample", seed=0, prompt=None, max_samples=None):
+        """Real-time decoding: an iterator of NumPy [B, chunk_size] blocks that ends where the encoding's frames run out
+        (or at max_samples); put together they are generate(encoding, ..., seed=seed) bit for bit.  prompt [B, P]: the
+        samples after it."""
+        if int(chunk_size) < 1:
+            raise ValueError("chunk_size must be >= 1")
+        eng, st, _ = self._prompted_state(encoding, conditions, seed, prompt)
+        return _stream_chunks(eng.dec, st, int(chunk_size), mode, max_samples)
+
+    def _prompted_state(self, encoding, conditions, seed, prompt):
+        enc = np.asarray(encoding, dtype=np.float32)
+        if enc.ndim != 3 or enc.shape[2] != self.latent_channels:
+            raise ValueError("encoding must be [batch, frames, latent_channels]")
+        B, frames = int(enc.shape[0]), int(enc.shape[1])
+        p = _check_prompt(B, prompt)
+        if p is not None and p.shape[1] > frames * self.pool_stride:
+            raise ValueError("prompt of %d samples exceeds frames * pool_stride = %d" % (p.shape[1], frames * self.pool_stride))
+        e = torch.as_tensor(enc, device="cuda")
+        if self.condition_size > 0:
+            if conditions is None:
+                raise ValueError("this auto-encoder was built with condition_size > 0; pass conditions")
+            c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
+            e = torch.cat([e, c[:, None, :].expand(-1, frames, -1)], dim=2)               # model.py:161-167
+        eng = self._eng or self._engine(B, frames * self.pool_stride)
+        st = eng.dec.generation_state(B, e.contiguous(), seed)
+        if p is not None:
+            eng.dec.prime(st, p)
+        return eng, st, p
 
     def mu_law(self, inputs, conditions=None):
         raise AttributeError("WaveNetAutoEncoder.mu_law reads self.targets, which the reference never defines "
