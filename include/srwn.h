@@ -150,10 +150,12 @@ int srwn_residual_group_bwd(const void* g_top, void* g_out, void* df_out, const 
  * sqrt(.5) on the residual pair.  Halo (sum(dilations)/gcd) <= 31.
  * part16 != 0 (dtype SRWN_BF16 only): part_f / part_r are written in the COMPUTE type instead of fp32 -- the same number
  * of elements per (layer, slab), as 16 x 16 blocks in lane order (layout SRWN_PARTIALS_BLK16 of SrwnReduceJob below):
- * half the bytes both ways for one more bf16 rounding per partial sum (the 256 x 30 partials of config 2 are 0.38 GB per
- * step in fp32, written here and read back by the reduction; measured cost in accuracy: DESIGN.md 4c).  The two bias
- * partials stay fp32.
- * ic_audio != NULL (the stack's FIRST group, dcs given; bf16 mode: with part16): the launch also leaves the partial sums
+ * half the bytes both ways (the 256 x 30 partials of config 2 are 0.38 GB per step in fp32, written here and read back by
+ * the reduction) for one more bf16 rounding per segment a workgroup runs: a later segment re-reads the block, adds its
+ * fp32 sum and rounds again, so k segments per workgroup round the running sum k times (measured cost in accuracy, by k:
+ * DESIGN.md 4c; the engine passes fp32 slabs for a group with more segments than workgroups).  The two bias partials
+ * stay fp32.
+ * ic_audio != NULL (the stack's FIRST group, dcs given; with fp32 slabs or part16 blocks): the launch also leaves the partial sums
  * of the input conv's kernel and bias gradient (model.py:40; what srwn_init_conv_wgrad's first stage forms from g_out in a
  * launch of its own) -- ic_partials[slab][3 R] = [sum_t audio[t-1-ic_shift] G_0[t,:] | sum_t audio[t-ic_shift] G_0[t,:] |
  * sum_t G_0[t,:]] over rows the workgroup's segments own, fp32, 8 / (R/16) slabs per workgroup (the launch's waves split
@@ -460,7 +462,7 @@ int srwn_wgrad_layers(const void* x, const void* z, const void* df, const void* 
  * partials[slab][nlayers*64][256], bias_partials[slab][256] (column sums of d; may be NULL); nslabs from
  * srwn_wgrad_skip_wt_slabs.  part16 != 0: `partials` holds the same [nlayers*64, 256] matrix per slab in bf16, as 16 x 16
  * blocks in lane order (SRWN_PARTIALS_BLK16 with 256 columns: half the partial bytes both ways, one more bf16 rounding
- * per partial sum).  bf16, R = 64, S = 256 (csrc/srwn_wgradt.hip); other shapes: srwn_wgrad_wide on z. */
+ * per partial sum -- one only: a slab's segments are summed in registers before its single store).  bf16, R = 64, S = 256 (csrc/srwn_wgradt.hip); other shapes: srwn_wgrad_wide on z. */
 int32_t srwn_wgrad_skip_wt_slabs(const int32_t* st, const int32_t* seg_rows, int32_t nlayers, int32_t T);
 int srwn_wgrad_skip_wt(const void* cT, int64_t wt_layer_stride, const int32_t* st, const int32_t* seg_rows,
                        int32_t nlayers, const void* d, int64_t d_row_stride, void* partials, float* bias_partials,

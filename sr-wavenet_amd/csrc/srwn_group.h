@@ -3,6 +3,7 @@
 // gfx950 (MI355X) only.  Segment geometry and time decomposition: header of srwn_group.hip.
 #pragma once
 #include <cstdint>
+#include <cstdlib>
 #include "srwn_common.h"
 
 namespace srwn {
@@ -188,6 +189,16 @@ inline int num_cus() {
       cus = 256;
   }
   return cus;
+}
+
+// Workgroups of the group kernels' launches (and their partial slabs): one per CU, or fewer under the test hook
+// SRWN_GROUP_GRID = cap (> 0), so that each workgroup walks several segments with the segment geometry unchanged.  Read on
+// every call (tests set it per case); unset or <= 0: num_cus().  choose_segments and the cost model stay on num_cus().
+inline int group_grid() {
+  const int cus = num_cus();
+  const char* e = getenv("SRWN_GROUP_GRID");
+  const long cap = e ? strtol(e, nullptr, 10) : 0;
+  return (cap > 0 && cap < cus) ? (int)cap : cus;
 }
 
 // common stride, sub-dilations, halo of a run of layers

@@ -1306,7 +1306,8 @@ int launch_group_fwd(GroupFwdArgs& a, bool cond, int seg_rows, hipStream_t st) {
   if (nseg > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "residual_group_fwd: too many segments");
   a.nseg = (int)nseg;
   const size_t sh = fixed + (size_t)a.NT * 32 * row_bytes;
-  long long blocks = nseg < num_cus() ? nseg : num_cus();
+  const int grid_cap = group_grid();
+  long long blocks = nseg < grid_cap ? nseg : grid_cap;
   dim3 grid((unsigned)blocks), block(64 * NWV);
 #define SRWN_GF(C)                                                                                              \
   {                                                                                                             \
@@ -1342,7 +1343,8 @@ int launch_group_bwd(GroupBwdArgs& a, int seg_rows, hipStream_t st) {
   if (nseg > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "residual_group_bwd: too many segments");
   a.nseg = (int)nseg;
   const size_t sh = fixed + (size_t)a.NT * 32 * row_bytes;
-  long long blocks = nseg < num_cus() ? nseg : num_cus();
+  const int grid_cap = group_grid();
+  long long blocks = nseg < grid_cap ? nseg : grid_cap;
   if (WT) {
     if (a.W != seg_rows) return set_error(SRWN_E_SHAPE, "residual_group_bwd_wt: seg_rows %d does not fit (use srwn_group_wt_geometry)", seg_rows);
     a.KT = (a.W + 31) / 32;
@@ -1361,8 +1363,8 @@ int launch_group_bwd(GroupBwdArgs& a, int seg_rows, hipStream_t st) {
     }                                                                                                           \
     if constexpr (WT && D) {                                                                                     \
       if (a.ic_audio) {                                                                                          \
-        if (sizeof(T) == 2 && !a.part16) return set_error(SRWN_E_UNSUPPORTED, "residual_group_bwd_wt: the input conv gradient goes with bf16 partial blocks (part16) in bf16 mode"); \
-        kfn = two ? group_bwd_kernel<T, RT, D, MT2, NWB, NWV, WT, false, sizeof(T) == 2, true> : group_bwd_kernel<T, RT, D, MAXT, NWB, NWV, WT, false, sizeof(T) == 2, true>; \
+        if (a.part16) kfn = two ? group_bwd_kernel<T, RT, D, MT2, NWB, NWV, WT, false, sizeof(T) == 2, true> : group_bwd_kernel<T, RT, D, MAXT, NWB, NWV, WT, false, sizeof(T) == 2, true>; \
+        else kfn = two ? group_bwd_kernel<T, RT, D, MT2, NWB, NWV, WT, false, false, true> : group_bwd_kernel<T, RT, D, MAXT, NWB, NWV, WT, false, false, true>; \
       }                                                                                                          \
     } else {                                                                                                     \
       if (a.ic_audio) return set_error(SRWN_E_UNSUPPORTED, "residual_group_bwd_wt: the input conv gradient is built for stacks with a skip path"); \
@@ -1638,7 +1640,8 @@ extern "C" int srwn_group_wt_geometry(const int32_t* dilations, int32_t nlayers,
   if (seg_rows) *seg_rows = W;
   if (tiles_per_seg) *tiles_per_seg = KT;
   if (elems_per_layer) *elems_per_layer = (int64_t)nseg * KT * R * 32;
-  if (nslabs) *nslabs = (int32_t)(nseg < num_cus() ? nseg : num_cus());
+  const int grid_cap = group_grid();
+  if (nslabs) *nslabs = (int32_t)(nseg < grid_cap ? nseg : grid_cap);
   return 0;
 }
 

@@ -296,7 +296,7 @@ extern "C" int32_t srwn_wgrad_skip_wt_slabs(const int32_t* st, const int32_t* se
   WtBlk blk[kMaxBlk];
   const int nb = plan_blocks(st, seg_rows, nlayers, T, blk);
   if (nb < 1) return 0;
-  const int s = num_cus() / nb;
+  const int s = group_grid() / nb;
   return s < 1 ? 1 : s;
 }
 

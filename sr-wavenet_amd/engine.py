@@ -510,6 +510,7 @@ class WaveNetEngine:
             self.xTs = z(L, wt_elems)
             self.cTs = z(L, wt_elems)
             self.nslabs = max(g[3] for g in geo)
+            self.wt_segs = [(g[2] // (g[1] * R * 32), g[3]) for g in geo]      # per group: (segments, workgroups)
             # per layer: the stride and segment length of its group (what fixes the positions its tiles hold)
             self.wt_layer_st = [math.gcd(*self.dil[l0:l1]) for l0, l1 in self.groups for _ in range(l0, l1)]
             self.wt_layer_seg = [self.wt_seg_rows[i] for i, (l0, l1) in enumerate(self.groups) for _ in range(l0, l1)]
@@ -524,12 +525,22 @@ class WaveNetEngine:
         # residual 1x1 weight gradients are stored in the compute type (16 x 16 blocks in lane order) instead of fp32 --
         # 256 workgroups x 30 layers x 48 KB = 0.38 GB per step written by the backward group kernels and read back by the
         # reduction, halved, for one more bf16 rounding per partial (measured: +1.3e-4 .. 5.7e-4 relative L2 on those
-        # gradients, whose bf16-mode error against the exact-fp32 mode is 7e-3: DESIGN.md 4c)
-        self.part16 = (self.fused_wt and self.dt == torch.bfloat16 and _os.environ.get("SRWN_PART16", "1") != "0")
+        # gradients, whose bf16-mode error against the exact-fp32 mode is 7e-3: DESIGN.md 4c).
+        # ... but only in the groups whose workgroups run ONE segment each: on every later segment a workgroup re-reads its
+        # bf16 block, adds the segment's fp32 sum and rounds again (k segments per workgroup: k roundings of the running
+        # sum; measured 1.9e-3 at k = 1 growing to 3.9e-3 at 8 and 7.0e-3 at 32).  A group with more segments than
+        # workgroups (e.g. 16 x 16000 clips per GPU) keeps fp32 slabs.  SRWN_PART16=2: bf16 blocks in every group
+        # (measurement: tests/test_gpu_multiseg.py)
+        p16env = _os.environ.get("SRWN_PART16", "1")
+        self.part16 = (self.fused_wt and self.dt == torch.bfloat16 and p16env != "0")
+        self.group_p16 = [self.part16 and (nseg <= nwg or p16env == "2") for nseg, nwg in self.wt_segs] if self.fused_wt else []
         if self.use_wl:
             ns = self.nslabs
-            pdt = torch.bfloat16 if self.part16 else torch.float32
-            self.pl_f = z(L * ns * 2 * R * R, dt=pdt); self.pl_r = z(L * ns * R * R, dt=pdt)
+            mk = lambda dt: (z(L * ns * 2 * R * R, dt=dt), z(L * ns * R * R, dt=dt))
+            pl16 = mk(torch.bfloat16) if any(self.group_p16) else None
+            pl32 = mk(torch.float32) if not (self.group_p16 and all(self.group_p16)) else None
+            self.pl_f, self.pl_r = pl16 or pl32      # the partials of the engine's mode; fp32 slabs where no group keeps blocks
+            self.pl_f32, self.pl_r32 = pl32 or (None, None)      # (fp32 slabs of the groups that fall back)
             self.pl_bf = z(L * ns * R, dt=torch.float32); self.pl_br = z(L * ns * R, dt=torch.float32)
         from . import _lib
         # the input conv's weight-gradient partials: srwn_init_conv_wgrad's stage-1 slabs, or -- default path, unconditioned
@@ -953,12 +964,14 @@ class WaveNetEngine:
             sec = self.sections
             self._ic_job = (self.ic_ws, ns * (8 // (R // 16)), (self.Kw + 1) * R, 1, True, 1.0,
                             self.grads.data_ptr() + 4 * sec["init_w"].offset, 0)
+        p16 = self.group_p16[self.groups.index((l0, l1))]
+        pl_f, pl_r = (self.pl_f, self.pl_r) if p16 or not self.part16 else (self.pl_f32, self.pl_r32)
         with _Span(self, "group_bwd_wt"):
             K.residual_group_bwd_wt(g_top, self.gs[l0:l1], self.zs[l0:l1], None if flow else self.dcs[l0:l1],
                                     self.xTs[l0:l1], self.cTs[l0:l1],
                                     [self.wptr(self.o_convT[l]) for l in range(l0, l1)],
                                     [self.wptr(self.o_resT[l]) for l in range(l0, l1)], self.dil[l0:l1],
-                                    self.pl_f[l0 * ns * 2 * R * R:], self.pl_r[l0 * ns * R * R:],
+                                    pl_f[l0 * ns * 2 * R * R:], pl_r[l0 * ns * R * R:],
                                     self.pl_bf[l0 * ns * R:], self.pl_br[l0 * ns * R:], ns,
                                     self.wt_seg_rows[self.groups.index((l0, l1))], self.Kw, write_all_g=bool(self.E), ic=ic)
 
@@ -1047,11 +1060,23 @@ class WaveNetEngine:
         NR = N * R
         xs_p, dfs_p, gs_p = self.xs.data_ptr(), self.dfs.data_ptr(), self.gs.data_ptr()
         if self.use_wl:
-            blk = (R,) if self.part16 else ()      # (bf16 partial blocks in lane order: SRWN_PARTIALS_BLK16, R columns)
-            jobs = [(self.pl_f, ns, Kw * R * R, L, True, 1.0, gp + 4 * sec["WF"].offset, Kw * R * R) + blk,
-                    (self.pl_bf, ns, R, L, True, 1.0, gp + 4 * sec["BF"].offset, R),
-                    (self.pl_r, ns, R * R, L, True, SQRT_HALF, gp + 4 * sec["WR"].offset, R * R) + blk,
-                    (self.pl_br, ns, R, L, True, SQRT_HALF, gp + 4 * sec["BR"].offset, R)]
+            # runs of layers whose groups keep their partials in one format (one run unless a group fell back to fp32)
+            runs = []
+            for (l0, l1), p16 in zip(self.groups, self.group_p16) if self.group_p16 else [((0, L), False)]:
+                if runs and runs[-1][2] == p16:
+                    runs[-1][1] = l1
+                else:
+                    runs.append([l0, l1, p16])
+            jf, jr = [], []
+            for l0, l1, p16 in runs:
+                pl_f, pl_r = (self.pl_f, self.pl_r) if p16 or not self.part16 else (self.pl_f32, self.pl_r32)
+                blk = (R,) if p16 else ()      # (bf16 partial blocks in lane order: SRWN_PARTIALS_BLK16, R columns)
+                jf.append((pl_f[l0 * ns * Kw * R * R:], ns, Kw * R * R, l1 - l0, True, 1.0,
+                           gp + 4 * (sec["WF"].offset + l0 * Kw * R * R), Kw * R * R) + blk)
+                jr.append((pl_r[l0 * ns * R * R:], ns, R * R, l1 - l0, True, SQRT_HALF,
+                           gp + 4 * (sec["WR"].offset + l0 * R * R), R * R) + blk)
+            jobs = jf + [(self.pl_bf, ns, R, L, True, 1.0, gp + 4 * sec["BF"].offset, R)] + jr + [
+                (self.pl_br, ns, R, L, True, SQRT_HALF, gp + 4 * sec["BR"].offset, R)]
             if self._ic_job is not None:      # the input conv's kernel + bias gradient (init_w | init_b are adjacent)
                 jobs.append(self._ic_job)
                 self._ic_job = None

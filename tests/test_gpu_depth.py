@@ -91,19 +91,26 @@ def _assert_bf16(errs, logits_tol, loss_tol, grad_tol):
     assert worst[0] < grad_tol, worst
 
 
+CONFIG2_SHAPE = (2, 4300, 64, 256, 256)      # B, T, R, S, C of the config-2 depth case
+
+
+def _config2_case():
+    """Parameters, inputs and the (cached) oracle of the config-2 depth case: 3 x [1..512], 2 clips of 4300 samples."""
+    B, T, R, S, C = CONFIG2_SHAPE
+    sp = O.init_stack_params(3, DIL30, 2, R, S, C, bias_scale=0.05)
+    audio = O.synthetic_audio(B, T, seed=4).astype(np.float64)
+    codes = O.mu_law_encode(audio.astype(np.float32), C).astype(np.int64)
+    return sp, audio, codes, _oracle_cached("config2", sp, audio, codes)
+
+
 @pytest.mark.parametrize("fuse", ["1", "0"])
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
 def test_config2_depth_and_dilations_vs_oracle(monkeypatch, dt, fuse):
     """30 layers, 3 x [1..512], 64 residual / 256 skip channels, 256-way softmax; B = 2 clips of 4300 samples (the
     receptive field is 3071).  Both launch structures: multi-layer kernels (default) and one launch per layer."""
     monkeypatch.setenv("SRWN_FUSE", fuse)
-    B, T, R, S, C = 2, 4300, 64, 256, 256
-    sp = O.init_stack_params(3, DIL30, 2, R, S, C, bias_scale=0.05)
-    rng = np.random.default_rng(3)
-    audio = O.synthetic_audio(B, T, seed=4).astype(np.float64)
-    codes = O.mu_law_encode(audio.astype(np.float32), C).astype(np.int64)
-    logits, loss, grads = _oracle_cached("config2", sp, audio, codes)
-    eng = _engine(sp, DIL30, B, T, R, S, C, dt)
+    sp, audio, codes, (logits, loss, grads) = _config2_case()
+    eng = _engine(sp, DIL30, *CONFIG2_SHAPE, dt)
     assert eng.fused_bwd == (fuse == "1")
     eng.set_inputs(dev(audio), dev(codes, torch.int32))
     errs = _check(eng, logits, loss, grads, dt)

@@ -18,13 +18,15 @@ pytestmark = pytest.mark.gpu
 WORKER = os.path.join(ROOT, "tests", "dp_worker.py")
 
 
-def _run(mode, world, tmp_path, tag, buckets, port, backend="gloo", force_dist=False):
+def _run(mode, world, tmp_path, tag, buckets, port, backend="gloo", force_dist=False, part16=None):
     outs, procs = [], []
     for r in range(world):
         out = str(tmp_path / ("%s_%s_w%d_r%d.pt" % (mode, tag, world, r)))
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), SRWN_DIST_BACKEND=backend, SRWN_BUCKETS=buckets,
                    HSA_ENABLE_IPC_MODE_LEGACY="0")
+        if part16 is not None:
+            env["SRWN_PART16"] = part16
         env.pop("SRWN_FORCE_DIST", None)
         if force_dist:
             env["SRWN_FORCE_DIST"] = "1"
@@ -45,21 +47,26 @@ def _run(mode, world, tmp_path, tag, buckets, port, backend="gloo", force_dist=F
     return [torch.load(o, weights_only=True) for o in outs]
 
 
-@pytest.mark.parametrize("mode,buckets", [("softmax", "0"), ("softmax", "1"), ("mol", "1"), ("student", "0"), ("deep", "1"),
-                                          ("pooled", "0"), ("contrastive", "0")])
-def test_two_ranks_equal_one_process_on_the_global_batch(tmp_path, mode, buckets):
+@pytest.mark.parametrize("mode,buckets,part16", [
+    pytest.param("softmax", "0", None, id="softmax-0"), pytest.param("softmax", "1", None, id="softmax-1"),
+    pytest.param("mol", "1", None, id="mol-1"), pytest.param("student", "0", None, id="student-0"),
+    pytest.param("deep", "1", "1", id="deep-1"), pytest.param("deep", "1", "0", id="deep-1-part16_0"),
+    pytest.param("pooled", "0", None, id="pooled-0"), pytest.param("contrastive", "0", None, id="contrastive-0")])
+def test_two_ranks_equal_one_process_on_the_global_batch(tmp_path, mode, buckets, part16):
     """"deep": BASELINE config 3's stack and dtype (30 layers, bf16) with two ranks through the schedule the scaling bench
     replays: backward cut at layer 10, first bucket all-reduced beside the lower part, three hipGraphs.  The shards are
     whole clips, every kernel works clip by clip, so even in bf16 two ranks and one process form the same per-clip
-    gradients: only the order of the fp32 sums differs.
+    gradients: only the order of the fp32 sums differs -- with fp32 partial slabs (SRWN_PART16=0).  The default bf16
+    partial blocks (SRWN_PART16=1) round each workgroup's partial sum, and which rows meet in one partial differs between
+    a rank's half batch and the whole one, so there the parameter bound below is looser.
     "pooled" / "contrastive": the clip-level heads (class WaveNet, class SiameseWaveNet) write their head_w2 / head_b2
     gradients during forward, outside the backward chain the buckets follow; those must be all-reduced too.  A
     contrastive rank holds its own pairs (its left clips, then their right partners).  (The engine keeps one bucket for
     the clip-level heads.)"""
     port = 29600 + (os.getpid() % 200) + {"softmax": 0, "mol": 1, "student": 2, "deep": 3, "pooled": 4,
-                                          "contrastive": 5}[mode] * 3 + int(buckets)
-    ref = _run(mode, 1, tmp_path, "ref", "0", port)[0]
-    r0, r1 = _run(mode, 2, tmp_path, "dp" + buckets, buckets, port + 400)
+                                          "contrastive": 5}[mode] * 3 + int(buckets) + (18 if part16 == "0" else 0)
+    ref = _run(mode, 1, tmp_path, "ref", "0", port, part16=part16)[0]
+    r0, r1 = _run(mode, 2, tmp_path, "dp" + buckets, buckets, port + 400, part16=part16)
     assert r0["info"]["world"] == 2 and r1["info"]["world"] == 2
     if mode != "student":
         assert r0["info"]["bucketed"] == (buckets == "1"), r0["info"]
@@ -95,8 +102,9 @@ def test_two_ranks_equal_one_process_on_the_global_batch(tmp_path, mode, buckets
     p, q = r0["params"].double(), ref["params"].double()
     err = float((p - q)[live].abs().max())
     # (two more Adam steps amplify what the first one left: one step is lr = 1e-3 per entry whatever the gradient's size, so
-    # the bound asks that no live entry has gone a whole step apart; "deep", bf16 with bf16 partial blocks: 5.2e-4 measured)
-    assert err < (1e-3 if mode == "deep" else 3e-4), err
+    # the bound asks that no live entry has gone a whole step apart; "deep", bf16 with bf16 partial blocks: 5.2e-4 measured,
+    # hence 1e-3 there; with fp32 partial slabs the strict bound)
+    assert err < (1e-3 if mode == "deep" and part16 != "0" else 3e-4), err
     # losses: each rank reports its shard's loss; mean losses average to the global one, sum losses add
     l2 = float(r0["loss"]) + float(r1["loss"])
     lg = float(ref["loss"])

@@ -229,7 +229,8 @@ def test_skip_wgrad_from_tiles_equals_wgrad256(monkeypatch, dil, B, T, seg, part
     wrong row would show as 1e-2 or more.  The bias gradient (column sums of dskip: no c) agrees to the order of the
     fp32 sums, by a block's idle waves or, when every block has four layers, by the column-sum kernel."""
     # part16 = "0": fp32 partial slabs -- the kernel's contraction is held to the exact one below at 2e-5; "1" (the
-    # default): its partial slabs are bf16 blocks, one more rounding per partial sum (bound: 2 x the 1.0e-3 .. 1.4e-3 measured)
+    # default): its partial slabs are bf16 blocks, one more rounding per partial sum -- this kernel sums a slab's segments in
+    # registers and stores once (bound: 2 x the 1.0e-3 .. 1.4e-3 measured)
     monkeypatch.setenv("SRWN_PART16", part16)
     _, eng = _pair(monkeypatch, dil, B, T, 64, 256, 256 if len(dil) != 4 else 64, torch.bfloat16, seg_rows=seg,
                    fuse_wt="1", ref_fuse="1")     # (64 classes: the engine's other reduction schedule)
@@ -417,7 +418,9 @@ def test_group_wt_bf16_partial_blocks_vs_fp32_partials(monkeypatch, dil, B, T, R
     """SRWN_PART16 (default): the backward group kernels store their per-workgroup weight-gradient partials as bf16 blocks
     instead of fp32.  Same chain, same products: activations, bottom gradients and every gradient that does not pass
     through those partials are bit-equal to the fp32-partial build of the same path; the conv-tap, residual 1x1 and (64 / 256
-    channels: srwn_wgrad_skip_wt) skip 1x1 kernel gradients differ by one bf16 rounding per partial sum (bound: 2 x the worst measured over these shapes)."""
+    channels: srwn_wgrad_skip_wt) skip 1x1 kernel gradients differ by one bf16 rounding per partial sum -- a workgroup that runs
+    several segments would re-round its block once per segment, so the engine keeps fp32 slabs in such a group
+    (tests/test_gpu_multiseg.py) -- (bound: 2 x the worst measured over these shapes)."""
     EG = sub("engine")
     cfg = EG.StackConfig(dilations=list(dil), dilation_channels=R, skip_channels=S, output_channels=64, shift_input=True,
                          dtype=torch.bfloat16)
