@@ -581,6 +581,64 @@ int srwn_generate16_mol_resume(const void* wl, const void* wh1, const void* wh2,
 int srwn_generate_ring_fill(const void* xs, int64_t layer_stride, int32_t T_src, int32_t P, const int32_t* dilations,
                             int32_t nlayers, int32_t B, int32_t R, void* ring, int32_t dtype, void* stream);
 
+/* ---- generation pools (since srwn_version() 105): B slots over one set of rings, each slot holding its own stream at its
+ * own step, so that streams join and leave a running batch.  The rings follow ONE clock, the launch's `clock`: step j of
+ * the launch writes ring position (clock + j) mod (d_l+1) and reads the delayed tap at (clock + j + 1) mod (d_l+1), for
+ * every slot alike; the causal padding comes only from the rings (a join zero-fills or prompt-fills its slot's rows).
+ * What depends on a stream's own position is read per slot from `slots` [B]:
+ *   t      the slot's own step of its next sample: step j of the launch is the slot's step t_u = t + j for both samplers'
+ *          counters -- softmax (seed, 0, t_u), mixture (seed, 0, t_u*(M+1)+m): a slot draws what a batch-of-one run with
+ *          that seed draws, whichever slot it sits in -- and for the conditioning frame clamp(t_u / pool_stride, 0,
+ *          cond_frames-1) of its rows [u*cond_frames, (u+1)*cond_frames) of cond;
+ *   t_end  the slot runs while t_u < t_end (t_end <= t: idle).  audio_out / codes_out / logits_out rows and the carry are
+ *          written only for steps that run; other rows keep what the caller put there.  On return t += min(nsteps,
+ *          max(t_end - t, 0));
+ *   seed   the samplers' seed.
+ * Steps and limits are int32: 2^31 steps is 37 hours at 16 kHz. */
+typedef struct SrwnGenSlot {
+  int32_t t;
+  int32_t t_end;
+  uint64_t seed;
+} SrwnGenSlot;
+/* Each *_slots entry point takes the arguments of its *_resume twin without `seed`, and (clock, carry, slots) in place of
+ * (t0, carry): carry [B][2] and slots [B] are required; `forced` and `mode` apply to the whole launch.  Idle columns keep
+ * computing (their ring rows are rewritten by the next join).  Argument errors (SRWN_E_*) return before any launch. */
+int srwn_generate_slots(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
+                        const float* bias_r, const float* bs_sum, const float* b1, const float* b2, const float* init_w,
+                        const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float* logits_out,
+                        const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                        int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, int32_t dtype,
+                        void* stream, int32_t clock, float* carry, SrwnGenSlot* slots);
+int srwn_generate_mol_slots(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
+                            const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                            const float* init_w, const float* init_b, void* ring, float* audio_out, int32_t* codes_out,
+                            float* logits_out, const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B,
+                            int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                            const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                            int32_t dtype, void* stream, int32_t clock, float* carry, SrwnGenSlot* slots);
+int srwn_generate16_slots(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const float* bias_r,
+                          const float* bs_sum, const float* b1, const float* b2, const float* init_w, const float* init_b,
+                          void* ring, float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                          const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R,
+                          int32_t S, int32_t C, int32_t mode, void* stream, int32_t clock, float* carry,
+                          SrwnGenSlot* slots);
+int srwn_generate16_mol_slots(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const float* bias_r,
+                              const float* bs_sum, const float* b1, const float* b2, const float* init_w,
+                              const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float* logits_out,
+                              const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                              int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                              int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode, void* stream,
+                              int32_t clock, float* carry, SrwnGenSlot* slots);
+/* The rings of pool slots after prompts, from ONE parallel forward pass over n prompts (layout as srwn_generate_ring_fill:
+ * layer l at xs + l * layer_stride, [n, T_src, R] rows): row i fills the rows of slot dst[i] of every layer ring so that a
+ * slot launch at `clock` continues it at its local step P[i] -- local step tau of that stream sits at ring position
+ * (clock - P[i] + tau) mod (d_l+1), zero for tau < 0 (P[i] = 0 clears the slot).  dst and P are device int32 [n]; a row
+ * whose dst is outside [0, B) or whose P is outside [0, T_src] is skipped.  Rows of slots not named are not touched.
+ * xs may be NULL when every P[i] is 0. */
+int srwn_generate_ring_fill_slots(const void* xs, int64_t layer_stride, int32_t T_src, int32_t n, const int32_t* dst,
+                                  const int32_t* P, int32_t clock, const int32_t* dilations, int32_t nlayers, int32_t B,
+                                  int32_t R, void* ring, int32_t dtype, void* stream);
+
 /* ---- discretised mixture-of-logistics loss of the reference's live teacher:
  * discretized_mix_logistic_loss (ops.py:124-175, sum_all=True) on logits [rows, ldl] fp32 whose first 4*M
  * columns are (logit_probs, means, log_scales, coeffs) and targets x [rows] in [-1,1]:

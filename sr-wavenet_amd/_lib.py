@@ -27,6 +27,13 @@ EPI_NONE, EPI_RELU, EPI_MASK, EPI_F32 = 0, 1, 2, 4
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
+
+class SrwnGenSlot(C.Structure):
+    """Mirror of srwn.h's SrwnGenSlot (16 bytes): one slot of a generation pool, passed to the *_slots entry points as a
+    device array."""
+    _fields_ = [("t", C.c_int32), ("t_end", C.c_int32), ("seed", C.c_uint64)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/srwn.h (checked by tests/test_abi.py)
 SIGNATURES = {
     "srwn_version": (C.c_int, []),
@@ -117,6 +124,17 @@ SIGNATURES = {
                                              _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, C.c_uint64, _p,
                                              _i32, _p]),
     "srwn_generate_ring_fill": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
+    # generation pools: each *_slots is its *_resume twin without the seed, (clock, carry, slots) for (t0, carry)
+    "srwn_generate_slots": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                      _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
+    "srwn_generate_mol_slots": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32,
+                                          _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, _i32, _p,
+                                          _i32, _p, _p]),
+    "srwn_generate16_slots": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                        _i32, _i32, _i32, _i32, _i32, _i32, _p, _i32, _p, _p]),
+    "srwn_generate16_mol_slots": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
+                                            _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, _p, _i32, _p, _p]),
+    "srwn_generate_ring_fill_slots": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
     "srwn_mol_loss": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _i64, _i64, _f32, _i32, _p]),
     "srwn_wgrad256_slabs": (_i32, [_i64, _i32]),
     "srwn_wgrad256": (C.c_int, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p]),

@@ -49,6 +49,9 @@ struct GenArgs {
   int dil[kGenMaxLayers];
   long long ring_off[kGenMaxLayers];
 };
+// the slot form (generation pools, srwn.h SrwnGenSlot): t0 is the pool's clock; a struct of its own, so that the other
+// instantiations keep their arguments
+struct GenSlotArgs : GenArgs { SrwnGenSlot* slots; };
 
 __device__ __forceinline__ float gen_mu_law_decode(int code, int Q) {   // ops.py:96-104, as srwn_mu_law_decode
   const float mu = (float)(Q - 1);
@@ -83,8 +86,8 @@ __device__ __forceinline__ void gen_carry_out(float* carry, const float* forced,
 template <typename T, int RT> struct GenCond { f32x4 cc[RT][4]; };
 struct GenNoCond {};
 
-template <typename T, int NBUF, bool COND, int RT, int SS>
-__global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
+template <typename T, int NBUF, bool COND, int RT, int SS, bool SLOTS = false>
+__global__ __launch_bounds__(256) void generate_kernel(typename std::conditional<SLOTS, GenSlotArgs, GenArgs>::type a) {
   constexpr int R = 32 * RT, KS = R / 16, S = SS, SQ = S / 4;   // SQ: skip/head-1 channels per wave
   constexpr int MQ = SQ / 32;                                    // ... = MQ 32-row tiles per wave
   constexpr int LGS = 256;                                       // row stride of the logits exchange (C <= 256)
@@ -105,6 +108,7 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
   float* c_iw = c_b2 + LGS;          // [2][R]
   float* c_ib = c_iw + 2 * R;        // [R]
   float* c_dec = c_ib + R;           // [256] mu-law decode of every code (ops.py:96-104 has a pow(): one table per launch)
+  int* sl = reinterpret_cast<int*>(c_dec + 256);   // slot form: [5][32] t, steps run, seed lo, seed hi, current frame
 
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col = lane & 31, half = lane >> 5;
@@ -130,8 +134,34 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
     prev[threadIdx.x] = (a.carry && u < a.B) ? a.carry[2 * u + (threadIdx.x >> 5)] : 0.0f;
   }
   if (a.Q >= 2) c_dec[threadIdx.x] = gen_mu_law_decode(threadIdx.x < a.Q ? threadIdx.x : a.Q - 1, a.Q);
+  if constexpr (SLOTS) {   // the group's slots, read once (a.nsteps is the END step here: the launch runs a.nsteps - t0)
+    if (threadIdx.x < 32) {
+      const int u = u0 + threadIdx.x;
+      int st = 0, sn = 0;
+      unsigned long long sd = 0;
+      if (u < a.B) {
+        const SrwnGenSlot g = a.slots[u];
+        const long long left = (long long)g.t_end - g.t;
+        const int n = a.nsteps - a.t0;
+        st = g.t; sd = g.seed;
+        sn = left <= 0 ? 0 : (left < n ? (int)left : n);
+      }
+      sl[threadIdx.x] = st; sl[32 + threadIdx.x] = sn;
+      sl[64 + threadIdx.x] = (int)(unsigned)sd; sl[96 + threadIdx.x] = (int)(unsigned)(sd >> 32);
+      if constexpr (COND) sl[128 + threadIdx.x] = max(min(st / a.pool, a.cond_frames - 1), 0);
+    }
+  }
   lds_dma_copy(wcr, wbuf, LAYER_B, wave, lane, 4);
   __syncthreads();
+  // slot form: the seed of local utterance ul, its own step at absolute step t, and whether it runs at step t
+  auto slot_seed = [&](int ul) {
+    return (unsigned long long)(unsigned)sl[64 + ul] | ((unsigned long long)(unsigned)sl[96 + ul] << 32);
+  };
+  auto slot_t = [&](int ul, int t) { return (int)((unsigned)sl[ul] + (unsigned)(t - a.t0)); };
+  auto live = [&](int ul, int t) {
+    if constexpr (SLOTS) return t - a.t0 < sl[32 + ul];
+    else return true;
+  };
 
   // operands of one layer that do not depend on the current step's activations: the tap-0 window from
   // the ring (written d >= 1 steps ago) and this wave's skip-weight fragments (from L2).  Loaded two
@@ -144,12 +174,14 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
     const int l = l_ < a.L ? l_ : a.L - 1;
     const int d = a.dil[l], depth = d + 1;
     const int td = t - d;
-    const int slot = (td >= 0 ? td : 0) % depth;
+    // (slot form: a true modulus -- a primed slot has real history while the clock is still below d)
+    const int slot = SLOTS ? (td >= 0 ? td % depth : td + depth) : (td >= 0 ? td : 0) % depth;
     const T* rp = ring + a.ring_off[l] + ((size_t)slot * 32 + col) * R + 8 * half;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) p.xd[ks] = load_nat(rp + 16 * ks);
     if constexpr (COND) {   // cb_l of the current frame (accumulator layout); the ring holds conditioned inputs
-      const int fc = min(t / a.pool, a.cond_frames - 1);
+      int fc = min(t / a.pool, a.cond_frames - 1);
+      if constexpr (SLOTS) fc = sl[128 + col];   // the slot's own frame at step t (one division per step, not per layer)
       const T* ccp = condp + ((size_t)ucl * a.cond_frames + fc) * a.cond_ld + (size_t)l * R + 4 * half;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt)
@@ -201,7 +233,7 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
       }
       preload(lfill, t, pfill);   // issued AFTER the LDS-DMA so the counted wait below leaves it in flight
       Frag<T> xd[KS];
-      const bool tap0 = (t - d) >= 0;   // zero before the clip starts
+      const bool tap0 = SLOTS || (t - d) >= 0;   // zero before the clip starts (slot form: the rings hold the padding)
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) xd[ks] = tap0 ? p.xd[ks] : zero_frag<T>();
       if constexpr (COND) {
@@ -348,30 +380,40 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
       //      counter-based uniforms; lanes = utterances (M <= 16 mixtures: a short serial loop)
       if (wave == 0 && half == 0) {
         const float* l = lgl + col * LGS;
+        // slot form: the slot's seed and own step under utterance key 0 (what a batch-of-one run draws)
+        const unsigned long long sseed = SLOTS ? slot_seed(col) : a.seed;
+        const unsigned su = SLOTS ? 0u : (unsigned)ug;
+        const int tu = SLOTS ? slot_t(col, t) : t;
         int sel = 0;
         float best = -INFINITY;
         for (int m = 0; m < a.M; ++m) {
-          const float u1 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(a.seed, (unsigned)ug, (unsigned)(t * (a.M + 1) + m));
+          const float u1 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + m));
           const float v = l[m] - logf(-logf(u1));
           if (v > best) { best = v; sel = m; }
         }
         float smp = l[a.M + sel];                                  // mode 0: the selected mean (no logistic noise)
         if (a.mode == 1) {
-          const float u2 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(a.seed, (unsigned)ug, (unsigned)(t * (a.M + 1) + a.M));
+          const float u2 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + a.M));
           smp += expf(fmaxf(l[2 * a.M + sel], -7.0f)) * (logf(u2) - logf(1.0f - u2));
         }
+        // slot form: the frame table of step t + 1 (every preload of step t is behind the head's barriers, the step's last
+        // one orders this before the next; clamped at 0 too: an idle slot may hold any t).  Conditioning comes with this
+        // head only: the conditioned softmax teacher is not built
+        if constexpr (SLOTS && COND) sl[128 + col] = max(min(slot_t(col, t + 1) / a.pool, a.cond_frames - 1), 0);
         smp = fminf(fmaxf(smp, -1.0f), 1.0f);
-        if (uok) {
-          a.audio_out[(size_t)ug * a.Tout + t] = smp;
-          a.codes_out[(size_t)ug * a.Tout + t] = sel;
+        if (live(col, t)) {
+          if (uok) {
+            a.audio_out[(size_t)ug * a.Tout + t] = smp;
+            a.codes_out[(size_t)ug * a.Tout + t] = sel;
+          }
+          prev[32 + col] = prev[col];
+          prev[col] = smp;
         }
-        prev[32 + col] = prev[col];
-        prev[col] = smp;
       }
       if (a.logits_out) {
         for (int i = threadIdx.x; i < 32 * a.C; i += 256) {
           const int ul = i / a.C, c = i - ul * a.C;
-          if (u0 + ul < a.B) a.logits_out[((size_t)(u0 + ul) * a.Tout + t) * a.C + c] = lgl[ul * LGS + c];
+          if (u0 + ul < a.B && live(ul, t)) a.logits_out[((size_t)(u0 + ul) * a.Tout + t) * a.C + c] = lgl[ul * LGS + c];
         }
       }
       __syncthreads();
@@ -404,7 +446,8 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
           if (lane >= off) inc += o;
         }
         const float total = __shfl(inc, 63);
-        const float target = gen_uniform(a.seed, (unsigned)u, (unsigned)t) * total;
+        const float target = (SLOTS ? gen_uniform(slot_seed(ul), 0u, (unsigned)slot_t(ul, t))
+                                    : gen_uniform(a.seed, (unsigned)u, (unsigned)t)) * total;
         const unsigned long long hit = __ballot(inc > target);
         const int src = hit ? (__ffsll((long long)hit) - 1) : 63;
         float run = inc - loc;
@@ -414,7 +457,7 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
         if (pick >= a.C) pick = a.C - 1;
         code = __shfl(pick, src);
       }
-      if (lane == 0) {
+      if (lane == 0 && live(ul, t)) {
         const float smp = c_dec[code];
         if (u < a.B) {
           a.audio_out[(size_t)u * a.Tout + t] = smp;
@@ -423,7 +466,7 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
         prev[32 + ul] = prev[ul];
         prev[ul] = smp;
       }
-      if (a.logits_out && u < a.B && 4 * lane < a.C) {
+      if (a.logits_out && u < a.B && 4 * lane < a.C && live(ul, t)) {
         float* lo = a.logits_out + ((size_t)u * a.Tout + t) * a.C + 4 * lane;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -432,8 +475,15 @@ __global__ __launch_bounds__(256) void generate_kernel(GenArgs a) {
     }
     __syncthreads();
   }
-  if (a.carry && threadIdx.x < 32) gen_carry_out(a.carry, a.forced, prev, u0 + threadIdx.x, threadIdx.x, a.B, a.Tout,
-                                                  a.t0, a.nsteps);
+  if constexpr (SLOTS) {   // the steps each slot ran (prev[] stopped with them); its own step advances by as many
+    const int ul = threadIdx.x, u = u0 + ul;
+    if (ul < 32 && u < a.B && sl[32 + ul] > 0) {
+      gen_carry_out(a.carry, a.forced, prev, u, ul, a.B, a.Tout, a.t0, a.t0 + sl[32 + ul]);
+      a.slots[u].t = sl[ul] + sl[32 + ul];
+    }
+  } else if (a.carry && threadIdx.x < 32) {
+    gen_carry_out(a.carry, a.forced, prev, u0 + threadIdx.x, threadIdx.x, a.B, a.Tout, a.t0, a.nsteps);
+  }
 }
 
 extern "C" int64_t srwn_generate_ring_elems(const int32_t* dilations, int32_t nlayers, int32_t R) {
@@ -442,16 +492,49 @@ extern "C" int64_t srwn_generate_ring_elems(const int32_t* dilations, int32_t nl
   return n;   // per group of 32 utterances
 }
 
+template <bool SL, typename A>
+static int generate_launch(A& a, int R, int S, bool cond, int dtype, int nlayers, unsigned groups, hipStream_t st) {
+  const size_t lfr = (size_t)(R / 32) * 3 * (R / 16);   // fragment images per layer: conv RT x 2KS + residual RT x KS
+  const size_t slot_lds = SL ? 5 * 32 * 4 : 0;           // the slot form's per-slot table
+  // widths: (64, 256) the north-star stack, (32, 256) generator.py's default teacher, (32, 128) teacher.py's
+#define SRWN_GEN_PICK(TT, NB)                                                                                             \
+  ((R == 64 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 2, 256, SL> : generate_kernel<TT, NB, false, 2, 256, SL>)  \
+   : (R == 32 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 1, 256, SL> : generate_kernel<TT, NB, false, 1, 256, SL>) \
+   : (R == 32 && S == 128) ? (cond ? generate_kernel<TT, NB, true, 1, 128, SL> : generate_kernel<TT, NB, false, 1, 128, SL>) \
+                           : (cond ? generate_kernel<TT, NB, true, 2, 128, SL> : generate_kernel<TT, NB, false, 2, 128, SL>))
+  if (dtype == SRWN_BF16) {
+    auto kfn = SRWN_GEN_PICK(bf16_t, 2);
+    const size_t sh = 2 * lfr * sizeof(Frag<bf16_t>) * 64 + 32 * S * sizeof(bf16_t) + 32 * 256 * 4 + 64 * 4 +
+                      (size_t)(2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4 + slot_lds;
+    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return set_error((int)e, "generate: LDS %zu: %s", sh, hipGetErrorString(e));
+    hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, st, a);
+  } else if (dtype == SRWN_F32) {
+    auto kfn = SRWN_GEN_PICK(float, 1);
+    const size_t sh = 1 * lfr * sizeof(Frag<float>) * 64 + 32 * S * sizeof(float) + 32 * 256 * 4 + 64 * 4 +
+                      (size_t)(2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4 + slot_lds;
+    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+    if (e != hipSuccess) return set_error((int)e, "generate: LDS %zu: %s", sh, hipGetErrorString(e));
+    hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, st, a);
+  } else {
+    return set_error(SRWN_E_DTYPE, "generate: dtype %d", dtype);
+  }
+#undef SRWN_GEN_PICK
+  return check_launch("generate");
+}
+
 static int generate_impl(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
                          const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                          const float* init_w, const float* init_b, void* ring, float* audio_out, int32_t* codes_out,
                          float* logits_out, const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B,
                          int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode,
                          uint64_t seed, int32_t dtype, void* stream, const void* cond, int32_t cond_frames,
-                         int32_t pool, int64_t cond_ld, int32_t M, int32_t t0, float* carry) {
+                         int32_t pool, int64_t cond_ld, int32_t M, int32_t t0, float* carry,
+                         SrwnGenSlot* slots = nullptr, bool slot_form = false) {
   if (B == 0 || nsteps == 0) return 0;
   if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate: t0=%d", t0);
   if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate: a launch that resumes at t0=%d needs the carry", t0);
+  if (slot_form && (!carry || !slots)) return set_error(SRWN_E_NULL, "generate_slots: the carry and the slots are required");
   if (!wcr || !wskip || !w1 || !w2 || !bias_f || !bias_r || !bs_sum || !b1 || !b2 || !init_w || !init_b || !ring ||
       !audio_out || !codes_out || !dilations)
     return set_error(SRWN_E_NULL, "generate: null pointer");
@@ -459,7 +542,8 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
     return set_error(SRWN_E_UNSUPPORTED, "generate: built for R=64 or 32, S=256 or 128, K=2, C<=256 (got R=%d S=%d K=%d C=%d)", R, S, K, C);
   if (B < 0 || nsteps < 0 || nsteps > Tout || nlayers < 1 || nlayers > kGenMaxLayers || (mode != 0 && mode != 1))
     return set_error(SRWN_E_SHAPE, "generate: B=%d nsteps=%d Tout=%d layers=%d mode=%d", B, nsteps, Tout, nlayers, mode);
-  GenArgs a;
+  GenSlotArgs a;   // (the other instantiations get its GenArgs part)
+  a.slots = slots;
   a.wcr = wcr; a.wskip = wskip; a.w1 = w1; a.w2 = w2; a.bias_f = bias_f; a.bias_r = bias_r; a.bs_sum = bs_sum;
   a.b1 = b1; a.b2 = b2; a.init_w = init_w; a.init_b = init_b; a.ring = ring; a.audio_out = audio_out;
   a.codes_out = codes_out; a.logits_out = logits_out; a.forced = forced;
@@ -482,31 +566,8 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
   a.ring_group_elems = off;
   const unsigned groups = (unsigned)((B + 31) / 32);
   hipStream_t st = (hipStream_t)stream;
-  const size_t lfr = (size_t)(R / 32) * 3 * (R / 16);   // fragment images per layer: conv RT x 2KS + residual RT x KS
-  // widths: (64, 256) the north-star stack, (32, 256) generator.py's default teacher, (32, 128) teacher.py's
-#define SRWN_GEN_PICK(TT, NB)                                                                                   \
-  ((R == 64 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 2, 256> : generate_kernel<TT, NB, false, 2, 256>)  \
-   : (R == 32 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 1, 256> : generate_kernel<TT, NB, false, 1, 256>) \
-   : (R == 32 && S == 128) ? (cond ? generate_kernel<TT, NB, true, 1, 128> : generate_kernel<TT, NB, false, 1, 128>) \
-                           : (cond ? generate_kernel<TT, NB, true, 2, 128> : generate_kernel<TT, NB, false, 2, 128>))
-  if (dtype == SRWN_BF16) {
-    auto kfn = SRWN_GEN_PICK(bf16_t, 2);
-    const size_t sh = 2 * lfr * sizeof(Frag<bf16_t>) * 64 + 32 * S * sizeof(bf16_t) + 32 * 256 * 4 + 64 * 4 +
-                      (size_t)(2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4;
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return set_error((int)e, "generate: LDS %zu: %s", sh, hipGetErrorString(e));
-    hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, st, a);
-  } else if (dtype == SRWN_F32) {
-    auto kfn = SRWN_GEN_PICK(float, 1);
-    const size_t sh = 1 * lfr * sizeof(Frag<float>) * 64 + 32 * S * sizeof(float) + 32 * 256 * 4 + 64 * 4 +
-                      (size_t)(2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4;
-    hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
-    if (e != hipSuccess) return set_error((int)e, "generate: LDS %zu: %s", sh, hipGetErrorString(e));
-    hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, st, a);
-  } else {
-    return set_error(SRWN_E_DTYPE, "generate: dtype %d", dtype);
-  }
-  return check_launch("generate");
+  if (slot_form) return generate_launch<true>(a, R, S, cond != nullptr, dtype, nlayers, groups, st);
+  return generate_launch<false>(static_cast<GenArgs&>(a), R, S, cond != nullptr, dtype, nlayers, groups, st);
 }
 
 extern "C" int srwn_generate_resume(const void* wcr, const void* wskip, const void* w1, const void* w2,
@@ -568,6 +629,40 @@ extern "C" int srwn_generate_mol(const void* wcr, const void* wskip, const void*
                                   codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, K,
                                   num_mixtures, cond, cond_frames, pool_stride, cond_ld, mode, seed, dtype, stream, 0,
                                   nullptr);
+}
+
+// ---- the slot form (generation pools, srwn.h): the arguments of the *_resume twins without the seed, with the pool's
+// clock as t0 and the per-slot state
+extern "C" int srwn_generate_slots(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                   const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                   const float* b2, const float* init_w, const float* init_b, void* ring,
+                                   float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                   const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
+                                   int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, int32_t dtype, void* stream,
+                                   int32_t clock, float* carry, SrwnGenSlot* slots) {
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, 0, dtype, stream,
+                       nullptr, 1, 1, 0, 0, clock, carry, slots, true);
+}
+
+extern "C" int srwn_generate_mol_slots(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                       const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                       const float* b2, const float* init_w, const float* init_b, void* ring,
+                                       float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                       const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                       int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                                       const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                                       int32_t mode, int32_t dtype, void* stream, int32_t clock, float* carry,
+                                       SrwnGenSlot* slots) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
+    return set_error(SRWN_E_SHAPE, "generate_mol_slots: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
+                     pool_stride, (long long)cond_ld);
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, 0,
+                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, clock,
+                       carry, slots, true);
 }
 
 // ---- the rings after a prompt of P samples, from the layer inputs of ONE parallel forward pass over it (what the loop of
@@ -636,4 +731,80 @@ extern "C" int srwn_generate_ring_fill(const void* xs, int64_t layer_stride, int
   if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_fill_kernel<bf16_t>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(ring_fill_kernel<float>, grid, dim3(256), 0, st, a);
   return check_launch("generate_ring_fill");
+}
+
+// ---- the rings of pool slots after prompts (srwn.h): row i of one parallel forward pass -> the rows of slot dst[i] of
+// every layer ring, so that a slot launch at `clock` continues it at its local step P[i].  Local step tau sits at ring
+// position (clock - P + tau) mod (d+1): the oldest one the ring holds, base = P - 1 - d, at (clock - 1 - d) mod (d+1)
+// whatever P is.  One (layer, row) per workgroup column; 16-byte vectors along the row's R channels, then positions.
+struct RingFillSlotsArgs {
+  const void* xs; void* ring; const int32_t* dst; const int32_t* P;
+  long long layer_stride, ring_group_elems;
+  int T_src, B, R, clock;
+  int dil[kGenMaxLayers];
+  long long ring_off[kGenMaxLayers];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void ring_fill_slots_kernel(RingFillSlotsArgs a) {
+  constexpr int V = 16 / sizeof(T);
+  const int l = blockIdx.y, i = blockIdx.z;
+  const int u = a.dst[i], P = a.P[i];
+  if (u < 0 || u >= a.B || P < 0 || P > a.T_src) return;     // a row that names no slot of the pool, or overlong
+  const int d = a.dil[l], depth = d + 1, vpr = a.R / V;
+  const int nvec = depth * vpr;
+  const int base = P - 1 - d;
+  int sb = (a.clock - 1 - d) % depth;                          // ring position of local step base
+  if (sb < 0) sb += depth;
+  const T* xp = a.xs ? reinterpret_cast<const T*>(a.xs) + (size_t)l * a.layer_stride + (size_t)i * a.T_src * a.R : nullptr;
+  T* rp = reinterpret_cast<T*>(a.ring) + (size_t)(u >> 5) * a.ring_group_elems + a.ring_off[l] + (size_t)(u & 31) * a.R;
+  for (int k = blockIdx.x * 256 + threadIdx.x; k < nvec; k += gridDim.x * 256) {
+    const int cv = k % vpr, s = k / vpr;
+    int off = s - sb;
+    if (off < 0) off += depth;
+    const int tau = base + off;                                  // <= P - 1 < T_src
+    uint4 v = {0u, 0u, 0u, 0u};
+    if (xp && tau >= 0) v = *reinterpret_cast<const uint4*>(xp + (size_t)tau * a.R + cv * V);
+    *reinterpret_cast<uint4*>(rp + (size_t)s * 32 * a.R + cv * V) = v;
+  }
+}
+
+extern "C" int srwn_generate_ring_fill_slots(const void* xs, int64_t layer_stride, int32_t T_src, int32_t n,
+                                             const int32_t* dst, const int32_t* P, int32_t clock,
+                                             const int32_t* dilations, int32_t nlayers, int32_t B, int32_t R, void* ring,
+                                             int32_t dtype, void* stream) {
+  if (n < 0) return set_error(SRWN_E_SHAPE, "generate_ring_fill_slots: n=%d", n);
+  if (n == 0) return 0;
+  if (!ring || !dilations || !dst || !P) return set_error(SRWN_E_NULL, "generate_ring_fill_slots: null pointer");
+  if (R != 64 && R != 32) return set_error(SRWN_E_UNSUPPORTED, "generate_ring_fill_slots: built for R=64 or 32 (got R=%d)", R);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "generate_ring_fill_slots: dtype %d", dtype);
+  const int V = dtype == SRWN_BF16 ? 8 : 4;
+  if (B < 1 || clock < 0 || T_src < 0 || n > 65535 || nlayers < 1 || nlayers > kGenMaxLayers || layer_stride < 0 ||
+      (xs && (layer_stride % V || (reinterpret_cast<uintptr_t>(xs) & 15) ||
+              (nlayers > 1 && layer_stride < (int64_t)n * T_src * R))))
+    return set_error(SRWN_E_SHAPE, "generate_ring_fill_slots: n=%d B=%d clock=%d T_src=%d layers=%d layer_stride=%lld", n, B,
+                     clock, T_src, nlayers, (long long)layer_stride);
+  if ((reinterpret_cast<uintptr_t>(ring) & 15))
+    return set_error(SRWN_E_SHAPE, "generate_ring_fill_slots: ring not 16-byte aligned");
+  RingFillSlotsArgs a;
+  a.xs = xs; a.ring = ring; a.dst = dst; a.P = P; a.layer_stride = layer_stride; a.T_src = T_src; a.B = B; a.R = R;
+  a.clock = clock;
+  long long off = 0;
+  int maxvec = 0;
+  for (int l = 0; l < kGenMaxLayers; ++l) {
+    a.dil[l] = (l < nlayers) ? dilations[l] : 1;
+    a.ring_off[l] = off;
+    if (l < nlayers) {
+      if (dilations[l] < 1 || dilations[l] > (1 << 20))
+        return set_error(SRWN_E_SHAPE, "generate_ring_fill_slots: dilation %d", dilations[l]);
+      off += (long long)(dilations[l] + 1) * 32 * R;
+      maxvec = max(maxvec, (dilations[l] + 1) * (R / V));
+    }
+  }
+  a.ring_group_elems = off;
+  const dim3 grid((unsigned)min((maxvec + 255) / 256, 1024), (unsigned)nlayers, (unsigned)n);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_fill_slots_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(ring_fill_slots_kernel<float>, grid, dim3(256), 0, st, a);
+  return check_launch("generate_ring_fill_slots");
 }

@@ -45,6 +45,9 @@ struct Gen16Args {
   int dil[kG16MaxLayers];
   long long ring_off[kG16MaxLayers];
 };
+// the slot form (generation pools): t0 is the pool's clock, and per-slot state replaces seed / t where a stream's own
+// position matters (srwn.h, SrwnGenSlot).  A struct of its own, so that the other instantiations keep their arguments
+struct Gen16SlotArgs : Gen16Args { SrwnGenSlot* slots; };
 
 __device__ __forceinline__ float g16_mu_law_decode(int code, int Q) {   // ops.py:96-104, as srwn_mu_law_decode
   const float mu = (float)(Q - 1);
@@ -87,8 +90,8 @@ struct PreT : std::conditional<COND, G16Cond<NCB>, G16NoCond>::type {
   Frag<T> x0[G16W<R, S>::KR][NCB];            // [k-step of the delayed tap][column block]
 };
 
-template <int NCB, bool COND, bool MOL, int R, int S>
-__global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
+template <int NCB, bool COND, bool MOL, int R, int S, bool SLOTS = false>
+__global__ __launch_bounds__(256) void generate16_kernel(typename std::conditional<SLOTS, Gen16SlotArgs, Gen16Args>::type a) {
   constexpr int NU = 16 * NCB;                // utterances of this workgroup
   constexpr int NI = 4 * NCB;                 // utterances a wave samples
   using W = G16W<R, S>;
@@ -108,6 +111,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
   float* c_iw = c_b2 + 256;                                   // [2][R]
   float* c_ib = c_iw + 2 * R;                                 // [R]
   float* c_dec = c_ib + R;                                    // [256] mu-law decode of every code (one pow() each, once)
+  int* sl = reinterpret_cast<int*>(c_dec + 256);              // slot form: [4][32] t, steps run, seed lo, seed hi
 
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col = lane & 15, rq = lane >> 4;                  // D tile: column (utterance in its block), rows 4 rq + r
@@ -127,7 +131,30 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
     prev[threadIdx.x] = (a.carry && ul < NU && u < a.B) ? a.carry[2 * u + (threadIdx.x >> 5)] : 0.0f;
   }
   c_dec[threadIdx.x] = g16_mu_law_decode((int)threadIdx.x < a.Q ? (int)threadIdx.x : a.Q - 1, a.Q);
+  if constexpr (SLOTS) {   // the slots of this workgroup, read once: nothing of them stays live in registers
+    if (threadIdx.x < 32) {
+      const int ul = threadIdx.x, u = u0 + ul;
+      int st = 0, sn = 0;
+      unsigned long long sd = 0;
+      if (ul < NU && u < a.B) {
+        const SrwnGenSlot g = a.slots[u];
+        const long long left = (long long)g.t_end - g.t;
+        st = g.t; sd = g.seed;
+        sn = left <= 0 ? 0 : (left < a.nsteps ? (int)left : a.nsteps);
+      }
+      sl[ul] = st; sl[32 + ul] = sn; sl[64 + ul] = (int)(unsigned)sd; sl[96 + ul] = (int)(unsigned)(sd >> 32);
+    }
+  }
   __syncthreads();
+  // slot form: the seed of local utterance ul, its own step at launch step j, and whether it runs at step j
+  auto slot_seed = [&](int ul) {
+    return (unsigned long long)(unsigned)sl[64 + ul] | ((unsigned long long)(unsigned)sl[96 + ul] << 32);
+  };
+  auto slot_t = [&](int ul, int j) { return (int)((unsigned)sl[ul] + (unsigned)j); };
+  auto live = [&](int ul, int j) {
+    if constexpr (SLOTS) return j < sl[32 + ul];
+    else return true;
+  };
 
   // per-layer scalars live in lane-indexed registers (lane l: layer l) and are fetched with v_readlane: the ring depth,
   // the ring's element offset, and the slot t % depth the current step writes (kept by increment: no division per layer)
@@ -150,7 +177,12 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
       for (int c2 = 0; c2 < NCB; ++c2) {
         const int ug = u0 + 16 * c2 + col;
         const int uc = ug < a.B ? ug : a.B - 1;
-        p.cc[c2] = *reinterpret_cast<const bf16x4*>(condp + ((size_t)uc * a.cond_frames + fc) * a.cond_ld + (size_t)l * R + 16 * wave + 4 * rq);
+        int fc_u = fc;
+        if constexpr (SLOTS) {   // the slot's own frame, clamped at both ends (an idle slot may hold any t)
+          fc_u = slot_t(16 * c2 + col, tt - a.t0) / a.pool;
+          fc_u = fc_u < 0 ? 0 : (fc_u < a.cond_frames ? fc_u : a.cond_frames - 1);
+        }
+        p.cc[c2] = *reinterpret_cast<const bf16x4*>(condp + ((size_t)uc * a.cond_frames + fc_u) * a.cond_ld + (size_t)l * R + 16 * wave + 4 * rq);
       }
       }
     }
@@ -392,8 +424,12 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
         const int u = u0 + ul, mx = lane & 15;
         const float* lg = lgl + ul * LGS;
         float v = -INFINITY;
+        // slot form: the slot's seed and own step under utterance key 0 (what a batch-of-one run draws)
+        const unsigned long long sseed = SLOTS ? slot_seed(ul) : a.seed;
+        const unsigned su = SLOTS ? 0u : (unsigned)u;
+        const int tu = SLOTS ? slot_t(ul, j) : t;
         if (mx < a.M) {
-          const float u1 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(a.seed, (unsigned)u, (unsigned)(t * (a.M + 1) + mx));
+          const float u1 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + mx));
           v = lg[mx] - logf(-logf(u1));
         }
         int sel = mx;
@@ -405,22 +441,24 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
         if (mx == 0) {
           float smp = lg[a.M + sel];                               // mode 0: the selected mean (no logistic noise)
           if (a.mode == 1) {
-            const float u2 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(a.seed, (unsigned)u, (unsigned)(t * (a.M + 1) + a.M));
+            const float u2 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + a.M));
             smp += expf(fmaxf(lg[2 * a.M + sel], -7.0f)) * (logf(u2) - logf(1.0f - u2));
           }
           smp = fminf(fmaxf(smp, -1.0f), 1.0f);
-          if (u < a.B) {
-            a.audio_out[(size_t)u * a.Tout + j] = smp;
-            a.codes_out[(size_t)u * a.Tout + j] = sel;
+          if (live(ul, j)) {
+            if (u < a.B) {
+              a.audio_out[(size_t)u * a.Tout + j] = smp;
+              a.codes_out[(size_t)u * a.Tout + j] = sel;
+            }
+            prev[32 + ul] = prev[ul];
+            prev[ul] = smp;
           }
-          prev[32 + ul] = prev[ul];
-          prev[ul] = smp;
         }
       }
       if (a.logits_out) {
         for (int i = threadIdx.x; i < NU * a.C; i += 256) {
           const int ul = i / a.C, c = i - ul * a.C;
-          if (u0 + ul < a.B) a.logits_out[((size_t)(u0 + ul) * a.Tout + j) * a.C + c] = lgl[ul * LGS + c];
+          if (u0 + ul < a.B && live(ul, j)) a.logits_out[((size_t)(u0 + ul) * a.Tout + j) * a.C + c] = lgl[ul * LGS + c];
         }
       }
       wg_barrier();
@@ -473,7 +511,13 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
             if (lane >= off) inc[i] += o;
           }
         // lane j draws the uniform of utterance j & 7 once
-        const float uni = g16_uniform(a.seed, (unsigned)(u0 + NI * wave + (lane & (NI - 1))), (unsigned)t);
+        float uni;
+        if constexpr (SLOTS) {
+          const int ul = NI * wave + (lane & (NI - 1));
+          uni = g16_uniform(slot_seed(ul), 0u, (unsigned)slot_t(ul, j));
+        } else {
+          uni = g16_uniform(a.seed, (unsigned)(u0 + NI * wave + (lane & (NI - 1))), (unsigned)t);
+        }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           const float total = __shfl(inc[i], 63);
@@ -497,18 +541,20 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
         for (int i = 1; i < NI; ++i) cd = (lane == i) ? code[i] : cd;
         const int ul = NI * wave + lane, u = u0 + ul;
         const float smp = c_dec[cd];
-        if (u < a.B) {
-          a.audio_out[(size_t)u * a.Tout + j] = smp;
-          a.codes_out[(size_t)u * a.Tout + j] = cd;
+        if (live(ul, j)) {
+          if (u < a.B) {
+            a.audio_out[(size_t)u * a.Tout + j] = smp;
+            a.codes_out[(size_t)u * a.Tout + j] = cd;
+          }
+          prev[32 + ul] = prev[ul];
+          prev[ul] = smp;
         }
-        prev[32 + ul] = prev[ul];
-        prev[ul] = smp;
       }
       if (a.logits_out) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
           const int u = u0 + NI * wave + i;
-          if (u < a.B && 4 * lane < a.C) {
+          if (u < a.B && 4 * lane < a.C && live(NI * wave + i, j)) {
             float* lo = a.logits_out + ((size_t)u * a.Tout + j) * a.C + 4 * lane;
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -522,14 +568,16 @@ __global__ __launch_bounds__(256) void generate16_kernel(Gen16Args a) {
   // the carry for the next launch (the step's last barrier ordered prev): emitted samples, or forced ones where forced
   if (a.carry && threadIdx.x < NU) {
     const int ul = threadIdx.x, u = u0 + ul;
-    if (u < a.B) {
+    const int n = SLOTS ? sl[32 + ul] : a.nsteps;      // (slot form: the steps this slot ran; prev[] stopped with them)
+    if (u < a.B && (!SLOTS || n > 0)) {
       float c0 = prev[ul], c1 = prev[32 + ul];
       if (a.forced) {
-        c0 = a.forced[(size_t)u * a.Tout + a.nsteps - 1];
-        if (a.nsteps >= 2) c1 = a.forced[(size_t)u * a.Tout + a.nsteps - 2];
+        c0 = a.forced[(size_t)u * a.Tout + n - 1];
+        if (n >= 2) c1 = a.forced[(size_t)u * a.Tout + n - 2];
       }
       a.carry[2 * u] = c0;
       a.carry[2 * u + 1] = c1;
+      if constexpr (SLOTS) a.slots[u].t = sl[ul] + n;
     }
   }
 }
@@ -546,8 +594,8 @@ extern "C" int64_t srwn_generate16_image_elems(int32_t nlayers, int32_t which, i
   return (int64_t)4 * 4 * HKS * FR;
 }
 
-template <int R, int S>
-static int generate16_launch(Gen16Args& a, const int32_t* dilations, int32_t nlayers, int32_t B, bool cond, int32_t M, void* stream) {
+template <int R, int S, bool SLOTS, typename A>
+static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, int32_t B, bool cond, int32_t M, void* stream) {
   long long off = 0;
   for (int l = 0; l < kG16MaxLayers; ++l) {
     a.dil[l] = (l < nlayers) ? dilations[l] : 1;
@@ -564,10 +612,10 @@ static int generate16_launch(Gen16Args& a, const int32_t* dilations, int32_t nla
   const unsigned groups = half ? (unsigned)((B + 15) / 16) : (unsigned)((B + 31) / 32);
   using W = G16W<R, S>;
   const size_t sh = (size_t)(2 * 32 * W::LSX + 32 * W::LSH) * sizeof(T) +
-                    (size_t)(32 * LGS + 64 + 2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4;
-  auto kfn = M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S> : generate16_kernel<2, true, true, R, S>)
-                           : (half ? generate16_kernel<1, false, true, R, S> : generate16_kernel<2, false, true, R, S>))
-                   : (half ? generate16_kernel<1, false, false, R, S> : generate16_kernel<2, false, false, R, S>);
+                    (size_t)(32 * LGS + 64 + 2 * nlayers * R + 2 * S + 256 + 3 * R + 256 + (SLOTS ? 4 * 32 : 0)) * 4;
+  auto kfn = M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S, SLOTS> : generate16_kernel<2, true, true, R, S, SLOTS>)
+                           : (half ? generate16_kernel<1, false, true, R, S, SLOTS> : generate16_kernel<2, false, true, R, S, SLOTS>))
+                   : (half ? generate16_kernel<1, false, false, R, S, SLOTS> : generate16_kernel<2, false, false, R, S, SLOTS>);
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
   if (e != hipSuccess) return set_error((int)e, "generate16: LDS %zu: %s", sh, hipGetErrorString(e));
   hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, (hipStream_t)stream, a);
@@ -580,10 +628,11 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
                            const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
                            int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
                            int32_t M, const void* cond, int32_t cond_frames, int32_t pool, int64_t cond_ld, int32_t t0,
-                           float* carry) {
+                           float* carry, SrwnGenSlot* slots = nullptr, bool slot_form = false) {
   if (B == 0 || nsteps == 0) return 0;
   if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate16: t0=%d", t0);
   if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate16: a launch that resumes at t0=%d needs the carry", t0);
+  if (slot_form && (!carry || !slots)) return set_error(SRWN_E_NULL, "generate16_slots: the carry and the slots are required");
   if (!wl || !wh1 || !wh2 || !bias_f || !bias_r || !bs_sum || !b1 || !b2 || !init_w || !init_b || !ring || !audio_out ||
       !codes_out || !dilations)
     return set_error(SRWN_E_NULL, "generate16: null pointer");
@@ -601,10 +650,20 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
   a.B = B; a.Tout = Tout; a.nsteps = nsteps; a.L = nlayers; a.C = C; a.Cp = (C + 31) / 32 * 32; a.mode = mode; a.Q = C; a.seed = seed;
   a.M = M; a.cond = cond; a.cond_frames = cond_frames; a.pool = pool; a.cond_ld = cond_ld;
   a.t0 = t0; a.carry = carry;
-  if (R == 64 && S == 256) return generate16_launch<64, 256>(a, dilations, nlayers, B, cond != nullptr, M, stream);
-  if (R == 64) return generate16_launch<64, 128>(a, dilations, nlayers, B, cond != nullptr, M, stream);
-  if (S == 256) return generate16_launch<32, 256>(a, dilations, nlayers, B, cond != nullptr, M, stream);
-  return generate16_launch<32, 128>(a, dilations, nlayers, B, cond != nullptr, M, stream);
+  const bool cd = cond != nullptr;
+  if (slot_form) {
+    Gen16SlotArgs b;
+    static_cast<Gen16Args&>(b) = a;
+    b.slots = slots;
+    if (R == 64 && S == 256) return generate16_launch<64, 256, true>(b, dilations, nlayers, B, cd, M, stream);
+    if (R == 64) return generate16_launch<64, 128, true>(b, dilations, nlayers, B, cd, M, stream);
+    if (S == 256) return generate16_launch<32, 256, true>(b, dilations, nlayers, B, cd, M, stream);
+    return generate16_launch<32, 128, true>(b, dilations, nlayers, B, cd, M, stream);
+  }
+  if (R == 64 && S == 256) return generate16_launch<64, 256, false>(a, dilations, nlayers, B, cd, M, stream);
+  if (R == 64) return generate16_launch<64, 128, false>(a, dilations, nlayers, B, cd, M, stream);
+  if (S == 256) return generate16_launch<32, 256, false>(a, dilations, nlayers, B, cd, M, stream);
+  return generate16_launch<32, 128, false>(a, dilations, nlayers, B, cd, M, stream);
 }
 
 extern "C" int srwn_generate16_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
@@ -657,4 +716,34 @@ extern "C" int srwn_generate16_mol(const void* wl, const void* wh1, const void* 
   return srwn_generate16_mol_resume(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out,
                                     codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, num_mixtures,
                                     cond, cond_frames, pool_stride, cond_ld, mode, seed, stream, 0, nullptr);
+}
+
+// ---- the slot form (generation pools, srwn.h): the arguments of the *_resume twins without the seed, with the pool's
+// clock as t0 and the per-slot state
+extern "C" int srwn_generate16_slots(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                     const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                     const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                     int32_t* codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                     int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
+                                     int32_t C, int32_t mode, void* stream, int32_t clock, float* carry,
+                                     SrwnGenSlot* slots) {
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, 0, stream, 0, nullptr, 1,
+                         1, 0, clock, carry, slots, true);
+}
+
+extern "C" int srwn_generate16_mol_slots(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                         const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                         const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                         int32_t* codes_out, float* logits_out, const float* forced,
+                                         const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                         int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                                         int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                                         void* stream, int32_t clock, float* carry, SrwnGenSlot* slots) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate16_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, 0, stream,
+                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, clock, carry, slots,
+                         true);
 }

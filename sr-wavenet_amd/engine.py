@@ -104,6 +104,252 @@ class GenerationState:
         self.t = 0
 
 
+INT32_MAX = 2 ** 31 - 1   # the generation kernels' steps, clock and limits are int32: 2^31 steps is about 37 h at 16 kHz
+
+
+def _pow2_at_least(n: int) -> int:
+    return 1 << max(0, int(n) - 1).bit_length()
+
+
+class GenerationPool:
+    """A fixed-capacity generation pool (WaveNetEngine.generation_pool): `capacity` slots over ONE set of layer rings, each
+    slot holding its own stream at its own step.  Streams `join` free slots (from prompts of any lengths and, for a
+    conditioned decoder, with their own encodings), `step` runs every live slot with one launch per chunk, and a stream
+    that reaches its end or `leave`s frees its slot for the next one.  The rings follow the pool's clock; what depends on
+    a stream's own position -- the samplers' counters, the conditioning frame, whether it still emits -- comes from the
+    per-slot table (srwn.h, SrwnGenSlot), so a slot produces the bits of a batch-of-one run with its seed.
+    Joins are ordered between steps.  Steps, clock and limits are int32 (2^31 steps is about 37 h at 16 kHz)."""
+
+    def __init__(self, eng: "WaveNetEngine", capacity: int, frames: int = 0):
+        import ctypes as C
+        from . import _lib
+        self.eng, self.capacity, self.frames = eng, int(capacity), int(frames)
+        self.conditioned = bool(eng.mol and eng.E)
+        self.E, self.pool_stride = int(eng.E), int(eng.cfg.pool_stride)
+        self.clock = 0
+        self._t = np.zeros(self.capacity, np.int64)          # host mirror of the device table (the kernel advances both alike)
+        self._end = np.zeros(self.capacity, np.int64)
+        self._seed = [0] * self.capacity
+        self._active = np.zeros(self.capacity, bool)
+        self._view = None
+        eng._repack_generation()
+        self._dl = (C.c_int32 * eng.L)(*eng.dil)
+        relems = int(_lib.load().srwn_generate_ring_elems(self._dl, eng.L, eng.R))
+        self.ring = torch.zeros(relems * ((self.capacity + 31) // 32), dtype=eng.dt, device=eng.dev)
+        self.carry = torch.zeros((self.capacity, 2), dtype=torch.float32, device=eng.dev)
+        self.slots = torch.zeros((self.capacity, 4), dtype=torch.int32, device=eng.dev)   # [t, t_end, seed lo, seed hi]
+        self.cond_all = None
+        if self.conditioned:
+            self.cond_all = torch.zeros((self.capacity * self.frames, eng.L * eng.R), dtype=eng.dt, device=eng.dev)
+
+    # ---- inspection
+    @property
+    def t(self) -> np.ndarray:
+        """Each slot's own step of its next sample."""
+        return self._t.copy()
+
+    @property
+    def active(self) -> List[int]:
+        return [int(u) for u in np.flatnonzero(self._active)]
+
+    @property
+    def free(self) -> List[int]:
+        return [int(u) for u in np.flatnonzero(~self._active)]
+
+    def _upload(self):
+        from . import _lib
+        tab = np.zeros(self.capacity, dtype=np.dtype(_lib.SrwnGenSlot))      # (srwn.h's layout, 16 bytes a slot)
+        tab["t"], tab["t_end"], tab["seed"] = self._t, self._end, np.array(self._seed, dtype=np.uint64)
+        self.slots.copy_(torch.from_numpy(tab.view(np.int32).reshape(self.capacity, 4)))
+
+    def _check_join(self, seeds, prompts, cond, max_samples, slots):
+        """Everything join refuses, before any device work: returns (seeds, prompts as float32 1-D arrays, the chosen
+        slots, t_end per stream)."""
+        seeds = [int(s) for s in seeds]
+        n = len(seeds)
+        if n < 1:
+            raise ValueError("join: no streams")
+        if any(s < 0 or s >= 2 ** 64 for s in seeds):
+            raise ValueError("join: seeds are unsigned 64-bit")
+
+        def per_stream(x, what):
+            if x is None or np.isscalar(x):
+                return [x] * n
+            x = list(x)
+            if len(x) != n:
+                raise ValueError("join: %d seeds but %d %s" % (n, len(x), what))
+            return x
+        ps = []
+        for p in per_stream(prompts, "prompts") if prompts is not None else [None] * n:
+            if p is None:
+                ps.append(np.zeros(0, np.float32))
+                continue
+            p = p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+            if p.ndim != 1:
+                raise ValueError("join: each prompt is 1-D [P], got shape %s" % (p.shape,))
+            ps.append(p.astype(np.float32))
+        mx = per_stream(max_samples, "max_samples")
+        limits = [INT32_MAX] * n
+        if self.conditioned:
+            if cond is None:
+                raise ValueError("this decoder is conditioned: pass cond, one [frames, %d] per stream" % self.E)
+            cond = per_stream(list(cond), "encodings")
+            for i, c in enumerate(cond):
+                shp = tuple(c.shape) if hasattr(c, "shape") else np.shape(c)
+                if len(shp) != 2 or shp[1] != self.E or not 1 <= shp[0] <= self.frames:
+                    raise ValueError("join: cond %d must be [1..%d frames, %d], got %s" % (i, self.frames, self.E, shp))
+                limits[i] = shp[0] * self.pool_stride
+        elif cond is not None:
+            raise ValueError("this decoder is not conditioned")
+        free = self.free
+        if slots is None:
+            if n > len(free):
+                raise ValueError("join: %d streams but %d free slots" % (n, len(free)))
+            slots = free[:n]
+        else:
+            slots = [int(u) for u in slots]
+            if len(slots) != n or len(set(slots)) != n:
+                raise ValueError("join: slots must name %d distinct slots" % n)
+            if any(u < 0 or u >= self.capacity or self._active[u] for u in slots):
+                raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
+        ends = []
+        for p, m, lim in zip(ps, mx, limits):
+            if len(p) > lim:
+                raise ValueError("join: prompt of %d samples exceeds frames * pool_stride = %d" % (len(p), lim))
+            if m is not None and int(m) < 0:
+                raise ValueError("join: max_samples %d" % int(m))
+            ends.append(min(lim, INT32_MAX if m is None else len(p) + int(m)))
+        return seeds, ps, cond, slots, ends
+
+    def _prime_view(self, n: int, T: int) -> "WaveNetEngine":
+        """The forward-only view the joins' prompt passes run in, its shape rounded up (powers of two; whole conditioning
+        frames) so that it is reused across joins rather than built per join."""
+        pool = self.pool_stride if self.eng.E else 1
+        B, Tp = _pow2_at_least(n), _pow2_at_least(T)
+        Tp = -(-Tp // pool) * pool
+        if self._view is None or (self._view.B, self._view.T) != (B, Tp):
+            self._view = None
+            self._view = WaveNetEngine(self.eng.cfg, B, Tp, self.eng.dev, share_from=self.eng, frozen=True)
+        return self._view
+
+    def join(self, seeds, prompts=None, cond=None, max_samples=None, slots=None) -> List[int]:
+        """n streams into free slots (the lowest ones, or `slots`): seeds [n]; prompts None or n entries of 1-D [P_i] (any
+        lengths, none included); cond (conditioned decoder) n encodings [frames_i <= frames, cond_channels]; max_samples
+        None, one int, or n entries: samples after the prompt (a conditioned stream ends at frames_i * pool_stride too).
+        One stack-only forward over all prompts (padded to the longest) and one srwn_generate_ring_fill_slots; returns the
+        slots."""
+        from . import _lib
+        seeds, ps, cond, slots, ends = self._check_join(seeds, prompts, cond, max_samples, slots)
+        eng, n, dev = self.eng, len(seeds), self.eng.dev
+        lens = [len(p) for p in ps]
+        dst = torch.tensor(slots, dtype=torch.int32, device=dev)
+        plen = torch.tensor(lens, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        if self.conditioned:
+            LR, F = eng.L * eng.R, self.frames
+            cin = torch.zeros((n * F, eng.Ep), dtype=eng.dt, device=dev)
+            for i, c in enumerate(cond):
+                c = torch.as_tensor(c).to(device=dev, dtype=torch.float32)
+                cin[i * F:i * F + c.shape[0], :self.E].copy_(c)
+            rows = torch.empty((n * F, LR), dtype=eng.dt, device=dev)
+            K.pw_linear(cin.data_ptr(), eng.Ep, 0, eng.Ep, eng.Ep, eng.wptr(eng.o_wc), eng.view("BC").reshape(-1), rows,
+                        LR, LR, n * F)                                                        # model.py:180
+            self.cond_all.view(self.capacity, F, LR)[dst.long()] = rows.view(n, F, LR)
+        P = max(lens)
+        xs, stride, T_src = None, 0, 0
+        if P > 0:
+            view = self._prime_view(n, P)
+            audio = torch.zeros((view.B, view.T), dtype=torch.float32, device=dev)
+            for i, p in enumerate(ps):
+                if len(p):
+                    audio[i, :len(p)].copy_(torch.from_numpy(p))
+            vc = None
+            if eng.E:
+                fv = view.T // self.pool_stride
+                vc = torch.zeros((view.B, fv, self.E), dtype=torch.float32, device=dev)
+                for i, c in enumerate(cond):
+                    c = torch.as_tensor(c).to(device=dev, dtype=torch.float32)[:fv]
+                    vc[i, :c.shape[0]].copy_(c)
+            view.set_inputs(audio, None, vc)
+            view.forward(want_logits=False, with_loss=False, train=False, stack_only=True)
+            xs, stride, T_src = view.xs.data_ptr(), view.B * view.T * eng.R, view.T
+        _lib.call("srwn_generate_ring_fill_slots", xs, stride, T_src, n, dst.data_ptr(), plen.data_ptr(), self.clock,
+                  self._dl, eng.L, self.capacity, eng.R, self.ring.data_ptr(), K.abi_dtype(eng.dt), st)
+        carry = np.zeros((n, 2), np.float32)
+        for i, p in enumerate(ps):
+            carry[i, :min(2, len(p))] = p[::-1][:2]
+        self.carry[dst.long()] = torch.from_numpy(carry).to(dev)
+        for i, u in enumerate(slots):
+            self._t[u], self._end[u], self._seed[u] = lens[i], ends[i], seeds[i]
+            self._active[u] = True
+        self._upload()
+        return list(slots)
+
+    def leave(self, slots) -> None:
+        """Ends the streams in `slots` (a slot already free stays free) and frees their slots."""
+        slots = [int(u) for u in slots]
+        if any(u < 0 or u >= self.capacity for u in slots):
+            raise ValueError("leave: slots %s outside the pool's %d" % (slots, self.capacity))
+        for u in slots:
+            self._active[u] = False
+            self._end[u] = self._t[u]
+        self._upload()
+
+    def step(self, nsteps: int, mode: str = "sample", forced: Optional[torch.Tensor] = None, want_logits: bool = False):
+        """One launch of `nsteps` pool steps: (audio [capacity, nsteps] f32, codes [capacity, nsteps] i32, logits
+        [capacity, nsteps, C] f32 or None, ran [capacity] int64 numpy).  Slot u's samples are row u's first ran[u]
+        entries; the rest of every row stays zero.  `forced` [capacity, nsteps]: teacher forcing for this launch (every
+        slot).  Slots whose stream reached its end become free."""
+        import os as _os
+        from . import _lib
+        eng, nsteps = self.eng, int(nsteps)
+        if nsteps < 0:
+            raise ValueError("step: nsteps %d" % nsteps)
+        if self.clock + nsteps > INT32_MAX:
+            raise ValueError("step: the pool's clock %d + %d steps passes int32" % (self.clock, nsteps))
+        md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
+        B, dev = self.capacity, eng.dev
+        audio = torch.zeros((B, nsteps), dtype=torch.float32, device=dev)
+        codes = torch.zeros((B, nsteps), dtype=torch.int32, device=dev)
+        logits = torch.zeros((B, nsteps, eng.C), dtype=torch.float32, device=dev) if want_logits else None
+        fp = None
+        if forced is not None:
+            forced = torch.as_tensor(forced).to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(forced.shape) != (B, nsteps):
+                raise ValueError("forced must be [capacity, nsteps]")
+            fp = forced.data_ptr()
+        ran = np.clip(self._end - self._t, 0, nsteps)
+        if nsteps == 0:
+            return audio, codes, logits, ran
+        st = torch.cuda.current_stream().cuda_stream
+        v = eng.view
+        common = (v("BF").data_ptr(), v("BR").data_ptr(), eng.bs_sum.data_ptr(), v("head_b1").data_ptr(),
+                  v("head_b2").data_ptr(), v("init_w").data_ptr(), v("init_b").data_ptr(), self.ring.data_ptr(),
+                  audio.data_ptr(), codes.data_ptr(), None if logits is None else logits.data_ptr(), fp, self._dl, eng.L,
+                  B, nsteps, nsteps, eng.R, eng.S)
+        tail = (self.clock, self.carry.data_ptr(), self.slots.data_ptr())
+        g16 = eng.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
+        lat = (eng.wptr(eng.o_g16), eng.wptr(eng.o_g16_h1), eng.wptr(eng.o_g16_h2)) if g16 else None
+        thr = (eng.wptr(eng.o_gen), eng.wptr(eng.o_skip_gen), eng.wptr(eng.o_w1), eng.wptr(eng.o_w2))
+        if eng.mol:
+            cptr = None if self.cond_all is None else self.cond_all.data_ptr()
+            frames = self.frames if self.cond_all is not None else 1
+            if g16:
+                _lib.call("srwn_generate16_mol_slots", *lat, *common, eng.C // 4, cptr, frames, self.pool_stride,
+                          eng.L * eng.R, md, st, *tail)
+            else:
+                _lib.call("srwn_generate_mol_slots", *thr, *common, eng.Kw, eng.C // 4, cptr, frames, self.pool_stride,
+                          eng.L * eng.R, md, K.abi_dtype(eng.dt), st, *tail)
+        elif g16:
+            _lib.call("srwn_generate16_slots", *lat, *common, eng.C, md, st, *tail)
+        else:
+            _lib.call("srwn_generate_slots", *thr, *common, eng.C, eng.Kw, md, K.abi_dtype(eng.dt), st, *tail)
+        self._t += ran
+        self.clock += nsteps
+        self._active &= self._t < self._end
+        return audio, codes, logits, ran
+
+
 CONTRASTIVE_LDS_FLOATS = 65536 // 4   # srwn_contrastive_head: rows*D + 2P floats in one workgroup (csrc/srwn_siamese.hip)
 
 
@@ -1384,6 +1630,27 @@ class WaveNetEngine:
         carry = torch.zeros((B, 2), dtype=torch.float32, device=self.dev)
         return GenerationState(B, ring, carry, int(seed), cond if frames else None, cond_all, frames,
                                frames * self.cfg.pool_stride if frames else None)
+
+    def generation_pool(self, capacity: int, frames: Optional[int] = None) -> "GenerationPool":
+        """A pool of `capacity` generation slots that streams join and leave while it runs (GenerationPool); `frames` = the
+        most conditioning frames a stream of a conditioned decoder brings.  Refuses, before any device work, what
+        `generate` refuses.  The generation weight images are gathered here: the pool keeps the weights it started with."""
+        if self.wavenet:
+            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
+                                      "the reference gate (canonical generation is not built)")
+        if self.o_gen is None or self.clip_head:
+            raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
+        if not self.mol and self.E:
+            raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
+                                      "decoder of the reference has the mixture-of-logistics head)")
+        if int(capacity) < 1:
+            raise ValueError("generation_pool: capacity %d" % int(capacity))
+        if self.mol and self.E:
+            if frames is None or int(frames) < 1:
+                raise ValueError("this decoder is conditioned: pass frames, the most encoding frames of a stream")
+        elif frames is not None:
+            raise ValueError("this decoder is not conditioned: no frames")
+        return GenerationPool(self, int(capacity), int(frames or 0))
 
     def _prime_view(self, B: int, T: int) -> "WaveNetEngine":
         """A forward-only (frozen) view of this stack at (B, T), kept for the next prompt of the same shape."""

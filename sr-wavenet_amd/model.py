@@ -345,6 +345,26 @@ class WaveNetTeacher(_EngineOwner):
             eng.prime(st, p)
         return _stream_chunks(eng, st, int(chunk_size), mode, max_samples)
 
+    def generation_pool(self, capacity, frames=None, mode="sample"):
+        """A pool of `capacity` generation slots that streams join and leave while it runs (GenerationPool).  A conditioned
+        (mixture-of-logistics) teacher takes `frames`, the most encoding frames a stream brings; each join then takes one
+        encoding [frames_i, latent] (and conditions [condition_size]) per stream."""
+        self._check_generation(1, None)
+        if int(capacity) < 1:
+            raise ValueError("generation_pool: capacity %d" % int(capacity))
+        if self.use_encoding and (frames is None or int(frames) < 1):
+            raise ValueError("this teacher was built with use_encoding=True; pass frames")
+        eng = self._primary or self._engine(1, self._default_length)
+        return GenerationPool(eng.generation_pool(int(capacity), frames if self.use_encoding else None),
+                              self._pool_cond, mode)
+
+    def _pool_cond(self, n, encoding, conditions):
+        if not self.use_encoding:
+            if encoding is not None:
+                raise ValueError("this teacher is not conditioned: no encoding")
+            return None
+        return _pool_encodings(n, encoding, conditions, self.latent_channels, self.condition_size)
+
     def _check_generation(self, batch_size, prompt):
         """What generation refuses before any device work; returns the prompt as float32 [B, P] (or None)."""
         if self.head == "softmax" and self.use_encoding:
@@ -364,6 +384,27 @@ class WaveNetTeacher(_EngineOwner):
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
             cond = torch.cat([cond, c[:, None, :].expand(-1, cond.shape[1], -1)], dim=2)
         return cond.contiguous()
+
+
+def _pool_encodings(n, encoding, conditions, latent, condition_size):
+    """The per-stream encodings of a pool join: n of [frames_i, latent] (+ conditions [condition_size] tiled over the
+    frames, model.py:161-167) -> n float32 arrays [frames_i, latent + condition_size]."""
+    if encoding is None:
+        raise ValueError("this decoder is conditioned: pass encoding, one [frames, latent] per stream")
+    encs = _per_stream(encoding, n, "encodings")
+    conds = _per_stream(conditions, n, "conditions")
+    out = []
+    for e, c in zip(encs, conds):
+        e = np.asarray(e, dtype=np.float32)
+        if e.ndim != 2 or e.shape[1] != latent:
+            raise ValueError("join: each encoding is [frames, %d], got shape %s" % (latent, e.shape))
+        if condition_size > 0:
+            if c is None:
+                raise ValueError("built with condition_size > 0: pass conditions, one [%d] per stream" % condition_size)
+            c = np.asarray(c, dtype=np.float32).reshape(1, condition_size)
+            e = np.concatenate([e, np.repeat(c, e.shape[0], 0)], 1)
+        out.append(e)
+    return out
 
 
 def _check_prompt(batch_size, prompt):
@@ -389,6 +430,65 @@ def _stream_chunks(eng, st, chunk, mode, max_samples):
         a, _, _ = eng.generate_chunk(st, n, mode=mode)
         made += n
         yield a.cpu().numpy()
+
+
+def _per_stream(x, n, what):
+    """A join argument as one entry per stream: None -> n Nones, else a list of exactly n entries."""
+    if x is None:
+        return [None] * n
+    if isinstance(x, (int, np.integer)):
+        return [int(x)] * n
+    x = list(x)
+    if len(x) != n:
+        raise ValueError("join: %d seeds but %d %s" % (n, len(x), what))
+    return x
+
+
+class GenerationPool(object):
+    """NumPy face of a generation pool (engine.GenerationPool): a fixed number of slots over one set of rings that streams
+    join and leave while it runs.  ``join(seed=[...], prompt=[...], ...)`` takes one entry per stream and returns their
+    slots; ``step(n)`` runs n pool steps in one launch and returns ``{slot: samples}`` of every slot that produced some; a
+    stream that reaches its end frees its slot; ``leave(slots)`` ends streams early.  A stream's samples put together are
+    what a batch-of-one ``generate`` with its seed and prompt returns."""
+
+    def __init__(self, pool, cond_fn, mode):
+        self._pool, self._cond_fn, self.mode = pool, cond_fn, mode
+
+    @property
+    def capacity(self):
+        return self._pool.capacity
+
+    @property
+    def active(self):
+        return self._pool.active
+
+    @property
+    def free(self):
+        return self._pool.free
+
+    @property
+    def t(self):
+        return self._pool.t
+
+    def join(self, seed, prompt=None, encoding=None, conditions=None, max_samples=None):
+        seeds = [int(s) for s in (seed if np.ndim(seed) else [seed])]
+        n = len(seeds)
+        prompts = _per_stream(prompt, n, "prompts")
+        for p in prompts:
+            if p is not None and np.ndim(p) != 1:
+                raise ValueError("join: each prompt is 1-D [P], got shape %s" % (np.shape(p),))
+        prompts = [None if p is None else np.asarray(p, dtype=np.float32) for p in prompts]
+        mx = _per_stream(max_samples, n, "max_samples")
+        cond = self._cond_fn(n, encoding, conditions)
+        return self._pool.join(seeds, prompts, cond, mx)
+
+    def step(self, n, mode=None, forced=None):
+        a, _, _, ran = self._pool.step(int(n), mode=mode or self.mode, forced=forced)
+        a = a.cpu().numpy()
+        return {u: a[u, :int(ran[u])] for u in range(self._pool.capacity) if ran[u] > 0}
+
+    def leave(self, slots):
+        self._pool.leave([slots] if np.isscalar(slots) else slots)
 
 
 class WaveNetAutoEncoder(object):
@@ -577,6 +677,20 @@ class WaveNetAutoEncoder(object):
             raise ValueError("chunk_size must be >= 1")
         eng, st, _ = self._prompted_state(encoding, conditions, seed, prompt)
         return _stream_chunks(eng.dec, st, int(chunk_size), mode, max_samples)
+
+    def generation_pool(self, capacity, frames, mode="sample"):
+        """A pool of `capacity` decoder slots that streams join and leave while it runs (GenerationPool): `frames` = the
+        most encoding frames a stream brings; each join takes one encoding [frames_i, latent_channels] (and conditions
+        [condition_size]) per stream, which ends at frames_i * pool_stride."""
+        if int(capacity) < 1:
+            raise ValueError("generation_pool: capacity %d" % int(capacity))
+        if frames is None or int(frames) < 1:
+            raise ValueError("generation_pool: frames %r (the most encoding frames of a stream)" % (frames,))
+        eng = self._eng or self._engine(1, int(frames) * self.pool_stride)
+        return GenerationPool(eng.dec.generation_pool(int(capacity), int(frames)), self._pool_cond, mode)
+
+    def _pool_cond(self, n, encoding, conditions):
+        return _pool_encodings(n, encoding, conditions, self.latent_channels, self.condition_size)
 
     def _prompted_state(self, encoding, conditions, seed, prompt):
         enc = np.asarray(encoding, dtype=np.float32)
