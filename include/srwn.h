@@ -639,6 +639,98 @@ int srwn_generate_ring_fill_slots(const void* xs, int64_t layer_stride, int32_t 
                                   const int32_t* P, int32_t clock, const int32_t* dilations, int32_t nlayers, int32_t B,
                                   int32_t R, void* ring, int32_t dtype, void* stream);
 
+/* ---- sampling controls of the generators (since srwn_version() 106): per utterance (or pool slot) a temperature, a
+ * top-k and a nucleus (top-p) cut; the defaults (1, 1, 0) mean "off".  Softmax head, mode 1, on the step's fp32 logits:
+ *   1. z = logits / temperature;
+ *   2. the classes are ordered by z descending, equal values by lower class first (the tie rule of mode 0);
+ *   3. top_k > 0: the first top_k classes of that order are kept (0: all C);
+ *   4. top_p < 1: of the kept classes, the shortest prefix of that order whose softmax mass is >= top_p times the kept mass
+ *      (at least one class stays);
+ *   5. the draw is mode 1's over what is left, in class order: the first class whose inclusive prefix sum of exp(z - max)
+ *      over the kept classes (dropped ones count 0) exceeds uniform * total, with the step's own uniform ((seed, u, t); in
+ *      pools (seed, 0, t_u)): no new random numbers.  top_k = 1 is mode 0's argmax whatever the uniform is.
+ * Mixture-of-logistics head, mode 1: the temperature only -- mixture = argmax_m(logit_m / temperature - log(-log u1_m)),
+ * sample = mean + temperature * exp(max(log_scale, -7)) * (log u2 - log(1 - u2)), clipped as before; top_k / top_p are
+ * not read.  Mode 0 ignores the controls.
+ * The array is data and the kernels sanitise it: a temperature that is not finite or not > 0 counts as 1; a top_k outside
+ * [0, C] counts as 0; a top_p outside (0, 1] (NaN included) counts as 1.  Whatever it holds, codes stay in [0, C) and the
+ * audio finite.  `reserved` is not read (write 0). */
+typedef struct SrwnGenSampling {
+  float temperature;
+  float top_p;
+  int32_t top_k;
+  int32_t reserved;
+} SrwnGenSampling;
+/* Each *_sampled entry point takes the arguments of the *_resume / *_slots call it is named after, plus `sampling`: a DEVICE
+ * array of B entries (one per utterance / per slot; a join writes its slot's entry as it writes the slot's carry), read
+ * once per launch; NULL = all defaults.  An utterance whose entry is all defaults, an idle slot, and every utterance of a
+ * launch with sampling = NULL run the code of the calls above and return their bits: those calls ARE these with NULL. */
+int srwn_generate_resume_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2, const float*
+                                 bias_f, const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                 const float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                 codes_out, float* logits_out, const float* forced, const int32_t* dilations, int32_t
+                                 nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C,
+                                 int32_t K, int32_t mode, uint64_t seed, int32_t dtype, void* stream, int32_t t0,
+                                 float* carry, const SrwnGenSampling* sampling);
+int srwn_generate_mol_resume_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2, const float*
+                                     bias_f, const float* bias_r, const float* bs_sum, const float* b1, const float*
+                                     b2, const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                     int32_t* codes_out, float* logits_out, const float* forced, const int32_t*
+                                     dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R,
+                                     int32_t S, int32_t K, int32_t num_mixtures, const void* cond, int32_t
+                                     cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed,
+                                     int32_t dtype, void* stream, int32_t t0, float* carry, const SrwnGenSampling*
+                                     sampling);
+int srwn_generate16_resume_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const float*
+                                   bias_r, const float* bs_sum, const float* b1, const float* b2, const float* init_w,
+                                   const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float*
+                                   logits_out, const float* forced, const int32_t* dilations, int32_t nlayers, int32_t
+                                   B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t mode,
+                                   uint64_t seed, void* stream, int32_t t0, float* carry, const SrwnGenSampling*
+                                   sampling);
+int srwn_generate16_mol_resume_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const
+                                       float* bias_r, const float* bs_sum, const float* b1, const float* b2, const
+                                       float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                       codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                       int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
+                                       int32_t num_mixtures, const void* cond, int32_t cond_frames, int32_t
+                                       pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed, void* stream,
+                                       int32_t t0, float* carry, const SrwnGenSampling* sampling);
+int srwn_generate_slots_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2, const float*
+                                bias_f, const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                const float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                codes_out, float* logits_out, const float* forced, const int32_t* dilations, int32_t
+                                nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C,
+                                int32_t K, int32_t mode, int32_t dtype, void* stream, int32_t clock, float* carry,
+                                SrwnGenSlot* slots, const SrwnGenSampling* sampling);
+int srwn_generate_mol_slots_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2, const float*
+                                    bias_f, const float* bias_r, const float* bs_sum, const float* b1, const float*
+                                    b2, const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                    int32_t* codes_out, float* logits_out, const float* forced, const int32_t*
+                                    dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R,
+                                    int32_t S, int32_t K, int32_t num_mixtures, const void* cond, int32_t cond_frames,
+                                    int32_t pool_stride, int64_t cond_ld, int32_t mode, int32_t dtype, void* stream,
+                                    int32_t clock, float* carry, SrwnGenSlot* slots, const SrwnGenSampling* sampling);
+int srwn_generate16_slots_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const float*
+                                  bias_r, const float* bs_sum, const float* b1, const float* b2, const float* init_w,
+                                  const float* init_b, void* ring, float* audio_out, int32_t* codes_out, float*
+                                  logits_out, const float* forced, const int32_t* dilations, int32_t nlayers, int32_t
+                                  B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t mode,
+                                  void* stream, int32_t clock, float* carry, SrwnGenSlot* slots, const
+                                  SrwnGenSampling* sampling);
+int srwn_generate16_mol_slots_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const
+                                      float* bias_r, const float* bs_sum, const float* b1, const float* b2, const
+                                      float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                      codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                      int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
+                                      int32_t num_mixtures, const void* cond, int32_t cond_frames, int32_t
+                                      pool_stride, int64_t cond_ld, int32_t mode, void* stream, int32_t clock, float*
+                                      carry, SrwnGenSlot* slots, const SrwnGenSampling* sampling);
+/* The draw of steps 1-5 on rows the caller chooses (the device function the generators call): logits [rows, ld] fp32 (C
+ * <= 256 columns used, ld >= C), sampling [rows] or NULL (defaults), uniforms [rows] in (0, 1), codes_out [rows]. */
+int srwn_sample_filtered(const float* logits, int64_t ld, const SrwnGenSampling* sampling, const float* uniforms,
+                         int32_t* codes_out, int64_t rows, int32_t C, void* stream);
+
 /* ---- discretised mixture-of-logistics loss of the reference's live teacher:
  * discretized_mix_logistic_loss (ops.py:124-175, sum_all=True) on logits [rows, ldl] fp32 whose first 4*M
  * columns are (logit_probs, means, log_scales, coeffs) and targets x [rows] in [-1,1]:

@@ -34,7 +34,16 @@ class SrwnGenSlot(C.Structure):
     _fields_ = [("t", C.c_int32), ("t_end", C.c_int32), ("seed", C.c_uint64)]
 
 
+class SrwnGenSampling(C.Structure):
+    """Mirror of srwn.h's SrwnGenSampling (16 bytes): one utterance's (or pool slot's) sampling controls, passed to the
+    *_sampled entry points and to srwn_sample_filtered as a device array.  The defaults (1, 1, 0) mean "off"."""
+    _fields_ = [("temperature", C.c_float), ("top_p", C.c_float), ("top_k", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/srwn.h (checked by tests/test_abi.py)
+SAMPLED = ["srwn_generate_resume", "srwn_generate_mol_resume", "srwn_generate16_resume", "srwn_generate16_mol_resume",
+           "srwn_generate_slots", "srwn_generate_mol_slots", "srwn_generate16_slots", "srwn_generate16_mol_slots"]
+
 SIGNATURES = {
     "srwn_version": (C.c_int, []),
     "srwn_last_error": (C.c_char_p, []),
@@ -135,6 +144,7 @@ SIGNATURES = {
     "srwn_generate16_mol_slots": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32,
                                             _i32, _i32, _i32, _i32, _i32, _p, _i32, _i32, _i64, _i32, _p, _i32, _p, _p]),
     "srwn_generate_ring_fill_slots": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i32, _p]),
+    "srwn_sample_filtered": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i32, _p]),
     "srwn_mol_loss": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _i64, _i64, _f32, _i32, _p]),
     "srwn_wgrad256_slabs": (_i32, [_i64, _i32]),
     "srwn_wgrad256": (C.c_int, [_p, _i64, _i64, _i32, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p]),
@@ -172,6 +182,11 @@ SIGNATURES = {
     "srwn_clip_scale": (C.c_int, [_p, _i64, _f32, _f32, _p, _p]),
     "srwn_adam_step_scaled": (C.c_int, [_p, _p, _p, _p, _i64, _p, _f32, _f32, _f32, _f32, _p, _i32, _p]),
 }
+
+# sampling controls: each *_sampled entry point is the call it is named after plus the device array of SrwnGenSampling
+for _n in SAMPLED:
+    SIGNATURES[_n + "_sampled"] = (SIGNATURES[_n][0], SIGNATURES[_n][1] + [_p])
+del _n
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "srwn_common.h"
 #include "srwn_host.h"
+#include "srwn_sample.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -52,6 +53,14 @@ struct GenArgs {
 // the slot form (generation pools, srwn.h SrwnGenSlot): t0 is the pool's clock; a struct of its own, so that the other
 // instantiations keep their arguments
 struct GenSlotArgs : GenArgs { SrwnGenSlot* slots; };
+// the forms with sampling controls (srwn.h, SrwnGenSampling): instantiations of their own with the per-utterance array, so
+// that a launch without controls runs the kernels it ran before
+struct GenSampArgs : GenArgs { const SrwnGenSampling* sampling; };
+struct GenSlotSampArgs : GenSlotArgs { const SrwnGenSampling* sampling; };
+template <bool SLOTS, bool SAMP> struct GenArgsOf {
+  using type = typename std::conditional<SLOTS, typename std::conditional<SAMP, GenSlotSampArgs, GenSlotArgs>::type,
+                                         typename std::conditional<SAMP, GenSampArgs, GenArgs>::type>::type;
+};
 
 __device__ __forceinline__ float gen_mu_law_decode(int code, int Q) {   // ops.py:96-104, as srwn_mu_law_decode
   const float mu = (float)(Q - 1);
@@ -86,8 +95,8 @@ __device__ __forceinline__ void gen_carry_out(float* carry, const float* forced,
 template <typename T, int RT> struct GenCond { f32x4 cc[RT][4]; };
 struct GenNoCond {};
 
-template <typename T, int NBUF, bool COND, int RT, int SS, bool SLOTS = false>
-__global__ __launch_bounds__(256) void generate_kernel(typename std::conditional<SLOTS, GenSlotArgs, GenArgs>::type a) {
+template <typename T, int NBUF, bool COND, int RT, int SS, bool SLOTS = false, bool SAMP = false>
+__global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS, SAMP>::type a) {
   constexpr int R = 32 * RT, KS = R / 16, S = SS, SQ = S / 4;   // SQ: skip/head-1 channels per wave
   constexpr int MQ = SQ / 32;                                    // ... = MQ 32-row tiles per wave
   constexpr int LGS = 256;                                       // row stride of the logits exchange (C <= 256)
@@ -109,6 +118,7 @@ __global__ __launch_bounds__(256) void generate_kernel(typename std::conditional
   float* c_ib = c_iw + 2 * R;        // [R]
   float* c_dec = c_ib + R;           // [256] mu-law decode of every code (ops.py:96-104 has a pow(): one table per launch)
   int* sl = reinterpret_cast<int*>(c_dec + 256);   // slot form: [5][32] t, steps run, seed lo, seed hi, current frame
+  int* sc = sl + (SLOTS ? 5 * 32 : 0);             // sampling controls: [4][32] tau, top_p (floats), top_k, on
 
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col = lane & 31, half = lane >> 5;
@@ -149,6 +159,15 @@ __global__ __launch_bounds__(256) void generate_kernel(typename std::conditional
       sl[threadIdx.x] = st; sl[32 + threadIdx.x] = sn;
       sl[64 + threadIdx.x] = (int)(unsigned)sd; sl[96 + threadIdx.x] = (int)(unsigned)(sd >> 32);
       if constexpr (COND) sl[128 + threadIdx.x] = max(min(st / a.pool, a.cond_frames - 1), 0);
+    }
+  }
+  if constexpr (SAMP) {   // the group's controls, sanitised, read once (mode 0 ignores them)
+    if (threadIdx.x < 32) {
+      const int u = u0 + threadIdx.x;
+      samp::Ctl c{1.0f, 1.0f, 0, 0};
+      if (u < a.B && a.mode == 1) c = samp::sanitise(a.sampling, u, a.C);
+      sc[threadIdx.x] = __builtin_bit_cast(int, c.tau); sc[32 + threadIdx.x] = __builtin_bit_cast(int, c.top_p);
+      sc[64 + threadIdx.x] = c.top_k; sc[96 + threadIdx.x] = c.on;
     }
   }
   lds_dma_copy(wcr, wbuf, LAYER_B, wave, lane, 4);
@@ -388,13 +407,16 @@ __global__ __launch_bounds__(256) void generate_kernel(typename std::conditional
         float best = -INFINITY;
         for (int m = 0; m < a.M; ++m) {
           const float u1 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + m));
-          const float v = l[m] - logf(-logf(u1));
+          float v = l[m] - logf(-logf(u1));
+          if constexpr (SAMP) v = l[m] / __builtin_bit_cast(float, sc[col]) - logf(-logf(u1));   // (tau = 1: the same bits)
           if (v > best) { best = v; sel = m; }
         }
         float smp = l[a.M + sel];                                  // mode 0: the selected mean (no logistic noise)
         if (a.mode == 1) {
           const float u2 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + a.M));
-          smp += expf(fmaxf(l[2 * a.M + sel], -7.0f)) * (logf(u2) - logf(1.0f - u2));
+          float sc_ = expf(fmaxf(l[2 * a.M + sel], -7.0f));
+          if constexpr (SAMP) sc_ = __builtin_bit_cast(float, sc[col]) * sc_;      // the temperature on the logistic noise
+          smp += sc_ * (logf(u2) - logf(1.0f - u2));
         }
         // slot form: the frame table of step t + 1 (every preload of step t is behind the head's barriers, the step's last
         // one orders this before the next; clamped at 0 too: an idle slot may hold any t).  Conditioning comes with this
@@ -456,6 +478,16 @@ __global__ __launch_bounds__(256) void generate_kernel(typename std::conditional
         for (int e = 3; e >= 0; --e) { if (run + ev[0] + (e > 0 ? ev[1] : 0.f) + (e > 1 ? ev[2] : 0.f) + (e > 2 ? ev[3] : 0.f) > target) pick = 4 * lane + e; }
         if (pick >= a.C) pick = a.C - 1;
         code = __shfl(pick, src);
+        if constexpr (SAMP) {
+          // an utterance with controls: temperature / top-k / nucleus selection on its row (srwn_sample.h) behind a
+          // wave-uniform branch; one at the defaults or an idle slot keeps the draw above
+          if (__builtin_amdgcn_readfirstlane((int)(sc[96 + ul] != 0 && live(ul, t)))) {
+            const float un = SLOTS ? gen_uniform(slot_seed(ul), 0u, (unsigned)slot_t(ul, t))
+                                   : gen_uniform(a.seed, (unsigned)u, (unsigned)t);
+            code = samp::filtered_code(v, a.C, __builtin_bit_cast(float, sc[ul]), sc[64 + ul],
+                                       __builtin_bit_cast(float, sc[32 + ul]), un, lane);
+          }
+        }
       }
       if (lane == 0 && live(ul, t)) {
         const float smp = c_dec[code];
@@ -492,16 +524,16 @@ extern "C" int64_t srwn_generate_ring_elems(const int32_t* dilations, int32_t nl
   return n;   // per group of 32 utterances
 }
 
-template <bool SL, typename A>
+template <bool SL, bool SA, typename A>
 static int generate_launch(A& a, int R, int S, bool cond, int dtype, int nlayers, unsigned groups, hipStream_t st) {
   const size_t lfr = (size_t)(R / 32) * 3 * (R / 16);   // fragment images per layer: conv RT x 2KS + residual RT x KS
-  const size_t slot_lds = SL ? 5 * 32 * 4 : 0;           // the slot form's per-slot table
+  const size_t slot_lds = (SL ? 5 * 32 * 4 : 0) + (SA ? 4 * 32 * 4 : 0);   // the per-slot table, the sampling controls
   // widths: (64, 256) the north-star stack, (32, 256) generator.py's default teacher, (32, 128) teacher.py's
 #define SRWN_GEN_PICK(TT, NB)                                                                                             \
-  ((R == 64 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 2, 256, SL> : generate_kernel<TT, NB, false, 2, 256, SL>)  \
-   : (R == 32 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 1, 256, SL> : generate_kernel<TT, NB, false, 1, 256, SL>) \
-   : (R == 32 && S == 128) ? (cond ? generate_kernel<TT, NB, true, 1, 128, SL> : generate_kernel<TT, NB, false, 1, 128, SL>) \
-                           : (cond ? generate_kernel<TT, NB, true, 2, 128, SL> : generate_kernel<TT, NB, false, 2, 128, SL>))
+  ((R == 64 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 2, 256, SL, SA> : generate_kernel<TT, NB, false, 2, 256, SL, SA>)  \
+   : (R == 32 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 1, 256, SL, SA> : generate_kernel<TT, NB, false, 1, 256, SL, SA>) \
+   : (R == 32 && S == 128) ? (cond ? generate_kernel<TT, NB, true, 1, 128, SL, SA> : generate_kernel<TT, NB, false, 1, 128, SL, SA>) \
+                           : (cond ? generate_kernel<TT, NB, true, 2, 128, SL, SA> : generate_kernel<TT, NB, false, 2, 128, SL, SA>))
   if (dtype == SRWN_BF16) {
     auto kfn = SRWN_GEN_PICK(bf16_t, 2);
     const size_t sh = 2 * lfr * sizeof(Frag<bf16_t>) * 64 + 32 * S * sizeof(bf16_t) + 32 * 256 * 4 + 64 * 4 +
@@ -530,7 +562,7 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
                          int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode,
                          uint64_t seed, int32_t dtype, void* stream, const void* cond, int32_t cond_frames,
                          int32_t pool, int64_t cond_ld, int32_t M, int32_t t0, float* carry,
-                         SrwnGenSlot* slots = nullptr, bool slot_form = false) {
+                         const SrwnGenSampling* sampling, SrwnGenSlot* slots = nullptr, bool slot_form = false) {
   if (B == 0 || nsteps == 0) return 0;
   if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate: t0=%d", t0);
   if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate: a launch that resumes at t0=%d needs the carry", t0);
@@ -542,8 +574,9 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
     return set_error(SRWN_E_UNSUPPORTED, "generate: built for R=64 or 32, S=256 or 128, K=2, C<=256 (got R=%d S=%d K=%d C=%d)", R, S, K, C);
   if (B < 0 || nsteps < 0 || nsteps > Tout || nlayers < 1 || nlayers > kGenMaxLayers || (mode != 0 && mode != 1))
     return set_error(SRWN_E_SHAPE, "generate: B=%d nsteps=%d Tout=%d layers=%d mode=%d", B, nsteps, Tout, nlayers, mode);
-  GenSlotArgs a;   // (the other instantiations get its GenArgs part)
+  GenSlotSampArgs a;   // (the other instantiations get its GenSlotArgs / GenArgs part)
   a.slots = slots;
+  a.sampling = sampling;
   a.wcr = wcr; a.wskip = wskip; a.w1 = w1; a.w2 = w2; a.bias_f = bias_f; a.bias_r = bias_r; a.bs_sum = bs_sum;
   a.b1 = b1; a.b2 = b2; a.init_w = init_w; a.init_b = init_b; a.ring = ring; a.audio_out = audio_out;
   a.codes_out = codes_out; a.logits_out = logits_out; a.forced = forced;
@@ -566,10 +599,33 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
   a.ring_group_elems = off;
   const unsigned groups = (unsigned)((B + 31) / 32);
   hipStream_t st = (hipStream_t)stream;
-  if (slot_form) return generate_launch<true>(a, R, S, cond != nullptr, dtype, nlayers, groups, st);
-  return generate_launch<false>(static_cast<GenArgs&>(a), R, S, cond != nullptr, dtype, nlayers, groups, st);
+  const bool cd = cond != nullptr;
+  if (slot_form) {
+    if (sampling) return generate_launch<true, true>(a, R, S, cd, dtype, nlayers, groups, st);
+    return generate_launch<true, false>(static_cast<GenSlotArgs&>(a), R, S, cd, dtype, nlayers, groups, st);
+  }
+  if (sampling) {   // (no slots: the GenArgs part and the array)
+    GenSampArgs b;
+    static_cast<GenArgs&>(b) = a;
+    b.sampling = sampling;
+    return generate_launch<false, true>(b, R, S, cd, dtype, nlayers, groups, st);
+  }
+  return generate_launch<false, false>(static_cast<GenArgs&>(a), R, S, cd, dtype, nlayers, groups, st);
 }
 
+extern "C" int srwn_generate_resume_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                    const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                    const float* b2, const float* init_w, const float* init_b, void* ring,
+                                    float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                    const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
+                                    int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, uint64_t seed,
+                                    int32_t dtype, void* stream, int32_t t0, float* carry, const SrwnGenSampling* sampling) {
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, seed, dtype, stream,
+                       nullptr, 1, 1, 0, 0, t0, carry, sampling);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate_resume(const void* wcr, const void* wskip, const void* w1, const void* w2,
                                     const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
                                     const float* b2, const float* init_w, const float* init_b, void* ring,
@@ -577,9 +633,9 @@ extern "C" int srwn_generate_resume(const void* wcr, const void* wskip, const vo
                                     const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
                                     int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, uint64_t seed,
                                     int32_t dtype, void* stream, int32_t t0, float* carry) {
-  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, seed, dtype, stream,
-                       nullptr, 1, 1, 0, 0, t0, carry);
+  return srwn_generate_resume_sampled(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, seed, dtype,
+      stream, t0, carry, nullptr);
 }
 
 extern "C" int srwn_generate(const void* wcr, const void* wskip, const void* w1, const void* w2, const float* bias_f,
@@ -597,6 +653,27 @@ extern "C" int srwn_generate(const void* wcr, const void* wskip, const void* w1,
 // [B*cond_frames, cond_ld] = the per-layer conditioning biases cb_l at columns [l*R, (l+1)*R) (srwn_pw_linear of
 // encoding_w_condition, model.py:180); head = 4*num_mixtures logits, sampled as ops.py:178-201.  b2 and the w2
 // image cover ceil(4M/32)*32 rows.  codes_out receives the selected mixture index.
+extern "C" int srwn_generate_mol_resume_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                        const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                        const float* b2, const float* init_w, const float* init_b, void* ring,
+                                        float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                        const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                        int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                                        const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                                        int32_t mode, uint64_t seed, int32_t dtype, void* stream, int32_t t0,
+                                        float* carry, const SrwnGenSampling* sampling) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate_mol: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
+    return set_error(SRWN_E_SHAPE, "generate_mol: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames, pool_stride,
+                     (long long)cond_ld);
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, seed,
+                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, t0,
+                       carry, sampling);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate_mol_resume(const void* wcr, const void* wskip, const void* w1, const void* w2,
                                         const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
                                         const float* b2, const float* init_w, const float* init_b, void* ring,
@@ -606,15 +683,9 @@ extern "C" int srwn_generate_mol_resume(const void* wcr, const void* wskip, cons
                                         const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
                                         int32_t mode, uint64_t seed, int32_t dtype, void* stream, int32_t t0,
                                         float* carry) {
-  if (num_mixtures < 1 || num_mixtures > 16)
-    return set_error(SRWN_E_SHAPE, "generate_mol: num_mixtures=%d (1..16)", num_mixtures);
-  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
-    return set_error(SRWN_E_SHAPE, "generate_mol: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames, pool_stride,
-                     (long long)cond_ld);
-  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, seed,
-                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, t0,
-                       carry);
+  return srwn_generate_mol_resume_sampled(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, K, num_mixtures, cond,
+      cond_frames, pool_stride, cond_ld, mode, seed, dtype, stream, t0, carry, nullptr);
 }
 
 extern "C" int srwn_generate_mol(const void* wcr, const void* wskip, const void* w1, const void* w2,
@@ -633,6 +704,19 @@ extern "C" int srwn_generate_mol(const void* wcr, const void* wskip, const void*
 
 // ---- the slot form (generation pools, srwn.h): the arguments of the *_resume twins without the seed, with the pool's
 // clock as t0 and the per-slot state
+extern "C" int srwn_generate_slots_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                   const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                   const float* b2, const float* init_w, const float* init_b, void* ring,
+                                   float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                   const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
+                                   int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, int32_t dtype, void* stream,
+                                   int32_t clock, float* carry, SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, 0, dtype, stream,
+                       nullptr, 1, 1, 0, 0, clock, carry, sampling, slots, true);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate_slots(const void* wcr, const void* wskip, const void* w1, const void* w2,
                                    const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
                                    const float* b2, const float* init_w, const float* init_b, void* ring,
@@ -640,11 +724,32 @@ extern "C" int srwn_generate_slots(const void* wcr, const void* wskip, const voi
                                    const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
                                    int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode, int32_t dtype, void* stream,
                                    int32_t clock, float* carry, SrwnGenSlot* slots) {
-  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, 0, dtype, stream,
-                       nullptr, 1, 1, 0, 0, clock, carry, slots, true);
+  return srwn_generate_slots_sampled(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, K, mode, dtype,
+      stream, clock, carry, slots, nullptr);
 }
 
+extern "C" int srwn_generate_mol_slots_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                       const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                       const float* b2, const float* init_w, const float* init_b, void* ring,
+                                       float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                       const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                       int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                                       const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                                       int32_t mode, int32_t dtype, void* stream, int32_t clock, float* carry,
+                                       SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
+    return set_error(SRWN_E_SHAPE, "generate_mol_slots: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
+                     pool_stride, (long long)cond_ld);
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, 0,
+                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, clock,
+                       carry, sampling, slots, true);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate_mol_slots(const void* wcr, const void* wskip, const void* w1, const void* w2,
                                        const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
                                        const float* b2, const float* init_w, const float* init_b, void* ring,
@@ -654,15 +759,9 @@ extern "C" int srwn_generate_mol_slots(const void* wcr, const void* wskip, const
                                        const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
                                        int32_t mode, int32_t dtype, void* stream, int32_t clock, float* carry,
                                        SrwnGenSlot* slots) {
-  if (num_mixtures < 1 || num_mixtures > 16)
-    return set_error(SRWN_E_SHAPE, "generate_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
-  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
-    return set_error(SRWN_E_SHAPE, "generate_mol_slots: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
-                     pool_stride, (long long)cond_ld);
-  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, 0,
-                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, clock,
-                       carry, slots, true);
+  return srwn_generate_mol_slots_sampled(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, K, num_mixtures, cond,
+      cond_frames, pool_stride, cond_ld, mode, dtype, stream, clock, carry, slots, nullptr);
 }
 
 // ---- the rings after a prompt of P samples, from the layer inputs of ONE parallel forward pass over it (what the loop of

@@ -18,6 +18,7 @@
 #include "srwn_common.h"
 #include "srwn_group.h"
 #include "srwn_host.h"
+#include "srwn_sample.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -48,6 +49,14 @@ struct Gen16Args {
 // the slot form (generation pools): t0 is the pool's clock, and per-slot state replaces seed / t where a stream's own
 // position matters (srwn.h, SrwnGenSlot).  A struct of its own, so that the other instantiations keep their arguments
 struct Gen16SlotArgs : Gen16Args { SrwnGenSlot* slots; };
+// the forms with sampling controls (srwn.h, SrwnGenSampling): instantiations of their own with the per-utterance array, so
+// that a launch without controls runs the kernels it ran before
+struct Gen16SampArgs : Gen16Args { const SrwnGenSampling* sampling; };
+struct Gen16SlotSampArgs : Gen16SlotArgs { const SrwnGenSampling* sampling; };
+template <bool SLOTS, bool SAMP> struct Gen16ArgsOf {
+  using type = typename std::conditional<SLOTS, typename std::conditional<SAMP, Gen16SlotSampArgs, Gen16SlotArgs>::type,
+                                         typename std::conditional<SAMP, Gen16SampArgs, Gen16Args>::type>::type;
+};
 
 __device__ __forceinline__ float g16_mu_law_decode(int code, int Q) {   // ops.py:96-104, as srwn_mu_law_decode
   const float mu = (float)(Q - 1);
@@ -90,8 +99,8 @@ struct PreT : std::conditional<COND, G16Cond<NCB>, G16NoCond>::type {
   Frag<T> x0[G16W<R, S>::KR][NCB];            // [k-step of the delayed tap][column block]
 };
 
-template <int NCB, bool COND, bool MOL, int R, int S, bool SLOTS = false>
-__global__ __launch_bounds__(256) void generate16_kernel(typename std::conditional<SLOTS, Gen16SlotArgs, Gen16Args>::type a) {
+template <int NCB, bool COND, bool MOL, int R, int S, bool SLOTS = false, bool SAMP = false>
+__global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SLOTS, SAMP>::type a) {
   constexpr int NU = 16 * NCB;                // utterances of this workgroup
   constexpr int NI = 4 * NCB;                 // utterances a wave samples
   using W = G16W<R, S>;
@@ -112,6 +121,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename std::condition
   float* c_ib = c_iw + 2 * R;                                 // [R]
   float* c_dec = c_ib + R;                                    // [256] mu-law decode of every code (one pow() each, once)
   int* sl = reinterpret_cast<int*>(c_dec + 256);              // slot form: [4][32] t, steps run, seed lo, seed hi
+  int* sc = sl + (SLOTS ? 4 * 32 : 0);                        // sampling controls: [4][32] tau, top_p (floats), top_k, on
 
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int col = lane & 15, rq = lane >> 4;                  // D tile: column (utterance in its block), rows 4 rq + r
@@ -143,6 +153,15 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename std::condition
         sn = left <= 0 ? 0 : (left < a.nsteps ? (int)left : a.nsteps);
       }
       sl[ul] = st; sl[32 + ul] = sn; sl[64 + ul] = (int)(unsigned)sd; sl[96 + ul] = (int)(unsigned)(sd >> 32);
+    }
+  }
+  if constexpr (SAMP) {    // the controls of this workgroup's utterances, sanitised, read once (mode 0 ignores them)
+    if (threadIdx.x < 32) {
+      const int ul = threadIdx.x, u = u0 + ul;
+      samp::Ctl c{1.0f, 1.0f, 0, 0};
+      if (ul < NU && u < a.B && a.mode == 1) c = samp::sanitise(a.sampling, u, a.C);
+      sc[ul] = __builtin_bit_cast(int, c.tau); sc[32 + ul] = __builtin_bit_cast(int, c.top_p);
+      sc[64 + ul] = c.top_k; sc[96 + ul] = c.on;
     }
   }
   __syncthreads();
@@ -431,6 +450,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename std::condition
         if (mx < a.M) {
           const float u1 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + mx));
           v = lg[mx] - logf(-logf(u1));
+          if constexpr (SAMP) v = lg[mx] / __builtin_bit_cast(float, sc[ul]) - logf(-logf(u1));   // (tau = 1: the same bits)
         }
         int sel = mx;
 #pragma unroll
@@ -442,7 +462,9 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename std::condition
           float smp = lg[a.M + sel];                               // mode 0: the selected mean (no logistic noise)
           if (a.mode == 1) {
             const float u2 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + a.M));
-            smp += expf(fmaxf(lg[2 * a.M + sel], -7.0f)) * (logf(u2) - logf(1.0f - u2));
+            float sc_ = expf(fmaxf(lg[2 * a.M + sel], -7.0f));
+            if constexpr (SAMP) sc_ = __builtin_bit_cast(float, sc[ul]) * sc_;      // the temperature on the logistic noise
+            smp += sc_ * (logf(u2) - logf(1.0f - u2));
           }
           smp = fminf(fmaxf(smp, -1.0f), 1.0f);
           if (live(ul, j)) {
@@ -480,6 +502,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename std::condition
           if (4 * lane + e < a.C && v[i][e] > m[i]) { m[i] = v[i][e]; am[i] = 4 * lane + e; }
       }
       int code[NI];
+      int ovr = -1;        // lane i: the code of utterance i where its controls are on
       if (a.mode == 0) {   // argmax, ties to the lower class
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1)
@@ -534,11 +557,26 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename std::condition
           if (pick >= a.C) pick = a.C - 1;
           code[i] = __shfl(pick, src);
         }
+        if constexpr (SAMP) {
+          // utterances with controls: temperature / top-k / nucleus selection on their row (srwn_sample.h), one after the
+          // other behind a wave-uniform branch each; an utterance at the defaults or an idle slot keeps the draw above
+#pragma unroll 1
+          for (int i = 0; i < NI; ++i) {
+            const int ul = NI * wave + i;
+            if (__builtin_amdgcn_readfirstlane((int)(sc[96 + ul] != 0 && live(ul, j)))) {
+              const f32x4 vv = *reinterpret_cast<const f32x4*>(lgl + ul * LGS + 4 * lane);
+              const int c = samp::filtered_code(vv, a.C, __builtin_bit_cast(float, sc[ul]), sc[64 + ul],
+                                                __builtin_bit_cast(float, sc[32 + ul]), __shfl(uni, i), lane);
+              if (lane == i) ovr = c;
+            }
+          }
+        }
       }
       if (lane < NI) {     // lane i publishes utterance i
         int cd = code[0];
 #pragma unroll
         for (int i = 1; i < NI; ++i) cd = (lane == i) ? code[i] : cd;
+        if constexpr (SAMP) cd = ovr >= 0 ? ovr : cd;
         const int ul = NI * wave + lane, u = u0 + ul;
         const float smp = c_dec[cd];
         if (live(ul, j)) {
@@ -594,7 +632,7 @@ extern "C" int64_t srwn_generate16_image_elems(int32_t nlayers, int32_t which, i
   return (int64_t)4 * 4 * HKS * FR;
 }
 
-template <int R, int S, bool SLOTS, typename A>
+template <int R, int S, bool SLOTS, bool SAMP, typename A>
 static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, int32_t B, bool cond, int32_t M, void* stream) {
   long long off = 0;
   for (int l = 0; l < kG16MaxLayers; ++l) {
@@ -612,10 +650,10 @@ static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, in
   const unsigned groups = half ? (unsigned)((B + 15) / 16) : (unsigned)((B + 31) / 32);
   using W = G16W<R, S>;
   const size_t sh = (size_t)(2 * 32 * W::LSX + 32 * W::LSH) * sizeof(T) +
-                    (size_t)(32 * LGS + 64 + 2 * nlayers * R + 2 * S + 256 + 3 * R + 256 + (SLOTS ? 4 * 32 : 0)) * 4;
-  auto kfn = M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S, SLOTS> : generate16_kernel<2, true, true, R, S, SLOTS>)
-                           : (half ? generate16_kernel<1, false, true, R, S, SLOTS> : generate16_kernel<2, false, true, R, S, SLOTS>))
-                   : (half ? generate16_kernel<1, false, false, R, S, SLOTS> : generate16_kernel<2, false, false, R, S, SLOTS>);
+                    (size_t)(32 * LGS + 64 + 2 * nlayers * R + 2 * S + 256 + 3 * R + 256 + (SLOTS ? 4 * 32 : 0) + (SAMP ? 4 * 32 : 0)) * 4;
+  auto kfn = M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S, SLOTS, SAMP> : generate16_kernel<2, true, true, R, S, SLOTS, SAMP>)
+                           : (half ? generate16_kernel<1, false, true, R, S, SLOTS, SAMP> : generate16_kernel<2, false, true, R, S, SLOTS, SAMP>))
+                   : (half ? generate16_kernel<1, false, false, R, S, SLOTS, SAMP> : generate16_kernel<2, false, false, R, S, SLOTS, SAMP>);
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
   if (e != hipSuccess) return set_error((int)e, "generate16: LDS %zu: %s", sh, hipGetErrorString(e));
   hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, (hipStream_t)stream, a);
@@ -628,7 +666,8 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
                            const float* forced, const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
                            int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
                            int32_t M, const void* cond, int32_t cond_frames, int32_t pool, int64_t cond_ld, int32_t t0,
-                           float* carry, SrwnGenSlot* slots = nullptr, bool slot_form = false) {
+                           float* carry, const SrwnGenSampling* sampling, SrwnGenSlot* slots = nullptr,
+                           bool slot_form = false) {
   if (B == 0 || nsteps == 0) return 0;
   if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate16: t0=%d", t0);
   if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate16: a launch that resumes at t0=%d needs the carry", t0);
@@ -651,21 +690,44 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
   a.M = M; a.cond = cond; a.cond_frames = cond_frames; a.pool = pool; a.cond_ld = cond_ld;
   a.t0 = t0; a.carry = carry;
   const bool cd = cond != nullptr;
+#define SRWN_G16_WIDTHS(SL, SA, args)                                                                          \
+  do {                                                                                                         \
+    if (R == 64 && S == 256) return generate16_launch<64, 256, SL, SA>(args, dilations, nlayers, B, cd, M, stream); \
+    if (R == 64) return generate16_launch<64, 128, SL, SA>(args, dilations, nlayers, B, cd, M, stream);       \
+    if (S == 256) return generate16_launch<32, 256, SL, SA>(args, dilations, nlayers, B, cd, M, stream);      \
+    return generate16_launch<32, 128, SL, SA>(args, dilations, nlayers, B, cd, M, stream);                    \
+  } while (0)
   if (slot_form) {
-    Gen16SlotArgs b;
+    Gen16SlotSampArgs b;   // (without controls: its Gen16SlotArgs part, and the kernels of the calls without them)
     static_cast<Gen16Args&>(b) = a;
     b.slots = slots;
-    if (R == 64 && S == 256) return generate16_launch<64, 256, true>(b, dilations, nlayers, B, cd, M, stream);
-    if (R == 64) return generate16_launch<64, 128, true>(b, dilations, nlayers, B, cd, M, stream);
-    if (S == 256) return generate16_launch<32, 256, true>(b, dilations, nlayers, B, cd, M, stream);
-    return generate16_launch<32, 128, true>(b, dilations, nlayers, B, cd, M, stream);
+    b.sampling = sampling;
+    if (sampling) SRWN_G16_WIDTHS(true, true, b);
+    SRWN_G16_WIDTHS(true, false, static_cast<Gen16SlotArgs&>(b));
   }
-  if (R == 64 && S == 256) return generate16_launch<64, 256, false>(a, dilations, nlayers, B, cd, M, stream);
-  if (R == 64) return generate16_launch<64, 128, false>(a, dilations, nlayers, B, cd, M, stream);
-  if (S == 256) return generate16_launch<32, 256, false>(a, dilations, nlayers, B, cd, M, stream);
-  return generate16_launch<32, 128, false>(a, dilations, nlayers, B, cd, M, stream);
+  if (sampling) {
+    Gen16SampArgs b;
+    static_cast<Gen16Args&>(b) = a;
+    b.sampling = sampling;
+    SRWN_G16_WIDTHS(false, true, b);
+  }
+  SRWN_G16_WIDTHS(false, false, a);
+#undef SRWN_G16_WIDTHS
 }
 
+extern "C" int srwn_generate16_resume_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                      const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                      const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                      int32_t* codes_out, float* logits_out, const float* forced,
+                                      const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
+                                      int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
+                                      int32_t t0, float* carry, const SrwnGenSampling* sampling) {
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, seed, stream, 0, nullptr, 1,
+                         1, 0, t0, carry, sampling);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate16_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
                                       const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                                       const float* init_w, const float* init_b, void* ring, float* audio_out,
@@ -673,9 +735,9 @@ extern "C" int srwn_generate16_resume(const void* wl, const void* wh1, const voi
                                       const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps,
                                       int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
                                       int32_t t0, float* carry) {
-  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, seed, stream, 0, nullptr, 1,
-                         1, 0, t0, carry);
+  return srwn_generate16_resume_sampled(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, seed, stream,
+      t0, carry, nullptr);
 }
 
 extern "C" int srwn_generate16(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
@@ -691,6 +753,22 @@ extern "C" int srwn_generate16(const void* wl, const void* wh1, const void* wh2,
 
 // the same body for the conditioned mixture-of-logistics decoder (srwn_generate_mol's arguments; wh2 / b2 cover
 // ceil(4M/32)*32 rows)
+extern "C" int srwn_generate16_mol_resume_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                          const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                          const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                          int32_t* codes_out, float* logits_out, const float* forced,
+                                          const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                          int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                                          int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                                          uint64_t seed, void* stream, int32_t t0, float* carry, const SrwnGenSampling* sampling) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate16_mol: num_mixtures=%d (1..16)", num_mixtures);
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, seed, stream,
+                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, t0, carry, sampling);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate16_mol_resume(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
                                           const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                                           const float* init_w, const float* init_b, void* ring, float* audio_out,
@@ -699,11 +777,9 @@ extern "C" int srwn_generate16_mol_resume(const void* wl, const void* wh1, const
                                           int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
                                           int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
                                           uint64_t seed, void* stream, int32_t t0, float* carry) {
-  if (num_mixtures < 1 || num_mixtures > 16)
-    return set_error(SRWN_E_SHAPE, "generate16_mol: num_mixtures=%d (1..16)", num_mixtures);
-  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, seed, stream,
-                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, t0, carry);
+  return srwn_generate16_mol_resume_sampled(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, num_mixtures, cond,
+      cond_frames, pool_stride, cond_ld, mode, seed, stream, t0, carry, nullptr);
 }
 
 extern "C" int srwn_generate16_mol(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
@@ -720,6 +796,19 @@ extern "C" int srwn_generate16_mol(const void* wl, const void* wh1, const void* 
 
 // ---- the slot form (generation pools, srwn.h): the arguments of the *_resume twins without the seed, with the pool's
 // clock as t0 and the per-slot state
+extern "C" int srwn_generate16_slots_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                     const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                     const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                     int32_t* codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                     int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
+                                     int32_t C, int32_t mode, void* stream, int32_t clock, float* carry,
+                                     SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, 0, stream, 0, nullptr, 1,
+                         1, 0, clock, carry, sampling, slots, true);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate16_slots(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
                                      const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                                      const float* init_w, const float* init_b, void* ring, float* audio_out,
@@ -727,11 +816,27 @@ extern "C" int srwn_generate16_slots(const void* wl, const void* wh1, const void
                                      int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
                                      int32_t C, int32_t mode, void* stream, int32_t clock, float* carry,
                                      SrwnGenSlot* slots) {
-  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, 0, stream, 0, nullptr, 1,
-                         1, 0, clock, carry, slots, true);
+  return srwn_generate16_slots_sampled(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, C, mode, stream, clock,
+      carry, slots, nullptr);
 }
 
+extern "C" int srwn_generate16_mol_slots_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                         const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                         const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                         int32_t* codes_out, float* logits_out, const float* forced,
+                                         const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                         int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                                         int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                                         void* stream, int32_t clock, float* carry, SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate16_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, 0, stream,
+                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, clock, carry, sampling, slots, true);
+}
+
+// (without sampling controls: the call above with NULL)
 extern "C" int srwn_generate16_mol_slots(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
                                          const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
                                          const float* init_w, const float* init_b, void* ring, float* audio_out,
@@ -740,10 +845,7 @@ extern "C" int srwn_generate16_mol_slots(const void* wl, const void* wh1, const 
                                          int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
                                          int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
                                          void* stream, int32_t clock, float* carry, SrwnGenSlot* slots) {
-  if (num_mixtures < 1 || num_mixtures > 16)
-    return set_error(SRWN_E_SHAPE, "generate16_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
-  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
-                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, 0, stream,
-                         num_mixtures, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, clock, carry, slots,
-                         true);
+  return srwn_generate16_mol_slots_sampled(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
+      audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, num_mixtures, cond,
+      cond_frames, pool_stride, cond_ld, mode, stream, clock, carry, slots, nullptr);
 }

@@ -7,6 +7,7 @@
 #include <cmath>
 #include "srwn_common.h"
 #include "srwn_host.h"
+#include "srwn_sample.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -64,6 +65,23 @@ __global__ __launch_bounds__(256) void categorical_sample_kernel(const float* __
     if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
   }
   if (lane == 0) out[row] = arg;
+}
+
+// one wave per row: the generators' filtered draw (srwn_sample.h) on logits and uniforms the caller chooses
+__global__ __launch_bounds__(256) void sample_filtered_kernel(const float* __restrict__ logits, int64_t ld,
+                                                              const SrwnGenSampling* __restrict__ sampling,
+                                                              const float* __restrict__ uniforms,
+                                                              int32_t* __restrict__ out, int64_t rows, int C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;                                  // (a whole wave: every lane of a running wave is active)
+  samp::Ctl c{1.0f, 1.0f, 0, 0};
+  if (sampling) c = samp::sanitise(sampling + row, 0, C);
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = (4 * lane + e < C) ? logits[row * ld + 4 * lane + e] : -INFINITY;
+  const int code = samp::filtered_code(v, C, c.tau, c.top_k, c.top_p, uniforms[row], lane);
+  if (lane == 0) out[row] = code;
 }
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -170,6 +188,18 @@ extern "C" int srwn_categorical_sample(const float* logits, int32_t* out, int64_
   hipLaunchKernelGGL(categorical_sample_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      logits, out, rows, C, seed);
   return check_launch("categorical_sample");
+}
+
+extern "C" int srwn_sample_filtered(const float* logits, int64_t ld, const SrwnGenSampling* sampling,
+                                    const float* uniforms, int32_t* codes_out, int64_t rows, int32_t C, void* stream) {
+  if (rows == 0) return 0;
+  if (C < 1 || C > 256) return set_error(SRWN_E_UNSUPPORTED, "sample_filtered: built for 1 <= C <= 256 (got C=%d)", C);
+  if (!logits || !uniforms || !codes_out) return set_error(SRWN_E_NULL, "sample_filtered: null pointer");
+  if (rows < 0 || ld < C || (rows + 3) / 4 > 0x7fffffffLL)
+    return set_error(SRWN_E_SHAPE, "sample_filtered: rows=%lld ld=%lld C=%d", (long long)rows, (long long)ld, C);
+  hipLaunchKernelGGL(sample_filtered_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits,
+                     ld, sampling, uniforms, codes_out, rows, C);
+  return check_launch("sample_filtered");
 }
 
 extern "C" int srwn_probs_logistic(const float* scale, const float* mu, const float* y, float* out, int64_t n,

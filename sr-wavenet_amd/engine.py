@@ -96,12 +96,62 @@ class GenerationState:
     """One resumable generation run (WaveNetEngine.generation_state): the per-layer rings of the queue-cached generator,
     the carry [B, 2] fp32 = (a[t-1], a[t-2]) the next step's input conv reads, the absolute step t of the next sample, the
     seed of the samplers' counters, and for a conditioned decoder the encoding `cond`, its per-layer conditioning
-    `cond_all` [B*frames, L*R] and `limit` = frames * pool_stride (the last step it covers)."""
+    `cond_all` [B*frames, L*R] and `limit` = frames * pool_stride (the last step it covers).  `sampling`: the run's
+    sampling controls as a device array of SrwnGenSampling [B] (None: every utterance at the defaults)."""
 
-    def __init__(self, batch, ring, carry, seed, cond=None, cond_all=None, frames=0, limit=None):
+    def __init__(self, batch, ring, carry, seed, cond=None, cond_all=None, frames=0, limit=None, sampling=None):
         self.batch, self.ring, self.carry, self.seed = int(batch), ring, carry, int(seed)
         self.cond, self.cond_all, self.frames, self.limit = cond, cond_all, int(frames), limit
+        self.sampling = sampling
         self.t = 0
+
+
+def sampling_table(n, temperature, top_k, top_p, C, mol, who="generate"):
+    """The sampling controls of n streams as srwn.h's SrwnGenSampling rows (a NumPy structured array [n]), or None when
+    every stream is at the defaults (temperature 1, top_k 0, top_p 1: the calls without controls).  Each argument is a
+    scalar, a sequence of n, or None (the default).  Ranges: temperature finite and > 0 (as float32), top_k 0 (off) or
+    1..C, 0 < top_p <= 1; a mixture-of-logistics head (`mol`) takes the temperature only.  ValueError otherwise, naming
+    the argument and the value.  No device work."""
+    from . import _lib
+    n = int(n)
+
+    def per(x, default, name):
+        if x is None:
+            return [default] * n
+        if np.ndim(x) == 0:
+            return [x] * n
+        x = list(x)
+        if len(x) != n:
+            raise ValueError("%s: %s has %d entries for %d streams: %r" % (who, name, len(x), n, x))
+        return x
+    taus, ks, ps = per(temperature, 1.0, "temperature"), per(top_k, 0, "top_k"), per(top_p, 1.0, "top_p")
+    tab = np.zeros(n, dtype=np.dtype(_lib.SrwnGenSampling))
+    for i, (t, k, p) in enumerate(zip(taus, ks, ps)):
+        try:
+            t32, p32 = np.float32(t), np.float32(p)
+        except (TypeError, ValueError):
+            raise ValueError("%s: temperature %r / top_p %r are not numbers" % (who, t, p))
+        if not (np.isfinite(t32) and t32 > 0):
+            raise ValueError("%s: temperature %r: finite and > 0" % (who, t))
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise ValueError("%s: top_k %r: an integer, 0 (off) or 1..%d" % (who, k, C))
+        if mol and int(k) != 0:
+            raise ValueError("%s: top_k %r: the mixture-of-logistics head takes temperature only" % (who, k))
+        if mol and not p32 == 1:
+            raise ValueError("%s: top_p %r: the mixture-of-logistics head takes temperature only" % (who, p))
+        if not 0 <= int(k) <= C:
+            raise ValueError("%s: top_k %r: 0 (off) or 1..%d classes" % (who, k, C))
+        if not (p32 > 0 and p32 <= 1):
+            raise ValueError("%s: top_p %r: 0 < top_p <= 1" % (who, p))
+        tab[i] = (t32, p32, int(k), 0)
+    if np.all(tab["temperature"] == 1) and np.all(tab["top_p"] == 1) and np.all(tab["top_k"] == 0):
+        return None
+    return tab
+
+
+def _sampling_to_device(tab, dev):
+    """A SrwnGenSampling table as the device array the *_sampled entry points read ([n, 4] 32-bit words)."""
+    return torch.from_numpy(tab.view(np.int32).reshape(len(tab), 4).copy()).to(dev)
 
 
 INT32_MAX = 2 ** 31 - 1   # the generation kernels' steps, clock and limits are int32: 2^31 steps is about 37 h at 16 kHz
@@ -138,6 +188,9 @@ class GenerationPool:
         self.ring = torch.zeros(relems * ((self.capacity + 31) // 32), dtype=eng.dt, device=eng.dev)
         self.carry = torch.zeros((self.capacity, 2), dtype=torch.float32, device=eng.dev)
         self.slots = torch.zeros((self.capacity, 4), dtype=torch.int32, device=eng.dev)   # [t, t_end, seed lo, seed hi]
+        self.C, self.mol = int(eng.C), bool(eng.mol)
+        self._samp = None        # the slots' sampling controls (host SrwnGenSampling [capacity]) once a join brought some
+        self.sampling = None     # ... and the device array the *_slots_sampled launches read
         self.cond_all = None
         if self.conditioned:
             self.cond_all = torch.zeros((self.capacity * self.frames, eng.L * eng.R), dtype=eng.dt, device=eng.dev)
@@ -161,16 +214,23 @@ class GenerationPool:
         tab = np.zeros(self.capacity, dtype=np.dtype(_lib.SrwnGenSlot))      # (srwn.h's layout, 16 bytes a slot)
         tab["t"], tab["t_end"], tab["seed"] = self._t, self._end, np.array(self._seed, dtype=np.uint64)
         self.slots.copy_(torch.from_numpy(tab.view(np.int32).reshape(self.capacity, 4)))
+        if getattr(self, "_samp", None) is not None:
+            if self.sampling is None:
+                self.sampling = torch.zeros((self.capacity, 4), dtype=torch.int32, device=self.eng.dev)
+            self.sampling.copy_(torch.from_numpy(self._samp.view(np.int32).reshape(self.capacity, 4)))
 
-    def _check_join(self, seeds, prompts, cond, max_samples, slots):
+    def _check_join(self, seeds, prompts, cond, max_samples, slots, temperature=None, top_k=None, top_p=None):
         """Everything join refuses, before any device work: returns (seeds, prompts as float32 1-D arrays, the chosen
-        slots, t_end per stream)."""
+        slots, t_end per stream, the streams' sampling controls or None)."""
         seeds = [int(s) for s in seeds]
         n = len(seeds)
         if n < 1:
             raise ValueError("join: no streams")
         if any(s < 0 or s >= 2 ** 64 for s in seeds):
             raise ValueError("join: seeds are unsigned 64-bit")
+        samp = None
+        if temperature is not None or top_k is not None or top_p is not None:
+            samp = sampling_table(n, temperature, top_k, top_p, self.C, self.mol, "join")
 
         def per_stream(x, what):
             if x is None or np.isscalar(x):
@@ -219,7 +279,7 @@ class GenerationPool:
             if m is not None and int(m) < 0:
                 raise ValueError("join: max_samples %d" % int(m))
             ends.append(min(lim, INT32_MAX if m is None else len(p) + int(m)))
-        return seeds, ps, cond, slots, ends
+        return seeds, ps, cond, slots, ends, samp
 
     def _prime_view(self, n: int, T: int) -> "WaveNetEngine":
         """The forward-only view the joins' prompt passes run in, its shape rounded up (powers of two; whole conditioning
@@ -232,14 +292,18 @@ class GenerationPool:
             self._view = WaveNetEngine(self.eng.cfg, B, Tp, self.eng.dev, share_from=self.eng, frozen=True)
         return self._view
 
-    def join(self, seeds, prompts=None, cond=None, max_samples=None, slots=None) -> List[int]:
+    def join(self, seeds, prompts=None, cond=None, max_samples=None, slots=None, *, temperature=None, top_k=None,
+             top_p=None) -> List[int]:
         """n streams into free slots (the lowest ones, or `slots`): seeds [n]; prompts None or n entries of 1-D [P_i] (any
         lengths, none included); cond (conditioned decoder) n encodings [frames_i <= frames, cond_channels]; max_samples
         None, one int, or n entries: samples after the prompt (a conditioned stream ends at frames_i * pool_stride too).
+        temperature / top_k / top_p: the streams' sampling controls (sampling_table: a scalar or one entry per stream; None
+        = the default), written into their slots' entries of the pool's SrwnGenSampling array as the carry is.
         One stack-only forward over all prompts (padded to the longest) and one srwn_generate_ring_fill_slots; returns the
         slots."""
         from . import _lib
-        seeds, ps, cond, slots, ends = self._check_join(seeds, prompts, cond, max_samples, slots)
+        seeds, ps, cond, slots, ends, samp = self._check_join(seeds, prompts, cond, max_samples, slots, temperature, top_k,
+                                                              top_p)
         eng, n, dev = self.eng, len(seeds), self.eng.dev
         lens = [len(p) for p in ps]
         dst = torch.tensor(slots, dtype=torch.int32, device=dev)
@@ -282,6 +346,12 @@ class GenerationPool:
         for i, u in enumerate(slots):
             self._t[u], self._end[u], self._seed[u] = lens[i], ends[i], seeds[i]
             self._active[u] = True
+        if samp is not None and self._samp is None:
+            self._samp = np.zeros(self.capacity, dtype=np.dtype(_lib.SrwnGenSampling))
+            self._samp["temperature"], self._samp["top_p"] = 1.0, 1.0
+        if self._samp is not None:      # (a join without controls puts its slots back at the defaults)
+            for i, u in enumerate(slots):
+                self._samp[u] = samp[i] if samp is not None else (1.0, 1.0, 0, 0)
         self._upload()
         return list(slots)
 
@@ -331,19 +401,22 @@ class GenerationPool:
         g16 = eng.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
         lat = (eng.wptr(eng.o_g16), eng.wptr(eng.o_g16_h1), eng.wptr(eng.o_g16_h2)) if g16 else None
         thr = (eng.wptr(eng.o_gen), eng.wptr(eng.o_skip_gen), eng.wptr(eng.o_w1), eng.wptr(eng.o_w2))
+        sfx = ""
+        if self.sampling is not None:      # some join brought sampling controls: the twins that read the pool's array
+            sfx, tail = "_sampled", tail + (self.sampling.data_ptr(),)
         if eng.mol:
             cptr = None if self.cond_all is None else self.cond_all.data_ptr()
             frames = self.frames if self.cond_all is not None else 1
             if g16:
-                _lib.call("srwn_generate16_mol_slots", *lat, *common, eng.C // 4, cptr, frames, self.pool_stride,
+                _lib.call("srwn_generate16_mol_slots" + sfx, *lat, *common, eng.C // 4, cptr, frames, self.pool_stride,
                           eng.L * eng.R, md, st, *tail)
             else:
-                _lib.call("srwn_generate_mol_slots", *thr, *common, eng.Kw, eng.C // 4, cptr, frames, self.pool_stride,
-                          eng.L * eng.R, md, K.abi_dtype(eng.dt), st, *tail)
+                _lib.call("srwn_generate_mol_slots" + sfx, *thr, *common, eng.Kw, eng.C // 4, cptr, frames,
+                          self.pool_stride, eng.L * eng.R, md, K.abi_dtype(eng.dt), st, *tail)
         elif g16:
-            _lib.call("srwn_generate16_slots", *lat, *common, eng.C, md, st, *tail)
+            _lib.call("srwn_generate16_slots" + sfx, *lat, *common, eng.C, md, st, *tail)
         else:
-            _lib.call("srwn_generate_slots", *thr, *common, eng.C, eng.Kw, md, K.abi_dtype(eng.dt), st, *tail)
+            _lib.call("srwn_generate_slots" + sfx, *thr, *common, eng.C, eng.Kw, md, K.abi_dtype(eng.dt), st, *tail)
         self._t += ran
         self.clock += nsteps
         self._active &= self._t < self._end
@@ -1514,8 +1587,11 @@ class WaveNetEngine:
         return self.loss
 
     def generate(self, nsteps: int, mode: str = "sample", seed: int = 0, forced: Optional[torch.Tensor] = None,
-                 want_logits: bool = False, batch: Optional[int] = None, cond: Optional[torch.Tensor] = None):
+                 want_logits: bool = False, batch: Optional[int] = None, cond: Optional[torch.Tensor] = None, *,
+                 temperature=1.0, top_k=0, top_p=1.0):
         """Queue-cached autoregressive generation of `nsteps` samples for `batch` utterances.
+        temperature / top_k / top_p (mode "sample"): the sampling controls of srwn.h's SrwnGenSampling, each a scalar or one
+        entry per utterance (sampling_table); the defaults are the plain draw.
         Softmax teacher: returns (audio [B,nsteps] f32, mu-law codes [B,nsteps] i32, logits [B,nsteps,C] f32 or None).
         Mixture-of-logistics decoder (head_mode "mol"; `cond` = encoding_w_condition [B, frames, cond_channels] when the
         stack is conditioned): returns (audio, selected mixture, logits [B,nsteps,4M])."""
@@ -1527,6 +1603,9 @@ class WaveNetEngine:
         if self.o_gen is None or self.clip_head:
             raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
         B = int(batch or self.B)
+        samp = None
+        if self.mol or not (self.E or cond is not None):      # (the conditioned softmax teacher is refused below)
+            samp = sampling_table(B, temperature, top_k, top_p, self.C, self.mol, "generate")
         self._repack_generation()      # (the generation-only images follow the parameters lazily: not part of a training step)
         dl = (C.c_int32 * self.L)(*self.dil)
         relems = int(_lib.load().srwn_generate_ring_elems(dl, self.L, self.R))
@@ -1548,6 +1627,8 @@ class WaveNetEngine:
                   nsteps, nsteps, self.R, self.S)
         md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
         st = torch.cuda.current_stream().cuda_stream
+        # with controls: the *_resume_sampled twins from step 0 (the one-shot calls are those with t0 = 0, no carry, NULL)
+        sdev = None if samp is None else _sampling_to_device(samp, self.dev)
         if self.mol:
             cond_all, frames = None, 1
             if self.E:
@@ -1565,7 +1646,17 @@ class WaveNetEngine:
             elif cond is not None:
                 raise ValueError("this decoder is not conditioned")
             import os as _os
-            if self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0":
+            g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
+            cptr = None if cond_all is None else cond_all.data_ptr()
+            if sdev is not None and g16:
+                _lib.call("srwn_generate16_mol_resume_sampled", self.wptr(self.o_g16), self.wptr(self.o_g16_h1),
+                          self.wptr(self.o_g16_h2), *common[4:21], self.R, self.S, self.C // 4, cptr, frames,
+                          self.cfg.pool_stride, self.L * self.R, md, int(seed), st, 0, None, sdev.data_ptr())
+            elif sdev is not None:
+                _lib.call("srwn_generate_mol_resume_sampled", *common, self.Kw, self.C // 4, cptr, frames,
+                          self.cfg.pool_stride, self.L * self.R, md, int(seed), K.abi_dtype(self.dt), st, 0, None,
+                          sdev.data_ptr())
+            elif g16:
                 _lib.call("srwn_generate16_mol", self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2),
                           *common[4:21], self.R, self.S, self.C // 4, None if cond_all is None else cond_all.data_ptr(), frames,
                           self.cfg.pool_stride, self.L * self.R, md, int(seed), st)
@@ -1578,7 +1669,15 @@ class WaveNetEngine:
                 raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
                                           "decoder of the reference has the mixture-of-logistics head)")
             import os as _os
-            if self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0":
+            g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
+            if sdev is not None and g16:
+                _lib.call("srwn_generate16_resume_sampled", self.wptr(self.o_g16), self.wptr(self.o_g16_h1),
+                          self.wptr(self.o_g16_h2), *common[4:21], self.R, self.S, self.C, md, int(seed), st, 0, None,
+                          sdev.data_ptr())
+            elif sdev is not None:
+                _lib.call("srwn_generate_resume_sampled", *common, self.C, self.Kw, md, int(seed), K.abi_dtype(self.dt), st,
+                          0, None, sdev.data_ptr())
+            elif g16:
                 _lib.call("srwn_generate16", self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2),
                           *common[4:21], self.R, self.S, self.C, md, int(seed), st)
             else:
@@ -1588,10 +1687,12 @@ class WaveNetEngine:
     # ------------------------------------------------------------------------------------------
     # resumable generation: streaming, chunks, prompts
     # ------------------------------------------------------------------------------------------
-    def generation_state(self, batch: int, cond: Optional[torch.Tensor] = None, seed: int = 0) -> "GenerationState":
+    def generation_state(self, batch: int, cond: Optional[torch.Tensor] = None, seed: int = 0, *, temperature=1.0,
+                         top_k=0, top_p=1.0) -> "GenerationState":
         """A generation run of `batch` utterances that `generate_chunk` advances chunk by chunk and `prime` can start from a
         prompt: the layer rings, the carry (the last two input samples, [B, 2] fp32), the absolute step t, the seed and,
         for a conditioned decoder, the per-layer conditioning (`cond` = encoding_w_condition [B, frames, cond_channels]).
+        temperature / top_k / top_p: the run's sampling controls (as `generate`), kept in the state for every chunk.
         The generation weight images are gathered here: train between chunks and the run keeps the weights it started
         with (make a new state to pick up new ones)."""
         import ctypes as C
@@ -1604,6 +1705,9 @@ class WaveNetEngine:
         B = int(batch)
         if B < 1:
             raise ValueError("generation_state: batch %d" % B)
+        samp = None
+        if self.mol or not (self.E or cond is not None):      # (the conditioned softmax teacher is refused below)
+            samp = sampling_table(B, temperature, top_k, top_p, self.C, self.mol, "generation_state")
         cond_all, frames = None, 0
         if self.mol and self.E:
             if cond is None:
@@ -1629,7 +1733,8 @@ class WaveNetEngine:
         ring = torch.zeros(relems * ((B + 31) // 32), dtype=self.dt, device=self.dev)
         carry = torch.zeros((B, 2), dtype=torch.float32, device=self.dev)
         return GenerationState(B, ring, carry, int(seed), cond if frames else None, cond_all, frames,
-                               frames * self.cfg.pool_stride if frames else None)
+                               frames * self.cfg.pool_stride if frames else None,
+                               None if samp is None else _sampling_to_device(samp, self.dev))
 
     def generation_pool(self, capacity: int, frames: Optional[int] = None) -> "GenerationPool":
         """A pool of `capacity` generation slots that streams join and leave while it runs (GenerationPool); `frames` = the
@@ -1729,6 +1834,9 @@ class WaveNetEngine:
                   nsteps, nsteps, self.R, self.S)
         thr = (self.wptr(self.o_gen), self.wptr(self.o_skip_gen), self.wptr(self.o_w1), self.wptr(self.o_w2))
         resume = (state.t, state.carry.data_ptr())
+        sfx = ""
+        if state.sampling is not None:      # the run has sampling controls: the twins that read its array
+            sfx, resume = "_sampled", resume + (state.sampling.data_ptr(),)
         g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
         if g16:
             lat = (self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2))
@@ -1736,15 +1844,15 @@ class WaveNetEngine:
             cptr = None if state.cond_all is None else state.cond_all.data_ptr()
             frames = state.frames if state.cond_all is not None else 1
             if g16:
-                _lib.call("srwn_generate16_mol_resume", *lat, *common, self.C // 4, cptr, frames, self.cfg.pool_stride,
+                _lib.call("srwn_generate16_mol_resume" + sfx, *lat, *common, self.C // 4, cptr, frames, self.cfg.pool_stride,
                           self.L * self.R, md, int(state.seed), st, *resume)
             else:
-                _lib.call("srwn_generate_mol_resume", *thr, *common, self.Kw, self.C // 4, cptr, frames,
+                _lib.call("srwn_generate_mol_resume" + sfx, *thr, *common, self.Kw, self.C // 4, cptr, frames,
                           self.cfg.pool_stride, self.L * self.R, md, int(state.seed), K.abi_dtype(self.dt), st, *resume)
         elif g16:
-            _lib.call("srwn_generate16_resume", *lat, *common, self.C, md, int(state.seed), st, *resume)
+            _lib.call("srwn_generate16_resume" + sfx, *lat, *common, self.C, md, int(state.seed), st, *resume)
         else:
-            _lib.call("srwn_generate_resume", *thr, *common, self.C, self.Kw, md, int(state.seed), K.abi_dtype(self.dt),
+            _lib.call("srwn_generate_resume" + sfx, *thr, *common, self.C, self.Kw, md, int(state.seed), K.abi_dtype(self.dt),
                       st, *resume)
         state.t += nsteps
         return audio, codes, logits

@@ -292,16 +292,22 @@ class WaveNetTeacher(_EngineOwner):
         return np.float32(eng.loss.item())
 
     def generate(self, batch_size, num_samples, mode="sample", seed=0, forced=None, return_logits=False,
-                 encoding=None, conditions=None, prompt=None):
+                 encoding=None, conditions=None, prompt=None, *, temperature=1.0, top_k=0, top_p=1.0):
         """Queue-cached autoregressive generation (the O(T L) replacement of the reference's O(T^2 L)
         loop, teacher.py:140-171): returns audio [B, num_samples] float32, or (audio, codes, logits) when
         return_logits.  `forced` [B, num_samples] = teacher forcing.  The softmax teacher emits mu-law decoded
         samples; the mixture-of-logistics teacher (optionally conditioned on `encoding`) emits logistic samples.
-        `prompt` [B, P]: the num_samples that FOLLOW the prompt (one parallel pass over it primes the generator)."""
+        `prompt` [B, P]: the num_samples that FOLLOW the prompt (one parallel pass over it primes the generator).
+        temperature / top_k / top_p (mode "sample"; each a scalar or one entry per utterance): divide the logits by the
+        temperature, keep the top_k most likely classes, keep the smallest set of classes holding top_p of the mass, then
+        draw with the step's usual uniform; the mixture-of-logistics head takes the temperature only (on the mixture
+        choice and the logistic noise).  The defaults are the plain draw."""
+        ctl = dict(temperature=temperature, top_k=top_k, top_p=top_p)
         if prompt is not None:
             p = self._check_generation(batch_size, prompt)
+            self._check_sampling(batch_size, ctl, "generate")
             eng = self._primary or self._engine(1, self._default_length)
-            st = eng.generation_state(int(batch_size), self._generation_cond(encoding, conditions), seed)
+            st = eng.generation_state(int(batch_size), self._generation_cond(encoding, conditions), seed, **ctl)
             eng.prime(st, p)
             f = None if forced is None else torch.as_tensor(np.asarray(forced, dtype=np.float32), device="cuda")
             a, c, lg = eng.generate_chunk(st, int(num_samples), mode=mode, forced=f, want_logits=return_logits)
@@ -313,6 +319,7 @@ class WaveNetTeacher(_EngineOwner):
         if self.gate_mode == "wavenet":
             raise NotImplementedError("generation: gate_mode 'wavenet' is trained only (the generation kernels implement "
                                       "the reference gate)")
+        self._check_sampling(batch_size, ctl, "generate")
         eng = self._primary or self._engine(1, self._default_length)
         f = None if forced is None else torch.as_tensor(np.asarray(forced, dtype=np.float32), device="cuda")
         cond = None
@@ -325,22 +332,25 @@ class WaveNetTeacher(_EngineOwner):
                 cond = torch.cat([cond, c[:, None, :].expand(-1, cond.shape[1], -1)], dim=2)
             cond = cond.contiguous()
         a, c, lg = eng.generate(int(num_samples), mode=mode, seed=seed, forced=f, want_logits=return_logits,
-                                batch=int(batch_size), cond=cond)
+                                batch=int(batch_size), cond=cond, **ctl)
         if return_logits:
             return a.cpu().numpy(), c.cpu().numpy(), lg.cpu().numpy()
         return a.cpu().numpy()
 
     def stream(self, batch_size, chunk_size, mode="sample", seed=0, prompt=None, encoding=None, conditions=None,
-               max_samples=None):
+               max_samples=None, *, temperature=1.0, top_k=0, top_p=1.0):
         """Real-time generation: an iterator of NumPy [B, chunk_size] blocks (the last one shorter where max_samples or
         the encoding ends), each back as soon as its samples exist.  The blocks put together are generate(..., seed) bit
         for bit.  prompt [B, P]: continue from it.  A conditioned decoder stops where the encoding's frames run out
-        (frames * pool_stride samples in all, the prompt included); otherwise the stream ends only at max_samples."""
+        (frames * pool_stride samples in all, the prompt included); otherwise the stream ends only at max_samples.
+        temperature / top_k / top_p: the sampling controls of `generate`, for the whole stream."""
         p = self._check_generation(batch_size, prompt)
         if int(chunk_size) < 1:
             raise ValueError("chunk_size must be >= 1")
+        ctl = dict(temperature=temperature, top_k=top_k, top_p=top_p)
+        self._check_sampling(batch_size, ctl, "stream")
         eng = self._primary or self._engine(1, self._default_length)
-        st = eng.generation_state(int(batch_size), self._generation_cond(encoding, conditions), seed)
+        st = eng.generation_state(int(batch_size), self._generation_cond(encoding, conditions), seed, **ctl)
         if p is not None:
             eng.prime(st, p)
         return _stream_chunks(eng, st, int(chunk_size), mode, max_samples)
@@ -364,6 +374,13 @@ class WaveNetTeacher(_EngineOwner):
                 raise ValueError("this teacher is not conditioned: no encoding")
             return None
         return _pool_encodings(n, encoding, conditions, self.latent_channels, self.condition_size)
+
+    def _check_sampling(self, n, ctl, who):
+        """The sampling controls' ranges, before any device work (engine.sampling_table)."""
+        from .engine import sampling_table
+        mol = self.head == "mol"
+        sampling_table(int(n), ctl["temperature"], ctl["top_k"], ctl["top_p"],
+                       64 if mol else int(self.quantization_channels), mol, who)      # (a mixture head refuses top_k)
 
     def _check_generation(self, batch_size, prompt):
         """What generation refuses before any device work; returns the prompt as float32 [B, P] (or None)."""
@@ -470,7 +487,10 @@ class GenerationPool(object):
     def t(self):
         return self._pool.t
 
-    def join(self, seed, prompt=None, encoding=None, conditions=None, max_samples=None):
+    def join(self, seed, prompt=None, encoding=None, conditions=None, max_samples=None, *, temperature=None, top_k=None,
+             top_p=None):
+        """temperature / top_k / top_p: the joining streams' sampling controls (a scalar or one entry per stream; None = the
+        default), as `generate` takes them."""
         seeds = [int(s) for s in (seed if np.ndim(seed) else [seed])]
         n = len(seeds)
         prompts = _per_stream(prompt, n, "prompts")
@@ -480,7 +500,9 @@ class GenerationPool(object):
         prompts = [None if p is None else np.asarray(p, dtype=np.float32) for p in prompts]
         mx = _per_stream(max_samples, n, "max_samples")
         cond = self._cond_fn(n, encoding, conditions)
-        return self._pool.join(seeds, prompts, cond, mx)
+        if temperature is None and top_k is None and top_p is None:
+            return self._pool.join(seeds, prompts, cond, mx)
+        return self._pool.join(seeds, prompts, cond, mx, temperature=temperature, top_k=top_k, top_p=top_p)
 
     def step(self, n, mode=None, forced=None):
         a, _, _, ran = self._pool.step(int(n), mode=mode or self.mode, forced=forced)
@@ -640,13 +662,17 @@ class WaveNetAutoEncoder(object):
         self._put_encoding(eng, encoding)
         return eng.dec.forward(want_logits=True, with_loss=False).cpu().numpy()
 
-    def generate(self, encoding, conditions=None, num_samples=None, mode="sample", seed=0, prompt=None):
+    def generate(self, encoding, conditions=None, num_samples=None, mode="sample", seed=0, prompt=None, *,
+                 temperature=1.0, top_k=0, top_p=1.0):
         """Queue-cached autoregressive sampling from the decoder given an encoding (the O(T L) replacement of the
         reference's sample-by-sample loop over ``reconstruct_with_encoding``, generator.py:150-170 /
         teacher.py:140-171): audio [B, num_samples] in [-1, 1].  prompt [B, P]: the num_samples (default: the rest of
-        the encoding) that follow the prompt's P samples."""
+        the encoding) that follow the prompt's P samples.  temperature (mode "sample"; a scalar or one entry per
+        utterance): on the mixture choice and the logistic noise; top_k / top_p do not apply to a mixture head."""
+        ctl = dict(temperature=temperature, top_k=top_k, top_p=top_p)
+        self._check_sampling(np.shape(encoding)[0] if np.ndim(encoding) == 3 else 1, ctl, "generate")
         if prompt is not None:
-            eng, st, p = self._prompted_state(encoding, conditions, seed, prompt)
+            eng, st, p = self._prompted_state(encoding, conditions, seed, prompt, ctl)
             rest = st.limit - p.shape[1]
             T = int(num_samples) if num_samples is not None else rest
             if T > rest:
@@ -666,16 +692,19 @@ class WaveNetAutoEncoder(object):
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
             e = torch.cat([e, c[:, None, :].expand(-1, frames, -1)], dim=2)               # model.py:161-167
         eng = self._eng or self._engine(B, frames * self.pool_stride)
-        a, _, _ = eng.dec.generate(T, mode=mode, seed=seed, batch=B, cond=e.contiguous())
+        a, _, _ = eng.dec.generate(T, mode=mode, seed=seed, batch=B, cond=e.contiguous(), **ctl)
         return a.cpu().numpy()
 
-    def stream(self, encoding, conditions=None, chunk_size=160, mode="sample", seed=0, prompt=None, max_samples=None):
+    def stream(self, encoding, conditions=None, chunk_size=160, mode="sample", seed=0, prompt=None, max_samples=None, *,
+               temperature=1.0, top_k=0, top_p=1.0):
         """Real-time decoding: an iterator of NumPy [B, chunk_size] blocks that ends where the encoding's frames run out
         (or at max_samples); put together they are generate(encoding, ..., seed=seed) bit for bit.  prompt [B, P]: the
-        samples after it."""
+        samples after it.  temperature: as `generate`, for the whole stream."""
         if int(chunk_size) < 1:
             raise ValueError("chunk_size must be >= 1")
-        eng, st, _ = self._prompted_state(encoding, conditions, seed, prompt)
+        ctl = dict(temperature=temperature, top_k=top_k, top_p=top_p)
+        self._check_sampling(np.shape(encoding)[0] if np.ndim(encoding) == 3 else 1, ctl, "stream")
+        eng, st, _ = self._prompted_state(encoding, conditions, seed, prompt, ctl)
         return _stream_chunks(eng.dec, st, int(chunk_size), mode, max_samples)
 
     def generation_pool(self, capacity, frames, mode="sample"):
@@ -692,7 +721,12 @@ class WaveNetAutoEncoder(object):
     def _pool_cond(self, n, encoding, conditions):
         return _pool_encodings(n, encoding, conditions, self.latent_channels, self.condition_size)
 
-    def _prompted_state(self, encoding, conditions, seed, prompt):
+    def _check_sampling(self, n, ctl, who):
+        """The sampling controls' ranges, before any device work (engine.sampling_table): a mixture head."""
+        from .engine import sampling_table
+        sampling_table(int(n), ctl["temperature"], ctl["top_k"], ctl["top_p"], 64, True, who)      # (top_k is refused: C unused)
+
+    def _prompted_state(self, encoding, conditions, seed, prompt, ctl=None):
         enc = np.asarray(encoding, dtype=np.float32)
         if enc.ndim != 3 or enc.shape[2] != self.latent_channels:
             raise ValueError("encoding must be [batch, frames, latent_channels]")
@@ -707,7 +741,7 @@ class WaveNetAutoEncoder(object):
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
             e = torch.cat([e, c[:, None, :].expand(-1, frames, -1)], dim=2)               # model.py:161-167
         eng = self._eng or self._engine(B, frames * self.pool_stride)
-        st = eng.dec.generation_state(B, e.contiguous(), seed)
+        st = eng.dec.generation_state(B, e.contiguous(), seed, **(ctl or {}))
         if p is not None:
             eng.dec.prime(st, p)
         return eng, st, p

@@ -191,6 +191,29 @@ def categorical_sample(logits, d=None, seed=0):
     call("srwn_categorical_sample", x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], int(seed), K._stream())
     return out.reshape(shp[:-1]).long()
 
+def sample_filtered(logits, uniforms, temperature=1.0, top_k=0, top_p=1.0):
+    """The generators' filtered draw on rows the caller chooses (srwn.h, SrwnGenSampling): one class index per row of
+    ``logits`` [rows, C <= 256] from softmax(logits / temperature) cut to the top_k most likely classes and then to the
+    smallest set holding top_p of the mass, drawn with ``uniforms`` [rows] in (0, 1) by inclusive prefix sums in class
+    order.  temperature / top_k / top_p: a scalar or one entry per row; the defaults are the plain draw."""
+    from ._lib import call
+    from .engine import sampling_table, _sampling_to_device
+    x = logits.to(device="cuda", dtype=torch.float32).contiguous()
+    shp = x.shape
+    x = x.reshape(-1, shp[-1])
+    u = torch.as_tensor(uniforms).to(device="cuda", dtype=torch.float32).contiguous().reshape(-1)
+    if u.numel() != x.shape[0]:
+        raise ValueError("sample_filtered: %d uniforms for %d rows" % (u.numel(), x.shape[0]))
+    if not 1 <= x.shape[1] <= 256:
+        raise ValueError("sample_filtered: C %d: 1..256 classes" % x.shape[1])
+    tab = sampling_table(x.shape[0], temperature, top_k, top_p, x.shape[1], False, "sample_filtered")
+    sdev = None if tab is None else _sampling_to_device(tab, x.device)
+    out = torch.empty((x.shape[0],), dtype=torch.int32, device="cuda")
+    call("srwn_sample_filtered", x.data_ptr(), x.shape[1], None if sdev is None else sdev.data_ptr(), u.data_ptr(),
+         out.data_ptr(), x.shape[0], x.shape[1], K._stream())
+    return out.reshape(shp[:-1]).long()
+
+
 
 def log_prob_from_logits(x):
     """ops.py:111-115: numerically stable log-softmax over the last axis."""
