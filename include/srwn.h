@@ -767,6 +767,64 @@ int srwn_flow_affine_bwd(const void* h, const float* w2, const float* prm, const
 int srwn_clamp(const float* x, float* y, int64_t n, float lo, float hi, void* stream);
 int srwn_clamp_bwd(const float* x, const float* dy, float* dx, int64_t n, float lo, float hi, void* stream);
 
+/* ---- chunked synthesis with the student (since srwn_version() 107): the flows of model.py:415-535 as an inference-only
+ * stream.  A batch of B streams is synthesised in chunks [t0, t0 + n) of absolute time, t0 read from a DEVICE clock (one
+ * int64 per synthesizer state), so the same launch arguments -- and a captured graph -- serve every chunk of a size.
+ * Per flow and stream the state is the carry (the flow input's samples x[t0-1], x[t0-2], fp32 [B,2]) and, for every
+ * layer group (srwn_group_plan), a boundary buffer [B][hist + max_chunk][R] (dtype) whose first hist = sum of the group's
+ * dilations rows hold the group's input rows of times [t0 - hist, t0) (zeros at the start) and whose next n rows hold
+ * the chunk.  A tap or a conditioning frame is taken by absolute time: a tap at t < 0 is the conv's zero padding at every
+ * layer (ops.py:9), the frame of time t is clamp(t / pool_stride, 0, cond_frames - 1).  Every stored value has the bits
+ * the whole-clip entry points give it.  Argument errors return SRWN_E_* before anything is launched: a null pointer
+ * (-3), n < 1 or n > max_chunk or buffers too short (-2), R other than 32 / 64, K other than 2 or a group whose halo
+ * (sum of dilations / their gcd) exceeds 31 (-4), an unknown dtype (-1).
+ *
+ *   srwn_flow_stream_in     model.py:423-424 + 431-435 for rows [hist, hist + n) of the flow's first boundary buffer:
+ *                           RightShift + the K = 2 input conv (init_w [2,1,R], init_b [R], fp32) on x [B, x_stride]
+ *                           fp32 (rows t < 0 of the chunk from the carry), rounded to dtype as srwn_causal_conv1d_fwd
+ *                           rounds, then + cond0[b, frame] (the first layer's conditioning bias, rows of
+ *                           cond_row_stride elements, cond_frames rows per stream) rounded as srwn_add_frame_bias.
+ *   srwn_residual_group_fwd_stream
+ *                           model.py:428-453 for one layer group (ops.py:23-46 per layer): srwn_residual_group_fwd on
+ *                           the buffer x_in [B][in_clip_rows][R] = [hist history rows | n chunk rows], segments cut
+ *                           over the chunk rows only, and ONLY the top layer's chunk rows stored, to rows
+ *                           [out_hist, out_hist + n) of x_out [B][out_clip_rows][R] (the next group's buffer, or the
+ *                           flow's top buffer with out_hist = 0).  No z, no inner layer's output.  cond_next[g] = the
+ *                           conditioning bias of the layer above layer g, or NULL.  A group of one layer is allowed.
+ *   srwn_flow_stream_out    model.py:451-452, 479-483 (+ 535 with clamp != 0) on rows [0, n) of the flow's top buffer
+ *                           h [B][top_clip_rows][R]: x_out = x_in * exp(p0) + p1 in srwn_flow_affine_fwd's arithmetic
+ *                           (x_in, x_out fp32 [B, x_stride]); renews the carry from x_in; moves rows [n, n + hist) of
+ *                           every buffer of roll_table (nroll int64 triples {address, rows per stream, hist}, a device
+ *                           array) to its front -- the next chunk's history; an overlapping move when n < hist, walked
+ *                           front to back -- and, with advance_clock != 0 (the last flow), adds n to *clock.
+ *   srwn_logistic_noise     the first flow's input (student.py:100 draws it on the host): noise[b, j] = temperature[b]
+ *                           * (log u - log(1 - u)), u from the counter-based bits of (seed[b], *clock + j): splitmix64
+ *                           as srwn_categorical_sample mixes it, the TOP 23 BITS k of the result, u = (k + 1/2) / 2^23.
+ *                           So 2^-24 <= u <= 1 - 2^-24, both u and 1 - u are exact and positive in fp32 and every
+ *                           draw is finite (|noise| <= 16.64).  Evaluated as +-log1p(|2u - 1| / min(u, 1 - u)), whose
+ *                           operands are exact: a few ulp at every u, also where log u - log(1 - u) would cancel.
+ *                           temperature, seed: device arrays [B] (fp32, uint64).  temperature 0 writes +0.
+ *   srwn_logistic_from_bits out[i] = log u - log(1 - u) for k = bits[i] & 0x7fffff: the map above on bits the caller
+ *                           chooses (tests: k = 0 and k = 2^23 - 1). */
+int srwn_flow_stream_in(const float* x, int64_t x_stride, const float* carry, const float* init_w, const float* init_b,
+                        const void* cond0, int32_t cond_frames, int32_t pool_stride, int64_t cond_row_stride, void* out,
+                        int64_t out_clip_rows, int32_t out_hist, int32_t B, int32_t n, int32_t max_chunk, int32_t R,
+                        int32_t dtype, const int64_t* clock, void* stream);
+int srwn_residual_group_fwd_stream(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                   int32_t out_hist, const void* const* wconv, const void* const* wres,
+                                   const float* const* bias_f, const float* const* bias_r,
+                                   const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                   int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers, int32_t B,
+                                   int32_t n, int32_t max_chunk, int32_t R, int32_t K, int32_t dtype,
+                                   const int64_t* clock, void* stream);
+int srwn_flow_stream_out(const void* h, int64_t top_clip_rows, const float* flow_w, const float* flow_b,
+                         const float* x_in, float* x_out, int64_t x_stride, float* carry, int32_t clamp,
+                         const int64_t* roll_table, int32_t nroll, int32_t B, int32_t n, int32_t max_chunk, int32_t R,
+                         int32_t dtype, int64_t* clock, int32_t advance_clock, void* stream);
+int srwn_logistic_noise(float* noise, int64_t noise_stride, const float* temperature, const uint64_t* seed,
+                        const int64_t* clock, int32_t B, int32_t n, void* stream);
+int srwn_logistic_from_bits(const uint32_t* bits, float* out, int64_t n, void* stream);
+
 /* ---- data gradient of _DilatedCausalConv1d (ops.py:6-10) wrt a narrow input (the 1-channel flow input,
  * model.py:423-424); `shift` is the adjoint of RightShift (ops.py:78-80):
  *   dx[b,u,i] (+)= scale * sum_k sum_o w[k,i,o] * dy[b, u + shift + (K-1-k)*dilation, o]   (0 beyond the clip)

@@ -171,6 +171,15 @@ SIGNATURES = {
     "srwn_flow_partials": (_i64, [_i64]),
     "srwn_flow_affine_fwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     "srwn_flow_affine_bwd": (C.c_int, [_p, _p, _p, _p, _p, _f32, _p, _p, _p, _i64, _i32, _i32, _p]),
+    # chunked synthesis with the student (srwn_version() 107)
+    "srwn_flow_stream_in": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i32, _i64, _p, _i64, _i32, _i32, _i32, _i32, _i32,
+                                      _i32, _p, _p]),
+    "srwn_residual_group_fwd_stream": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p, _i32,
+                                                 _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "srwn_flow_stream_out": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p,
+                                       _i32, _p]),
+    "srwn_logistic_noise": (C.c_int, [_p, _i64, _p, _p, _p, _i32, _i32, _p]),
+    "srwn_logistic_from_bits": (C.c_int, [_p, _p, _i64, _p]),
     "srwn_causal_conv1d_dgrad": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _p]),
     "srwn_stft_frames": (_i32, [_i32]),
     "srwn_stft_power": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p]),

@@ -18,6 +18,7 @@
 //   stream into the second weight buffer while layer g computes.
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 #include "srwn_common.h"
 #include "srwn_group.h"
@@ -58,6 +59,19 @@ struct GroupFwdArgs {
   const float* ic_audio; const float* ic_w; const float* ic_b; int ic_shift;
 };
 
+// The STREAM instantiations (srwn_residual_group_fwd_stream: chunked inference, no backward pass) take these on top.  The
+// input is [B][in_clip_rows][R], of which rows [0, hrows) are the group's HISTORY -- the last hrows = st * H rows of its
+// input before the chunk -- and rows [hrows, hrows + n) the chunk; Tlen = hrows + n.  Buffer row 0 sits at absolute time
+// *clock - hrows.  Segments are cut over the chunk's rows only (positions j >= H of every residue class); the history is
+// read as halo, never owned.  Only the top layer's owned rows are stored: chunk row t of stream b at
+// x_out + ((b * out_clip_rows) + out_hist + t) * R.
+struct GroupFwdStreamArgs : GroupFwdArgs {
+  const long long* clock;         // device scalar: absolute time of the chunk's first row
+  int hrows;                      // st * H: history rows in front of the chunk
+  int st_act;                     // residue classes that hold a chunk row: min(st, n)
+  long long in_clip_rows, out_clip_rows, out_row_off;   // out_row_off = out_hist - hrows (buffer row -> output row)
+};
+
 // In-kernel time stamps (MI355X guide, "In-kernel stamps"): lane 0 of waves 0 and 1 of workgroup 0 append the shader
 // clock to a buffer no other code reads.  Compiled in only when a buffer was registered (STAMP instantiation).
 template <bool STAMP> struct Stamper {
@@ -79,9 +93,11 @@ template <> struct Stamper<true> {
   }
 };
 
-template <typename T, int RT, bool COND, int MAXT, int NWB, int NWV = 8, bool WDMA = true, bool STAMP = false, bool WT = false, bool IC = false>
-__global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
+template <typename T, int RT, bool COND, int MAXT, int NWB, int NWV = 8, bool WDMA = true, bool STAMP = false, bool WT = false, bool IC = false,
+          bool STREAM = false>
+__global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type a) {
   static_assert(!IC || (WT && !COND), "input conv fused in: the unconditioned weight-gradient-tile kernels only");
+  static_assert(!STREAM || (COND && !WT && !IC && !STAMP), "stream form: the conditioned plain kernels only");
   constexpr int R = 32 * RT, K = 2, KS = R / 16;
   constexpr int NCONV = RT * K * KS, NRES = RT * KS, NW = NCONV + NRES;   // weight fragments per layer
   constexpr int LS = RowStage<T>::stride(R), VEC = RowStage<T>::VEC;
@@ -153,19 +169,34 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
     if (tid < 2 * R / 4) *reinterpret_cast<f32x4*>(bbuf + buf * 2 * R + 4 * tid) = breg;
   };
 
+  // (STREAM) what the chunk's place in absolute time fixes, once per workgroup: buffer rows before `pad` lie before the
+  // stream's start (the conv's zero padding at every layer), and buffer row t_buf lies in conditioning frame
+  // fq0 + (frem0 + t_buf) / pool (frame 0 before the start)
+  int pad = 0, fq0 = 0, frem0 = 0;
+  if constexpr (STREAM) {
+    const long long c0 = *a.clock - a.hrows;
+    if (c0 >= 0) { fq0 = (int)(c0 / a.pool); frem0 = (int)(c0 - (long long)fq0 * a.pool); }
+    else { pad = (int)(-c0); frem0 = (int)c0; }
+  }
+
   for (int sblk = blockIdx.x; sblk < a.nseg; sblk += gridDim.x) {
     const int seg = xcd_segment(sblk, a.nseg);
     // segment -> (clip b, residue r, first position j0); consecutive ids = neighbouring memory
-    const int per_clip = a.st * a.nsub;
+    int per_clip_;
+    if constexpr (STREAM) per_clip_ = a.st_act * a.nsub; else per_clip_ = a.st * a.nsub;
+    const int per_clip = per_clip_;
     const int b = seg / per_clip;
     const int rem = seg - b * per_clip;
     int r, j0;
     if (a.nsub == 1) { r = rem; j0 = 0; }
     else { r = rem / a.nsub; j0 = (rem - r * a.nsub) * a.W; }
+    if (STREAM) j0 += a.H;                                     // (the history's positions are nobody's segment)
     const int Jr = (a.Tlen - r + a.st - 1) / a.st;             // positions of this residue class (may be 0)
     const int Wseg = (Jr - j0) < a.W ? (Jr - j0) : a.W;        // positions this segment owns (<= 0: nothing to do)
     const int jbase = j0 - a.H;                                // position of image row 0
-    const size_t clip = (size_t)b * a.Tlen;
+    size_t clip_;
+    if constexpr (STREAM) clip_ = (size_t)b * (size_t)a.in_clip_rows; else clip_ = (size_t)b * a.Tlen;
+    const size_t clip = clip_;
     // global row (element offset / R) of position j, clamped into the residue class
     auto grow = [&](int j) -> size_t {
       int jj = j < 0 ? 0 : j;
@@ -224,7 +255,9 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
           int i = i0 + u * RPP + tid / LPR;
           i = i < nrows ? i : nrows - 1;
           // (non-temporal, like the backward kernel's row loads: read once, the halo rows twice)
-          v[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(x0 + grow(jbase + i) * R + (tid % LPR) * VEC));
+          const f32x4* src = reinterpret_cast<const f32x4*>(x0 + grow(jbase + i) * R + (tid % LPR) * VEC);
+          if constexpr (STREAM) v[u] = *src;      // (the rows stay hot: the history roll and the next chunk read them again)
+          else v[u] = __builtin_nontemporal_load(src);
         }
 #pragma unroll
         for (int u = 0; u < UN; ++u) {
@@ -283,7 +316,7 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
       wg_barrier();
       stamp(11);
       const bool more = g + 1 < a.nl;
-      const bool xrows = !WT || a.store_inner_x || !more;   // the layer's output rows go to HBM (WT: the group's top layer only)
+      const bool xrows = STREAM ? !more : (!WT || a.store_inner_x || !more);   // the layer's output rows go to HBM (WT, STREAM: the group's top layer only)
       if (NWB == 2 && more) wload(g + 1, wb ^ 1);
 
       const Frag<T>* lds_conv = wbuf + (size_t)wb * NW * 64;
@@ -302,13 +335,16 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
         if (WT && !more && q < a.H / 32) continue;
         T* trow = img + (size_t)(32 * q) * LS;           // the tile's own rows
         const int j = jbase + 32 * q + col;              // this lane's position
-        const bool ok0 = (j - d) >= 0;                   // causal zero padding of the delayed tap (ops.py:9)
+        // causal zero padding of the delayed tap (ops.py:9); STREAM: by absolute time, at every layer (pad = 0 once the
+        // stream is hrows old: then only the taps in front of the buffer, which feed no owned row)
+        const bool ok0 = STREAM ? ((j - d) * a.st + r >= pad) : ((j - d) >= 0);
         // rows of this tile that exist and belong to the segment: [lo, hi)
         int lo = a.H - 32 * q;
         lo = lo < 0 ? 0 : lo;
         int hi = a.H + Wseg - 32 * q;
         hi = hi > 32 ? 32 : hi;
         const bool st_ok = hi > lo;
+        if (STREAM && !more && !st_ok) continue;         // a history tile of the top layer feeds nothing
 
         Frag<T> cur1[KS];
 #pragma unroll
@@ -371,7 +407,7 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
               cf[2 * mt + (qq >> 3)].set(qq & 7, gate_of_z<T>(z));
             }
           if (STAMP) { asm volatile("" :: "v"(zz[0][0])); stamp(13); }
-          if (st_ok) {
+          if (!STREAM && st_ok) {       // (STREAM: no backward pass reads z)
             wave_lds_order();             // the reads of the own rows above are done
 #pragma unroll
             for (int mt = 0; mt < RT; ++mt)
@@ -416,7 +452,13 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
         if (COND && cg) {
           have_cnd = true;
           const unsigned t = (unsigned)(grow(j) - clip);      // time step of this lane's row (clamped)
-          const T* crow_ = cg + ((size_t)b * a.cond_frames + t / (unsigned)a.pool) * a.cond_stride;
+          unsigned frame = t / (unsigned)a.pool;
+          if constexpr (STREAM) {
+            const int tr = frem0 + (int)t;
+            frame = (unsigned)fq0 + (tr < 0 ? 0u : (unsigned)tr / (unsigned)a.pool);
+            frame = frame < (unsigned)a.cond_frames ? frame : (unsigned)a.cond_frames - 1u;
+          }
+          const T* crow_ = cg + ((size_t)b * a.cond_frames + frame) * a.cond_stride;
 #pragma unroll
           for (int mt = 0; mt < RT; ++mt)
 #pragma unroll
@@ -462,13 +504,17 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(GroupFwdArgs a) {
               int rr = i * RPI + rsub;
               rr = rr < lo ? lo : (rr < hi ? rr : hi - 1);
               const f32x4 v = *reinterpret_cast<const f32x4*>(trow + (size_t)rr * LS + piece * VEC);
+              if constexpr (STREAM) {      // (plain store: the next launch reads these rows)
+                const long long orow = (long long)b * a.out_clip_rows + a.out_row_off + (long long)(grow(jbase + 32 * q + rr) - clip);
+                *reinterpret_cast<f32x4*>(reinterpret_cast<T*>(a.x_out) + orow * R + piece * VEC) = v;
+              } else
               *reinterpret_cast<f32x4*>(xg + grow(jbase + 32 * q + rr) * R + piece * VEC) = v;
             }
           }
         }
         stamp(16);
       }
-      if (NWB == 2 && more) wstore(wb ^ 1, nstored, xrows);
+      if (NWB == 2 && more) wstore(wb ^ 1, STREAM ? 0 : nstored, xrows);      // (STREAM: an inner layer issues no store)
       stamp(17);
       wg_barrier();
       stamp(18);
@@ -1269,6 +1315,11 @@ __global__ __launch_bounds__(64 * NWV) void group_bwd_kernel(GroupBwdArgs a) {
   }
 }
 
+// waves and tiles per wave of the bf16 R = 64 stream body (an A/B build may pass others)
+#ifndef SRWN_GFS_WAVES
+#define SRWN_GFS_WAVES 8
+#define SRWN_GFS_MAXT 3
+#endif
 unsigned long long* g_stamps = nullptr;
 // tiles the forward / backward group kernels can hold per segment image (LDS and waves x tiles per wave)
 template <typename T, int RT, int MAXT, int NWB, int NWV> int fwd_nt_max() {
@@ -1328,6 +1379,45 @@ int launch_group_fwd(GroupFwdArgs& a, bool cond, int seg_rows, hipStream_t st) {
   }
   if (cond) SRWN_GF(true) else SRWN_GF(false)
 #undef SRWN_GF
+}
+
+// The stream form: segments over the chunk's positions of every residue class that holds a chunk row; the halo is always
+// the whole H (the history supplies it).  The cut depends on (B, n, st, H) and the chip alone -- never on the clock -- so a
+// captured launch stays valid for every chunk of its size.
+template <typename T, int RT, int MAXT, int NWB, int NWV = 8>
+int launch_group_fwd_stream(GroupFwdStreamArgs& a, int n, hipStream_t st) {
+  constexpr int R = 32 * RT, KS = R / 16, NW = RT * 2 * KS + RT * KS;
+  const size_t fixed = (size_t)NWB * NW * 64 * sizeof(Frag<T>) + (size_t)NWB * 2 * R * 4;
+  const size_t row_bytes = (size_t)RowStage<T>::stride(R) * sizeof(T);
+  const int nt_max = fwd_nt_max<T, RT, MAXT, NWB, NWV>();
+  const int wmax = nt_max * 32 - a.H;
+  if (wmax < 32) return set_error(SRWN_E_UNSUPPORTED, "residual_group_fwd_stream: halo %d too large", a.H);
+  a.st_act = a.st < n ? a.st : n;
+  const int J = (n + a.st - 1) / a.st;                       // chunk positions of the fullest residue class
+  int ns = (J + wmax - 1) / wmax;                            // fewest segments the image size allows
+  const long long streams = (long long)a.B * a.st_act;
+  long long want = (num_cus() + streams - 1) / streams;      // enough segments for one per CU ...
+  const int floor_w = 32 * NWV - a.H;                        // ... while a segment still fills one round of the waves' tiles
+  long long cap = J / floor_w; if (cap < 1) cap = 1;
+  if (want > cap) want = cap;
+  if (want > ns) ns = (int)want;
+  int w = (J + ns - 1) / ns;
+  if (w < 1) w = 1;
+  a.W = w;
+  a.nsub = (J + w - 1) / w;
+  a.NT = (a.H + w + 31) / 32;
+  const long long nseg = streams * a.nsub;
+  if (nseg > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: too many segments");
+  a.nseg = (int)nseg;
+  const size_t sh = fixed + (size_t)a.NT * 32 * row_bytes;
+  const int grid_cap = group_grid();
+  const long long blocks = nseg < grid_cap ? nseg : grid_cap;
+  dim3 grid((unsigned)blocks), block(64 * NWV);
+  auto kfn = group_fwd_kernel<T, RT, true, MAXT, NWB, NWV, true, false, false, false, true>;
+  hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
+  if (e != hipSuccess) return set_error((int)e, "residual_group_fwd_stream: LDS %zu: %s", sh, hipGetErrorString(e));
+  hipLaunchKernelGGL(kfn, grid, block, sh, st, a);
+  return check_launch("residual_group_fwd_stream");
 }
 
 template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool WT = false>
@@ -1587,6 +1677,64 @@ extern "C" int srwn_residual_group_fwd_wt(const void* x0, void* x_out, void* z_o
   return group_fwd_impl(x0, x_out, z_out, layer_stride, wconv, wres, bias_f, bias_r, cond_next, cond_frames, pool_stride,
                         cond_row_stride, dilations, nlayers, B, T, R, K, seg_rows, dtype, stream, xT, cT, wt_layer_stride,
                         store_inner_x);
+}
+
+// The inference / stream form of srwn_residual_group_fwd (srwn.h): one chunk of a batch of streams, the group's causal
+// context taken from the history rows in front of the chunk, time taken from a device clock.
+extern "C" int srwn_residual_group_fwd_stream(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                              int32_t out_hist, const void* const* wconv, const void* const* wres,
+                                              const float* const* bias_f, const float* const* bias_r,
+                                              const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                              int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers,
+                                              int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t K,
+                                              int32_t dtype, const int64_t* clock, void* stream) {
+  if (!x_in || !x_out || !wconv || !wres || !bias_f || !bias_r || !dilations || !clock)
+    return set_error(SRWN_E_NULL, "residual_group_fwd_stream: null pointer (the clock is the synthesizer state's device scalar)");
+  if (K != 2) return set_error(SRWN_E_UNSUPPORTED, "residual_group_fwd_stream: filter_width %d (only 2 is built)", K);
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "residual_group_fwd_stream: dilation_channels %d (built: 32, 64)", R);
+  if (nlayers < 1 || nlayers > kMaxGroup || B < 1 || max_chunk < 1 || out_hist < 0)
+    return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: nlayers=%d (max %d) B=%d max_chunk=%d out_hist=%d", nlayers, kMaxGroup, B, max_chunk, out_hist);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
+  GroupFwdStreamArgs a;
+  a.safe_wait = safe_wait();
+  a.x0 = x_in; a.x_out = x_out; a.z_out = nullptr; a.layer_stride = 0;
+  a.xT = nullptr; a.cT = nullptr; a.wt_stride = 0; a.KT = 0; a.store_inner_x = 0;
+  a.ic_audio = nullptr; a.ic_w = nullptr; a.ic_b = nullptr; a.ic_shift = 0;
+  bool any_cond = false;
+  for (int g = 0; g < kMaxGroup; ++g) {
+    const bool in = g < nlayers;
+    a.wconv[g] = in ? wconv[g] : nullptr; a.wres[g] = in ? wres[g] : nullptr;
+    a.bias_f[g] = in ? bias_f[g] : nullptr; a.bias_r[g] = in ? bias_r[g] : nullptr;
+    a.cond[g] = (in && cond_next) ? cond_next[g] : nullptr;
+    a.sub[g] = 1;
+    if (in && (!a.wconv[g] || !a.wres[g] || !a.bias_f[g] || !a.bias_r[g]))
+      return set_error(SRWN_E_NULL, "residual_group_fwd_stream: layer %d: null weights", g);
+    any_cond = any_cond || a.cond[g] != nullptr;
+  }
+  if (pool_stride < 1 || cond_frames < 1 || (any_cond && (cond_row_stride < R || cond_row_stride % 8)))
+    return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: cond frames %d, pool %d, row stride %d", cond_frames, pool_stride, cond_row_stride);
+  a.cond_frames = cond_frames; a.pool = pool_stride; a.cond_stride = cond_row_stride;
+  a.nl = nlayers; a.B = B; a.stamps = nullptr;
+  if (group_geometry(dilations, nlayers, &a.st, a.sub, &a.H) != 0)
+    return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: dilations must be >= 1");
+  if (a.H > 31) return set_error(SRWN_E_UNSUPPORTED, "residual_group_fwd_stream: halo %d > 31 (sum of dilations / their gcd)", a.H);
+  const long long hrows = (long long)a.st * a.H;
+  if (hrows + max_chunk > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: %lld history rows", hrows);
+  if (in_clip_rows < hrows + max_chunk || out_clip_rows < (long long)out_hist + max_chunk)
+    return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: buffers of %lld / %lld rows per stream for %lld + %d and %d + %d",
+                     (long long)in_clip_rows, (long long)out_clip_rows, hrows, max_chunk, out_hist, max_chunk);
+  a.hrows = (int)hrows; a.Tlen = (int)hrows + n;
+  a.clock = reinterpret_cast<const long long*>(clock);
+  a.in_clip_rows = in_clip_rows; a.out_clip_rows = out_clip_rows; a.out_row_off = (long long)out_hist - hrows;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) {
+    if (R == 32) return launch_group_fwd_stream<bf16_t, 1, 3, 2>(a, n, st);
+    return launch_group_fwd_stream<bf16_t, 2, SRWN_GFS_MAXT, 2, SRWN_GFS_WAVES>(a, n, st);
+  } else if (dtype == SRWN_F32) {
+    if (R == 32) return launch_group_fwd_stream<float, 1, 1, 1>(a, n, st);
+    return launch_group_fwd_stream<float, 2, 1, 1>(a, n, st);
+  }
+  return set_error(SRWN_E_DTYPE, "residual_group_fwd_stream: dtype %d", dtype);
 }
 
 // The FIRST group of a stack with the stack's input conv fused in (model.py:40 / 172-173; K = 2 taps, 1 -> R channels,

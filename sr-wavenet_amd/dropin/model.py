@@ -13,3 +13,4 @@ WaveNetTeacher = _m.WaveNetTeacher
 WaveNetAutoEncoder = _m.WaveNetAutoEncoder
 ParallelWaveNet = _m.ParallelWaveNet
 SiameseWaveNet = _m.SiameseWaveNet
+StudentSynthesizer = _m.StudentSynthesizer

@@ -864,6 +864,21 @@ class ParallelWaveNet(object):
             out.update(f.tf_variables("%s/Flow%d/Flow%d" % (self._name, i, i)))           # model.py:417,468,510
         return out
 
+    def synthesizer(self, max_batch=1, max_chunk=1600, max_frames=None):
+        """A ``StudentSynthesizer`` with this model's hyper-parameters and a COPY of its current flow parameters (a
+        snapshot: call it again after more training).  max_frames defaults to input_size // pool_stride."""
+        if self._primary is None:
+            self._engine(1, self.input_size)
+        syn = StudentSynthesizer(self.dilations, self.num_flows, filter_width=self.filter_width,
+                                 dilation_channels=self.dilation_channels, latent_channels=self.latent_channels,
+                                 condition_size=self.condition_size, pool_stride=self.pool_stride, name=self._name,
+                                 dtype=self._flow_cfg.dtype, max_batch=max_batch, max_chunk=max_chunk,
+                                 max_frames=max_frames or max(1, self.input_size // self.pool_stride))
+        for w, f in zip(syn._eng.weights, self._primary.flows):
+            w.params.copy_(f.params)
+        syn._eng.repack()
+        return syn
+
     # --- checkpointing (model.py:540-567) ---------------------------------------------------------------
     def load(self, sess, logdir):
         if self._teacher_dir is not None and self._teacher is not None:
@@ -933,6 +948,103 @@ class ParallelWaveNet(object):
     def reconstruct(self, sess, inputs, conditions=None):
         """The teacher's own reconstruction (``teacher_out``, model.py:651-656)."""
         return self._ae_teacher(inputs).reconstruct(inputs, conditions)
+
+
+class StudentSynthesizer(object):
+    """The deployable form of the student: the flows of a trained ``ParallelWaveNet`` (model.py:415-535) as a streaming
+    synthesizer (``student.FlowSynthesizer``), with no teacher anywhere.  It serves any batch <= ``max_batch`` and any
+    length = frames * pool_stride with frames <= ``max_frames``, in one call (``synthesize``) or chunk by chunk
+    (``stream``); the noise is drawn on the device from per-stream seeds (or given).  ``load`` reads what
+    ``ParallelWaveNet.save`` wrote, by the reference's variable names; the gate and skip variables a flow never reads are
+    ignored."""
+
+    def __init__(self, dilations, num_flows, filter_width=2, dilation_channels=32, latent_channels=16, condition_size=0,
+                 pool_stride=512, name="ParallelWaveNet", dtype=None, max_batch=1, max_chunk=1600, max_frames=32):
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        from .student import FlowSynthesizer
+        self.dilations, self.num_flows = list(dilations), int(num_flows)
+        self.filter_width, self.dilation_channels = filter_width, dilation_channels
+        self.latent_channels, self.condition_size, self.pool_stride = latent_channels, condition_size, pool_stride
+        self._name = name
+        self.max_batch, self.max_chunk, self.max_frames = int(max_batch), int(max_chunk), int(max_frames)
+        cfg = StackConfig(dilations=list(dilations), filter_width=filter_width, dilation_channels=dilation_channels,
+                          cond_channels=latent_channels + condition_size, pool_stride=pool_stride,
+                          dtype=dtype or _default_dtype())
+        self._eng = FlowSynthesizer(cfg, num_flows, max_batch=max_batch, max_chunk=max_chunk, max_frames=max_frames)
+
+    @property
+    def network_params(self):
+        out = {}
+        for i, w in enumerate(self._eng.weights):
+            out.update(w.tf_variables("%s/Flow%d/Flow%d" % (self._name, i, i)))           # model.py:417,468,510
+        return out
+
+    def load(self, logdir):
+        ok = _read_state(logdir, lambda: self.network_params)
+        if ok:
+            self._eng.repack()
+        return ok
+
+    @classmethod
+    def from_checkpoint(cls, logdir, dilations, num_flows, **kwargs):
+        """A synthesizer on the flows saved in `logdir` (``ParallelWaveNet.save``); the hyper-parameters are the
+        constructor's (the student's checkpoint holds variables only)."""
+        syn = cls(dilations, num_flows, **kwargs)
+        if not syn.load(logdir):
+            raise FileNotFoundError("%s: no student checkpoint (ParallelWaveNet.save writes one)" % logdir)
+        return syn
+
+    # ------------------------------------------------------------------------------------------------
+    def _begin(self, encoding, conditions, seed, temperature, noise):
+        enc = np.asarray(encoding, dtype=np.float32)
+        if enc.ndim != 3 or enc.shape[2] != self.latent_channels:
+            raise ValueError("encoding must be [batch, frames, latent_channels=%d]" % self.latent_channels)
+        B, frames = int(enc.shape[0]), int(enc.shape[1])
+        if not 1 <= B <= self.max_batch or not 1 <= frames <= self.max_frames:
+            raise ValueError("encoding of %d streams x %d frames: this synthesizer was built for max_batch=%d, max_frames=%d"
+                             % (B, frames, self.max_batch, self.max_frames))
+        e = torch.as_tensor(enc)
+        if self.condition_size > 0:
+            if conditions is None:
+                raise ValueError("this student was built with condition_size > 0; pass conditions [B, condition_size]")
+            c = np.asarray(conditions, dtype=np.float32)
+            if c.shape != (B, self.condition_size):
+                raise ValueError("conditions must be [%d, %d]" % (B, self.condition_size))
+            e = torch.cat([e, torch.as_tensor(c)[:, None, :].expand(-1, frames, -1)], dim=2)   # model.py:496-499
+        T = frames * self.pool_stride
+        nz = None
+        if noise is not None:
+            nz = torch.as_tensor(np.asarray(noise, dtype=np.float32))
+            if tuple(nz.shape) != (B, T):
+                raise ValueError("noise must be [%d, %d] (= frames * pool_stride)" % (B, T))
+            nz = nz.to("cuda")
+        st = self._eng.start(e.contiguous(), seed, temperature)
+        return st, nz, B, T
+
+    def _chunks(self, st, nz, T, size):
+        t = 0
+        while t < T:
+            n = min(size, T - t)
+            yield self._eng.step(st, n, None if nz is None else nz[:, t:t + n])
+            t += n
+
+    def synthesize(self, encoding, conditions=None, seed=0, temperature=1.0, noise=None):
+        """encoding [B, frames, latent_channels] -> audio [B, frames * pool_stride, 1] in [-1, 1] (model.py:535), made in
+        chunks of max_chunk.  seed / temperature: scalars or one per stream (a scalar seed s: stream b draws with s + b);
+        noise [B, T]: the logistic noise itself (``ParallelWaveNet.generate``'s `inputs`)."""
+        st, nz, B, T = self._begin(encoding, conditions, seed, temperature, noise)
+        out = torch.cat(list(self._chunks(st, nz, T, self.max_chunk)), dim=1)
+        return out.view(B, T, 1).cpu().numpy()
+
+    def stream(self, encoding, conditions=None, chunk_size=160, seed=0, temperature=1.0, noise=None):
+        """The same audio as an iterator of NumPy [B, chunk, 1] blocks (the last one shorter when chunk_size does not
+        divide the length); chunking never changes a sample."""
+        chunk_size = int(chunk_size)
+        if not 1 <= chunk_size <= self.max_chunk:
+            raise ValueError("chunk_size %d: 1..max_chunk = %d" % (chunk_size, self.max_chunk))
+        st, nz, B, T = self._begin(encoding, conditions, seed, temperature, noise)
+        return (c.view(B, -1, 1).cpu().numpy() for c in self._chunks(st, nz, T, chunk_size))
 
 
 class SiameseWaveNet(_EngineOwner):

@@ -417,3 +417,238 @@ class StudentEngine:
         self._g_fb.replay()
         self.allreduce_grads()
         self._g_opt.replay()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Inference: the flows as a chunked stream (csrc/srwn_stream.hip, srwn_residual_group_fwd_stream).  No teacher, no
+# training buffers: per flow the weights, one boundary buffer per layer group and a conditioning table.
+# ----------------------------------------------------------------------------------------------------------------------
+def stream_history_rows(dilations, groups=None) -> List[int]:
+    """Rows of its own input a layer group must keep between two chunks: the sum of its layers' dilations
+    (= stride x halo of the group kernel), for every group of ``srwn_group_plan``'s cut."""
+    dil = [int(d) for d in dilations]
+    groups = K.group_plan(dil, 31, 8) if groups is None else groups
+    return [sum(dil[l0:l1]) for l0, l1 in groups]
+
+
+class FlowWeights:
+    """The weight side of one flow without the training engine around it: ``FlowStack``'s parameter layout, reference
+    variable names and image packing (the forward images only), on buffers of its own."""
+
+    layout = staticmethod(FlowStack.layout)
+    param_count = staticmethod(FlowStack.param_count)
+    view = WaveNetEngine.view
+    wptr = WaveNetEngine.wptr
+    named_tensors = FlowStack.named_tensors
+    load_oracle_params = FlowStack.load_oracle_params
+
+    def __init__(self, cfg: StackConfig, device="cuda"):
+        self.cfg = cfg
+        self.dev = torch.device(device)
+        self.dt = cfg.dtype
+        self.L, self.R, self.Kw, self.E = len(cfg.dilations), cfg.dilation_channels, cfg.filter_width, cfg.cond_channels
+        self.S = cfg.skip_channels
+        self.Ep = (self.E + 15) // 16 * 16
+        self.sections = self.layout(cfg)
+        self.nparams = self.param_count(cfg)
+        self.params = torch.zeros(self.nparams, dtype=torch.float32, device=self.dev)
+        # the variables a flow never reads (ops.py:31-33, 44) exist in checkpoints only: stride-0 host placeholders, so that
+        # FlowStack.tf_variables can be asked for the names; `tf_variables` below drops them again
+        ph = torch.zeros(1)
+        L, R, S, Kw = self.L, self.R, self.S, self.Kw
+        self.dead_gate = {"WG": ph.expand(L, Kw, R, R), "BG": ph.expand(L, R)}
+        self.dead_skip = {"WS": ph.expand(L, R, S), "BS": ph.expand(L, S)}
+        self.packed = None
+        self._plan()
+
+    def tf_variables(self, scope: str) -> Dict[str, torch.Tensor]:
+        """Reference name -> tensor for the variables a flow reads (the dead gate and skip variables are left out)."""
+        return {k: v for k, v in FlowStack.tf_variables(self, scope).items() if v.is_cuda}
+
+    def _plan(self):
+        from . import packing as P
+        L, R, Kw, E, Ep, sec = self.L, self.R, self.Kw, self.E, self.Ep, self.sections
+        pk = K.Packer(self.dev)
+        self.o_conv = [P.pack_conv(pk, sec["WF"].offset + l * Kw * R * R, Kw, R) for l in range(L)]
+        self.o_res = [P.pack_res(pk, sec["WR"].offset + l * R * R, R) for l in range(L)]
+        self.o_wc = pk.reserve(L * R // 32, Ep // 16)      # every layer's conditioning 1x1 as one product (model.py:180)
+        for l in range(L):
+            P.fill_linear(pk, self.o_wc + l * (R // 32) * (Ep // 16) * 512, sec["WC"].offset + l * E * R, E, R,
+                          R // 32, Ep // 16)
+        self._pk = pk
+        self.packed_elems = pk.total
+
+    def repack(self):
+        """The images from the current parameters.  The gather index is as large as the images and only needed here: it
+        is built for the call and dropped."""
+        if self.packed is None:
+            self.packed = torch.zeros(self.packed_elems, dtype=self.dt, device=self.dev)
+        self._pk.finalize()
+        self._pk.gather(self.params, self.packed)
+        torch.cuda.current_stream().synchronize()
+        self._pk.idx = None
+
+
+class SynthState:
+    """One batch of streams of a ``FlowSynthesizer`` (which holds the device side: a synthesizer serves one state at a
+    time).  ``t``: samples made so far; ``limit`` = frames * pool_stride."""
+
+    def __init__(self, batch: int, frames: int, limit: int, serial: int):
+        self.B, self.frames, self.limit, self.t, self._serial = batch, frames, limit, 0, serial
+
+
+class FlowSynthesizer:
+    """``num_flows`` flows (model.py:415-535) as a streaming synthesizer: ``start`` a batch of streams on their
+    encodings, then ``step`` it chunk by chunk.  Per chunk and flow: one entry launch, one launch per layer group, one
+    exit launch (+ one noise launch per chunk); the sequence of a (batch, chunk size) is captured as a hipGraph when it
+    is used a second time and replayed from then on (SRWN_MODEL_GRAPHS=0: eager launches)."""
+
+    def __init__(self, flow_cfg: StackConfig, num_flows: int, max_batch: int = 1, max_chunk: int = 1600,
+                 max_frames: int = 32, device="cuda"):
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        if not flow_cfg.cond_channels:
+            raise ValueError("a flow is conditioned on the encoding (model.py:431): cond_channels > 0")
+        if flow_cfg.gate_mode != "reference":
+            raise NotImplementedError("gate_mode %r is not built for the flows of ParallelWaveNet" % (flow_cfg.gate_mode,))
+        if flow_cfg.filter_width != 2 or flow_cfg.dilation_channels not in (32, 64):
+            raise NotImplementedError("flows: filter_width 2 and dilation_channels 32 / 64 are built")
+        if min(int(num_flows), int(max_batch), int(max_chunk), int(max_frames)) < 1:
+            raise ValueError("num_flows, max_batch, max_chunk and max_frames must be >= 1")
+        cfg = replace(flow_cfg, head_mode="flow", shift_input=True, output_channels=2)
+        self.cfg, self.F = cfg, int(num_flows)
+        self.max_batch, self.max_chunk, self.max_frames = int(max_batch), int(max_chunk), int(max_frames)
+        self.dev, self.dt = torch.device(device), cfg.dtype
+        self.dil = [int(d) for d in cfg.dilations]
+        self.L, self.R, self.E, self.pool = len(self.dil), cfg.dilation_channels, cfg.cond_channels, int(cfg.pool_stride)
+        import os as _os
+        self.groups = K.group_plan(self.dil, 31, int(_os.environ.get("SRWN_GROUP_LAYERS", "8")))
+        self.hist = stream_history_rows(self.dil, self.groups)
+        self.weights = [FlowWeights(cfg, self.dev) for _ in range(self.F)]
+        Bm, C, R = self.max_batch, self.max_chunk, self.R
+        z = lambda *s, dt=self.dt: torch.zeros(s, dtype=dt, device=self.dev)
+        self.bufs = [[z(Bm, h + C, R) for h in self.hist] for _ in range(self.F)]      # [hist rows | chunk rows] per group
+        self.top = z(Bm, C, R)                                                        # a flow's last layer, chunk rows only
+        self.rows_c = Bm * self.max_frames
+        self.cond_in = z(self.rows_c, self.weights[0].Ep)
+        self.cond_all = [z(self.L, self.rows_c, R) for _ in range(self.F)]
+        self.xbuf = [z(Bm, C, dt=torch.float32) for _ in range(self.F + 1)]           # noise, x_1 .. x_F
+        self.carry = [z(Bm, 2, dt=torch.float32) for _ in range(self.F)]
+        self.seeds = torch.zeros(Bm, dtype=torch.int64, device=self.dev)
+        self.temps = z(Bm, dt=torch.float32)
+        self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.roll = [torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs[i], self.hist)], dtype=torch.int64,
+                                  device=self.dev) for i in range(self.F)]
+        self._graphs: Dict[tuple, object] = {}
+        self._seen: set = set()
+        self._serial = 0
+        self._state: Optional[SynthState] = None
+        self.use_graphs = _os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
+        self.launches_per_chunk = 1 + self.F * (2 + len(self.groups))
+        for w in self.weights:
+            w.repack()
+
+    def repack(self):
+        for w in self.weights:
+            w.repack()
+
+    # ------------------------------------------------------------------------------------------------
+    def start(self, cond, seeds=0, temperature=1.0) -> SynthState:
+        """cond [B, frames <= max_frames, E] (encoding_w_condition) -> a state at clock 0: zero history, zero carry.
+        seeds / temperature: one value per stream, or a scalar (seed s: stream b draws with s + b)."""
+        cond = torch.as_tensor(cond, dtype=torch.float32)
+        if cond.dim() != 3 or cond.shape[2] != self.E:
+            raise ValueError("cond must be [batch, frames, %d], got %s" % (self.E, tuple(cond.shape)))
+        B, frames = int(cond.shape[0]), int(cond.shape[1])
+        if not 1 <= B <= self.max_batch or not 1 <= frames <= self.max_frames:
+            raise ValueError("cond: %d streams x %d frames; this synthesizer holds max_batch=%d, max_frames=%d"
+                             % (B, frames, self.max_batch, self.max_frames))
+        sd = np.asarray(seeds)
+        sd = (int(sd) + np.arange(B)) if sd.ndim == 0 else sd.reshape(-1)
+        tp = np.asarray(temperature, dtype=np.float64)
+        tp = np.full(B, float(tp)) if tp.ndim == 0 else tp.reshape(-1)
+        if sd.shape[0] != B or tp.shape[0] != B:
+            raise ValueError("seeds / temperature: one value per stream (%d) or a scalar" % B)
+        if not np.all(np.isfinite(tp)) or np.any(tp < 0):
+            raise ValueError("temperature must be finite and >= 0")
+        self.seeds[:B].copy_(torch.as_tensor(np.asarray([int(s) & 0x7fffffffffffffff for s in sd], dtype=np.int64)))
+        self.temps[:B].copy_(torch.as_tensor(tp.astype(np.float32)))
+        self.cond_in.zero_()
+        self.cond_in.view(self.max_batch, self.max_frames, -1)[:B, :frames, :self.E].copy_(cond.to(self.dev))
+        st = K._stream()
+        for i, w in enumerate(self.weights):      # cb of every layer and frame (model.py:180), one product per flow
+            call("srwn_pw_linear_ychunks", self.cond_in.data_ptr(), w.Ep, w.Ep, w.wptr(w.o_wc),
+                 w.view("BC").reshape(-1).data_ptr(), self.cond_all[i].data_ptr(), self.R, self.R, self.rows_c * self.R,
+                 self.L * self.R, self.L * self.R, self.rows_c, K.abi_dtype(self.dt), st)
+            for b in self.bufs[i]:
+                b.zero_()
+            self.carry[i].zero_()
+        self.clock.zero_()
+        self._serial += 1
+        self._state = SynthState(B, frames, frames * self.pool, self._serial)
+        return self._state
+
+    def _launch_chunk(self, B: int, n: int, device_noise: bool):
+        import ctypes as C_
+        st, dt, R, C = K._stream(), K.abi_dtype(self.dt), self.R, self.max_chunk
+        ck = self.clock.data_ptr()
+        if device_noise:
+            call("srwn_logistic_noise", self.xbuf[0].data_ptr(), C, self.temps.data_ptr(), self.seeds.data_ptr(), ck, B, n, st)
+        G = len(self.groups)
+        for i, w in enumerate(self.weights):
+            v, bufs = w.view, self.bufs[i]
+            ca = self.cond_all[i]
+            call("srwn_flow_stream_in", self.xbuf[i].data_ptr(), C, self.carry[i].data_ptr(), v("init_w").data_ptr(),
+                 v("init_b").data_ptr(), ca[0].data_ptr(), self.max_frames, self.pool, R, bufs[0].data_ptr(),
+                 self.hist[0] + C, self.hist[0], B, n, C, R, dt, ck, st)
+            for g, (l0, l1) in enumerate(self.groups):
+                last = g + 1 == G
+                out = self.top if last else bufs[g + 1]
+                nl = l1 - l0
+                cond = [ca[l + 1].data_ptr() if l + 1 < self.L else None for l in range(l0, l1)]
+                call("srwn_residual_group_fwd_stream", bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
+                     C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1],
+                     K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
+                     K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
+                     K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
+                     K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
+                     K._ptr_array(cond), self.max_frames, self.pool, R, (C_.c_int32 * nl)(*self.dil[l0:l1]), nl, B, n, C, R,
+                     self.cfg.filter_width, dt, ck, st)
+            lastf = i + 1 == self.F
+            call("srwn_flow_stream_out", self.top.data_ptr(), C, v("flow_w").data_ptr(), v("flow_b").data_ptr(),
+                 self.xbuf[i].data_ptr(), self.xbuf[i + 1].data_ptr(), C, self.carry[i].data_ptr(), 1 if lastf else 0,
+                 self.roll[i].data_ptr(), G, B, n, C, R, dt, ck, 1 if lastf else 0, st)
+
+    def step(self, state: SynthState, n: int, noise=None) -> torch.Tensor:
+        """The next n samples of every stream: [B, n] fp32 in [-1, 1].  noise [B, n]: the first flow's input instead of the
+        device draw.  Refuses (ValueError, state untouched) n outside 1..max_chunk and steps past frames * pool_stride."""
+        if state is not self._state or state._serial != self._serial:
+            raise ValueError("this state is not the synthesizer's current one (start() began another)")
+        n = int(n)
+        if not 1 <= n <= self.max_chunk:
+            raise ValueError("chunk of %d samples: 1..max_chunk = %d" % (n, self.max_chunk))
+        if state.t + n > state.limit:
+            raise ValueError("chunk of %d samples at %d: the encoding ends at frames * pool_stride = %d"
+                             % (n, state.t, state.limit))
+        B = state.B
+        if noise is not None:
+            nz = torch.as_tensor(noise, dtype=torch.float32)
+            if tuple(nz.shape) != (B, n):
+                raise ValueError("noise must be [%d, %d], got %s" % (B, n, tuple(nz.shape)))
+            self.xbuf[0][:B, :n].copy_(nz.to(self.dev))
+        key = (B, n, noise is None)
+        g = self._graphs.get(key)
+        if g is not None:
+            g.replay()
+        elif self.use_graphs and key in self._seen:      # second use of this (batch, chunk size): capture, then replay
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._launch_chunk(B, n, noise is None)
+            self._graphs[key] = g
+            g.replay()
+        else:
+            self._seen.add(key)
+            self._launch_chunk(B, n, noise is None)
+        state.t += n
+        return self.xbuf[self.F][:B, :n].clone()
