@@ -825,6 +825,58 @@ int srwn_logistic_noise(float* noise, int64_t noise_stride, const float* tempera
                         const int64_t* clock, int32_t B, int32_t n, void* stream);
 int srwn_logistic_from_bits(const uint32_t* bits, float* out, int64_t n, void* stream);
 
+/* ---- student synthesis pools (since srwn_version() 108): the four launches above for `capacity` SLOTS over one set of
+ * flow buffers, every slot a stream at a clock of its own.  The device table slots[capacity] replaces the clock:
+ *   t      absolute time of the slot's next sample          t_end   where its stream ends
+ * A slot is live when t < t_end and owns ran = clamp(t_end - t, 0, n) rows of a chunk of n: rows [0, ran) of its chunk
+ * are computed with time t + row (taps before time 0 are the zero padding, frames by t + row, noise counter t + row), so
+ * a stream has the bits the clock forms give a batch of one, in any slot, whenever it joined and whatever the other slots
+ * hold.  A slot with ran = 0 has no group segment and no history roll (its segments end at the table entry); the noise,
+ * entry and exit launches still start its threads, and the exit launch writes its row of zeros.  The segment cut
+ * of the group launch depends on (capacity, n, stride, halo) and the chip alone, so a captured graph serves every chunk
+ * of its size.  temperature / seed stay device arrays [capacity].  Argument errors as above, plus capacity < 1 (-2).
+ *
+ *   srwn_logistic_noise_slots            noise[u, j] for j < ran(u), counter slots[u].t + j; other entries untouched.
+ *   srwn_flow_stream_in_slots            rows [hist, hist + ran(u)) of slot u, frame of time slots[u].t + row.
+ *   srwn_residual_group_fwd_stream_slots buffer row 0 of slot u sits at time slots[u].t - hist.
+ *   srwn_flow_stream_out_slots           x_out[u, j] for j < ran(u), +0 for ran(u) <= j < n (free slots: a row of zeros);
+ *                                        the carry and the history roll of the slots with ran > 0; with advance != 0 (the
+ *                                        last flow) slots[u].t += n for the live slots, by the workgroup that finishes
+ *                                        last (`arrive`: one device int32, zero before the first launch and zero again
+ *                                        after every launch that completes; a caller re-zeroes it after a failed
+ *                                        one), since every workgroup of the launch reads the table.
+ *   srwn_flow_stream_reset_slots         what a join needs: zeroes rows [0, hist) of slot u of every buffer of roll_table
+ *                                        (the tables of all flows, nroll triples) and carry[f][u][0..1] for f < ncarry
+ *                                        (carry + f * carry_stride floats), for the nslots slots of the device array
+ *                                        slot_ids (int32; ids outside [0, capacity) are ignored). */
+typedef struct SrwnSynthSlot {
+  int64_t t;
+  int64_t t_end;
+} SrwnSynthSlot;
+
+int srwn_logistic_noise_slots(float* noise, int64_t noise_stride, const float* temperature, const uint64_t* seed,
+                              const SrwnSynthSlot* slots, int32_t capacity, int32_t n, void* stream);
+int srwn_flow_stream_in_slots(const float* x, int64_t x_stride, const float* carry, const float* init_w,
+                              const float* init_b, const void* cond0, int32_t cond_frames, int32_t pool_stride,
+                              int64_t cond_row_stride, void* out, int64_t out_clip_rows, int32_t out_hist,
+                              int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
+                              const SrwnSynthSlot* slots, void* stream);
+int srwn_residual_group_fwd_stream_slots(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                         int32_t out_hist, const void* const* wconv, const void* const* wres,
+                                         const float* const* bias_f, const float* const* bias_r,
+                                         const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                         int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers,
+                                         int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t K,
+                                         int32_t dtype, const SrwnSynthSlot* slots, void* stream);
+int srwn_flow_stream_out_slots(const void* h, int64_t top_clip_rows, const float* flow_w, const float* flow_b,
+                               const float* x_in, float* x_out, int64_t x_stride, float* carry, int32_t clamp,
+                               const int64_t* roll_table, int32_t nroll, int32_t capacity, int32_t n, int32_t max_chunk,
+                               int32_t R, int32_t dtype, SrwnSynthSlot* slots, int32_t* arrive, int32_t advance,
+                               void* stream);
+int srwn_flow_stream_reset_slots(const int64_t* roll_table, int32_t nroll, float* carry, int32_t ncarry,
+                                 int64_t carry_stride, const int32_t* slot_ids, int32_t nslots, int32_t capacity,
+                                 int32_t R, int32_t dtype, void* stream);
+
 /* ---- data gradient of _DilatedCausalConv1d (ops.py:6-10) wrt a narrow input (the 1-channel flow input,
  * model.py:423-424); `shift` is the adjoint of RightShift (ops.py:78-80):
  *   dx[b,u,i] (+)= scale * sum_k sum_o w[k,i,o] * dy[b, u + shift + (K-1-k)*dilation, o]   (0 beyond the clip)

@@ -34,6 +34,12 @@ class SrwnGenSlot(C.Structure):
     _fields_ = [("t", C.c_int32), ("t_end", C.c_int32), ("seed", C.c_uint64)]
 
 
+class SrwnSynthSlot(C.Structure):
+    """Mirror of srwn.h's SrwnSynthSlot (16 bytes): one slot of a student synthesis pool -- its own absolute time and its
+    stream's end -- passed to the synthesis *_slots entry points as a device array."""
+    _fields_ = [("t", C.c_int64), ("t_end", C.c_int64)]
+
+
 class SrwnGenSampling(C.Structure):
     """Mirror of srwn.h's SrwnGenSampling (16 bytes): one utterance's (or pool slot's) sampling controls, passed to the
     *_sampled entry points and to srwn_sample_filtered as a device array.  The defaults (1, 1, 0) mean "off"."""
@@ -180,6 +186,15 @@ SIGNATURES = {
                                        _i32, _p]),
     "srwn_logistic_noise": (C.c_int, [_p, _i64, _p, _p, _p, _i32, _i32, _p]),
     "srwn_logistic_from_bits": (C.c_int, [_p, _p, _i64, _p]),
+    # student synthesis pools (srwn_version() 108): the slot forms take the device table of SrwnSynthSlot for the clock
+    "srwn_logistic_noise_slots": (C.c_int, [_p, _i64, _p, _p, _p, _i32, _i32, _p]),
+    "srwn_flow_stream_in_slots": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i32, _i64, _p, _i64, _i32, _i32, _i32, _i32,
+                                            _i32, _i32, _p, _p]),
+    "srwn_residual_group_fwd_stream_slots": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _p,
+                                                       _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p]),
+    "srwn_flow_stream_out_slots": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32,
+                                             _i32, _p, _p, _i32, _p]),
+    "srwn_flow_stream_reset_slots": (C.c_int, [_p, _i32, _p, _i32, _i64, _p, _i32, _i32, _i32, _i32, _p]),
     "srwn_causal_conv1d_dgrad": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _p]),
     "srwn_stft_frames": (_i32, [_i32]),
     "srwn_stft_power": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p]),

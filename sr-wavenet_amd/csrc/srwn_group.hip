@@ -72,6 +72,15 @@ struct GroupFwdStreamArgs : GroupFwdArgs {
   long long in_clip_rows, out_clip_rows, out_row_off;   // out_row_off = out_hist - hrows (buffer row -> output row)
 };
 
+// The SLOTS instantiations (srwn_residual_group_fwd_stream_slots: synthesis pools, srwn.h SrwnSynthSlot) take the pool's
+// table instead of the clock: clip b is a slot whose buffer row 0 sits at absolute time slots[b].t - hrows and whose chunk
+// has ran = clamp(t_end - t, 0, n) rows.  What the stream form derives from the clock once per workgroup is derived per
+// segment from the segment's slot; a segment of a slot without rows ends there.  A struct of its own, so that the other
+// instantiations keep their arguments.
+struct GroupFwdSlotArgs : GroupFwdStreamArgs {
+  const SrwnSynthSlot* slots;
+};
+
 // In-kernel time stamps (MI355X guide, "In-kernel stamps"): lane 0 of waves 0 and 1 of workgroup 0 append the shader
 // clock to a buffer no other code reads.  Compiled in only when a buffer was registered (STAMP instantiation).
 template <bool STAMP> struct Stamper {
@@ -94,9 +103,11 @@ template <> struct Stamper<true> {
 };
 
 template <typename T, int RT, bool COND, int MAXT, int NWB, int NWV = 8, bool WDMA = true, bool STAMP = false, bool WT = false, bool IC = false,
-          bool STREAM = false>
-__global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type a) {
+          bool STREAM = false, bool SLOTS = false>
+__global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
+    typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type>::type a) {
   static_assert(!IC || (WT && !COND), "input conv fused in: the unconditioned weight-gradient-tile kernels only");
+  static_assert(!SLOTS || STREAM, "slot form: a stream form");
   static_assert(!STREAM || (COND && !WT && !IC && !STAMP), "stream form: the conditioned plain kernels only");
   constexpr int R = 32 * RT, K = 2, KS = R / 16;
   constexpr int NCONV = RT * K * KS, NRES = RT * KS, NW = NCONV + NRES;   // weight fragments per layer
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(typename std::condi
   // stream's start (the conv's zero padding at every layer), and buffer row t_buf lies in conditioning frame
   // fq0 + (frem0 + t_buf) / pool (frame 0 before the start)
   int pad = 0, fq0 = 0, frem0 = 0;
-  if constexpr (STREAM) {
+  if constexpr (STREAM && !SLOTS) {
     const long long c0 = *a.clock - a.hrows;
     if (c0 >= 0) { fq0 = (int)(c0 / a.pool); frem0 = (int)(c0 - (long long)fq0 * a.pool); }
     else { pad = (int)(-c0); frem0 = (int)c0; }
@@ -191,8 +202,22 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(typename std::condi
     if (a.nsub == 1) { r = rem; j0 = 0; }
     else { r = rem / a.nsub; j0 = (rem - r * a.nsub) * a.W; }
     if (STREAM) j0 += a.H;                                     // (the history's positions are nobody's segment)
-    const int Jr = (a.Tlen - r + a.st - 1) / a.st;             // positions of this residue class (may be 0)
+    int Tlen_ = a.Tlen;
+    if constexpr (SLOTS) {     // the slot's own place in time, and the rows it has in this chunk
+      const SrwnSynthSlot sl = a.slots[b];
+      const long long left = sl.t_end - sl.t;
+      if (left <= 0) continue;                                 // (workgroup-uniform, before the segment's first barrier)
+      const int n = a.Tlen - a.hrows;
+      Tlen_ = a.hrows + (left < n ? (int)left : n);
+      const long long c0 = sl.t - a.hrows;
+      pad = 0; fq0 = 0; frem0 = 0;
+      if (c0 >= 0) { fq0 = (int)(c0 / a.pool); frem0 = (int)(c0 - (long long)fq0 * a.pool); }
+      else { pad = (int)(-c0); frem0 = (int)c0; }
+    }
+    const int Tlen = Tlen_;
+    const int Jr = (Tlen - r + a.st - 1) / a.st;               // positions of this residue class (may be 0)
     const int Wseg = (Jr - j0) < a.W ? (Jr - j0) : a.W;        // positions this segment owns (<= 0: nothing to do)
+    if (SLOTS && Wseg <= 0) continue;                          // a chunk cut short by the stream's end: no row of this segment
     const int jbase = j0 - a.H;                                // position of image row 0
     size_t clip_;
     if constexpr (STREAM) clip_ = (size_t)b * (size_t)a.in_clip_rows; else clip_ = (size_t)b * a.Tlen;
@@ -203,7 +228,7 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(typename std::condi
       jj = jj < Jr ? jj : Jr - 1;
       jj = jj < 0 ? 0 : jj;
       size_t t = (size_t)jj * a.st + r;
-      t = t < (size_t)a.Tlen ? t : (size_t)a.Tlen - 1;
+      t = t < (size_t)Tlen ? t : (size_t)Tlen - 1;
       return clip + t;
     };
 
@@ -225,7 +250,7 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(typename std::condi
         i = i < nrows ? i : nrows - 1;
         const int t = (int)(grow(jbase + i) - clip);        // (rows beyond the clip are clamped re-computations, as the loads were)
         const int t1 = t - a.ic_shift, t0 = t1 - 1;
-        const bool ok1 = t1 >= 0 && t1 < a.Tlen, ok0 = t0 >= 0 && t0 < a.Tlen;
+        const bool ok1 = t1 >= 0 && t1 < Tlen, ok0 = t0 >= 0 && t0 < Tlen;
         x1[u] = au[ok1 ? t1 : 0];
         x0v[u] = au[ok0 ? t0 : 0];
         x1[u] = ok1 ? x1[u] : 0.0f;
@@ -1384,8 +1409,8 @@ int launch_group_fwd(GroupFwdArgs& a, bool cond, int seg_rows, hipStream_t st) {
 // The stream form: segments over the chunk's positions of every residue class that holds a chunk row; the halo is always
 // the whole H (the history supplies it).  The cut depends on (B, n, st, H) and the chip alone -- never on the clock -- so a
 // captured launch stays valid for every chunk of its size.
-template <typename T, int RT, int MAXT, int NWB, int NWV = 8>
-int launch_group_fwd_stream(GroupFwdStreamArgs& a, int n, hipStream_t st) {
+template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool SLOTS = false>
+int launch_group_fwd_stream(typename std::conditional<SLOTS, GroupFwdSlotArgs, GroupFwdStreamArgs>::type& a, int n, hipStream_t st) {
   constexpr int R = 32 * RT, KS = R / 16, NW = RT * 2 * KS + RT * KS;
   const size_t fixed = (size_t)NWB * NW * 64 * sizeof(Frag<T>) + (size_t)NWB * 2 * R * 4;
   const size_t row_bytes = (size_t)RowStage<T>::stride(R) * sizeof(T);
@@ -1413,11 +1438,11 @@ int launch_group_fwd_stream(GroupFwdStreamArgs& a, int n, hipStream_t st) {
   const int grid_cap = group_grid();
   const long long blocks = nseg < grid_cap ? nseg : grid_cap;
   dim3 grid((unsigned)blocks), block(64 * NWV);
-  auto kfn = group_fwd_kernel<T, RT, true, MAXT, NWB, NWV, true, false, false, false, true>;
+  auto kfn = group_fwd_kernel<T, RT, true, MAXT, NWB, NWV, true, false, false, false, true, SLOTS>;
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
   if (e != hipSuccess) return set_error((int)e, "residual_group_fwd_stream: LDS %zu: %s", sh, hipGetErrorString(e));
   hipLaunchKernelGGL(kfn, grid, block, sh, st, a);
-  return check_launch("residual_group_fwd_stream");
+  return check_launch(SLOTS ? "residual_group_fwd_stream_slots" : "residual_group_fwd_stream");
 }
 
 template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool WT = false>
@@ -1681,21 +1706,22 @@ extern "C" int srwn_residual_group_fwd_wt(const void* x0, void* x_out, void* z_o
 
 // The inference / stream form of srwn_residual_group_fwd (srwn.h): one chunk of a batch of streams, the group's causal
 // context taken from the history rows in front of the chunk, time taken from a device clock.
-extern "C" int srwn_residual_group_fwd_stream(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
-                                              int32_t out_hist, const void* const* wconv, const void* const* wres,
-                                              const float* const* bias_f, const float* const* bias_r,
-                                              const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
-                                              int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers,
-                                              int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t K,
-                                              int32_t dtype, const int64_t* clock, void* stream) {
+namespace {
+template <bool SLOTS>
+int group_fwd_stream_impl(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows, int32_t out_hist,
+                          const void* const* wconv, const void* const* wres, const float* const* bias_f,
+                          const float* const* bias_r, const void* const* cond_next, int32_t cond_frames,
+                          int32_t pool_stride, int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers, int32_t B,
+                          int32_t n, int32_t max_chunk, int32_t R, int32_t K, int32_t dtype, const void* clock, void* stream) {
   if (!x_in || !x_out || !wconv || !wres || !bias_f || !bias_r || !dilations || !clock)
-    return set_error(SRWN_E_NULL, "residual_group_fwd_stream: null pointer (the clock is the synthesizer state's device scalar)");
+    return set_error(SRWN_E_NULL, SLOTS ? "residual_group_fwd_stream_slots: null pointer (slots is the pool's device table)"
+                                        : "residual_group_fwd_stream: null pointer (the clock is the synthesizer state's device scalar)");
   if (K != 2) return set_error(SRWN_E_UNSUPPORTED, "residual_group_fwd_stream: filter_width %d (only 2 is built)", K);
   if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "residual_group_fwd_stream: dilation_channels %d (built: 32, 64)", R);
   if (nlayers < 1 || nlayers > kMaxGroup || B < 1 || max_chunk < 1 || out_hist < 0)
     return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: nlayers=%d (max %d) B=%d max_chunk=%d out_hist=%d", nlayers, kMaxGroup, B, max_chunk, out_hist);
   if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  GroupFwdStreamArgs a;
+  typename std::conditional<SLOTS, GroupFwdSlotArgs, GroupFwdStreamArgs>::type a;
   a.safe_wait = safe_wait();
   a.x0 = x_in; a.x_out = x_out; a.z_out = nullptr; a.layer_stride = 0;
   a.xT = nullptr; a.cT = nullptr; a.wt_stride = 0; a.KT = 0; a.store_inner_x = 0;
@@ -1724,18 +1750,47 @@ extern "C" int srwn_residual_group_fwd_stream(const void* x_in, int64_t in_clip_
     return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: buffers of %lld / %lld rows per stream for %lld + %d and %d + %d",
                      (long long)in_clip_rows, (long long)out_clip_rows, hrows, max_chunk, out_hist, max_chunk);
   a.hrows = (int)hrows; a.Tlen = (int)hrows + n;
-  a.clock = reinterpret_cast<const long long*>(clock);
+  if constexpr (SLOTS) { a.clock = nullptr; a.slots = reinterpret_cast<const SrwnSynthSlot*>(clock); }
+  else a.clock = reinterpret_cast<const long long*>(clock);
   a.in_clip_rows = in_clip_rows; a.out_clip_rows = out_clip_rows; a.out_row_off = (long long)out_hist - hrows;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SRWN_BF16) {
-    if (R == 32) return launch_group_fwd_stream<bf16_t, 1, 3, 2>(a, n, st);
-    return launch_group_fwd_stream<bf16_t, 2, SRWN_GFS_MAXT, 2, SRWN_GFS_WAVES>(a, n, st);
+    if (R == 32) return launch_group_fwd_stream<bf16_t, 1, 3, 2, 8, SLOTS>(a, n, st);
+    return launch_group_fwd_stream<bf16_t, 2, SRWN_GFS_MAXT, 2, SRWN_GFS_WAVES, SLOTS>(a, n, st);
   } else if (dtype == SRWN_F32) {
-    if (R == 32) return launch_group_fwd_stream<float, 1, 1, 1>(a, n, st);
-    return launch_group_fwd_stream<float, 2, 1, 1>(a, n, st);
+    if (R == 32) return launch_group_fwd_stream<float, 1, 1, 1, 8, SLOTS>(a, n, st);
+    return launch_group_fwd_stream<float, 2, 1, 1, 8, SLOTS>(a, n, st);
   }
   return set_error(SRWN_E_DTYPE, "residual_group_fwd_stream: dtype %d", dtype);
 }
+}  // namespace
+
+extern "C" int srwn_residual_group_fwd_stream(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                              int32_t out_hist, const void* const* wconv, const void* const* wres,
+                                              const float* const* bias_f, const float* const* bias_r,
+                                              const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                              int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers,
+                                              int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t K,
+                                              int32_t dtype, const int64_t* clock, void* stream) {
+  return group_fwd_stream_impl<false>(x_in, in_clip_rows, x_out, out_clip_rows, out_hist, wconv, wres, bias_f, bias_r,
+                                      cond_next, cond_frames, pool_stride, cond_row_stride, dilations, nlayers, B, n,
+                                      max_chunk, R, K, dtype, clock, stream);
+}
+
+// The slot form (synthesis pools): the same launch on the pool's table, every clip a slot at a clock of its own.
+extern "C" int srwn_residual_group_fwd_stream_slots(const void* x_in, int64_t in_clip_rows, void* x_out,
+                                                    int64_t out_clip_rows, int32_t out_hist, const void* const* wconv,
+                                                    const void* const* wres, const float* const* bias_f,
+                                                    const float* const* bias_r, const void* const* cond_next,
+                                                    int32_t cond_frames, int32_t pool_stride, int32_t cond_row_stride,
+                                                    const int32_t* dilations, int32_t nlayers, int32_t capacity, int32_t n,
+                                                    int32_t max_chunk, int32_t R, int32_t K, int32_t dtype,
+                                                    const SrwnSynthSlot* slots, void* stream) {
+  return group_fwd_stream_impl<true>(x_in, in_clip_rows, x_out, out_clip_rows, out_hist, wconv, wres, bias_f, bias_r,
+                                     cond_next, cond_frames, pool_stride, cond_row_stride, dilations, nlayers, capacity, n,
+                                     max_chunk, R, K, dtype, slots, stream);
+}
+
 
 // The FIRST group of a stack with the stack's input conv fused in (model.py:40 / 172-173; K = 2 taps, 1 -> R channels,
 // RightShift as `shift`): what srwn_causal_conv1d_fwd would have written to x0 is computed into the segment image, in

@@ -1046,6 +1046,58 @@ class StudentSynthesizer(object):
         st, nz, B, T = self._begin(encoding, conditions, seed, temperature, noise)
         return (c.view(B, -1, 1).cpu().numpy() for c in self._chunks(st, nz, T, chunk_size))
 
+    def pool(self):
+        """A ``SynthesisPool`` on this synthesizer's buffers: ``max_batch`` slots that streams join and leave while it
+        runs.  It ends a running ``stream``; the next ``synthesize`` / ``stream`` closes the pool."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        return SynthesisPool(self._eng.pool(), self.latent_channels, self.condition_size)
+
+
+class SynthesisPool(object):
+    """NumPy face of a student synthesis pool (student.SynthPool): ``join(encoding=[...], ...)`` takes one
+    [frames_i, latent] per stream and returns their slots; ``step(n)`` advances every live slot by n samples with the
+    launches of one synthesizer chunk and returns ``{slot: samples}`` of every slot that produced some; a stream that
+    reaches its end frees its slot; ``leave(slots)`` ends streams early.  A stream's samples put together are what
+    ``StudentSynthesizer.synthesize`` of that stream alone returns with its seed and temperature."""
+
+    def __init__(self, pool, latent, condition_size):
+        self._pool, self._latent, self._cs = pool, latent, condition_size
+
+    @property
+    def capacity(self):
+        return self._pool.capacity
+
+    @property
+    def active(self):
+        return self._pool.active
+
+    @property
+    def free(self):
+        return self._pool.free
+
+    @property
+    def t(self):
+        return self._pool.t
+
+    def join(self, encoding, conditions=None, seed=0, temperature=None, max_samples=None):
+        """encoding: one [frames_i, latent] per stream (a single 2-D array: one stream); conditions: one [condition_size]
+        per stream, tiled over its frames; seed: one per stream or a scalar s (stream i draws with s + i)."""
+        if isinstance(encoding, np.ndarray) and encoding.ndim == 2:
+            encoding = [encoding]
+            conditions = None if conditions is None else [conditions]
+        encoding = list(encoding)
+        cond = _pool_encodings(len(encoding), encoding, conditions, self._latent, self._cs)
+        return self._pool.join(cond, seed, temperature, max_samples)
+
+    def step(self, n):
+        a, ran = self._pool.step(int(n))
+        a = a.cpu().numpy()
+        return {u: a[u, :int(ran[u])] for u in range(self._pool.capacity) if ran[u] > 0}
+
+    def leave(self, slots):
+        self._pool.leave([slots] if np.isscalar(slots) else slots)
+
 
 class SiameseWaveNet(_EngineOwner):
     """model.py:660-797: two towers of class ``WaveNet``'s network (input conv, residual stack, skip sum, relu -> 1x1

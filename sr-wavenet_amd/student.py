@@ -501,7 +501,8 @@ class FlowSynthesizer:
     """``num_flows`` flows (model.py:415-535) as a streaming synthesizer: ``start`` a batch of streams on their
     encodings, then ``step`` it chunk by chunk.  Per chunk and flow: one entry launch, one launch per layer group, one
     exit launch (+ one noise launch per chunk); the sequence of a (batch, chunk size) is captured as a hipGraph when it
-    is used a second time and replayed from then on (SRWN_MODEL_GRAPHS=0: eager launches)."""
+    is used a second time and replayed from then on (SRWN_MODEL_GRAPHS=0: eager launches).  ``pool`` serves the same
+    buffers as slots that streams join and leave while the batch runs (``SynthPool``)."""
 
     def __init__(self, flow_cfg: StackConfig, num_flows: int, max_batch: int = 1, max_chunk: int = 1600,
                  max_frames: int = 32, device="cuda"):
@@ -520,7 +521,7 @@ class FlowSynthesizer:
         self.max_batch, self.max_chunk, self.max_frames = int(max_batch), int(max_chunk), int(max_frames)
         self.dev, self.dt = torch.device(device), cfg.dtype
         self.dil = [int(d) for d in cfg.dilations]
-        self.L, self.R, self.E, self.pool = len(self.dil), cfg.dilation_channels, cfg.cond_channels, int(cfg.pool_stride)
+        self.L, self.R, self.E, self.pool_stride = len(self.dil), cfg.dilation_channels, cfg.cond_channels, int(cfg.pool_stride)
         import os as _os
         self.groups = K.group_plan(self.dil, 31, int(_os.environ.get("SRWN_GROUP_LAYERS", "8")))
         self.hist = stream_history_rows(self.dil, self.groups)
@@ -533,16 +534,19 @@ class FlowSynthesizer:
         self.cond_in = z(self.rows_c, self.weights[0].Ep)
         self.cond_all = [z(self.L, self.rows_c, R) for _ in range(self.F)]
         self.xbuf = [z(Bm, C, dt=torch.float32) for _ in range(self.F + 1)]           # noise, x_1 .. x_F
-        self.carry = [z(Bm, 2, dt=torch.float32) for _ in range(self.F)]
+        self.carry_all = z(self.F, Bm, 2, dt=torch.float32)
+        self.carry = [self.carry_all[i] for i in range(self.F)]
         self.seeds = torch.zeros(Bm, dtype=torch.int64, device=self.dev)
         self.temps = z(Bm, dt=torch.float32)
         self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.roll = [torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs[i], self.hist)], dtype=torch.int64,
                                   device=self.dev) for i in range(self.F)]
+        self.roll_all = torch.cat(self.roll, 0).contiguous()      # every flow's table in one (a pool join resets through it)
         self._graphs: Dict[tuple, object] = {}
         self._seen: set = set()
         self._serial = 0
         self._state: Optional[SynthState] = None
+        self._pool: Optional["SynthPool"] = None
         self.use_graphs = _os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
         self.launches_per_chunk = 1 + self.F * (2 + len(self.groups))
         for w in self.weights:
@@ -585,39 +589,57 @@ class FlowSynthesizer:
             self.carry[i].zero_()
         self.clock.zero_()
         self._serial += 1
-        self._state = SynthState(B, frames, frames * self.pool, self._serial)
+        if self._pool is not None:      # the buffers serve one of the two at a time
+            self._pool._open = False
+            self._pool = None
+        self._state = SynthState(B, frames, frames * self.pool_stride, self._serial)
         return self._state
 
-    def _launch_chunk(self, B: int, n: int, device_noise: bool):
+    def pool(self) -> "SynthPool":
+        """A ``SynthPool`` on this synthesizer's buffers: max_batch slots, each a stream at a clock of its own.  The current
+        ``SynthState`` (and an earlier pool) ends here, as at ``start``; ``start`` closes the pool."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        if self._pool is not None:
+            self._pool._open = False
+        self._serial += 1
+        self._state = None
+        self._pool = SynthPool(self)
+        return self._pool
+
+    def _launch_chunk(self, B: int, n: int, device_noise: bool, pool: Optional["SynthPool"] = None):
+        """The 1 + F x (2 + G) launches of a chunk.  pool: the slot forms, on the pool's table instead of the clock."""
         import ctypes as C_
         st, dt, R, C = K._stream(), K.abi_dtype(self.dt), self.R, self.max_chunk
-        ck = self.clock.data_ptr()
+        sfx = "" if pool is None else "_slots"
+        ck = self.clock.data_ptr() if pool is None else pool.slots.data_ptr()
         if device_noise:
-            call("srwn_logistic_noise", self.xbuf[0].data_ptr(), C, self.temps.data_ptr(), self.seeds.data_ptr(), ck, B, n, st)
+            call("srwn_logistic_noise" + sfx, self.xbuf[0].data_ptr(), C, self.temps.data_ptr(), self.seeds.data_ptr(), ck, B, n, st)
         G = len(self.groups)
         for i, w in enumerate(self.weights):
             v, bufs = w.view, self.bufs[i]
             ca = self.cond_all[i]
-            call("srwn_flow_stream_in", self.xbuf[i].data_ptr(), C, self.carry[i].data_ptr(), v("init_w").data_ptr(),
-                 v("init_b").data_ptr(), ca[0].data_ptr(), self.max_frames, self.pool, R, bufs[0].data_ptr(),
+            call("srwn_flow_stream_in" + sfx, self.xbuf[i].data_ptr(), C, self.carry[i].data_ptr(), v("init_w").data_ptr(),
+                 v("init_b").data_ptr(), ca[0].data_ptr(), self.max_frames, self.pool_stride, R, bufs[0].data_ptr(),
                  self.hist[0] + C, self.hist[0], B, n, C, R, dt, ck, st)
             for g, (l0, l1) in enumerate(self.groups):
                 last = g + 1 == G
                 out = self.top if last else bufs[g + 1]
                 nl = l1 - l0
                 cond = [ca[l + 1].data_ptr() if l + 1 < self.L else None for l in range(l0, l1)]
-                call("srwn_residual_group_fwd_stream", bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
+                call("srwn_residual_group_fwd_stream" + sfx, bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
                      C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1],
                      K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
                      K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
                      K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
                      K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                     K._ptr_array(cond), self.max_frames, self.pool, R, (C_.c_int32 * nl)(*self.dil[l0:l1]), nl, B, n, C, R,
+                     K._ptr_array(cond), self.max_frames, self.pool_stride, R, (C_.c_int32 * nl)(*self.dil[l0:l1]), nl, B, n, C, R,
                      self.cfg.filter_width, dt, ck, st)
             lastf = i + 1 == self.F
-            call("srwn_flow_stream_out", self.top.data_ptr(), C, v("flow_w").data_ptr(), v("flow_b").data_ptr(),
+            tail = (ck,) if pool is None else (ck, pool.arrive.data_ptr())
+            call("srwn_flow_stream_out" + sfx, self.top.data_ptr(), C, v("flow_w").data_ptr(), v("flow_b").data_ptr(),
                  self.xbuf[i].data_ptr(), self.xbuf[i + 1].data_ptr(), C, self.carry[i].data_ptr(), 1 if lastf else 0,
-                 self.roll[i].data_ptr(), G, B, n, C, R, dt, ck, 1 if lastf else 0, st)
+                 self.roll[i].data_ptr(), G, B, n, C, R, dt, *tail, 1 if lastf else 0, st)
 
     def step(self, state: SynthState, n: int, noise=None) -> torch.Tensor:
         """The next n samples of every stream: [B, n] fp32 in [-1, 1].  noise [B, n]: the first flow's input instead of the
@@ -652,3 +674,183 @@ class FlowSynthesizer:
             self._launch_chunk(B, n, noise is None)
         state.t += n
         return self.xbuf[self.F][:B, :n].clone()
+
+
+class SynthPool:
+    """``FlowSynthesizer.pool()``: the synthesizer's ``max_batch`` rows as SLOTS, each holding a stream at a clock of its
+    own (srwn.h, SrwnSynthSlot).  Streams ``join`` free slots with their encodings, seeds and temperatures, ``step`` runs
+    every live slot with the launches of one synthesizer chunk, and a stream that reaches its end or ``leave``s frees its
+    slot for the next one.  A stream has, bit for bit, the samples of a batch-of-one ``FlowSynthesizer`` run with its
+    encoding, seed and temperature -- in any slot, whenever it joined, whatever the chunk sizes and the other slots."""
+
+    def __init__(self, syn: "FlowSynthesizer"):
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        self.syn, self.capacity = syn, syn.max_batch
+        self.frames, self.pool_stride, self.E = syn.max_frames, syn.pool_stride, syn.E
+        self._t = np.zeros(self.capacity, np.int64)          # host mirror of the device table (the kernel advances both)
+        self._end = np.zeros(self.capacity, np.int64)
+        self._active = np.zeros(self.capacity, bool)
+        self.slots = torch.zeros((self.capacity, 2), dtype=torch.int64, device=syn.dev)      # [t, t_end] per slot
+        self.arrive = torch.zeros(1, dtype=torch.int32, device=syn.dev)      # the last flow's exit launch counts its workgroups here
+        self._graphs: Dict[tuple, object] = {}
+        self._seen: set = set()
+        self._open = True
+
+    # ---- inspection
+    @property
+    def t(self) -> np.ndarray:
+        """Each slot's own time of its next sample."""
+        return self._t.copy()
+
+    @property
+    def active(self) -> List[int]:
+        return [int(u) for u in np.flatnonzero(self._active)]
+
+    @property
+    def free(self) -> List[int]:
+        return [int(u) for u in np.flatnonzero(~self._active)]
+
+    def _check_open(self):
+        if not self._open:
+            raise ValueError("this pool is closed (the synthesizer started a batch or opened another pool)")
+
+    def _upload(self):
+        """The host mirrors -> the device table, after join and leave.  The exit launch's workgroup counter is put back to
+        zero with it: a launch that completed left it at zero, one that failed may not have."""
+        self.slots.copy_(torch.from_numpy(np.stack([self._t, self._end], 1)))
+        self.arrive.zero_()
+
+    def _check_join(self, cond, seeds, temperature, max_samples, slots):
+        """Everything join refuses, before any device work: (encodings as float32 tensors, seeds, temperatures, the chosen
+        slots, t_end per stream)."""
+        self._check_open()
+        if isinstance(cond, (torch.Tensor, np.ndarray)) and cond.ndim == 2:
+            cond = [cond]
+        cond = [c.detach().to("cpu", torch.float32) if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c, dtype=np.float32))
+                for c in cond]
+        n = len(cond)
+        if n < 1:
+            raise ValueError("join: no streams")
+        for i, c in enumerate(cond):
+            if c.dim() != 2 or c.shape[1] != self.E or not 1 <= c.shape[0] <= self.frames:
+                raise ValueError("join: cond %d must be [1..%d frames, %d], got %s" % (i, self.frames, self.E, tuple(c.shape)))
+
+        def per_stream(x, what, default):
+            if x is None:
+                return [default] * n
+            if np.ndim(x) == 0:
+                return [x] * n
+            x = list(x)
+            if len(x) != n:
+                raise ValueError("join: %d encodings but %d %s" % (n, len(x), what))
+            return [default if v is None else v for v in x]
+        sd = np.asarray(seeds)
+        sd = [int(sd) + i for i in range(n)] if sd.ndim == 0 else [int(s) for s in per_stream(seeds, "seeds", 0)]
+        tp = [float(v) for v in per_stream(temperature, "temperatures", 1.0)]
+        if not np.all(np.isfinite(tp)) or any(v < 0 for v in tp):
+            raise ValueError("join: temperature must be finite and >= 0")
+        ends = []
+        for c, m in zip(cond, per_stream(max_samples, "max_samples", None)):
+            lim = int(c.shape[0]) * self.pool_stride
+            if m is not None and int(m) < 0:
+                raise ValueError("join: max_samples %d" % int(m))
+            ends.append(lim if m is None else min(lim, int(m)))
+        free = self.free
+        if slots is None:
+            if n > len(free):
+                raise ValueError("join: %d streams but %d free slots" % (n, len(free)))
+            slots = free[:n]
+        else:
+            slots = [int(u) for u in slots]
+            if len(slots) != n or len(set(slots)) != n:
+                raise ValueError("join: slots must name %d distinct slots" % n)
+            if any(u < 0 or u >= self.capacity or self._active[u] for u in slots):
+                raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
+        return cond, sd, tp, slots, ends
+
+    def join(self, cond, seeds=0, temperature=None, max_samples=None, slots=None) -> List[int]:
+        """n streams into free slots (the lowest ones, or `slots`): cond n encodings [frames_i <= max_frames, E]; seeds one
+        per stream or a scalar s (stream i draws with s + i); temperature None (1), a scalar or one per stream;
+        max_samples None, one int or n entries: a stream ends at min(frames_i * pool_stride, max_samples).  Writes the
+        joined slots' seeds, temperatures and rows of every flow's conditioning table (srwn_pw_linear_ychunks on those rows)
+        and zeroes their history rows and carries (srwn_flow_stream_reset_slots); returns the slots."""
+        cond, sd, tp, slots, ends = self._check_join(cond, seeds, temperature, max_samples, slots)
+        syn, n = self.syn, len(cond)
+        dev, Fm, st = syn.dev, syn.max_frames, K._stream()
+        dst = torch.tensor(slots, dtype=torch.int64, device=dev)
+        syn.seeds[dst] = torch.tensor([s & 0x7fffffffffffffff for s in sd], dtype=torch.int64).to(dev)
+        syn.temps[dst] = torch.tensor(tp, dtype=torch.float32).to(dev)
+        cin = syn.cond_in.view(syn.max_batch, Fm, -1)
+        for u, c in zip(slots, cond):
+            cin[u].zero_()
+            cin[u, :c.shape[0], :self.E].copy_(c.to(dev))
+        order = sorted(slots)
+        runs, u0 = [], order[0]
+        for a, b in zip(order, order[1:] + [None]):      # neighbouring slots share a product
+            if b != a + 1:
+                runs.append((u0, a + 1 - u0))
+                u0 = b
+        esz = syn.cond_in.element_size()
+        for i, w in enumerate(syn.weights):
+            for u0, k in runs:
+                call("srwn_pw_linear_ychunks", syn.cond_in.data_ptr() + u0 * Fm * w.Ep * esz, w.Ep, w.Ep, w.wptr(w.o_wc),
+                     w.view("BC").reshape(-1).data_ptr(), syn.cond_all[i].data_ptr() + u0 * Fm * syn.R * esz, syn.R, syn.R,
+                     syn.rows_c * syn.R, syn.L * syn.R, syn.L * syn.R, k * Fm, K.abi_dtype(syn.dt), st)
+        ids = dst.to(torch.int32)
+        call("srwn_flow_stream_reset_slots", syn.roll_all.data_ptr(), syn.roll_all.shape[0], syn.carry_all.data_ptr(), syn.F,
+             syn.max_batch * 2, ids.data_ptr(), n, self.capacity, syn.R, K.abi_dtype(syn.dt), st)
+        for u, e in zip(slots, ends):
+            self._t[u], self._end[u] = 0, e
+            self._active[u] = e > 0
+        self._upload()
+        return list(slots)
+
+    def leave(self, slots) -> None:
+        """Ends the streams in `slots` (a slot already free stays free) and frees their slots."""
+        self._check_open()
+        slots = [int(u) for u in (slots if np.ndim(slots) else [slots])]
+        if any(u < 0 or u >= self.capacity for u in slots):
+            raise ValueError("leave: slots %s outside the pool's %d" % (slots, self.capacity))
+        for u in slots:
+            self._active[u] = False
+            self._end[u] = self._t[u]
+        self._upload()
+
+    def step(self, n: int, noise=None):
+        """The next n samples of every live slot, with the launches of one synthesizer chunk: (audio [capacity, n] f32,
+        ran [capacity] int64 numpy).  Slot u's samples are row u's first ran[u] entries; the rest of every row is zero.
+        noise [capacity, n]: the first flow's input instead of the device draw (every slot).  Slots whose stream reached its
+        end become free.  With no live slot nothing is launched."""
+        self._check_open()
+        syn, n = self.syn, int(n)
+        if not 1 <= n <= syn.max_chunk:
+            raise ValueError("chunk of %d samples: 1..max_chunk = %d" % (n, syn.max_chunk))
+        B = self.capacity
+        nz = None
+        if noise is not None:
+            nz = torch.as_tensor(noise, dtype=torch.float32)
+            if tuple(nz.shape) != (B, n):
+                raise ValueError("noise must be [capacity = %d, %d], got %s" % (B, n, tuple(nz.shape)))
+        ran = np.clip(self._end - self._t, 0, n)
+        if not ran.any():
+            return torch.zeros((B, n), dtype=torch.float32, device=syn.dev), ran
+        if nz is not None:
+            syn.xbuf[0][:, :n].copy_(nz.to(syn.dev))
+        key = (n, noise is None)
+        g = self._graphs.get(key)
+        if g is not None:
+            g.replay()
+        elif syn.use_graphs and key in self._seen:      # second use of this chunk size: capture, then replay
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                syn._launch_chunk(B, n, noise is None, self)
+            self._graphs[key] = g
+            g.replay()
+        else:
+            self._seen.add(key)
+            syn._launch_chunk(B, n, noise is None, self)
+        self._t += ran
+        self._active &= self._t < self._end
+        return syn.xbuf[syn.F][:, :n].clone(), ran
