@@ -968,6 +968,27 @@ int srwn_wgrad_nc_layers(const void* r, const void* a, const void* dpre, const v
 /* first encoder layer on the raw clip (model.py:141-142): a[b,t,c] = relu(bias[c] + sum_k w[k][c]*relu(x[b,t+k])) */
 int srwn_nc_input_fwd(const float* x, const float* w, const float* bias, void* a, int32_t B, int32_t T, int32_t C,
                       int32_t K, int32_t dtype, void* stream);
+/* ---- the encoder for inference (since srwn_version() 109; csrc/srwn_ncstream.hip): the whole chain above for B streams x
+ * `nframes` frames in one launch -- a_0 = relu(nc_conv(relu(x))), r_0, then a_{l+1} = relu(conv(r_l) + b_l),
+ * r_{l+1} = relu(a_{l+1} Wr_l + br_l) for every layer, on chip -- leaving only the per-frame means of a_1..a_L:
+ * means [nlayers][B*nframes][128] bf16, the layout srwn_pw_linear_ksplit consumes (x_chunk_stride = B*nframes*128).
+ *   x          audio window [B][ld] fp32 whose row 0 is a frame boundary; valid_rows = real samples in it,
+ *              nframes*pool_stride <= valid_rows <= nframes*pool_stride + nlayers + 1 (and <= ld).  Rows at or beyond
+ *              valid_rows are past the end of the clip: the input of every layer is zero there (SAME padding).
+ *   nc_w/nc_b  'nc_conv' [2][128] / [128] fp32; nc_wr: its 1x1 as image [4][8] in permuted k order; nc_br [128]
+ *   wconv/wres layer l's images at + l*stride elements ([4][16] natural k / [4][8] permuted k, as srwn_nc_layer_fwd);
+ *              bias_c / bias_r [nlayers][128] fp32.  The last layer's residual 1x1 is never read.
+ *   partials   workspace of srwn_nc_encode_partials(B, nframes, pool_stride, nlayers) floats (fixed-order segment sums)
+ * A frame's result depends on its own window only: not on its place in the launch, the streams beside it or nframes.
+ * bf16, 128 channels, K = 2, at most srwn_nc_encode_max_layers() layers; fp32 or other widths: SRWN_E_UNSUPPORTED (run
+ * the layers one launch each); argument errors return before any launch. */
+int32_t srwn_nc_encode_max_layers(void);
+int64_t srwn_nc_encode_partials(int32_t B, int32_t nframes, int32_t pool_stride, int32_t nlayers);
+int srwn_nc_encode_frames(const float* x, int64_t ld, const float* nc_w, const float* nc_b, const void* nc_wr,
+                          const float* nc_br, const void* wconv, int64_t wconv_stride, const void* wres,
+                          int64_t wres_stride, const float* bias_c, const float* bias_r, float* partials, void* means,
+                          int32_t B, int32_t nframes, int32_t pool_stride, int32_t valid_rows, int32_t nlayers, int32_t C,
+                          int32_t K, int32_t dtype, void* stream);
 /* small products on the [B*frames] axis (latent 1x1 model.py:152, gradient wrt the encoding through model.py:180):
  *   C[m][n] = (accumulate ? C : 0) + bias[n] + sum_k A(m,k)*B(k,n), chunked addressing on both operands:
  *   A(m,k) = a[(k/a_chunk)*a_chunk_stride + m*lda + k%a_chunk];  B(k,n) = b[(k/b_chunk)*b_chunk_stride + (k%b_chunk)*ldb_k + n*ldb_n]

@@ -167,6 +167,11 @@ SIGNATURES = {
     "srwn_nc_mask_bits": (C.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p]),
     "srwn_nc_layer_bwd": (C.c_int, [_p, _p, _p, _p, _p, _p, _i64, _i32, _i32, _f32, _p, _p, _i32, _i32, _i32, _i32,
                                     _i32, _p]),
+    # the encoder for inference (srwn_version() 109)
+    "srwn_nc_encode_max_layers": (_i32, []),
+    "srwn_nc_encode_partials": (_i64, [_i32, _i32, _i32, _i32]),
+    "srwn_nc_encode_frames": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _i32,
+                                        _i32, _i32, _i32, _i32, _p]),
     "srwn_small_gemm": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _i64, _i64, _i32, _i64, _p, _p, _i64, _i32, _i32,
                                   _i32, _i32, _i32, _p]),
     "srwn_small_wgrad": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, _f32, _p]),

@@ -14,3 +14,4 @@ WaveNetAutoEncoder = _m.WaveNetAutoEncoder
 ParallelWaveNet = _m.ParallelWaveNet
 SiameseWaveNet = _m.SiameseWaveNet
 StudentSynthesizer = _m.StudentSynthesizer
+AudioEncoder = _m.AudioEncoder

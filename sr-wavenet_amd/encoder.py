@@ -32,33 +32,44 @@ from . import _lib
 from ._lib import call
 from .engine import Section, StackConfig, WaveNetEngine
 
+# What SRWN_ENC_FUSED means when it is not set (FrameEncoder in bf16): "0" the layer-by-layer twin, "1" the one-launch
+# chain.  Set by measurement: tools/encode_bench.py case (b) at B = 1, pool 512 has the chain at 0.160 ms per push
+# against the twin's 0.367 (spreads <= 0.016).  The README's knob table, FrameEncoder's docstring and that
+# tool's header state the same value (tests/test_encoder_stream.py holds the knob table to it).
+ENC_FUSED_DEFAULT = "1"
 
-class EncoderStack:
-    def __init__(self, nlayers: int, batch: int, length: int, pool_stride: int, encoder_channels: int = 128,
-                 skip_channels: int = 256, latent_channels: int = 16, filter_width: int = 2,
-                 dtype: torch.dtype = torch.bfloat16, learning_rate: float = 1e-3, device="cuda", seed: int = 0):
-        if encoder_channels != 128:
-            raise NotImplementedError("encoder_channels %d: the encoder kernels are built for 128 (the reference "
-                                      "default, model.py:76)" % encoder_channels)
-        if filter_width != 2:
-            raise NotImplementedError("filter_width %d: only 2 is built" % filter_width)
-        if skip_channels % 32 or skip_channels < 32:
-            raise NotImplementedError("skip_channels must be a multiple of 32")
-        if length % pool_stride:
-            raise ValueError("length %d is not a multiple of pool_stride %d" % (length, pool_stride))
-        self.L, self.B, self.T, self.pool = int(nlayers), int(batch), int(length), int(pool_stride)
-        self.N = self.B * self.T
-        self.frames = self.T // self.pool
-        self.rows_c = self.B * self.frames
-        self.EC, self.S, self.lat, self.Kw = encoder_channels, skip_channels, latent_channels, filter_width
-        self.dt, self.dev, self.lr = dtype, torch.device(device), learning_rate
-        self._build_params(seed)
-        self._build_packing()
-        self._alloc()
-        self.repack()
 
-    # -- parameters ----------------------------------------------------------------------------------
-    def _build_params(self, seed):
+def plan_frames(received: int, emitted: int, nlayers: int, pool_stride: int, final: bool = False,
+                max_frames: Optional[int] = None):
+    """Which frames of a stream can be encoded now, and from which samples.
+
+    With 'nc_conv' plus ``nlayers`` K = 2 layers that each look one sample ahead and none back, frame f depends on the
+    samples [f*P, (f+1)*P + nlayers + 1) and nothing else.  A running stream (``final=False``) that has received
+    ``received`` samples may therefore emit frame f once (f+1)*P + nlayers + 1 <= received; at the end of the clip
+    (``final=True``) every whole frame is due and the missing look-ahead is the clip-end zero padding.  Returns the
+    launches for the frames [emitted, due) as tuples ``(first_frame, nframes, start, valid_rows)``: a window of the stream
+    starting at sample ``start = first_frame * P`` with ``valid_rows`` real samples in it, at most ``max_frames`` frames
+    each.  Pure Python: the CPU tests drive the fp64 oracle with it."""
+    received, emitted, L, P = int(received), int(emitted), int(nlayers), int(pool_stride)
+    if received < 0 or emitted < 0 or L < 0 or P < 1 or emitted * P > received:
+        raise ValueError("plan_frames: received=%d emitted=%d nlayers=%d pool_stride=%d" % (received, emitted, L, P))
+    if max_frames is not None and max_frames < 1:
+        raise ValueError("plan_frames: max_frames %r" % (max_frames,))
+    due = received // P if final else max(0, (received - L - 1) // P)
+    out = []
+    f = emitted
+    while f < due:
+        n = due - f if max_frames is None else min(due - f, int(max_frames))
+        out.append((f, n, f * P, min(received - f * P, n * P + L + 1)))
+        f += n
+    return out
+
+
+class _EncoderParams:
+    """The encoder's flat fp32 parameter buffer by section, its initialisation and the reference's variable names:
+    what ``EncoderStack`` (training) and ``EncoderWeights`` (inference) share.  Needs self.L/EC/S/Kw/lat/dev."""
+
+    def _build_sections(self):
         L, EC, S, Kw, lat = self.L, self.EC, self.S, self.Kw, self.lat
         secs: Dict[str, Section] = {}
         off = 0
@@ -68,19 +79,17 @@ class EncoderStack:
             secs[name] = Section(name, off, shape)
             off += secs[name].numel
         self.sections, self.nparams = secs, off
-        z = lambda: torch.zeros(off, dtype=torch.float32, device=self.dev)
-        self.params, self.grads, self.adam_m, self.adam_v = z(), z(), z(), z()
-        self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.params = torch.zeros(off, dtype=torch.float32, device=self.dev)
         # 'nc_conv' has a skip 1x1 whose output is discarded (model.py:141): a variable without gradient
         self.dead = {"nc_ws": torch.zeros((EC, S), device=self.dev), "nc_bs": torch.zeros(S, device=self.dev)}
-        self.init_parameters(seed)
 
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
         s = self.sections[name]
         buf = self.params if buf is None else buf
         return buf[s.offset:s.offset + s.numel].view(s.shape)
 
-    def init_parameters(self, seed: int):
+    def _init_host(self, seed: int):
+        """Xavier-uniform kernels, zero biases -> self.params and the dead skip kernel."""
         rng = np.random.default_rng(seed)
 
         def xav(shape, fan_in, fan_out):
@@ -99,9 +108,8 @@ class EncoderStack:
         put("EWS", xav((L, EC, S), EC, S)); put("lat_w", xav((S, lat), S, lat))
         self.params.copy_(host)
         self.dead["nc_ws"].copy_(xav((EC, S), EC, S))
-        self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
 
-    def load_oracle_params(self, ep):
+    def _oracle_host(self, ep):
         host = torch.zeros(self.nparams, dtype=torch.float32)
 
         def put(name, arr):
@@ -113,8 +121,6 @@ class EncoderStack:
             put(nm, np.stack([getattr(p, f) for p in ep.layers]))
         put("lat_w", ep.lat_w); put("lat_b", ep.lat_b)
         self.params.copy_(host)
-        self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
-        self.repack()
 
     def named_tensors(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         v = lambda n: self.view(n, buf)
@@ -146,6 +152,52 @@ class EncoderStack:
         out[f"{scope}/{cname(2 * self.L + 2)}/kernel"] = n["lat_w"].unsqueeze(0)
         out[f"{scope}/{cname(2 * self.L + 2)}/bias"] = n["lat_b"]
         return out
+
+
+def _check_encoder_widths(encoder_channels, filter_width, skip_channels):
+    if encoder_channels != 128:
+        raise NotImplementedError("encoder_channels %d: the encoder kernels are built for 128 (the reference "
+                                  "default, model.py:76)" % encoder_channels)
+    if filter_width != 2:
+        raise NotImplementedError("filter_width %d: only 2 is built" % filter_width)
+    if skip_channels % 32 or skip_channels < 32:
+        raise NotImplementedError("skip_channels must be a multiple of 32")
+
+
+class EncoderStack(_EncoderParams):
+    def __init__(self, nlayers: int, batch: int, length: int, pool_stride: int, encoder_channels: int = 128,
+                 skip_channels: int = 256, latent_channels: int = 16, filter_width: int = 2,
+                 dtype: torch.dtype = torch.bfloat16, learning_rate: float = 1e-3, device="cuda", seed: int = 0):
+        _check_encoder_widths(encoder_channels, filter_width, skip_channels)
+        if length % pool_stride:
+            raise ValueError("length %d is not a multiple of pool_stride %d" % (length, pool_stride))
+        self.L, self.B, self.T, self.pool = int(nlayers), int(batch), int(length), int(pool_stride)
+        self.N = self.B * self.T
+        self.frames = self.T // self.pool
+        self.rows_c = self.B * self.frames
+        self.EC, self.S, self.lat, self.Kw = encoder_channels, skip_channels, latent_channels, filter_width
+        self.dt, self.dev, self.lr = dtype, torch.device(device), learning_rate
+        self._build_params(seed)
+        self._build_packing()
+        self._alloc()
+        self.repack()
+
+    # -- parameters ----------------------------------------------------------------------------------
+    def _build_params(self, seed):
+        self._build_sections()
+        z = lambda: torch.zeros(self.nparams, dtype=torch.float32, device=self.dev)
+        self.grads, self.adam_m, self.adam_v = z(), z(), z()
+        self.adam_step = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.init_parameters(seed)
+
+    def init_parameters(self, seed: int):
+        self._init_host(seed)
+        self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
+
+    def load_oracle_params(self, ep):
+        self._oracle_host(ep)
+        self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
+        self.repack()
 
     # -- MFMA weight images --------------------------------------------------------------------------
     def _build_packing(self):
@@ -416,3 +468,233 @@ class AutoEncoderEngine:
         self.allreduce_grads()
         self._g_opt.replay()
         return self.loss
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The encoder on its own: weights without a training shape, and the frame encoder that serves any batch and length
+# ----------------------------------------------------------------------------------------------------------------------
+class EncoderWeights(_EncoderParams):
+    """The encoder's parameters and MFMA images for inference: the sections, names and loaders of ``EncoderStack`` with
+    no batch, length, gradients or Adam state."""
+
+    def __init__(self, nlayers: int, encoder_channels: int = 128, skip_channels: int = 256, latent_channels: int = 16,
+                 filter_width: int = 2, dtype: torch.dtype = torch.bfloat16, device="cuda", seed: int = 0):
+        _check_encoder_widths(encoder_channels, filter_width, skip_channels)
+        if nlayers < 1:
+            raise ValueError("nlayers %d" % nlayers)
+        self.L = int(nlayers)
+        self.EC, self.S, self.lat, self.Kw = encoder_channels, skip_channels, latent_channels, filter_width
+        self.dt, self.dev = dtype, torch.device(device)
+        self._build_sections()
+        self._init_host(seed)
+        self._build_packing()
+        self.repack()
+
+    def load_oracle_params(self, ep):
+        self._oracle_host(ep)
+        self.repack()
+
+    def _build_packing(self):
+        L, EC, S, Kw = self.L, self.EC, self.S, self.Kw
+        sec = self.sections
+        pk = K.Packer(self.dev)
+        # per layer [conv | 1x1 in permuted k order] back to back: the one-launch kernel walks them by a stride
+        self.o_conv, self.o_wr_p, self.o_wr = [], [], []
+        for l in range(L):
+            self.o_conv.append(P.pack_conv(pk, sec["EW"].offset + l * Kw * EC * EC, Kw, EC))
+            self.o_wr_p.append(P.pack_linear(pk, sec["EWR"].offset + l * EC * EC, EC, EC, EC, perm=True))
+        self.layer_stride = self.o_conv[1] - self.o_conv[0] if L > 1 else 0
+        self.o_nc_wr_p = P.pack_linear(pk, sec["nc_wr"].offset, EC, EC, EC, perm=True)
+        # natural k order: the layer-by-layer path's row-streaming GEMMs (srwn_tap_linear)
+        self.o_nc_wr = P.pack_linear(pk, sec["nc_wr"].offset, EC, EC, EC)
+        for l in range(L):
+            self.o_wr.append(P.pack_linear(pk, sec["EWR"].offset + l * EC * EC, EC, EC, EC))
+        # every skip 1x1 as one image: rows = skip channel, k = layer*EC + n (applied to the frame means)
+        self.o_ws = pk.reserve(S // 32, L * EC // 16)
+        for l in range(L):
+            P.fill_linear(pk, self.o_ws, sec["EWS"].offset + l * EC * S, EC, S, S // 32, L * EC // 16,
+                          ks_offset=l * EC // 16, ks_count=EC // 16)
+        pk.finalize()
+        self.packer = pk
+        self.packed = torch.zeros(max(pk.total, 1), dtype=self.dt, device=self.dev)
+        self.bs_sum = torch.zeros(S, dtype=torch.float32, device=self.dev)
+
+    def wptr(self, off: int) -> int:
+        return self.packed.data_ptr() + off * self.packed.element_size()
+
+    def repack(self):
+        """Images and the sum of the skip biases from the current parameters (call after changing ``params``)."""
+        self.packer.gather(self.params, self.packed)
+        K.reduce_partials(self.view("EBS").reshape(-1), self.L, self.S, 1, True, 1.0, self.bs_sum.data_ptr(), 0)
+
+
+class EncoderStreamState:
+    """One batch of streams moving in lockstep through a ``FrameEncoder``: the samples received, the frames emitted and
+    the audio not consumed yet (fewer than pool_stride + nlayers + 1 samples per stream, on the device)."""
+    __slots__ = ("owner", "B", "received", "emitted", "tail", "closed")
+
+    def __init__(self, owner, B, tail):
+        self.owner, self.B, self.received, self.emitted, self.tail, self.closed = owner, B, 0, 0, tail, False
+
+
+class FrameEncoder:
+    """Audio in, latent frames out (createEncoder, model.py:136-156) for any batch <= ``max_batch`` and any length, whole
+    clips (``encode``) or chunk by chunk (``start`` / ``push`` / ``finish``).
+
+    Every layer of the encoder looks one sample ahead and none back, so a frame depends on its own pool_stride + L + 1
+    samples only (``plan_frames``): a stream carries no activations, only the audio it has not consumed, and a frame's
+    value does not depend on how the audio was cut.  In bf16 the whole chain of a launch's frames is ONE kernel
+    (srwn_nc_encode_frames) that leaves the per-frame means of a_1..a_L: the default (``ENC_FUSED_DEFAULT``), up to the
+    kernel's 32 layers.  SRWN_ENC_FUSED=0, fp32 and deeper encoders run the same windows one launch per layer with the
+    training kernels (each window as a clip of its own); ``fused`` says which path an object runs.  Both end in the
+    pooled skip product, its reduction and the latent 1x1."""
+
+    def __init__(self, weights: EncoderWeights, pool_stride: int, max_batch: int = 1, max_frames: int = 32):
+        self._check_weights(weights)
+        if pool_stride < 1 or max_batch < 1 or max_frames < 1:
+            raise ValueError("FrameEncoder: pool_stride=%r max_batch=%r max_frames=%r" % (pool_stride, max_batch, max_frames))
+        w = self.w = weights
+        self.P, self.max_batch, self.max_frames = int(pool_stride), int(max_batch), int(max_frames)
+        self.L, self.lat = w.L, w.lat
+        lib = _lib.load()
+        self.fused = (w.dt == torch.bfloat16 and os.environ.get("SRWN_ENC_FUSED", ENC_FUSED_DEFAULT) != "0" and
+                      w.L <= int(lib.srwn_nc_encode_max_layers()))
+        # the twin's layers: srwn_nc_layer_fwd in bf16 unless SRWN_NC_FUSED=0 (two time-tap GEMMs per layer, as in training)
+        self.layer_fused = w.dt == torch.bfloat16 and os.environ.get("SRWN_NC_FUSED", "1") != "0"
+        rows = self.max_batch * self.max_frames
+        f = lambda *s: torch.zeros(s, dtype=torch.float32, device=w.dev)
+        self.a_mean = torch.zeros(w.L * rows * w.EC, dtype=w.dt, device=w.dev)
+        self.s_parts = f(w.L * rows * w.S)
+        self.s_mean = f(rows * w.S)
+        self.enc = f(rows * w.lat)
+        self.wmax = self.max_frames * self.P + w.L + 1          # the longest window of one launch
+        if self.fused:
+            self.parts = f(int(lib.srwn_nc_encode_partials(self.max_batch, self.max_frames, self.P, w.L)))
+        else:
+            n = self.max_batch * self.wmax
+            self.xs = f(n)
+            self.r = torch.zeros(2 * n * w.EC, dtype=w.dt, device=w.dev)
+            self.a = torch.zeros((w.L + 1) * n * w.EC, dtype=w.dt, device=w.dev)      # [a_0 | a_1 .. a_L]
+
+    @staticmethod
+    def _check_weights(w):
+        if getattr(w, "EC", None) != 128:
+            raise NotImplementedError("encoder_channels %r: the encoder kernels are built for 128" % getattr(w, "EC", None))
+        if getattr(w, "Kw", None) != 2:
+            raise NotImplementedError("filter_width %r: only 2 is built" % getattr(w, "Kw", None))
+
+    def device_bytes(self) -> int:
+        """Bytes of the buffers this object owns (the weights' parameters and images are counted with the weights)."""
+        return sum(t.numel() * t.element_size() for t in vars(self).values() if isinstance(t, torch.Tensor))
+
+    # -- one launch sequence: B streams x nframes frames from a window --------------------------------------------
+    def _run(self, x: torch.Tensor, nframes: int, valid: int) -> torch.Tensor:
+        """x [B, >= valid] fp32 (rows `x.stride(0)` apart), column 0 = the first frame's first sample."""
+        w, P_, L = self.w, self.P, self.L
+        B, EC, S, dt = x.shape[0], w.EC, w.S, K.abi_dtype(w.dt)
+        rows, st, v = B * nframes, K._stream(), w.view
+        if self.fused:
+            call("srwn_nc_encode_frames", x.data_ptr(), x.stride(0), v("nc_w").data_ptr(), v("nc_b").data_ptr(),
+                 w.wptr(w.o_nc_wr_p), v("nc_br").data_ptr(), w.wptr(w.o_conv[0]), w.layer_stride, w.wptr(w.o_wr_p[0]),
+                 w.layer_stride, v("EB").data_ptr(), v("EBR").data_ptr(), self.parts.data_ptr(), self.a_mean.data_ptr(),
+                 B, nframes, P_, valid, L, EC, w.Kw, dt, st)
+        else:
+            self._layers(x, nframes, valid)
+        call("srwn_pw_linear_ksplit", self.a_mean.data_ptr(), EC, rows * EC, EC, L * EC, w.wptr(w.o_ws),
+             w.bs_sum.data_ptr(), self.s_parts.data_ptr(), S, S, S, rows, L, dt, st)
+        K.reduce_partials(self.s_parts, L, rows * S, 1, True, 1.0, self.s_mean.data_ptr(), 0)
+        call("srwn_small_gemm", self.s_mean.data_ptr(), S, S, 0, K.F32, v("lat_w").data_ptr(), self.lat, 1, S, 0,
+             v("lat_b").data_ptr(), self.enc.data_ptr(), self.lat, K.F32, rows, self.lat, S, 0, st)
+        return self.enc[:rows * self.lat].view(B, nframes, self.lat).clone()
+
+    def _layers(self, x, nframes, valid):
+        """The window as a clip of its own, one launch per layer (EncoderStack.forward's kernels): the false zero padding
+        at its end moves inward one row per layer and never reaches a frame row."""
+        w, P_, L = self.w, self.P, self.L
+        B, EC, T = x.shape[0], w.EC, int(valid)
+        N, dt, st, v, es = B * T, K.abi_dtype(w.dt), K._stream(), w.view, self.a.element_size()
+        xs = self.xs[:N].view(B, T)
+        xs.copy_(x[:, :T])
+        a = lambda l: self.a.data_ptr() + l * N * EC * es
+        r = lambda l: self.r.data_ptr() + (l & 1) * N * EC * es
+        frames = (T + P_ - 1) // P_
+
+        def tap(xp, ntaps, step, wp, bias, yp):
+            call("srwn_tap_linear", xp, EC, ntaps, step, T, EC, wp, bias.data_ptr(), yp, EC, EC, N, None, EC, None, L * EC,
+                 frames, P_, 1.0 / P_, K.EPI_RELU, dt, st)
+
+        call("srwn_nc_input_fwd", xs.data_ptr(), v("nc_w").data_ptr(), v("nc_b").data_ptr(), a(0), B, T, EC, w.Kw, dt, st)
+        tap(a(0), 1, 0, w.wptr(w.o_nc_wr), v("nc_br"), r(0))
+        for l in range(L):
+            last = l == L - 1          # the last layer's residual output is never used (model.py:144-150)
+            if self.layer_fused:
+                call("srwn_nc_layer_fwd", r(l), w.wptr(w.o_conv[l]), w.wptr(w.o_wr_p[l]), v("EB")[l].data_ptr(),
+                     v("EBR")[l].data_ptr(), a(l + 1), None if last else r(l + 1), None, None, B, T, EC, w.Kw, dt, st)
+                continue
+            tap(r(l), w.Kw, 1, w.wptr(w.o_conv[l]), v("EB")[l], a(l + 1))
+            if not last:
+                tap(a(l + 1), 1, 0, w.wptr(w.o_wr[l]), v("EBR")[l], r(l + 1))
+        call("srwn_frame_sum_batched", a(1), N * EC, self.a_mean.data_ptr(), B * nframes * EC, L, B, T, EC, nframes, P_,
+             1.0 / P_, dt, st)
+
+    # -- public --------------------------------------------------------------------------------------------------
+    def _audio(self, audio, B=None):
+        if isinstance(audio, torch.Tensor):
+            x = audio
+        else:
+            x = torch.as_tensor(np.asarray(audio, dtype=np.float32))
+        if x.dim() != 2:
+            raise ValueError("audio must be [batch, samples], got shape %s" % (tuple(x.shape),))
+        if not 1 <= x.shape[0] <= self.max_batch:
+            raise ValueError("batch %d: this encoder was built for max_batch=%d" % (x.shape[0], self.max_batch))
+        if B is not None and x.shape[0] != B:
+            raise ValueError("audio of %d streams pushed into a state of %d" % (x.shape[0], B))
+        if x.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+            raise ValueError("audio must be floating point, got %s" % x.dtype)
+        return x
+
+    def _emit(self, buf, base, received, emitted, final):
+        """Runs the launches `plan_frames` asks for over buf (column 0 = sample `base`) -> ([B, k, latent], frames)."""
+        outs = []
+        for (f0, n, start, valid) in plan_frames(received, emitted, self.L, self.P, final, self.max_frames):
+            outs.append(self._run(buf[:, start - base:], n, valid))
+            emitted = f0 + n
+        if not outs:
+            return torch.zeros((buf.shape[0], 0, self.lat), dtype=torch.float32, device=self.w.dev), emitted
+        return (outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)), emitted
+
+    def encode(self, audio) -> torch.Tensor:
+        """audio [B, T] -> [B, T // pool_stride, latent] fp32 on the device (T < pool_stride: no frame)."""
+        x = self._audio(audio).to(device=self.w.dev, dtype=torch.float32).contiguous()
+        return self._emit(x, 0, x.shape[1], 0, True)[0]
+
+    def start(self, batch: int = 1) -> EncoderStreamState:
+        if not 1 <= int(batch) <= self.max_batch:
+            raise ValueError("batch %r: this encoder was built for max_batch=%d" % (batch, self.max_batch))
+        return EncoderStreamState(self, int(batch), torch.zeros((int(batch), 0), dtype=torch.float32, device=self.w.dev))
+
+    def _state(self, state):
+        if not isinstance(state, EncoderStreamState) or state.owner is not self:
+            raise ValueError("this state was not started by this encoder")
+        if state.closed:
+            raise ValueError("this stream is closed (finish was called)")
+        return state
+
+    def push(self, state: EncoderStreamState, audio) -> torch.Tensor:
+        """audio [B, n], n >= 0 -> the frames whose look-ahead is now complete, [B, k, latent] (k may be 0)."""
+        st = self._state(state)
+        x = self._audio(audio, st.B)
+        buf = torch.cat([st.tail, x.to(device=self.w.dev, dtype=torch.float32)], dim=1)
+        base, received = st.emitted * self.P, st.received + int(x.shape[1])
+        out, emitted = self._emit(buf, base, received, st.emitted, False)
+        st.tail = buf[:, emitted * self.P - base:].clone()
+        st.received, st.emitted = received, emitted
+        return out
+
+    def finish(self, state: EncoderStreamState) -> torch.Tensor:
+        """The remaining whole frames, with the clip-end padding; the state is closed afterwards."""
+        st = self._state(state)
+        out, emitted = self._emit(st.tail, st.emitted * self.P, st.received, st.emitted, True)
+        st.emitted, st.closed = emitted, True
+        st.tail = st.tail[:, :0]
+        return out

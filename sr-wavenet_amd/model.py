@@ -9,6 +9,8 @@ wrappers, but no TensorFlow: the graph body is the fixed kernel sequence of ``en
                             model.py:100-112); this is the benchmark path.
 * ``WaveNetAutoEncoder`` -- model.py:75-285: non-causal encoder + conditioned mixture-of-logistics decoder
                             (encoder.AutoEncoderEngine), the teacher teacher.py trains.
+* ``AudioEncoder``       -- that auto-encoder's encoder on its own (encoder.FrameEncoder): any batch, any length,
+                            whole clips or streams.
 * ``ParallelWaveNet``    -- model.py:290-656: the IAF student distilled against that frozen teacher
                             (student.StudentEngine).
 * ``SiameseWaveNet``     -- model.py:660-797: two weight-sharing WaveNet towers trained on pairs with the contrastive
@@ -645,6 +647,20 @@ class WaveNetAutoEncoder(object):
         eng = self._stage(inputs, conditions)
         return eng.encode().view(eng.B, -1, self.latent_channels).cpu().numpy()
 
+    def encoder(self, max_batch=1, max_frames=32):
+        """An ``AudioEncoder`` with this model's hyper-parameters and a COPY of its current encoder parameters (a
+        snapshot: call it again after more training).  It takes any batch <= max_batch and any length."""
+        eng = self._eng or self._engine(1, self.input_size)
+        enc = AudioEncoder(len(self.dilations), skip_channels=self.skip_channels, latent_channels=self.latent_channels,
+                           pool_stride=self.pool_stride, encoder_channels=self.encoder_channels,
+                           filter_width=self.filter_width, name=self._name, dtype=self._cfg.dtype, max_batch=max_batch,
+                           max_frames=max_frames)
+        enc._w.params.copy_(eng.enc.params)
+        for k, t in eng.enc.dead.items():
+            enc._w.dead[k].copy_(t)
+        enc._w.repack()
+        return enc
+
     def reconstruct(self, inputs, conditions=None, seed=None):
         """``self.out`` (model.py:268-273): encode, run the decoder teacher-forced on the same clip, sample."""
         eng = self._stage(inputs, conditions)
@@ -749,6 +765,102 @@ class WaveNetAutoEncoder(object):
     def mu_law(self, inputs, conditions=None):
         raise AttributeError("WaveNetAutoEncoder.mu_law reads self.targets, which the reference never defines "
                              "(model.py:100,276): it raises there too")
+
+
+class AudioEncoder(object):
+    """The deployable form of the auto-encoder's encoder (createEncoder, model.py:136-156): audio in, latent frames out
+    (``encoder.FrameEncoder``), with no decoder and no training state anywhere.  One object serves any batch <=
+    ``max_batch`` and any length, whole clips (``encode``) or chunk by chunk (``stream``); a frame's value does not
+    depend on how the audio was cut.  ``load`` reads what ``WaveNetAutoEncoder.save`` wrote, by the reference's
+    variable names; the decoder's variables in the file are ignored."""
+
+    def __init__(self, num_layers, skip_channels=256, latent_channels=16, pool_stride=512, encoder_channels=128,
+                 filter_width=2, name="WaveNetAutoEncoder", dtype=None, max_batch=1, max_frames=32):
+        from .encoder import EncoderWeights, FrameEncoder, _check_encoder_widths
+        _check_encoder_widths(encoder_channels, filter_width, skip_channels)
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        self.num_layers, self.skip_channels, self.latent_channels = int(num_layers), skip_channels, latent_channels
+        self.pool_stride, self.encoder_channels, self.filter_width = int(pool_stride), encoder_channels, filter_width
+        self._name = name
+        self.max_batch, self.max_frames = int(max_batch), int(max_frames)
+        self._w = EncoderWeights(self.num_layers, encoder_channels, skip_channels, latent_channels, filter_width,
+                                 dtype or _default_dtype())
+        self._eng = FrameEncoder(self._w, self.pool_stride, max_batch=max_batch, max_frames=max_frames)
+
+    @property
+    def network_params(self):
+        return self._w.tf_variables(self._name + "/Encoder")
+
+    def load(self, logdir):
+        ok = _read_state(logdir, lambda: self.network_params)
+        if ok:
+            self._w.repack()
+        return ok
+
+    @classmethod
+    def from_checkpoint(cls, logdir, **kwargs):
+        """An encoder on the variables saved in `logdir`, with the hyper-parameters of the ``config.json`` that
+        ``WaveNetAutoEncoder.save`` writes beside them; kwargs: dtype, max_batch, max_frames."""
+        import json
+        with open(os.path.join(logdir, "config.json")) as f:
+            cfg = json.load(f)
+        enc = cls(len(cfg["dilations"]), skip_channels=cfg["skip_channels"], latent_channels=cfg["latent_channels"],
+                  pool_stride=cfg["pool_stride"], encoder_channels=cfg["encoder_channels"],
+                  filter_width=cfg["filter_width"], name=cfg.get("name", "WaveNetAutoEncoder"), **kwargs)
+        if not enc.load(logdir):
+            raise FileNotFoundError("%s: no checkpoint to restore (WaveNetAutoEncoder.save writes one)" % logdir)
+        return enc
+
+    def _check(self, inputs, batch=None):
+        """Shape refusals, before anything touches the device."""
+        x = np.asarray(inputs, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("inputs must be [batch, samples], got shape %s" % (x.shape,))
+        if not 1 <= x.shape[0] <= self.max_batch:
+            raise ValueError("batch %d: this encoder was built for max_batch=%d" % (x.shape[0], self.max_batch))
+        if batch is not None and x.shape[0] != batch:
+            raise ValueError("audio of %d streams pushed into a stream of %d" % (x.shape[0], batch))
+        return x
+
+    def encode(self, inputs):
+        """inputs [B, T] -> encoding [B, T // pool_stride, latent_channels] (NumPy), for any T."""
+        x = self._check(inputs)
+        return self._eng.encode(torch.as_tensor(x)).cpu().numpy()
+
+    def stream(self, batch_size=1):
+        """An ``EncoderStream`` of `batch_size` streams in lockstep: ``push(audio [B, n])`` returns the frames whose
+        look-ahead is complete, ``finish()`` the rest with the clip-end padding."""
+        if not 1 <= int(batch_size) <= self.max_batch:
+            raise ValueError("batch_size %r: this encoder was built for max_batch=%d" % (batch_size, self.max_batch))
+        return EncoderStream(self, int(batch_size))
+
+
+class EncoderStream(object):
+    """NumPy face of one running batch of encoder streams (``AudioEncoder.stream``).  ``t``: samples received per
+    stream; ``frames``: frames emitted.  Everything ``push`` returned followed by what ``finish`` returns equals
+    ``AudioEncoder.encode`` of the concatenated audio."""
+
+    def __init__(self, owner, batch_size):
+        self._owner, self.batch_size = owner, batch_size
+        self._st = owner._eng.start(batch_size)
+
+    @property
+    def t(self):
+        return self._st.received
+
+    @property
+    def frames(self):
+        return self._st.emitted
+
+    def push(self, audio):
+        if self._st.closed:
+            raise ValueError("this stream is closed (finish was called)")
+        x = self._owner._check(audio, self.batch_size)
+        return self._owner._eng.push(self._st, torch.as_tensor(x)).cpu().numpy()
+
+    def finish(self):
+        return self._owner._eng.finish(self._st).cpu().numpy()
 
 
 class ParallelWaveNet(object):
