@@ -16,13 +16,12 @@
 #include <cstdlib>
 #include <type_traits>
 #include "srwn_common.h"
+#include "srwn_gen_ring.h"
 #include "srwn_host.h"
 #include "srwn_sample.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
-
-constexpr int kGenMaxLayers = 64;
 
 struct GenArgs {
   const void* wcr;      // per layer: [conv image RT x 2KS (tap0 natural, tap1 permuted) | res image RT x KS (permuted)]
@@ -61,21 +60,6 @@ template <bool SLOTS, bool SAMP> struct GenArgsOf {
   using type = typename std::conditional<SLOTS, typename std::conditional<SAMP, GenSlotSampArgs, GenSlotArgs>::type,
                                          typename std::conditional<SAMP, GenSampArgs, GenArgs>::type>::type;
 };
-
-__device__ __forceinline__ float gen_mu_law_decode(int code, int Q) {   // ops.py:96-104, as srwn_mu_law_decode
-  const float mu = (float)(Q - 1);
-  const float signal = __fadd_rn(__fmul_rn(2.0f, __fdiv_rn((float)code, mu)), -1.0f);
-  const float p = (float)pow((double)Q, (double)fabsf(signal));
-  const float magnitude = __fmul_rn((float)(1.0 / (double)(Q - 1)), __fadd_rn(p, -1.0f));
-  const float sgn = (signal > 0.0f) ? 1.0f : ((signal < 0.0f) ? -1.0f : 0.0f);
-  return __fmul_rn(sgn, magnitude);
-}
-
-__device__ __forceinline__ float gen_uniform(unsigned long long seed, unsigned u, unsigned t) {
-  unsigned long long x = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)u * 0x100000001ull + t + 1);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-  return (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f);   // (0,1)
-}
 
 // the carry a launch leaves for the next one (its last __syncthreads ordered prev): the samples step t_end reads, i.e. the
 // emitted ones of a free-running launch, the forced ones of a forced launch (prev[] holds the emitted ones there; after a
@@ -519,9 +503,8 @@ __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS,
 }
 
 extern "C" int64_t srwn_generate_ring_elems(const int32_t* dilations, int32_t nlayers, int32_t R) {
-  int64_t n = 0;
-  for (int l = 0; l < nlayers; ++l) n += (int64_t)(dilations[l] + 1) * 32 * R;
-  return n;   // per group of 32 utterances
+  int bad;
+  return gen_ring_layout(dilations, nlayers, R, INT32_MAX, &bad);   // per group of 32 utterances
 }
 
 template <bool SL, bool SA, typename A>
@@ -563,6 +546,11 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
                          uint64_t seed, int32_t dtype, void* stream, const void* cond, int32_t cond_frames,
                          int32_t pool, int64_t cond_ld, int32_t M, int32_t t0, float* carry,
                          const SrwnGenSampling* sampling, SrwnGenSlot* slots = nullptr, bool slot_form = false) {
+  // the mixture-of-logistics head (M > 0): its conditioning, checked before anything else as its entry points always did
+  if (M > 0 && cond && (cond_frames < 1 || pool < 1 || cond_ld < (int64_t)nlayers * R))
+    return set_error(SRWN_E_SHAPE, "%s: cond_frames=%d pool_stride=%d cond_ld=%lld",
+                     slot_form ? "generate_mol_slots" : "generate_mol", cond_frames, pool, (long long)cond_ld);
+  if (!cond) cond_frames = pool = 1;
   if (B == 0 || nsteps == 0) return 0;
   if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate: t0=%d", t0);
   if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate: a launch that resumes at t0=%d needs the carry", t0);
@@ -587,16 +575,9 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
   a.audio_out = audio_out - sh; a.codes_out = codes_out - sh;
   a.logits_out = logits_out ? logits_out - sh * C : nullptr; a.forced = forced ? forced - sh : nullptr;
   a.nsteps = t0 + nsteps; a.t0 = t0; a.carry = carry;
-  long long off = 0;
-  for (int l = 0; l < kGenMaxLayers; ++l) {
-    a.dil[l] = (l < nlayers) ? dilations[l] : 1;
-    a.ring_off[l] = off;
-    if (l < nlayers) {
-      if (dilations[l] < 1) return set_error(SRWN_E_SHAPE, "generate: dilation %d", dilations[l]);
-      off += (long long)(dilations[l] + 1) * 32 * R;
-    }
-  }
-  a.ring_group_elems = off;
+  int bad;
+  a.ring_group_elems = gen_ring_layout(dilations, nlayers, R, INT32_MAX, &bad, a.dil, a.ring_off);
+  if (bad >= 0) return set_error(SRWN_E_SHAPE, "generate: dilation %d", dilations[bad]);
   const unsigned groups = (unsigned)((B + 31) / 32);
   hipStream_t st = (hipStream_t)stream;
   const bool cd = cond != nullptr;
@@ -664,12 +645,9 @@ extern "C" int srwn_generate_mol_resume_sampled(const void* wcr, const void* wsk
                                         float* carry, const SrwnGenSampling* sampling) {
   if (num_mixtures < 1 || num_mixtures > 16)
     return set_error(SRWN_E_SHAPE, "generate_mol: num_mixtures=%d (1..16)", num_mixtures);
-  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
-    return set_error(SRWN_E_SHAPE, "generate_mol: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames, pool_stride,
-                     (long long)cond_ld);
   return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
                        logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, seed,
-                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, t0,
+                       dtype, stream, cond, cond_frames, pool_stride, cond_ld, num_mixtures, t0,
                        carry, sampling);
 }
 
@@ -740,12 +718,9 @@ extern "C" int srwn_generate_mol_slots_sampled(const void* wcr, const void* wski
                                        SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
   if (num_mixtures < 1 || num_mixtures > 16)
     return set_error(SRWN_E_SHAPE, "generate_mol_slots: num_mixtures=%d (1..16)", num_mixtures);
-  if (cond && (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R))
-    return set_error(SRWN_E_SHAPE, "generate_mol_slots: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
-                     pool_stride, (long long)cond_ld);
   return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
                        logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, 0,
-                       dtype, stream, cond, cond ? cond_frames : 1, cond ? pool_stride : 1, cond_ld, num_mixtures, clock,
+                       dtype, stream, cond, cond_frames, pool_stride, cond_ld, num_mixtures, clock,
                        carry, sampling, slots, true);
 }
 
@@ -811,20 +786,11 @@ extern "C" int srwn_generate_ring_fill(const void* xs, int64_t layer_stride, int
                      nlayers, (long long)layer_stride);
   RingFillArgs a;
   a.xs = xs; a.ring = ring; a.layer_stride = layer_stride; a.T_src = T_src; a.P = P; a.B = B; a.R = R;
-  long long off = 0;
-  int maxvec = 0;
-  for (int l = 0; l < kGenMaxLayers; ++l) {
-    a.dil[l] = (l < nlayers) ? dilations[l] : 1;
-    a.ring_off[l] = off;
-    if (l < nlayers) {
-      if (dilations[l] < 1 || dilations[l] > (1 << 20))
-        return set_error(SRWN_E_SHAPE, "generate_ring_fill: dilation %d", dilations[l]);
-      off += (long long)(dilations[l] + 1) * 32 * R;
-      maxvec = max(maxvec, (dilations[l] + 1) * 32 * (R / V));
-    }
-  }
+  int bad, maxvec = 0;
+  a.ring_group_elems = gen_ring_layout(dilations, nlayers, R, 1 << 20, &bad, a.dil, a.ring_off);
+  if (bad >= 0) return set_error(SRWN_E_SHAPE, "generate_ring_fill: dilation %d", dilations[bad]);
+  for (int l = 0; l < nlayers; ++l) maxvec = max(maxvec, (a.dil[l] + 1) * 32 * (R / V));
   if ((reinterpret_cast<uintptr_t>(ring) & 15)) return set_error(SRWN_E_SHAPE, "generate_ring_fill: ring not 16-byte aligned");
-  a.ring_group_elems = off;
   const dim3 grid((unsigned)min((maxvec + 255) / 256, 1024), (unsigned)nlayers, (unsigned)((B + 31) / 32));
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_fill_kernel<bf16_t>, grid, dim3(256), 0, st, a);
@@ -888,19 +854,10 @@ extern "C" int srwn_generate_ring_fill_slots(const void* xs, int64_t layer_strid
   RingFillSlotsArgs a;
   a.xs = xs; a.ring = ring; a.dst = dst; a.P = P; a.layer_stride = layer_stride; a.T_src = T_src; a.B = B; a.R = R;
   a.clock = clock;
-  long long off = 0;
-  int maxvec = 0;
-  for (int l = 0; l < kGenMaxLayers; ++l) {
-    a.dil[l] = (l < nlayers) ? dilations[l] : 1;
-    a.ring_off[l] = off;
-    if (l < nlayers) {
-      if (dilations[l] < 1 || dilations[l] > (1 << 20))
-        return set_error(SRWN_E_SHAPE, "generate_ring_fill_slots: dilation %d", dilations[l]);
-      off += (long long)(dilations[l] + 1) * 32 * R;
-      maxvec = max(maxvec, (dilations[l] + 1) * (R / V));
-    }
-  }
-  a.ring_group_elems = off;
+  int bad, maxvec = 0;
+  a.ring_group_elems = gen_ring_layout(dilations, nlayers, R, 1 << 20, &bad, a.dil, a.ring_off);
+  if (bad >= 0) return set_error(SRWN_E_SHAPE, "generate_ring_fill_slots: dilation %d", dilations[bad]);
+  for (int l = 0; l < nlayers; ++l) maxvec = max(maxvec, (a.dil[l] + 1) * (R / V));
   const dim3 grid((unsigned)min((maxvec + 255) / 256, 1024), (unsigned)nlayers, (unsigned)n);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_fill_slots_kernel<bf16_t>, grid, dim3(256), 0, st, a);

@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "srwn_common.h"
 #include "srwn_group.h"
+#include "srwn_gen_ring.h"
 #include "srwn_host.h"
 #include "srwn_sample.h"
 #include "../../include/srwn.h"
@@ -25,8 +26,6 @@ using namespace srwn;
 using namespace srwn::grp;
 
 namespace {
-
-constexpr int kG16MaxLayers = 64;
 
 struct Gen16Args {
   const void* wl;       // per layer: [4 waves][conv ks 0..3 | res ks 0..1 | skip (rb 0..3) x (ks 0..1)] 16x32 A fragments
@@ -43,8 +42,8 @@ struct Gen16Args {
   int t0; float* carry;                         // resume form (as generate_kernel's GenArgs): absolute first step, carry [B][2]
   long long ring_group_elems;
   unsigned long long seed;
-  int dil[kG16MaxLayers];
-  long long ring_off[kG16MaxLayers];
+  int dil[kGenMaxLayers];
+  long long ring_off[kGenMaxLayers];
 };
 // the slot form (generation pools): t0 is the pool's clock, and per-slot state replaces seed / t where a stream's own
 // position matters (srwn.h, SrwnGenSlot).  A struct of its own, so that the other instantiations keep their arguments
@@ -57,21 +56,6 @@ template <bool SLOTS, bool SAMP> struct Gen16ArgsOf {
   using type = typename std::conditional<SLOTS, typename std::conditional<SAMP, Gen16SlotSampArgs, Gen16SlotArgs>::type,
                                          typename std::conditional<SAMP, Gen16SampArgs, Gen16Args>::type>::type;
 };
-
-__device__ __forceinline__ float g16_mu_law_decode(int code, int Q) {   // ops.py:96-104, as srwn_mu_law_decode
-  const float mu = (float)(Q - 1);
-  const float signal = __fadd_rn(__fmul_rn(2.0f, __fdiv_rn((float)code, mu)), -1.0f);
-  const float p = (float)pow((double)Q, (double)fabsf(signal));
-  const float magnitude = __fmul_rn((float)(1.0 / (double)(Q - 1)), __fadd_rn(p, -1.0f));
-  const float sgn = (signal > 0.0f) ? 1.0f : ((signal < 0.0f) ? -1.0f : 0.0f);
-  return __fmul_rn(sgn, magnitude);
-}
-
-__device__ __forceinline__ float g16_uniform(unsigned long long seed, unsigned u, unsigned t) {   // as gen_uniform (srwn_gen.hip)
-  unsigned long long x = seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)u * 0x100000001ull + t + 1);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-  return (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f);
-}
 
 typedef bf16_t T;
 constexpr int LGS = 256;
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
     const int ul = threadIdx.x & 31, u = u0 + ul;
     prev[threadIdx.x] = (a.carry && ul < NU && u < a.B) ? a.carry[2 * u + (threadIdx.x >> 5)] : 0.0f;
   }
-  c_dec[threadIdx.x] = g16_mu_law_decode((int)threadIdx.x < a.Q ? (int)threadIdx.x : a.Q - 1, a.Q);
+  c_dec[threadIdx.x] = gen_mu_law_decode((int)threadIdx.x < a.Q ? (int)threadIdx.x : a.Q - 1, a.Q);
   if constexpr (SLOTS) {   // the slots of this workgroup, read once: nothing of them stays live in registers
     if (threadIdx.x < 32) {
       const int ul = threadIdx.x, u = u0 + ul;
@@ -448,7 +432,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
         const unsigned su = SLOTS ? 0u : (unsigned)u;
         const int tu = SLOTS ? slot_t(ul, j) : t;
         if (mx < a.M) {
-          const float u1 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + mx));
+          const float u1 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + mx));
           v = lg[mx] - logf(-logf(u1));
           if constexpr (SAMP) v = lg[mx] / __builtin_bit_cast(float, sc[ul]) - logf(-logf(u1));   // (tau = 1: the same bits)
         }
@@ -461,7 +445,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
         if (mx == 0) {
           float smp = lg[a.M + sel];                               // mode 0: the selected mean (no logistic noise)
           if (a.mode == 1) {
-            const float u2 = 1e-5f + (1.0f - 2e-5f) * g16_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + a.M));
+            const float u2 = 1e-5f + (1.0f - 2e-5f) * gen_uniform(sseed, su, (unsigned)(tu * (a.M + 1) + a.M));
             float sc_ = expf(fmaxf(lg[2 * a.M + sel], -7.0f));
             if constexpr (SAMP) sc_ = __builtin_bit_cast(float, sc[ul]) * sc_;      // the temperature on the logistic noise
             smp += sc_ * (logf(u2) - logf(1.0f - u2));
@@ -537,9 +521,9 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
         float uni;
         if constexpr (SLOTS) {
           const int ul = NI * wave + (lane & (NI - 1));
-          uni = g16_uniform(slot_seed(ul), 0u, (unsigned)slot_t(ul, j));
+          uni = gen_uniform(slot_seed(ul), 0u, (unsigned)slot_t(ul, j));
         } else {
-          uni = g16_uniform(a.seed, (unsigned)(u0 + NI * wave + (lane & (NI - 1))), (unsigned)t);
+          uni = gen_uniform(a.seed, (unsigned)(u0 + NI * wave + (lane & (NI - 1))), (unsigned)t);
         }
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
@@ -634,16 +618,9 @@ extern "C" int64_t srwn_generate16_image_elems(int32_t nlayers, int32_t which, i
 
 template <int R, int S, bool SLOTS, bool SAMP, typename A>
 static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, int32_t B, bool cond, int32_t M, void* stream) {
-  long long off = 0;
-  for (int l = 0; l < kG16MaxLayers; ++l) {
-    a.dil[l] = (l < nlayers) ? dilations[l] : 1;
-    a.ring_off[l] = off;
-    if (l < nlayers) {
-      if (dilations[l] < 1) return set_error(SRWN_E_SHAPE, "generate16: dilation %d", dilations[l]);
-      off += (long long)(dilations[l] + 1) * 32 * R;
-    }
-  }
-  a.ring_group_elems = off;
+  int bad;
+  a.ring_group_elems = gen_ring_layout(dilations, nlayers, R, INT32_MAX, &bad, a.dil, a.ring_off);
+  if (bad >= 0) return set_error(SRWN_E_SHAPE, "generate16: dilation %d", dilations[bad]);
   // half-size workgroups while they still find a CU each (and always for a single stream's latency)
   bool half = (B + 15) / 16 <= num_cus();
   if (const char* e = getenv("SRWN_GEN16_NCB")) half = atoi(e) == 1;   // (tests: both bodies at any batch)
@@ -677,7 +654,7 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
     return set_error(SRWN_E_NULL, "generate16: null pointer");
   if ((R != 64 && R != 32) || (S != 256 && S != 128) || C < 2 || C > 256)
     return set_error(SRWN_E_UNSUPPORTED, "generate16: built for R = 64 or 32, S = 256 or 128, C <= 256 (got R=%d S=%d C=%d)", R, S, C);
-  if (B < 0 || nsteps < 0 || nsteps > Tout || nlayers < 1 || nlayers > kG16MaxLayers || (mode != 0 && mode != 1))
+  if (B < 0 || nsteps < 0 || nsteps > Tout || nlayers < 1 || nlayers > kGenMaxLayers || (mode != 0 && mode != 1))
     return set_error(SRWN_E_SHAPE, "generate16: B=%d nsteps=%d Tout=%d layers=%d mode=%d", B, nsteps, Tout, nlayers, mode);
   if (M == 0 && cond) return set_error(SRWN_E_UNSUPPORTED, "generate16: the conditioned softmax teacher is not built");
   if (cond && (cond_frames < 1 || pool < 1 || cond_ld < (int64_t)nlayers * R || (cond_ld % 4)))

@@ -17,7 +17,9 @@ buffers laid out struct-of-arrays across layers so every batched kernel sees a c
 """
 from __future__ import annotations
 
+import ctypes
 import math
+import os as _os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -171,8 +173,6 @@ class GenerationPool:
     Joins are ordered between steps.  Steps, clock and limits are int32 (2^31 steps is about 37 h at 16 kHz)."""
 
     def __init__(self, eng: "WaveNetEngine", capacity: int, frames: int = 0):
-        import ctypes as C
-        from . import _lib
         self.eng, self.capacity, self.frames = eng, int(capacity), int(frames)
         self.conditioned = bool(eng.mol and eng.E)
         self.E, self.pool_stride = int(eng.E), int(eng.cfg.pool_stride)
@@ -183,9 +183,7 @@ class GenerationPool:
         self._active = np.zeros(self.capacity, bool)
         self._view = None
         eng._repack_generation()
-        self._dl = (C.c_int32 * eng.L)(*eng.dil)
-        relems = int(_lib.load().srwn_generate_ring_elems(self._dl, eng.L, eng.R))
-        self.ring = torch.zeros(relems * ((self.capacity + 31) // 32), dtype=eng.dt, device=eng.dev)
+        self.ring = eng._gen_ring(self.capacity)
         self.carry = torch.zeros((self.capacity, 2), dtype=torch.float32, device=eng.dev)
         self.slots = torch.zeros((self.capacity, 4), dtype=torch.int32, device=eng.dev)   # [t, t_end, seed lo, seed hi]
         self.C, self.mol = int(eng.C), bool(eng.mol)
@@ -311,14 +309,11 @@ class GenerationPool:
         st = torch.cuda.current_stream().cuda_stream
         if self.conditioned:
             LR, F = eng.L * eng.R, self.frames
-            cin = torch.zeros((n * F, eng.Ep), dtype=eng.dt, device=dev)
+            enc = torch.zeros((n, F, self.E), dtype=torch.float32, device=dev)      # (frames a stream lacks: zero rows)
             for i, c in enumerate(cond):
                 c = torch.as_tensor(c).to(device=dev, dtype=torch.float32)
-                cin[i * F:i * F + c.shape[0], :self.E].copy_(c)
-            rows = torch.empty((n * F, LR), dtype=eng.dt, device=dev)
-            K.pw_linear(cin.data_ptr(), eng.Ep, 0, eng.Ep, eng.Ep, eng.wptr(eng.o_wc), eng.view("BC").reshape(-1), rows,
-                        LR, LR, n * F)                                                        # model.py:180
-            self.cond_all.view(self.capacity, F, LR)[dst.long()] = rows.view(n, F, LR)
+                enc[i, :c.shape[0]].copy_(c)
+            self.cond_all.view(self.capacity, F, LR)[dst.long()] = eng._project_cond(enc.view(n * F, self.E)).view(n, F, LR)
         P = max(lens)
         xs, stride, T_src = None, 0, 0
         if P > 0:
@@ -338,7 +333,7 @@ class GenerationPool:
             view.forward(want_logits=False, with_loss=False, train=False, stack_only=True)
             xs, stride, T_src = view.xs.data_ptr(), view.B * view.T * eng.R, view.T
         _lib.call("srwn_generate_ring_fill_slots", xs, stride, T_src, n, dst.data_ptr(), plen.data_ptr(), self.clock,
-                  self._dl, eng.L, self.capacity, eng.R, self.ring.data_ptr(), K.abi_dtype(eng.dt), st)
+                  eng._gen_dilations(), eng.L, self.capacity, eng.R, self.ring.data_ptr(), K.abi_dtype(eng.dt), st)
         carry = np.zeros((n, 2), np.float32)
         for i, p in enumerate(ps):
             carry[i, :min(2, len(p))] = p[::-1][:2]
@@ -370,53 +365,17 @@ class GenerationPool:
         [capacity, nsteps, C] f32 or None, ran [capacity] int64 numpy).  Slot u's samples are row u's first ran[u]
         entries; the rest of every row stays zero.  `forced` [capacity, nsteps]: teacher forcing for this launch (every
         slot).  Slots whose stream reached its end become free."""
-        import os as _os
-        from . import _lib
         eng, nsteps = self.eng, int(nsteps)
         if nsteps < 0:
             raise ValueError("step: nsteps %d" % nsteps)
         if self.clock + nsteps > INT32_MAX:
             raise ValueError("step: the pool's clock %d + %d steps passes int32" % (self.clock, nsteps))
-        md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
-        B, dev = self.capacity, eng.dev
-        audio = torch.zeros((B, nsteps), dtype=torch.float32, device=dev)
-        codes = torch.zeros((B, nsteps), dtype=torch.int32, device=dev)
-        logits = torch.zeros((B, nsteps, eng.C), dtype=torch.float32, device=dev) if want_logits else None
-        fp = None
-        if forced is not None:
-            forced = torch.as_tensor(forced).to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(forced.shape) != (B, nsteps):
-                raise ValueError("forced must be [capacity, nsteps]")
-            fp = forced.data_ptr()
+        audio, codes, logits, forced = eng._gen_outputs(self.capacity, nsteps, want_logits, forced, "capacity")
         ran = np.clip(self._end - self._t, 0, nsteps)
         if nsteps == 0:
             return audio, codes, logits, ran
-        st = torch.cuda.current_stream().cuda_stream
-        v = eng.view
-        common = (v("BF").data_ptr(), v("BR").data_ptr(), eng.bs_sum.data_ptr(), v("head_b1").data_ptr(),
-                  v("head_b2").data_ptr(), v("init_w").data_ptr(), v("init_b").data_ptr(), self.ring.data_ptr(),
-                  audio.data_ptr(), codes.data_ptr(), None if logits is None else logits.data_ptr(), fp, self._dl, eng.L,
-                  B, nsteps, nsteps, eng.R, eng.S)
-        tail = (self.clock, self.carry.data_ptr(), self.slots.data_ptr())
-        g16 = eng.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
-        lat = (eng.wptr(eng.o_g16), eng.wptr(eng.o_g16_h1), eng.wptr(eng.o_g16_h2)) if g16 else None
-        thr = (eng.wptr(eng.o_gen), eng.wptr(eng.o_skip_gen), eng.wptr(eng.o_w1), eng.wptr(eng.o_w2))
-        sfx = ""
-        if self.sampling is not None:      # some join brought sampling controls: the twins that read the pool's array
-            sfx, tail = "_sampled", tail + (self.sampling.data_ptr(),)
-        if eng.mol:
-            cptr = None if self.cond_all is None else self.cond_all.data_ptr()
-            frames = self.frames if self.cond_all is not None else 1
-            if g16:
-                _lib.call("srwn_generate16_mol_slots" + sfx, *lat, *common, eng.C // 4, cptr, frames, self.pool_stride,
-                          eng.L * eng.R, md, st, *tail)
-            else:
-                _lib.call("srwn_generate_mol_slots" + sfx, *thr, *common, eng.Kw, eng.C // 4, cptr, frames,
-                          self.pool_stride, eng.L * eng.R, md, K.abi_dtype(eng.dt), st, *tail)
-        elif g16:
-            _lib.call("srwn_generate16_slots" + sfx, *lat, *common, eng.C, md, st, *tail)
-        else:
-            _lib.call("srwn_generate_slots" + sfx, *thr, *common, eng.C, eng.Kw, md, K.abi_dtype(eng.dt), st, *tail)
+        eng._launch_generation(self.ring, audio, codes, logits, forced, self.capacity, nsteps, mode, 0, self.clock,
+                               self.carry, self.sampling, self.cond_all, self.frames, self.slots)
         self._t += ran
         self.clock += nsteps
         self._active &= self._t < self._end
@@ -1586,6 +1545,101 @@ class WaveNetEngine:
         self.optimizer_step()
         return self.loss
 
+    # ------------------------------------------------------------------------------------------
+    # generation: what generate, generation_state / generate_chunk and the pools share
+    # ------------------------------------------------------------------------------------------
+    def _check_generates(self):
+        """What every way into generation refuses first (reads wavenet, o_gen and cfg.head_mode only)."""
+        if self.wavenet:
+            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
+                                      "the reference gate (canonical generation is not built)")
+        if self.o_gen is None or self.clip_head:
+            raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
+
+    def _refuse_conditioned_softmax(self, cond=None):
+        """The softmax teacher with conditioning channels, or handed an encoding (reads mol and E only)."""
+        if not self.mol and (self.E or cond is not None):
+            raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
+                                      "decoder of the reference has the mixture-of-logistics head)")
+
+    def _gen16(self) -> bool:
+        """Whether a launch runs the latency body (csrc/srwn_gen16.hip) rather than the throughput body (csrc/srwn_gen.hip):
+        where its images were built, unless SRWN_GEN16=0.  Read at every launch (the parity tests flip it on one engine)."""
+        return self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
+
+    def _gen_dilations(self):
+        """The dilations as the int32 array the generators' entry points take."""
+        return (ctypes.c_int32 * self.L)(*self.dil)
+
+    def _gen_ring(self, n: int) -> torch.Tensor:
+        """The zeroed layer rings of n streams (one set per group of 32)."""
+        from . import _lib
+        relems = int(_lib.load().srwn_generate_ring_elems(self._gen_dilations(), self.L, self.R))
+        return torch.zeros(relems * ((n + 31) // 32), dtype=self.dt, device=self.dev)
+
+    def _gen_outputs(self, rows: int, nsteps: int, want_logits: bool, forced, rows_name: str = "batch"):
+        """One launch's zeroed outputs -- audio [rows, nsteps] f32, codes [rows, nsteps] i32, logits [rows, nsteps, C] f32 or
+        None -- and `forced` as the [rows, nsteps] f32 device tensor the kernels read (None: free running)."""
+        audio = torch.zeros((rows, nsteps), dtype=torch.float32, device=self.dev)
+        codes = torch.zeros((rows, nsteps), dtype=torch.int32, device=self.dev)
+        logits = torch.zeros((rows, nsteps, self.C), dtype=torch.float32, device=self.dev) if want_logits else None
+        if forced is not None:
+            forced = torch.as_tensor(forced).to(device=self.dev, dtype=torch.float32).contiguous()
+            if tuple(forced.shape) != (rows, nsteps):
+                raise ValueError("forced must be [%s, nsteps]" % rows_name)
+        return audio, codes, logits, forced
+
+    def _project_cond(self, enc: torch.Tensor) -> torch.Tensor:
+        """Encoding rows [rows, cond_channels] -> the conditioning biases of every layer [rows, L*R] (model.py:180): the
+        rows padded to the Ep columns of the packed kernel, one pw_linear."""
+        rows, LR = enc.shape[0], self.L * self.R
+        cin = torch.zeros((rows, self.Ep), dtype=self.dt, device=self.dev)
+        cin[:, :self.E].copy_(enc)
+        out = torch.empty((rows, LR), dtype=self.dt, device=self.dev)
+        K.pw_linear(cin.data_ptr(), self.Ep, 0, self.Ep, self.Ep, self.wptr(self.o_wc), self.view("BC").reshape(-1), out,
+                    LR, LR, rows)
+        return out
+
+    # the general forms of the C ABI, [latency body][mixture-of-logistics head][slot form]: with t0 = 0, a NULL carry and
+    # NULL sampling they run the kernels of the plain calls, so every launch goes through one of these eight
+    _GEN_ENTRY = ((("srwn_generate_resume_sampled", "srwn_generate_slots_sampled"),
+                   ("srwn_generate_mol_resume_sampled", "srwn_generate_mol_slots_sampled")),
+                  (("srwn_generate16_resume_sampled", "srwn_generate16_slots_sampled"),
+                   ("srwn_generate16_mol_resume_sampled", "srwn_generate16_mol_slots_sampled")))
+
+    def _launch_generation(self, ring, audio, codes, logits, forced, batch, nsteps, mode, seed, t0, carry, sampling,
+                           cond_all, frames, slots=None):
+        """THE launch of the queue-cached generators: `nsteps` steps from absolute step t0 for `batch` streams over `ring`
+        into audio / codes / logits (None: not kept), teacher-forced where `forced` is given.  carry [batch, 2] (None with
+        t0 = 0: none read, none written), sampling: the SrwnGenSampling device array or None, cond_all [batch * frames,
+        L*R] or None.  `slots` (a pool's SrwnGenSlot table) selects the slot form: t0 is then the pool's clock and the
+        seeds are the slots'.  The argument list is srwn.h's, built once from its blocks."""
+        from . import _lib
+        ptr = lambda t: None if t is None else t.data_ptr()
+        v, g16 = self.view, self._gen16()
+        if g16:
+            weights = (self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2))
+        else:
+            weights = (self.wptr(self.o_gen), self.wptr(self.o_skip_gen), self.wptr(self.o_w1), self.wptr(self.o_w2))
+        shared = (v("BF").data_ptr(), v("BR").data_ptr(), self.bs_sum.data_ptr(), v("head_b1").data_ptr(),
+                  v("head_b2").data_ptr(), v("init_w").data_ptr(), v("init_b").data_ptr(), ring.data_ptr(),
+                  audio.data_ptr(), codes.data_ptr(), ptr(logits), ptr(forced), self._gen_dilations(), self.L, batch,
+                  nsteps, nsteps, self.R, self.S)
+        # the throughput body alone takes the filter width (after C, before num_mixtures) and the dtype (before the stream)
+        kw, dtype = ((), ()) if g16 else ((self.Kw,), (K.abi_dtype(self.dt),))
+        if self.mol:
+            head = kw + (self.C // 4, ptr(cond_all), frames if cond_all is not None else 1, self.cfg.pool_stride,
+                         self.L * self.R)
+        else:
+            head = (self.C,) + kw
+        md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
+        st = torch.cuda.current_stream().cuda_stream
+        if slots is None:
+            tail = (md, int(seed)) + dtype + (st, t0, ptr(carry))
+        else:
+            tail = (md,) + dtype + (st, t0, carry.data_ptr(), slots.data_ptr())
+        _lib.call(self._GEN_ENTRY[g16][bool(self.mol)][slots is not None], *weights, *shared, *head, *tail, ptr(sampling))
+
     def generate(self, nsteps: int, mode: str = "sample", seed: int = 0, forced: Optional[torch.Tensor] = None,
                  want_logits: bool = False, batch: Optional[int] = None, cond: Optional[torch.Tensor] = None, *,
                  temperature=1.0, top_k=0, top_p=1.0):
@@ -1595,93 +1649,29 @@ class WaveNetEngine:
         Softmax teacher: returns (audio [B,nsteps] f32, mu-law codes [B,nsteps] i32, logits [B,nsteps,C] f32 or None).
         Mixture-of-logistics decoder (head_mode "mol"; `cond` = encoding_w_condition [B, frames, cond_channels] when the
         stack is conditioned): returns (audio, selected mixture, logits [B,nsteps,4M])."""
-        import ctypes as C
-        from . import _lib
-        if self.wavenet:
-            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
-                                      "the reference gate (canonical generation is not built)")
-        if self.o_gen is None or self.clip_head:
-            raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
+        self._check_generates()
         B = int(batch or self.B)
         samp = None
         if self.mol or not (self.E or cond is not None):      # (the conditioned softmax teacher is refused below)
             samp = sampling_table(B, temperature, top_k, top_p, self.C, self.mol, "generate")
         self._repack_generation()      # (the generation-only images follow the parameters lazily: not part of a training step)
-        dl = (C.c_int32 * self.L)(*self.dil)
-        relems = int(_lib.load().srwn_generate_ring_elems(dl, self.L, self.R))
-        ring = torch.zeros(relems * ((B + 31) // 32), dtype=self.dt, device=self.dev)
-        audio = torch.zeros((B, nsteps), dtype=torch.float32, device=self.dev)
-        codes = torch.zeros((B, nsteps), dtype=torch.int32, device=self.dev)
-        logits = torch.zeros((B, nsteps, self.C), dtype=torch.float32, device=self.dev) if want_logits else None
-        fp = None
-        if forced is not None:
-            forced = forced.to(device=self.dev, dtype=torch.float32).contiguous()
-            if tuple(forced.shape) != (B, nsteps):
-                raise ValueError("forced must be [batch, nsteps]")
-            fp = forced.data_ptr()
-        v = self.view
-        common = (self.wptr(self.o_gen), self.wptr(self.o_skip_gen), self.wptr(self.o_w1), self.wptr(self.o_w2),
-                  v("BF").data_ptr(), v("BR").data_ptr(), self.bs_sum.data_ptr(), v("head_b1").data_ptr(),
-                  v("head_b2").data_ptr(), v("init_w").data_ptr(), v("init_b").data_ptr(), ring.data_ptr(),
-                  audio.data_ptr(), codes.data_ptr(), None if logits is None else logits.data_ptr(), fp, dl, self.L, B,
-                  nsteps, nsteps, self.R, self.S)
-        md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
-        st = torch.cuda.current_stream().cuda_stream
-        # with controls: the *_resume_sampled twins from step 0 (the one-shot calls are those with t0 = 0, no carry, NULL)
-        sdev = None if samp is None else _sampling_to_device(samp, self.dev)
-        if self.mol:
-            cond_all, frames = None, 1
-            if self.E:
-                if cond is None:
-                    raise ValueError("this decoder is conditioned: pass cond [batch, frames, cond_channels]")
-                cond = cond.to(device=self.dev, dtype=torch.float32)
-                frames = cond.shape[1]
-                if tuple(cond.shape) != (B, frames, self.E) or frames * self.cfg.pool_stride < nsteps:
-                    raise ValueError("cond must be [batch, frames >= nsteps/pool_stride, %d]" % self.E)
-                cin = torch.zeros((B * frames, self.Ep), dtype=self.dt, device=self.dev)
-                cin[:, :self.E].copy_(cond.reshape(B * frames, self.E))
-                cond_all = torch.empty((B * frames, self.L * self.R), dtype=self.dt, device=self.dev)
-                K.pw_linear(cin.data_ptr(), self.Ep, 0, self.Ep, self.Ep, self.wptr(self.o_wc), v("BC").reshape(-1),
-                            cond_all, self.L * self.R, self.L * self.R, B * frames)          # model.py:180
-            elif cond is not None:
-                raise ValueError("this decoder is not conditioned")
-            import os as _os
-            g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
-            cptr = None if cond_all is None else cond_all.data_ptr()
-            if sdev is not None and g16:
-                _lib.call("srwn_generate16_mol_resume_sampled", self.wptr(self.o_g16), self.wptr(self.o_g16_h1),
-                          self.wptr(self.o_g16_h2), *common[4:21], self.R, self.S, self.C // 4, cptr, frames,
-                          self.cfg.pool_stride, self.L * self.R, md, int(seed), st, 0, None, sdev.data_ptr())
-            elif sdev is not None:
-                _lib.call("srwn_generate_mol_resume_sampled", *common, self.Kw, self.C // 4, cptr, frames,
-                          self.cfg.pool_stride, self.L * self.R, md, int(seed), K.abi_dtype(self.dt), st, 0, None,
-                          sdev.data_ptr())
-            elif g16:
-                _lib.call("srwn_generate16_mol", self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2),
-                          *common[4:21], self.R, self.S, self.C // 4, None if cond_all is None else cond_all.data_ptr(), frames,
-                          self.cfg.pool_stride, self.L * self.R, md, int(seed), st)
-            else:
-                _lib.call("srwn_generate_mol", *common, self.Kw, self.C // 4,
-                          None if cond_all is None else cond_all.data_ptr(), frames, self.cfg.pool_stride, self.L * self.R,
-                          md, int(seed), K.abi_dtype(self.dt), st)
-        else:
-            if self.E or cond is not None:
-                raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
-                                          "decoder of the reference has the mixture-of-logistics head)")
-            import os as _os
-            g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
-            if sdev is not None and g16:
-                _lib.call("srwn_generate16_resume_sampled", self.wptr(self.o_g16), self.wptr(self.o_g16_h1),
-                          self.wptr(self.o_g16_h2), *common[4:21], self.R, self.S, self.C, md, int(seed), st, 0, None,
-                          sdev.data_ptr())
-            elif sdev is not None:
-                _lib.call("srwn_generate_resume_sampled", *common, self.C, self.Kw, md, int(seed), K.abi_dtype(self.dt), st,
-                          0, None, sdev.data_ptr())
-            elif g16:
-                _lib.call("srwn_generate16", self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2),
-                          *common[4:21], self.R, self.S, self.C, md, int(seed), st)
-            else:
-                _lib.call("srwn_generate", *common, self.C, self.Kw, md, int(seed), K.abi_dtype(self.dt), st)
+        ring = self._gen_ring(B)
+        audio, codes, logits, forced = self._gen_outputs(B, nsteps, want_logits, forced)
+        self._refuse_conditioned_softmax(cond)
+        cond_all, frames = None, 1
+        if self.E:
+            if cond is None:
+                raise ValueError("this decoder is conditioned: pass cond [batch, frames, cond_channels]")
+            cond = cond.to(device=self.dev, dtype=torch.float32)
+            frames = cond.shape[1]
+            if tuple(cond.shape) != (B, frames, self.E) or frames * self.cfg.pool_stride < nsteps:
+                raise ValueError("cond must be [batch, frames >= nsteps/pool_stride, %d]" % self.E)
+            cond_all = self._project_cond(cond.reshape(B * frames, self.E))
+        elif cond is not None:
+            raise ValueError("this decoder is not conditioned")
+        # one launch from step 0: no carry to read (t0 = 0) and none written (NULL); the state of a run is generation_state's
+        self._launch_generation(ring, audio, codes, logits, forced, B, nsteps, mode, seed, 0, None,
+                                None if samp is None else _sampling_to_device(samp, self.dev), cond_all, frames)
         return audio, codes, logits
 
     # ------------------------------------------------------------------------------------------
@@ -1695,42 +1685,27 @@ class WaveNetEngine:
         temperature / top_k / top_p: the run's sampling controls (as `generate`), kept in the state for every chunk.
         The generation weight images are gathered here: train between chunks and the run keeps the weights it started
         with (make a new state to pick up new ones)."""
-        import ctypes as C
-        from . import _lib
-        if self.wavenet:
-            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
-                                      "the reference gate (canonical generation is not built)")
-        if self.o_gen is None or self.clip_head:
-            raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
+        self._check_generates()
         B = int(batch)
         if B < 1:
             raise ValueError("generation_state: batch %d" % B)
         samp = None
         if self.mol or not (self.E or cond is not None):      # (the conditioned softmax teacher is refused below)
             samp = sampling_table(B, temperature, top_k, top_p, self.C, self.mol, "generation_state")
+        self._refuse_conditioned_softmax(cond)
         cond_all, frames = None, 0
-        if self.mol and self.E:
+        if self.E:
             if cond is None:
                 raise ValueError("this decoder is conditioned: pass cond [batch, frames, cond_channels]")
             cond = cond.to(device=self.dev, dtype=torch.float32).contiguous()
             frames = int(cond.shape[1]) if cond.dim() == 3 else 0
             if cond.dim() != 3 or tuple(cond.shape) != (B, frames, self.E) or frames < 1:
                 raise ValueError("cond must be [batch, frames, %d]" % self.E)
-            cin = torch.zeros((B * frames, self.Ep), dtype=self.dt, device=self.dev)
-            cin[:, :self.E].copy_(cond.reshape(B * frames, self.E))
-            cond_all = torch.empty((B * frames, self.L * self.R), dtype=self.dt, device=self.dev)
-            K.pw_linear(cin.data_ptr(), self.Ep, 0, self.Ep, self.Ep, self.wptr(self.o_wc), self.view("BC").reshape(-1),
-                        cond_all, self.L * self.R, self.L * self.R, B * frames)          # model.py:180
-        elif self.mol:
-            if cond is not None:
-                raise ValueError("this decoder is not conditioned")
-        elif self.E or cond is not None:
-            raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
-                                      "decoder of the reference has the mixture-of-logistics head)")
+            cond_all = self._project_cond(cond.reshape(B * frames, self.E))
+        elif cond is not None:
+            raise ValueError("this decoder is not conditioned")
         self._repack_generation()
-        dl = (C.c_int32 * self.L)(*self.dil)
-        relems = int(_lib.load().srwn_generate_ring_elems(dl, self.L, self.R))
-        ring = torch.zeros(relems * ((B + 31) // 32), dtype=self.dt, device=self.dev)
+        ring = self._gen_ring(B)
         carry = torch.zeros((B, 2), dtype=torch.float32, device=self.dev)
         return GenerationState(B, ring, carry, int(seed), cond if frames else None, cond_all, frames,
                                frames * self.cfg.pool_stride if frames else None,
@@ -1740,14 +1715,8 @@ class WaveNetEngine:
         """A pool of `capacity` generation slots that streams join and leave while it runs (GenerationPool); `frames` = the
         most conditioning frames a stream of a conditioned decoder brings.  Refuses, before any device work, what
         `generate` refuses.  The generation weight images are gathered here: the pool keeps the weights it started with."""
-        if self.wavenet:
-            raise NotImplementedError("generate: gate_mode 'wavenet' is trained only; the generation kernels implement "
-                                      "the reference gate (canonical generation is not built)")
-        if self.o_gen is None or self.clip_head:
-            raise NotImplementedError("generate: built for R=64 or 32, S=256 or 128, K=2 stacks with a per-time-step head")
-        if not self.mol and self.E:
-            raise NotImplementedError("generate: the conditioned softmax teacher is not built (the conditioned "
-                                      "decoder of the reference has the mixture-of-logistics head)")
+        self._check_generates()
+        self._refuse_conditioned_softmax()
         if int(capacity) < 1:
             raise ValueError("generation_pool: capacity %d" % int(capacity))
         if self.mol and self.E:
@@ -1771,7 +1740,6 @@ class WaveNetEngine:
         (rounded up to a whole conditioning frame; the causal convs keep the padding out of every x_l[t < P]), its stored
         layer inputs into the rings (srwn_generate_ring_fill), the carry from the prompt's last two samples, t = P.  The
         next chunk's first sample is the one after the prompt."""
-        import ctypes as C
         from . import _lib
         prompt = torch.as_tensor(prompt).to(device=self.dev, dtype=torch.float32)
         if prompt.dim() != 2 or prompt.shape[0] != state.batch:
@@ -1790,9 +1758,8 @@ class WaveNetEngine:
         audio[:, :P].copy_(prompt)
         view.set_inputs(audio, None, state.cond[:, :P_pad // pool] if self.E else None)
         view.forward(want_logits=False, with_loss=False, train=False, stack_only=True)
-        dl = (C.c_int32 * self.L)(*self.dil)
-        _lib.call("srwn_generate_ring_fill", view.xs.data_ptr(), B * P_pad * self.R, P_pad, P, dl, self.L, B, self.R,
-                  state.ring.data_ptr(), K.abi_dtype(self.dt), torch.cuda.current_stream().cuda_stream)
+        _lib.call("srwn_generate_ring_fill", view.xs.data_ptr(), B * P_pad * self.R, P_pad, P, self._gen_dilations(), self.L,
+                  B, self.R, state.ring.data_ptr(), K.abi_dtype(self.dt), torch.cuda.current_stream().cuda_stream)
         state.carry[:, 0].copy_(prompt[:, P - 1])
         if P >= 2:
             state.carry[:, 1].copy_(prompt[:, P - 2])
@@ -1804,56 +1771,17 @@ class WaveNetEngine:
         same outputs): (audio [B, nsteps] f32, codes [B, nsteps] i32, logits [B, nsteps, C] f32 or None); advances
         state.t.  Chunks of any lengths give the bits of one `generate` call over their sum.  `forced` [B, nsteps]:
         teacher forcing for this chunk only."""
-        import ctypes as C
-        import os as _os
-        from . import _lib
         B, nsteps = state.batch, int(nsteps)
         if nsteps < 0:
             raise ValueError("generate_chunk: nsteps %d" % nsteps)
         if state.limit is not None and state.t + nsteps > state.limit:
             raise ValueError("generate_chunk: steps %d..%d run past the encoding's frames * pool_stride = %d"
                              % (state.t, state.t + nsteps, state.limit))
-        audio = torch.zeros((B, nsteps), dtype=torch.float32, device=self.dev)
-        codes = torch.zeros((B, nsteps), dtype=torch.int32, device=self.dev)
-        logits = torch.zeros((B, nsteps, self.C), dtype=torch.float32, device=self.dev) if want_logits else None
-        fp = None
-        if forced is not None:
-            forced = torch.as_tensor(forced).to(device=self.dev, dtype=torch.float32).contiguous()
-            if tuple(forced.shape) != (B, nsteps):
-                raise ValueError("forced must be [batch, nsteps]")
-            fp = forced.data_ptr()
+        audio, codes, logits, forced = self._gen_outputs(B, nsteps, want_logits, forced)
         if nsteps == 0:
             return audio, codes, logits
-        md = {"argmax": 0, "mean": 0, "sample": 1}[mode]
-        st = torch.cuda.current_stream().cuda_stream
-        dl = (C.c_int32 * self.L)(*self.dil)
-        v = self.view
-        common = (v("BF").data_ptr(), v("BR").data_ptr(), self.bs_sum.data_ptr(), v("head_b1").data_ptr(),
-                  v("head_b2").data_ptr(), v("init_w").data_ptr(), v("init_b").data_ptr(), state.ring.data_ptr(),
-                  audio.data_ptr(), codes.data_ptr(), None if logits is None else logits.data_ptr(), fp, dl, self.L, B,
-                  nsteps, nsteps, self.R, self.S)
-        thr = (self.wptr(self.o_gen), self.wptr(self.o_skip_gen), self.wptr(self.o_w1), self.wptr(self.o_w2))
-        resume = (state.t, state.carry.data_ptr())
-        sfx = ""
-        if state.sampling is not None:      # the run has sampling controls: the twins that read its array
-            sfx, resume = "_sampled", resume + (state.sampling.data_ptr(),)
-        g16 = self.o_g16 is not None and _os.environ.get("SRWN_GEN16", "1") != "0"
-        if g16:
-            lat = (self.wptr(self.o_g16), self.wptr(self.o_g16_h1), self.wptr(self.o_g16_h2))
-        if self.mol:
-            cptr = None if state.cond_all is None else state.cond_all.data_ptr()
-            frames = state.frames if state.cond_all is not None else 1
-            if g16:
-                _lib.call("srwn_generate16_mol_resume" + sfx, *lat, *common, self.C // 4, cptr, frames, self.cfg.pool_stride,
-                          self.L * self.R, md, int(state.seed), st, *resume)
-            else:
-                _lib.call("srwn_generate_mol_resume" + sfx, *thr, *common, self.Kw, self.C // 4, cptr, frames,
-                          self.cfg.pool_stride, self.L * self.R, md, int(state.seed), K.abi_dtype(self.dt), st, *resume)
-        elif g16:
-            _lib.call("srwn_generate16_resume" + sfx, *lat, *common, self.C, md, int(state.seed), st, *resume)
-        else:
-            _lib.call("srwn_generate_resume" + sfx, *thr, *common, self.C, self.Kw, md, int(state.seed), K.abi_dtype(self.dt),
-                      st, *resume)
+        self._launch_generation(state.ring, audio, codes, logits, forced, B, nsteps, mode, state.seed, state.t, state.carry,
+                                state.sampling, state.cond_all, state.frames)
         state.t += nsteps
         return audio, codes, logits
 
