@@ -774,8 +774,9 @@ int srwn_clamp_bwd(const float* x, const float* dy, float* dx, int64_t n, float 
  * layer group (srwn_group_plan), a boundary buffer [B][hist + max_chunk][R] (dtype) whose first hist = sum of the group's
  * dilations rows hold the group's input rows of times [t0 - hist, t0) (zeros at the start) and whose next n rows hold
  * the chunk.  A tap or a conditioning frame is taken by absolute time: a tap at t < 0 is the conv's zero padding at every
- * layer (ops.py:9), the frame of time t is clamp(t / pool_stride, 0, cond_frames - 1).  Every stored value has the bits
- * the whole-clip entry points give it.  Argument errors return SRWN_E_* before anything is launched: a null pointer
+ * layer (ops.py:9), the frame of time t is max(t, 0) / pool_stride, kept in row frame mod cond_frames of the table (a
+ * ring, see 110 below; the identity while frame < cond_frames).  Every stored value has the bits the whole-clip entry
+ * points give it.  Argument errors return SRWN_E_* before anything is launched: a null pointer
  * (-3), n < 1 or n > max_chunk or buffers too short (-2), R other than 32 / 64, K other than 2 or a group whose halo
  * (sum of dilations / their gcd) exceeds 31 (-4), an unknown dtype (-1).
  *
@@ -840,8 +841,8 @@ int srwn_logistic_from_bits(const uint32_t* bits, float* out, int64_t n, void* s
  *   srwn_flow_stream_in_slots            rows [hist, hist + ran(u)) of slot u, frame of time slots[u].t + row.
  *   srwn_residual_group_fwd_stream_slots buffer row 0 of slot u sits at time slots[u].t - hist.
  *   srwn_flow_stream_out_slots           x_out[u, j] for j < ran(u), +0 for ran(u) <= j < n (free slots: a row of zeros);
- *                                        the carry and the history roll of the slots with ran > 0; with advance != 0 (the
- *                                        last flow) slots[u].t += n for the live slots, by the workgroup that finishes
+ *                                        the carry and the history roll (by ran(u) rows) of the slots with ran > 0; with advance != 0 (the
+ *                                        last flow) slots[u].t += ran(u) for the live slots, by the workgroup that finishes
  *                                        last (`arrive`: one device int32, zero before the first launch and zero again
  *                                        after every launch that completes; a caller re-zeroes it after a failed
  *                                        one), since every workgroup of the launch reads the table.
@@ -876,6 +877,41 @@ int srwn_flow_stream_out_slots(const void* h, int64_t top_clip_rows, const float
 int srwn_flow_stream_reset_slots(const int64_t* roll_table, int32_t nroll, float* carry, int32_t ncarry,
                                  int64_t carry_stride, const int32_t* slot_ids, int32_t nslots, int32_t capacity,
                                  int32_t R, int32_t dtype, void* stream);
+
+/* ---- live synthesis (since srwn_version() 110): the conditioning tables of the four stream launches above (and of their
+ * slot forms) are RINGS.  A table holds cond_frames rows per stream; frame q of a stream (q = time / pool_stride, 0 for a
+ * time before the start) is looked up in row q mod cond_frames.  A caller that writes a stream's whole encoding once
+ * (frames < cond_frames, as every caller before 110 does) sees the identity, and those entry points keep their
+ * signatures and their bits.  A caller that keeps FEEDING a running stream writes frame q to row q mod cond_frames
+ * while the stream runs, and may do so as long as no frame a later launch still reads is overwritten: a chunk starting
+ * at time t recomputes the halo rows of a group back to t - hist, so with hist_max the largest history of the flow's
+ * groups the oldest frame still read is max(t - hist_max, 0) / pool_stride, and after `fed` frames the ring has room for
+ *     max(0, cond_frames - fed + max(t - hist_max, 0) / pool_stride)
+ * more.  A launch then never spans cond_frames frames: the group kernel reduces the first frame of a segment modulo
+ * cond_frames once, on the scalar side, and wraps a row with one compare and subtract (no 64-bit division per tile).
+ * Rows a tile computes but never stores (padding rows, rows of idle slots) may read any row of the ring; the lookup
+ * stays inside the table for them.
+ *
+ *   srwn_cond_ring_feed   for ONE flow: projects the new frames of n streams through the packed conditioning image of all
+ *                         L layers (wpack: the image srwn_pw_linear_ychunks takes, Cin = the padded encoding width, a
+ *                         multiple of 16; bias [L*R] fp32) and writes them into the ring table [L][capacity *
+ *                         cond_frames][R] (dtype).  Entry i < n names stream streams[i] (int32, distinct), its first
+ *                         new frame first_frame[i] (int64, absolute) and counts[i] (int32) frames, all DEVICE arrays;
+ *                         frame j of the entry is read from row streams[i] * x_stream_rows + j of x (rows of
+ *                         x_row_stride elements, dtype) and written to row streams[i] * cond_frames + (first_frame[i] +
+ *                         j) mod cond_frames of every layer.  One launch however many streams are fed.  The rows it
+ *                         writes have the bits srwn_pw_linear_ychunks writes for the same frame, image and dtype (one
+ *                         device body serves both).  max_k bounds the counts (the grid is sized by it; a larger count is
+ *                         cut at max_k).  Errors before any launch: a null pointer (-3); cond_frames < 1, max_k >
+ *                         cond_frames (more frames at once than the ring holds), n > capacity (more streams than the table
+ *                         holds), x_stream_rows < max_k, Cin not a multiple of 16 (-2); R other than 32 / 64 (-4); an
+ *                         unknown dtype (-1).  The device arrays cannot be read before the launch: an entry whose stream
+ *                         lies outside [0, capacity) or whose first frame is negative is skipped by the kernel, as
+ *                         srwn_flow_stream_reset_slots skips such ids.  n = 0 or max_k = 0: nothing to do (0). */
+int srwn_cond_ring_feed(const void* x, int64_t x_row_stride, int64_t x_stream_rows, int32_t Cin, const void* wpack,
+                        const float* bias, void* table, int32_t L, int32_t R, int32_t cond_frames, int32_t capacity,
+                        const int32_t* streams, const int64_t* first_frame, const int32_t* counts, int32_t n,
+                        int32_t max_k, int32_t dtype, void* stream);
 
 /* ---- data gradient of _DilatedCausalConv1d (ops.py:6-10) wrt a narrow input (the 1-channel flow input,
  * model.py:423-424); `shift` is the adjoint of RightShift (ops.py:78-80):

@@ -200,6 +200,9 @@ SIGNATURES = {
     "srwn_flow_stream_out_slots": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32,
                                              _i32, _p, _p, _i32, _p]),
     "srwn_flow_stream_reset_slots": (C.c_int, [_p, _i32, _p, _i32, _i64, _p, _i32, _i32, _i32, _i32, _p]),
+    # live synthesis (srwn_version() 110): new frames of running streams into the ring conditioning table of one flow
+    "srwn_cond_ring_feed": (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _i32,
+                                      _i32, _p]),
     "srwn_causal_conv1d_dgrad": (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i32, _p]),
     "srwn_stft_frames": (_i32, [_i32]),
     "srwn_stft_power": (C.c_int, [_p, _p, _p, _p, _i32, _i32, _p]),

@@ -367,13 +367,14 @@ __device__ __forceinline__ Frag<T> pw_load_b(const PwArgs& a, int64_t row, bool 
   return f;
 }
 
+// One wave's tile of the product: MT row tiles of the image (block `mb` of them) x NT column tiles of 32 rows.  Column
+// tile nt reads x row rowx[nt] and writes y row rowy[nt] (pw_linear_kernel: the same row; cond_ring_feed_kernel: a frame
+// of the staging buffer -> its row of the ring).  An output's value is bias + the MFMAs of k-steps ks_lo.. in order,
+// whatever MT, NT and the tile it falls in: both kernels give a row the same bits.
 template <typename T, int MT, int NT, int PRO, int EPI>
-__global__ __launch_bounds__(256) void pw_linear_kernel(PwArgs a) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 31, half = lane >> 5;
-  const int64_t row_wave = ((int64_t)blockIdx.x * 4 + wave) * (32 * NT);
-  if (row_wave >= a.rows) return;
-  const int mb = blockIdx.y;  // block of MT row tiles
+__device__ __forceinline__ void pw_tile(const PwArgs& a, int mb, const int64_t (&rowx)[NT], const int64_t (&rowy)[NT],
+                                        const bool (&valid)[NT], int lane) {
+  const int half = lane >> 5;
   const Frag<T>* wp = reinterpret_cast<const Frag<T>*>(a.wpack) + (size_t)mb * MT * a.ks_total * 64 + lane;
   const int ks_lo = blockIdx.z * a.ks_per_split;
   const int ks_hi = (ks_lo + a.ks_per_split < a.ks_total) ? ks_lo + a.ks_per_split : a.ks_total;
@@ -389,18 +390,10 @@ __global__ __launch_bounds__(256) void pw_linear_kernel(PwArgs a) {
       for (int nt = 0; nt < NT; ++nt) acc[mt][nt][q] = bv;
     }
 
-  int64_t rowc[NT];
-  bool valid[NT];
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    rowc[nt] = row_wave + 32 * nt + col;
-    valid[nt] = rowc[nt] < a.rows;
-  }
-
   for (int ks = ks_lo; ks < ks_hi; ++ks) {
     Frag<T> bf[NT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) bf[nt] = pw_load_b<T, PRO>(a, rowc[nt], valid[nt], ks, half);
+    for (int nt = 0; nt < NT; ++nt) bf[nt] = pw_load_b<T, PRO>(a, rowx[nt], valid[nt], ks, half);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
       const Frag<T> af = wp[((size_t)mt * a.ks_total + ks) * 64];
@@ -412,8 +405,8 @@ __global__ __launch_bounds__(256) void pw_linear_kernel(PwArgs a) {
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     if (!valid[nt]) continue;
-    T* yrow = reinterpret_cast<T*>(a.y) + rowc[nt] * a.y_row_stride;
-    const T* arow = (EPI == SRWN_EPI_MASK) ? reinterpret_cast<const T*>(a.aux) + rowc[nt] * a.aux_row_stride : nullptr;
+    T* yrow = reinterpret_cast<T*>(a.y) + rowy[nt] * a.y_row_stride;
+    const T* arow = (EPI == SRWN_EPI_MASK) ? reinterpret_cast<const T*>(a.aux) + rowy[nt] * a.aux_row_stride : nullptr;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
 #pragma unroll
@@ -432,7 +425,7 @@ __global__ __launch_bounds__(256) void pw_linear_kernel(PwArgs a) {
           for (int e = 0; e < 4; ++e) v[e] = (m[e] > 0.0f) ? v[e] : 0.0f;
         }
         if (EPI == SRWN_EPI_F32)
-          store4(reinterpret_cast<float*>(a.y) + (int64_t)blockIdx.z * a.y_split_stride + rowc[nt] * a.y_row_stride + n0,
+          store4(reinterpret_cast<float*>(a.y) + (int64_t)blockIdx.z * a.y_split_stride + rowy[nt] * a.y_row_stride + n0,
                  v[0], v[1], v[2], v[3]);
         else if (a.y_chunk_len > 0)
           store4(yrow + (int64_t)(n0 / a.y_chunk_len) * a.y_chunk_stride + n0 % a.y_chunk_len, v[0], v[1], v[2], v[3]);
@@ -440,6 +433,100 @@ __global__ __launch_bounds__(256) void pw_linear_kernel(PwArgs a) {
       }
     }
   }
+}
+
+template <typename T, int MT, int NT, int PRO, int EPI>
+__global__ __launch_bounds__(256) void pw_linear_kernel(PwArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 31;
+  const int64_t row_wave = ((int64_t)blockIdx.x * 4 + wave) * (32 * NT);
+  if (row_wave >= a.rows) return;
+  int64_t rowc[NT];
+  bool valid[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    rowc[nt] = row_wave + 32 * nt + col;
+    valid[nt] = rowc[nt] < a.rows;
+  }
+  pw_tile<T, MT, NT, PRO, EPI>(a, blockIdx.y, rowc, rowc, valid, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// srwn_cond_ring_feed: the conditioning product of srwn_pw_linear_ychunks (pw_tile, one row tile per wave) for the new
+// frames of n streams of a ring table.  Virtual row v = entry * max_k + j: frame j of entry `entry`, read from row
+// stream * x_stream_rows + j of the staging buffer, written to ring row stream * cond_frames + (first + j) mod cond_frames
+// of every layer.  Entries with a stream outside the table or first < 0 are skipped, counts are cut at max_k.
+// ------------------------------------------------------------------------------------------
+struct RingArgs {
+  PwArgs p;
+  const int32_t* streams; const int64_t* first; const int32_t* counts;
+  int n, max_k, cond_frames, capacity; int64_t x_stream_rows;
+};
+
+template <typename T, int NT>
+__global__ __launch_bounds__(256) void cond_ring_feed_kernel(RingArgs r) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 31;
+  const int64_t total = (int64_t)r.n * r.max_k;
+  const int64_t row_wave = ((int64_t)blockIdx.x * 4 + wave) * (32 * NT);
+  if (row_wave >= total) return;
+  int64_t rowx[NT], rowy[NT];
+  bool valid[NT];
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int64_t v = row_wave + 32 * nt + col;
+    rowx[nt] = 0; rowy[nt] = 0; valid[nt] = false;
+    if (v < total) {
+      const int e = (int)(v / r.max_k), j = (int)(v - (int64_t)e * r.max_k);
+      const int u = r.streams[e];
+      const long long f0 = r.first[e];
+      const int k = r.counts[e] < r.max_k ? r.counts[e] : r.max_k;
+      if (u >= 0 && u < r.capacity && f0 >= 0 && j < k) {
+        int slot = (int)(f0 % r.cond_frames) + j;        // j < max_k <= cond_frames: one wrap
+        slot = slot < r.cond_frames ? slot : slot - r.cond_frames;
+        rowx[nt] = (int64_t)u * r.x_stream_rows + j;
+        rowy[nt] = (int64_t)u * r.cond_frames + slot;
+        valid[nt] = true;
+      }
+    }
+  }
+  pw_tile<T, 1, NT, SRWN_PRO_NONE, SRWN_EPI_NONE>(r.p, blockIdx.y, rowx, rowy, valid, lane);
+}
+
+extern "C" int srwn_cond_ring_feed(const void* x, int64_t x_row_stride, int64_t x_stream_rows, int32_t Cin,
+                                   const void* wpack, const float* bias, void* table, int32_t L, int32_t R,
+                                   int32_t cond_frames, int32_t capacity, const int32_t* streams,
+                                   const int64_t* first_frame, const int32_t* counts, int32_t n, int32_t max_k,
+                                   int32_t dtype, void* stream) {
+  if (!x || !wpack || !bias || !table || !streams || !first_frame || !counts)
+    return set_error(SRWN_E_NULL, "cond_ring_feed: null pointer");
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "cond_ring_feed: dilation_channels %d (built: 32, 64)", R);
+  if (cond_frames < 1) return set_error(SRWN_E_SHAPE, "cond_ring_feed: a ring of %d frames", cond_frames);
+  if (max_k > cond_frames)
+    return set_error(SRWN_E_SHAPE, "cond_ring_feed: %d frames fed at once into a ring of %d", max_k, cond_frames);
+  if (capacity < 1 || n < 0 || n > capacity)
+    return set_error(SRWN_E_SHAPE, "cond_ring_feed: %d streams named, the table holds %d", n, capacity);
+  if (L < 1 || max_k < 0 || Cin < 16 || Cin % 16 || x_row_stride < Cin || x_row_stride % 8 || x_stream_rows < max_k ||
+      (int64_t)capacity * cond_frames > 0x7fffffffLL)
+    return set_error(SRWN_E_SHAPE, "cond_ring_feed: L=%d max_k=%d Cin=%d x strides %lld / %lld", L, max_k, Cin,
+                     (long long)x_row_stride, (long long)x_stream_rows);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "cond_ring_feed: dtype %d", dtype);
+  if (n == 0 || max_k == 0) return 0;
+  RingArgs r{};
+  r.p = PwArgs{x, x_row_stride, 0, Cin, Cin / 16, wpack, bias, table, R, L * R, 0, nullptr, 0, Cin / 16, 0,
+               R, (int64_t)capacity * cond_frames * R};
+  r.streams = streams; r.first = first_frame; r.counts = counts;
+  r.n = n; r.max_k = max_k; r.cond_frames = cond_frames; r.capacity = capacity; r.x_stream_rows = x_stream_rows;
+  const int64_t total = (int64_t)n * max_k;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) {
+    dim3 grid((unsigned)((total + 4 * 64 - 1) / (4 * 64)), (unsigned)(L * R / 32));
+    hipLaunchKernelGGL((cond_ring_feed_kernel<bf16_t, 2>), grid, dim3(256), 0, st, r);
+  } else {
+    dim3 grid((unsigned)((total + 4 * 32 - 1) / (4 * 32)), (unsigned)(L * R / 32));
+    hipLaunchKernelGGL((cond_ring_feed_kernel<float, 1>), grid, dim3(256), 0, st, r);
+  }
+  return check_launch("cond_ring_feed");
 }
 
 template <typename T, int MT, int NT>

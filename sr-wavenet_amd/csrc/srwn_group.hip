@@ -186,8 +186,11 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
   int pad = 0, fq0 = 0, frem0 = 0;
   if constexpr (STREAM && !SLOTS) {
     const long long c0 = *a.clock - a.hrows;
-    if (c0 >= 0) { fq0 = (int)(c0 / a.pool); frem0 = (int)(c0 - (long long)fq0 * a.pool); }
-    else { pad = (int)(-c0); frem0 = (int)c0; }
+    if (c0 >= 0) {      // (the table is a ring of cond_frames rows: fq0 is kept modulo cond_frames, reduced here, once)
+      const long long q = c0 / a.pool;
+      frem0 = (int)(c0 - q * a.pool);
+      fq0 = (int)(q < a.cond_frames ? q : q % a.cond_frames);
+    } else { pad = (int)(-c0); frem0 = (int)c0; }
   }
 
   for (int sblk = blockIdx.x; sblk < a.nseg; sblk += gridDim.x) {
@@ -211,8 +214,11 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
       Tlen_ = a.hrows + (left < n ? (int)left : n);
       const long long c0 = sl.t - a.hrows;
       pad = 0; fq0 = 0; frem0 = 0;
-      if (c0 >= 0) { fq0 = (int)(c0 / a.pool); frem0 = (int)(c0 - (long long)fq0 * a.pool); }
-      else { pad = (int)(-c0); frem0 = (int)c0; }
+      if (c0 >= 0) {
+        const long long q = c0 / a.pool;
+        frem0 = (int)(c0 - q * a.pool);
+        fq0 = (int)(q < a.cond_frames ? q : q % a.cond_frames);
+      } else { pad = (int)(-c0); frem0 = (int)c0; }
     }
     const int Tlen = Tlen_;
     const int Jr = (Tlen - r + a.st - 1) / a.st;               // positions of this residue class (may be 0)
@@ -480,7 +486,10 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
           unsigned frame = t / (unsigned)a.pool;
           if constexpr (STREAM) {
             const int tr = frem0 + (int)t;
+            // ring row of the frame: fq0 < cond_frames was reduced on the scalar side, and the rows a launch stores span
+            // fewer than cond_frames frames, so one compare and subtract wraps them; the min keeps any other row in bounds
             frame = (unsigned)fq0 + (tr < 0 ? 0u : (unsigned)tr / (unsigned)a.pool);
+            frame = frame < (unsigned)a.cond_frames ? frame : frame - (unsigned)a.cond_frames;
             frame = frame < (unsigned)a.cond_frames ? frame : (unsigned)a.cond_frames - 1u;
           }
           const T* crow_ = cg + ((size_t)b * a.cond_frames + frame) * a.cond_stride;

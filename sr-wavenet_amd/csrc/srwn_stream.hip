@@ -79,9 +79,11 @@ __global__ __launch_bounds__(256) void flow_stream_in_kernel(const float* __rest
   const float* xb = x + (int64_t)b * x_stride;
   const float x1 = t >= 1 ? xb[t - 1] : carry[2 * b];
   const float x0 = t >= 2 ? xb[t - 2] : carry[2 * b + (1 - t)];      // t = 1: x[-1] = carry[0]; t = 0: x[-2] = carry[1]
+  // the conditioning table is a ring of cond_frames rows per stream (srwn.h): frame q of the stream lives in row
+  // q mod cond_frames.  A stream that got its whole encoding at the start has q < cond_frames: the identity.
   const long long tabs = t0 + t;
   long long f = tabs / pool;
-  f = f < cond_frames ? f : cond_frames - 1;
+  if (f >= cond_frames) f %= cond_frames;
   float c[8];
   Row8s<T>::load(cond + ((int64_t)b * cond_frames + f) * cond_stride + 8 * sub, c);
   T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
@@ -99,12 +101,12 @@ __global__ __launch_bounds__(256) void flow_stream_in_kernel(const float* __rest
 // flow exit.  Blocks [0, naff): the head and the affine transform in flow_affine_fwd_kernel's arithmetic, rows of the
 // flow's top buffer [B][top_clip_rows][R]; the thread of a stream's last row also renews the carry of the flow's input.
 // Blocks [naff, naff + nroll * B): the history roll, one block per (boundary buffer, stream): rows [n, n + hist) move to
-// [0, hist).  For n < hist the ranges overlap: the block walks them front to back, each step reading all of its rows
+// [0, hist) (slot form: rows [ran, ran + hist)).  For n < hist the ranges overlap: the block walks them front to back, each step reading all of its rows
 // before it writes any (a barrier between), and a row written in one step lies in front of every row a later step reads.
 // ------------------------------------------------------------------------------------------
 struct RollEntry { void* buf; long long clip_rows; long long hist; };      // int64 triples, as the engine's table holds them
 
-// (SLOTS) slots[b].t += n for the live slots.  Every workgroup of the exit launch reads the table, so the one that
+// (SLOTS) slots[b].t += ran(b) for the live slots.  Every workgroup of the exit launch reads the table, so the one that
 // arrives LAST -- after all of them have read -- does the writing: each counts itself in once it is done, the one that
 // finds every other counted puts the counter back to zero for the next launch and advances the table, one thread per
 // slot, ordinary stores.  Called by all threads of every workgroup, at its end.
@@ -121,7 +123,7 @@ __device__ __forceinline__ void slots_advance(SrwnSynthSlot* slots, int* arrive,
   if (threadIdx.x == 0) *arrive = 0;
   for (int b = threadIdx.x; b < B; b += 256) {
     const SrwnSynthSlot s = slots[b];
-    if (s.t < s.t_end) slots[b].t = s.t + n;
+    if (s.t < s.t_end) slots[b].t = s.t + slot_rows(s, n);
   }
 }
 
@@ -138,8 +140,10 @@ __global__ __launch_bounds__(256) void flow_stream_out_kernel(const T* __restric
     const int k = ((int)blockIdx.x - naff) / B, b = ((int)blockIdx.x - naff) % B;
     const RollEntry e = roll[k];
     int hist = (int)e.hist;
-    if constexpr (SLOTS) {
-      if (slot_rows(clock.slots[b], n) == 0) hist = 0;      // a slot without rows in this chunk keeps its buffers as they are
+    int nsh = n;
+    if constexpr (SLOTS) {      // a slot whose chunk was cut short moves by the rows it ran: a live stream goes on from there
+      nsh = slot_rows(clock.slots[b], n);
+      if (nsh == 0) hist = 0;                               // a slot without rows in this chunk keeps its buffers as they are
     }
     f32x4* base = reinterpret_cast<f32x4*>(reinterpret_cast<T*>(e.buf) + (size_t)b * (size_t)e.clip_rows * R);
     const int piece = threadIdx.x % PPR, rloc = threadIdx.x / PPR;
@@ -148,7 +152,7 @@ __global__ __launch_bounds__(256) void flow_stream_out_kernel(const T* __restric
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int i = i0 + u * RPB + rloc;
-        if (i < hist) v[u] = base[(size_t)(i + n) * PPR + piece];
+        if (i < hist) v[u] = base[(size_t)(i + nsh) * PPR + piece];
       }
       __syncthreads();
 #pragma unroll

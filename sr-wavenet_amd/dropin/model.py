@@ -15,3 +15,4 @@ ParallelWaveNet = _m.ParallelWaveNet
 SiameseWaveNet = _m.SiameseWaveNet
 StudentSynthesizer = _m.StudentSynthesizer
 AudioEncoder = _m.AudioEncoder
+Resynthesizer = _m.Resynthesizer

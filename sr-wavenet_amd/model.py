@@ -1066,7 +1066,8 @@ class StudentSynthesizer(object):
     """The deployable form of the student: the flows of a trained ``ParallelWaveNet`` (model.py:415-535) as a streaming
     synthesizer (``student.FlowSynthesizer``), with no teacher anywhere.  It serves any batch <= ``max_batch`` and any
     length = frames * pool_stride with frames <= ``max_frames``, in one call (``synthesize``) or chunk by chunk
-    (``stream``); the noise is drawn on the device from per-stream seeds (or given).  ``load`` reads what
+    (``stream``), and streams of any length whose encoding arrives while they run (``live``); the noise is drawn on the
+    device from per-stream seeds (or given).  ``load`` reads what
     ``ParallelWaveNet.save`` wrote, by the reference's variable names; the gate and skip variables a flow never reads are
     ignored."""
 
@@ -1165,6 +1166,77 @@ class StudentSynthesizer(object):
             raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
         return SynthesisPool(self._eng.pool(), self.latent_channels, self.condition_size)
 
+    def live(self, batch, conditions=None, seed=0, temperature=1.0):
+        """A ``LiveSynthesis`` of `batch` streams whose encoding arrives while they run: ``feed`` frames, ``step`` samples,
+        with no bound on the length (the conditioning tables are rings of ``max_frames`` frames).  conditions
+        [batch, condition_size] are tiled onto every fed frame.  It ends a running ``stream`` or pool, like ``synthesize``."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        return LiveSynthesis(self, int(batch), conditions, seed, temperature)
+
+    def _device_conditions(self, batch, conditions):
+        """conditions [batch, condition_size] on the device (None when the student has none)."""
+        if self.condition_size <= 0:
+            return None
+        if conditions is None:
+            raise ValueError("this student was built with condition_size > 0; pass conditions [B, condition_size]")
+        c = np.asarray(conditions, dtype=np.float32)
+        if c.shape != (batch, self.condition_size):
+            raise ValueError("conditions must be [%d, %d]" % (batch, self.condition_size))
+        return torch.as_tensor(c).to("cuda")
+
+
+class LiveSynthesis(object):
+    """One running batch of live streams (``StudentSynthesizer.live``).  ``feed(encoding [B, k, latent])`` hands every
+    stream its next k frames (k <= ``room``), ``step(n)`` returns the next n <= ``available`` samples [B, n, 1]; ``t``:
+    samples made so far.  The samples are those ``synthesize`` gives the whole encoding with the same seed and
+    temperature, however the frames and chunks were cut."""
+
+    def __init__(self, owner, batch, conditions, seed, temperature):
+        if not 1 <= batch <= owner.max_batch:
+            raise ValueError("batch %d: this synthesizer was built for max_batch=%d" % (batch, owner.max_batch))
+        self._owner, self.batch_size = owner, batch
+        self._cond = owner._device_conditions(batch, conditions)
+        self._st = owner._eng.start(None, seed, temperature, live=True, batch=batch)
+
+    @property
+    def t(self):
+        return self._st.t
+
+    @property
+    def fed(self):
+        return self._st.fed
+
+    @property
+    def room(self):
+        return self._owner._eng.room(self._st)
+
+    @property
+    def available(self):
+        """Samples that can be made now: fed * pool_stride - t."""
+        return self._st.limit - self._st.t
+
+    def _feed_device(self, enc):
+        """enc [B, k, latent] on the device (or NumPy): + the tiled conditions (model.py:496-499), into the rings."""
+        o = self._owner
+        e = torch.as_tensor(enc, dtype=torch.float32)
+        if e.dim() != 3 or e.shape[0] != self.batch_size or e.shape[2] != o.latent_channels:
+            raise ValueError("encoding must be [%d, k, latent_channels=%d], got %s"
+                             % (self.batch_size, o.latent_channels, tuple(e.shape)))
+        if self._cond is not None:
+            e = torch.cat([e.to("cuda"), self._cond[:, None, :].expand(-1, e.shape[1], -1)], dim=2)
+        o._eng.feed(self._st, e)
+
+    def feed(self, encoding):
+        self._feed_device(encoding if isinstance(encoding, torch.Tensor) else np.asarray(encoding, dtype=np.float32))
+
+    def _step_device(self, n):
+        return self._owner._eng.step(self._st, n)
+
+    def step(self, n):
+        n = int(n)
+        return self._step_device(n).view(self.batch_size, n, 1).cpu().numpy()
+
 
 class SynthesisPool(object):
     """NumPy face of a student synthesis pool (student.SynthPool): ``join(encoding=[...], ...)`` takes one
@@ -1175,6 +1247,7 @@ class SynthesisPool(object):
 
     def __init__(self, pool, latent, condition_size):
         self._pool, self._latent, self._cs = pool, latent, condition_size
+        self._live_cond = {}      # slot -> the conditions of the live stream joined there last
 
     @property
     def capacity(self):
@@ -1192,15 +1265,48 @@ class SynthesisPool(object):
     def t(self):
         return self._pool.t
 
-    def join(self, encoding, conditions=None, seed=0, temperature=None, max_samples=None):
+    def join(self, encoding, conditions=None, seed=0, temperature=None, max_samples=None, live=False):
         """encoding: one [frames_i, latent] per stream (a single 2-D array: one stream); conditions: one [condition_size]
-        per stream, tiled over its frames; seed: one per stream or a scalar s (stream i draws with s + i)."""
+        per stream, tiled over its frames; seed: one per stream or a scalar s (stream i draws with s + i).
+        live=True: the streams are fed while they run (``feed``); an encoding holds a stream's first frames ([0, latent]:
+        none yet), its conditions are kept and tiled onto every frame fed later; a live stream that has used up its frames
+        waits (no samples) until it is fed, closed or left."""
+        if live and not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
         if isinstance(encoding, np.ndarray) and encoding.ndim == 2:
             encoding = [encoding]
             conditions = None if conditions is None else [conditions]
         encoding = list(encoding)
         cond = _pool_encodings(len(encoding), encoding, conditions, self._latent, self._cs)
-        return self._pool.join(cond, seed, temperature, max_samples)
+        slots = self._pool.join(cond, seed, temperature, max_samples, live=live)
+        if live and self._cs > 0:
+            for u, c in zip(slots, _per_stream(conditions, len(slots), "conditions")):
+                self._live_cond[u] = np.asarray(c, dtype=np.float32).reshape(1, self._cs)
+        return slots
+
+    def feed(self, slots, encoding):
+        """The next frames of live slots: encoding[i] [k_i, latent] for slots[i] (k_i <= ``room``)."""
+        slots = [int(slots)] if np.isscalar(slots) else [int(u) for u in slots]
+        if isinstance(encoding, np.ndarray) and encoding.ndim == 2:
+            encoding = [encoding]
+        encs = [np.asarray(e, dtype=np.float32) for e in encoding]
+        if len(encs) != len(slots):
+            raise ValueError("feed: %d slots but %d encodings" % (len(slots), len(encs)))
+        for e in encs:
+            if e.ndim != 2 or e.shape[1] != self._latent:
+                raise ValueError("feed: each encoding is [k, %d], got shape %s" % (self._latent, e.shape))
+        if self._cs > 0:
+            if any(u not in self._live_cond for u in slots):
+                raise ValueError("feed: slots %s are not all live streams of this pool" % (slots,))
+            encs = [np.concatenate([e, np.repeat(self._live_cond[u], e.shape[0], 0)], 1) for u, e in zip(slots, encs)]
+        self._pool.feed(slots, encs)
+
+    def room(self, slot):
+        return self._pool.room(int(slot))
+
+    def close(self, slots):
+        """No more frames will come for these live streams: each frees its slot at the end of what it was fed."""
+        self._pool.close([slots] if np.isscalar(slots) else slots)
 
     def step(self, n):
         a, ran = self._pool.step(int(n))
@@ -1209,6 +1315,100 @@ class SynthesisPool(object):
 
     def leave(self, slots):
         self._pool.leave([slots] if np.isscalar(slots) else slots)
+
+
+class Resynthesizer(object):
+    """The live pipeline: an ``AudioEncoder`` feeding a ``StudentSynthesizer``.  Audio chunks in, resynthesized audio
+    chunks out, with no bound on the length; the latent frames go from the encoder into the synthesizer's conditioning
+    rings as device tensors and never visit the host.  Both halves keep their own contracts, so the audio of a stream put
+    together equals ``synthesizer.synthesize(encoder.encode(audio), ...)`` however the audio was cut."""
+
+    def __init__(self, encoder, synthesizer):
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        if not isinstance(encoder, AudioEncoder) or not isinstance(synthesizer, StudentSynthesizer):
+            raise TypeError("Resynthesizer(encoder: AudioEncoder, synthesizer: StudentSynthesizer)")
+        if int(encoder.pool_stride) != int(synthesizer.pool_stride):
+            raise ValueError("pool_stride: the encoder makes a frame per %d samples, the synthesizer reads one per %d"
+                             % (encoder.pool_stride, synthesizer.pool_stride))
+        if int(encoder.latent_channels) != int(synthesizer.latent_channels):
+            raise ValueError("latent_channels: the encoder gives %d, the synthesizer takes %d"
+                             % (encoder.latent_channels, synthesizer.latent_channels))
+        cs = synthesizer.condition_size
+        if synthesizer._eng.E != encoder.latent_channels + cs:
+            raise ValueError("condition_size %d: the synthesizer's flows read %d channels, not %d + %d"
+                             % (cs, synthesizer._eng.E, encoder.latent_channels, cs))
+        self.encoder, self.synthesizer = encoder, synthesizer
+        self.pool_stride = int(encoder.pool_stride)
+        # samples of audio a sample of output waits for beyond itself: the rest of its frame and the encoder's look-ahead
+        self.lookahead = self.pool_stride + encoder.num_layers + 1
+
+    def stream(self, batch=1, conditions=None, seed=0, temperature=1.0, chunk_size=160):
+        """A ``ResynthesisStream`` of `batch` streams in lockstep: ``push(audio [B, m])`` returns every sample that can be
+        made by now, [B, m', 1]; ``finish()`` the rest.  conditions [B, condition_size] are tiled onto every frame on the
+        device (model.py:496-499); chunk_size: the largest synthesizer chunk."""
+        batch, chunk_size = int(batch), int(chunk_size)
+        if not 1 <= batch <= min(self.encoder.max_batch, self.synthesizer.max_batch):
+            raise ValueError("batch %d: the encoder holds %d streams, the synthesizer %d"
+                             % (batch, self.encoder.max_batch, self.synthesizer.max_batch))
+        if not 1 <= chunk_size <= self.synthesizer.max_chunk:
+            raise ValueError("chunk_size %d: 1..max_chunk = %d" % (chunk_size, self.synthesizer.max_chunk))
+        return ResynthesisStream(self, batch, conditions, seed, temperature, chunk_size)
+
+
+class ResynthesisStream(object):
+    """One running batch of ``Resynthesizer.stream``.  ``t``: samples returned so far per stream; ``received``: samples
+    pushed.  ``push`` may return no sample ([B, 0, 1]) while the first frame's look-ahead is incomplete."""
+
+    def __init__(self, owner, batch, conditions, seed, temperature, chunk_size):
+        self._owner, self.batch_size, self._chunk = owner, batch, chunk_size
+        self._enc = owner.encoder._eng.start(batch)
+        self._live = owner.synthesizer.live(batch, conditions, seed, temperature)
+
+    @property
+    def t(self):
+        return self._live.t
+
+    @property
+    def received(self):
+        return self._enc.received
+
+    def _drain(self, frames, outs):
+        """frames [B, k, latent] (device) into the rings and every sample they allow: feed -> step -> feed while the
+        ring has less room than the frames that are due."""
+        live, k, f0 = self._live, int(frames.shape[1]), 0
+        while True:
+            if f0 < k:
+                r = min(live.room, k - f0)
+                if r > 0:
+                    live._feed_device(frames[:, f0:f0 + r])
+                    f0 += r
+            n = min(live.available, self._chunk)
+            if n <= 0:
+                if f0 < k:      # (cannot happen on a ring that starts a live stream: room > 0 once every sample is made)
+                    raise RuntimeError("the conditioning ring has no room and no sample to make")
+                return
+            outs.append(live._step_device(n))
+
+    def _result(self, outs):
+        B = self.batch_size
+        if not outs:
+            return np.zeros((B, 0, 1), np.float32)
+        return torch.cat(outs, dim=1).view(B, -1, 1).cpu().numpy()
+
+    def push(self, audio):
+        if self._enc.closed:
+            raise ValueError("this stream is closed (finish was called)")
+        x = self._owner.encoder._check(audio, self.batch_size)
+        outs = []
+        self._drain(self._owner.encoder._eng.push(self._enc, torch.as_tensor(x)), outs)
+        return self._result(outs)
+
+    def finish(self):
+        """The encoder's remaining whole frames (clip-end padding) and the samples they allow; closes the stream."""
+        outs = []
+        self._drain(self._owner.encoder._eng.finish(self._enc), outs)
+        return self._result(outs)
 
 
 class SiameseWaveNet(_EngineOwner):

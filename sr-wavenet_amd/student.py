@@ -431,6 +431,24 @@ def stream_history_rows(dilations, groups=None) -> List[int]:
     return [sum(dil[l0:l1]) for l0, l1 in groups]
 
 
+def live_room(fed: int, t: int, hist_max: int, pool_stride: int, capacity: int) -> int:
+    """How many frames a LIVE stream may be fed now.  Its conditioning tables are rings of ``capacity`` frames: frame f
+    lives in row f mod capacity.  A chunk starting at time t recomputes the halo rows of group g back to t - hist_g, so
+    the oldest frame still read is max(t - hist_max, 0) // pool_stride; a feed must not overwrite that frame or a newer
+    one.  With ``fed`` frames written so far: max(0, capacity - fed + max(t - hist_max, 0) // pool_stride).  Feeding k
+    frames at a time never stalls iff capacity >= ceil(hist_max / pool_stride) + k.  Pure Python: the CPU tests drive
+    the fp64 oracle with it."""
+    fed, t, hist_max, pool_stride, capacity = int(fed), int(t), int(hist_max), int(pool_stride), int(capacity)
+    if fed < 0 or t < 0 or hist_max < 0 or pool_stride < 1 or capacity < 1 or t > fed * pool_stride:
+        raise ValueError("live_room: fed=%d t=%d hist_max=%d pool_stride=%d capacity=%d" % (fed, t, hist_max, pool_stride, capacity))
+    return max(0, capacity - fed + max(t - hist_max, 0) // pool_stride)
+
+
+def live_min_frames(hist_max: int, pool_stride: int) -> int:
+    """The smallest ring a live stream can run on one frame at a time: ceil(hist_max / pool_stride) + 1."""
+    return -(-int(hist_max) // int(pool_stride)) + 1
+
+
 class FlowWeights:
     """The weight side of one flow without the training engine around it: ``FlowStack``'s parameter layout, reference
     variable names and image packing (the forward images only), on buffers of its own."""
@@ -491,10 +509,12 @@ class FlowWeights:
 
 class SynthState:
     """One batch of streams of a ``FlowSynthesizer`` (which holds the device side: a synthesizer serves one state at a
-    time).  ``t``: samples made so far; ``limit`` = frames * pool_stride."""
+    time).  ``t``: samples made so far; ``limit`` = frames * pool_stride.  A ``live`` state is fed its frames while it runs
+    (``FlowSynthesizer.feed``): ``fed`` frames so far, ``limit`` = fed * pool_stride."""
 
-    def __init__(self, batch: int, frames: int, limit: int, serial: int):
+    def __init__(self, batch: int, frames: int, limit: int, serial: int, live: bool = False):
         self.B, self.frames, self.limit, self.t, self._serial = batch, frames, limit, 0, serial
+        self.live, self.fed = bool(live), frames
 
 
 class FlowSynthesizer:
@@ -502,7 +522,9 @@ class FlowSynthesizer:
     encodings, then ``step`` it chunk by chunk.  Per chunk and flow: one entry launch, one launch per layer group, one
     exit launch (+ one noise launch per chunk); the sequence of a (batch, chunk size) is captured as a hipGraph when it
     is used a second time and replayed from then on (SRWN_MODEL_GRAPHS=0: eager launches).  ``pool`` serves the same
-    buffers as slots that streams join and leave while the batch runs (``SynthPool``)."""
+    buffers as slots that streams join and leave while the batch runs (``SynthPool``).  ``start(..., live=True)`` begins
+    streams that are handed their frames while they run (``feed`` / ``room``): the conditioning tables then serve as
+    rings of ``max_frames`` frames and a stream has no bound on its length."""
 
     def __init__(self, flow_cfg: StackConfig, num_flows: int, max_batch: int = 1, max_chunk: int = 1600,
                  max_frames: int = 32, device="cuda"):
@@ -557,14 +579,23 @@ class FlowSynthesizer:
             w.repack()
 
     # ------------------------------------------------------------------------------------------------
-    def start(self, cond, seeds=0, temperature=1.0) -> SynthState:
+    def start(self, cond, seeds=0, temperature=1.0, live=False, batch=None) -> SynthState:
         """cond [B, frames <= max_frames, E] (encoding_w_condition) -> a state at clock 0: zero history, zero carry.
-        seeds / temperature: one value per stream, or a scalar (seed s: stream b draws with s + b)."""
+        seeds / temperature: one value per stream, or a scalar (seed s: stream b draws with s + b).
+        live=True: the encoding arrives while the stream runs (``feed``); cond is None (`batch` streams, default 1) or the
+        first frames, and the conditioning tables serve as rings of max_frames frames (``live_room``)."""
+        if live:
+            need = live_min_frames(max(self.hist), self.pool_stride)
+            if self.max_frames < need:
+                raise ValueError("a live stream needs a ring of max_frames >= ceil(%d / %d) + 1 = %d frames, this synthesizer "
+                                 "holds %d" % (max(self.hist), self.pool_stride, need, self.max_frames))
+            if cond is None:
+                cond = torch.zeros((1 if batch is None else int(batch), 0, self.E), dtype=torch.float32)
         cond = torch.as_tensor(cond, dtype=torch.float32)
         if cond.dim() != 3 or cond.shape[2] != self.E:
             raise ValueError("cond must be [batch, frames, %d], got %s" % (self.E, tuple(cond.shape)))
         B, frames = int(cond.shape[0]), int(cond.shape[1])
-        if not 1 <= B <= self.max_batch or not 1 <= frames <= self.max_frames:
+        if not 1 <= B <= self.max_batch or not (0 if live else 1) <= frames <= self.max_frames:
             raise ValueError("cond: %d streams x %d frames; this synthesizer holds max_batch=%d, max_frames=%d"
                              % (B, frames, self.max_batch, self.max_frames))
         sd = np.asarray(seeds)
@@ -578,12 +609,14 @@ class FlowSynthesizer:
         self.seeds[:B].copy_(torch.as_tensor(np.asarray([int(s) & 0x7fffffffffffffff for s in sd], dtype=np.int64)))
         self.temps[:B].copy_(torch.as_tensor(tp.astype(np.float32)))
         self.cond_in.zero_()
-        self.cond_in.view(self.max_batch, self.max_frames, -1)[:B, :frames, :self.E].copy_(cond.to(self.dev))
         st = K._stream()
+        if not live:
+            self.cond_in.view(self.max_batch, self.max_frames, -1)[:B, :frames, :self.E].copy_(cond.to(self.dev))
         for i, w in enumerate(self.weights):      # cb of every layer and frame (model.py:180), one product per flow
-            call("srwn_pw_linear_ychunks", self.cond_in.data_ptr(), w.Ep, w.Ep, w.wptr(w.o_wc),
-                 w.view("BC").reshape(-1).data_ptr(), self.cond_all[i].data_ptr(), self.R, self.R, self.rows_c * self.R,
-                 self.L * self.R, self.L * self.R, self.rows_c, K.abi_dtype(self.dt), st)
+            if not live:
+                call("srwn_pw_linear_ychunks", self.cond_in.data_ptr(), w.Ep, w.Ep, w.wptr(w.o_wc),
+                     w.view("BC").reshape(-1).data_ptr(), self.cond_all[i].data_ptr(), self.R, self.R, self.rows_c * self.R,
+                     self.L * self.R, self.L * self.R, self.rows_c, K.abi_dtype(self.dt), st)
             for b in self.bufs[i]:
                 b.zero_()
             self.carry[i].zero_()
@@ -592,8 +625,60 @@ class FlowSynthesizer:
         if self._pool is not None:      # the buffers serve one of the two at a time
             self._pool._open = False
             self._pool = None
-        self._state = SynthState(B, frames, frames * self.pool_stride, self._serial)
+        self._state = SynthState(B, 0 if live else frames, 0 if live else frames * self.pool_stride, self._serial, live)
+        if live and frames:
+            self.feed(self._state, cond)
         return self._state
+
+    def _check_state(self, state):
+        if state is not self._state or state._serial != self._serial:
+            raise ValueError("this state is not the synthesizer's current one (start() began another)")
+
+    def room(self, state: SynthState) -> int:
+        """Frames a live state may be fed now (``live_room``); 0 for a state that got its encoding at ``start``."""
+        self._check_state(state)
+        if not state.live:
+            return 0
+        return live_room(state.fed, state.t, max(self.hist), self.pool_stride, self.max_frames)
+
+    def _ring_feed(self, streams, first, counts, max_k):
+        """srwn_cond_ring_feed, one launch per flow: frames [first_i, first_i + counts_i) of the named streams, staged in
+        ``cond_in`` [max_batch, max_frames, Ep] (stream u's new frames in rows 0.. of its block), into every flow's ring."""
+        n = len(streams)
+        host = np.empty(2 * n, np.int64)           # one upload: first [n] int64 | streams [n] int32 | counts [n] int32
+        host[:n] = first
+        i32 = host[n:].view(np.int32)
+        i32[:n], i32[n:] = streams, counts
+        dev = torch.from_numpy(host).to(self.dev)
+        base, st = dev.data_ptr(), K._stream()
+        for i, w in enumerate(self.weights):
+            call("srwn_cond_ring_feed", self.cond_in.data_ptr(), w.Ep, self.max_frames, w.Ep, w.wptr(w.o_wc),
+                 w.view("BC").reshape(-1).data_ptr(), self.cond_all[i].data_ptr(), self.L, self.R, self.max_frames,
+                 self.max_batch, base + 8 * n, base, base + 12 * n, n, int(max_k), K.abi_dtype(self.dt), st)
+
+    def feed(self, state: SynthState, frames) -> None:
+        """The next k frames of every stream of a live state: frames [B, k, E] (encoding_w_condition).  A device tensor is
+        taken as it is: no host copy, no synchronisation.  Refuses (ValueError, state untouched) a state that is not live
+        and k > ``room``.  Afterwards ``step`` may run up to fed * pool_stride."""
+        self._check_state(state)
+        if not state.live:
+            raise ValueError("feed: this state got its whole encoding at start (start(..., live=True) begins a live one)")
+        fr = torch.as_tensor(frames, dtype=torch.float32)
+        if fr.dim() != 3 or fr.shape[0] != state.B or fr.shape[2] != self.E:
+            raise ValueError("feed: frames must be [%d, k, %d], got %s" % (state.B, self.E, tuple(fr.shape)))
+        k = int(fr.shape[1])
+        if k == 0:
+            return
+        room = self.room(state)
+        if k > room:
+            raise ValueError("feed: %d frames, but the ring of %d has room for %d at t = %d with %d fed"
+                             % (k, self.max_frames, room, state.t, state.fed))
+        B = state.B
+        self.cond_in.view(self.max_batch, self.max_frames, -1)[:B, :k, :self.E].copy_(fr)
+        self._ring_feed(np.arange(B), np.full(B, state.fed), np.full(B, k), k)
+        state.fed += k
+        state.frames = state.fed
+        state.limit = state.fed * self.pool_stride
 
     def pool(self) -> "SynthPool":
         """A ``SynthPool`` on this synthesizer's buffers: max_batch slots, each a stream at a clock of its own.  The current
@@ -644,8 +729,7 @@ class FlowSynthesizer:
     def step(self, state: SynthState, n: int, noise=None) -> torch.Tensor:
         """The next n samples of every stream: [B, n] fp32 in [-1, 1].  noise [B, n]: the first flow's input instead of the
         device draw.  Refuses (ValueError, state untouched) n outside 1..max_chunk and steps past frames * pool_stride."""
-        if state is not self._state or state._serial != self._serial:
-            raise ValueError("this state is not the synthesizer's current one (start() began another)")
+        self._check_state(state)
         n = int(n)
         if not 1 <= n <= self.max_chunk:
             raise ValueError("chunk of %d samples: 1..max_chunk = %d" % (n, self.max_chunk))
@@ -691,6 +775,9 @@ class SynthPool:
         self._t = np.zeros(self.capacity, np.int64)          # host mirror of the device table (the kernel advances both)
         self._end = np.zeros(self.capacity, np.int64)
         self._active = np.zeros(self.capacity, bool)
+        self._live = np.zeros(self.capacity, bool)           # live slots: fed while they run; t_end = fed * pool_stride
+        self._closed = np.zeros(self.capacity, bool)         # ... until closed: no more frames will come
+        self._fed = np.zeros(self.capacity, np.int64)
         self.slots = torch.zeros((self.capacity, 2), dtype=torch.int64, device=syn.dev)      # [t, t_end] per slot
         self.arrive = torch.zeros(1, dtype=torch.int32, device=syn.dev)      # the last flow's exit launch counts its workgroups here
         self._graphs: Dict[tuple, object] = {}
@@ -721,20 +808,31 @@ class SynthPool:
         self.slots.copy_(torch.from_numpy(np.stack([self._t, self._end], 1)))
         self.arrive.zero_()
 
-    def _check_join(self, cond, seeds, temperature, max_samples, slots):
+    def _check_join(self, cond, seeds, temperature, max_samples, slots, live=False):
         """Everything join refuses, before any device work: (encodings as float32 tensors, seeds, temperatures, the chosen
         slots, t_end per stream)."""
         self._check_open()
+        if live:
+            need = live_min_frames(max(self.syn.hist), self.pool_stride)
+            if self.frames < need:
+                raise ValueError("join: a live stream needs a ring of max_frames >= ceil(%d / %d) + 1 = %d frames, this "
+                                 "synthesizer holds %d" % (max(self.syn.hist), self.pool_stride, need, self.frames))
+            if max_samples is not None:
+                raise ValueError("join: a live stream ends where close() finds it; max_samples is for bounded streams")
+            if cond is None:
+                cond = [None]
         if isinstance(cond, (torch.Tensor, np.ndarray)) and cond.ndim == 2:
             cond = [cond]
-        cond = [c.detach().to("cpu", torch.float32) if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c, dtype=np.float32))
+        cond = [torch.zeros((0, self.E)) if (live and c is None) else
+                c.detach().to("cpu", torch.float32) if isinstance(c, torch.Tensor) else torch.as_tensor(np.asarray(c, dtype=np.float32))
                 for c in cond]
         n = len(cond)
         if n < 1:
             raise ValueError("join: no streams")
         for i, c in enumerate(cond):
-            if c.dim() != 2 or c.shape[1] != self.E or not 1 <= c.shape[0] <= self.frames:
-                raise ValueError("join: cond %d must be [1..%d frames, %d], got %s" % (i, self.frames, self.E, tuple(c.shape)))
+            if c.dim() != 2 or c.shape[1] != self.E or not (0 if live else 1) <= c.shape[0] <= self.frames:
+                raise ValueError("join: cond %d must be [%d..%d frames, %d], got %s"
+                                 % (i, 0 if live else 1, self.frames, self.E, tuple(c.shape)))
 
         def per_stream(x, what, default):
             if x is None:
@@ -769,13 +867,17 @@ class SynthPool:
                 raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
         return cond, sd, tp, slots, ends
 
-    def join(self, cond, seeds=0, temperature=None, max_samples=None, slots=None) -> List[int]:
+    def join(self, cond, seeds=0, temperature=None, max_samples=None, slots=None, live=False) -> List[int]:
         """n streams into free slots (the lowest ones, or `slots`): cond n encodings [frames_i <= max_frames, E]; seeds one
         per stream or a scalar s (stream i draws with s + i); temperature None (1), a scalar or one per stream;
         max_samples None, one int or n entries: a stream ends at min(frames_i * pool_stride, max_samples).  Writes the
         joined slots' seeds, temperatures and rows of every flow's conditioning table (srwn_pw_linear_ychunks on those rows)
-        and zeroes their history rows and carries (srwn_flow_stream_reset_slots); returns the slots."""
-        cond, sd, tp, slots, ends = self._check_join(cond, seeds, temperature, max_samples, slots)
+        and zeroes their history rows and carries (srwn_flow_stream_reset_slots); returns the slots.
+        live=True: the streams are fed while they run (``feed``): cond holds each stream's first frames (None or an entry
+        None: no frame yet), their table rows serve as rings of max_frames frames and are written by srwn_cond_ring_feed; a
+        live stream that has used up its frames is STARVED, not ended: it stays active with ran = 0 until it is fed,
+        closed (``close``: it ends where its frames end) or left."""
+        cond, sd, tp, slots, ends = self._check_join(cond, seeds, temperature, max_samples, slots, live)
         syn, n = self.syn, len(cond)
         dev, Fm, st = syn.dev, syn.max_frames, K._stream()
         dst = torch.tensor(slots, dtype=torch.int64, device=dev)
@@ -792,6 +894,11 @@ class SynthPool:
                 runs.append((u0, a + 1 - u0))
                 u0 = b
         esz = syn.cond_in.element_size()
+        if live:      # the first frames enter the rings as every later one does
+            runs = []
+            ks = [int(c.shape[0]) for c in cond]
+            if max(ks) > 0:
+                syn._ring_feed(np.asarray(slots), np.zeros(n, np.int64), np.asarray(ks), max(ks))
         for i, w in enumerate(syn.weights):
             for u0, k in runs:
                 call("srwn_pw_linear_ychunks", syn.cond_in.data_ptr() + u0 * Fm * w.Ep * esz, w.Ep, w.Ep, w.wptr(w.o_wc),
@@ -800,11 +907,71 @@ class SynthPool:
         ids = dst.to(torch.int32)
         call("srwn_flow_stream_reset_slots", syn.roll_all.data_ptr(), syn.roll_all.shape[0], syn.carry_all.data_ptr(), syn.F,
              syn.max_batch * 2, ids.data_ptr(), n, self.capacity, syn.R, K.abi_dtype(syn.dt), st)
-        for u, e in zip(slots, ends):
+        for u, e, c in zip(slots, ends, cond):
             self._t[u], self._end[u] = 0, e
-            self._active[u] = e > 0
+            self._active[u] = live or e > 0
+            self._live[u], self._closed[u], self._fed[u] = live, False, int(c.shape[0]) if live else 0
         self._upload()
         return list(slots)
+
+    # ---- live slots
+    def _slot_list(self, slots, who):
+        slots = [int(u) for u in (slots if np.ndim(slots) else [slots])]
+        if any(u < 0 or u >= self.capacity for u in slots):
+            raise ValueError("%s: slots %s outside the pool's %d" % (who, slots, self.capacity))
+        return slots
+
+    def room(self, slot: int) -> int:
+        """Frames a live slot may be fed now (``live_room``); 0 for every other slot."""
+        self._check_open()
+        u, = self._slot_list(slot, "room")
+        if not (self._active[u] and self._live[u]) or self._closed[u]:
+            return 0
+        return live_room(int(self._fed[u]), int(self._t[u]), max(self.syn.hist), self.pool_stride, self.frames)
+
+    def feed(self, slots, frames) -> None:
+        """The next frames of live slots: frames[i] [k_i, E] for slots[i] (device tensors are taken as they are).  One
+        srwn_cond_ring_feed per flow however many slots are fed; each slot's t_end grows to fed * pool_stride, on the host
+        mirror and the device table together.  Refuses (ValueError, nothing changed) a slot that is not a live, open stream
+        and k_i > room(slot).  The other slots are not touched."""
+        self._check_open()
+        slots = self._slot_list(slots, "feed")
+        if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 2:
+            frames = [frames]
+        frames = [torch.as_tensor(f, dtype=torch.float32) for f in frames]
+        if len(frames) != len(slots) or len(set(slots)) != len(slots):
+            raise ValueError("feed: %d distinct slots need one [k, %d] each, got %d" % (len(slots), self.E, len(frames)))
+        for u, f in zip(slots, frames):
+            if not (self._active[u] and self._live[u]) or self._closed[u]:
+                raise ValueError("feed: slot %d holds no live, open stream" % u)
+            if f.dim() != 2 or f.shape[1] != self.E:
+                raise ValueError("feed: frames of slot %d must be [k, %d], got %s" % (u, self.E, tuple(f.shape)))
+            if f.shape[0] > self.room(u):
+                raise ValueError("feed: %d frames for slot %d, but its ring of %d has room for %d at t = %d with %d fed"
+                                 % (f.shape[0], u, self.frames, self.room(u), self._t[u], self._fed[u]))
+        pairs = [(u, f) for u, f in zip(slots, frames) if f.shape[0] > 0]
+        if not pairs:
+            return
+        syn = self.syn
+        cin = syn.cond_in.view(syn.max_batch, syn.max_frames, -1)
+        for u, f in pairs:
+            cin[u, :f.shape[0], :self.E].copy_(f)
+        ks = [int(f.shape[0]) for _, f in pairs]
+        us = [u for u, _ in pairs]
+        syn._ring_feed(np.asarray(us), self._fed[us].copy(), np.asarray(ks), max(ks))
+        for u, k in zip(us, ks):
+            self._fed[u] += k
+            self._end[u] = self._fed[u] * self.pool_stride
+        self._upload()
+
+    def close(self, slots) -> None:
+        """No more frames will come for the live streams in `slots`: each frees its slot at the end of what it was fed,
+        like a bounded stream (at once when it is already there)."""
+        self._check_open()
+        for u in self._slot_list(slots, "close"):
+            if self._active[u] and self._live[u]:
+                self._closed[u] = True
+                self._active[u] = self._t[u] < self._end[u]
 
     def leave(self, slots) -> None:
         """Ends the streams in `slots` (a slot already free stays free) and frees their slots."""
@@ -814,6 +981,7 @@ class SynthPool:
             raise ValueError("leave: slots %s outside the pool's %d" % (slots, self.capacity))
         for u in slots:
             self._active[u] = False
+            self._live[u] = False
             self._end[u] = self._t[u]
         self._upload()
 
@@ -852,5 +1020,5 @@ class SynthPool:
             self._seen.add(key)
             syn._launch_chunk(B, n, noise is None, self)
         self._t += ran
-        self._active &= self._t < self._end
+        self._active &= (self._t < self._end) | (self._live & ~self._closed)      # a starved live slot stays
         return syn.xbuf[syn.F][:, :n].clone(), ran
