@@ -1025,6 +1025,54 @@ int srwn_nc_encode_frames(const float* x, int64_t ld, const float* nc_w, const f
                           int64_t wres_stride, const float* bias_c, const float* bias_r, float* partials, void* means,
                           int32_t B, int32_t nframes, int32_t pool_stride, int32_t valid_rows, int32_t nlayers, int32_t C,
                           int32_t K, int32_t dtype, void* stream);
+/* ---- encoder pools (since srwn_version() 111; csrc/srwn_ncstream.hip): the same chain (createEncoder, model.py:136-156)
+ * over a LIST of frames of independent streams, each at a clock of its own.  A stream's audio lives in its row of a ring
+ * [capacity][ring_len] fp32, sample s in column s mod ring_len; a frame reads its own pool_stride + nlayers + 1 samples
+ * and nothing else, so a launch is any list of frames of any streams.
+ *
+ *   SrwnEncFrame                  one item of a launch (16 bytes, a DEVICE array): the row of the ring, the ring column
+ *                                 of the frame's first sample (first_sample mod ring_len, reduced on the host), and the
+ *                                 number of real samples from there on: pool_stride + nlayers + 1 for a frame whose
+ *                                 look-ahead is complete, fewer (>= pool_stride) at the end of a clip, where the missing
+ *                                 rows are the SAME padding.  Rows are counted from the frame's first sample and a row
+ *                                 >= valid is never loaded, so a column still holding an older sample is unreachable.
+ *   srwn_nc_encode_frame_list     srwn_nc_encode_frames with workgroup (segment, item) instead of (segment, frame,
+ *                                 stream): means [nlayers][nitems][128] bf16 (srwn_pw_linear_ksplit with rows =
+ *                                 nitems), partials = srwn_nc_encode_list_partials(nitems, pool_stride, nlayers)
+ *                                 floats.  One device body serves both entries (two instantiations that differ in the
+ *                                 addressing only; every sum keeps its fixed order), so item i has the bits of the same
+ *                                 window as a one-frame srwn_nc_encode_frames call, whatever the other items hold.  The
+ *                                 table cannot be read before the launch: an item whose stream lies outside [0,
+ *                                 capacity), whose col lies outside [0, ring_len) or whose valid lies outside
+ *                                 [pool_stride, pool_stride + nlayers + 1] is skipped and its row of means is zero, as
+ *                                 srwn_cond_ring_feed skips such ids.  Errors before any launch: a null pointer (-3);
+ *                                 ring_len < pool_stride + nlayers + 1, nitems < 0 or > 65535, capacity < 1,
+ *                                 pool_stride < 1, nlayers outside 1..srwn_nc_encode_max_layers() (-2); C, K or a
+ *                                 dtype the chain is not built for (-4; an unknown dtype -1); nitems = 0: nothing (0).
+ *   srwn_audio_ring_put           new audio into the rings, one launch however many streams: entry i < n copies
+ *                                 counts[i] floats from src + src_offset[i] to row streams[i], columns (first_col[i] +
+ *                                 j) mod ring_len.  streams, src_offset, first_col, counts: int32 DEVICE arrays (they
+ *                                 may share one upload with src); max_count bounds the counts (the grid is sized by it,
+ *                                 a larger count is cut).  An entry whose stream lies outside [0, capacity), whose
+ *                                 first_col lies outside [0, ring_len) or whose offset is negative is skipped.  Errors:
+ *                                 a null pointer (-3); ring_len < 1, capacity < 1, n < 0 or > 65535, max_count < 0 or >
+ *                                 ring_len (-2); n = 0 or max_count = 0: nothing (0). */
+typedef struct SrwnEncFrame {
+  int32_t stream;   /* row of the audio ring, 0 .. capacity-1 */
+  int32_t col;      /* ring column of the frame's first sample */
+  int32_t valid;    /* real samples from the frame's first sample on */
+  int32_t reserved; /* 0 */
+} SrwnEncFrame;
+int64_t srwn_nc_encode_list_partials(int32_t nitems, int32_t pool_stride, int32_t nlayers);
+int srwn_nc_encode_frame_list(const float* ring, int32_t ring_len, int32_t capacity, const SrwnEncFrame* frames,
+                              int32_t nitems, const float* nc_w, const float* nc_b, const void* nc_wr,
+                              const float* nc_br, const void* wconv, int64_t wconv_stride, const void* wres,
+                              int64_t wres_stride, const float* bias_c, const float* bias_r, float* partials,
+                              void* means, int32_t pool_stride, int32_t nlayers, int32_t C, int32_t K, int32_t dtype,
+                              void* stream);
+int srwn_audio_ring_put(float* ring, int32_t ring_len, int32_t capacity, const float* src, const int32_t* streams,
+                        const int32_t* src_offset, const int32_t* first_col, const int32_t* counts, int32_t n,
+                        int32_t max_count, void* stream);
 /* small products on the [B*frames] axis (latent 1x1 model.py:152, gradient wrt the encoding through model.py:180):
  *   C[m][n] = (accumulate ? C : 0) + bias[n] + sum_k A(m,k)*B(k,n), chunked addressing on both operands:
  *   A(m,k) = a[(k/a_chunk)*a_chunk_stride + m*lda + k%a_chunk];  B(k,n) = b[(k/b_chunk)*b_chunk_stride + (k%b_chunk)*ldb_k + n*ldb_n]

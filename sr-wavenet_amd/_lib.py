@@ -40,6 +40,12 @@ class SrwnSynthSlot(C.Structure):
     _fields_ = [("t", C.c_int64), ("t_end", C.c_int64)]
 
 
+class SrwnEncFrame(C.Structure):
+    """Mirror of srwn.h's SrwnEncFrame (16 bytes): one frame of a launch of srwn_nc_encode_frame_list, passed as a device
+    array -- the row of the audio ring, the ring column of the frame's first sample and the real samples from there on."""
+    _fields_ = [("stream", C.c_int32), ("col", C.c_int32), ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SrwnGenSampling(C.Structure):
     """Mirror of srwn.h's SrwnGenSampling (16 bytes): one utterance's (or pool slot's) sampling controls, passed to the
     *_sampled entry points and to srwn_sample_filtered as a device array.  The defaults (1, 1, 0) mean "off"."""
@@ -172,6 +178,11 @@ SIGNATURES = {
     "srwn_nc_encode_partials": (_i64, [_i32, _i32, _i32, _i32]),
     "srwn_nc_encode_frames": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _i32,
                                         _i32, _i32, _i32, _i32, _p]),
+    # encoder pools (srwn_version() 111): the chain over a device list of SrwnEncFrame, audio from a ring per stream
+    "srwn_nc_encode_list_partials": (_i64, [_i32, _i32, _i32]),
+    "srwn_nc_encode_frame_list": (C.c_int, [_p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p,
+                                            _i32, _i32, _i32, _i32, _i32, _p]),
+    "srwn_audio_ring_put": (C.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _i32, _p]),
     "srwn_small_gemm": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _i64, _i64, _i32, _i64, _p, _p, _i64, _i32, _i32,
                                   _i32, _i32, _i32, _p]),
     "srwn_small_wgrad": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i32, _i32, _i32, _f32, _p]),

@@ -31,7 +31,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-faile
 # do not.
 NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"], "srwn_siamese.hip": ["contrastive_head_kernel"],
             "srwn_wngate.hip": ["wavenet_layer_fwd_kernel", "wavenet_layer_bwd_kernel"],
-            "srwn_ncstream.hip": ["nc_encode_frames_kernel"]}
+            "srwn_ncstream.hip": ["nc_encode_frames_kernel", "nc_encode_frames_kernelINS_10NcListArgs"]}
 
 
 def _deps():

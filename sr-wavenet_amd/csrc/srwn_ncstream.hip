@@ -15,7 +15,15 @@
 // ascending, segments ascending), so a frame's bits depend on its own window only: not on its place in the launch, the
 // streams beside it or the number of frames.  Rows at or beyond `valid_rows` are beyond the clip: the input of EVERY
 // layer is zero there (SAME padding), so r_l is stored as zero on those rows rather than computed from zeros below.
+//
+// The same chain serves a LIST of frames (srwn_nc_encode_frame_list): workgroup (segment, item) takes its stream, the ring
+// column of its first sample and its count of real samples from a device table instead of the grid, and reads the audio
+// from a ring [capacity][ring_len] (sample s in column s mod ring_len).  One device body, two instantiations: the
+// addressing of the audio and of the output row differ and nothing else does, so a frame from the list has the bits of
+// the same frame from the rectangle.  Rows are counted from the frame's first sample and gated by `valid` before any
+// load, so a column of the ring that holds an older sample is never read.
 #include <atomic>
+#include <type_traits>
 
 #include "srwn_common.h"
 #include "srwn_host.h"
@@ -47,10 +55,17 @@ struct NcEncArgs {
   int L, P, nframes, valid;
 };
 
+struct NcListArgs : NcEncArgs {                        // x = the ring, ld = ring_len; nframes / valid unused
+  const SrwnEncFrame* items;                           // [gridDim.y], device
+  int ring_len, capacity;
+};
+
 // this thread's LDS-DMA pieces are in LDS (the barrier that follows makes them every wave's)
 __device__ __forceinline__ void copies_landed() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
-__global__ __launch_bounds__(256) void nc_encode_frames_kernel(NcEncArgs a) {
+template <class A>
+__global__ __launch_bounds__(256) void nc_encode_frames_kernel(A a) {
+  constexpr bool kList = std::is_same<A, NcListArgs>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   Frag<bf16_t>* lds_conv = reinterpret_cast<Frag<bf16_t>*>(smem);           // [RT][taps*KS][64]
   Frag<bf16_t>* lds_res = lds_conv + kRT * kTaps * kKS * 64;                  // [RT][KS][64], permuted k
@@ -59,13 +74,24 @@ __global__ __launch_bounds__(256) void nc_encode_frames_kernel(NcEncArgs a) {
   bf16_t* act = reinterpret_cast<bf16_t*>(lds_sum + 3 * kC);                  // [129][kLS]: r_l, or a_{l+1} in passing
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int col = lane & 31, half = lane >> 5;
-  const int seg = blockIdx.x, f = blockIdx.y, b = blockIdx.z;
+  const int seg = blockIdx.x, f = kList ? 0 : blockIdx.y;      // (a list item's window is the frame's own)
   const int nrows = min(kSeg, a.P - seg * kSeg);       // frame rows of this segment
   const int tr = 32 * wave + col;                      // this lane's row of the segment
   const int gt = f * a.P + seg * kSeg + tr;            // ... and of the window
   const bool active = 32 * wave < nrows + a.L;         // tiles further ahead than the chain looks are not computed
-  const int64_t R = (int64_t)gridDim.z * a.nframes;
-  const int64_t row = (int64_t)b * a.nframes + f;
+  const int64_t R = kList ? (int64_t)gridDim.y : (int64_t)gridDim.z * a.nframes;
+  SrwnEncFrame it{};
+  if constexpr (kList) {
+    it = a.items[blockIdx.y];                          // uniform: a scalar load
+    if (it.stream < 0 || it.stream >= a.capacity || it.col < 0 || it.col >= a.ring_len || it.valid < a.P ||
+        it.valid > a.P + a.L + 1) {                    // a table that cannot be checked before the launch: zeros
+      if (tid < kC)
+        for (int l = 0; l < a.L; ++l) a.parts[(((int64_t)seg * a.L + l) * R + blockIdx.y) * kC + tid] = 0.0f;
+      return;
+    }
+  }
+  const int b = kList ? it.stream : blockIdx.z;        // the row of the audio
+  const int64_t row = kList ? (int64_t)blockIdx.y : (int64_t)b * a.nframes + f;
 
   lds_dma_copy(a.nc_wr, lds_res, kResBytes, wave, lane, 4);
   lds_dma_copy(a.wconv, lds_conv, kConvBytes, wave, lane, 4);
@@ -98,7 +124,9 @@ __global__ __launch_bounds__(256) void nc_encode_frames_kernel(NcEncArgs a) {
       for (int mt = 0; mt < kRT; ++mt) mma(accR[mt], af[s & 1][mt], cf[s]);
       __builtin_amdgcn_sched_barrier(0);
     }
-    const bool in_clip = gt < a.valid;
+    bool in_clip;      // (the count is read from the arguments here: through a local copy the frames instantiation
+                       // compiled to other scalar code and its launch ran 2 % longer)
+    if constexpr (kList) in_clip = gt < it.valid; else in_clip = gt < a.valid;
     wave_lds_order();                     // the frame sums have read this wave's rows
 #pragma unroll
     for (int mt = 0; mt < kRT; ++mt)
@@ -116,8 +144,17 @@ __global__ __launch_bounds__(256) void nc_encode_frames_kernel(NcEncArgs a) {
     Frag<bf16_t> cf[kKS];
     if (active) {
       const float* xb = a.x + (int64_t)b * a.ld;
-      const float x0 = gt < a.valid ? fmaxf(xb[gt], 0.0f) : 0.0f;
-      const float x1 = gt + 1 < a.valid ? fmaxf(xb[gt + 1], 0.0f) : 0.0f;
+      float x0, x1;
+      if constexpr (kList) {                           // col < ring_len and a row that is read is < valid <= ring_len:
+        int c0 = it.col + gt, c1 = it.col + gt + 1;    // one compare and subtract wraps it
+        if (c0 >= a.ring_len) c0 -= a.ring_len;
+        if (c1 >= a.ring_len) c1 -= a.ring_len;
+        x0 = gt < it.valid ? fmaxf(xb[c0], 0.0f) : 0.0f;
+        x1 = gt + 1 < it.valid ? fmaxf(xb[c1], 0.0f) : 0.0f;
+      } else {
+        x0 = gt < a.valid ? fmaxf(xb[gt], 0.0f) : 0.0f;
+        x1 = gt + 1 < a.valid ? fmaxf(xb[gt + 1], 0.0f) : 0.0f;
+      }
 #pragma unroll
       for (int mt = 0; mt < kRT; ++mt)
 #pragma unroll
@@ -231,6 +268,56 @@ __global__ __launch_bounds__(256) void nc_frame_finish_kernel(const float* __res
   out[i] = (bf16_t)(s * scale);
 }
 
+// dst row streams[i], columns (first_col[i] + j) mod ring_len <- src[src_offset[i] + j], j < counts[i]
+__global__ __launch_bounds__(256) void audio_ring_put_kernel(float* __restrict__ ring, int ring_len, int capacity,
+                                                             const float* __restrict__ src,
+                                                             const int32_t* __restrict__ streams,
+                                                             const int32_t* __restrict__ src_offset,
+                                                             const int32_t* __restrict__ first_col,
+                                                             const int32_t* __restrict__ counts, int max_count) {
+  const int i = blockIdx.y;
+  const int u = streams[i], c0 = first_col[i], n = min(min(counts[i], max_count), ring_len);
+  if (u < 0 || u >= capacity || c0 < 0 || c0 >= ring_len || src_offset[i] < 0) return;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  int c = c0 + j;                                      // < 2 ring_len
+  if (c >= ring_len) c -= ring_len;
+  ring[(int64_t)u * ring_len + c] = src[(int64_t)src_offset[i] + j];
+}
+
+// once per device and kernel: the attribute call is host time on a path of five launches.  The attribute belongs to the
+// current device; two threads that both find the bit clear both set the same value, which is harmless.
+template <class Kern>
+int allow_lds(Kern kern, std::atomic<uint64_t>& lds_set, const char* who) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+  const uint64_t bit = (dev >= 0 && dev < 64) ? (uint64_t)1 << dev : 0;       // (beyond 64 devices: every call)
+  if (!(lds_set.load(std::memory_order_acquire) & bit)) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    if (e != hipSuccess) return set_error((int)e, "%s: LDS %zu: %s", who, kLdsBytes, hipGetErrorString(e));
+    lds_set.fetch_or(bit, std::memory_order_release);
+  }
+  return 0;
+}
+
+// what the two chain entries check alike; 1: go on
+int check_chain(const char* who, bool nulls, const void* wres, int32_t nlayers, int32_t C, int32_t K, int32_t dtype) {
+  if (nulls) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+  if (C != kC || K != kTaps || dtype != SRWN_BF16)
+    return set_error(SRWN_E_UNSUPPORTED, "%s: built for 128 channels, K=2, bf16 (got C=%d K=%d dtype=%d)", who, C, K, dtype);
+  if (nlayers < 1 || nlayers > kMaxL)
+    return set_error(SRWN_E_SHAPE, "%s: %d layers, the kernel holds 1..%d", who, nlayers, kMaxL);
+  if (nlayers > 1 && !wres) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  return 1;
+}
+
+int finish_frames(const float* partials, void* means, int nseg, int64_t n, int32_t pool_stride, hipStream_t st) {
+  hipLaunchKernelGGL(nc_frame_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, partials, (bf16_t*)means,
+                     nseg, n, 1.0f / (float)pool_stride);
+  return check_launch("nc_frame_finish");
+}
+
 }  // namespace
 
 extern "C" int32_t srwn_nc_encode_max_layers(void) { return kMaxL; }
@@ -240,20 +327,20 @@ extern "C" int64_t srwn_nc_encode_partials(int32_t B, int32_t nframes, int32_t p
   return (int64_t)((pool_stride + kSeg - 1) / kSeg) * nlayers * B * nframes * kC;
 }
 
+extern "C" int64_t srwn_nc_encode_list_partials(int32_t nitems, int32_t pool_stride, int32_t nlayers) {
+  return srwn_nc_encode_partials(1, nitems, pool_stride, nlayers);
+}
+
 extern "C" int srwn_nc_encode_frames(const float* x, int64_t ld, const float* nc_w, const float* nc_b, const void* nc_wr,
                                      const float* nc_br, const void* wconv, int64_t wconv_stride, const void* wres,
                                      int64_t wres_stride, const float* bias_c, const float* bias_r, float* partials,
                                      void* means, int32_t B, int32_t nframes, int32_t pool_stride, int32_t valid_rows,
                                      int32_t nlayers, int32_t C, int32_t K, int32_t dtype, void* stream) {
+  const char* who = "nc_encode_frames";
   if (B == 0 || nframes == 0) return 0;
-  if (!x || !nc_w || !nc_b || !nc_wr || !nc_br || !wconv || !bias_c || !bias_r || !partials || !means)
-    return set_error(SRWN_E_NULL, "nc_encode_frames: null pointer");
-  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "nc_encode_frames: dtype %d", dtype);
-  if (C != kC || K != kTaps || dtype != SRWN_BF16)
-    return set_error(SRWN_E_UNSUPPORTED, "nc_encode_frames: built for 128 channels, K=2, bf16 (got C=%d K=%d dtype=%d)", C, K, dtype);
-  if (nlayers < 1 || nlayers > kMaxL)
-    return set_error(SRWN_E_SHAPE, "nc_encode_frames: %d layers, the kernel holds 1..%d", nlayers, kMaxL);
-  if (nlayers > 1 && !wres) return set_error(SRWN_E_NULL, "nc_encode_frames: null pointer");
+  int rc = check_chain(who, !x || !nc_w || !nc_b || !nc_wr || !nc_br || !wconv || !bias_c || !bias_r || !partials || !means,
+                       wres, nlayers, C, K, dtype);
+  if (rc != 1) return rc;
   if (B < 0 || nframes < 0 || B > 65535 || nframes > 65535 || pool_stride < 1 ||
       (int64_t)nframes * pool_stride + nlayers + 1 > 0x7fffffffLL)
     return set_error(SRWN_E_SHAPE, "nc_encode_frames: B=%d nframes=%d pool=%d", B, nframes, pool_stride);
@@ -269,24 +356,57 @@ extern "C" int srwn_nc_encode_frames(const float* x, int64_t ld, const float* nc
   a.bias_c = bias_c; a.bias_r = bias_r; a.parts = partials;
   a.L = nlayers; a.P = pool_stride; a.nframes = nframes; a.valid = valid_rows;
   hipStream_t st = (hipStream_t)stream;
-  // once per device: the attribute call is host time on a path of five launches.  The attribute belongs to the current
-  // device; two threads that both find the bit clear both set the same value, which is harmless.
   static std::atomic<uint64_t> lds_set{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  const uint64_t bit = (dev >= 0 && dev < 64) ? (uint64_t)1 << dev : 0;       // (beyond 64 devices: every call)
-  if (!(lds_set.load(std::memory_order_acquire) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)nc_encode_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)kLdsBytes);
-    if (e != hipSuccess) return set_error((int)e, "nc_encode_frames: LDS %zu: %s", kLdsBytes, hipGetErrorString(e));
-    lds_set.fetch_or(bit, std::memory_order_release);
-  }
-  hipLaunchKernelGGL(nc_encode_frames_kernel, dim3((unsigned)nseg, (unsigned)nframes, (unsigned)B), dim3(256), kLdsBytes,
-                     st, a);
-  int rc = check_launch("nc_encode_frames");
-  if (rc) return rc;
-  const int64_t n = (int64_t)nlayers * B * nframes * kC;
-  hipLaunchKernelGGL(nc_frame_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)partials,
-                     (bf16_t*)means, nseg, n, 1.0f / (float)pool_stride);
-  return check_launch("nc_frame_finish");
+  if ((rc = allow_lds(nc_encode_frames_kernel<NcEncArgs>, lds_set, who))) return rc;
+  hipLaunchKernelGGL(nc_encode_frames_kernel<NcEncArgs>, dim3((unsigned)nseg, (unsigned)nframes, (unsigned)B), dim3(256),
+                     kLdsBytes, st, a);
+  if ((rc = check_launch(who))) return rc;
+  return finish_frames(partials, means, nseg, (int64_t)nlayers * B * nframes * kC, pool_stride, st);
+}
+
+extern "C" int srwn_nc_encode_frame_list(const float* ring, int32_t ring_len, int32_t capacity, const SrwnEncFrame* frames,
+                                         int32_t nitems, const float* nc_w, const float* nc_b, const void* nc_wr,
+                                         const float* nc_br, const void* wconv, int64_t wconv_stride, const void* wres,
+                                         int64_t wres_stride, const float* bias_c, const float* bias_r, float* partials,
+                                         void* means, int32_t pool_stride, int32_t nlayers, int32_t C, int32_t K,
+                                         int32_t dtype, void* stream) {
+  const char* who = "nc_encode_frame_list";
+  if (nitems == 0) return 0;
+  int rc = check_chain(who, !ring || !frames || !nc_w || !nc_b || !nc_wr || !nc_br || !wconv || !bias_c || !bias_r ||
+                                !partials || !means, wres, nlayers, C, K, dtype);
+  if (rc != 1) return rc;
+  if (pool_stride < 1 || (pool_stride + kSeg - 1) / kSeg > 65535)
+    return set_error(SRWN_E_SHAPE, "nc_encode_frame_list: pool_stride %d", pool_stride);
+  if (nitems < 0 || nitems > 65535 || capacity < 1 || (int64_t)pool_stride + nlayers + 1 > 0x7fffffffLL ||
+      ring_len < pool_stride + nlayers + 1)
+    return set_error(SRWN_E_SHAPE, "nc_encode_frame_list: nitems=%d capacity=%d ring_len=%d (a frame reads %lld samples)",
+                     nitems, capacity, ring_len, (long long)pool_stride + nlayers + 1);
+  const int nseg = (pool_stride + kSeg - 1) / kSeg;
+  NcListArgs a;
+  a.x = ring; a.ld = ring_len; a.nc_w = nc_w; a.nc_b = nc_b; a.nc_wr = (const bf16_t*)nc_wr; a.nc_br = nc_br;
+  a.wconv = (const bf16_t*)wconv; a.wconv_stride = wconv_stride; a.wres = (const bf16_t*)wres; a.wres_stride = wres_stride;
+  a.bias_c = bias_c; a.bias_r = bias_r; a.parts = partials;
+  a.L = nlayers; a.P = pool_stride; a.nframes = 1; a.valid = 0;
+  a.items = frames; a.ring_len = ring_len; a.capacity = capacity;
+  hipStream_t st = (hipStream_t)stream;
+  static std::atomic<uint64_t> lds_set{0};
+  if ((rc = allow_lds(nc_encode_frames_kernel<NcListArgs>, lds_set, who))) return rc;
+  hipLaunchKernelGGL(nc_encode_frames_kernel<NcListArgs>, dim3((unsigned)nseg, (unsigned)nitems), dim3(256), kLdsBytes, st,
+                     a);
+  if ((rc = check_launch(who))) return rc;
+  return finish_frames(partials, means, nseg, (int64_t)nlayers * nitems * kC, pool_stride, st);
+}
+
+extern "C" int srwn_audio_ring_put(float* ring, int32_t ring_len, int32_t capacity, const float* src,
+                                   const int32_t* streams, const int32_t* src_offset, const int32_t* first_col,
+                                   const int32_t* counts, int32_t n, int32_t max_count, void* stream) {
+  if (n == 0 || max_count == 0) return 0;
+  if (!ring || !src || !streams || !src_offset || !first_col || !counts)
+    return set_error(SRWN_E_NULL, "audio_ring_put: null pointer");
+  if (ring_len < 1 || capacity < 1 || n < 0 || n > 65535 || max_count < 0 || max_count > ring_len)
+    return set_error(SRWN_E_SHAPE, "audio_ring_put: ring_len=%d capacity=%d n=%d max_count=%d", ring_len, capacity, n,
+                     max_count);
+  hipLaunchKernelGGL(audio_ring_put_kernel, dim3((unsigned)((max_count + 255) / 256), (unsigned)n), dim3(256), 0,
+                     (hipStream_t)stream, ring, ring_len, capacity, src, streams, src_offset, first_col, counts, max_count);
+  return check_launch("audio_ring_put");
 }

@@ -65,6 +65,38 @@ def plan_frames(received: int, emitted: int, nlayers: int, pool_stride: int, fin
     return out
 
 
+def plan_pool(received, emitted, final, active, nlayers, pool_stride, max_rows, limit=None):
+    """One step of an encoder POOL: which frames of which slots are encoded now, as launches of frames of any streams.
+
+    Slot u holds a stream of its own with ``received[u]`` samples in, ``emitted[u]`` frames out and ``final[u]`` once no
+    more audio comes.  A frame is due by ``plan_frames``' rule -- running: (f+1)*P + L + 1 <= received, final: every whole
+    frame -- and ``limit[u]`` (a sequence or a dict; None or a missing slot: no cap) caps the frames a slot emits this
+    step: the back-pressure of a consumer with a bounded ring, under which the frames held back simply stay audio.
+    Returns the launches, each a list of ``(slot, frame, first_sample, valid)`` ordered by slot, then frame (one slot's
+    frames are neighbouring rows), at most ``max_rows`` items each; ``first_sample = frame * P`` and ``valid =
+    min(received - frame * P, P + L + 1)`` real samples from there on.  Pure Python: the CPU tests drive the fp64 oracle
+    with it."""
+    L, P, max_rows = int(nlayers), int(pool_stride), int(max_rows)
+    n = len(received)
+    if L < 0 or P < 1 or max_rows < 1 or not (len(emitted) == len(final) == len(active) == n):
+        raise ValueError("plan_pool: nlayers=%d pool_stride=%d max_rows=%d over %d slots" % (L, P, max_rows, n))
+    items = []
+    for u in range(n):
+        if not active[u]:
+            continue
+        r, e = int(received[u]), int(emitted[u])
+        if r < 0 or e < 0 or e * P > r:
+            raise ValueError("plan_pool: slot %d received=%d emitted=%d" % (u, r, e))
+        due = r // P if final[u] else max(0, (r - L - 1) // P)
+        cap = None if limit is None else (limit.get(u) if isinstance(limit, dict) else limit[u])
+        if cap is not None:
+            if int(cap) < 0:
+                raise ValueError("plan_pool: limit %d for slot %d" % (int(cap), u))
+            due = min(due, e + int(cap))
+        items.extend((u, f, f * P, min(r - f * P, P + L + 1)) for f in range(e, due))
+    return [items[i:i + max_rows] for i in range(0, len(items), max_rows)]
+
+
 class _EncoderParams:
     """The encoder's flat fp32 parameter buffer by section, its initialisation and the reference's variable names:
     what ``EncoderStack`` (training) and ``EncoderWeights`` (inference) share.  Needs self.L/EC/S/Kw/lat/dev."""
@@ -698,3 +730,220 @@ class FrameEncoder:
         st.emitted, st.closed = emitted, True
         st.tail = st.tail[:, :0]
         return out
+
+    def pool(self, audio_ring: Optional[int] = None, max_rows: Optional[int] = None) -> "EncoderPool":
+        """An ``EncoderPool`` on this encoder's buffers: its ``max_batch`` rows as slots, each a stream at a clock of its
+        own.  audio_ring: samples a slot can hold (>= pool_stride + L + 1; default max_frames * pool_stride + L + 1 +
+        pool_stride); max_rows: frames per launch (default, and at most, max_batch * max_frames)."""
+        return EncoderPool(self, audio_ring, max_rows)
+
+
+class EncoderPool:
+    """``FrameEncoder.pool()``: the encoder's ``max_batch`` rows as SLOTS, each holding a stream with its own samples
+    received, frames emitted and end.  Streams ``join`` free slots, ``push`` audio of any length whenever it arrives (one
+    upload and one srwn_audio_ring_put however many slots are written; a slot's audio lives in its row of a device ring,
+    sample s in column s mod audio_ring, and nothing is re-allocated), ``step`` encodes every frame that is due -- of
+    every slot, as launches over a LIST of frames (``plan_pool``; srwn_nc_encode_frame_list on the fused path, the same
+    plan gathered into windows and run layer by layer otherwise) -- and a stream that was ``finish``ed frees its slot
+    with its last frame.  A stream's frames put together equal ``FrameEncoder.encode`` of its audio alone, bit for bit:
+    in any slot, whenever it joined, however its audio was cut and whatever the other slots hold.  A frame reads its own
+    ``valid`` samples counted from its first one, so what an earlier stream left in a slot's ring is never read."""
+
+    def __init__(self, owner: FrameEncoder, audio_ring: Optional[int] = None, max_rows: Optional[int] = None):
+        fe = self.fe = owner
+        self.P, self.L, self.lat, self.capacity = fe.P, fe.L, fe.lat, fe.max_batch
+        self.window = self.P + self.L + 1                                  # the samples one frame reads
+        rows = fe.max_batch * fe.max_frames
+        self.audio_ring = fe.max_frames * self.P + self.L + 1 + self.P if audio_ring is None else int(audio_ring)
+        self.max_rows = rows if max_rows is None else int(max_rows)
+        if self.audio_ring < self.window:
+            raise ValueError("pool: audio_ring %d holds less than one frame's pool_stride + L + 1 = %d samples"
+                             % (self.audio_ring, self.window))
+        if not 1 <= self.max_rows <= rows:
+            raise ValueError("pool: max_rows %d: 1..max_batch * max_frames = %d" % (self.max_rows, rows))
+        if self.capacity * self.audio_ring + 4 * self.capacity > 0x7fffffff:
+            raise ValueError("pool: %d slots of %d samples" % (self.capacity, self.audio_ring))
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        cap, dev = self.capacity, fe.w.dev
+        self._received = np.zeros(cap, np.int64)
+        self._emitted = np.zeros(cap, np.int64)
+        self._final = np.zeros(cap, bool)
+        self._active = np.zeros(cap, bool)
+        self.ring = torch.zeros((cap, self.audio_ring), dtype=torch.float32, device=dev)
+        # one upload per push: [streams | src_offset | first_col | counts] (n each) and the concatenated audio behind them
+        self.stage = torch.zeros(4 * cap + cap * self.audio_ring, dtype=torch.int32, device=dev)
+        self.table = torch.zeros((self.max_rows, 4), dtype=torch.int32, device=dev)      # SrwnEncFrame per item
+
+    # ---- inspection
+    @property
+    def active(self):
+        return [int(u) for u in np.flatnonzero(self._active)]
+
+    @property
+    def free(self):
+        return [int(u) for u in np.flatnonzero(~self._active)]
+
+    @property
+    def received(self) -> np.ndarray:
+        """Samples pushed into each slot's stream so far."""
+        return self._received.copy()
+
+    @property
+    def emitted(self) -> np.ndarray:
+        """Frames each slot's stream has emitted so far."""
+        return self._emitted.copy()
+
+    def _slot_list(self, slots, who):
+        slots = [int(u) for u in (slots if np.ndim(slots) else [slots])]
+        if any(u < 0 or u >= self.capacity for u in slots):
+            raise ValueError("%s: slots %s outside the pool's %d" % (who, slots, self.capacity))
+        if len(set(slots)) != len(slots):
+            raise ValueError("%s: slots %s are not distinct" % (who, slots))
+        return slots
+
+    def audio_room(self, slot: int) -> int:
+        """Samples a slot can take now: audio_ring minus what it holds beyond its emitted frames."""
+        u, = self._slot_list(slot, "audio_room")
+        return int(self.audio_ring - (self._received[u] - self._emitted[u] * self.P))
+
+    # ---- streams come and go
+    def join(self, n: int = 1, slots=None):
+        """n streams into free slots (the lowest ones, or `slots`); returns the slots.  A slot starts at sample 0."""
+        free = self.free
+        if slots is None:
+            if int(n) < 1 or int(n) > len(free):
+                raise ValueError("join: %d streams but %d free slots" % (int(n), len(free)))
+            slots = free[:int(n)]
+        else:
+            slots = self._slot_list(slots, "join")
+            if not slots or any(self._active[u] for u in slots):
+                raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
+        for u in slots:
+            self._received[u] = self._emitted[u] = 0
+            self._final[u], self._active[u] = False, True
+        return list(slots)
+
+    def leave(self, slots) -> None:
+        """Ends the streams in `slots` where they are (a slot already free stays free) and frees their slots."""
+        for u in self._slot_list(slots, "leave"):
+            self._active[u] = False
+
+    def finish(self, slots) -> None:
+        """No more audio comes for these streams: their remaining whole frames are due with the clip-end padding, and each
+        frees its slot with its last frame (at the next ``step``)."""
+        slots = self._slot_list(slots, "finish")
+        if any(not self._active[u] for u in slots):
+            raise ValueError("finish: slots %s do not all hold a stream" % (slots,))
+        for u in slots:
+            self._final[u] = True
+
+    def push(self, slots, audio) -> None:
+        """audio[i], 1-D of any length (0 too), behind what slots[i] has received.  Refuses (ValueError, nothing changed) a
+        slot that holds no stream or was finished, more than ``audio_room(slot)`` samples and audio that is not floating
+        point.  One host-to-device copy and one srwn_audio_ring_put, whatever the number of slots."""
+        one = not np.ndim(slots)
+        slots = self._slot_list(slots, "push")
+        if one or isinstance(audio, (np.ndarray, torch.Tensor)):
+            audio = [audio]
+        audio = list(audio)
+        if len(audio) != len(slots):
+            raise ValueError("push: %d slots but %d pieces of audio" % (len(slots), len(audio)))
+        xs = []
+        for u, x in zip(slots, audio):
+            if isinstance(x, torch.Tensor):
+                if not x.is_floating_point():
+                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
+                x = x.detach().to("cpu", torch.float32).numpy()
+            else:
+                x = np.asarray(x)
+                if x.dtype.kind != "f":
+                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
+                x = x.astype(np.float32, copy=False)
+            if x.ndim != 1:
+                raise ValueError("push: the audio of a slot is 1-D [samples], got shape %s" % (x.shape,))
+            if not self._active[u]:
+                raise ValueError("push: slot %d holds no stream" % u)
+            if self._final[u]:
+                raise ValueError("push: the stream in slot %d was finished" % u)
+            if x.shape[0] > self.audio_room(u):
+                raise ValueError("push: %d samples for slot %d, but its ring of %d has room for %d (received %d, emitted "
+                                 "%d frames)" % (x.shape[0], u, self.audio_ring, self.audio_room(u), self._received[u],
+                                                 self._emitted[u]))
+            xs.append(x)
+        pairs = [(u, x) for u, x in zip(slots, xs) if x.shape[0] > 0]
+        if not pairs:
+            return
+        n = len(pairs)
+        counts = np.asarray([x.shape[0] for _, x in pairs], np.int64)
+        us = np.asarray([u for u, _ in pairs], np.int64)
+        total = int(counts.sum())
+        host = np.empty(4 * n + total, np.int32)
+        host[0:n] = us
+        host[n:2 * n] = np.cumsum(counts) - counts
+        host[2 * n:3 * n] = self._received[us] % self.audio_ring
+        host[3 * n:4 * n] = counts
+        host[4 * n:].view(np.float32)[:] = np.concatenate([x for _, x in pairs])
+        self.stage[:host.shape[0]].copy_(torch.from_numpy(host))
+        sp = self.stage.data_ptr()
+        call("srwn_audio_ring_put", self.ring.data_ptr(), self.audio_ring, self.capacity, sp + 16 * n, sp, sp + 4 * n,
+             sp + 8 * n, sp + 12 * n, n, int(counts.max()), K._stream())
+        self._received[us] += counts
+
+    # ---- one step: every frame that is due
+    def _launch(self, items) -> torch.Tensor:
+        """The frames of one launch of ``plan_pool`` -> [len(items), latent] fp32 (a copy)."""
+        fe, w, n = self.fe, self.fe.w, len(items)
+        tab = np.zeros((n, 4), np.int32)
+        tab[:, 0] = [it[0] for it in items]
+        tab[:, 1] = [it[2] % self.audio_ring for it in items]
+        tab[:, 2] = [it[3] for it in items]
+        if not fe.fused:
+            return self._launch_windows(tab)
+        self.table[:n].copy_(torch.from_numpy(tab))
+        EC, S, L, dt, st, v = w.EC, w.S, self.L, K.abi_dtype(w.dt), K._stream(), w.view
+        call("srwn_nc_encode_frame_list", self.ring.data_ptr(), self.audio_ring, self.capacity, self.table.data_ptr(), n,
+             v("nc_w").data_ptr(), v("nc_b").data_ptr(), w.wptr(w.o_nc_wr_p), v("nc_br").data_ptr(), w.wptr(w.o_conv[0]),
+             w.layer_stride, w.wptr(w.o_wr_p[0]), w.layer_stride, v("EB").data_ptr(), v("EBR").data_ptr(),
+             fe.parts.data_ptr(), fe.a_mean.data_ptr(), self.P, L, EC, w.Kw, dt, st)
+        call("srwn_pw_linear_ksplit", fe.a_mean.data_ptr(), EC, n * EC, EC, L * EC, w.wptr(w.o_ws), w.bs_sum.data_ptr(),
+             fe.s_parts.data_ptr(), S, S, S, n, L, dt, st)
+        K.reduce_partials(fe.s_parts, L, n * S, 1, True, 1.0, fe.s_mean.data_ptr(), 0)
+        call("srwn_small_gemm", fe.s_mean.data_ptr(), S, S, 0, K.F32, v("lat_w").data_ptr(), self.lat, 1, S, 0,
+             v("lat_b").data_ptr(), fe.enc.data_ptr(), self.lat, K.F32, n, self.lat, S, 0, st)
+        return fe.enc[:n * self.lat].view(n, self.lat).clone()
+
+    def _launch_windows(self, tab) -> torch.Tensor:
+        """The layer-by-layer encoders (fp32, SRWN_ENC_FUSED=0, more than 32 layers) on the same plan: the items' windows
+        gathered from the ring, grouped by `valid`, each group a batch of one-frame windows through ``FrameEncoder._run``."""
+        fe, dev = self.fe, self.fe.w.dev
+        out = torch.zeros((tab.shape[0], self.lat), dtype=torch.float32, device=dev)
+        gmax = max(1, min(fe.max_batch * fe.max_frames, (fe.max_batch * fe.wmax) // self.window))
+        for valid in sorted(set(int(x) for x in tab[:, 2])):
+            idx = np.flatnonzero(tab[:, 2] == valid)
+            for g0 in range(0, len(idx), gmax):
+                g = idx[g0:g0 + gmax]
+                cols = (tab[g, 1].astype(np.int64)[:, None] + np.arange(valid)[None, :]) % self.audio_ring
+                x = self.ring[torch.from_numpy(tab[g, 0].astype(np.int64)).to(dev)[:, None], torch.from_numpy(cols).to(dev)]
+                out[torch.from_numpy(g).to(dev)] = fe._run(x.contiguous(), 1, valid)[:, 0]
+        return out
+
+    def step(self, limit=None):
+        """Every frame that is due now (``plan_pool``; limit: frames per slot at most, a sequence or a dict) -> {slot:
+        frames [k, latent] fp32 on the device} for the slots with k > 0.  A finished slot whose frames are all out becomes
+        free.  With nothing due nothing is launched."""
+        launches = plan_pool(self._received, self._emitted, self._final, self._active, self.L, self.P, self.max_rows, limit)
+        pieces = {}
+        for items in launches:
+            out = self._launch(items)
+            i = 0
+            while i < len(items):
+                j = i
+                while j < len(items) and items[j][0] == items[i][0]:
+                    j += 1
+                pieces.setdefault(items[i][0], []).append(out[i:j])
+                self._emitted[items[i][0]] += j - i
+                i = j
+        done = self._active & self._final & ((self._emitted + 1) * self.P > self._received)
+        self._active[done] = False
+        return {u: (p[0] if len(p) == 1 else torch.cat(p, dim=0)) for u, p in pieces.items()}

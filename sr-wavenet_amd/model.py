@@ -835,6 +835,14 @@ class AudioEncoder(object):
             raise ValueError("batch_size %r: this encoder was built for max_batch=%d" % (batch_size, self.max_batch))
         return EncoderStream(self, int(batch_size))
 
+    def pool(self, audio_ring=None, max_rows=None):
+        """An ``AudioEncoderPool``: this encoder's ``max_batch`` rows as slots that streams join and leave, each pushing
+        audio of any length at a clock of its own (``encoder.EncoderPool``).  audio_ring: samples a slot can hold
+        (default max_frames * pool_stride + num_layers + 1 + pool_stride); max_rows: frames per launch."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        return AudioEncoderPool(self._eng.pool(audio_ring, max_rows))
+
 
 class EncoderStream(object):
     """NumPy face of one running batch of encoder streams (``AudioEncoder.stream``).  ``t``: samples received per
@@ -861,6 +869,42 @@ class EncoderStream(object):
 
     def finish(self):
         return self._owner._eng.finish(self._st).cpu().numpy()
+
+
+class AudioEncoderPool(object):
+    """NumPy face of an encoder pool (``AudioEncoder.pool``; encoder.EncoderPool).  ``join`` returns slots,
+    ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``finish(slots)`` ends streams, ``step()`` returns
+    ``{slot: frames [k, latent]}`` for every slot with new frames and frees the finished slots whose frames are all out.
+    A stream's frames put together are ``AudioEncoder.encode`` of its audio alone."""
+
+    def __init__(self, pool):
+        self._pool = pool
+
+    capacity = property(lambda self: self._pool.capacity)
+    active = property(lambda self: self._pool.active)
+    free = property(lambda self: self._pool.free)
+    received = property(lambda self: self._pool.received)
+    emitted = property(lambda self: self._pool.emitted)
+
+    def audio_room(self, slot):
+        return self._pool.audio_room(int(slot))
+
+    def join(self, n=1, slots=None):
+        return self._pool.join(n, slots)
+
+    def push(self, slots, audio):
+        one = np.isscalar(slots) or (isinstance(audio, np.ndarray) and audio.dtype != object and audio.ndim == 1)
+        audio = [audio] if one else list(audio)
+        self._pool.push([int(slots)] if np.isscalar(slots) else slots, [np.asarray(a) for a in audio])
+
+    def finish(self, slots):
+        self._pool.finish(slots)
+
+    def leave(self, slots):
+        self._pool.leave(slots)
+
+    def step(self, limit=None):
+        return {u: f.cpu().numpy() for u, f in self._pool.step(limit).items()}
 
 
 class ParallelWaveNet(object):
@@ -1355,6 +1399,14 @@ class Resynthesizer(object):
             raise ValueError("chunk_size %d: 1..max_chunk = %d" % (chunk_size, self.synthesizer.max_chunk))
         return ResynthesisStream(self, batch, conditions, seed, temperature, chunk_size)
 
+    def pool(self, chunk_size=160, audio_ring=None):
+        """A ``ResynthesisPool``: independent callers on one encoder and one synthesizer.  Streams join and leave while the
+        batch runs, audio arrives ragged, and each caller receives what it would have received alone.  chunk_size: the
+        samples a ``step`` makes per stream at most; audio_ring: samples of audio a slot can hold (``AudioEncoder.pool``)."""
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        return ResynthesisPool(self, int(chunk_size), audio_ring)
+
 
 class ResynthesisStream(object):
     """One running batch of ``Resynthesizer.stream``.  ``t``: samples returned so far per stream; ``received``: samples
@@ -1409,6 +1461,120 @@ class ResynthesisStream(object):
         outs = []
         self._drain(self._owner.encoder._eng.finish(self._enc), outs)
         return self._result(outs)
+
+
+class ResynthesisPool(object):
+    """``Resynthesizer.pool()``: an encoder pool and a live synthesis pool sharing slot ids; capacity is the smaller
+    ``max_batch``.  ``join`` returns slots, ``push(slots, audio)`` takes one 1-D array per slot of any length (at most
+    ``audio_room(slot)``), ``finish(slots)`` ends streams, ``step()`` returns ``{slot: samples}``.  One step: the encoder
+    emits for each slot at most the frames the synthesizer's conditioning ring has room for (the rest stays audio in the
+    slot's audio ring: there is no second queue), the new frames are fed as device tensors with the slot's conditions
+    tiled on, the slots whose audio is finished and fully encoded are closed, and the synthesizer makes up to
+    ``chunk_size`` samples per slot.  A stream that reaches its end frees its slot in both halves.  A stream's samples
+    put together are ``synthesizer.synthesize(encoder.encode(audio), conditions, seed, temperature)`` of it alone."""
+
+    def __init__(self, owner, chunk_size, audio_ring):
+        from .student import live_min_frames
+        enc, syn = owner.encoder, owner.synthesizer
+        if not 1 <= chunk_size <= syn.max_chunk:
+            raise ValueError("chunk_size %d: 1..max_chunk = %d" % (chunk_size, syn.max_chunk))
+        need = live_min_frames(max(syn._eng.hist), owner.pool_stride)
+        if syn.max_frames < need:
+            raise ValueError("pool: live streams need a synthesizer ring of max_frames >= %d frames, this one holds %d"
+                             % (need, syn.max_frames))
+        self._owner, self._chunk = owner, chunk_size
+        self.capacity = min(enc.max_batch, syn.max_batch)
+        self._cs = syn.condition_size
+        self._enc = enc._eng.pool(audio_ring)
+        self._syn = syn._eng.pool()
+        self._cond = {}        # slot -> its stream's conditions [1, condition_size] on the device (None without)
+
+    @property
+    def active(self):
+        return sorted(self._cond)
+
+    @property
+    def free(self):
+        return [u for u in range(self.capacity) if u not in self._cond]
+
+    @property
+    def t(self):
+        """Samples returned so far, per slot."""
+        return self._syn.t[:self.capacity]
+
+    @property
+    def received(self):
+        return self._enc.received[:self.capacity]
+
+    def audio_room(self, slot):
+        return self._enc.audio_room(int(slot))
+
+    def _slots(self, slots, who):
+        slots = [int(slots)] if np.isscalar(slots) else [int(u) for u in slots]
+        if any(u not in self._cond for u in slots):
+            raise ValueError("%s: slots %s do not all hold a stream of this pool" % (who, slots))
+        return slots
+
+    def join(self, conditions=None, seed=0, temperature=None, n=1):
+        """n streams into the lowest free slots; conditions [n, condition_size] (one row per stream), seed a scalar s
+        (stream i draws with s + i) or one per stream, temperature None, a scalar or one per stream.  Returns the slots."""
+        n = int(n)
+        free = self.free
+        if n < 1 or n > len(free):
+            raise ValueError("join: %d streams but %d free slots" % (n, len(free)))
+        conds = [None] * n
+        if self._cs > 0:
+            if conditions is None:
+                raise ValueError("this student was built with condition_size > 0; pass conditions [n, condition_size]")
+            c = np.asarray(conditions, dtype=np.float32)
+            if c.shape != (n, self._cs):
+                raise ValueError("conditions must be [%d, %d]" % (n, self._cs))
+            conds = [torch.as_tensor(c[i:i + 1]).to("cuda") for i in range(n)]
+        slots = free[:n]
+        self._syn.join([None] * n, seed, temperature, slots=slots, live=True)
+        self._enc.join(slots=slots)
+        for u, c in zip(slots, conds):
+            self._cond[u] = c
+        return slots
+
+    def push(self, slots, audio):
+        one = np.isscalar(slots) or (isinstance(audio, np.ndarray) and audio.dtype != object and audio.ndim == 1)
+        audio = [audio] if one else list(audio)
+        self._enc.push(self._slots(slots, "push"), [np.asarray(a) for a in audio])
+
+    def finish(self, slots):
+        """No more audio comes for these streams; each frees its slot once its last sample has been returned."""
+        self._enc.finish(self._slots(slots, "finish"))
+
+    def leave(self, slots):
+        """Ends these streams where they are and frees their slots in both halves."""
+        slots = self._slots(slots, "leave")
+        self._enc.leave(slots)
+        self._syn.leave(slots)
+        for u in slots:
+            del self._cond[u]
+
+    def step(self):
+        if not self._cond:
+            return {}
+        enc, syn = self._enc, self._syn
+        frames = enc.step({u: syn.room(u) for u in enc.active})
+        if frames:
+            us = sorted(frames)
+            fr = [frames[u] if self._cond[u] is None else
+                  torch.cat([frames[u], self._cond[u].expand(frames[u].shape[0], -1)], dim=1) for u in us]   # model.py:496-499
+            syn.feed(us, fr)
+        done = [u for u in self._cond if not enc._active[u]]          # finished and fully encoded: the stream's end is known
+        if done:
+            syn.close(done)
+        a, ran = syn.step(self._chunk)
+        out = {}
+        if ran.any():
+            a = a.cpu().numpy()
+            out = {u: a[u, :int(ran[u])] for u in self._cond if ran[u] > 0}
+        for u in [u for u in self._cond if not syn._active[u]]:
+            del self._cond[u]
+        return out
 
 
 class SiameseWaveNet(_EngineOwner):
