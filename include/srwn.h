@@ -913,6 +913,48 @@ int srwn_cond_ring_feed(const void* x, int64_t x_row_stride, int64_t x_stream_ro
                         const int32_t* streams, const int64_t* first_frame, const int32_t* counts, int32_t n,
                         int32_t max_k, int32_t dtype, void* stream);
 
+/* ---- live autoregressive decoding (since srwn_version() 112): the conditioned mixture-of-logistics decoder of
+ * srwn_generate_mol_resume_sampled / srwn_generate16_mol_resume_sampled over a conditioning table that is a RING, so that
+ * the encoder's frames can be fed while the decoder runs and a stream is not bounded by the table it started with.  The
+ * two *_live_sampled entry points take the arguments of their *_mol_resume_sampled twins; `cond` is required and
+ * cond_frames is the ring length: the table is [B * cond_frames, cond_ld] (the layout of the twins), and frame q = t /
+ * pool_stride of stream u is looked up in row u * cond_frames + q mod cond_frames (the twins: min(q, cond_frames - 1)).
+ * A step reads the row of its own frame only, so after `fed` frames a run at step t has room for
+ *     cond_frames - fed + t / pool_stride
+ * more (no history term: nothing older than the current frame is read again).  The latency body requests layer 0's
+ * operands of step t + 1 during step t; after a launch's last step that row may belong to a frame not fed yet: the ring
+ * lookup keeps it inside the table and its value is never used (the next launch requests it again).  Neither body reads
+ * ahead otherwise.  Every other argument, the carry, the rings and the random draws are the twins': a live run over a
+ * ring returns the bits of the twin over the whole table.  Kernels of their own; the twins' launches run the code they
+ * ran before.  Errors before any launch: a null cond (-3); cond_frames < 1, pool_stride < 1, cond_ld < nlayers * R
+ * (latency body: or not a multiple of 4) (-2); then the twins' checks.
+ *
+ *   srwn_cond_ring_scatter   the feed: rows [B * k, rows_ld] (dtype; row u * k + j = the conditioning biases of all
+ *                                layers, srwn_pw_linear's output, of new frame first_frame + j of stream u) -> row
+ *                                u * cond_frames + (first_frame + j) mod cond_frames of table [B * cond_frames, cond_ld];
+ *                                `width` elements per row in 16-byte vectors.  One launch however many streams.  Errors
+ *                                before any launch: a null pointer (-3); k > cond_frames, cond_frames < 1, first_frame <
+ *                                0, a width, leading dimension or address that is not a whole number of vectors, width
+ *                                beyond a leading dimension (-2); an unknown dtype (-1).  B = 0 or k = 0: nothing (0). */
+int srwn_generate_mol_live_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2, const float*
+                                   bias_f, const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                   const float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                   codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                   int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
+                                   int32_t K, int32_t num_mixtures, const void* cond, int32_t cond_frames, int32_t
+                                   pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed, int32_t dtype, void*
+                                   stream, int32_t t0, float* carry, const SrwnGenSampling* sampling);
+int srwn_generate16_mol_live_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const
+                                     float* bias_r, const float* bs_sum, const float* b1, const float* b2, const
+                                     float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                     codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                     int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t S,
+                                     int32_t num_mixtures, const void* cond, int32_t cond_frames, int32_t
+                                     pool_stride, int64_t cond_ld, int32_t mode, uint64_t seed, void* stream,
+                                     int32_t t0, float* carry, const SrwnGenSampling* sampling);
+int srwn_cond_ring_scatter(const void* rows, int64_t rows_ld, void* table, int64_t cond_ld, int32_t B, int32_t k,
+                               int64_t first_frame, int32_t cond_frames, int32_t width, int32_t dtype, void* stream);
+
 /* ---- data gradient of _DilatedCausalConv1d (ops.py:6-10) wrt a narrow input (the 1-channel flow input,
  * model.py:423-424); `shift` is the adjoint of RightShift (ops.py:78-80):
  *   dx[b,u,i] (+)= scale * sum_k sum_o w[k,i,o] * dy[b, u + shift + (K-1-k)*dilation, o]   (0 beyond the clip)

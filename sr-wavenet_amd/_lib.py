@@ -230,6 +230,12 @@ SIGNATURES = {
 for _n in SAMPLED:
     SIGNATURES[_n + "_sampled"] = (SIGNATURES[_n][0], SIGNATURES[_n][1] + [_p])
 del _n
+# live autoregressive decoding (srwn_version() 112): the *_mol_resume_sampled twins over a ring conditioning table, and the
+# feed's scatter of projected frames into it
+for _n in ("srwn_generate", "srwn_generate16"):
+    SIGNATURES[_n + "_mol_live_sampled"] = SIGNATURES[_n + "_mol_resume_sampled"]
+del _n
+SIGNATURES["srwn_cond_ring_scatter"] = (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

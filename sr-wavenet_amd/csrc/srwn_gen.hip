@@ -79,7 +79,9 @@ __device__ __forceinline__ void gen_carry_out(float* carry, const float* forced,
 template <typename T, int RT> struct GenCond { f32x4 cc[RT][4]; };
 struct GenNoCond {};
 
-template <typename T, int NBUF, bool COND, int RT, int SS, bool SLOTS = false, bool SAMP = false>
+// RING (the live form, srwn.h: srwn_generate_mol_live_sampled): the conditioning table is a ring of cond_frames rows per
+// utterance that the caller keeps feeding; instantiations of their own, so that every other launch keeps its code
+template <typename T, int NBUF, bool COND, int RT, int SS, bool SLOTS = false, bool SAMP = false, bool RING = false>
 __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS, SAMP>::type a) {
   constexpr int R = 32 * RT, KS = R / 16, S = SS, SQ = S / 4;   // SQ: skip/head-1 channels per wave
   constexpr int MQ = SQ / 32;                                    // ... = MQ 32-row tiles per wave
@@ -185,6 +187,10 @@ __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS,
     if constexpr (COND) {   // cb_l of the current frame (accumulator layout); the ring holds conditioned inputs
       int fc = min(t / a.pool, a.cond_frames - 1);
       if constexpr (SLOTS) fc = sl[128 + col];   // the slot's own frame at step t (one division per step, not per layer)
+      // the live form: frame q sits in row q mod cond_frames.  Every preload of this body is issued for the step that is
+      // running (the `t` above is the step loop's, also for the sets filled two layers ahead), so no lookup reads a frame
+      // ahead of the step: the row is always one the caller has fed
+      if constexpr (RING) fc = (t / a.pool) % a.cond_frames;
       const T* ccp = condp + ((size_t)ucl * a.cond_frames + fc) * a.cond_ld + (size_t)l * R + 4 * half;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt)
@@ -507,7 +513,7 @@ extern "C" int64_t srwn_generate_ring_elems(const int32_t* dilations, int32_t nl
   return gen_ring_layout(dilations, nlayers, R, INT32_MAX, &bad);   // per group of 32 utterances
 }
 
-template <bool SL, bool SA, typename A>
+template <bool SL, bool SA, bool RG = false, typename A>
 static int generate_launch(A& a, int R, int S, bool cond, int dtype, int nlayers, unsigned groups, hipStream_t st) {
   const size_t lfr = (size_t)(R / 32) * 3 * (R / 16);   // fragment images per layer: conv RT x 2KS + residual RT x KS
   const size_t slot_lds = (SL ? 5 * 32 * 4 : 0) + (SA ? 4 * 32 * 4 : 0);   // the per-slot table, the sampling controls
@@ -517,15 +523,22 @@ static int generate_launch(A& a, int R, int S, bool cond, int dtype, int nlayers
    : (R == 32 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 1, 256, SL, SA> : generate_kernel<TT, NB, false, 1, 256, SL, SA>) \
    : (R == 32 && S == 128) ? (cond ? generate_kernel<TT, NB, true, 1, 128, SL, SA> : generate_kernel<TT, NB, false, 1, 128, SL, SA>) \
                            : (cond ? generate_kernel<TT, NB, true, 2, 128, SL, SA> : generate_kernel<TT, NB, false, 2, 128, SL, SA>))
+  // the live form is conditioned and has no slots: its own instantiation of every width
+#define SRWN_GEN_PICK_RING(TT, NB)                                                                \
+  ((R == 64 && S == 256) ? generate_kernel<TT, NB, true, 2, 256, false, SA, true>                 \
+   : (R == 32 && S == 256) ? generate_kernel<TT, NB, true, 1, 256, false, SA, true>               \
+   : (R == 32 && S == 128) ? generate_kernel<TT, NB, true, 1, 128, false, SA, true>               \
+                           : generate_kernel<TT, NB, true, 2, 128, false, SA, true>)
+#define SRWN_GEN_KFN(TT, NB) [&] { if constexpr (RG) return SRWN_GEN_PICK_RING(TT, NB); else return SRWN_GEN_PICK(TT, NB); }()
   if (dtype == SRWN_BF16) {
-    auto kfn = SRWN_GEN_PICK(bf16_t, 2);
+    auto kfn = SRWN_GEN_KFN(bf16_t, 2);
     const size_t sh = 2 * lfr * sizeof(Frag<bf16_t>) * 64 + 32 * S * sizeof(bf16_t) + 32 * 256 * 4 + 64 * 4 +
                       (size_t)(2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4 + slot_lds;
     hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
     if (e != hipSuccess) return set_error((int)e, "generate: LDS %zu: %s", sh, hipGetErrorString(e));
     hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, st, a);
   } else if (dtype == SRWN_F32) {
-    auto kfn = SRWN_GEN_PICK(float, 1);
+    auto kfn = SRWN_GEN_KFN(float, 1);
     const size_t sh = 1 * lfr * sizeof(Frag<float>) * 64 + 32 * S * sizeof(float) + 32 * 256 * 4 + 64 * 4 +
                       (size_t)(2 * nlayers * R + 2 * S + 256 + 3 * R + 256) * 4 + slot_lds;
     hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
@@ -534,6 +547,8 @@ static int generate_launch(A& a, int R, int S, bool cond, int dtype, int nlayers
   } else {
     return set_error(SRWN_E_DTYPE, "generate: dtype %d", dtype);
   }
+#undef SRWN_GEN_KFN
+#undef SRWN_GEN_PICK_RING
 #undef SRWN_GEN_PICK
   return check_launch("generate");
 }
@@ -545,7 +560,8 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
                          int32_t Tout, int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t K, int32_t mode,
                          uint64_t seed, int32_t dtype, void* stream, const void* cond, int32_t cond_frames,
                          int32_t pool, int64_t cond_ld, int32_t M, int32_t t0, float* carry,
-                         const SrwnGenSampling* sampling, SrwnGenSlot* slots = nullptr, bool slot_form = false) {
+                         const SrwnGenSampling* sampling, SrwnGenSlot* slots = nullptr, bool slot_form = false,
+                         bool ring_form = false) {
   // the mixture-of-logistics head (M > 0): its conditioning, checked before anything else as its entry points always did
   if (M > 0 && cond && (cond_frames < 1 || pool < 1 || cond_ld < (int64_t)nlayers * R))
     return set_error(SRWN_E_SHAPE, "%s: cond_frames=%d pool_stride=%d cond_ld=%lld",
@@ -589,8 +605,10 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
     GenSampArgs b;
     static_cast<GenArgs&>(b) = a;
     b.sampling = sampling;
+    if (ring_form) return generate_launch<false, true, true>(b, R, S, cd, dtype, nlayers, groups, st);
     return generate_launch<false, true>(b, R, S, cd, dtype, nlayers, groups, st);
   }
+  if (ring_form) return generate_launch<false, false, true>(static_cast<GenArgs&>(a), R, S, cd, dtype, nlayers, groups, st);
   return generate_launch<false, false>(static_cast<GenArgs&>(a), R, S, cd, dtype, nlayers, groups, st);
 }
 
@@ -678,6 +696,29 @@ extern "C" int srwn_generate_mol(const void* wcr, const void* wskip, const void*
                                   codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, K,
                                   num_mixtures, cond, cond_frames, pool_stride, cond_ld, mode, seed, dtype, stream, 0,
                                   nullptr);
+}
+
+// ---- the live form (srwn.h, srwn_version() 112): srwn_generate_mol_resume_sampled over a conditioning table that is a ring
+// of cond_frames frames per utterance (frame q in row q mod cond_frames), fed while the run goes on.  `cond` is required
+extern "C" int srwn_generate_mol_live_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                      const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                      const float* b2, const float* init_w, const float* init_b, void* ring,
+                                      float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                      const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                      int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                                      const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                                      int32_t mode, uint64_t seed, int32_t dtype, void* stream, int32_t t0,
+                                      float* carry, const SrwnGenSampling* sampling) {
+  if (!cond) return set_error(SRWN_E_NULL, "generate_mol_live: the conditioning ring is required");
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate_mol_live: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R)
+    return set_error(SRWN_E_SHAPE, "generate_mol_live: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
+                     pool_stride, (long long)cond_ld);
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, seed,
+                       dtype, stream, cond, cond_frames, pool_stride, cond_ld, num_mixtures, t0, carry, sampling, nullptr,
+                       false, true);
 }
 
 // ---- the slot form (generation pools, srwn.h): the arguments of the *_resume twins without the seed, with the pool's
@@ -863,4 +904,52 @@ extern "C" int srwn_generate_ring_fill_slots(const void* xs, int64_t layer_strid
   if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_fill_slots_kernel<bf16_t>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(ring_fill_slots_kernel<float>, grid, dim3(256), 0, st, a);
   return check_launch("generate_ring_fill_slots");
+}
+
+// ---- the feed of the live form (srwn.h): the projected conditioning rows of k new frames per utterance -> their rows of
+// the ring table.  Memory-bound: one 16-byte vector per thread, consecutive threads along a row.
+struct CondScatterArgs {
+  const void* rows; void* table;
+  long long rows_ld, cond_ld, first;
+  int B, k, cond_frames, vpr;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void cond_scatter_kernel(CondScatterArgs a) {
+  constexpr int V = 16 / sizeof(T);
+  const long long nvec = (long long)a.B * a.k * a.vpr;
+  const int f0 = (int)(a.first % a.cond_frames);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
+    const int cv = (int)(i % a.vpr);
+    const long long r = i / a.vpr;                               // source row u * k + j
+    const int u = (int)(r / a.k), j = (int)(r - (long long)u * a.k);
+    int slot = f0 + j;                                           // j < k <= cond_frames: one wrap
+    slot = slot < a.cond_frames ? slot : slot - a.cond_frames;
+    const T* sp = reinterpret_cast<const T*>(a.rows) + r * a.rows_ld + cv * V;
+    T* dp = reinterpret_cast<T*>(a.table) + ((long long)u * a.cond_frames + slot) * a.cond_ld + cv * V;
+    *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
+  }
+}
+
+extern "C" int srwn_cond_ring_scatter(const void* rows, int64_t rows_ld, void* table, int64_t cond_ld, int32_t B,
+                                          int32_t k, int64_t first_frame, int32_t cond_frames, int32_t width,
+                                          int32_t dtype, void* stream) {
+  if (B == 0 || k == 0) return 0;
+  if (!rows || !table) return set_error(SRWN_E_NULL, "cond_ring_scatter: null pointer");
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "cond_ring_scatter: dtype %d", dtype);
+  const int V = dtype == SRWN_BF16 ? 8 : 4;
+  if (B < 0 || k < 0 || cond_frames < 1 || k > cond_frames || first_frame < 0 || width < V || width % V || rows_ld < width ||
+      cond_ld < width || rows_ld % V || cond_ld % V || (reinterpret_cast<uintptr_t>(rows) & 15) ||
+      (reinterpret_cast<uintptr_t>(table) & 15) || (int64_t)B * cond_frames > 0x7fffffffLL)
+    return set_error(SRWN_E_SHAPE, "cond_ring_scatter: B=%d k=%d first=%lld cond_frames=%d width=%d ld %lld / %lld", B, k,
+                     (long long)first_frame, cond_frames, width, (long long)rows_ld, (long long)cond_ld);
+  CondScatterArgs a;
+  a.rows = rows; a.table = table; a.rows_ld = rows_ld; a.cond_ld = cond_ld; a.first = first_frame;
+  a.B = B; a.k = k; a.cond_frames = cond_frames; a.vpr = width / V;
+  const long long nvec = (long long)B * k * a.vpr;
+  const dim3 grid((unsigned)min((nvec + 255) / 256, (long long)4096));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) hipLaunchKernelGGL(cond_scatter_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(cond_scatter_kernel<float>, grid, dim3(256), 0, st, a);
+  return check_launch("cond_ring_scatter");
 }

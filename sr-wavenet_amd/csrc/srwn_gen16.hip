@@ -83,7 +83,9 @@ struct PreT : std::conditional<COND, G16Cond<NCB>, G16NoCond>::type {
   Frag<T> x0[G16W<R, S>::KR][NCB];            // [k-step of the delayed tap][column block]
 };
 
-template <int NCB, bool COND, bool MOL, int R, int S, bool SLOTS = false, bool SAMP = false>
+// RING (the live form, srwn.h: srwn_generate16_mol_live_sampled): the conditioning table is a ring of cond_frames rows per
+// utterance that the caller keeps feeding; instantiations of their own, so that every other launch keeps its code
+template <int NCB, bool COND, bool MOL, int R, int S, bool SLOTS = false, bool SAMP = false, bool RING = false>
 __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SLOTS, SAMP>::type a) {
   constexpr int NU = 16 * NCB;                // utterances of this workgroup
   constexpr int NI = 4 * NCB;                 // utterances a wave samples
@@ -175,7 +177,12 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
     if constexpr (COND) {   // (first: the epilogue of the layer below needs it before anything else of this set)
       if (chw) {
       const int tt = t + ahead;
-      const int fc = tt / a.pool < a.cond_frames ? tt / a.pool : a.cond_frames - 1;
+      int fc = tt / a.pool < a.cond_frames ? tt / a.pool : a.cond_frames - 1;
+      // the live form: frame q sits in row q mod cond_frames.  This is the body's one read ahead of the step: the top
+      // layer requests layer 0 of step t + 1 (ahead = 1), which after a launch's last step may be a frame the caller has
+      // not fed yet -- the modulus keeps the row inside the table and the value is dropped (the next launch's first step
+      // requests its own, j == 0 below).  Every other operand set is requested for the step that is running
+      if constexpr (RING) fc = (tt / a.pool) % a.cond_frames;
 #pragma unroll
       for (int c2 = 0; c2 < NCB; ++c2) {
         const int ug = u0 + 16 * c2 + col;
@@ -616,7 +623,7 @@ extern "C" int64_t srwn_generate16_image_elems(int32_t nlayers, int32_t which, i
   return (int64_t)4 * 4 * HKS * FR;
 }
 
-template <int R, int S, bool SLOTS, bool SAMP, typename A>
+template <int R, int S, bool SLOTS, bool SAMP, bool RING = false, typename A>
 static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, int32_t B, bool cond, int32_t M, void* stream) {
   int bad;
   a.ring_group_elems = gen_ring_layout(dilations, nlayers, R, INT32_MAX, &bad, a.dil, a.ring_off);
@@ -628,9 +635,15 @@ static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, in
   using W = G16W<R, S>;
   const size_t sh = (size_t)(2 * 32 * W::LSX + 32 * W::LSH) * sizeof(T) +
                     (size_t)(32 * LGS + 64 + 2 * nlayers * R + 2 * S + 256 + 3 * R + 256 + (SLOTS ? 4 * 32 : 0) + (SAMP ? 4 * 32 : 0)) * 4;
-  auto kfn = M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S, SLOTS, SAMP> : generate16_kernel<2, true, true, R, S, SLOTS, SAMP>)
+  auto pick = [&] {
+    if constexpr (RING)   // the live form: the conditioned mixture-of-logistics decoder, no slots
+      return half ? generate16_kernel<1, true, true, R, S, false, SAMP, true> : generate16_kernel<2, true, true, R, S, false, SAMP, true>;
+    else
+      return M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S, SLOTS, SAMP> : generate16_kernel<2, true, true, R, S, SLOTS, SAMP>)
                            : (half ? generate16_kernel<1, false, true, R, S, SLOTS, SAMP> : generate16_kernel<2, false, true, R, S, SLOTS, SAMP>))
                    : (half ? generate16_kernel<1, false, false, R, S, SLOTS, SAMP> : generate16_kernel<2, false, false, R, S, SLOTS, SAMP>);
+  };
+  auto kfn = pick();
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
   if (e != hipSuccess) return set_error((int)e, "generate16: LDS %zu: %s", sh, hipGetErrorString(e));
   hipLaunchKernelGGL(kfn, dim3(groups), dim3(256), sh, (hipStream_t)stream, a);
@@ -644,7 +657,7 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
                            int32_t nsteps, int32_t R, int32_t S, int32_t C, int32_t mode, uint64_t seed, void* stream,
                            int32_t M, const void* cond, int32_t cond_frames, int32_t pool, int64_t cond_ld, int32_t t0,
                            float* carry, const SrwnGenSampling* sampling, SrwnGenSlot* slots = nullptr,
-                           bool slot_form = false) {
+                           bool slot_form = false, bool ring_form = false) {
   if (B == 0 || nsteps == 0) return 0;
   if (t0 < 0 || (int64_t)t0 + nsteps > INT32_MAX) return set_error(SRWN_E_SHAPE, "generate16: t0=%d", t0);
   if (t0 > 0 && !carry) return set_error(SRWN_E_NULL, "generate16: a launch that resumes at t0=%d needs the carry", t0);
@@ -667,6 +680,7 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
   a.M = M; a.cond = cond; a.cond_frames = cond_frames; a.pool = pool; a.cond_ld = cond_ld;
   a.t0 = t0; a.carry = carry;
   const bool cd = cond != nullptr;
+#define SRWN_G16_RING(SA) SA, true   /* the live form's (SAMP, RING) */
 #define SRWN_G16_WIDTHS(SL, SA, args)                                                                          \
   do {                                                                                                         \
     if (R == 64 && S == 256) return generate16_launch<64, 256, SL, SA>(args, dilations, nlayers, B, cd, M, stream); \
@@ -686,9 +700,12 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
     Gen16SampArgs b;
     static_cast<Gen16Args&>(b) = a;
     b.sampling = sampling;
+    if (ring_form) SRWN_G16_WIDTHS(false, SRWN_G16_RING(true), b);
     SRWN_G16_WIDTHS(false, true, b);
   }
+  if (ring_form) SRWN_G16_WIDTHS(false, SRWN_G16_RING(false), a);
   SRWN_G16_WIDTHS(false, false, a);
+#undef SRWN_G16_RING
 #undef SRWN_G16_WIDTHS
 }
 
@@ -769,6 +786,27 @@ extern "C" int srwn_generate16_mol(const void* wl, const void* wh1, const void* 
   return srwn_generate16_mol_resume(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out,
                                     codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, num_mixtures,
                                     cond, cond_frames, pool_stride, cond_ld, mode, seed, stream, 0, nullptr);
+}
+
+// ---- the live form (srwn.h, srwn_version() 112): srwn_generate16_mol_resume_sampled over a conditioning table that is a
+// ring of cond_frames frames per utterance (frame q in row q mod cond_frames), fed while the run goes on
+extern "C" int srwn_generate16_mol_live_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                        const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                        const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                        int32_t* codes_out, float* logits_out, const float* forced,
+                                        const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                        int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                                        int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                                        uint64_t seed, void* stream, int32_t t0, float* carry, const SrwnGenSampling* sampling) {
+  if (!cond) return set_error(SRWN_E_NULL, "generate16_mol_live: the conditioning ring is required");
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate16_mol_live: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R || (cond_ld % 4))
+    return set_error(SRWN_E_SHAPE, "generate16_mol_live: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
+                     pool_stride, (long long)cond_ld);
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, seed, stream,
+                         num_mixtures, cond, cond_frames, pool_stride, cond_ld, t0, carry, sampling, nullptr, false, true);
 }
 
 // ---- the slot form (generation pools, srwn.h): the arguments of the *_resume twins without the seed, with the pool's

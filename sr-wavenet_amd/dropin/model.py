@@ -16,3 +16,4 @@ SiameseWaveNet = _m.SiameseWaveNet
 StudentSynthesizer = _m.StudentSynthesizer
 AudioEncoder = _m.AudioEncoder
 Resynthesizer = _m.Resynthesizer
+TeacherResynthesizer = _m.TeacherResynthesizer

@@ -107,6 +107,34 @@ class GenerationState:
         self.sampling = sampling
         self.t = 0
 
+    live = False      # (LiveGenerationState: the conditioning table is a ring that `feed` fills while the run goes on)
+
+
+class LiveGenerationState(GenerationState):
+    """A generation run whose encoding arrives while it runs (WaveNetEngine.live_generation_state / feed): `cond_all`
+    [B * max_frames, L*R] is a RING -- frame q of a stream in row q mod max_frames -- `fed` the frames written so far and
+    `limit` = fed * pool_stride.  `cond` keeps the raw frames fed while t == 0 (what `prime` runs its forward pass on) and
+    is dropped at the first step.  `stage_in` / `stage_out`: the feed's projection operands, [B * max_frames, Ep] (its
+    padding columns stay zero) and [B * max_frames, L*R]."""
+
+    live = True
+
+    def __init__(self, batch, ring, carry, seed, cond_all, max_frames, sampling=None, stage_in=None, stage_out=None):
+        super().__init__(batch, ring, carry, seed, None, cond_all, max_frames, 0, sampling)
+        self.max_frames, self.fed = int(max_frames), 0
+        self.stage_in, self.stage_out = stage_in, stage_out
+
+
+def live_decode_room(max_frames: int, fed: int, t: int, pool_stride: int) -> int:
+    """How many frames a live DECODER run may be fed now: max_frames - fed + t // pool_stride.  Its conditioning table is
+    a ring of ``max_frames`` frames (frame q in row q mod max_frames) and step t reads the row of its own frame t //
+    pool_stride only -- the layer rings carry everything older -- so every frame before the current one may be
+    overwritten: unlike ``student.live_room`` there is no history term.  Pure Python."""
+    max_frames, fed, t, pool_stride = int(max_frames), int(fed), int(t), int(pool_stride)
+    if max_frames < 1 or fed < 0 or t < 0 or pool_stride < 1 or t > fed * pool_stride:
+        raise ValueError("live_decode_room: max_frames=%d fed=%d t=%d pool_stride=%d" % (max_frames, fed, t, pool_stride))
+    return max_frames - fed + t // pool_stride
+
 
 def sampling_table(n, temperature, top_k, top_p, C, mol, who="generate"):
     """The sampling controls of n streams as srwn.h's SrwnGenSampling rows (a NumPy structured array [n]), or None when
@@ -1608,12 +1636,13 @@ class WaveNetEngine:
                    ("srwn_generate16_mol_resume_sampled", "srwn_generate16_mol_slots_sampled")))
 
     def _launch_generation(self, ring, audio, codes, logits, forced, batch, nsteps, mode, seed, t0, carry, sampling,
-                           cond_all, frames, slots=None):
+                           cond_all, frames, slots=None, live=False):
         """THE launch of the queue-cached generators: `nsteps` steps from absolute step t0 for `batch` streams over `ring`
         into audio / codes / logits (None: not kept), teacher-forced where `forced` is given.  carry [batch, 2] (None with
         t0 = 0: none read, none written), sampling: the SrwnGenSampling device array or None, cond_all [batch * frames,
         L*R] or None.  `slots` (a pool's SrwnGenSlot table) selects the slot form: t0 is then the pool's clock and the
-        seeds are the slots'.  The argument list is srwn.h's, built once from its blocks."""
+        seeds are the slots'.  `live` (a LiveGenerationState's launch): cond_all is a ring of `frames` frames per stream and
+        the live entry point runs.  The argument list is srwn.h's, built once from its blocks."""
         from . import _lib
         ptr = lambda t: None if t is None else t.data_ptr()
         v, g16 = self.view, self._gen16()
@@ -1638,7 +1667,10 @@ class WaveNetEngine:
             tail = (md, int(seed)) + dtype + (st, t0, ptr(carry))
         else:
             tail = (md,) + dtype + (st, t0, carry.data_ptr(), slots.data_ptr())
-        _lib.call(self._GEN_ENTRY[g16][bool(self.mol)][slots is not None], *weights, *shared, *head, *tail, ptr(sampling))
+        entry = self._GEN_ENTRY[g16][bool(self.mol)][slots is not None]
+        if live:      # the live forms (srwn_version() 112) are named after their *_mol_resume_sampled twins
+            entry = entry.replace("_resume_", "_live_")
+        _lib.call(entry, *weights, *shared, *head, *tail, ptr(sampling))
 
     def generate(self, nsteps: int, mode: str = "sample", seed: int = 0, forced: Optional[torch.Tensor] = None,
                  want_logits: bool = False, batch: Optional[int] = None, cond: Optional[torch.Tensor] = None, *,
@@ -1711,6 +1743,60 @@ class WaveNetEngine:
                                frames * self.cfg.pool_stride if frames else None,
                                None if samp is None else _sampling_to_device(samp, self.dev))
 
+    def live_generation_state(self, batch: int, max_frames: int, seed: int = 0, *, temperature=1.0) -> "LiveGenerationState":
+        """A generation run of the conditioned mixture-of-logistics decoder whose encoding is FED while it runs (`feed`):
+        the state of `generation_state` with a zeroed conditioning ring of `max_frames` frames per stream and fed = 0.
+        `generate_chunk` advances it up to fed * pool_stride, `prime` starts it (at t = 0) from a prompt over the frames fed
+        by then; the samples are those of `generate` over the whole encoding with the same seed and temperature."""
+        self._check_generates()
+        self._refuse_conditioned_softmax()
+        if not self.E:
+            raise ValueError("this decoder is not conditioned")
+        B, F = int(batch), int(max_frames)
+        if B < 1 or F < 1:
+            raise ValueError("live_generation_state: batch %d, max_frames %d" % (B, F))
+        samp = sampling_table(B, temperature, 0, 1.0, self.C, True, "live_generation_state")
+        self._repack_generation()
+        LR = self.L * self.R
+        return LiveGenerationState(B, self._gen_ring(B), torch.zeros((B, 2), dtype=torch.float32, device=self.dev),
+                                   int(seed), torch.zeros((B * F, LR), dtype=self.dt, device=self.dev), F,
+                                   None if samp is None else _sampling_to_device(samp, self.dev),
+                                   torch.zeros((B * F, self.Ep), dtype=self.dt, device=self.dev),
+                                   torch.empty((B * F, LR), dtype=self.dt, device=self.dev))
+
+    def feed(self, state: "LiveGenerationState", frames: torch.Tensor) -> None:
+        """The next k frames of every stream of a live state: frames [B, k, cond_channels] (encoding_w_condition), a device
+        tensor taken as it is.  Refuses (ValueError, before any device work, state untouched) k > `live_decode_room`.  The
+        rows are `_project_cond`'s (the same srwn_pw_linear over the same image, so the bits of the one-shot table) in a
+        staging buffer, scattered into the ring by ONE srwn_cond_ring_scatter however many streams; afterwards
+        `generate_chunk` may run up to fed * pool_stride."""
+        from . import _lib
+        if not state.live:
+            raise ValueError("feed: this state got its whole encoding at generation_state (live_generation_state begins "
+                             "a live one)")
+        fr = torch.as_tensor(frames)
+        B, pool = state.batch, self.cfg.pool_stride
+        if fr.dim() != 3 or fr.shape[0] != B or fr.shape[2] != self.E:
+            raise ValueError("feed: frames must be [%d, k, %d], got %s" % (B, self.E, tuple(fr.shape)))
+        k = int(fr.shape[1])
+        if k == 0:
+            return
+        room = live_decode_room(state.max_frames, state.fed, state.t, pool)
+        if k > room:
+            raise ValueError("feed: %d frames, but the ring of %d has room for %d at t = %d with %d fed"
+                             % (k, state.max_frames, room, state.t, state.fed))
+        fr = fr.to(device=self.dev, dtype=torch.float32)
+        LR, rows = self.L * self.R, B * k
+        state.stage_in[:rows, :self.E].copy_(fr.reshape(rows, self.E))
+        K.pw_linear(state.stage_in.data_ptr(), self.Ep, 0, self.Ep, self.Ep, self.wptr(self.o_wc),
+                    self.view("BC").reshape(-1), state.stage_out[:rows], LR, LR, rows)
+        _lib.call("srwn_cond_ring_scatter", state.stage_out.data_ptr(), LR, state.cond_all.data_ptr(), LR, B, k,
+                  state.fed, state.max_frames, LR, K.abi_dtype(self.dt), torch.cuda.current_stream().cuda_stream)
+        if state.t == 0:      # (what `prime` needs: the raw frames of a run that has not started)
+            state.cond = fr.contiguous() if state.cond is None else torch.cat([state.cond, fr], dim=1)
+        state.fed += k
+        state.limit = state.fed * pool
+
     def generation_pool(self, capacity: int, frames: Optional[int] = None) -> "GenerationPool":
         """A pool of `capacity` generation slots that streams join and leave while it runs (GenerationPool); `frames` = the
         most conditioning frames a stream of a conditioned decoder brings.  Refuses, before any device work, what
@@ -1781,8 +1867,10 @@ class WaveNetEngine:
         if nsteps == 0:
             return audio, codes, logits
         self._launch_generation(state.ring, audio, codes, logits, forced, B, nsteps, mode, state.seed, state.t, state.carry,
-                                state.sampling, state.cond_all, state.frames)
+                                state.sampling, state.cond_all, state.frames, live=state.live)
         state.t += nsteps
+        if state.live:
+            state.cond = None      # (the raw frames served `prime`, which only starts a run)
         return audio, codes, logits
 
     def capture_graphs(self):

@@ -762,9 +762,200 @@ class WaveNetAutoEncoder(object):
             eng.dec.prime(st, p)
         return eng, st, p
 
+    def live(self, batch, conditions=None, max_frames=32, mode="sample", seed=0, prompt_frames=None, prompt=None, *,
+             temperature=1.0):
+        """Live decoding: a ``LiveDecoding`` of `batch` streams in lockstep whose encoding is FED while the decoder runs
+        (``feed`` / ``step``), on a conditioning ring of `max_frames` frames -- a stream has no bound on its length.  The
+        samples put together are ``generate(encoding, conditions, seed=seed, ...)`` of the whole encoding bit for bit.
+        conditions [B, condition_size] are tiled onto every frame fed.  prompt [B, P] with prompt_frames [B, k, latent]
+        (P <= k * pool_stride, k <= max_frames): the frames are fed and the run starts after the prompt."""
+        batch, max_frames = int(batch), int(max_frames)
+        if batch < 1 or max_frames < 1:
+            raise ValueError("live: batch %d, max_frames %d" % (batch, max_frames))
+        self._check_sampling(batch, dict(temperature=temperature, top_k=0, top_p=1.0), "live")
+        p = _check_prompt(batch, prompt)
+        pf = None
+        if p is not None or prompt_frames is not None:
+            if p is None or prompt_frames is None:
+                raise ValueError("live: prompt [B, P] and prompt_frames [B, k, latent] come together")
+            pf = prompt_frames if isinstance(prompt_frames, torch.Tensor) else np.asarray(prompt_frames, dtype=np.float32)
+            if pf.ndim != 3 or pf.shape[0] != batch or pf.shape[2] != self.latent_channels or pf.shape[1] > max_frames:
+                raise ValueError("prompt_frames must be [%d, k <= max_frames = %d, latent_channels=%d], got %s"
+                                 % (batch, max_frames, self.latent_channels, tuple(pf.shape)))
+            if p.shape[1] > pf.shape[1] * self.pool_stride:
+                raise ValueError("prompt of %d samples exceeds frames * pool_stride = %d"
+                                 % (p.shape[1], pf.shape[1] * self.pool_stride))
+        if self.condition_size > 0:
+            if conditions is None:
+                raise ValueError("this auto-encoder was built with condition_size > 0; pass conditions")
+            c = np.asarray(conditions, dtype=np.float32)
+            if c.shape != (batch, self.condition_size):
+                raise ValueError("conditions must be [%d, %d]" % (batch, self.condition_size))
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        eng = self._eng or self._engine(batch, max_frames * self.pool_stride)
+        cond = torch.as_tensor(c).to("cuda") if self.condition_size > 0 else None
+        st = eng.dec.live_generation_state(batch, max_frames, seed, temperature=temperature)
+        live = LiveDecoding(self, eng.dec, st, cond, mode)
+        if pf is not None:
+            live.feed(pf)
+            eng.dec.prime(st, p)
+        return live
+
+    def resynthesizer(self, max_batch=1, max_frames=32):
+        """A ``TeacherResynthesizer``: ``self.encoder(max_batch, max_frames)`` (a snapshot of the encoder's parameters)
+        feeding this model's decoder on conditioning rings of `max_frames` frames."""
+        return TeacherResynthesizer(self.encoder(max_batch, max_frames), self, max_frames=max_frames)
+
     def mu_law(self, inputs, conditions=None):
         raise AttributeError("WaveNetAutoEncoder.mu_law reads self.targets, which the reference never defines "
                              "(model.py:100,276): it raises there too")
+
+
+class LiveDecoding(object):
+    """One running batch of live decoder streams (``WaveNetAutoEncoder.live``).  ``feed(encoding [B, k, latent])`` hands
+    every stream its next k frames (k <= ``room``), ``step(n)`` returns the next n <= ``available`` samples [B, n]; ``t``:
+    samples made so far (a prompt's included), ``fed``: frames fed.  The samples are those ``generate`` gives the whole
+    encoding with the same seed and temperature, however the frames and chunks were cut."""
+
+    def __init__(self, owner, dec, state, cond, mode):
+        self._owner, self._dec, self._st, self._cond, self._mode = owner, dec, state, cond, mode
+        self.batch_size = state.batch
+
+    @property
+    def t(self):
+        return self._st.t
+
+    @property
+    def fed(self):
+        return self._st.fed
+
+    @property
+    def room(self):
+        from .engine import live_decode_room
+        return live_decode_room(self._st.max_frames, self._st.fed, self._st.t, self._owner.pool_stride)
+
+    @property
+    def available(self):
+        """Samples that can be made now: fed * pool_stride - t."""
+        return self._st.limit - self._st.t
+
+    def _feed_device(self, enc):
+        """enc [B, k, latent] on the device (or NumPy): + the tiled conditions (model.py:161-167), into the ring."""
+        o = self._owner
+        e = torch.as_tensor(enc, dtype=torch.float32)
+        if e.dim() != 3 or e.shape[0] != self.batch_size or e.shape[2] != o.latent_channels:
+            raise ValueError("encoding must be [%d, k, latent_channels=%d], got %s"
+                             % (self.batch_size, o.latent_channels, tuple(e.shape)))
+        if e.shape[1] > self.room:
+            raise ValueError("feed: %d frames, but the ring of %d has room for %d at t = %d with %d fed"
+                             % (e.shape[1], self._st.max_frames, self.room, self.t, self.fed))
+        if self._cond is not None:
+            e = torch.cat([e.to("cuda"), self._cond[:, None, :].expand(-1, e.shape[1], -1)], dim=2)
+        self._dec.feed(self._st, e)
+
+    def feed(self, encoding):
+        self._feed_device(encoding if isinstance(encoding, torch.Tensor) else np.asarray(encoding, dtype=np.float32))
+
+    def _step_device(self, n, forced=None, want_logits=False):
+        """(audio [B, n] f32, selected mixture [B, n] i32, logits [B, n, 4M] f32 or None) on the device."""
+        return self._dec.generate_chunk(self._st, int(n), mode=self._mode, forced=forced, want_logits=want_logits)
+
+    def step(self, n, forced=None, return_logits=False):
+        """The next n samples [B, n] (NumPy); forced [B, n]: teacher forcing for this chunk; return_logits: (samples, logits
+        [B, n, 4 * num_mixtures])."""
+        a, _, lg = self._step_device(n, forced, return_logits)
+        return (a.cpu().numpy(), lg.cpu().numpy()) if return_logits else a.cpu().numpy()
+
+
+class TeacherResynthesizer(object):
+    """The live auto-encoder loop at teacher quality: an ``AudioEncoder`` feeding the autoregressive decoder of a
+    ``WaveNetAutoEncoder`` (``Resynthesizer`` is the same pipeline on the student).  Audio chunks in, decoded audio chunks
+    out, with no bound on the length; the latent frames go from the encoder into the decoder's conditioning ring as device
+    tensors.  The audio of a stream put together equals ``autoencoder.generate(encoder.encode(audio), conditions,
+    seed=seed, ...)`` however the audio and the chunks were cut."""
+
+    def __init__(self, encoder, autoencoder, max_frames=None):
+        if not isinstance(encoder, AudioEncoder) or not isinstance(autoencoder, WaveNetAutoEncoder):
+            raise TypeError("TeacherResynthesizer(encoder: AudioEncoder, autoencoder: WaveNetAutoEncoder)")
+        if int(encoder.pool_stride) != int(autoencoder.pool_stride):
+            raise ValueError("pool_stride: the encoder makes a frame per %d samples, the decoder reads one per %d"
+                             % (encoder.pool_stride, autoencoder.pool_stride))
+        if int(encoder.latent_channels) != int(autoencoder.latent_channels):
+            raise ValueError("latent_channels: the encoder gives %d, the decoder takes %d"
+                             % (encoder.latent_channels, autoencoder.latent_channels))
+        if not torch.cuda.is_available():
+            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        self.encoder, self.autoencoder = encoder, autoencoder
+        self.pool_stride = int(encoder.pool_stride)
+        self.max_frames = int(max_frames if max_frames is not None else encoder.max_frames)
+        # samples of audio a sample of output waits for beyond itself: the rest of its frame and the encoder's look-ahead
+        self.lookahead = self.pool_stride + encoder.num_layers + 1
+
+    def stream(self, batch=1, conditions=None, seed=0, temperature=1.0, chunk_size=160):
+        """A ``TeacherResynthesisStream`` of `batch` streams in lockstep: ``push(audio [B, m])`` returns every sample that
+        can be made by now, [B, m']; ``finish()`` the rest.  conditions [B, condition_size] are tiled onto every frame on
+        the device; chunk_size: the most samples of one decoder launch."""
+        batch, chunk_size = int(batch), int(chunk_size)
+        if not 1 <= batch <= self.encoder.max_batch:
+            raise ValueError("batch %d: the encoder holds %d streams" % (batch, self.encoder.max_batch))
+        if chunk_size < 1:
+            raise ValueError("chunk_size %d: at least 1" % chunk_size)
+        return TeacherResynthesisStream(self, batch, conditions, seed, temperature, chunk_size)
+
+
+class TeacherResynthesisStream(object):
+    """One running batch of ``TeacherResynthesizer.stream``.  ``t``: samples returned so far per stream; ``received``:
+    samples pushed.  ``push`` may return no sample ([B, 0]) while the first frame's look-ahead is incomplete."""
+
+    def __init__(self, owner, batch, conditions, seed, temperature, chunk_size):
+        self._owner, self.batch_size, self._chunk = owner, batch, chunk_size
+        self._live = owner.autoencoder.live(batch, conditions, owner.max_frames, seed=seed, temperature=temperature)
+        self._enc = owner.encoder._eng.start(batch)
+
+    @property
+    def t(self):
+        return self._live.t
+
+    @property
+    def received(self):
+        return self._enc.received
+
+    def _drain(self, frames, outs):
+        """frames [B, k, latent] (device) into the ring and every sample they allow: feed -> step -> feed while the ring
+        has less room than the frames that are due (the drain loop of ``ResynthesisStream``)."""
+        live, k, f0 = self._live, int(frames.shape[1]), 0
+        while True:
+            if f0 < k:
+                r = min(live.room, k - f0)
+                if r > 0:
+                    live._feed_device(frames[:, f0:f0 + r])
+                    f0 += r
+            n = min(live.available, self._chunk)
+            if n <= 0:
+                if f0 < k:      # (cannot happen: room > 0 once every sample of the fed frames is made)
+                    raise RuntimeError("the conditioning ring has no room and no sample to make")
+                return
+            outs.append(live._step_device(n)[0])
+
+    def _result(self, outs):
+        if not outs:
+            return np.zeros((self.batch_size, 0), np.float32)
+        return torch.cat(outs, dim=1).cpu().numpy()
+
+    def push(self, audio):
+        if self._enc.closed:
+            raise ValueError("this stream is closed (finish was called)")
+        x = self._owner.encoder._check(audio, self.batch_size)
+        outs = []
+        self._drain(self._owner.encoder._eng.push(self._enc, torch.as_tensor(x)), outs)
+        return self._result(outs)
+
+    def finish(self):
+        """The encoder's remaining whole frames (clip-end padding) and the samples they allow; closes the stream."""
+        outs = []
+        self._drain(self._owner.encoder._eng.finish(self._enc), outs)
+        return self._result(outs)
 
 
 class AudioEncoder(object):
