@@ -31,6 +31,7 @@ from . import packing as P
 from . import _lib
 from ._lib import call
 from .engine import Section, StackConfig, WaveNetEngine
+from .slots import SlotTable
 
 # What SRWN_ENC_FUSED means when it is not set (FrameEncoder in bf16): "0" the layer-by-layer twin, "1" the one-launch
 # chain.  Set by measurement: tools/encode_bench.py case (b) at B = 1, pool 512 has the chain at 0.160 ms per push
@@ -738,7 +739,7 @@ class FrameEncoder:
         return EncoderPool(self, audio_ring, max_rows)
 
 
-class EncoderPool:
+class EncoderPool(SlotTable):
     """``FrameEncoder.pool()``: the encoder's ``max_batch`` rows as SLOTS, each holding a stream with its own samples
     received, frames emitted and end.  Streams ``join`` free slots, ``push`` audio of any length whenever it arrives (one
     upload and one srwn_audio_ring_put however many slots are written; a slot's audio lives in its row of a device ring,
@@ -763,8 +764,7 @@ class EncoderPool:
             raise ValueError("pool: max_rows %d: 1..max_batch * max_frames = %d" % (self.max_rows, rows))
         if self.capacity * self.audio_ring + 4 * self.capacity > 0x7fffffff:
             raise ValueError("pool: %d slots of %d samples" % (self.capacity, self.audio_ring))
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         cap, dev = self.capacity, fe.w.dev
         self._received = np.zeros(cap, np.int64)
         self._emitted = np.zeros(cap, np.int64)
@@ -777,14 +777,6 @@ class EncoderPool:
 
     # ---- inspection
     @property
-    def active(self):
-        return [int(u) for u in np.flatnonzero(self._active)]
-
-    @property
-    def free(self):
-        return [int(u) for u in np.flatnonzero(~self._active)]
-
-    @property
     def received(self) -> np.ndarray:
         """Samples pushed into each slot's stream so far."""
         return self._received.copy()
@@ -794,14 +786,6 @@ class EncoderPool:
         """Frames each slot's stream has emitted so far."""
         return self._emitted.copy()
 
-    def _slot_list(self, slots, who):
-        slots = [int(u) for u in (slots if np.ndim(slots) else [slots])]
-        if any(u < 0 or u >= self.capacity for u in slots):
-            raise ValueError("%s: slots %s outside the pool's %d" % (who, slots, self.capacity))
-        if len(set(slots)) != len(slots):
-            raise ValueError("%s: slots %s are not distinct" % (who, slots))
-        return slots
-
     def audio_room(self, slot: int) -> int:
         """Samples a slot can take now: audio_ring minus what it holds beyond its emitted frames."""
         u, = self._slot_list(slot, "audio_room")
@@ -810,15 +794,7 @@ class EncoderPool:
     # ---- streams come and go
     def join(self, n: int = 1, slots=None):
         """n streams into free slots (the lowest ones, or `slots`); returns the slots.  A slot starts at sample 0."""
-        free = self.free
-        if slots is None:
-            if int(n) < 1 or int(n) > len(free):
-                raise ValueError("join: %d streams but %d free slots" % (int(n), len(free)))
-            slots = free[:int(n)]
-        else:
-            slots = self._slot_list(slots, "join")
-            if not slots or any(self._active[u] for u in slots):
-                raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
+        slots = self._take_slots(int(n) if slots is None else None, slots)
         for u in slots:
             self._received[u] = self._emitted[u] = 0
             self._final[u], self._active[u] = False, True
@@ -826,13 +802,13 @@ class EncoderPool:
 
     def leave(self, slots) -> None:
         """Ends the streams in `slots` where they are (a slot already free stays free) and frees their slots."""
-        for u in self._slot_list(slots, "leave"):
+        for u in self._slot_list(slots, "leave", distinct=True):
             self._active[u] = False
 
     def finish(self, slots) -> None:
         """No more audio comes for these streams: their remaining whole frames are due with the clip-end padding, and each
         frees its slot with its last frame (at the next ``step``)."""
-        slots = self._slot_list(slots, "finish")
+        slots = self._slot_list(slots, "finish", distinct=True)
         if any(not self._active[u] for u in slots):
             raise ValueError("finish: slots %s do not all hold a stream" % (slots,))
         for u in slots:
@@ -843,7 +819,7 @@ class EncoderPool:
         slot that holds no stream or was finished, more than ``audio_room(slot)`` samples and audio that is not floating
         point.  One host-to-device copy and one srwn_audio_ring_put, whatever the number of slots."""
         one = not np.ndim(slots)
-        slots = self._slot_list(slots, "push")
+        slots = self._slot_list(slots, "push", distinct=True)
         if one or isinstance(audio, (np.ndarray, torch.Tensor)):
             audio = [audio]
         audio = list(audio)

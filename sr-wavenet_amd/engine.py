@@ -29,6 +29,7 @@ import torch
 from . import dp
 from . import kernels as K
 from . import packing as P
+from .slots import SlotTable, per_stream
 
 SQRT_HALF = 0.7071067811865476
 
@@ -144,17 +145,8 @@ def sampling_table(n, temperature, top_k, top_p, C, mol, who="generate"):
     the argument and the value.  No device work."""
     from . import _lib
     n = int(n)
-
-    def per(x, default, name):
-        if x is None:
-            return [default] * n
-        if np.ndim(x) == 0:
-            return [x] * n
-        x = list(x)
-        if len(x) != n:
-            raise ValueError("%s: %s has %d entries for %d streams: %r" % (who, name, len(x), n, x))
-        return x
-    taus, ks, ps = per(temperature, 1.0, "temperature"), per(top_k, 0, "top_k"), per(top_p, 1.0, "top_p")
+    taus, ks, ps = (per_stream(x, n, name, who, default)
+                    for x, name, default in ((temperature, "temperature", 1.0), (top_k, "top_k", 0), (top_p, "top_p", 1.0)))
     tab = np.zeros(n, dtype=np.dtype(_lib.SrwnGenSampling))
     for i, (t, k, p) in enumerate(zip(taus, ks, ps)):
         try:
@@ -191,7 +183,7 @@ def _pow2_at_least(n: int) -> int:
     return 1 << max(0, int(n) - 1).bit_length()
 
 
-class GenerationPool:
+class GenerationPool(SlotTable):
     """A fixed-capacity generation pool (WaveNetEngine.generation_pool): `capacity` slots over ONE set of layer rings, each
     slot holding its own stream at its own step.  Streams `join` free slots (from prompts of any lengths and, for a
     conditioned decoder, with their own encodings), `step` runs every live slot with one launch per chunk, and a stream
@@ -227,14 +219,6 @@ class GenerationPool:
         """Each slot's own step of its next sample."""
         return self._t.copy()
 
-    @property
-    def active(self) -> List[int]:
-        return [int(u) for u in np.flatnonzero(self._active)]
-
-    @property
-    def free(self) -> List[int]:
-        return [int(u) for u in np.flatnonzero(~self._active)]
-
     def _upload(self):
         from . import _lib
         tab = np.zeros(self.capacity, dtype=np.dtype(_lib.SrwnGenSlot))      # (srwn.h's layout, 16 bytes a slot)
@@ -257,16 +241,8 @@ class GenerationPool:
         samp = None
         if temperature is not None or top_k is not None or top_p is not None:
             samp = sampling_table(n, temperature, top_k, top_p, self.C, self.mol, "join")
-
-        def per_stream(x, what):
-            if x is None or np.isscalar(x):
-                return [x] * n
-            x = list(x)
-            if len(x) != n:
-                raise ValueError("join: %d seeds but %d %s" % (n, len(x), what))
-            return x
         ps = []
-        for p in per_stream(prompts, "prompts") if prompts is not None else [None] * n:
+        for p in per_stream(prompts, n, "prompts"):
             if p is None:
                 ps.append(np.zeros(0, np.float32))
                 continue
@@ -274,12 +250,12 @@ class GenerationPool:
             if p.ndim != 1:
                 raise ValueError("join: each prompt is 1-D [P], got shape %s" % (p.shape,))
             ps.append(p.astype(np.float32))
-        mx = per_stream(max_samples, "max_samples")
+        mx = per_stream(max_samples, n, "max_samples")
         limits = [INT32_MAX] * n
         if self.conditioned:
             if cond is None:
                 raise ValueError("this decoder is conditioned: pass cond, one [frames, %d] per stream" % self.E)
-            cond = per_stream(list(cond), "encodings")
+            cond = per_stream(list(cond), n, "encodings")
             for i, c in enumerate(cond):
                 shp = tuple(c.shape) if hasattr(c, "shape") else np.shape(c)
                 if len(shp) != 2 or shp[1] != self.E or not 1 <= shp[0] <= self.frames:
@@ -287,17 +263,7 @@ class GenerationPool:
                 limits[i] = shp[0] * self.pool_stride
         elif cond is not None:
             raise ValueError("this decoder is not conditioned")
-        free = self.free
-        if slots is None:
-            if n > len(free):
-                raise ValueError("join: %d streams but %d free slots" % (n, len(free)))
-            slots = free[:n]
-        else:
-            slots = [int(u) for u in slots]
-            if len(slots) != n or len(set(slots)) != n:
-                raise ValueError("join: slots must name %d distinct slots" % n)
-            if any(u < 0 or u >= self.capacity or self._active[u] for u in slots):
-                raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
+        slots = self._take_slots(n, slots)
         ends = []
         for p, m, lim in zip(ps, mx, limits):
             if len(p) > lim:
@@ -380,10 +346,7 @@ class GenerationPool:
 
     def leave(self, slots) -> None:
         """Ends the streams in `slots` (a slot already free stays free) and frees their slots."""
-        slots = [int(u) for u in slots]
-        if any(u < 0 or u >= self.capacity for u in slots):
-            raise ValueError("leave: slots %s outside the pool's %d" % (slots, self.capacity))
-        for u in slots:
+        for u in self._slot_list(slots, "leave"):
             self._active[u] = False
             self._end[u] = self._t[u]
         self._upload()

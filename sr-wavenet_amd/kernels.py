@@ -9,6 +9,7 @@ from __future__ import annotations
 from typing import List, Optional, Tuple
 
 import ctypes as _ct
+import gc
 
 import torch
 
@@ -27,6 +28,34 @@ def abi_dtype(dt: torch.dtype) -> int:
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _need_gpu() -> None:
+    if not torch.cuda.is_available():
+        raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+
+
+def run_cached_graph(graphs: dict, seen: set, key, enabled: bool, launch) -> None:
+    """Runs the launch sequence `launch()` of `key`: a replay of its hipGraph once captured; on the second sight of the
+    key (with graphs `enabled`) the sequence is captured, kept in `graphs` and replayed; before that, and with graphs
+    off, eager launches.  The caller's buffers are persistent, so a replay sees each call's new inputs."""
+    g = graphs.get(key)
+    if g is not None:
+        g.replay()
+    elif enabled and key in seen:
+        torch.cuda.synchronize()
+        # torch.cuda.graph (torch 2.10) collects garbage before a capture only under torch.compiler.config.force_cudagraph_gc;
+        # a collection that starts inside the capture and reaches a dead synthesizer <-> pool cycle destroys its hipGraphs
+        # and buffers mid-capture and aborts
+        gc.collect()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            launch()
+        graphs[key] = g
+        g.replay()
+    else:
+        seen.add(key)
+        launch()
 
 
 def _chk(t: torch.Tensor, name: str, dtype=None, shape=None):

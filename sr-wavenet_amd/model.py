@@ -27,6 +27,7 @@ import torch
 
 from . import kernels as K
 from .engine import StackConfig, WaveNetEngine
+from .slots import SlotTable, per_stream, slot_list
 
 
 def _train_step(eng):
@@ -49,6 +50,40 @@ def _train_step(eng):
 
 def _default_dtype():
     return torch.float32 if os.environ.get("SRWN_DTYPE", "bf16").lower() in ("f32", "fp32", "float32") else torch.bfloat16
+
+
+# --- conditions ---------------------------------------------------------------------------------------------------
+# The reference concatenates a clip's conditions onto every frame of its encoding (encoding_w_condition: model.py:161-167
+# for the decoder, model.py:496-499 for the student's flows).
+def _tile_conditions(frames, cond):
+    """frames [B, k, latent] and conditions [B, condition_size] (torch, one device) -> [B, k, latent + condition_size]."""
+    return torch.cat([frames, cond[:, None, :].expand(-1, frames.shape[1], -1)], dim=2)
+
+
+def _tile_conditions_np(frames, cond):
+    """One stream in NumPy: frames [k, latent] and conditions [1, condition_size] -> [k, latent + condition_size]."""
+    return np.concatenate([frames, np.repeat(cond, frames.shape[0], 0)], 1)
+
+
+def _check_conditions(batch, conditions, condition_size, who):
+    """conditions as float32 NumPy [batch, condition_size] (None when the model `who` has none); no device work."""
+    if condition_size <= 0:
+        return None
+    if conditions is None:
+        raise ValueError("this %s was built with condition_size > 0; pass conditions [%d, %d]" % (who, batch, condition_size))
+    c = np.asarray(conditions, dtype=np.float32)
+    if c.shape != (batch, condition_size):
+        raise ValueError("conditions must be [%d, %d]" % (batch, condition_size))
+    return c
+
+
+def _to_device(c):
+    return None if c is None else torch.as_tensor(c).to("cuda")
+
+
+def _device_conditions(batch, conditions, condition_size, who):
+    """The same, checked and then on the device (the caller has asked for the GPU)."""
+    return _to_device(_check_conditions(batch, conditions, condition_size, who))
 
 
 # --- checkpoint files --------------------------------------------------------------------------------------------
@@ -102,8 +137,7 @@ class _EngineOwner:
     """Builds one engine per (batch, length) seen, all sharing the same parameters."""
 
     def _setup(self, cfg: StackConfig, seed: int):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         self._cfg = cfg
         self._seed = seed
         self._engines: Dict[tuple, WaveNetEngine] = {}
@@ -271,7 +305,7 @@ class WaveNetTeacher(_EngineOwner):
             e = torch.as_tensor(np.asarray(encoding, dtype=np.float32), device="cuda")
             if self.condition_size > 0:
                 c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
-                e = torch.cat([e, c[:, None, :].expand(-1, e.shape[1], -1)], dim=2)   # model.py:162-165
+                e = _tile_conditions(e, c)
             cond = e.contiguous()
         codes = None
         if self.head == "softmax":
@@ -324,15 +358,7 @@ class WaveNetTeacher(_EngineOwner):
         self._check_sampling(batch_size, ctl, "generate")
         eng = self._primary or self._engine(1, self._default_length)
         f = None if forced is None else torch.as_tensor(np.asarray(forced, dtype=np.float32), device="cuda")
-        cond = None
-        if self.use_encoding:
-            if encoding is None:
-                raise ValueError("this teacher was built with use_encoding=True; pass encoding [B, frames, latent]")
-            cond = torch.as_tensor(np.asarray(encoding, dtype=np.float32), device="cuda")
-            if self.condition_size > 0:
-                c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
-                cond = torch.cat([cond, c[:, None, :].expand(-1, cond.shape[1], -1)], dim=2)
-            cond = cond.contiguous()
+        cond = self._generation_cond(encoding, conditions)
         a, c, lg = eng.generate(int(num_samples), mode=mode, seed=seed, forced=f, want_logits=return_logits,
                                 batch=int(batch_size), cond=cond, **ctl)
         if return_logits:
@@ -401,17 +427,17 @@ class WaveNetTeacher(_EngineOwner):
         cond = torch.as_tensor(np.asarray(encoding, dtype=np.float32), device="cuda")
         if self.condition_size > 0:
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
-            cond = torch.cat([cond, c[:, None, :].expand(-1, cond.shape[1], -1)], dim=2)
+            cond = _tile_conditions(cond, c)
         return cond.contiguous()
 
 
 def _pool_encodings(n, encoding, conditions, latent, condition_size):
     """The per-stream encodings of a pool join: n of [frames_i, latent] (+ conditions [condition_size] tiled over the
-    frames, model.py:161-167) -> n float32 arrays [frames_i, latent + condition_size]."""
+    frames) -> n float32 arrays [frames_i, latent + condition_size]."""
     if encoding is None:
         raise ValueError("this decoder is conditioned: pass encoding, one [frames, latent] per stream")
-    encs = _per_stream(encoding, n, "encodings")
-    conds = _per_stream(conditions, n, "conditions")
+    encs = per_stream(encoding, n, "encodings")
+    conds = per_stream(conditions, n, "conditions")
     out = []
     for e, c in zip(encs, conds):
         e = np.asarray(e, dtype=np.float32)
@@ -420,8 +446,7 @@ def _pool_encodings(n, encoding, conditions, latent, condition_size):
         if condition_size > 0:
             if c is None:
                 raise ValueError("built with condition_size > 0: pass conditions, one [%d] per stream" % condition_size)
-            c = np.asarray(c, dtype=np.float32).reshape(1, condition_size)
-            e = np.concatenate([e, np.repeat(c, e.shape[0], 0)], 1)
+            e = _tile_conditions_np(e, np.asarray(c, dtype=np.float32).reshape(1, condition_size))
         out.append(e)
     return out
 
@@ -451,19 +476,30 @@ def _stream_chunks(eng, st, chunk, mode, max_samples):
         yield a.cpu().numpy()
 
 
-def _per_stream(x, n, what):
-    """A join argument as one entry per stream: None -> n Nones, else a list of exactly n entries."""
-    if x is None:
-        return [None] * n
-    if isinstance(x, (int, np.integer)):
-        return [int(x)] * n
-    x = list(x)
-    if len(x) != n:
-        raise ValueError("join: %d seeds but %d %s" % (n, len(x), what))
-    return x
+def _ran_dict(a, ran, slots):
+    """A pool step's device rows a [capacity, n] as {slot: its ran[slot] samples} (NumPy) for the `slots` that made some."""
+    a = a.cpu().numpy()
+    return {u: a[u, :int(ran[u])] for u in slots if ran[u] > 0}
 
 
-class GenerationPool(object):
+def _audio_pieces(slots, audio):
+    """What a pool's ``push`` was given as one array per slot: one slot, or one 1-D array, is a single piece."""
+    one = np.isscalar(slots) or (isinstance(audio, np.ndarray) and audio.dtype != object and audio.ndim == 1)
+    return [np.asarray(a) for a in ([audio] if one else audio)]
+
+
+class _PoolFace(object):
+    """What the NumPy faces of the pools share: ``self._pool``'s slot view, forwarded."""
+
+    capacity = property(lambda self: self._pool.capacity)
+    active = property(lambda self: self._pool.active)
+    free = property(lambda self: self._pool.free)
+
+    def leave(self, slots):
+        self._pool.leave(slots)
+
+
+class GenerationPool(_PoolFace):
     """NumPy face of a generation pool (engine.GenerationPool): a fixed number of slots over one set of rings that streams
     join and leave while it runs.  ``join(seed=[...], prompt=[...], ...)`` takes one entry per stream and returns their
     slots; ``step(n)`` runs n pool steps in one launch and returns ``{slot: samples}`` of every slot that produced some; a
@@ -473,21 +509,7 @@ class GenerationPool(object):
     def __init__(self, pool, cond_fn, mode):
         self._pool, self._cond_fn, self.mode = pool, cond_fn, mode
 
-    @property
-    def capacity(self):
-        return self._pool.capacity
-
-    @property
-    def active(self):
-        return self._pool.active
-
-    @property
-    def free(self):
-        return self._pool.free
-
-    @property
-    def t(self):
-        return self._pool.t
+    t = property(lambda self: self._pool.t)
 
     def join(self, seed, prompt=None, encoding=None, conditions=None, max_samples=None, *, temperature=None, top_k=None,
              top_p=None):
@@ -495,12 +517,12 @@ class GenerationPool(object):
         default), as `generate` takes them."""
         seeds = [int(s) for s in (seed if np.ndim(seed) else [seed])]
         n = len(seeds)
-        prompts = _per_stream(prompt, n, "prompts")
+        prompts = per_stream(prompt, n, "prompts")
         for p in prompts:
             if p is not None and np.ndim(p) != 1:
                 raise ValueError("join: each prompt is 1-D [P], got shape %s" % (np.shape(p),))
         prompts = [None if p is None else np.asarray(p, dtype=np.float32) for p in prompts]
-        mx = _per_stream(max_samples, n, "max_samples")
+        mx = per_stream(max_samples, n, "max_samples")
         cond = self._cond_fn(n, encoding, conditions)
         if temperature is None and top_k is None and top_p is None:
             return self._pool.join(seeds, prompts, cond, mx)
@@ -508,11 +530,7 @@ class GenerationPool(object):
 
     def step(self, n, mode=None, forced=None):
         a, _, _, ran = self._pool.step(int(n), mode=mode or self.mode, forced=forced)
-        a = a.cpu().numpy()
-        return {u: a[u, :int(ran[u])] for u in range(self._pool.capacity) if ran[u] > 0}
-
-    def leave(self, slots):
-        self._pool.leave([slots] if np.isscalar(slots) else slots)
+        return _ran_dict(a, ran, range(self._pool.capacity))
 
 
 class WaveNetAutoEncoder(object):
@@ -526,8 +544,7 @@ class WaveNetAutoEncoder(object):
     def __init__(self, input_size, condition_size, num_mixtures, dilations, filter_width=2, encoder_channels=128,
                  dilation_channels=32, skip_channels=256, latent_channels=16, pool_stride=512,
                  name="WaveNetAutoEncoder", learning_rate=0.001, dtype=None, seed=0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         self._ctor = dict(input_size=int(input_size), condition_size=int(condition_size),
                           num_mixtures=int(num_mixtures), dilations=[int(d) for d in dilations],
                           filter_width=int(filter_width), encoder_channels=int(encoder_channels),
@@ -706,7 +723,7 @@ class WaveNetAutoEncoder(object):
             if conditions is None:
                 raise ValueError("this auto-encoder was built with condition_size > 0; pass conditions")
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
-            e = torch.cat([e, c[:, None, :].expand(-1, frames, -1)], dim=2)               # model.py:161-167
+            e = _tile_conditions(e, c)
         eng = self._eng or self._engine(B, frames * self.pool_stride)
         a, _, _ = eng.dec.generate(T, mode=mode, seed=seed, batch=B, cond=e.contiguous(), **ctl)
         return a.cpu().numpy()
@@ -755,7 +772,7 @@ class WaveNetAutoEncoder(object):
             if conditions is None:
                 raise ValueError("this auto-encoder was built with condition_size > 0; pass conditions")
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
-            e = torch.cat([e, c[:, None, :].expand(-1, frames, -1)], dim=2)               # model.py:161-167
+            e = _tile_conditions(e, c)
         eng = self._eng or self._engine(B, frames * self.pool_stride)
         st = eng.dec.generation_state(B, e.contiguous(), seed, **(ctl or {}))
         if p is not None:
@@ -785,16 +802,10 @@ class WaveNetAutoEncoder(object):
             if p.shape[1] > pf.shape[1] * self.pool_stride:
                 raise ValueError("prompt of %d samples exceeds frames * pool_stride = %d"
                                  % (p.shape[1], pf.shape[1] * self.pool_stride))
-        if self.condition_size > 0:
-            if conditions is None:
-                raise ValueError("this auto-encoder was built with condition_size > 0; pass conditions")
-            c = np.asarray(conditions, dtype=np.float32)
-            if c.shape != (batch, self.condition_size):
-                raise ValueError("conditions must be [%d, %d]" % (batch, self.condition_size))
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        c = _check_conditions(batch, conditions, self.condition_size, "auto-encoder")
+        K._need_gpu()
         eng = self._eng or self._engine(batch, max_frames * self.pool_stride)
-        cond = torch.as_tensor(c).to("cuda") if self.condition_size > 0 else None
+        cond = _to_device(c)
         st = eng.dec.live_generation_state(batch, max_frames, seed, temperature=temperature)
         live = LiveDecoding(self, eng.dec, st, cond, mode)
         if pf is not None:
@@ -812,28 +823,17 @@ class WaveNetAutoEncoder(object):
                              "(model.py:100,276): it raises there too")
 
 
-class LiveDecoding(object):
-    """One running batch of live decoder streams (``WaveNetAutoEncoder.live``).  ``feed(encoding [B, k, latent])`` hands
-    every stream its next k frames (k <= ``room``), ``step(n)`` returns the next n <= ``available`` samples [B, n]; ``t``:
-    samples made so far (a prompt's included), ``fed``: frames fed.  The samples are those ``generate`` gives the whole
-    encoding with the same seed and temperature, however the frames and chunks were cut."""
+class _LiveStream(object):
+    """What ``LiveDecoding`` and ``LiveSynthesis`` share: a running batch of ``batch_size`` streams of ``_owner`` on the
+    engine state ``_st``, fed through a conditioning ring of ``_ring`` frames, with the conditions ``_cond`` (device, or
+    None) tiled onto every frame fed.  A subclass gives ``room``, ``_take`` (the engine call the frames go to) and
+    ``step`` / ``_step_device``."""
 
-    def __init__(self, owner, dec, state, cond, mode):
-        self._owner, self._dec, self._st, self._cond, self._mode = owner, dec, state, cond, mode
-        self.batch_size = state.batch
+    def __init__(self, owner, state, cond, batch, ring):
+        self._owner, self._st, self._cond, self.batch_size, self._ring = owner, state, cond, batch, ring
 
-    @property
-    def t(self):
-        return self._st.t
-
-    @property
-    def fed(self):
-        return self._st.fed
-
-    @property
-    def room(self):
-        from .engine import live_decode_room
-        return live_decode_room(self._st.max_frames, self._st.fed, self._st.t, self._owner.pool_stride)
+    t = property(lambda self: self._st.t)
+    fed = property(lambda self: self._st.fed)
 
     @property
     def available(self):
@@ -841,7 +841,7 @@ class LiveDecoding(object):
         return self._st.limit - self._st.t
 
     def _feed_device(self, enc):
-        """enc [B, k, latent] on the device (or NumPy): + the tiled conditions (model.py:161-167), into the ring."""
+        """enc [B, k, latent] on the device (or NumPy): + the tiled conditions, into the ring."""
         o = self._owner
         e = torch.as_tensor(enc, dtype=torch.float32)
         if e.dim() != 3 or e.shape[0] != self.batch_size or e.shape[2] != o.latent_channels:
@@ -849,13 +849,32 @@ class LiveDecoding(object):
                              % (self.batch_size, o.latent_channels, tuple(e.shape)))
         if e.shape[1] > self.room:
             raise ValueError("feed: %d frames, but the ring of %d has room for %d at t = %d with %d fed"
-                             % (e.shape[1], self._st.max_frames, self.room, self.t, self.fed))
+                             % (e.shape[1], self._ring, self.room, self.t, self.fed))
         if self._cond is not None:
-            e = torch.cat([e.to("cuda"), self._cond[:, None, :].expand(-1, e.shape[1], -1)], dim=2)
-        self._dec.feed(self._st, e)
+            e = _tile_conditions(e.to("cuda"), self._cond)
+        self._take(e)
 
     def feed(self, encoding):
         self._feed_device(encoding if isinstance(encoding, torch.Tensor) else np.asarray(encoding, dtype=np.float32))
+
+
+class LiveDecoding(_LiveStream):
+    """One running batch of live decoder streams (``WaveNetAutoEncoder.live``).  ``feed(encoding [B, k, latent])`` hands
+    every stream its next k frames (k <= ``room``), ``step(n)`` returns the next n <= ``available`` samples [B, n]; ``t``:
+    samples made so far (a prompt's included), ``fed``: frames fed.  The samples are those ``generate`` gives the whole
+    encoding with the same seed and temperature, however the frames and chunks were cut."""
+
+    def __init__(self, owner, dec, state, cond, mode):
+        super().__init__(owner, state, cond, state.batch, state.max_frames)
+        self._dec, self._mode = dec, mode
+
+    @property
+    def room(self):
+        from .engine import live_decode_room
+        return live_decode_room(self._st.max_frames, self._st.fed, self._st.t, self._owner.pool_stride)
+
+    def _take(self, e):
+        self._dec.feed(self._st, e)
 
     def _step_device(self, n, forced=None, want_logits=False):
         """(audio [B, n] f32, selected mixture [B, n] i32, logits [B, n, 4M] f32 or None) on the device."""
@@ -868,62 +887,44 @@ class LiveDecoding(object):
         return (a.cpu().numpy(), lg.cpu().numpy()) if return_logits else a.cpu().numpy()
 
 
-class TeacherResynthesizer(object):
-    """The live auto-encoder loop at teacher quality: an ``AudioEncoder`` feeding the autoregressive decoder of a
-    ``WaveNetAutoEncoder`` (``Resynthesizer`` is the same pipeline on the student).  Audio chunks in, decoded audio chunks
-    out, with no bound on the length; the latent frames go from the encoder into the decoder's conditioning ring as device
-    tensors.  The audio of a stream put together equals ``autoencoder.generate(encoder.encode(audio), conditions,
-    seed=seed, ...)`` however the audio and the chunks were cut."""
-
-    def __init__(self, encoder, autoencoder, max_frames=None):
-        if not isinstance(encoder, AudioEncoder) or not isinstance(autoencoder, WaveNetAutoEncoder):
-            raise TypeError("TeacherResynthesizer(encoder: AudioEncoder, autoencoder: WaveNetAutoEncoder)")
-        if int(encoder.pool_stride) != int(autoencoder.pool_stride):
-            raise ValueError("pool_stride: the encoder makes a frame per %d samples, the decoder reads one per %d"
-                             % (encoder.pool_stride, autoencoder.pool_stride))
-        if int(encoder.latent_channels) != int(autoencoder.latent_channels):
-            raise ValueError("latent_channels: the encoder gives %d, the decoder takes %d"
-                             % (encoder.latent_channels, autoencoder.latent_channels))
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
-        self.encoder, self.autoencoder = encoder, autoencoder
-        self.pool_stride = int(encoder.pool_stride)
-        self.max_frames = int(max_frames if max_frames is not None else encoder.max_frames)
-        # samples of audio a sample of output waits for beyond itself: the rest of its frame and the encoder's look-ahead
-        self.lookahead = self.pool_stride + encoder.num_layers + 1
-
-    def stream(self, batch=1, conditions=None, seed=0, temperature=1.0, chunk_size=160):
-        """A ``TeacherResynthesisStream`` of `batch` streams in lockstep: ``push(audio [B, m])`` returns every sample that
-        can be made by now, [B, m']; ``finish()`` the rest.  conditions [B, condition_size] are tiled onto every frame on
-        the device; chunk_size: the most samples of one decoder launch."""
-        batch, chunk_size = int(batch), int(chunk_size)
-        if not 1 <= batch <= self.encoder.max_batch:
-            raise ValueError("batch %d: the encoder holds %d streams" % (batch, self.encoder.max_batch))
-        if chunk_size < 1:
-            raise ValueError("chunk_size %d: at least 1" % chunk_size)
-        return TeacherResynthesisStream(self, batch, conditions, seed, temperature, chunk_size)
+def _check_resynthesis_halves(who, encoder, other, other_type, arg, half):
+    """What both resynthesizers ask of their halves -- an ``AudioEncoder`` and `other` (the argument `arg`, of
+    `other_type`, whose `half` reads the frames) with one pool_stride and one latent width.  Returns ``lookahead``: the
+    samples of audio a sample of output waits for beyond itself, the rest of its frame and the encoder's look-ahead."""
+    if not isinstance(encoder, AudioEncoder) or not isinstance(other, other_type):
+        raise TypeError("%s(encoder: AudioEncoder, %s: %s)" % (who, arg, other_type.__name__))
+    if int(encoder.pool_stride) != int(other.pool_stride):
+        raise ValueError("pool_stride: the encoder makes a frame per %d samples, the %s reads one per %d"
+                         % (encoder.pool_stride, half, other.pool_stride))
+    if int(encoder.latent_channels) != int(other.latent_channels):
+        raise ValueError("latent_channels: the encoder gives %d, the %s takes %d"
+                         % (encoder.latent_channels, half, other.latent_channels))
+    return int(encoder.pool_stride) + encoder.num_layers + 1
 
 
-class TeacherResynthesisStream(object):
-    """One running batch of ``TeacherResynthesizer.stream``.  ``t``: samples returned so far per stream; ``received``:
-    samples pushed.  ``push`` may return no sample ([B, 0]) while the first frame's look-ahead is incomplete."""
+class _ResynthesisStream(object):
+    """One running batch of a resynthesizer's ``stream``: an encoder stream state ``_enc`` whose frames go, on the device,
+    into the live half ``_live`` (a ``_LiveStream``).  ``t``: samples returned so far per stream; ``received``: samples
+    pushed.  ``push`` may return no sample while the first frame's look-ahead is incomplete.  A subclass gives
+    ``_start_live``, ``_audio`` (the audio of what its live half's ``_step_device`` returns) and ``_tail``, the axes its
+    results have after [B, m]."""
+
+    _tail = ()
 
     def __init__(self, owner, batch, conditions, seed, temperature, chunk_size):
         self._owner, self.batch_size, self._chunk = owner, batch, chunk_size
-        self._live = owner.autoencoder.live(batch, conditions, owner.max_frames, seed=seed, temperature=temperature)
+        self._live = self._start_live(batch, conditions, seed, temperature)      # (its refusals come before any device work)
         self._enc = owner.encoder._eng.start(batch)
 
-    @property
-    def t(self):
-        return self._live.t
+    t = property(lambda self: self._live.t)
+    received = property(lambda self: self._enc.received)
 
-    @property
-    def received(self):
-        return self._enc.received
+    def _audio(self, chunk):
+        return chunk
 
     def _drain(self, frames, outs):
         """frames [B, k, latent] (device) into the ring and every sample they allow: feed -> step -> feed while the ring
-        has less room than the frames that are due (the drain loop of ``ResynthesisStream``)."""
+        has less room than the frames that are due."""
         live, k, f0 = self._live, int(frames.shape[1]), 0
         while True:
             if f0 < k:
@@ -933,15 +934,16 @@ class TeacherResynthesisStream(object):
                     f0 += r
             n = min(live.available, self._chunk)
             if n <= 0:
-                if f0 < k:      # (cannot happen: room > 0 once every sample of the fed frames is made)
+                if f0 < k:      # (cannot happen on a ring that starts a live stream: room > 0 once every sample is made)
                     raise RuntimeError("the conditioning ring has no room and no sample to make")
                 return
-            outs.append(live._step_device(n)[0])
+            outs.append(self._audio(live._step_device(n)))
 
     def _result(self, outs):
+        B = self.batch_size
         if not outs:
-            return np.zeros((self.batch_size, 0), np.float32)
-        return torch.cat(outs, dim=1).cpu().numpy()
+            return np.zeros((B, 0) + self._tail, np.float32)
+        return torch.cat(outs, dim=1).view(B, -1, *self._tail).cpu().numpy()
 
     def push(self, audio):
         if self._enc.closed:
@@ -958,6 +960,44 @@ class TeacherResynthesisStream(object):
         return self._result(outs)
 
 
+class TeacherResynthesizer(object):
+    """The live auto-encoder loop at teacher quality: an ``AudioEncoder`` feeding the autoregressive decoder of a
+    ``WaveNetAutoEncoder`` (``Resynthesizer`` is the same pipeline on the student).  Audio chunks in, decoded audio chunks
+    out, with no bound on the length; the latent frames go from the encoder into the decoder's conditioning ring as device
+    tensors.  The audio of a stream put together equals ``autoencoder.generate(encoder.encode(audio), conditions,
+    seed=seed, ...)`` however the audio and the chunks were cut."""
+
+    def __init__(self, encoder, autoencoder, max_frames=None):
+        self.lookahead = _check_resynthesis_halves("TeacherResynthesizer", encoder, autoencoder, WaveNetAutoEncoder,
+                                                   "autoencoder", "decoder")
+        K._need_gpu()
+        self.encoder, self.autoencoder = encoder, autoencoder
+        self.pool_stride = int(encoder.pool_stride)
+        self.max_frames = int(max_frames if max_frames is not None else encoder.max_frames)
+
+    def stream(self, batch=1, conditions=None, seed=0, temperature=1.0, chunk_size=160):
+        """A ``TeacherResynthesisStream`` of `batch` streams in lockstep: ``push(audio [B, m])`` returns every sample that
+        can be made by now, [B, m']; ``finish()`` the rest.  conditions [B, condition_size] are tiled onto every frame on
+        the device; chunk_size: the most samples of one decoder launch."""
+        batch, chunk_size = int(batch), int(chunk_size)
+        if not 1 <= batch <= self.encoder.max_batch:
+            raise ValueError("batch %d: the encoder holds %d streams" % (batch, self.encoder.max_batch))
+        if chunk_size < 1:
+            raise ValueError("chunk_size %d: at least 1" % chunk_size)
+        return TeacherResynthesisStream(self, batch, conditions, seed, temperature, chunk_size)
+
+
+class TeacherResynthesisStream(_ResynthesisStream):
+    """One running batch of ``TeacherResynthesizer.stream``: ``push`` / ``finish`` return samples [B, m]."""
+
+    def _start_live(self, batch, conditions, seed, temperature):
+        o = self._owner
+        return o.autoencoder.live(batch, conditions, o.max_frames, seed=seed, temperature=temperature)
+
+    def _audio(self, chunk):
+        return chunk[0]      # of (audio, selected mixture, logits)
+
+
 class AudioEncoder(object):
     """The deployable form of the auto-encoder's encoder (createEncoder, model.py:136-156): audio in, latent frames out
     (``encoder.FrameEncoder``), with no decoder and no training state anywhere.  One object serves any batch <=
@@ -969,8 +1009,7 @@ class AudioEncoder(object):
                  filter_width=2, name="WaveNetAutoEncoder", dtype=None, max_batch=1, max_frames=32):
         from .encoder import EncoderWeights, FrameEncoder, _check_encoder_widths
         _check_encoder_widths(encoder_channels, filter_width, skip_channels)
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         self.num_layers, self.skip_channels, self.latent_channels = int(num_layers), skip_channels, latent_channels
         self.pool_stride, self.encoder_channels, self.filter_width = int(pool_stride), encoder_channels, filter_width
         self._name = name
@@ -1030,8 +1069,7 @@ class AudioEncoder(object):
         """An ``AudioEncoderPool``: this encoder's ``max_batch`` rows as slots that streams join and leave, each pushing
         audio of any length at a clock of its own (``encoder.EncoderPool``).  audio_ring: samples a slot can hold
         (default max_frames * pool_stride + num_layers + 1 + pool_stride); max_rows: frames per launch."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         return AudioEncoderPool(self._eng.pool(audio_ring, max_rows))
 
 
@@ -1062,7 +1100,7 @@ class EncoderStream(object):
         return self._owner._eng.finish(self._st).cpu().numpy()
 
 
-class AudioEncoderPool(object):
+class AudioEncoderPool(_PoolFace):
     """NumPy face of an encoder pool (``AudioEncoder.pool``; encoder.EncoderPool).  ``join`` returns slots,
     ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``finish(slots)`` ends streams, ``step()`` returns
     ``{slot: frames [k, latent]}`` for every slot with new frames and frees the finished slots whose frames are all out.
@@ -1071,9 +1109,6 @@ class AudioEncoderPool(object):
     def __init__(self, pool):
         self._pool = pool
 
-    capacity = property(lambda self: self._pool.capacity)
-    active = property(lambda self: self._pool.active)
-    free = property(lambda self: self._pool.free)
     received = property(lambda self: self._pool.received)
     emitted = property(lambda self: self._pool.emitted)
 
@@ -1084,15 +1119,10 @@ class AudioEncoderPool(object):
         return self._pool.join(n, slots)
 
     def push(self, slots, audio):
-        one = np.isscalar(slots) or (isinstance(audio, np.ndarray) and audio.dtype != object and audio.ndim == 1)
-        audio = [audio] if one else list(audio)
-        self._pool.push([int(slots)] if np.isscalar(slots) else slots, [np.asarray(a) for a in audio])
+        self._pool.push([int(slots)] if np.isscalar(slots) else slots, _audio_pieces(slots, audio))
 
     def finish(self, slots):
         self._pool.finish(slots)
-
-    def leave(self, slots):
-        self._pool.leave(slots)
 
     def step(self, limit=None):
         return {u: f.cpu().numpy() for u, f in self._pool.step(limit).items()}
@@ -1112,8 +1142,7 @@ class ParallelWaveNet(object):
     def __init__(self, input_size, condition_size, dilations, teacher, num_flows=2, filter_width=2,
                  dilation_channels=32, skip_channels=256, latent_channels=16, pool_stride=512,
                  name="ParallelWaveNet", alpha=1.0, beta=1.0, gamma=1.0, learning_rate=0.001, dtype=None, seed=0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         self.input_size = input_size
         self.condition_size = condition_size
         self.dilations = dilations
@@ -1195,7 +1224,7 @@ class ParallelWaveNet(object):
             if conditions is None:
                 raise ValueError("this student was built with condition_size > 0; pass conditions [B, condition_size]")
             c = torch.as_tensor(np.asarray(conditions, dtype=np.float32), device="cuda")
-            e = torch.cat([e, c[:, None, :].expand(-1, e.shape[1], -1)], dim=2)          # model.py:496-499
+            e = _tile_conditions(e, c)
         if tuple(e.shape) != (B, T // self.pool_stride, self.latent_channels + self.condition_size):
             raise ValueError("encoding must be [batch, samples/pool_stride, latent_channels]")
         tr = None if truth is None else torch.as_tensor(np.asarray(truth, dtype=np.float32), device="cuda")
@@ -1308,8 +1337,7 @@ class StudentSynthesizer(object):
 
     def __init__(self, dilations, num_flows, filter_width=2, dilation_channels=32, latent_channels=16, condition_size=0,
                  pool_stride=512, name="ParallelWaveNet", dtype=None, max_batch=1, max_chunk=1600, max_frames=32):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         from .student import FlowSynthesizer
         self.dilations, self.num_flows = list(dilations), int(num_flows)
         self.filter_width, self.dilation_channels = filter_width, dilation_channels
@@ -1359,7 +1387,7 @@ class StudentSynthesizer(object):
             c = np.asarray(conditions, dtype=np.float32)
             if c.shape != (B, self.condition_size):
                 raise ValueError("conditions must be [%d, %d]" % (B, self.condition_size))
-            e = torch.cat([e, torch.as_tensor(c)[:, None, :].expand(-1, frames, -1)], dim=2)   # model.py:496-499
+            e = _tile_conditions(e, torch.as_tensor(c))
         T = frames * self.pool_stride
         nz = None
         if noise is not None:
@@ -1397,31 +1425,18 @@ class StudentSynthesizer(object):
     def pool(self):
         """A ``SynthesisPool`` on this synthesizer's buffers: ``max_batch`` slots that streams join and leave while it
         runs.  It ends a running ``stream``; the next ``synthesize`` / ``stream`` closes the pool."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         return SynthesisPool(self._eng.pool(), self.latent_channels, self.condition_size)
 
     def live(self, batch, conditions=None, seed=0, temperature=1.0):
         """A ``LiveSynthesis`` of `batch` streams whose encoding arrives while they run: ``feed`` frames, ``step`` samples,
         with no bound on the length (the conditioning tables are rings of ``max_frames`` frames).  conditions
         [batch, condition_size] are tiled onto every fed frame.  It ends a running ``stream`` or pool, like ``synthesize``."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         return LiveSynthesis(self, int(batch), conditions, seed, temperature)
 
-    def _device_conditions(self, batch, conditions):
-        """conditions [batch, condition_size] on the device (None when the student has none)."""
-        if self.condition_size <= 0:
-            return None
-        if conditions is None:
-            raise ValueError("this student was built with condition_size > 0; pass conditions [B, condition_size]")
-        c = np.asarray(conditions, dtype=np.float32)
-        if c.shape != (batch, self.condition_size):
-            raise ValueError("conditions must be [%d, %d]" % (batch, self.condition_size))
-        return torch.as_tensor(c).to("cuda")
 
-
-class LiveSynthesis(object):
+class LiveSynthesis(_LiveStream):
     """One running batch of live streams (``StudentSynthesizer.live``).  ``feed(encoding [B, k, latent])`` hands every
     stream its next k frames (k <= ``room``), ``step(n)`` returns the next n <= ``available`` samples [B, n, 1]; ``t``:
     samples made so far.  The samples are those ``synthesize`` gives the whole encoding with the same seed and
@@ -1430,40 +1445,16 @@ class LiveSynthesis(object):
     def __init__(self, owner, batch, conditions, seed, temperature):
         if not 1 <= batch <= owner.max_batch:
             raise ValueError("batch %d: this synthesizer was built for max_batch=%d" % (batch, owner.max_batch))
-        self._owner, self.batch_size = owner, batch
-        self._cond = owner._device_conditions(batch, conditions)
-        self._st = owner._eng.start(None, seed, temperature, live=True, batch=batch)
-
-    @property
-    def t(self):
-        return self._st.t
-
-    @property
-    def fed(self):
-        return self._st.fed
+        cond = _device_conditions(batch, conditions, owner.condition_size, "student")
+        super().__init__(owner, owner._eng.start(None, seed, temperature, live=True, batch=batch), cond, batch,
+                         owner.max_frames)
 
     @property
     def room(self):
         return self._owner._eng.room(self._st)
 
-    @property
-    def available(self):
-        """Samples that can be made now: fed * pool_stride - t."""
-        return self._st.limit - self._st.t
-
-    def _feed_device(self, enc):
-        """enc [B, k, latent] on the device (or NumPy): + the tiled conditions (model.py:496-499), into the rings."""
-        o = self._owner
-        e = torch.as_tensor(enc, dtype=torch.float32)
-        if e.dim() != 3 or e.shape[0] != self.batch_size or e.shape[2] != o.latent_channels:
-            raise ValueError("encoding must be [%d, k, latent_channels=%d], got %s"
-                             % (self.batch_size, o.latent_channels, tuple(e.shape)))
-        if self._cond is not None:
-            e = torch.cat([e.to("cuda"), self._cond[:, None, :].expand(-1, e.shape[1], -1)], dim=2)
-        o._eng.feed(self._st, e)
-
-    def feed(self, encoding):
-        self._feed_device(encoding if isinstance(encoding, torch.Tensor) else np.asarray(encoding, dtype=np.float32))
+    def _take(self, e):
+        self._owner._eng.feed(self._st, e)
 
     def _step_device(self, n):
         return self._owner._eng.step(self._st, n)
@@ -1473,7 +1464,7 @@ class LiveSynthesis(object):
         return self._step_device(n).view(self.batch_size, n, 1).cpu().numpy()
 
 
-class SynthesisPool(object):
+class SynthesisPool(_PoolFace):
     """NumPy face of a student synthesis pool (student.SynthPool): ``join(encoding=[...], ...)`` takes one
     [frames_i, latent] per stream and returns their slots; ``step(n)`` advances every live slot by n samples with the
     launches of one synthesizer chunk and returns ``{slot: samples}`` of every slot that produced some; a stream that
@@ -1484,21 +1475,7 @@ class SynthesisPool(object):
         self._pool, self._latent, self._cs = pool, latent, condition_size
         self._live_cond = {}      # slot -> the conditions of the live stream joined there last
 
-    @property
-    def capacity(self):
-        return self._pool.capacity
-
-    @property
-    def active(self):
-        return self._pool.active
-
-    @property
-    def free(self):
-        return self._pool.free
-
-    @property
-    def t(self):
-        return self._pool.t
+    t = property(lambda self: self._pool.t)
 
     def join(self, encoding, conditions=None, seed=0, temperature=None, max_samples=None, live=False):
         """encoding: one [frames_i, latent] per stream (a single 2-D array: one stream); conditions: one [condition_size]
@@ -1506,8 +1483,8 @@ class SynthesisPool(object):
         live=True: the streams are fed while they run (``feed``); an encoding holds a stream's first frames ([0, latent]:
         none yet), its conditions are kept and tiled onto every frame fed later; a live stream that has used up its frames
         waits (no samples) until it is fed, closed or left."""
-        if live and not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        if live:
+            K._need_gpu()
         if isinstance(encoding, np.ndarray) and encoding.ndim == 2:
             encoding = [encoding]
             conditions = None if conditions is None else [conditions]
@@ -1515,13 +1492,13 @@ class SynthesisPool(object):
         cond = _pool_encodings(len(encoding), encoding, conditions, self._latent, self._cs)
         slots = self._pool.join(cond, seed, temperature, max_samples, live=live)
         if live and self._cs > 0:
-            for u, c in zip(slots, _per_stream(conditions, len(slots), "conditions")):
+            for u, c in zip(slots, per_stream(conditions, len(slots), "conditions")):
                 self._live_cond[u] = np.asarray(c, dtype=np.float32).reshape(1, self._cs)
         return slots
 
     def feed(self, slots, encoding):
         """The next frames of live slots: encoding[i] [k_i, latent] for slots[i] (k_i <= ``room``)."""
-        slots = [int(slots)] if np.isscalar(slots) else [int(u) for u in slots]
+        slots = slot_list(slots, self.capacity, "feed")
         if isinstance(encoding, np.ndarray) and encoding.ndim == 2:
             encoding = [encoding]
         encs = [np.asarray(e, dtype=np.float32) for e in encoding]
@@ -1533,7 +1510,7 @@ class SynthesisPool(object):
         if self._cs > 0:
             if any(u not in self._live_cond for u in slots):
                 raise ValueError("feed: slots %s are not all live streams of this pool" % (slots,))
-            encs = [np.concatenate([e, np.repeat(self._live_cond[u], e.shape[0], 0)], 1) for u, e in zip(slots, encs)]
+            encs = [_tile_conditions_np(e, self._live_cond[u]) for u, e in zip(slots, encs)]
         self._pool.feed(slots, encs)
 
     def room(self, slot):
@@ -1541,15 +1518,11 @@ class SynthesisPool(object):
 
     def close(self, slots):
         """No more frames will come for these live streams: each frees its slot at the end of what it was fed."""
-        self._pool.close([slots] if np.isscalar(slots) else slots)
+        self._pool.close(slots)
 
     def step(self, n):
         a, ran = self._pool.step(int(n))
-        a = a.cpu().numpy()
-        return {u: a[u, :int(ran[u])] for u in range(self._pool.capacity) if ran[u] > 0}
-
-    def leave(self, slots):
-        self._pool.leave([slots] if np.isscalar(slots) else slots)
+        return _ran_dict(a, ran, range(self._pool.capacity))
 
 
 class Resynthesizer(object):
@@ -1559,24 +1532,15 @@ class Resynthesizer(object):
     together equals ``synthesizer.synthesize(encoder.encode(audio), ...)`` however the audio was cut."""
 
     def __init__(self, encoder, synthesizer):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
-        if not isinstance(encoder, AudioEncoder) or not isinstance(synthesizer, StudentSynthesizer):
-            raise TypeError("Resynthesizer(encoder: AudioEncoder, synthesizer: StudentSynthesizer)")
-        if int(encoder.pool_stride) != int(synthesizer.pool_stride):
-            raise ValueError("pool_stride: the encoder makes a frame per %d samples, the synthesizer reads one per %d"
-                             % (encoder.pool_stride, synthesizer.pool_stride))
-        if int(encoder.latent_channels) != int(synthesizer.latent_channels):
-            raise ValueError("latent_channels: the encoder gives %d, the synthesizer takes %d"
-                             % (encoder.latent_channels, synthesizer.latent_channels))
+        K._need_gpu()
+        self.lookahead = _check_resynthesis_halves("Resynthesizer", encoder, synthesizer, StudentSynthesizer, "synthesizer",
+                                                   "synthesizer")
         cs = synthesizer.condition_size
         if synthesizer._eng.E != encoder.latent_channels + cs:
             raise ValueError("condition_size %d: the synthesizer's flows read %d channels, not %d + %d"
                              % (cs, synthesizer._eng.E, encoder.latent_channels, cs))
         self.encoder, self.synthesizer = encoder, synthesizer
         self.pool_stride = int(encoder.pool_stride)
-        # samples of audio a sample of output waits for beyond itself: the rest of its frame and the encoder's look-ahead
-        self.lookahead = self.pool_stride + encoder.num_layers + 1
 
     def stream(self, batch=1, conditions=None, seed=0, temperature=1.0, chunk_size=160):
         """A ``ResynthesisStream`` of `batch` streams in lockstep: ``push(audio [B, m])`` returns every sample that can be
@@ -1594,67 +1558,20 @@ class Resynthesizer(object):
         """A ``ResynthesisPool``: independent callers on one encoder and one synthesizer.  Streams join and leave while the
         batch runs, audio arrives ragged, and each caller receives what it would have received alone.  chunk_size: the
         samples a ``step`` makes per stream at most; audio_ring: samples of audio a slot can hold (``AudioEncoder.pool``)."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         return ResynthesisPool(self, int(chunk_size), audio_ring)
 
 
-class ResynthesisStream(object):
-    """One running batch of ``Resynthesizer.stream``.  ``t``: samples returned so far per stream; ``received``: samples
-    pushed.  ``push`` may return no sample ([B, 0, 1]) while the first frame's look-ahead is incomplete."""
+class ResynthesisStream(_ResynthesisStream):
+    """One running batch of ``Resynthesizer.stream``: ``push`` / ``finish`` return samples [B, m, 1]."""
 
-    def __init__(self, owner, batch, conditions, seed, temperature, chunk_size):
-        self._owner, self.batch_size, self._chunk = owner, batch, chunk_size
-        self._enc = owner.encoder._eng.start(batch)
-        self._live = owner.synthesizer.live(batch, conditions, seed, temperature)
+    _tail = (1,)
 
-    @property
-    def t(self):
-        return self._live.t
-
-    @property
-    def received(self):
-        return self._enc.received
-
-    def _drain(self, frames, outs):
-        """frames [B, k, latent] (device) into the rings and every sample they allow: feed -> step -> feed while the
-        ring has less room than the frames that are due."""
-        live, k, f0 = self._live, int(frames.shape[1]), 0
-        while True:
-            if f0 < k:
-                r = min(live.room, k - f0)
-                if r > 0:
-                    live._feed_device(frames[:, f0:f0 + r])
-                    f0 += r
-            n = min(live.available, self._chunk)
-            if n <= 0:
-                if f0 < k:      # (cannot happen on a ring that starts a live stream: room > 0 once every sample is made)
-                    raise RuntimeError("the conditioning ring has no room and no sample to make")
-                return
-            outs.append(live._step_device(n))
-
-    def _result(self, outs):
-        B = self.batch_size
-        if not outs:
-            return np.zeros((B, 0, 1), np.float32)
-        return torch.cat(outs, dim=1).view(B, -1, 1).cpu().numpy()
-
-    def push(self, audio):
-        if self._enc.closed:
-            raise ValueError("this stream is closed (finish was called)")
-        x = self._owner.encoder._check(audio, self.batch_size)
-        outs = []
-        self._drain(self._owner.encoder._eng.push(self._enc, torch.as_tensor(x)), outs)
-        return self._result(outs)
-
-    def finish(self):
-        """The encoder's remaining whole frames (clip-end padding) and the samples they allow; closes the stream."""
-        outs = []
-        self._drain(self._owner.encoder._eng.finish(self._enc), outs)
-        return self._result(outs)
+    def _start_live(self, batch, conditions, seed, temperature):
+        return self._owner.synthesizer.live(batch, conditions, seed, temperature)
 
 
-class ResynthesisPool(object):
+class ResynthesisPool(SlotTable):
     """``Resynthesizer.pool()``: an encoder pool and a live synthesis pool sharing slot ids; capacity is the smaller
     ``max_batch``.  ``join`` returns slots, ``push(slots, audio)`` takes one 1-D array per slot of any length (at most
     ``audio_room(slot)``), ``finish(slots)`` ends streams, ``step()`` returns ``{slot: samples}``.  One step: the encoder
@@ -1681,12 +1598,8 @@ class ResynthesisPool(object):
         self._cond = {}        # slot -> its stream's conditions [1, condition_size] on the device (None without)
 
     @property
-    def active(self):
-        return sorted(self._cond)
-
-    @property
-    def free(self):
-        return [u for u in range(self.capacity) if u not in self._cond]
+    def _active(self):      # (what SlotTable reads: a slot is taken while it has an entry in _cond)
+        return np.array([u in self._cond for u in range(self.capacity)], bool)
 
     @property
     def t(self):
@@ -1701,7 +1614,7 @@ class ResynthesisPool(object):
         return self._enc.audio_room(int(slot))
 
     def _slots(self, slots, who):
-        slots = [int(slots)] if np.isscalar(slots) else [int(u) for u in slots]
+        slots = self._slot_list(slots, who)
         if any(u not in self._cond for u in slots):
             raise ValueError("%s: slots %s do not all hold a stream of this pool" % (who, slots))
         return slots
@@ -1710,18 +1623,9 @@ class ResynthesisPool(object):
         """n streams into the lowest free slots; conditions [n, condition_size] (one row per stream), seed a scalar s
         (stream i draws with s + i) or one per stream, temperature None, a scalar or one per stream.  Returns the slots."""
         n = int(n)
-        free = self.free
-        if n < 1 or n > len(free):
-            raise ValueError("join: %d streams but %d free slots" % (n, len(free)))
-        conds = [None] * n
-        if self._cs > 0:
-            if conditions is None:
-                raise ValueError("this student was built with condition_size > 0; pass conditions [n, condition_size]")
-            c = np.asarray(conditions, dtype=np.float32)
-            if c.shape != (n, self._cs):
-                raise ValueError("conditions must be [%d, %d]" % (n, self._cs))
-            conds = [torch.as_tensor(c[i:i + 1]).to("cuda") for i in range(n)]
-        slots = free[:n]
+        slots = self._take_slots(n, None)
+        c = _device_conditions(n, conditions, self._cs, "student")
+        conds = [None if c is None else c[i:i + 1] for i in range(n)]
         self._syn.join([None] * n, seed, temperature, slots=slots, live=True)
         self._enc.join(slots=slots)
         for u, c in zip(slots, conds):
@@ -1729,9 +1633,7 @@ class ResynthesisPool(object):
         return slots
 
     def push(self, slots, audio):
-        one = np.isscalar(slots) or (isinstance(audio, np.ndarray) and audio.dtype != object and audio.ndim == 1)
-        audio = [audio] if one else list(audio)
-        self._enc.push(self._slots(slots, "push"), [np.asarray(a) for a in audio])
+        self._enc.push(self._slots(slots, "push"), _audio_pieces(slots, audio))
 
     def finish(self, slots):
         """No more audio comes for these streams; each frees its slot once its last sample has been returned."""
@@ -1752,17 +1654,13 @@ class ResynthesisPool(object):
         frames = enc.step({u: syn.room(u) for u in enc.active})
         if frames:
             us = sorted(frames)
-            fr = [frames[u] if self._cond[u] is None else
-                  torch.cat([frames[u], self._cond[u].expand(frames[u].shape[0], -1)], dim=1) for u in us]   # model.py:496-499
+            fr = [frames[u] if self._cond[u] is None else _tile_conditions(frames[u][None], self._cond[u])[0] for u in us]
             syn.feed(us, fr)
         done = [u for u in self._cond if not enc._active[u]]          # finished and fully encoded: the stream's end is known
         if done:
             syn.close(done)
         a, ran = syn.step(self._chunk)
-        out = {}
-        if ran.any():
-            a = a.cpu().numpy()
-            out = {u: a[u, :int(ran[u])] for u in self._cond if ran[u] > 0}
+        out = _ran_dict(a, ran, self._cond) if ran.any() else {}
         for u in [u for u in self._cond if not syn._active[u]]:
             del self._cond[u]
         return out

@@ -27,6 +27,7 @@ from . import dp
 from . import kernels as K
 from ._lib import call
 from .engine import SQRT_HALF, Section, StackConfig, WaveNetEngine, _Span
+from .slots import SlotTable, per_stream
 
 
 class FlowStorage:
@@ -528,8 +529,7 @@ class FlowSynthesizer:
 
     def __init__(self, flow_cfg: StackConfig, num_flows: int, max_batch: int = 1, max_chunk: int = 1600,
                  max_frames: int = 32, device="cuda"):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         if not flow_cfg.cond_channels:
             raise ValueError("a flow is conditioned on the encoding (model.py:431): cond_channels > 0")
         if flow_cfg.gate_mode != "reference":
@@ -683,8 +683,7 @@ class FlowSynthesizer:
     def pool(self) -> "SynthPool":
         """A ``SynthPool`` on this synthesizer's buffers: max_batch slots, each a stream at a clock of its own.  The current
         ``SynthState`` (and an earlier pool) ends here, as at ``start``; ``start`` closes the pool."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         if self._pool is not None:
             self._pool._open = False
         self._serial += 1
@@ -742,25 +741,13 @@ class FlowSynthesizer:
             if tuple(nz.shape) != (B, n):
                 raise ValueError("noise must be [%d, %d], got %s" % (B, n, tuple(nz.shape)))
             self.xbuf[0][:B, :n].copy_(nz.to(self.dev))
-        key = (B, n, noise is None)
-        g = self._graphs.get(key)
-        if g is not None:
-            g.replay()
-        elif self.use_graphs and key in self._seen:      # second use of this (batch, chunk size): capture, then replay
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._launch_chunk(B, n, noise is None)
-            self._graphs[key] = g
-            g.replay()
-        else:
-            self._seen.add(key)
-            self._launch_chunk(B, n, noise is None)
+        K.run_cached_graph(self._graphs, self._seen, (B, n, noise is None), self.use_graphs,      # per (batch, chunk size)
+                           lambda: self._launch_chunk(B, n, noise is None))
         state.t += n
         return self.xbuf[self.F][:B, :n].clone()
 
 
-class SynthPool:
+class SynthPool(SlotTable):
     """``FlowSynthesizer.pool()``: the synthesizer's ``max_batch`` rows as SLOTS, each holding a stream at a clock of its
     own (srwn.h, SrwnSynthSlot).  Streams ``join`` free slots with their encodings, seeds and temperatures, ``step`` runs
     every live slot with the launches of one synthesizer chunk, and a stream that reaches its end or ``leave``s frees its
@@ -768,8 +755,7 @@ class SynthPool:
     encoding, seed and temperature -- in any slot, whenever it joined, whatever the chunk sizes and the other slots."""
 
     def __init__(self, syn: "FlowSynthesizer"):
-        if not torch.cuda.is_available():
-            raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
+        K._need_gpu()
         self.syn, self.capacity = syn, syn.max_batch
         self.frames, self.pool_stride, self.E = syn.max_frames, syn.pool_stride, syn.E
         self._t = np.zeros(self.capacity, np.int64)          # host mirror of the device table (the kernel advances both)
@@ -789,14 +775,6 @@ class SynthPool:
     def t(self) -> np.ndarray:
         """Each slot's own time of its next sample."""
         return self._t.copy()
-
-    @property
-    def active(self) -> List[int]:
-        return [int(u) for u in np.flatnonzero(self._active)]
-
-    @property
-    def free(self) -> List[int]:
-        return [int(u) for u in np.flatnonzero(~self._active)]
 
     def _check_open(self):
         if not self._open:
@@ -833,39 +811,18 @@ class SynthPool:
             if c.dim() != 2 or c.shape[1] != self.E or not (0 if live else 1) <= c.shape[0] <= self.frames:
                 raise ValueError("join: cond %d must be [%d..%d frames, %d], got %s"
                                  % (i, 0 if live else 1, self.frames, self.E, tuple(c.shape)))
-
-        def per_stream(x, what, default):
-            if x is None:
-                return [default] * n
-            if np.ndim(x) == 0:
-                return [x] * n
-            x = list(x)
-            if len(x) != n:
-                raise ValueError("join: %d encodings but %d %s" % (n, len(x), what))
-            return [default if v is None else v for v in x]
         sd = np.asarray(seeds)
-        sd = [int(sd) + i for i in range(n)] if sd.ndim == 0 else [int(s) for s in per_stream(seeds, "seeds", 0)]
-        tp = [float(v) for v in per_stream(temperature, "temperatures", 1.0)]
+        sd = [int(sd) + i for i in range(n)] if sd.ndim == 0 else [int(s) for s in per_stream(seeds, n, "seeds", default=0)]
+        tp = [float(v) for v in per_stream(temperature, n, "temperatures", default=1.0)]
         if not np.all(np.isfinite(tp)) or any(v < 0 for v in tp):
             raise ValueError("join: temperature must be finite and >= 0")
         ends = []
-        for c, m in zip(cond, per_stream(max_samples, "max_samples", None)):
+        for c, m in zip(cond, per_stream(max_samples, n, "max_samples")):
             lim = int(c.shape[0]) * self.pool_stride
             if m is not None and int(m) < 0:
                 raise ValueError("join: max_samples %d" % int(m))
             ends.append(lim if m is None else min(lim, int(m)))
-        free = self.free
-        if slots is None:
-            if n > len(free):
-                raise ValueError("join: %d streams but %d free slots" % (n, len(free)))
-            slots = free[:n]
-        else:
-            slots = [int(u) for u in slots]
-            if len(slots) != n or len(set(slots)) != n:
-                raise ValueError("join: slots must name %d distinct slots" % n)
-            if any(u < 0 or u >= self.capacity or self._active[u] for u in slots):
-                raise ValueError("join: slots %s are not all free slots of this pool" % (slots,))
-        return cond, sd, tp, slots, ends
+        return cond, sd, tp, self._take_slots(n, slots), ends
 
     def join(self, cond, seeds=0, temperature=None, max_samples=None, slots=None, live=False) -> List[int]:
         """n streams into free slots (the lowest ones, or `slots`): cond n encodings [frames_i <= max_frames, E]; seeds one
@@ -915,12 +872,6 @@ class SynthPool:
         return list(slots)
 
     # ---- live slots
-    def _slot_list(self, slots, who):
-        slots = [int(u) for u in (slots if np.ndim(slots) else [slots])]
-        if any(u < 0 or u >= self.capacity for u in slots):
-            raise ValueError("%s: slots %s outside the pool's %d" % (who, slots, self.capacity))
-        return slots
-
     def room(self, slot: int) -> int:
         """Frames a live slot may be fed now (``live_room``); 0 for every other slot."""
         self._check_open()
@@ -976,10 +927,7 @@ class SynthPool:
     def leave(self, slots) -> None:
         """Ends the streams in `slots` (a slot already free stays free) and frees their slots."""
         self._check_open()
-        slots = [int(u) for u in (slots if np.ndim(slots) else [slots])]
-        if any(u < 0 or u >= self.capacity for u in slots):
-            raise ValueError("leave: slots %s outside the pool's %d" % (slots, self.capacity))
-        for u in slots:
+        for u in self._slot_list(slots, "leave"):
             self._active[u] = False
             self._live[u] = False
             self._end[u] = self._t[u]
@@ -1005,20 +953,8 @@ class SynthPool:
             return torch.zeros((B, n), dtype=torch.float32, device=syn.dev), ran
         if nz is not None:
             syn.xbuf[0][:, :n].copy_(nz.to(syn.dev))
-        key = (n, noise is None)
-        g = self._graphs.get(key)
-        if g is not None:
-            g.replay()
-        elif syn.use_graphs and key in self._seen:      # second use of this chunk size: capture, then replay
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                syn._launch_chunk(B, n, noise is None, self)
-            self._graphs[key] = g
-            g.replay()
-        else:
-            self._seen.add(key)
-            syn._launch_chunk(B, n, noise is None, self)
+        K.run_cached_graph(self._graphs, self._seen, (n, noise is None), syn.use_graphs,      # per chunk size
+                           lambda: syn._launch_chunk(B, n, noise is None, self))
         self._t += ran
         self._active &= (self._t < self._end) | (self._live & ~self._closed)      # a starved live slot stays
         return syn.xbuf[syn.F][:, :n].clone(), ran
