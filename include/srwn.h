@@ -1130,6 +1130,72 @@ int srwn_small_wgrad(const float* a, int64_t lda, const float* d, int64_t ldd, f
 int srwn_mol_sample(const float* logits, int64_t ldl, int32_t M, const float* u1, const float* u2, float* out,
                     int64_t rows, void* stream);
 
+/* ---- streaming classifier (since srwn_version() 113; csrc/srwn_recog.hip, csrc/srwn_group.hip): the causal stack of class
+ * WaveNet (createNetwork, model.py:33-62: input conv 40, residual layers 42-47, skip sum 50-51, head 1x1s 53-56, the
+ * sliding AVG pool 58 and the softmax 60) as an inference-only stream over audio of any length.  The input placeholder
+ * of the reference graph is [None, None]: on T > input_size samples the VALID pool yields T - input_size + 1 rows, one
+ * per window position; a stream emits the row of every `hop`-th position.  `window` is a multiple of `hop`; the stack
+ * advances by whole hops at hop-aligned absolute times only (audio that does not fill a hop waits with the caller).
+ *   H_j = sum of r1[t] over t in [j * hop, (j + 1) * hop)            fp32 [S], r1 = relu(W1 relu(sum_l skip_l + bs) + b1)
+ *   e_j = softmax(((H_{j-nW+1} + ... + H_j) / window) @ W2 + b2)     nW = window / hop, j >= nW - 1, oldest block first
+ * e_j is the graph's pooled output at position (j + 1) * hop - window.  State of a batch of B streams: a device clock
+ * (int64 absolute time of the next chunk's first row), per layer group of srwn_group_plan a boundary buffer
+ * [B][hist + max_chunk][R] (hist = the sum of the group's dilations), a carry [B] fp32 (the sample before the chunk) and
+ * the ring [B][ring_rows][S] fp32 of hop sums, H_j in row j mod ring_rows; all zero at the stream's start.  A chunk is
+ * n = k * hop rows, 1 <= n <= max_chunk.  R in {32, 64}, dtype SRWN_BF16 or SRWN_F32; no RightShift, no conditioning.
+ *
+ *   srwn_recog_stream_in    model.py:40 for rows [out_hist, out_hist + n) of the first boundary buffer: h0[t] = w0 x[t-1]
+ *                           + w1 x[t] + b (init_w [2,1,R], init_b [R], fp32) on x [B, x_stride] fp32, x[-1] of the chunk
+ *                           from carry[b]; arithmetic and rounding of srwn_causal_conv1d_fwd with shift 0.
+ *   srwn_residual_group_fwd_stream_z
+ *                           srwn_residual_group_fwd_stream (its arguments, its bits in x_out) that ALSO stores z of
+ *                           every layer of the group for the chunk's own rows (never history or halo rows): chunk row t
+ *                           of stream b of layer g at z_out + g * z_layer_stride + ((b * max_chunk) + t) * R, with the
+ *                           bits srwn_residual_group_fwd gives that row on the whole clip.  z_layer_stride >= B *
+ *                           max_chunk * R elements.  cond_next: NULL, or all entries NULL.
+ *   srwn_pooled_stream_head model.py:50-54 and the hop sums of a chunk of k hops in one launch, one workgroup per
+ *                           (stream, hop): per 32-row tile of the hop, in time order (the last one masked when hop % 32
+ *                           != 0), the gate c = z sigmoid(z) rebuilt from the stored z as srwn_pw_linear's SRWN_PRO_GATE
+ *                           does, r0 = relu(bs_sum + sum_l Ws_l c_l), r1 = relu(W1 r0 + b1) -- both rounded to dtype
+ *                           where the training forward stores them, r0 exchanged through LDS -- and the tile's rows of
+ *                           r1 summed neighbours first (rows 2i + 2i+1, then pairs of pairs ...), the tile sums added
+ *                           to the hop's fp32 sum in time order.  H_j goes to ring row j mod ring_rows, j = *clock /
+ *                           hop + i for hop i of the chunk.  z [nlayers][B][z_clip_rows][R] at z_layer_stride; wskip:
+ *                           the packed skip image [S/32][nlayers * R / 16] (natural k order, k = l * R + n) and w1 the
+ *                           packed head image [S/32][S/16], as srwn_pw_linear takes them.  S in {128, 256}.
+ *   srwn_hop_sum            the parity twin of the head's last step: the same sums, in the same order, from r1
+ *                           [B][r1_clip_rows][S] (dtype) that two srwn_pw_linear calls wrote.  S even.
+ *   srwn_window_mean        mean[b * k + i][S] = (sum of the nW ring rows that end at hop j = *clock / hop + i, oldest
+ *                           first) / window, zeros while j < nW - 1 (no window has filled: VALID).  ring_rows >= nW + k
+ *                           - 1, S <= 256.  With logits != NULL also logits[b * k + i][C] = mean @ w2 + b2 (w2 [S, ldw],
+ *                           fp32) in srwn_pooled_head's arithmetic; srwn_pooled_head (labels NULL, B * k rows) gives the
+ *                           probabilities.
+ *   srwn_recog_roll         moves rows [n, n + hist) of every buffer of roll_table (nroll int64 triples {address, rows per
+ *                           stream, hist}, a device array) to its front as srwn_flow_stream_out does, sets carry[b] =
+ *                           x[b][n - 1] and adds n to *clock.  The last launch of a chunk.
+ * Errors: a null pointer (-3), a width that is not built (-4), a chunk or buffer that does not fit (-2), dtype (-1). */
+int srwn_recog_stream_in(const float* x, int64_t x_stride, const float* carry, const float* init_w, const float* init_b,
+                         void* out, int64_t out_clip_rows, int32_t out_hist, int32_t B, int32_t n, int32_t max_chunk,
+                         int32_t R, int32_t dtype, void* stream);
+int srwn_residual_group_fwd_stream_z(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                     int32_t out_hist, void* z_out, int64_t z_layer_stride, const void* const* wconv,
+                                     const void* const* wres, const float* const* bias_f, const float* const* bias_r,
+                                     const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                     int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers, int32_t B,
+                                     int32_t n, int32_t max_chunk, int32_t R, int32_t K, int32_t dtype,
+                                     const int64_t* clock, void* stream);
+int srwn_pooled_stream_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers, const void* wskip,
+                            const float* bs_sum, const void* w1, const float* b1, float* ring, int32_t ring_rows,
+                            const int64_t* clock, int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int32_t R,
+                            int32_t S, int32_t dtype, void* stream);
+int srwn_hop_sum(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows, const int64_t* clock, int32_t B,
+                 int32_t k, int32_t hop, int32_t max_chunk, int32_t S, int32_t dtype, void* stream);
+int srwn_window_mean(const float* ring, int32_t ring_rows, float* mean, const int64_t* clock, int32_t B, int32_t k,
+                     int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2, float* logits, int32_t C,
+                     int32_t ldw, void* stream);
+int srwn_recog_roll(const int64_t* roll_table, int32_t nroll, const float* x, int64_t x_stride, float* carry,
+                    int64_t* clock, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,16 @@ for _n in ("srwn_generate", "srwn_generate16"):
     SIGNATURES[_n + "_mol_live_sampled"] = SIGNATURES[_n + "_mol_resume_sampled"]
 del _n
 SIGNATURES["srwn_cond_ring_scatter"] = (C.c_int, [_p, _i64, _p, _i64, _i32, _i32, _i64, _i32, _i32, _i32, _p])
+# streaming classifier (srwn_version() 113): the stream entry, the z-storing stream group, the pooled head of a chunk of
+# hops and its parity twin, the window mean and the roll
+SIGNATURES["srwn_recog_stream_in"] = (C.c_int, [_p, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p])
+SIGNATURES["srwn_residual_group_fwd_stream_z"] = (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _p, _i32, _i32,
+                                                            _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p])
+SIGNATURES["srwn_pooled_stream_head"] = (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _i32,
+                                                   _i32, _i32, _i32, _p])
+SIGNATURES["srwn_hop_sum"] = (C.c_int, [_p, _i64, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p])
+SIGNATURES["srwn_window_mean"] = (C.c_int, [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p])
+SIGNATURES["srwn_recog_roll"] = (C.c_int, [_p, _i32, _p, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -81,6 +81,14 @@ struct GroupFwdSlotArgs : GroupFwdStreamArgs {
   const SrwnSynthSlot* slots;
 };
 
+// The ZS instantiations (srwn_residual_group_fwd_stream_z: the streaming classifier, whose head reads every layer's z) also
+// store z of every layer of the group, for the chunk's own rows only: chunk row t of stream b of layer g at
+// z_out + g * layer_stride + ((b * z_clip_rows) + t) * R.  A struct of its own, so that the other instantiations keep their
+// arguments.
+struct GroupFwdStreamZArgs : GroupFwdStreamArgs {
+  long long z_clip_rows;
+};
+
 // In-kernel time stamps (MI355X guide, "In-kernel stamps"): lane 0 of waves 0 and 1 of workgroup 0 append the shader
 // clock to a buffer no other code reads.  Compiled in only when a buffer was registered (STAMP instantiation).
 template <bool STAMP> struct Stamper {
@@ -103,11 +111,13 @@ template <> struct Stamper<true> {
 };
 
 template <typename T, int RT, bool COND, int MAXT, int NWB, int NWV = 8, bool WDMA = true, bool STAMP = false, bool WT = false, bool IC = false,
-          bool STREAM = false, bool SLOTS = false>
+          bool STREAM = false, bool SLOTS = false, bool ZS = false>
 __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
-    typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type>::type a) {
+    typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<ZS, GroupFwdStreamZArgs,
+        typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type>::type>::type a) {
   static_assert(!IC || (WT && !COND), "input conv fused in: the unconditioned weight-gradient-tile kernels only");
   static_assert(!SLOTS || STREAM, "slot form: a stream form");
+  static_assert(!ZS || (STREAM && !SLOTS), "z of the chunk's rows: the clock stream form only");
   static_assert(!STREAM || (COND && !WT && !IC && !STAMP), "stream form: the conditioned plain kernels only");
   constexpr int R = 32 * RT, K = 2, KS = R / 16;
   constexpr int NCONV = RT * K * KS, NRES = RT * KS, NW = NCONV + NRES;   // weight fragments per layer
@@ -438,7 +448,7 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
               cf[2 * mt + (qq >> 3)].set(qq & 7, gate_of_z<T>(z));
             }
           if (STAMP) { asm volatile("" :: "v"(zz[0][0])); stamp(13); }
-          if (!STREAM && st_ok) {       // (STREAM: no backward pass reads z)
+          if ((!STREAM || ZS) && st_ok) {       // (STREAM: no backward pass reads z; ZS: the classifier's head does)
             wave_lds_order();             // the reads of the own rows above are done
 #pragma unroll
             for (int mt = 0; mt < RT; ++mt)
@@ -452,6 +462,10 @@ __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
               int rr = i * RPI + rsub;
               rr = rr < lo ? lo : (rr < hi ? rr : hi - 1);
               const f32x4 v = *reinterpret_cast<const f32x4*>(trow + (size_t)rr * LS + piece * VEC);
+              if constexpr (ZS) {      // (owned rows lie behind the history: buffer row - hrows = chunk row; plain store, the head reads them next)
+                const long long zrow = (long long)b * a.z_clip_rows + (long long)(grow(jbase + 32 * q + rr) - clip) - a.hrows;
+                *reinterpret_cast<f32x4*>(zg + zrow * R + piece * VEC) = v;
+              } else
               __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(zg + grow(jbase + 32 * q + rr) * R + piece * VEC));
             }
           }
@@ -1418,8 +1432,8 @@ int launch_group_fwd(GroupFwdArgs& a, bool cond, int seg_rows, hipStream_t st) {
 // The stream form: segments over the chunk's positions of every residue class that holds a chunk row; the halo is always
 // the whole H (the history supplies it).  The cut depends on (B, n, st, H) and the chip alone -- never on the clock -- so a
 // captured launch stays valid for every chunk of its size.
-template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool SLOTS = false>
-int launch_group_fwd_stream(typename std::conditional<SLOTS, GroupFwdSlotArgs, GroupFwdStreamArgs>::type& a, int n, hipStream_t st) {
+template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool SLOTS = false, bool ZS = false>
+int launch_group_fwd_stream(typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<ZS, GroupFwdStreamZArgs, GroupFwdStreamArgs>::type>::type& a, int n, hipStream_t st) {
   constexpr int R = 32 * RT, KS = R / 16, NW = RT * 2 * KS + RT * KS;
   const size_t fixed = (size_t)NWB * NW * 64 * sizeof(Frag<T>) + (size_t)NWB * 2 * R * 4;
   const size_t row_bytes = (size_t)RowStage<T>::stride(R) * sizeof(T);
@@ -1447,11 +1461,11 @@ int launch_group_fwd_stream(typename std::conditional<SLOTS, GroupFwdSlotArgs, G
   const int grid_cap = group_grid();
   const long long blocks = nseg < grid_cap ? nseg : grid_cap;
   dim3 grid((unsigned)blocks), block(64 * NWV);
-  auto kfn = group_fwd_kernel<T, RT, true, MAXT, NWB, NWV, true, false, false, false, true, SLOTS>;
+  auto kfn = group_fwd_kernel<T, RT, true, MAXT, NWB, NWV, true, false, false, false, true, SLOTS, ZS>;
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
   if (e != hipSuccess) return set_error((int)e, "residual_group_fwd_stream: LDS %zu: %s", sh, hipGetErrorString(e));
   hipLaunchKernelGGL(kfn, grid, block, sh, st, a);
-  return check_launch(SLOTS ? "residual_group_fwd_stream_slots" : "residual_group_fwd_stream");
+  return check_launch(SLOTS ? "residual_group_fwd_stream_slots" : (ZS ? "residual_group_fwd_stream_z" : "residual_group_fwd_stream"));
 }
 
 template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool WT = false>
@@ -1716,12 +1730,16 @@ extern "C" int srwn_residual_group_fwd_wt(const void* x0, void* x_out, void* z_o
 // The inference / stream form of srwn_residual_group_fwd (srwn.h): one chunk of a batch of streams, the group's causal
 // context taken from the history rows in front of the chunk, time taken from a device clock.
 namespace {
-template <bool SLOTS>
+template <bool SLOTS, bool ZS = false>
 int group_fwd_stream_impl(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows, int32_t out_hist,
                           const void* const* wconv, const void* const* wres, const float* const* bias_f,
                           const float* const* bias_r, const void* const* cond_next, int32_t cond_frames,
                           int32_t pool_stride, int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers, int32_t B,
-                          int32_t n, int32_t max_chunk, int32_t R, int32_t K, int32_t dtype, const void* clock, void* stream) {
+                          int32_t n, int32_t max_chunk, int32_t R, int32_t K, int32_t dtype, const void* clock, void* stream,
+                          void* z_out = nullptr, int64_t z_layer_stride = 0) {
+  if (ZS && (!z_out || z_layer_stride < (int64_t)B * max_chunk * R))
+    return set_error(z_out ? SRWN_E_SHAPE : SRWN_E_NULL, "residual_group_fwd_stream_z: z_out [layers][B][max_chunk][R] with a "
+                     "layer stride of at least B * max_chunk * R elements (got %lld)", (long long)z_layer_stride);
   if (!x_in || !x_out || !wconv || !wres || !bias_f || !bias_r || !dilations || !clock)
     return set_error(SRWN_E_NULL, SLOTS ? "residual_group_fwd_stream_slots: null pointer (slots is the pool's device table)"
                                         : "residual_group_fwd_stream: null pointer (the clock is the synthesizer state's device scalar)");
@@ -1730,9 +1748,10 @@ int group_fwd_stream_impl(const void* x_in, int64_t in_clip_rows, void* x_out, i
   if (nlayers < 1 || nlayers > kMaxGroup || B < 1 || max_chunk < 1 || out_hist < 0)
     return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: nlayers=%d (max %d) B=%d max_chunk=%d out_hist=%d", nlayers, kMaxGroup, B, max_chunk, out_hist);
   if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  typename std::conditional<SLOTS, GroupFwdSlotArgs, GroupFwdStreamArgs>::type a;
+  typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<ZS, GroupFwdStreamZArgs, GroupFwdStreamArgs>::type>::type a;
   a.safe_wait = safe_wait();
   a.x0 = x_in; a.x_out = x_out; a.z_out = nullptr; a.layer_stride = 0;
+  if constexpr (ZS) { a.z_out = z_out; a.layer_stride = z_layer_stride; a.z_clip_rows = max_chunk; }
   a.xT = nullptr; a.cT = nullptr; a.wt_stride = 0; a.KT = 0; a.store_inner_x = 0;
   a.ic_audio = nullptr; a.ic_w = nullptr; a.ic_b = nullptr; a.ic_shift = 0;
   bool any_cond = false;
@@ -1764,11 +1783,11 @@ int group_fwd_stream_impl(const void* x_in, int64_t in_clip_rows, void* x_out, i
   a.in_clip_rows = in_clip_rows; a.out_clip_rows = out_clip_rows; a.out_row_off = (long long)out_hist - hrows;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SRWN_BF16) {
-    if (R == 32) return launch_group_fwd_stream<bf16_t, 1, 3, 2, 8, SLOTS>(a, n, st);
-    return launch_group_fwd_stream<bf16_t, 2, SRWN_GFS_MAXT, 2, SRWN_GFS_WAVES, SLOTS>(a, n, st);
+    if (R == 32) return launch_group_fwd_stream<bf16_t, 1, 3, 2, 8, SLOTS, ZS>(a, n, st);
+    return launch_group_fwd_stream<bf16_t, 2, SRWN_GFS_MAXT, 2, SRWN_GFS_WAVES, SLOTS, ZS>(a, n, st);
   } else if (dtype == SRWN_F32) {
-    if (R == 32) return launch_group_fwd_stream<float, 1, 1, 1, 8, SLOTS>(a, n, st);
-    return launch_group_fwd_stream<float, 2, 1, 1, 8, SLOTS>(a, n, st);
+    if (R == 32) return launch_group_fwd_stream<float, 1, 1, 1, 8, SLOTS, ZS>(a, n, st);
+    return launch_group_fwd_stream<float, 2, 1, 1, 8, SLOTS, ZS>(a, n, st);
   }
   return set_error(SRWN_E_DTYPE, "residual_group_fwd_stream: dtype %d", dtype);
 }
@@ -1784,6 +1803,20 @@ extern "C" int srwn_residual_group_fwd_stream(const void* x_in, int64_t in_clip_
   return group_fwd_stream_impl<false>(x_in, in_clip_rows, x_out, out_clip_rows, out_hist, wconv, wres, bias_f, bias_r,
                                       cond_next, cond_frames, pool_stride, cond_row_stride, dilations, nlayers, B, n,
                                       max_chunk, R, K, dtype, clock, stream);
+}
+
+// The z form (the streaming classifier, srwn.h): the clock form that also stores every layer's z of the chunk's own rows.
+extern "C" int srwn_residual_group_fwd_stream_z(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                                int32_t out_hist, void* z_out, int64_t z_layer_stride,
+                                                const void* const* wconv, const void* const* wres,
+                                                const float* const* bias_f, const float* const* bias_r,
+                                                const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                                int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers,
+                                                int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t K,
+                                                int32_t dtype, const int64_t* clock, void* stream) {
+  return group_fwd_stream_impl<false, true>(x_in, in_clip_rows, x_out, out_clip_rows, out_hist, wconv, wres, bias_f, bias_r,
+                                            cond_next, cond_frames, pool_stride, cond_row_stride, dilations, nlayers, B, n,
+                                            max_chunk, R, K, dtype, clock, stream, z_out, z_layer_stride);
 }
 
 // The slot form (synthesis pools): the same launch on the pool's table, every clip a slot at a clock of its own.

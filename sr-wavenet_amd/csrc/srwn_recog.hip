@@ -1,0 +1,388 @@
+// Streaming classifier: the causal stack of class WaveNet (model.py:33-62) as an inference-only stream that emits the
+// pooled output of every window position it has passed.  gfx950 (MI355X) only; MFMA orientation and lane maps:
+// srwn_common.h.  The stack itself runs through srwn_residual_group_fwd_stream_z (csrc/srwn_group.hip); here is what
+// stands around it, one launch each:
+//   stream entry   the K = 2 input conv (model.py:40, no RightShift, no conditioning) from the chunk's audio and a
+//                  one-sample carry, written behind the history rows of the first boundary buffer
+//   pooled head    skip sum from the stored z (gate rebuilt as the skip sum's SRWN_PRO_GATE does), relu, head 1x1, relu
+//                  (model.py:50-54) and the sum of r1 over each hop, one workgroup per (stream, hop): r0, r1 and the
+//                  per-step logits never reach HBM.  The hop sum lands in a per-stream ring of fp32 rows [S]
+//   hop sum        the parity twin of the head's last step: the same sum from an r1 buffer that srwn_pw_linear wrote
+//   window mean    (sum of the nW = window / hop ring rows that end at a hop, oldest first) / window: the pooled r1 of
+//                  the window position that ends there (the AVG pool of model.py:58 commutes with the last 1x1); the
+//                  existing srwn_pooled_head turns the rows into probabilities
+//   roll           the history roll of the boundary buffers, the carry and the clock
+// A stream only ever advances by whole hops at hop-aligned absolute times, and a hop's 32-row tiles are cut from the
+// hop's first row: every ring row depends on absolute time only, so a stream has the same bits in any chunking, at any
+// batch size and in any row of the batch.
+#include <cmath>
+#include "srwn_common.h"
+#include "srwn_host.h"
+#include "../../include/srwn.h"
+
+using namespace srwn;
+
+namespace {
+
+// ------------------------------------------------------------------------------------------
+// stream entry: 8 channels per thread, one row per group of R/8 lanes
+//   v = b; v = fma(x[t-1], w[0], v); v = fma(x[t], w[1], v); round to T          (srwn_causal_conv1d_fwd, shift 0)
+// x[-1] of the chunk is the carry (zero at the stream's start: the conv's zero padding).
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void recog_stream_in_kernel(const float* __restrict__ x, int64_t x_stride,
+                                                              const float* __restrict__ carry,
+                                                              const float* __restrict__ w, const float* __restrict__ bias,
+                                                              T* __restrict__ out, int64_t out_clip_rows, int hist, int B,
+                                                              int n, int R) {
+  const int lpr = R / 8;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = idx / lpr;
+  const int sub = (int)(idx % lpr);
+  if (row >= (int64_t)B * n) return;
+  const int b = (int)(row / n);
+  const int t = (int)(row - (int64_t)b * n);
+  const float* xb = x + (int64_t)b * x_stride;
+  const float x0 = t >= 1 ? xb[t - 1] : carry[b];
+  const float x1 = xb[t];
+  T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = bias[8 * sub + j];
+    v[j] = fmaf(x0, w[8 * sub + j], v[j]);
+    v[j] = fmaf(x1, w[R + 8 * sub + j], v[j]);
+  }
+  store4(d, v[0], v[1], v[2], v[3]);
+  store4(d + 4, v[4], v[5], v[6], v[7]);
+}
+
+// The sum of a tile's 32 rows in the order both forms of the hop sum use: neighbours first, then pairs of pairs ...
+// (what an xor butterfly over the 32 lanes of a half wave leaves in every lane).
+__device__ __forceinline__ float half_wave_sum(float v) {
+#pragma unroll
+  for (int s = 1; s < 32; s <<= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+// ------------------------------------------------------------------------------------------
+// pooled head of a chunk of k hops.  Workgroup = (stream b, hop i of the chunk), 4 waves; wave w owns the output
+// channels [w * S/4, (w + 1) * S/4) of both products.  Per 32-row tile of the hop, in time order:
+//   accS = bs_sum + sum_l Ws_l . gate(z_l)      B fragments: 8 channels of one z row per lane (natural k order), the gate
+//                                               on the fragment as pw_load_b<SRWN_PRO_GATE>; A fragments from the
+//                                               packed skip image in L2 (rows = skip channel, k = l * R + n)
+//   r0 = relu(accS) rounded to T -> xch[32][S]  LDS, rows = time: the B operand of the head 1x1 for all four waves
+//   acc1 = b1 + W1 . r0;  r1 = relu(acc1) rounded to T
+//   hsum += half_wave_sum(r1 of the tile's valid rows)
+// and at the end H[b][(j0 + i) mod ring][:] = hsum, j0 = *clock / hop.  The arithmetic of r0 and r1 is srwn_pw_linear's
+// (accumulators start at the bias, k-steps in order).
+// LDS: xch = 32 x (S + 16 / sizeof(T)) x sizeof(T) bytes -- 33 280 for S = 256 in fp32, 16 896 in bf16.
+// ------------------------------------------------------------------------------------------
+template <typename T, int R, int S>
+__global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
+                                                                  int64_t z_clip_rows, int L, const T* __restrict__ wskip,
+                                                                  const float* __restrict__ bs_sum,
+                                                                  const T* __restrict__ w1, const float* __restrict__ b1,
+                                                                  float* __restrict__ ring, int ring_rows,
+                                                                  const long long* __restrict__ clock, int k, int hop) {
+  constexpr int MTW = S / 128;                // 32-channel output tiles per wave
+  constexpr int KSL = R / 16;                 // k-steps per layer
+  constexpr int KS1 = S / 16;
+  constexpr int LS = RowStage<T>::stride(S);
+  __shared__ __attribute__((aligned(16))) T xch[32 * LS];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int col = lane & 31, half = lane >> 5;
+  const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
+  const int ks_skip = L * KSL;
+  const Frag<T>* ws = reinterpret_cast<const Frag<T>*>(wskip) + (size_t)(wave * MTW) * ks_skip * 64 + lane;
+  const Frag<T>* wh = reinterpret_cast<const Frag<T>*>(w1) + (size_t)(wave * MTW) * KS1 * 64 + lane;
+  float bsv[MTW][16], b1v[MTW][16], hsum[MTW][16];
+#pragma unroll
+  for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int n = 32 * (wave * MTW + mt) + crow(q, half);
+      bsv[mt][q] = bs_sum[n];
+      b1v[mt][q] = b1[n];
+      hsum[mt][q] = 0.0f;
+    }
+  const T* zb = z + ((int64_t)b * z_clip_rows + (int64_t)i * hop) * R + 8 * half;
+  for (int t0 = 0; t0 < hop; t0 += 32) {
+    const int valid = hop - t0 < 32 ? hop - t0 : 32;
+    const int trow = t0 + (col < valid ? col : valid - 1);      // (a masked column re-reads the hop's last row)
+    const T* zr = zb + (int64_t)trow * R;
+    f32x16 acc[MTW];
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[mt][q] = bsv[mt][q];
+    for (int l = 0; l < L; ++l) {
+      Frag<T> bf[KSL];
+#pragma unroll
+      for (int ks = 0; ks < KSL; ++ks) {
+        bf[ks] = load_nat(zr + (int64_t)l * z_layer_stride + 16 * ks);
+        gate_frag<T>(bf[ks]);
+      }
+#pragma unroll
+      for (int ks = 0; ks < KSL; ++ks)
+#pragma unroll
+        for (int mt = 0; mt < MTW; ++mt) mma(acc[mt], ws[((size_t)mt * ks_skip + l * KSL + ks) * 64], bf[ks]);
+    }
+    __syncthreads();                          // the previous tile's reads of xch are done
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        store4(xch + col * LS + 32 * (wave * MTW + mt) + 8 * g + 4 * half, fmaxf(acc[mt][4 * g], 0.0f),
+               fmaxf(acc[mt][4 * g + 1], 0.0f), fmaxf(acc[mt][4 * g + 2], 0.0f), fmaxf(acc[mt][4 * g + 3], 0.0f));
+    __syncthreads();
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) acc[mt][q] = b1v[mt][q];
+#pragma unroll 4
+    for (int ks = 0; ks < KS1; ++ks) {
+      const Frag<T> bf = load_nat(xch + col * LS + 16 * ks + 8 * half);
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt) mma(acc[mt], wh[((size_t)mt * KS1 + ks) * 64], bf);
+    }
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const float r1 = (float)(T)fmaxf(acc[mt][q], 0.0f);
+        hsum[mt][q] += half_wave_sum(col < valid ? r1 : 0.0f);
+      }
+  }
+  const long long j = *clock / hop + i;
+  float* dst = ring + ((int64_t)b * ring_rows + (int64_t)(j % ring_rows)) * S;
+  if (col == 0) {
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) dst[32 * (wave * MTW + mt) + crow(q, half)] = hsum[mt][q];
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// hop sum (parity twin): r1 [B][r1_clip_rows][S] of the chunk -> the ring rows of its k hops.  One wave per (stream, hop,
+// 2 channels): lane (col, half) reads row t0 + col of channel 2 * w + half, tiles in time order, the tile's rows summed as
+// the head kernel sums them.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void hop_sum_kernel(const T* __restrict__ r1, int64_t r1_clip_rows,
+                                                      float* __restrict__ ring, int ring_rows,
+                                                      const long long* __restrict__ clock, int k, int hop, int S) {
+  const int lane = threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const int col = lane & 31, half = lane >> 5;
+  const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
+  const long long j = *clock / hop + i;
+  float* dst = ring + ((int64_t)b * ring_rows + (int64_t)(j % ring_rows)) * S;
+  const T* src = r1 + ((int64_t)b * r1_clip_rows + (int64_t)i * hop) * S;
+  for (int s = 2 * wave + half; s < S; s += 8) {      // (both halves of a wave run the same number of rounds: S is even)
+    float h = 0.0f;
+    for (int t0 = 0; t0 < hop; t0 += 32) {
+      const int t = t0 + col;
+      const float v = t < hop ? (float)src[(int64_t)t * S + s] : 0.0f;
+      h += half_wave_sum(v);
+    }
+    if (col == 0) dst[s] = h;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// window mean: row (b * k + i) = (sum of the nW ring rows that end at hop j = *clock / hop + i, oldest first) / window,
+// zeros where no window has filled yet (j < nW - 1).  With `logits`, also mean @ w2 + b2 in srwn_pooled_head's arithmetic.
+// One workgroup per row.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void window_mean_kernel(const float* __restrict__ ring, int ring_rows,
+                                                          float* __restrict__ mean, const long long* __restrict__ clock,
+                                                          int k, int hop, int nW, float window, int S,
+                                                          const float* __restrict__ w2, const float* __restrict__ b2,
+                                                          float* __restrict__ logits, int C, int ldw) {
+  __shared__ float m[256];
+  const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
+  const long long j = *clock / hop + i;
+  const float* rb = ring + (int64_t)b * ring_rows * S;
+  for (int s = threadIdx.x; s < S; s += 256) {
+    float acc = 0.0f;
+    if (j >= nW - 1)
+      for (int w = 0; w < nW; ++w) acc += rb[(int64_t)((j - nW + 1 + w) % ring_rows) * S + s];
+    acc = acc / window;
+    m[s] = acc;
+    mean[(int64_t)blockIdx.x * S + s] = acc;
+  }
+  if (!logits) return;
+  __syncthreads();
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float acc = b2[c];
+    for (int s = 0; s < S; ++s) acc = fmaf(m[s], w2[(int64_t)s * ldw + c], acc);
+    logits[(int64_t)blockIdx.x * C + c] = acc;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// roll.  Blocks [0, nroll * B): one per (boundary buffer, stream), rows [n, n + hist) move to [0, hist) -- for n < hist the
+// ranges overlap: the block walks them front to back, each step reading all of its rows before it writes any (a barrier
+// between), and a row written in one step lies in front of every row a later step reads (srwn_flow_stream_out's roll).
+// The last block: carry[b] = x[b][n - 1] and *clock += n (nothing in this launch reads either).
+// ------------------------------------------------------------------------------------------
+struct RollEntry { void* buf; long long clip_rows; long long hist; };      // int64 triples, as the host's table holds them
+
+template <typename T, int R>
+__global__ __launch_bounds__(256) void recog_roll_kernel(const RollEntry* __restrict__ roll, int nroll,
+                                                         const float* __restrict__ x, int64_t x_stride,
+                                                         float* __restrict__ carry, long long* __restrict__ clock, int B,
+                                                         int n) {
+  if ((int)blockIdx.x == nroll * B) {
+    for (int b = threadIdx.x; b < B; b += 256) carry[b] = x[(int64_t)b * x_stride + n - 1];
+    if (threadIdx.x == 0) *clock = *clock + n;
+    return;
+  }
+  constexpr int PPR = R * (int)sizeof(T) / 16, RPB = 256 / PPR, U = 4;
+  const int kk = (int)blockIdx.x / B, b = (int)blockIdx.x % B;
+  const RollEntry e = roll[kk];
+  const int hist = (int)e.hist;
+  f32x4* base = reinterpret_cast<f32x4*>(reinterpret_cast<T*>(e.buf) + (size_t)b * (size_t)e.clip_rows * R);
+  const int piece = threadIdx.x % PPR, rloc = threadIdx.x / PPR;
+  for (int i0 = 0; i0 < hist; i0 += RPB * U) {
+    f32x4 v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = i0 + u * RPB + rloc;
+      if (i < hist) v[u] = base[(size_t)(i + n) * PPR + piece];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = i0 + u * RPB + rloc;
+      if (i < hist) base[(size_t)i * PPR + piece] = v[u];
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+extern "C" int srwn_recog_stream_in(const float* x, int64_t x_stride, const float* carry, const float* init_w,
+                                    const float* init_b, void* out, int64_t out_clip_rows, int32_t out_hist, int32_t B,
+                                    int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream) {
+  if (!x || !carry || !init_w || !init_b || !out) return set_error(SRWN_E_NULL, "recog_stream_in: null pointer");
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_stream_in: dilation_channels %d (built: 32, 64)", R);
+  if (B < 1 || max_chunk < 1 || out_hist < 0)
+    return set_error(SRWN_E_SHAPE, "recog_stream_in: B=%d max_chunk=%d out_hist=%d", B, max_chunk, out_hist);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_stream_in: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
+  if (x_stride < max_chunk || out_clip_rows < (int64_t)out_hist + max_chunk)
+    return set_error(SRWN_E_SHAPE, "recog_stream_in: x stride %lld, %lld buffer rows per stream for %d + %d",
+                     (long long)x_stride, (long long)out_clip_rows, out_hist, max_chunk);
+  const int64_t threads = (int64_t)B * n * (R / 8);
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16)
+    hipLaunchKernelGGL(recog_stream_in_kernel<bf16_t>, grid, block, 0, st, x, x_stride, carry, init_w, init_b, (bf16_t*)out,
+                       out_clip_rows, out_hist, B, n, R);
+  else if (dtype == SRWN_F32)
+    hipLaunchKernelGGL(recog_stream_in_kernel<float>, grid, block, 0, st, x, x_stride, carry, init_w, init_b, (float*)out,
+                       out_clip_rows, out_hist, B, n, R);
+  else
+    return set_error(SRWN_E_DTYPE, "recog_stream_in: dtype %d", dtype);
+  return check_launch("recog_stream_in");
+}
+
+namespace {
+int hop_args(const char* who, int32_t ring_rows, int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int64_t clip_rows) {
+  if (B < 1 || k < 1 || hop < 1 || ring_rows < 1 || max_chunk < 1)
+    return set_error(SRWN_E_SHAPE, "%s: B=%d hops=%d hop=%d ring=%d max_chunk=%d", who, B, k, hop, ring_rows, max_chunk);
+  if ((int64_t)k * hop > max_chunk || clip_rows < max_chunk)
+    return set_error(SRWN_E_SHAPE, "%s: %d hops of %d rows in buffers of %lld rows per stream (max_chunk = %d)", who, k, hop,
+                     (long long)clip_rows, max_chunk);
+  if ((int64_t)B * k > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "%s: too many hops", who);
+  return 0;
+}
+}  // namespace
+
+extern "C" int srwn_pooled_stream_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                       const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                       float* ring, int32_t ring_rows, const int64_t* clock, int32_t B, int32_t k,
+                                       int32_t hop, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype, void* stream) {
+  if (!z || !wskip || !bs_sum || !w1 || !b1 || !ring || !clock) return set_error(SRWN_E_NULL, "pooled_stream_head: null pointer");
+  if ((R != 32 && R != 64) || (S != 128 && S != 256))
+    return set_error(SRWN_E_UNSUPPORTED, "pooled_stream_head: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", R, S);
+  if (const int rc = hop_args("pooled_stream_head", ring_rows, B, k, hop, max_chunk, z_clip_rows)) return rc;
+  if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
+    return set_error(SRWN_E_SHAPE, "pooled_stream_head: %d layers at a stride of %lld", nlayers, (long long)z_layer_stride);
+  dim3 grid((unsigned)(B * k)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const long long* ck = reinterpret_cast<const long long*>(clock);
+#define SRWN_PSH(TT, RR, SS)                                                                                              \
+  hipLaunchKernelGGL((pooled_stream_head_kernel<TT, RR, SS>), grid, block, 0, st, (const TT*)z, z_layer_stride, z_clip_rows, \
+                     nlayers, (const TT*)wskip, bs_sum, (const TT*)w1, b1, ring, ring_rows, ck, k, hop)
+#define SRWN_PSH_T(TT)                                       \
+  {                                                          \
+    if (R == 32 && S == 128) SRWN_PSH(TT, 32, 128);          \
+    else if (R == 32) SRWN_PSH(TT, 32, 256);                 \
+    else if (S == 128) SRWN_PSH(TT, 64, 128);                \
+    else SRWN_PSH(TT, 64, 256);                              \
+  }
+  if (dtype == SRWN_BF16) SRWN_PSH_T(bf16_t)
+  else if (dtype == SRWN_F32) SRWN_PSH_T(float)
+  else return set_error(SRWN_E_DTYPE, "pooled_stream_head: dtype %d", dtype);
+#undef SRWN_PSH_T
+#undef SRWN_PSH
+  return check_launch("pooled_stream_head");
+}
+
+extern "C" int srwn_hop_sum(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows, const int64_t* clock,
+                            int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int32_t S, int32_t dtype, void* stream) {
+  if (!r1 || !ring || !clock) return set_error(SRWN_E_NULL, "hop_sum: null pointer");
+  if (const int rc = hop_args("hop_sum", ring_rows, B, k, hop, max_chunk, r1_clip_rows)) return rc;
+  if (S < 2 || S % 2) return set_error(SRWN_E_SHAPE, "hop_sum: S=%d", S);
+  dim3 grid((unsigned)(B * k)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const long long* ck = reinterpret_cast<const long long*>(clock);
+  if (dtype == SRWN_BF16)
+    hipLaunchKernelGGL(hop_sum_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)r1, r1_clip_rows, ring, ring_rows, ck, k, hop, S);
+  else if (dtype == SRWN_F32)
+    hipLaunchKernelGGL(hop_sum_kernel<float>, grid, block, 0, st, (const float*)r1, r1_clip_rows, ring, ring_rows, ck, k, hop, S);
+  else
+    return set_error(SRWN_E_DTYPE, "hop_sum: dtype %d", dtype);
+  return check_launch("hop_sum");
+}
+
+extern "C" int srwn_window_mean(const float* ring, int32_t ring_rows, float* mean, const int64_t* clock, int32_t B,
+                                int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2,
+                                float* logits, int32_t C, int32_t ldw, void* stream) {
+  if (!ring || !mean || !clock || (logits && (!w2 || !b2))) return set_error(SRWN_E_NULL, "window_mean: null pointer");
+  if (B < 1 || k < 1 || hop < 1 || window < hop || window % hop || S < 1 || S > 256)
+    return set_error(SRWN_E_SHAPE, "window_mean: B=%d hops=%d hop=%d window=%d S=%d (window a multiple of hop, S <= 256)", B,
+                     k, hop, window, S);
+  const int nW = window / hop;
+  if (ring_rows < nW + k - 1)
+    return set_error(SRWN_E_SHAPE, "window_mean: a ring of %d rows for %d window rows + %d hops per launch - 1", ring_rows, nW, k);
+  if (logits && (C < 1 || ldw < C)) return set_error(SRWN_E_SHAPE, "window_mean: C=%d ldw=%d", C, ldw);
+  if ((int64_t)B * k > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "window_mean: too many rows");
+  hipLaunchKernelGGL(window_mean_kernel, dim3((unsigned)(B * k)), dim3(256), 0, (hipStream_t)stream, ring, ring_rows, mean,
+                     reinterpret_cast<const long long*>(clock), k, hop, nW, (float)window, S, w2, b2, logits, C, ldw);
+  return check_launch("window_mean");
+}
+
+extern "C" int srwn_recog_roll(const int64_t* roll_table, int32_t nroll, const float* x, int64_t x_stride, float* carry,
+                               int64_t* clock, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
+                               void* stream) {
+  if (!x || !carry || !clock || (nroll > 0 && !roll_table)) return set_error(SRWN_E_NULL, "recog_roll: null pointer");
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_roll: dilation_channels %d (built: 32, 64)", R);
+  if (B < 1 || nroll < 0 || max_chunk < 1 || x_stride < max_chunk)
+    return set_error(SRWN_E_SHAPE, "recog_roll: B=%d boundaries=%d max_chunk=%d x stride %lld", B, nroll, max_chunk, (long long)x_stride);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_roll: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
+  static_assert(sizeof(RollEntry) == 24, "the roll table is int64 triples");
+  dim3 grid((unsigned)((int64_t)nroll * B + 1)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const RollEntry* rt = reinterpret_cast<const RollEntry*>(roll_table);
+  long long* ck = reinterpret_cast<long long*>(clock);
+#define SRWN_RR(TT, RR) hipLaunchKernelGGL((recog_roll_kernel<TT, RR>), grid, block, 0, st, rt, nroll, x, x_stride, carry, ck, B, n)
+  if (dtype == SRWN_BF16) { if (R == 32) SRWN_RR(bf16_t, 32); else SRWN_RR(bf16_t, 64); }
+  else if (dtype == SRWN_F32) { if (R == 32) SRWN_RR(float, 32); else SRWN_RR(float, 64); }
+  else return set_error(SRWN_E_DTYPE, "recog_roll: dtype %d", dtype);
+#undef SRWN_RR
+  return check_launch("recog_roll");
+}

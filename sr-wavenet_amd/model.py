@@ -225,6 +225,78 @@ class WaveNet(_EngineOwner):
         eng.forward(with_loss=False)
         return eng.probs.cpu().numpy()[:, None, :]
 
+    def recognizer(self, max_batch=1, hop=None, window=None, max_hops=8):
+        """A ``StreamingClassifier`` on a copy of this model's current weights: audio of any length in, the pooled
+        posteriors of a window of `window` samples (default input_size) sliding by `hop` (default: the window) out.  With
+        hop = window = input_size its single emission on a clip of input_size samples is ``predict``'s."""
+        window = int(self.input_size if window is None else window)
+        hop = window if hop is None else int(hop)
+        from .recognizer import ClassifierWeights, check_classifier_widths, check_hop_window
+        check_hop_window(hop, window)
+        if self.gate_mode != "reference":
+            raise NotImplementedError("gate_mode %r is not built for the streaming classifier" % (self.gate_mode,))
+        check_classifier_widths(self.filter_width, self.dilation_channels, self.skip_channels)
+        if self._primary is None:
+            self._engine(1, self._default_length)
+        return StreamingClassifier(ClassifierWeights.from_engine(self._primary), max_batch=max_batch, hop=hop,
+                                   window=window, max_hops=max_hops)
+
+
+class StreamingClassifier(object):
+    """The deployable form of the ``WaveNet`` classifier (createNetwork, model.py:33-62) with a NumPy face: no training
+    engine, no clip length.  ``classify(audio [B, T])`` -> probabilities [B, n_emit, C] of every window position
+    (j + 1) * hop - window, j >= window / hop - 1, of a recording of any length; ``stream(batch)`` -> a
+    ``ClassifierStream`` to ``push`` audio into as it arrives.  An emission does not depend on how the audio was cut."""
+
+    def __init__(self, weights, max_batch=1, hop=160, window=16000, max_hops=8):
+        from .recognizer import StreamClassifier
+        self._w = weights
+        self._eng = StreamClassifier(weights, max_batch=max_batch, hop=hop, window=window, max_hops=max_hops)
+        self.max_batch, self.hop, self.window = self._eng.max_batch, self._eng.hop, self._eng.window
+
+    @classmethod
+    def from_checkpoint(cls, logdir, dilations, output_channels, dilation_channels=32, skip_channels=256, filter_width=2,
+                        name="WaveNet", dtype=None, max_batch=1, hop=160, window=16000, max_hops=8):
+        """A classifier on the variables saved in `logdir` (``WaveNet.save``'s .pt form or a TensorFlow bundle, by the
+        reference's variable names under `name`)."""
+        from .recognizer import ClassifierWeights, check_classifier_widths, check_hop_window
+        check_hop_window(hop, window)
+        check_classifier_widths(filter_width, dilation_channels, skip_channels)
+        w = ClassifierWeights(dilations, dilation_channels, skip_channels, output_channels, filter_width,
+                              dtype or _default_dtype())
+        if not w.load(logdir, name):
+            raise FileNotFoundError("%s: no checkpoint to restore (WaveNet.save writes one)" % logdir)
+        return cls(w, max_batch=max_batch, hop=hop, window=window, max_hops=max_hops)
+
+    def classify(self, inputs, return_logits=False):
+        """inputs [B, T] -> probabilities [B, n_emit, C] (NumPy), n_emit = max(0, T // hop - window / hop + 1)."""
+        out = self._eng.classify(self._eng._check_audio(inputs), return_logits)
+        return tuple(o.cpu().numpy() for o in out) if return_logits else out.cpu().numpy()
+
+    def stream(self, batch_size=1):
+        return ClassifierStream(self, self._eng.start(batch_size))
+
+
+class ClassifierStream(object):
+    """NumPy face of one running batch of classifier streams (``StreamingClassifier.stream``).  ``t``: samples received
+    per stream; ``emitted``: emissions returned so far."""
+
+    def __init__(self, owner, state):
+        self._owner, self._st, self.batch_size = owner, state, state.B
+
+    @property
+    def t(self):
+        return self._st.t
+
+    @property
+    def emitted(self):
+        return self._st.emitted
+
+    def push(self, audio, return_logits=False):
+        """audio [B, n], any n >= 0 -> probabilities [B, k, C] of the k window positions it completed (k may be 0)."""
+        out = self._owner._eng.push(self._st, audio, return_logits)
+        return tuple(o.cpu().numpy() for o in out) if return_logits else out.cpu().numpy()
+
 
 class WaveNetTeacher(_EngineOwner):
     """The mu-law softmax teacher of BASELINE.json configs[1-2]: ``createDecoder``'s stack

@@ -1,0 +1,341 @@
+"""The classifier of class ``WaveNet`` (createNetwork, model.py:33-62) as a standalone streaming recognizer: audio of any
+length in, the pooled posteriors of a sliding window out.
+
+The reference graph's input placeholder is [None, None]: on T > input_size samples its VALID average pool (model.py:58)
+yields T - input_size + 1 pooled rows, one per window position.  A stream emits the row of every ``hop``-th position:
+
+  H_j = sum of r1[t] over t in [j * hop, (j + 1) * hop)                fp32 [S], r1 = relu(W1 relu(sum_l skip_l + bs) + b1)
+  e_j = softmax(((H_{j-nW+1} + ... + H_j) / window) @ W2 + b2)         nW = window / hop, j >= nW - 1, oldest block first
+
+(the pool commutes with the last 1x1, as ``srwn_pooled_head`` already relies on).  Audio that does not fill a hop waits
+in the state, so the stack only ever advances by whole hops at hop-aligned absolute times: every H_j depends on absolute
+time only, and a stream has the same bits however its audio was cut, at any batch size and in any row of the batch.
+
+Per step of k hops: the stream entry (input conv), one ``srwn_residual_group_fwd_stream_z`` launch per layer group (the
+stream form of the group kernels that also stores every layer's z of the chunk's rows), ``srwn_pooled_stream_head`` (skip
+sum, head 1x1 and hop sums in one launch; ``SRWN_RECOG_FUSED=0``: the parity twin, two ``srwn_pw_linear`` calls into
+chunk-sized buffers and ``srwn_hop_sum``), ``srwn_window_mean``, ``srwn_pooled_head`` and the roll.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import kernels as K
+from . import packing as P
+from ._lib import call
+from .engine import Section, WaveNetEngine
+
+# What SRWN_RECOG_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
+RECOG_FUSED_DEFAULT = "1"
+
+
+def emissions_due(t_before: int, t_after: int, hop: int, window: int) -> Tuple[int, int]:
+    """Which emissions a stream owes once it holds ``t_after`` samples, having held ``t_before``: (first hop index j,
+    count).  Emission e_j covers the samples [(j + 1) * hop - window, (j + 1) * hop): it is due once (j + 1) * hop
+    samples are in, and exists only from j = window / hop - 1 on (VALID: no window reaches before the stream's start).
+    Pure Python: the CPU tests hold it to brute force."""
+    t_before, t_after, hop, window = int(t_before), int(t_after), int(hop), int(window)
+    check_hop_window(hop, window)
+    if t_before < 0 or t_after < t_before:
+        raise ValueError("emissions_due: t_before=%d t_after=%d" % (t_before, t_after))
+    nW = window // hop
+    lo = max(t_before // hop, nW - 1)
+    hi = t_after // hop
+    return lo, max(0, hi - lo)
+
+
+def check_hop_window(hop, window):
+    if int(hop) < 1:
+        raise ValueError("hop %r: at least 1" % (hop,))
+    if int(window) < int(hop) or int(window) % int(hop):
+        raise ValueError("window %r must be a multiple of hop %r" % (window, hop))
+
+
+def check_classifier_widths(filter_width, dilation_channels, skip_channels):
+    """What the streaming classifier's kernels are built for: refused before anything touches the device."""
+    if filter_width != 2:
+        raise NotImplementedError("filter_width %d: only 2 is built (reference default, model.py:9)" % filter_width)
+    if dilation_channels not in (32, 64) or skip_channels not in (128, 256):
+        raise NotImplementedError("streaming classifier: dilation_channels %d x skip_channels %d; built for {32, 64} x "
+                                  "{128, 256}" % (dilation_channels, skip_channels))
+
+
+class ClassifierWeights:
+    """The parameters and forward MFMA images of a ``WaveNet`` classifier without the training engine around it: the
+    engine's section layout and reference variable names, no activations, gradients or Adam state.  Built from a
+    ``WaveNet``'s engine (``from_engine``: a copy of its parameters) or filled from a checkpoint directory by the
+    reference's variable names (``load``: this package's .pt form or a TensorFlow bundle)."""
+
+    view = WaveNetEngine.view
+    wptr = WaveNetEngine.wptr
+    named_tensors = WaveNetEngine.named_tensors
+    wavenet, E = False, 0
+
+    def __init__(self, dilations, dilation_channels: int = 32, skip_channels: int = 256, output_channels: int = 256,
+                 filter_width: int = 2, dtype: torch.dtype = torch.bfloat16, device="cuda"):
+        check_classifier_widths(filter_width, dilation_channels, skip_channels)
+        if not 1 <= int(output_channels) <= 256:
+            raise NotImplementedError("output_channels must be in [1, 256]")
+        if len(dilations) < 1 or min(int(d) for d in dilations) < 1:
+            raise ValueError("dilations %r" % (list(dilations),))
+        K._need_gpu()
+        self.dil = [int(d) for d in dilations]
+        self.L, self.R, self.S, self.C, self.Kw = len(self.dil), int(dilation_channels), int(skip_channels), int(output_channels), 2
+        self.Cp = (self.C + 31) // 32 * 32
+        self.dt, self.dev = dtype, torch.device(device)
+        L, R, S, Kw, Cp = self.L, self.R, self.S, self.Kw, self.Cp
+        secs: Dict[str, Section] = {}
+        off = 0
+        for name, shape in (("init_w", (Kw, 1, R)), ("init_b", (R,)), ("WF", (L, Kw, R, R)), ("BF", (L, R)),
+                            ("WR", (L, R, R)), ("BR", (L, R)), ("WS", (L, R, S)), ("BS", (L, S)),
+                            ("head_w1", (S, S)), ("head_b1", (S,)), ("head_w2", (S, Cp)), ("head_b2", (Cp,))):
+            secs[name] = Section(name, off, shape)
+            off += secs[name].numel
+        self.sections, self.nparams = secs, off
+        self.params = torch.zeros(off, dtype=torch.float32, device=self.dev)
+        self.bs_sum = torch.zeros(S, dtype=torch.float32, device=self.dev)
+        ph = torch.zeros(1)      # the dead gate variables (ops.py:31-33) exist in checkpoints only: stride-0 host placeholders
+        self.dead_gate = {"WG": ph.expand(L, Kw, R, R), "BG": ph.expand(L, R)}
+        pk = K.Packer(self.dev)
+        self.o_conv = [P.pack_conv(pk, secs["WF"].offset + l * Kw * R * R, Kw, R) for l in range(L)]
+        self.o_res = [P.pack_res(pk, secs["WR"].offset + l * R * R, R) for l in range(L)]
+        self.o_skip = pk.reserve(S // 32, L * R // 16)      # all skip 1x1s as one image: rows = skip channel, k = l * R + n
+        for l in range(L):
+            P.fill_linear(pk, self.o_skip, secs["WS"].offset + l * R * S, R, S, S // 32, L * R // 16,
+                          ks_offset=l * R // 16, ks_count=R // 16)
+        self.o_w1 = P.pack_linear(pk, secs["head_w1"].offset, S, S, S)
+        pk.finalize()
+        self.packer = pk
+        self.packed = torch.zeros(max(pk.total, 1), dtype=self.dt, device=self.dev)
+        self.repack()
+
+    def repack(self):
+        """The images and the sum of the skip biases from the current parameters (call after changing ``params``)."""
+        self.packer.gather(self.params, self.packed, rowsum=(self.view("BS"), self.bs_sum))
+
+    def tf_variables(self, scope: str) -> Dict[str, torch.Tensor]:
+        """Reference name -> tensor for the variables the classifier reads (the dead gate variables are left out)."""
+        return {k: v for k, v in WaveNetEngine.tf_variables(self, scope, decoder=False).items() if v.is_cuda}
+
+    def load_oracle_params(self, sp):
+        """Copies an oracle ``StackParams`` (tests) into the flat buffer."""
+        host = torch.zeros(self.nparams, dtype=torch.float32)
+
+        def put(name, arr):
+            s = self.sections[name]
+            host[s.offset:s.offset + s.numel] = torch.tensor(np.asarray(arr), dtype=torch.float32).reshape(-1)
+
+        put("init_w", sp.init_w); put("init_b", sp.init_b)
+        for nm, f in (("WF", "wf"), ("BF", "bf"), ("WR", "wr"), ("BR", "br"), ("WS", "ws"), ("BS", "bs")):
+            put(nm, np.stack([getattr(l, f) for l in sp.layers]))
+        put("head_w1", sp.head_w1); put("head_b1", sp.head_b1)
+        w2 = np.zeros((self.S, self.Cp)); w2[:, :self.C] = sp.head_w2
+        b2 = np.zeros(self.Cp); b2[:self.C] = sp.head_b2
+        put("head_w2", w2); put("head_b2", b2)
+        self.params.copy_(host)
+        self.repack()
+
+    @classmethod
+    def from_engine(cls, eng: WaveNetEngine) -> "ClassifierWeights":
+        """A copy of a pooled-head engine's parameters (``WaveNet._engine``); later training does not reach it."""
+        cfg = eng.cfg
+        if cfg.head_mode != "pooled":
+            raise ValueError("a streaming classifier needs the time-pooled head of class WaveNet (head_mode 'pooled'), "
+                             "this engine has %r" % (cfg.head_mode,))
+        if cfg.gate_mode != "reference":
+            raise NotImplementedError("gate_mode %r is not built for the streaming classifier" % (cfg.gate_mode,))
+        if cfg.shift_input or cfg.cond_channels:
+            raise ValueError("the classifier's stack has no RightShift and no conditioning (model.py:33-62)")
+        w = cls(cfg.dilations, cfg.dilation_channels, cfg.skip_channels, cfg.output_channels, cfg.filter_width, cfg.dtype,
+                eng.dev)
+        for name, s in w.sections.items():
+            w.view(name).copy_(eng.view(name))
+        w.repack()
+        return w
+
+    def load(self, logdir, scope: str = "WaveNet") -> bool:
+        """Fills the parameters from the checkpoint that `logdir`'s state file names (``WaveNet.save`` or the reference's
+        tf.train.Saver wrote it), by the reference's variable names under `scope`."""
+        from .model import _read_state
+        ok = _read_state(logdir, lambda: self.tf_variables(scope))
+        if ok:
+            self.repack()
+        return bool(ok)
+
+
+class RecogState:
+    """One batch of streams of a ``StreamClassifier`` (which holds the device side: a classifier serves one state at a
+    time).  ``t``: samples received per stream; ``emitted``: emissions returned so far; ``pending``: samples waiting for
+    their hop to fill (< hop)."""
+
+    def __init__(self, batch: int, serial: int, rem: torch.Tensor):
+        self.B, self._serial, self.t, self.emitted, self._rem = batch, serial, 0, 0, rem
+
+    @property
+    def pending(self) -> int:
+        return int(self._rem.shape[1])
+
+
+class StreamClassifier:
+    """``start`` a batch of streams, then ``push`` audio of any length: the probabilities [B, k, C] of the k window
+    positions that audio completed (k >= 0), ``classify`` for whole recordings.  A step of h hops is one hipGraph per
+    (batch, h), captured when it is used a second time (SRWN_MODEL_GRAPHS=0: eager launches)."""
+
+    def __init__(self, weights: ClassifierWeights, max_batch: int = 1, hop: int = 160, window: int = 16000,
+                 max_hops: int = 8):
+        check_hop_window(hop, window)
+        if min(int(max_batch), int(max_hops)) < 1:
+            raise ValueError("max_batch and max_hops must be >= 1")
+        K._need_gpu()
+        w = self.w = weights
+        self.max_batch, self.hop, self.window, self.max_hops = int(max_batch), int(hop), int(window), int(max_hops)
+        self.nW = self.window // self.hop
+        self.max_chunk = self.max_hops * self.hop
+        self.ring_rows = self.nW + self.max_hops - 1      # a step writes max_hops rows before the oldest window is read
+        self.dev, self.dt = w.dev, w.dt
+        self.groups = K.group_plan(w.dil, 31, int(os.environ.get("SRWN_GROUP_LAYERS", "8")))
+        self.hist = [sum(w.dil[l0:l1]) for l0, l1 in self.groups]
+        Bm, C, R, S, L = self.max_batch, self.max_chunk, w.R, w.S, w.L
+        z = lambda *s, dt=self.dt: torch.zeros(s, dtype=dt, device=self.dev)
+        self.bufs = [z(Bm, h + C, R) for h in self.hist]      # [hist rows | chunk rows] per group
+        self.top = z(Bm, C, R)                                # the last layer's output: nothing reads it
+        self.zs = z(L, Bm, C, R)
+        self.xbuf = z(Bm, C, dt=torch.float32)
+        self.carry = z(Bm, dt=torch.float32)
+        self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
+        self.ring = z(Bm, self.ring_rows, S, dt=torch.float32)
+        self.mean = z(Bm * self.max_hops, S, dt=torch.float32)
+        self.logits = z(Bm * self.max_hops, w.C, dt=torch.float32)
+        self.probs = z(Bm * self.max_hops, w.C, dt=torch.float32)
+        self.roll = torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs, self.hist)], dtype=torch.int64,
+                                 device=self.dev)
+        self.fused = os.environ.get("SRWN_RECOG_FUSED", RECOG_FUSED_DEFAULT) != "0"
+        if not self.fused:
+            self.r0, self.r1 = z(Bm * C, S), z(Bm * C, S)
+        self.use_graphs = os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
+        self._graphs: Dict[tuple, object] = {}
+        self._seen: set = set()
+        self._serial = 0
+        self._state: Optional[RecogState] = None
+        self.launches_per_step = 4 + len(self.groups) + (1 if self.fused else 3)
+
+    def buffer_bytes(self) -> Dict[str, int]:
+        """Device bytes by buffer family (DESIGN's table)."""
+        nb = lambda ts: int(sum(t.numel() * t.element_size() for t in ts))
+        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]), "ring": nb([self.ring]),
+               "audio": nb([self.xbuf, self.carry]), "emissions": nb([self.mean, self.logits, self.probs]),
+               "images": nb([self.w.packed])}
+        if not self.fused:
+            out["twin r0/r1"] = nb([self.r0, self.r1])
+        return out
+
+    # ------------------------------------------------------------------------------------------------
+    def start(self, batch: int = 1) -> RecogState:
+        """`batch` streams at clock 0: zero history (the conv's zero padding), zero carry, empty ring."""
+        B = int(batch)
+        if not 1 <= B <= self.max_batch:
+            raise ValueError("batch %d: this classifier holds max_batch=%d" % (B, self.max_batch))
+        for b in self.bufs:
+            b.zero_()
+        self.carry.zero_(); self.clock.zero_(); self.ring.zero_()
+        self._serial += 1
+        self._state = RecogState(B, self._serial, torch.zeros((B, 0), dtype=torch.float32, device=self.dev))
+        return self._state
+
+    def _check_state(self, state):
+        if state is not self._state or state._serial != self._serial:
+            raise ValueError("this state is not the classifier's current one (start() began another)")
+
+    def _check_audio(self, audio, batch=None) -> torch.Tensor:
+        if isinstance(audio, torch.Tensor):
+            x = audio
+        else:
+            x = torch.as_tensor(np.asarray(audio, dtype=np.float32))
+        if x.dim() != 2:
+            raise ValueError("audio must be [batch, samples], got shape %s" % (tuple(x.shape),))
+        if not 1 <= x.shape[0] <= self.max_batch:
+            raise ValueError("batch %d: this classifier holds max_batch=%d" % (x.shape[0], self.max_batch))
+        if batch is not None and x.shape[0] != batch:
+            raise ValueError("audio of %d streams pushed into a state of %d" % (x.shape[0], batch))
+        return x
+
+    def _launch_step(self, B: int, h: int):
+        """The launches of a step of h hops (n = h * hop rows) on the audio staged in ``xbuf``."""
+        import ctypes as C_
+        w = self.w
+        st, dt, R, S, C, L = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk, w.L
+        n, ck, v = h * self.hop, self.clock.data_ptr(), w.view
+        call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
+             v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt, st)
+        G = len(self.groups)
+        zstride = self.max_batch * C * R
+        for g, (l0, l1) in enumerate(self.groups):
+            last = g + 1 == G
+            out = self.top if last else self.bufs[g + 1]
+            nl = l1 - l0
+            call("srwn_residual_group_fwd_stream_z", self.bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
+                 C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1], self.zs[l0].data_ptr(), zstride,
+                 K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
+                 K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
+                 K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
+                 K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
+                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, ck, st)
+        if self.fused:
+            call("srwn_pooled_stream_head", self.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
+                 w.wptr(w.o_w1), v("head_b1").data_ptr(), self.ring.data_ptr(), self.ring_rows, ck, B, h, self.hop, C, R, S,
+                 dt, st)
+        else:      # the training forward's two products (engine.forward: skip_sum, head_1x1) on the buffers' rows, up to
+            # the last stream's chunk: one launch each, so for B > 1 the stale rows between the streams' chunks ride along
+            rows = (B - 1) * C + n
+            K.pw_linear(self.zs.data_ptr(), R, zstride, R, L * R, w.wptr(w.o_skip), w.bs_sum, self.r0[:rows], S, S, rows,
+                        pro=K.PRO_GATE, epi=K.EPI_RELU)
+            K.pw_linear(self.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), self.r1[:rows], S, S, rows,
+                        epi=K.EPI_RELU)
+            call("srwn_hop_sum", self.r1.data_ptr(), C, self.ring.data_ptr(), self.ring_rows, ck, B, h, self.hop, C, S, dt, st)
+        call("srwn_window_mean", self.ring.data_ptr(), self.ring_rows, self.mean.data_ptr(), ck, B, h, self.hop, self.window,
+             S, v("head_w2").data_ptr(), v("head_b2").data_ptr(), self.logits.data_ptr(), w.C, w.Cp, st)
+        call("srwn_pooled_head", self.mean.data_ptr(), v("head_w2").data_ptr(), v("head_b2").data_ptr(), None,
+             self.probs.data_ptr(), None, None, None, None, B * h, S, w.C, w.Cp, st)
+        call("srwn_recog_roll", self.roll.data_ptr(), G, self.xbuf.data_ptr(), C, self.carry.data_ptr(), ck, B, n, C, R, dt, st)
+
+    def push(self, state: RecogState, audio, return_logits: bool = False):
+        """The next samples of every stream, audio [B, n] with any n >= 0 -> probabilities [B, k, C] fp32 of the k window
+        positions they completed (k may be 0); with return_logits also the pooled logits [B, k, C].  A device tensor is
+        taken as it is.  Refuses (ValueError, state untouched) a wrong rank or batch."""
+        self._check_state(state)
+        x = self._check_audio(audio, state.B).to(device=self.dev, dtype=torch.float32)
+        B, Cc = state.B, self.w.C
+        x = torch.cat([state._rem, x], 1) if state._rem.shape[1] else x
+        hops = int(x.shape[1]) // self.hop
+        done = state.t - state._rem.shape[1]                  # samples the stack has consumed (hop-aligned)
+        first, count = emissions_due(done, done + hops * self.hop, self.hop, self.window)
+        probs = torch.empty((B, count, Cc), dtype=torch.float32, device=self.dev)
+        logits = torch.empty((B, count, Cc), dtype=torch.float32, device=self.dev) if return_logits else None
+        at, j = 0, done // self.hop
+        for h0 in range(0, hops, self.max_hops):
+            h = min(self.max_hops, hops - h0)
+            n = h * self.hop
+            self.xbuf[:B, :n].copy_(x[:, h0 * self.hop:h0 * self.hop + n])
+            K.run_cached_graph(self._graphs, self._seen, (B, h), self.use_graphs, lambda: self._launch_step(B, h))
+            skip = min(max(first - j, 0), h)                  # hops of this step before the first full window
+            if h > skip:
+                sl = slice(at, at + h - skip)
+                probs[:, sl] = self.probs[:B * h].view(B, h, Cc)[:, skip:]
+                if return_logits:
+                    logits[:, sl] = self.logits[:B * h].view(B, h, Cc)[:, skip:]
+                at += h - skip
+            j += h
+        state._rem = x[:, hops * self.hop:].clone()
+        state.t = done + int(x.shape[1])
+        state.emitted += count
+        return (probs, logits) if return_logits else probs
+
+    def classify(self, audio, return_logits: bool = False):
+        """Whole recordings audio [B, T] of any T -> probabilities [B, n_emit, C], n_emit = max(0, T // hop - window /
+        hop + 1); a trailing part that does not fill a hop is not heard.  Starts a new state (the current one ends)."""
+        x = self._check_audio(audio)
+        return self.push(self.start(int(x.shape[0])), x, return_logits)
