@@ -955,6 +955,63 @@ int srwn_generate16_mol_live_sampled(const void* wl, const void* wh1, const void
 int srwn_cond_ring_scatter(const void* rows, int64_t rows_ld, void* table, int64_t cond_ld, int32_t B, int32_t k,
                                int64_t first_frame, int32_t cond_frames, int32_t width, int32_t dtype, void* stream);
 
+/* ---- live slots in generation pools (since srwn_version() 114): the slot form of the conditioned mixture-of-logistics
+ * decoder (srwn_generate_mol_slots_sampled / srwn_generate16_mol_slots_sampled) over per-slot conditioning RINGS, so that
+ * a pool slot is fed its encoding while it runs.  The two *_live_slots_sampled entry points take the arguments of their
+ * *_mol_slots_sampled twins; `cond` is required and cond_frames is the ring length of every slot: the table is
+ * [B * cond_frames, cond_ld], and slot u at its OWN step t_u looks its frame q = t_u / pool_stride up in row
+ * u * cond_frames + q mod cond_frames (a true modulus: an idle slot may hold any t).  A slot with t_end <= cond_frames *
+ * pool_stride whose frames sit in rows 0.. (a bounded stream) reads what the twins read.  The host raises a live slot's
+ * t_end to fed * pool_stride as it feeds it; a slot that reaches t_end inside a launch, or before it, idles as in the
+ * twins -- except that an idle column does NOT store into the layer rings: its ring rows stay exactly as its last own
+ * step left them (everything else of an idle column still computes on junk and is dropped).  The rings follow the pool's
+ * clock, so before the launch in which such a slot runs again its columns are realigned:
+ *
+ *   srwn_generate_ring_rotate_slots  for i < n, slot u = slot_ids[i] and every layer l with depth D = d_l + 1:
+ *                                new[(p + shift[i]) mod D] = old[p] for p in [0, D), over the slot's R elements, in the
+ *                                ring layout of srwn_generate_ring_elems (slot u: group u / 32, row u mod 32).  shift[i] =
+ *                                (clock of the slot's next own step) - (clock at which its last own step ended) >= 0.  In
+ *                                place, any shift and dilation: one owner workgroup per (slot, layer) column, three
+ *                                reversals of disjoint swaps.  Slots not listed, an entry outside [0, capacity) or with a
+ *                                negative shift, and a shift that is 0 mod D keep their bits.  slot_ids (device, int32 [n])
+ *                                must be distinct.  Errors before any launch: n < 0, n > 65535, capacity < 1, a layer count
+ *                                outside 1..64, a dilation < 1, a ring not 16-byte aligned (-2); a null pointer (-3); R not
+ *                                32 or 64 (-4); an unknown dtype (-1).  n = 0: nothing (0).
+ *   srwn_cond_ring_scatter_slots    the feed of ragged slots: row i of rows [n_rows, rows_ld] (srwn_pw_linear's output
+ *                                for one new frame) -> row dst_row[i] (device, int32 [n_rows]) of table [table_rows,
+ *                                cond_ld]; the host computes dst_row = slot * cond_frames + (fed_slot + j) mod cond_frames.
+ *                                `width` elements per row in 16-byte vectors; a destination outside the table is skipped;
+ *                                the destinations must be distinct (two rows to one destination would race).
+ *                                One launch however many slots and frames.  Errors before any launch: n_rows < 0 (-2, checked
+ *                                first); a null pointer (-3); table_rows < 1, a width, leading dimension or address that is not a whole
+ *                                number of vectors, width beyond a leading dimension (-2); an unknown dtype (-1).  n_rows =
+ *                                0: nothing (0).
+ *
+ * Kernels of their own; every earlier launch runs the code it ran before.  Errors of the generators before any launch: a
+ * null cond (-3); cond_frames < 1, pool_stride < 1, cond_ld < nlayers * R (latency body: or not a multiple of 4) (-2);
+ * then the twins' checks. */
+int srwn_generate_mol_live_slots_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2, const float*
+                                         bias_f, const float* bias_r, const float* bs_sum, const float* b1, const float*
+                                         b2, const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                         int32_t* codes_out, float* logits_out, const float* forced, const int32_t*
+                                         dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R,
+                                         int32_t S, int32_t K, int32_t num_mixtures, const void* cond, int32_t
+                                         cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode, int32_t dtype,
+                                         void* stream, int32_t clock, float* carry, SrwnGenSlot* slots, const
+                                         SrwnGenSampling* sampling);
+int srwn_generate16_mol_live_slots_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f, const
+                                           float* bias_r, const float* bs_sum, const float* b1, const float* b2, const
+                                           float* init_w, const float* init_b, void* ring, float* audio_out, int32_t*
+                                           codes_out, float* logits_out, const float* forced, const int32_t* dilations,
+                                           int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t
+                                           S, int32_t num_mixtures, const void* cond, int32_t cond_frames, int32_t
+                                           pool_stride, int64_t cond_ld, int32_t mode, void* stream, int32_t clock,
+                                           float* carry, SrwnGenSlot* slots, const SrwnGenSampling* sampling);
+int srwn_generate_ring_rotate_slots(void* ring, const int32_t* dilations, int32_t nlayers, int32_t capacity, int32_t R,
+                                    const int32_t* slot_ids, const int32_t* shift, int32_t n, int32_t dtype, void* stream);
+int srwn_cond_ring_scatter_slots(const void* rows, int64_t rows_ld, void* table, int64_t cond_ld, int32_t n_rows, const
+                                 int32_t* dst_row, int32_t table_rows, int32_t width, int32_t dtype, void* stream);
+
 /* ---- data gradient of _DilatedCausalConv1d (ops.py:6-10) wrt a narrow input (the 1-channel flow input,
  * model.py:423-424); `shift` is the adjoint of RightShift (ops.py:78-80):
  *   dx[b,u,i] (+)= scale * sum_k sum_o w[k,i,o] * dy[b, u + shift + (K-1-k)*dilation, o]   (0 beyond the clip)

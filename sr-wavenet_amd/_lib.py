@@ -247,6 +247,14 @@ SIGNATURES["srwn_hop_sum"] = (C.c_int, [_p, _i64, _p, _i32, _p, _i32, _i32, _i32
 SIGNATURES["srwn_window_mean"] = (C.c_int, [_p, _i32, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p])
 SIGNATURES["srwn_recog_roll"] = (C.c_int, [_p, _i32, _p, _i64, _p, _p, _i32, _i32, _i32, _i32, _i32, _p])
 
+# live slots in generation pools (srwn_version() 114): the *_mol_slots_sampled twins over per-slot conditioning rings, the
+# rotation of resuming slots' layer-ring columns and the feed's scatter by a device list of table rows
+for _n in ("srwn_generate", "srwn_generate16"):
+    SIGNATURES[_n + "_mol_live_slots_sampled"] = SIGNATURES[_n + "_mol_slots_sampled"]
+del _n
+SIGNATURES["srwn_generate_ring_rotate_slots"] = (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p])
+SIGNATURES["srwn_cond_ring_scatter_slots"] = (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i32, _p])
+
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded
 

@@ -80,7 +80,10 @@ template <typename T, int RT> struct GenCond { f32x4 cc[RT][4]; };
 struct GenNoCond {};
 
 // RING (the live form, srwn.h: srwn_generate_mol_live_sampled): the conditioning table is a ring of cond_frames rows per
-// utterance that the caller keeps feeding; instantiations of their own, so that every other launch keeps its code
+// utterance that the caller keeps feeding; instantiations of their own, so that every other launch keeps its code.
+// SLOTS && RING (the live slot form, srwn.h: srwn_generate_mol_live_slots_sampled): each slot's table rows are a ring read
+// at the slot's OWN frame, and a column stores into the layer rings only while its slot runs -- a slot that has used up
+// its frames keeps its ring rows as its last own step left them, for srwn_generate_ring_rotate_slots to realign
 template <typename T, int NBUF, bool COND, int RT, int SS, bool SLOTS = false, bool SAMP = false, bool RING = false>
 __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS, SAMP>::type a) {
   constexpr int R = 32 * RT, KS = R / 16, S = SS, SQ = S / 4;   // SQ: skip/head-1 channels per wave
@@ -144,7 +147,8 @@ __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS,
       }
       sl[threadIdx.x] = st; sl[32 + threadIdx.x] = sn;
       sl[64 + threadIdx.x] = (int)(unsigned)sd; sl[96 + threadIdx.x] = (int)(unsigned)(sd >> 32);
-      if constexpr (COND) sl[128 + threadIdx.x] = max(min(st / a.pool, a.cond_frames - 1), 0);
+      if constexpr (COND && RING) sl[128 + threadIdx.x] = gen_ring_row(st / a.pool, a.cond_frames);
+      else if constexpr (COND) sl[128 + threadIdx.x] = max(min(st / a.pool, a.cond_frames - 1), 0);
     }
   }
   if constexpr (SAMP) {   // the group's controls, sanitised, read once (mode 0 ignores them)
@@ -190,7 +194,7 @@ __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS,
       // the live form: frame q sits in row q mod cond_frames.  Every preload of this body is issued for the step that is
       // running (the `t` above is the step loop's, also for the sets filled two layers ahead), so no lookup reads a frame
       // ahead of the step: the row is always one the caller has fed
-      if constexpr (RING) fc = (t / a.pool) % a.cond_frames;
+      if constexpr (RING && !SLOTS) fc = (t / a.pool) % a.cond_frames;
       const T* ccp = condp + ((size_t)ucl * a.cond_frames + fc) * a.cond_ld + (size_t)l * R + 4 * half;
 #pragma unroll
       for (int mt = 0; mt < RT; ++mt)
@@ -262,7 +266,9 @@ __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS,
       for (int s = 0; s < KS; ++s)
 #pragma unroll
         for (int j = 0; j < 8; ++j) xc[s].set(j, h[s >> 1][8 * (s & 1) + j]);
-      if (wave == 0) {   // one writer per ring slot
+      // (live slot form: only while the column's slot runs at this step -- an idle column computes on junk as in the slot
+      // form, but leaves its ring rows alone)
+      if (wave == 0 && (!(SLOTS && RING) || live(col, t))) {   // one writer per ring slot
         T* wp = ring + a.ring_off[l] + ((size_t)(t % depth) * 32 + col) * R;
 #pragma unroll
         for (int mt = 0; mt < RT; ++mt)
@@ -411,7 +417,10 @@ __global__ __launch_bounds__(256) void generate_kernel(typename GenArgsOf<SLOTS,
         // slot form: the frame table of step t + 1 (every preload of step t is behind the head's barriers, the step's last
         // one orders this before the next; clamped at 0 too: an idle slot may hold any t).  Conditioning comes with this
         // head only: the conditioned softmax teacher is not built
-        if constexpr (SLOTS && COND) sl[128 + col] = max(min(slot_t(col, t + 1) / a.pool, a.cond_frames - 1), 0);
+        // (live slot form: the ring row of that frame, which after a starved slot's last step may be one not fed yet -- the
+        // modulus keeps it inside the table, the column is idle at that step and the next launch computes its own)
+        if constexpr (SLOTS && COND && RING) sl[128 + col] = gen_ring_row(slot_t(col, t + 1) / a.pool, a.cond_frames);
+        else if constexpr (SLOTS && COND) sl[128 + col] = max(min(slot_t(col, t + 1) / a.pool, a.cond_frames - 1), 0);
         smp = fminf(fmaxf(smp, -1.0f), 1.0f);
         if (live(col, t)) {
           if (uok) {
@@ -523,12 +532,12 @@ static int generate_launch(A& a, int R, int S, bool cond, int dtype, int nlayers
    : (R == 32 && S == 256) ? (cond ? generate_kernel<TT, NB, true, 1, 256, SL, SA> : generate_kernel<TT, NB, false, 1, 256, SL, SA>) \
    : (R == 32 && S == 128) ? (cond ? generate_kernel<TT, NB, true, 1, 128, SL, SA> : generate_kernel<TT, NB, false, 1, 128, SL, SA>) \
                            : (cond ? generate_kernel<TT, NB, true, 2, 128, SL, SA> : generate_kernel<TT, NB, false, 2, 128, SL, SA>))
-  // the live form is conditioned and has no slots: its own instantiation of every width
-#define SRWN_GEN_PICK_RING(TT, NB)                                                                \
-  ((R == 64 && S == 256) ? generate_kernel<TT, NB, true, 2, 256, false, SA, true>                 \
-   : (R == 32 && S == 256) ? generate_kernel<TT, NB, true, 1, 256, false, SA, true>               \
-   : (R == 32 && S == 128) ? generate_kernel<TT, NB, true, 1, 128, false, SA, true>               \
-                           : generate_kernel<TT, NB, true, 2, 128, false, SA, true>)
+  // the live forms are conditioned (without slots, or the live slot form): their own instantiation of every width
+#define SRWN_GEN_PICK_RING(TT, NB)                                                             \
+  ((R == 64 && S == 256) ? generate_kernel<TT, NB, true, 2, 256, SL, SA, true>                 \
+   : (R == 32 && S == 256) ? generate_kernel<TT, NB, true, 1, 256, SL, SA, true>               \
+   : (R == 32 && S == 128) ? generate_kernel<TT, NB, true, 1, 128, SL, SA, true>               \
+                           : generate_kernel<TT, NB, true, 2, 128, SL, SA, true>)
 #define SRWN_GEN_KFN(TT, NB) [&] { if constexpr (RG) return SRWN_GEN_PICK_RING(TT, NB); else return SRWN_GEN_PICK(TT, NB); }()
   if (dtype == SRWN_BF16) {
     auto kfn = SRWN_GEN_KFN(bf16_t, 2);
@@ -597,6 +606,10 @@ static int generate_impl(const void* wcr, const void* wskip, const void* w1, con
   const unsigned groups = (unsigned)((B + 31) / 32);
   hipStream_t st = (hipStream_t)stream;
   const bool cd = cond != nullptr;
+  if (slot_form && ring_form) {
+    if (sampling) return generate_launch<true, true, true>(a, R, S, cd, dtype, nlayers, groups, st);
+    return generate_launch<true, false, true>(static_cast<GenSlotArgs&>(a), R, S, cd, dtype, nlayers, groups, st);
+  }
   if (slot_form) {
     if (sampling) return generate_launch<true, true>(a, R, S, cd, dtype, nlayers, groups, st);
     return generate_launch<true, false>(static_cast<GenSlotArgs&>(a), R, S, cd, dtype, nlayers, groups, st);
@@ -780,6 +793,29 @@ extern "C" int srwn_generate_mol_slots(const void* wcr, const void* wskip, const
       cond_frames, pool_stride, cond_ld, mode, dtype, stream, clock, carry, slots, nullptr);
 }
 
+// ---- the live slot form (srwn.h, srwn_version() 114): srwn_generate_mol_slots_sampled over per-slot conditioning RINGS of
+// cond_frames frames (a slot's own frame q in row q mod cond_frames), with the ring stores of idle columns held back
+extern "C" int srwn_generate_mol_live_slots_sampled(const void* wcr, const void* wskip, const void* w1, const void* w2,
+                                       const float* bias_f, const float* bias_r, const float* bs_sum, const float* b1,
+                                       const float* b2, const float* init_w, const float* init_b, void* ring,
+                                       float* audio_out, int32_t* codes_out, float* logits_out, const float* forced,
+                                       const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                       int32_t nsteps, int32_t R, int32_t S, int32_t K, int32_t num_mixtures,
+                                       const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                                       int32_t mode, int32_t dtype, void* stream, int32_t clock, float* carry,
+                                       SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
+  if (!cond) return set_error(SRWN_E_NULL, "generate_mol_live_slots: the conditioning ring is required");
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate_mol_live_slots: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R)
+    return set_error(SRWN_E_SHAPE, "generate_mol_live_slots: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
+                     pool_stride, (long long)cond_ld);
+  return generate_impl(wcr, wskip, w1, w2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                       logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, K, mode, 0,
+                       dtype, stream, cond, cond_frames, pool_stride, cond_ld, num_mixtures, clock,
+                       carry, sampling, slots, true, true);
+}
+
 // ---- the rings after a prompt of P samples, from the layer inputs of ONE parallel forward pass over it (what the loop of
 // teacher.py:140-171 would have left after P steps): slot s of layer l <- x_l[t], the t in [P-1-d_l, P-1] with
 // t = s (mod d_l+1); zero where t < 0 or the utterance is past B (the causal padding the bodies rely on).  Memory-bound:
@@ -952,4 +988,118 @@ extern "C" int srwn_cond_ring_scatter(const void* rows, int64_t rows_ld, void* t
   if (dtype == SRWN_BF16) hipLaunchKernelGGL(cond_scatter_kernel<bf16_t>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(cond_scatter_kernel<float>, grid, dim3(256), 0, st, a);
   return check_launch("cond_ring_scatter");
+}
+
+// ---- the ring columns of pool slots that resume after a pause (srwn.h, srwn_version() 114).  The rings follow the pool's
+// clock: step c writes position c mod D (D = d_l + 1) and reads the delayed tap at (c + 1) mod D.  A slot whose last own
+// step ended at clock c_stop and whose next one runs at clock c' (its stores held back in between) needs
+// new[(p + shift) mod D] = old[p] with shift = c' - c_stop.  One OWNER workgroup per (listed slot, layer) column rotates it
+// in place by three reversals -- the whole column, its first s = shift mod D positions, the remaining D - s -- each a set
+// of disjoint swaps (a thread reads both ends of its pair into registers before it writes either), ordered by the
+// workgroup's own barriers: correct for any shift and depth, with no scratch and no ordering between workgroups.
+struct RingRotateArgs {
+  void* ring; const int32_t* slot_ids; const int32_t* shift;
+  long long ring_group_elems;
+  int B, R;
+  int dil[kGenMaxLayers];
+  long long ring_off[kGenMaxLayers];
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void ring_rotate_slots_kernel(RingRotateArgs a) {
+  constexpr int V = 16 / sizeof(T);
+  const int l = blockIdx.x, i = blockIdx.y;
+  const int u = a.slot_ids[i], sh = a.shift[i];
+  if (u < 0 || u >= a.B || sh < 0) return;                     // a row that names no slot of the pool (workgroup-uniform)
+  const int depth = a.dil[l] + 1, vpr = a.R / V;
+  const int s = sh % depth;
+  if (s == 0) return;                                          // in phase: the column keeps its bits
+  T* rp = reinterpret_cast<T*>(a.ring) + (size_t)(u >> 5) * a.ring_group_elems + a.ring_off[l] + (size_t)(u & 31) * a.R;
+  const size_t pos_stride = (size_t)32 * a.R;
+  auto reverse = [&](int lo, int n) {                          // positions [lo, lo + n) of the column, in place
+    const long long nv = (long long)(n / 2) * vpr;
+    for (long long k = threadIdx.x; k < nv; k += 256) {
+      const int cv = (int)(k % vpr), j = (int)(k / vpr);
+      uint4* pa = reinterpret_cast<uint4*>(rp + (size_t)(lo + j) * pos_stride + cv * V);
+      uint4* pb = reinterpret_cast<uint4*>(rp + (size_t)(lo + n - 1 - j) * pos_stride + cv * V);
+      const uint4 va = *pa, vb = *pb;
+      *pa = vb;
+      *pb = va;
+    }
+  };
+  reverse(0, depth);
+  __syncthreads();
+  reverse(0, s);
+  reverse(s, depth - s);                                       // (disjoint from the one above: no barrier between them)
+}
+
+extern "C" int srwn_generate_ring_rotate_slots(void* ring, const int32_t* dilations, int32_t nlayers, int32_t capacity,
+                                               int32_t R, const int32_t* slot_ids, const int32_t* shift, int32_t n,
+                                               int32_t dtype, void* stream) {
+  if (n < 0) return set_error(SRWN_E_SHAPE, "generate_ring_rotate_slots: n=%d", n);
+  if (n == 0) return 0;
+  if (!ring || !dilations || !slot_ids || !shift) return set_error(SRWN_E_NULL, "generate_ring_rotate_slots: null pointer");
+  if (R != 64 && R != 32) return set_error(SRWN_E_UNSUPPORTED, "generate_ring_rotate_slots: built for R=64 or 32 (got R=%d)", R);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "generate_ring_rotate_slots: dtype %d", dtype);
+  if (capacity < 1 || n > 65535 || nlayers < 1 || nlayers > kGenMaxLayers)
+    return set_error(SRWN_E_SHAPE, "generate_ring_rotate_slots: n=%d capacity=%d layers=%d", n, capacity, nlayers);
+  if ((reinterpret_cast<uintptr_t>(ring) & 15))
+    return set_error(SRWN_E_SHAPE, "generate_ring_rotate_slots: ring not 16-byte aligned");
+  RingRotateArgs a;
+  a.ring = ring; a.slot_ids = slot_ids; a.shift = shift; a.B = capacity; a.R = R;
+  int bad;
+  a.ring_group_elems = gen_ring_layout(dilations, nlayers, R, INT32_MAX - 1, &bad, a.dil, a.ring_off);
+  if (bad >= 0) return set_error(SRWN_E_SHAPE, "generate_ring_rotate_slots: dilation %d", dilations[bad]);
+  const dim3 grid((unsigned)nlayers, (unsigned)n);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) hipLaunchKernelGGL(ring_rotate_slots_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(ring_rotate_slots_kernel<float>, grid, dim3(256), 0, st, a);
+  return check_launch("generate_ring_rotate_slots");
+}
+
+// ---- the feed of the live slot form (srwn.h): projected conditioning rows -> the table rows a device list names (ragged
+// slots: dst_row[i] = slot * cond_frames + (fed_slot + j) mod cond_frames, computed by the host).  A row whose destination
+// is outside the table is skipped.  Memory-bound: one 16-byte vector per thread, consecutive threads along a row.
+struct CondScatterSlotsArgs {
+  const void* rows; void* table; const int32_t* dst_row;
+  long long rows_ld, cond_ld;
+  int n_rows, table_rows, vpr;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void cond_scatter_slots_kernel(CondScatterSlotsArgs a) {
+  constexpr int V = 16 / sizeof(T);
+  const long long nvec = (long long)a.n_rows * a.vpr;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
+    const int cv = (int)(i % a.vpr);
+    const long long r = i / a.vpr;
+    const int d = a.dst_row[r];
+    if (d < 0 || d >= a.table_rows) continue;
+    const T* sp = reinterpret_cast<const T*>(a.rows) + r * a.rows_ld + cv * V;
+    T* dp = reinterpret_cast<T*>(a.table) + (long long)d * a.cond_ld + cv * V;
+    *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
+  }
+}
+
+extern "C" int srwn_cond_ring_scatter_slots(const void* rows, int64_t rows_ld, void* table, int64_t cond_ld,
+                                            int32_t n_rows, const int32_t* dst_row, int32_t table_rows, int32_t width,
+                                            int32_t dtype, void* stream) {
+  if (n_rows < 0) return set_error(SRWN_E_SHAPE, "cond_ring_scatter_slots: n_rows=%d", n_rows);
+  if (n_rows == 0) return 0;
+  if (!rows || !table || !dst_row) return set_error(SRWN_E_NULL, "cond_ring_scatter_slots: null pointer");
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "cond_ring_scatter_slots: dtype %d", dtype);
+  const int V = dtype == SRWN_BF16 ? 8 : 4;
+  if (n_rows < 0 || table_rows < 1 || width < V || width % V || rows_ld < width || cond_ld < width || rows_ld % V ||
+      cond_ld % V || (reinterpret_cast<uintptr_t>(rows) & 15) || (reinterpret_cast<uintptr_t>(table) & 15))
+    return set_error(SRWN_E_SHAPE, "cond_ring_scatter_slots: n_rows=%d table_rows=%d width=%d ld %lld / %lld", n_rows,
+                     table_rows, width, (long long)rows_ld, (long long)cond_ld);
+  CondScatterSlotsArgs a;
+  a.rows = rows; a.table = table; a.dst_row = dst_row; a.rows_ld = rows_ld; a.cond_ld = cond_ld;
+  a.n_rows = n_rows; a.table_rows = table_rows; a.vpr = width / V;
+  const long long nvec = (long long)n_rows * a.vpr;
+  const dim3 grid((unsigned)min((nvec + 255) / 256, (long long)4096));
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16) hipLaunchKernelGGL(cond_scatter_slots_kernel<bf16_t>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(cond_scatter_slots_kernel<float>, grid, dim3(256), 0, st, a);
+  return check_launch("cond_ring_scatter_slots");
 }

@@ -84,7 +84,10 @@ struct PreT : std::conditional<COND, G16Cond<NCB>, G16NoCond>::type {
 };
 
 // RING (the live form, srwn.h: srwn_generate16_mol_live_sampled): the conditioning table is a ring of cond_frames rows per
-// utterance that the caller keeps feeding; instantiations of their own, so that every other launch keeps its code
+// utterance that the caller keeps feeding; instantiations of their own, so that every other launch keeps its code.
+// SLOTS && RING (the live slot form, srwn.h: srwn_generate16_mol_live_slots_sampled): each slot's table rows are a ring read
+// at the slot's OWN frame, and a row is copied into the layer rings only while its slot runs -- a slot that has used up
+// its frames keeps its ring rows as its last own step left them, for srwn_generate_ring_rotate_slots to realign
 template <int NCB, bool COND, bool MOL, int R, int S, bool SLOTS = false, bool SAMP = false, bool RING = false>
 __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SLOTS, SAMP>::type a) {
   constexpr int NU = 16 * NCB;                // utterances of this workgroup
@@ -182,7 +185,7 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
       // layer requests layer 0 of step t + 1 (ahead = 1), which after a launch's last step may be a frame the caller has
       // not fed yet -- the modulus keeps the row inside the table and the value is dropped (the next launch's first step
       // requests its own, j == 0 below).  Every other operand set is requested for the step that is running
-      if constexpr (RING) fc = (tt / a.pool) % a.cond_frames;
+      if constexpr (RING && !SLOTS) fc = (tt / a.pool) % a.cond_frames;
 #pragma unroll
       for (int c2 = 0; c2 < NCB; ++c2) {
         const int ug = u0 + 16 * c2 + col;
@@ -190,7 +193,12 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
         int fc_u = fc;
         if constexpr (SLOTS) {   // the slot's own frame, clamped at both ends (an idle slot may hold any t)
           fc_u = slot_t(16 * c2 + col, tt - a.t0) / a.pool;
-          fc_u = fc_u < 0 ? 0 : (fc_u < a.cond_frames ? fc_u : a.cond_frames - 1);
+          // (live slot form: the ring row of the slot's own frame.  The body's one read ahead -- the top layer requests
+          // layer 0 of step t + 1 -- may name a frame the slot has not been fed yet: the modulus keeps the row inside the
+          // table and the value is dropped, as in the live form: the slot is idle at that step, or the launch is over and
+          // the next one requests its own at j == 0.  A true modulus: an idle slot may hold any t)
+          if constexpr (RING) fc_u = gen_ring_row(fc_u, a.cond_frames);
+          else fc_u = fc_u < 0 ? 0 : (fc_u < a.cond_frames ? fc_u : a.cond_frames - 1);
         }
         p.cc[c2] = *reinterpret_cast<const bf16x4*>(condp + ((size_t)uc * a.cond_frames + fc_u) * a.cond_ld + (size_t)l * R + 16 * wave + 4 * rq);
       }
@@ -261,7 +269,8 @@ __global__ __launch_bounds__(256) void generate16_kernel(typename Gen16ArgsOf<SL
         constexpr int LPRW = R / 8, RPW = 64 / LPRW;          // lanes per row, rows per wave-instruction
         const int ul = RPW * wave + lane / LPRW;
         const int slot = __builtin_amdgcn_readlane(curv, l), roff = __builtin_amdgcn_readlane(roffv, l);
-        if (RPW * wave < NU) {
+        // (live slot form: only the rows whose slot runs at this step -- an idle row keeps what its last own step left)
+        if (RPW * wave < NU && (!(SLOTS && RING) || live(ul, j))) {
           const f32x4 v = *reinterpret_cast<const f32x4*>(xb + (size_t)ul * LSX + (lane % LPRW) * 8);
           *reinterpret_cast<f32x4*>(ring + roff + (size_t)slot * (32 * R) + ul * R + (lane % LPRW) * 8) = v;
         }
@@ -636,8 +645,8 @@ static int generate16_launch(A& a, const int32_t* dilations, int32_t nlayers, in
   const size_t sh = (size_t)(2 * 32 * W::LSX + 32 * W::LSH) * sizeof(T) +
                     (size_t)(32 * LGS + 64 + 2 * nlayers * R + 2 * S + 256 + 3 * R + 256 + (SLOTS ? 4 * 32 : 0) + (SAMP ? 4 * 32 : 0)) * 4;
   auto pick = [&] {
-    if constexpr (RING)   // the live form: the conditioned mixture-of-logistics decoder, no slots
-      return half ? generate16_kernel<1, true, true, R, S, false, SAMP, true> : generate16_kernel<2, true, true, R, S, false, SAMP, true>;
+    if constexpr (RING)   // the live forms: the conditioned mixture-of-logistics decoder, without slots or with them
+      return half ? generate16_kernel<1, true, true, R, S, SLOTS, SAMP, true> : generate16_kernel<2, true, true, R, S, SLOTS, SAMP, true>;
     else
       return M > 0 ? (cond ? (half ? generate16_kernel<1, true, true, R, S, SLOTS, SAMP> : generate16_kernel<2, true, true, R, S, SLOTS, SAMP>)
                            : (half ? generate16_kernel<1, false, true, R, S, SLOTS, SAMP> : generate16_kernel<2, false, true, R, S, SLOTS, SAMP>))
@@ -693,6 +702,10 @@ static int generate16_impl(const void* wl, const void* wh1, const void* wh2, con
     static_cast<Gen16Args&>(b) = a;
     b.slots = slots;
     b.sampling = sampling;
+    if (ring_form) {
+      if (sampling) SRWN_G16_WIDTHS(true, SRWN_G16_RING(true), b);
+      SRWN_G16_WIDTHS(true, SRWN_G16_RING(false), static_cast<Gen16SlotArgs&>(b));
+    }
     if (sampling) SRWN_G16_WIDTHS(true, true, b);
     SRWN_G16_WIDTHS(true, false, static_cast<Gen16SlotArgs&>(b));
   }
@@ -863,4 +876,25 @@ extern "C" int srwn_generate16_mol_slots(const void* wl, const void* wh1, const 
   return srwn_generate16_mol_slots_sampled(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring,
       audio_out, codes_out, logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, num_mixtures, cond,
       cond_frames, pool_stride, cond_ld, mode, stream, clock, carry, slots, nullptr);
+}
+
+// ---- the live slot form (srwn.h, srwn_version() 114): srwn_generate16_mol_slots_sampled over per-slot conditioning RINGS of
+// cond_frames frames (a slot's own frame q in row q mod cond_frames), with the ring copies of idle rows held back
+extern "C" int srwn_generate16_mol_live_slots_sampled(const void* wl, const void* wh1, const void* wh2, const float* bias_f,
+                                         const float* bias_r, const float* bs_sum, const float* b1, const float* b2,
+                                         const float* init_w, const float* init_b, void* ring, float* audio_out,
+                                         int32_t* codes_out, float* logits_out, const float* forced,
+                                         const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout,
+                                         int32_t nsteps, int32_t R, int32_t S, int32_t num_mixtures, const void* cond,
+                                         int32_t cond_frames, int32_t pool_stride, int64_t cond_ld, int32_t mode,
+                                         void* stream, int32_t clock, float* carry, SrwnGenSlot* slots, const SrwnGenSampling* sampling) {
+  if (!cond) return set_error(SRWN_E_NULL, "generate16_mol_live_slots: the conditioning ring is required");
+  if (num_mixtures < 1 || num_mixtures > 16)
+    return set_error(SRWN_E_SHAPE, "generate16_mol_live_slots: num_mixtures=%d (1..16)", num_mixtures);
+  if (cond_frames < 1 || pool_stride < 1 || cond_ld < (int64_t)nlayers * R || (cond_ld % 4))
+    return set_error(SRWN_E_SHAPE, "generate16_mol_live_slots: cond_frames=%d pool_stride=%d cond_ld=%lld", cond_frames,
+                     pool_stride, (long long)cond_ld);
+  return generate16_impl(wl, wh1, wh2, bias_f, bias_r, bs_sum, b1, b2, init_w, init_b, ring, audio_out, codes_out,
+                         logits_out, forced, dilations, nlayers, B, Tout, nsteps, R, S, 4 * num_mixtures, mode, 0, stream,
+                         num_mixtures, cond, cond_frames, pool_stride, cond_ld, clock, carry, sampling, slots, true, true);
 }

@@ -42,4 +42,11 @@ __device__ __forceinline__ float gen_uniform(unsigned long long seed, unsigned u
   return (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f);
 }
 
+// the live slot form: the row of a slot's own frame f in its ring of n conditioning frames -- a true modulus, inside the
+// table for the negative or garbage frames an idle slot may hold
+__device__ __forceinline__ int gen_ring_row(int f, int n) {
+  const int r = f % n;
+  return r < 0 ? r + n : r;
+}
+
 }  // namespace srwn

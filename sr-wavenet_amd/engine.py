@@ -137,6 +137,19 @@ def live_decode_room(max_frames: int, fed: int, t: int, pool_stride: int) -> int
     return max_frames - fed + t // pool_stride
 
 
+def live_slot_shift(clock: int, stopped_at: int) -> int:
+    """By how many positions the layer-ring columns of a pool slot are rotated before it runs again: clock - stopped_at,
+    where ``stopped_at`` is the pool clock at which the slot's last own step ended (a join: the join's clock) and
+    ``clock`` the one at which its next own step runs.  The rings follow the pool's clock -- step c of a layer of dilation
+    d writes position c mod (d + 1) and reads the delayed tap at (c + 1) mod (d + 1) -- and a slot that waits for frames
+    stores nothing meanwhile, so what it would have read at ``stopped_at`` must sit where ``clock`` reads:
+    new[(p + shift) mod (d + 1)] = old[p] (srwn_generate_ring_rotate_slots).  0: the slot never paused.  Pure Python."""
+    clock, stopped_at = int(clock), int(stopped_at)
+    if stopped_at < 0 or clock < stopped_at or clock > INT32_MAX:
+        raise ValueError("live_slot_shift: clock=%d stopped_at=%d" % (clock, stopped_at))
+    return clock - stopped_at
+
+
 def sampling_table(n, temperature, top_k, top_p, C, mol, who="generate"):
     """The sampling controls of n streams as srwn.h's SrwnGenSampling rows (a NumPy structured array [n]), or None when
     every stream is at the defaults (temperature 1, top_k 0, top_p 1: the calls without controls).  Each argument is a
@@ -190,10 +203,23 @@ class GenerationPool(SlotTable):
     that reaches its end or `leave`s frees its slot for the next one.  The rings follow the pool's clock; what depends on
     a stream's own position -- the samplers' counters, the conditioning frame, whether it still emits -- comes from the
     per-slot table (srwn.h, SrwnGenSlot), so a slot produces the bits of a batch-of-one run with its seed.
-    Joins are ordered between steps.  Steps, clock and limits are int32 (2^31 steps is about 37 h at 16 kHz)."""
+    Joins are ordered between steps.  Steps, clock and limits are int32 (2^31 steps is about 37 h at 16 kHz).
+    A LIVE pool (``generation_pool(..., live=True)``, the conditioned mixture-of-logistics decoder): `frames` is the length
+    of every slot's conditioning RING, and ``join(..., live=True)`` starts streams that are fed while they run (``feed`` /
+    ``room`` / ``close``).  A live slot that has used up its frames is starved, not ended: it stays taken with ran = 0, its
+    columns store nothing into the layer rings, and before the launch in which it runs again they are rotated by the
+    clock ticks it missed (``live_slot_shift``)."""
 
-    def __init__(self, eng: "WaveNetEngine", capacity: int, frames: int = 0):
+    live = False      # (a pool made with live=True: the live slot form's launches, per-slot feed state)
+
+    def __init__(self, eng: "WaveNetEngine", capacity: int, frames: int = 0, live: bool = False):
         self.eng, self.capacity, self.frames = eng, int(capacity), int(frames)
+        self.live = bool(live)
+        self._live = np.zeros(self.capacity, bool)           # live slots: fed while they run; t_end = fed * pool_stride
+        self._closed = np.zeros(self.capacity, bool)         # ... until closed: no more frames will come
+        self._fed = np.zeros(self.capacity, np.int64)
+        self._cap = np.full(self.capacity, INT32_MAX, np.int64)      # ... capped by prompt + max_samples
+        self._stopped = np.zeros(self.capacity, np.int64)    # the clock at which each slot's last own step ended
         self.conditioned = bool(eng.mol and eng.E)
         self.E, self.pool_stride = int(eng.E), int(eng.cfg.pool_stride)
         self.clock = 0
@@ -229,9 +255,12 @@ class GenerationPool(SlotTable):
                 self.sampling = torch.zeros((self.capacity, 4), dtype=torch.int32, device=self.eng.dev)
             self.sampling.copy_(torch.from_numpy(self._samp.view(np.int32).reshape(self.capacity, 4)))
 
-    def _check_join(self, seeds, prompts, cond, max_samples, slots, temperature=None, top_k=None, top_p=None):
+    def _check_join(self, seeds, prompts, cond, max_samples, slots, temperature=None, top_k=None, top_p=None, live=False):
         """Everything join refuses, before any device work: returns (seeds, prompts as float32 1-D arrays, the chosen
-        slots, t_end per stream, the streams' sampling controls or None)."""
+        slots, t_end per stream, the streams' sampling controls or None).  live: a stream brings 0..frames first frames
+        (an entry None: none yet)."""
+        if live and not self.live:
+            raise ValueError("join: live streams need a pool made with generation_pool(..., live=True)")
         seeds = [int(s) for s in seeds]
         n = len(seeds)
         if n < 1:
@@ -256,10 +285,13 @@ class GenerationPool(SlotTable):
             if cond is None:
                 raise ValueError("this decoder is conditioned: pass cond, one [frames, %d] per stream" % self.E)
             cond = per_stream(list(cond), n, "encodings")
+            if live:
+                cond = [np.zeros((0, self.E), np.float32) if c is None else c for c in cond]
             for i, c in enumerate(cond):
                 shp = tuple(c.shape) if hasattr(c, "shape") else np.shape(c)
-                if len(shp) != 2 or shp[1] != self.E or not 1 <= shp[0] <= self.frames:
-                    raise ValueError("join: cond %d must be [1..%d frames, %d], got %s" % (i, self.frames, self.E, shp))
+                if len(shp) != 2 or shp[1] != self.E or not (0 if live else 1) <= shp[0] <= self.frames:
+                    raise ValueError("join: cond %d must be [%d..%d frames, %d], got %s"
+                                     % (i, 0 if live else 1, self.frames, self.E, shp))
                 limits[i] = shp[0] * self.pool_stride
         elif cond is not None:
             raise ValueError("this decoder is not conditioned")
@@ -285,17 +317,20 @@ class GenerationPool(SlotTable):
         return self._view
 
     def join(self, seeds, prompts=None, cond=None, max_samples=None, slots=None, *, temperature=None, top_k=None,
-             top_p=None) -> List[int]:
+             top_p=None, live=False) -> List[int]:
         """n streams into free slots (the lowest ones, or `slots`): seeds [n]; prompts None or n entries of 1-D [P_i] (any
         lengths, none included); cond (conditioned decoder) n encodings [frames_i <= frames, cond_channels]; max_samples
         None, one int, or n entries: samples after the prompt (a conditioned stream ends at frames_i * pool_stride too).
         temperature / top_k / top_p: the streams' sampling controls (sampling_table: a scalar or one entry per stream; None
         = the default), written into their slots' entries of the pool's SrwnGenSampling array as the carry is.
         One stack-only forward over all prompts (padded to the longest) and one srwn_generate_ring_fill_slots; returns the
-        slots."""
+        slots.
+        live=True (a live pool): the streams are fed while they run (``feed``): cond[i] holds a stream's first frames
+        [k_i >= 0, cond_channels] (None: none yet), a prompt fits inside them (len <= k_i * pool_stride), and the stream
+        ends where ``close`` finds it or at prompt + max_samples; until then a slot that has used up its frames waits."""
         from . import _lib
         seeds, ps, cond, slots, ends, samp = self._check_join(seeds, prompts, cond, max_samples, slots, temperature, top_k,
-                                                              top_p)
+                                                              top_p, live)
         eng, n, dev = self.eng, len(seeds), self.eng.dev
         lens = [len(p) for p in ps]
         dst = torch.tensor(slots, dtype=torch.int32, device=dev)
@@ -335,6 +370,12 @@ class GenerationPool(SlotTable):
         for i, u in enumerate(slots):
             self._t[u], self._end[u], self._seed[u] = lens[i], ends[i], seeds[i]
             self._active[u] = True
+        if self.live:
+            mx = per_stream(max_samples, n, "max_samples")
+            for i, u in enumerate(slots):
+                self._live[u], self._closed[u], self._stopped[u] = live, False, self.clock
+                self._fed[u] = int(np.shape(cond[i])[0]) if live else 0
+                self._cap[u] = INT32_MAX if mx[i] is None else lens[i] + int(mx[i])
         if samp is not None and self._samp is None:
             self._samp = np.zeros(self.capacity, dtype=np.dtype(_lib.SrwnGenSampling))
             self._samp["temperature"], self._samp["top_p"] = 1.0, 1.0
@@ -349,7 +390,76 @@ class GenerationPool(SlotTable):
         for u in self._slot_list(slots, "leave"):
             self._active[u] = False
             self._end[u] = self._t[u]
+            if self.live:
+                self._live[u] = False
         self._upload()
+
+    @property
+    def any_runnable(self) -> bool:
+        """Whether a step would make a sample now: some slot is before its end (a starved live slot is not)."""
+        return bool((self._t < self._end).any())
+
+    # ---- live slots
+    def _open_live(self, u: int) -> bool:
+        return bool(self.live and self._active[u] and self._live[u] and not self._closed[u])
+
+    def room(self, slot: int) -> int:
+        """Frames a live slot may be fed now (``live_decode_room`` of its own fed and t); 0 for every other slot."""
+        u, = self._slot_list(slot, "room")
+        if not self._open_live(u):
+            return 0
+        return live_decode_room(self.frames, int(self._fed[u]), int(self._t[u]), self.pool_stride)
+
+    def _check_feed(self, slots, frames):
+        """Everything feed refuses, before any device work: (slots, frames as tensors [k_i, E])."""
+        slots = self._slot_list(slots, "feed")
+        if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 2:
+            frames = [frames]
+        frames = [f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f, dtype=np.float32)) for f in frames]
+        if len(frames) != len(slots) or len(set(slots)) != len(slots):
+            raise ValueError("feed: %d distinct slots need one [k, %d] each, got %d" % (len(slots), self.E, len(frames)))
+        for u, f in zip(slots, frames):
+            if not self._open_live(u):
+                raise ValueError("feed: slot %d holds no live, open stream" % u)
+            if f.dim() != 2 or f.shape[1] != self.E:
+                raise ValueError("feed: frames of slot %d must be [k, %d], got %s" % (u, self.E, tuple(f.shape)))
+            if f.shape[0] > self.room(u):
+                raise ValueError("feed: %d frames for slot %d, but its ring of %d has room for %d at t = %d with %d fed"
+                                 % (f.shape[0], u, self.frames, self.room(u), self._t[u], self._fed[u]))
+        return slots, frames
+
+    def feed(self, slots, frames) -> None:
+        """The next frames of live slots: frames[i] [k_i, cond_channels] for slots[i], NumPy or device tensors (device
+        tensors are taken as they are).  Refuses (ValueError, before any device work, nothing changed) k_i > ``room``, a
+        slot that holds no live, open stream, and lists of different lengths.  The rows are ``_project_cond``'s -- the same
+        srwn_pw_linear over the same image, so the bits of the one-shot table -- scattered into the slots' rings by ONE
+        srwn_cond_ring_scatter_slots however many slots and frames; each slot's t_end grows to fed * pool_stride on the
+        host mirror and the device table together."""
+        from . import _lib
+        slots, frames = self._check_feed(slots, frames)
+        pairs = [(u, f) for u, f in zip(slots, frames) if f.shape[0] > 0]
+        if not pairs:
+            return
+        eng, F = self.eng, self.frames
+        rows = torch.cat([f.to(device=eng.dev, dtype=torch.float32) for _, f in pairs], dim=0)
+        dst = np.concatenate([u * F + (int(self._fed[u]) + np.arange(f.shape[0])) % F for u, f in pairs]).astype(np.int32)
+        LR = eng.L * eng.R
+        out = eng._project_cond(rows)
+        dst_dev = torch.from_numpy(dst).to(eng.dev)
+        _lib.call("srwn_cond_ring_scatter_slots", out.data_ptr(), LR, self.cond_all.data_ptr(), LR, int(rows.shape[0]),
+                  dst_dev.data_ptr(), self.capacity * F, LR, K.abi_dtype(eng.dt), torch.cuda.current_stream().cuda_stream)
+        for u, f in pairs:
+            self._fed[u] += int(f.shape[0])
+            self._end[u] = min(int(self._fed[u]) * self.pool_stride, int(self._cap[u]))
+        self._upload()
+
+    def close(self, slots) -> None:
+        """No more frames will come for the live streams in `slots`: each frees its slot at the end of what it was fed,
+        like a bounded stream (at once when it is already there)."""
+        for u in self._slot_list(slots, "close"):
+            if self.live and self._active[u] and self._live[u]:
+                self._closed[u] = True
+                self._active[u] = self._t[u] < self._end[u]
 
     def step(self, nsteps: int, mode: str = "sample", forced: Optional[torch.Tensor] = None, want_logits: bool = False):
         """One launch of `nsteps` pool steps: (audio [capacity, nsteps] f32, codes [capacity, nsteps] i32, logits
@@ -365,12 +475,31 @@ class GenerationPool(SlotTable):
         ran = np.clip(self._end - self._t, 0, nsteps)
         if nsteps == 0:
             return audio, codes, logits, ran
+        if self.live:
+            self._realign(ran)
         eng._launch_generation(self.ring, audio, codes, logits, forced, self.capacity, nsteps, mode, 0, self.clock,
-                               self.carry, self.sampling, self.cond_all, self.frames, self.slots)
+                               self.carry, self.sampling, self.cond_all, self.frames, self.slots, live=self.live)
         self._t += ran
+        if self.live:
+            self._stopped[ran > 0] = self.clock + ran[ran > 0]
         self.clock += nsteps
-        self._active &= self._t < self._end
+        if self.live:      # (a starved live slot stays taken until it is closed, left or at prompt + max_samples)
+            self._active &= (self._t < self._end) | (self._live & ~self._closed & (self._t < self._cap))
+        else:
+            self._active &= self._t < self._end
         return audio, codes, logits, ran
+
+    def _realign(self, ran) -> None:
+        """Before a launch of a live pool: every slot that will run and whose last own step did not end at this clock has
+        the columns of its layer rings rotated by ``live_slot_shift``, all of them in one srwn_generate_ring_rotate_slots."""
+        eng = self.eng
+        us = [int(u) for u in np.flatnonzero(ran > 0)]
+        sh = [live_slot_shift(self.clock, self._stopped[u]) for u in us]
+        lag = [(u, s) for u, s in zip(us, sh) if s != 0]
+        if not lag:
+            return
+        tab = torch.tensor(lag, dtype=torch.int32).t().contiguous().to(eng.dev)      # [2, n]: the slots, their shifts
+        K.ring_rotate_slots(self.ring, eng._gen_dilations(), eng.L, self.capacity, eng.R, tab[0], tab[1])
 
 
 CONTRASTIVE_LDS_FLOATS = 65536 // 4   # srwn_contrastive_head: rows*D + 2P floats in one workgroup (csrc/srwn_siamese.hip)
@@ -1631,8 +1760,8 @@ class WaveNetEngine:
         else:
             tail = (md,) + dtype + (st, t0, carry.data_ptr(), slots.data_ptr())
         entry = self._GEN_ENTRY[g16][bool(self.mol)][slots is not None]
-        if live:      # the live forms (srwn_version() 112) are named after their *_mol_resume_sampled twins
-            entry = entry.replace("_resume_", "_live_")
+        if live:      # the live forms (srwn_version() 112, 114) are named after their *_mol_{resume,slots}_sampled twins
+            entry = entry.replace("_resume_", "_live_").replace("_slots_", "_live_slots_")
         _lib.call(entry, *weights, *shared, *head, *tail, ptr(sampling))
 
     def generate(self, nsteps: int, mode: str = "sample", seed: int = 0, forced: Optional[torch.Tensor] = None,
@@ -1760,12 +1889,18 @@ class WaveNetEngine:
         state.fed += k
         state.limit = state.fed * pool
 
-    def generation_pool(self, capacity: int, frames: Optional[int] = None) -> "GenerationPool":
+    def generation_pool(self, capacity: int, frames: Optional[int] = None, *, live: bool = False) -> "GenerationPool":
         """A pool of `capacity` generation slots that streams join and leave while it runs (GenerationPool); `frames` = the
         most conditioning frames a stream of a conditioned decoder brings.  Refuses, before any device work, what
-        `generate` refuses.  The generation weight images are gathered here: the pool keeps the weights it started with."""
+        `generate` refuses.  The generation weight images are gathered here: the pool keeps the weights it started with.
+        live=True (the conditioned mixture-of-logistics decoder only, refused otherwise as `live_generation_state` does):
+        `frames` is the length of every slot's conditioning ring and streams may ``join(..., live=True)`` to be fed while
+        they run; bounded streams still join such a pool.  A pool made without it runs the launches it always ran."""
         self._check_generates()
         self._refuse_conditioned_softmax()
+        if live and not (self.mol and self.E):
+            raise ValueError("this decoder is not conditioned: a live pool feeds the conditioned mixture-of-logistics "
+                             "decoder")
         if int(capacity) < 1:
             raise ValueError("generation_pool: capacity %d" % int(capacity))
         if self.mol and self.E:
@@ -1773,7 +1908,7 @@ class WaveNetEngine:
                 raise ValueError("this decoder is conditioned: pass frames, the most encoding frames of a stream")
         elif frames is not None:
             raise ValueError("this decoder is not conditioned: no frames")
-        return GenerationPool(self, int(capacity), int(frames or 0))
+        return GenerationPool(self, int(capacity), int(frames or 0), bool(live))
 
     def _prime_view(self, B: int, T: int) -> "WaveNetEngine":
         """A forward-only (frozen) view of this stack at (B, T), kept for the next prompt of the same shape."""

@@ -35,6 +35,18 @@ def _need_gpu() -> None:
         raise RuntimeError("sr-wavenet_amd needs an MI355X (HIP) device; there is no CPU fallback")
 
 
+# (named here: engine.py's quoted generator names are its launch table's and the ring fills', tests/test_generate_launch.py)
+_RING_ROTATE_SLOTS = "srwn_generate_ring_rotate_slots"
+
+
+def ring_rotate_slots(ring: torch.Tensor, dilations, nlayers: int, capacity: int, R: int, slot_ids: torch.Tensor,
+                      shift: torch.Tensor) -> None:
+    """The layer-ring columns of the pool slots `slot_ids` (device int32 [n], distinct) rotated in place by `shift`
+    (device int32 [n], >= 0) positions: new[(p + shift) mod (d_l + 1)] = old[p] in every layer (srwn.h)."""
+    call(_RING_ROTATE_SLOTS, ring.data_ptr(), dilations, nlayers, capacity, R, slot_ids.data_ptr(), shift.data_ptr(),
+         int(slot_ids.shape[0]), abi_dtype(ring.dtype), _stream())
+
+
 def run_cached_graph(graphs: dict, seen: set, key, enabled: bool, launch) -> None:
     """Runs the launch sequence `launch()` of `key`: a replay of its hipGraph once captured; on the second sight of the
     key (with graphs `enabled`) the sequence is captured, kept in `graphs` and replayed; before that, and with graphs

@@ -576,17 +576,29 @@ class GenerationPool(_PoolFace):
     join and leave while it runs.  ``join(seed=[...], prompt=[...], ...)`` takes one entry per stream and returns their
     slots; ``step(n)`` runs n pool steps in one launch and returns ``{slot: samples}`` of every slot that produced some; a
     stream that reaches its end frees its slot; ``leave(slots)`` ends streams early.  A stream's samples put together are
-    what a batch-of-one ``generate`` with its seed and prompt returns."""
+    what a batch-of-one ``generate`` with its seed and prompt returns.  On a live pool
+    (``WaveNetAutoEncoder.generation_pool(..., live=True)``) ``join(..., live=True)`` / ``feed`` / ``room`` / ``close``
+    mirror ``SynthesisPool``: the stream is fed while it runs and waits, with no samples, while it has none to make."""
 
-    def __init__(self, pool, cond_fn, mode):
+    def __init__(self, pool, cond_fn, mode, latent=None, condition_size=0):
         self._pool, self._cond_fn, self.mode = pool, cond_fn, mode
+        self._latent, self._cs = latent, int(condition_size)
+        self._live_cond = {}      # slot -> the conditions of the live stream joined there last
 
     t = property(lambda self: self._pool.t)
 
     def join(self, seed, prompt=None, encoding=None, conditions=None, max_samples=None, *, temperature=None, top_k=None,
-             top_p=None):
+             top_p=None, live=False):
         """temperature / top_k / top_p: the joining streams' sampling controls (a scalar or one entry per stream; None = the
-        default), as `generate` takes them."""
+        default), as `generate` takes them.  encoding: one [frames_i, latent] per stream.
+        live=True (a live pool): a single 2-D array is one stream; an encoding holds a stream's first frames ([0, latent]: none yet), its conditions are kept
+        and tiled onto every frame fed later (``feed``); a live stream that has used up its frames waits (no samples)
+        until it is fed, closed or left."""
+        if live:
+            K._need_gpu()
+        if live and isinstance(encoding, np.ndarray) and encoding.ndim == 2:
+            encoding = [encoding]
+            conditions = None if conditions is None else [conditions]
         seeds = [int(s) for s in (seed if np.ndim(seed) else [seed])]
         n = len(seeds)
         prompts = per_stream(prompt, n, "prompts")
@@ -596,9 +608,39 @@ class GenerationPool(_PoolFace):
         prompts = [None if p is None else np.asarray(p, dtype=np.float32) for p in prompts]
         mx = per_stream(max_samples, n, "max_samples")
         cond = self._cond_fn(n, encoding, conditions)
+        if live:
+            slots = self._pool.join(seeds, prompts, cond, mx, temperature=temperature, top_k=top_k, top_p=top_p, live=True)
+            if self._cs > 0:
+                for u, c in zip(slots, per_stream(conditions, n, "conditions")):
+                    self._live_cond[u] = np.asarray(c, dtype=np.float32).reshape(1, self._cs)
+            return slots
         if temperature is None and top_k is None and top_p is None:
             return self._pool.join(seeds, prompts, cond, mx)
         return self._pool.join(seeds, prompts, cond, mx, temperature=temperature, top_k=top_k, top_p=top_p)
+
+    def feed(self, slots, encoding):
+        """The next frames of live slots: encoding[i] [k_i, latent] for slots[i] (k_i <= ``room``)."""
+        slots = slot_list(slots, self.capacity, "feed")
+        if isinstance(encoding, np.ndarray) and encoding.ndim == 2:
+            encoding = [encoding]
+        encs = [np.asarray(e, dtype=np.float32) for e in encoding]
+        if len(encs) != len(slots):
+            raise ValueError("feed: %d slots but %d encodings" % (len(slots), len(encs)))
+        for e in encs:
+            if e.ndim != 2 or e.shape[1] != self._latent:
+                raise ValueError("feed: each encoding is [k, %s], got shape %s" % (self._latent, e.shape))
+        if self._cs > 0:
+            if any(u not in self._live_cond for u in slots):
+                raise ValueError("feed: slots %s are not all live streams of this pool" % (slots,))
+            encs = [_tile_conditions_np(e, self._live_cond[u]) for u, e in zip(slots, encs)]
+        self._pool.feed(slots, encs)
+
+    def room(self, slot):
+        return self._pool.room(int(slot))
+
+    def close(self, slots):
+        """No more frames will come for these live streams: each frees its slot at the end of what it was fed."""
+        self._pool.close(slots)
 
     def step(self, n, mode=None, forced=None):
         a, _, _, ran = self._pool.step(int(n), mode=mode or self.mode, forced=forced)
@@ -812,16 +854,22 @@ class WaveNetAutoEncoder(object):
         eng, st, _ = self._prompted_state(encoding, conditions, seed, prompt, ctl)
         return _stream_chunks(eng.dec, st, int(chunk_size), mode, max_samples)
 
-    def generation_pool(self, capacity, frames, mode="sample"):
+    def generation_pool(self, capacity, frames, mode="sample", *, live=False):
         """A pool of `capacity` decoder slots that streams join and leave while it runs (GenerationPool): `frames` = the
         most encoding frames a stream brings; each join takes one encoding [frames_i, latent_channels] (and conditions
-        [condition_size]) per stream, which ends at frames_i * pool_stride."""
+        [condition_size]) per stream, which ends at frames_i * pool_stride.
+        live=True: `frames` is the length of every slot's conditioning ring, and streams that ``join(..., live=True)`` are
+        fed while they run (``feed`` / ``room`` / ``close``), with no bound on their length; bounded streams still join."""
         if int(capacity) < 1:
             raise ValueError("generation_pool: capacity %d" % int(capacity))
         if frames is None or int(frames) < 1:
             raise ValueError("generation_pool: frames %r (the most encoding frames of a stream)" % (frames,))
+        if live:
+            K._need_gpu()
         eng = self._eng or self._engine(1, int(frames) * self.pool_stride)
-        return GenerationPool(eng.dec.generation_pool(int(capacity), int(frames)), self._pool_cond, mode)
+        pool = eng.dec.generation_pool(int(capacity), int(frames), live=True) if live else \
+            eng.dec.generation_pool(int(capacity), int(frames))
+        return GenerationPool(pool, self._pool_cond, mode, self.latent_channels, self.condition_size)
 
     def _pool_cond(self, n, encoding, conditions):
         return _pool_encodings(n, encoding, conditions, self.latent_channels, self.condition_size)
@@ -1057,6 +1105,13 @@ class TeacherResynthesizer(object):
         if chunk_size < 1:
             raise ValueError("chunk_size %d: at least 1" % chunk_size)
         return TeacherResynthesisStream(self, batch, conditions, seed, temperature, chunk_size)
+
+    def pool(self, chunk_size=160, audio_ring=None):
+        """A ``TeacherResynthesisPool``: independent callers on one encoder and one decoder.  Streams join and leave while
+        the batch runs, audio arrives ragged, and each caller receives what it would have received alone.  chunk_size: the
+        samples a ``step`` makes per stream at most; audio_ring: samples of audio a slot can hold (``AudioEncoder.pool``)."""
+        K._need_gpu()
+        return TeacherResynthesisPool(self, int(chunk_size), audio_ring)
 
 
 class TeacherResynthesisStream(_ResynthesisStream):
@@ -1643,31 +1698,18 @@ class ResynthesisStream(_ResynthesisStream):
         return self._owner.synthesizer.live(batch, conditions, seed, temperature)
 
 
-class ResynthesisPool(SlotTable):
-    """``Resynthesizer.pool()``: an encoder pool and a live synthesis pool sharing slot ids; capacity is the smaller
-    ``max_batch``.  ``join`` returns slots, ``push(slots, audio)`` takes one 1-D array per slot of any length (at most
-    ``audio_room(slot)``), ``finish(slots)`` ends streams, ``step()`` returns ``{slot: samples}``.  One step: the encoder
-    emits for each slot at most the frames the synthesizer's conditioning ring has room for (the rest stays audio in the
-    slot's audio ring: there is no second queue), the new frames are fed as device tensors with the slot's conditions
-    tiled on, the slots whose audio is finished and fully encoded are closed, and the synthesizer makes up to
-    ``chunk_size`` samples per slot.  A stream that reaches its end frees its slot in both halves.  A stream's samples
-    put together are ``synthesizer.synthesize(encoder.encode(audio), conditions, seed, temperature)`` of it alone."""
+class _ResynthesisPool(SlotTable):
+    """What ``ResynthesisPool`` and ``TeacherResynthesisPool`` share: an encoder pool ``_enc`` and a live decoding half
+    ``_half`` (a pool with ``room`` / ``feed`` / ``close`` / ``leave`` / ``t`` and ``_active``) sharing slot ids, the
+    streams' conditions ``_cond`` (slot -> [1, condition_size] on the device, None without: a slot is taken while it has an
+    entry), ``_cs`` and ``_chunk``.  A subclass gives ``_half``, ``_half_join`` and ``_half_step``.
+    One ``step``: the encoder emits for each slot at most the frames the decoding half's conditioning ring has room for
+    (the rest stays audio in the slot's audio ring: there is no second queue), the new frames are fed as device tensors
+    with the slot's conditions tiled on, the slots whose audio is finished and fully encoded are closed, and the
+    decoding half makes up to ``chunk_size`` samples per slot.  A stream that reaches its end frees its slot in both
+    halves."""
 
-    def __init__(self, owner, chunk_size, audio_ring):
-        from .student import live_min_frames
-        enc, syn = owner.encoder, owner.synthesizer
-        if not 1 <= chunk_size <= syn.max_chunk:
-            raise ValueError("chunk_size %d: 1..max_chunk = %d" % (chunk_size, syn.max_chunk))
-        need = live_min_frames(max(syn._eng.hist), owner.pool_stride)
-        if syn.max_frames < need:
-            raise ValueError("pool: live streams need a synthesizer ring of max_frames >= %d frames, this one holds %d"
-                             % (need, syn.max_frames))
-        self._owner, self._chunk = owner, chunk_size
-        self.capacity = min(enc.max_batch, syn.max_batch)
-        self._cs = syn.condition_size
-        self._enc = enc._eng.pool(audio_ring)
-        self._syn = syn._eng.pool()
-        self._cond = {}        # slot -> its stream's conditions [1, condition_size] on the device (None without)
+    _who = "student"
 
     @property
     def _active(self):      # (what SlotTable reads: a slot is taken while it has an entry in _cond)
@@ -1676,7 +1718,7 @@ class ResynthesisPool(SlotTable):
     @property
     def t(self):
         """Samples returned so far, per slot."""
-        return self._syn.t[:self.capacity]
+        return self._half.t[:self.capacity]
 
     @property
     def received(self):
@@ -1696,9 +1738,9 @@ class ResynthesisPool(SlotTable):
         (stream i draws with s + i) or one per stream, temperature None, a scalar or one per stream.  Returns the slots."""
         n = int(n)
         slots = self._take_slots(n, None)
-        c = _device_conditions(n, conditions, self._cs, "student")
+        c = _device_conditions(n, conditions, self._cs, self._who)
         conds = [None if c is None else c[i:i + 1] for i in range(n)]
-        self._syn.join([None] * n, seed, temperature, slots=slots, live=True)
+        self._half_join(n, seed, temperature, slots)
         self._enc.join(slots=slots)
         for u, c in zip(slots, conds):
             self._cond[u] = c
@@ -1715,27 +1757,97 @@ class ResynthesisPool(SlotTable):
         """Ends these streams where they are and frees their slots in both halves."""
         slots = self._slots(slots, "leave")
         self._enc.leave(slots)
-        self._syn.leave(slots)
+        self._half.leave(slots)
         for u in slots:
             del self._cond[u]
 
     def step(self):
         if not self._cond:
             return {}
-        enc, syn = self._enc, self._syn
-        frames = enc.step({u: syn.room(u) for u in enc.active})
+        enc, half = self._enc, self._half
+        frames = enc.step({u: half.room(u) for u in enc.active})
         if frames:
             us = sorted(frames)
             fr = [frames[u] if self._cond[u] is None else _tile_conditions(frames[u][None], self._cond[u])[0] for u in us]
-            syn.feed(us, fr)
+            half.feed(us, fr)
         done = [u for u in self._cond if not enc._active[u]]          # finished and fully encoded: the stream's end is known
         if done:
-            syn.close(done)
-        a, ran = syn.step(self._chunk)
+            half.close(done)
+        a, ran = self._half_step(self._chunk)
         out = _ran_dict(a, ran, self._cond) if ran.any() else {}
-        for u in [u for u in self._cond if not syn._active[u]]:
+        for u in [u for u in self._cond if not half._active[u]]:
             del self._cond[u]
         return out
+
+
+class ResynthesisPool(_ResynthesisPool):
+    """``Resynthesizer.pool()``: an encoder pool and a live synthesis pool sharing slot ids; capacity is the smaller
+    ``max_batch``.  ``join`` returns slots, ``push(slots, audio)`` takes one 1-D array per slot of any length (at most
+    ``audio_room(slot)``), ``finish(slots)`` ends streams, ``step()`` returns ``{slot: samples}`` (``_ResynthesisPool``:
+    frames the synthesizer's ring has room for, fed as device tensors; up to ``chunk_size`` samples per slot).  A stream's
+    samples put together are ``synthesizer.synthesize(encoder.encode(audio), conditions, seed, temperature)`` of it
+    alone."""
+
+    def __init__(self, owner, chunk_size, audio_ring):
+        from .student import live_min_frames
+        enc, syn = owner.encoder, owner.synthesizer
+        if not 1 <= chunk_size <= syn.max_chunk:
+            raise ValueError("chunk_size %d: 1..max_chunk = %d" % (chunk_size, syn.max_chunk))
+        need = live_min_frames(max(syn._eng.hist), owner.pool_stride)
+        if syn.max_frames < need:
+            raise ValueError("pool: live streams need a synthesizer ring of max_frames >= %d frames, this one holds %d"
+                             % (need, syn.max_frames))
+        self._owner, self._chunk = owner, chunk_size
+        self.capacity = min(enc.max_batch, syn.max_batch)
+        self._cs = syn.condition_size
+        self._enc = enc._eng.pool(audio_ring)
+        self._syn = syn._eng.pool()
+        self._cond = {}        # slot -> its stream's conditions [1, condition_size] on the device (None without)
+
+    _half = property(lambda self: self._syn)
+
+    def _half_join(self, n, seed, temperature, slots):
+        self._syn.join([None] * n, seed, temperature, slots=slots, live=True)
+
+    def _half_step(self, chunk):
+        return self._syn.step(chunk)
+
+
+class TeacherResynthesisPool(_ResynthesisPool):
+    """``TeacherResynthesizer.pool()``: an encoder pool and a LIVE generation pool of the decoder sharing slot ids;
+    capacity is the encoder's ``max_batch``, the decoder's conditioning rings hold ``max_frames`` frames.  The contract of
+    ``ResynthesisPool`` at teacher quality: ``join`` returns slots, ``push(slots, audio)`` takes one 1-D array per slot of
+    any length (at most ``audio_room(slot)``), ``finish(slots)`` ends streams, ``step()`` returns ``{slot: samples}``.  A
+    stream's samples put together are ``autoencoder.generate(encoder.encode(audio), conditions, seed=seed,
+    temperature=temperature)`` of it alone."""
+
+    _who = "auto-encoder"
+
+    def __init__(self, owner, chunk_size, audio_ring):
+        if chunk_size < 1:
+            raise ValueError("chunk_size %d: at least 1" % chunk_size)
+        enc, ae = owner.encoder, owner.autoencoder
+        self._owner, self._chunk = owner, chunk_size
+        self.capacity = int(enc.max_batch)
+        self._cs = int(ae.condition_size)
+        self._enc = enc._eng.pool(audio_ring)
+        eng = ae._eng or ae._engine(1, owner.max_frames * owner.pool_stride)
+        self._dec = eng.dec.generation_pool(self.capacity, owner.max_frames, live=True)
+        self._cond = {}        # slot -> its stream's conditions [1, condition_size] on the device (None without)
+
+    _half = property(lambda self: self._dec)
+
+    def _half_join(self, n, seed, temperature, slots):
+        sd = np.asarray(seed)
+        seeds = [int(sd) + i for i in range(n)] if sd.ndim == 0 else [int(v) for v in per_stream(seed, n, "seeds", default=0)]
+        self._dec.join(seeds, None, [None] * n, None, slots, temperature=temperature, live=True)
+
+    def _half_step(self, chunk):
+        dec = self._dec
+        if not dec.any_runnable:      # every stream waits for frames: nothing is launched
+            return None, np.zeros(self.capacity, np.int64)
+        a, _, _, ran = dec.step(chunk, mode="sample")
+        return a, ran
 
 
 class SiameseWaveNet(_EngineOwner):
