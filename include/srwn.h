@@ -1253,6 +1253,70 @@ int srwn_window_mean(const float* ring, int32_t ring_rows, float* mean, const in
 int srwn_recog_roll(const int64_t* roll_table, int32_t nroll, const float* x, int64_t x_stride, float* carry,
                     int64_t* clock, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream);
 
+/* ---- classifier pools (since srwn_version() 115; csrc/srwn_recog.hip, csrc/srwn_group.hip): the launches of the streaming
+ * classifier above (class WaveNet, createNetwork, model.py:33-62) for `capacity` SLOTS over one set of buffers, every slot a
+ * stream at a clock of its own.  The device table slots[capacity] of SrwnSynthSlot replaces the clock, with the meaning it
+ * has for the synthesis pools: t is the absolute time of the slot's next row, and the slot owns ran(u) = clamp(t_end - t,
+ * 0, n) rows of a chunk of n = k * hop.  For the classifier t and ran are multiples of hop (t >= 0).  The HOST writes the
+ * whole table before every step -- t = the samples the slot's stack has consumed, t_end = t + the whole hops the step
+ * gives it -- and no launch modifies it: there is no device advance and no arrive counter.  A slot with ran = 0 (free, or
+ * no whole hop waiting) has no group segment, no head workgroup that works, no roll; its rows of mean, logits and
+ * probabilities are zeros / the softmax of the bias and are discarded by the caller.  A stream has the bits the clock
+ * forms give a batch of one: in any slot, whenever it joined, however its audio was cut, whatever k the steps had and
+ * whatever the other slots hold.  The segment cut of the group launch and every grid depend on (capacity, k) and the
+ * chip alone, so a captured graph serves every step of its k.
+ *
+ * A join zeroes the history rows of the joined slots: srwn_flow_stream_reset_slots with the classifier's roll table and
+ * ncarry = 0 (carry NULL).  The hop-sum ring needs NO reset: srwn_window_mean_slots emits zeros while j < nW - 1, and from
+ * then on a window reads the rows j - nW + 1 .. j >= 0 only, every one of which this stream wrote (ring_rows >= nW + k -
+ * 1 keeps them apart); what an earlier stream left in the slot's ring is never read.  The audio lives in the pool's audio
+ * ring [capacity][ring_len] fp32, sample s of a slot in column s mod ring_len (the layout srwn_audio_ring_put writes);
+ * ring_len >= max_chunk + 1, so that sample t - 1 is still there beside a whole chunk: there is no carry array.
+ *
+ *   srwn_recog_stream_in_slots      srwn_recog_stream_in for rows [out_hist, out_hist + ran(u)) of slot u: row i from the
+ *                                   samples slots[u].t + i - 1 and slots[u].t + i of the audio ring (x[-1] = 0 at time
+ *                                   0); arithmetic and rounding of the clock form.  Other rows are not touched.
+ *   srwn_residual_group_fwd_stream_z_slots
+ *                                   srwn_residual_group_fwd_stream_slots (its arguments, its bits in x_out) that also
+ *                                   stores z of every layer of the group for the slot's own chunk rows [0, ran(u)), as
+ *                                   srwn_residual_group_fwd_stream_z lays them out (slot u in the place of stream b);
+ *                                   rows >= ran(u) of x_out and z_out are not touched.  R in {32, 64}, bf16 and fp32.
+ *   srwn_pooled_stream_head_slots   srwn_pooled_stream_head with one workgroup per (slot u, hop i < k) that works only
+ *                                   when (i + 1) * hop <= ran(u) and otherwise returns without touching the ring.  H_j
+ *                                   goes to row j mod ring_rows of slot u's ring, j = slots[u].t / hop + i.  The
+ *                                   arithmetic and the order of every sum are the clock form's (one device body).
+ *   srwn_hop_sum_slots              the parity twin, as srwn_hop_sum is srwn_pooled_stream_head's.
+ *   srwn_window_mean_slots          srwn_window_mean with row u * k + i from slot u's ring at j = slots[u].t / hop + i;
+ *                                   the row is zero where j < nW - 1 or (i + 1) * hop > ran(u).  logits as in the clock
+ *                                   form; srwn_pooled_head over capacity * k rows gives the probabilities.
+ *   srwn_recog_roll_slots           the history roll of every buffer of roll_table by ran(u) rows (rows [ran, ran +
+ *                                   hist) to the front), for the slots with ran > 0.  Nothing else: no carry, no clock.
+ * Errors: a null pointer (-3), a width that is not built (-4), capacity < 1, a chunk, a buffer or a ring that does not fit
+ * (-2; ring_len < max_chunk + 1 among them), dtype (-1). */
+int srwn_recog_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w, const float* init_b,
+                               void* out, int64_t out_clip_rows, int32_t out_hist, int32_t capacity, int32_t n,
+                               int32_t max_chunk, int32_t R, int32_t dtype, const SrwnSynthSlot* slots, void* stream);
+int srwn_residual_group_fwd_stream_z_slots(const void* x_in, int64_t in_clip_rows, void* x_out, int64_t out_clip_rows,
+                                           int32_t out_hist, void* z_out, int64_t z_layer_stride,
+                                           const void* const* wconv, const void* const* wres,
+                                           const float* const* bias_f, const float* const* bias_r,
+                                           const void* const* cond_next, int32_t cond_frames, int32_t pool_stride,
+                                           int32_t cond_row_stride, const int32_t* dilations, int32_t nlayers,
+                                           int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t K,
+                                           int32_t dtype, const SrwnSynthSlot* slots, void* stream);
+int srwn_pooled_stream_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                  const void* wskip, const float* bs_sum, const void* w1, const float* b1, float* ring,
+                                  int32_t ring_rows, const SrwnSynthSlot* slots, int32_t capacity, int32_t k, int32_t hop,
+                                  int32_t max_chunk, int32_t R, int32_t S, int32_t dtype, void* stream);
+int srwn_hop_sum_slots(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows, const SrwnSynthSlot* slots,
+                       int32_t capacity, int32_t k, int32_t hop, int32_t max_chunk, int32_t S, int32_t dtype,
+                       void* stream);
+int srwn_window_mean_slots(const float* ring, int32_t ring_rows, float* mean, const SrwnSynthSlot* slots, int32_t capacity,
+                           int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2,
+                           float* logits, int32_t C, int32_t ldw, void* stream);
+int srwn_recog_roll_slots(const int64_t* roll_table, int32_t nroll, const SrwnSynthSlot* slots, int32_t capacity, int32_t n,
+                          int32_t max_chunk, int32_t R, int32_t dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

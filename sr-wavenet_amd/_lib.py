@@ -254,6 +254,14 @@ for _n in ("srwn_generate", "srwn_generate16"):
 del _n
 SIGNATURES["srwn_generate_ring_rotate_slots"] = (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p])
 SIGNATURES["srwn_cond_ring_scatter_slots"] = (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i32, _i32, _i32, _p])
+# classifier pools (srwn_version() 115): the slot forms of the streaming classifier's launches, on the device table of
+# SrwnSynthSlot for the clock; the stream entry reads the pool's audio ring and there is no carry
+SIGNATURES["srwn_recog_stream_in_slots"] = (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p])
+SIGNATURES["srwn_residual_group_fwd_stream_z_slots"] = SIGNATURES["srwn_residual_group_fwd_stream_z"]
+SIGNATURES["srwn_pooled_stream_head_slots"] = SIGNATURES["srwn_pooled_stream_head"]
+SIGNATURES["srwn_hop_sum_slots"] = SIGNATURES["srwn_hop_sum"]
+SIGNATURES["srwn_window_mean_slots"] = SIGNATURES["srwn_window_mean"]
+SIGNATURES["srwn_recog_roll_slots"] = (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -89,6 +89,20 @@ struct GroupFwdStreamZArgs : GroupFwdStreamArgs {
   long long z_clip_rows;
 };
 
+// The SLOTS && ZS instantiations (srwn_residual_group_fwd_stream_z_slots: classifier pools): the slot form that stores z as
+// the z form does, for the rows the slot has in this chunk -- chunk rows [0, ran) of slot b; a slot without rows has no
+// segment and stores nothing.  A struct of its own, so that the other instantiations keep their arguments.
+struct GroupFwdSlotZArgs : GroupFwdSlotArgs {
+  long long z_clip_rows;
+};
+
+// which of the argument structs above an instantiation takes
+template <bool STREAM, bool SLOTS, bool ZS> struct GroupFwdArgsOf {
+  typedef typename std::conditional<SLOTS, typename std::conditional<ZS, GroupFwdSlotZArgs, GroupFwdSlotArgs>::type,
+      typename std::conditional<ZS, GroupFwdStreamZArgs,
+          typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type>::type>::type type;
+};
+
 // In-kernel time stamps (MI355X guide, "In-kernel stamps"): lane 0 of waves 0 and 1 of workgroup 0 append the shader
 // clock to a buffer no other code reads.  Compiled in only when a buffer was registered (STAMP instantiation).
 template <bool STAMP> struct Stamper {
@@ -113,11 +127,10 @@ template <> struct Stamper<true> {
 template <typename T, int RT, bool COND, int MAXT, int NWB, int NWV = 8, bool WDMA = true, bool STAMP = false, bool WT = false, bool IC = false,
           bool STREAM = false, bool SLOTS = false, bool ZS = false>
 __global__ __launch_bounds__(64 * NWV) void group_fwd_kernel(
-    typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<ZS, GroupFwdStreamZArgs,
-        typename std::conditional<STREAM, GroupFwdStreamArgs, GroupFwdArgs>::type>::type>::type a) {
+    typename GroupFwdArgsOf<STREAM, SLOTS, ZS>::type a) {
   static_assert(!IC || (WT && !COND), "input conv fused in: the unconditioned weight-gradient-tile kernels only");
   static_assert(!SLOTS || STREAM, "slot form: a stream form");
-  static_assert(!ZS || (STREAM && !SLOTS), "z of the chunk's rows: the clock stream form only");
+  static_assert(!ZS || STREAM, "z of the chunk's rows: the stream forms only");
   static_assert(!STREAM || (COND && !WT && !IC && !STAMP), "stream form: the conditioned plain kernels only");
   constexpr int R = 32 * RT, K = 2, KS = R / 16;
   constexpr int NCONV = RT * K * KS, NRES = RT * KS, NW = NCONV + NRES;   // weight fragments per layer
@@ -1433,7 +1446,7 @@ int launch_group_fwd(GroupFwdArgs& a, bool cond, int seg_rows, hipStream_t st) {
 // the whole H (the history supplies it).  The cut depends on (B, n, st, H) and the chip alone -- never on the clock -- so a
 // captured launch stays valid for every chunk of its size.
 template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool SLOTS = false, bool ZS = false>
-int launch_group_fwd_stream(typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<ZS, GroupFwdStreamZArgs, GroupFwdStreamArgs>::type>::type& a, int n, hipStream_t st) {
+int launch_group_fwd_stream(typename GroupFwdArgsOf<true, SLOTS, ZS>::type& a, int n, hipStream_t st) {
   constexpr int R = 32 * RT, KS = R / 16, NW = RT * 2 * KS + RT * KS;
   const size_t fixed = (size_t)NWB * NW * 64 * sizeof(Frag<T>) + (size_t)NWB * 2 * R * 4;
   const size_t row_bytes = (size_t)RowStage<T>::stride(R) * sizeof(T);
@@ -1465,7 +1478,8 @@ int launch_group_fwd_stream(typename std::conditional<SLOTS, GroupFwdSlotArgs, t
   hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh);
   if (e != hipSuccess) return set_error((int)e, "residual_group_fwd_stream: LDS %zu: %s", sh, hipGetErrorString(e));
   hipLaunchKernelGGL(kfn, grid, block, sh, st, a);
-  return check_launch(SLOTS ? "residual_group_fwd_stream_slots" : (ZS ? "residual_group_fwd_stream_z" : "residual_group_fwd_stream"));
+  return check_launch(SLOTS ? (ZS ? "residual_group_fwd_stream_z_slots" : "residual_group_fwd_stream_slots")
+                            : (ZS ? "residual_group_fwd_stream_z" : "residual_group_fwd_stream"));
 }
 
 template <typename T, int RT, int MAXT, int NWB, int NWV = 8, bool WT = false>
@@ -1748,7 +1762,7 @@ int group_fwd_stream_impl(const void* x_in, int64_t in_clip_rows, void* x_out, i
   if (nlayers < 1 || nlayers > kMaxGroup || B < 1 || max_chunk < 1 || out_hist < 0)
     return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: nlayers=%d (max %d) B=%d max_chunk=%d out_hist=%d", nlayers, kMaxGroup, B, max_chunk, out_hist);
   if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "residual_group_fwd_stream: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  typename std::conditional<SLOTS, GroupFwdSlotArgs, typename std::conditional<ZS, GroupFwdStreamZArgs, GroupFwdStreamArgs>::type>::type a;
+  typename GroupFwdArgsOf<true, SLOTS, ZS>::type a;
   a.safe_wait = safe_wait();
   a.x0 = x_in; a.x_out = x_out; a.z_out = nullptr; a.layer_stride = 0;
   if constexpr (ZS) { a.z_out = z_out; a.layer_stride = z_layer_stride; a.z_clip_rows = max_chunk; }
@@ -1833,6 +1847,22 @@ extern "C" int srwn_residual_group_fwd_stream_slots(const void* x_in, int64_t in
                                      max_chunk, R, K, dtype, slots, stream);
 }
 
+
+// The z slot form (classifier pools, srwn.h): the slot form that also stores every layer's z of the rows a slot has in the
+// chunk.
+extern "C" int srwn_residual_group_fwd_stream_z_slots(const void* x_in, int64_t in_clip_rows, void* x_out,
+                                                      int64_t out_clip_rows, int32_t out_hist, void* z_out,
+                                                      int64_t z_layer_stride, const void* const* wconv,
+                                                      const void* const* wres, const float* const* bias_f,
+                                                      const float* const* bias_r, const void* const* cond_next,
+                                                      int32_t cond_frames, int32_t pool_stride, int32_t cond_row_stride,
+                                                      const int32_t* dilations, int32_t nlayers, int32_t capacity,
+                                                      int32_t n, int32_t max_chunk, int32_t R, int32_t K, int32_t dtype,
+                                                      const SrwnSynthSlot* slots, void* stream) {
+  return group_fwd_stream_impl<true, true>(x_in, in_clip_rows, x_out, out_clip_rows, out_hist, wconv, wres, bias_f, bias_r,
+                                           cond_next, cond_frames, pool_stride, cond_row_stride, dilations, nlayers,
+                                           capacity, n, max_chunk, R, K, dtype, slots, stream, z_out, z_layer_stride);
+}
 
 // The FIRST group of a stack with the stack's input conv fused in (model.py:40 / 172-173; K = 2 taps, 1 -> R channels,
 // RightShift as `shift`): what srwn_causal_conv1d_fwd would have written to x0 is computed into the segment image, in

@@ -15,7 +15,15 @@
 // A stream only ever advances by whole hops at hop-aligned absolute times, and a hop's 32-row tiles are cut from the
 // hop's first row: every ring row depends on absolute time only, so a stream has the same bits in any chunking, at any
 // batch size and in any row of the batch.
+//
+// The slot forms (classifier pools; srwn.h, srwn_version() 115) are the same kernels on the pool's table of SrwnSynthSlot
+// instead of the clock: slot u is a stream at its own absolute time slots[u].t (a multiple of hop) with ran = clamp(t_end -
+// t, 0, n) rows in this chunk (a multiple of hop too).  The host writes the whole table before every step and no launch
+// modifies it.  What the clock forms take from *clock they take from the slot; a workgroup or thread whose hop or row lies
+// beyond ran returns before it reads or writes anything.  The stream entry reads the audio -- and the sample before the
+// chunk -- from the pool's audio ring, so the slot forms keep no carry.
 #include <cmath>
+#include <type_traits>
 #include "srwn_common.h"
 #include "srwn_host.h"
 #include "../../include/srwn.h"
@@ -57,6 +65,50 @@ __global__ __launch_bounds__(256) void recog_stream_in_kernel(const float* __res
   store4(d + 4, v[4], v[5], v[6], v[7]);
 }
 
+// the clock or the table: what a kernel's SLOTS instantiation takes in the place of the clock
+template <bool SLOTS> struct When { typedef typename std::conditional<SLOTS, const SrwnSynthSlot*, const long long*>::type type; };
+
+// rows slot `sl` has in a chunk of n
+__device__ __forceinline__ int slot_ran(const SrwnSynthSlot& sl, int n) {
+  const long long left = sl.t_end - sl.t;
+  return left <= 0 ? 0 : (left < n ? (int)left : n);
+}
+
+// stream entry, slot form: row t < ran(u) of slot u is absolute sample s = slots[u].t + t, read from the audio ring's
+// column s mod ring_len; x[s - 1] from the ring too (0 at s = 0).  The arithmetic is the clock form's.
+template <typename T>
+__global__ __launch_bounds__(256) void recog_stream_in_slots_kernel(const float* __restrict__ ring, int ring_len,
+                                                                    const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, T* __restrict__ out,
+                                                                    int64_t out_clip_rows, int hist, int capacity, int n,
+                                                                    int R, const SrwnSynthSlot* __restrict__ slots) {
+  const int lpr = R / 8;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = idx / lpr;
+  const int sub = (int)(idx % lpr);
+  if (row >= (int64_t)capacity * n) return;
+  const int b = (int)(row / n);
+  const int t = (int)(row - (int64_t)b * n);
+  const SrwnSynthSlot sl = slots[b];
+  if (sl.t < 0 || t >= slot_ran(sl, n)) return;
+  const float* xb = ring + (int64_t)b * ring_len;
+  const long long s = sl.t + t;
+  const int c1 = (int)(s % ring_len);
+  const int c0 = c1 > 0 ? c1 - 1 : ring_len - 1;
+  const float x0 = s >= 1 ? xb[c0] : 0.0f;
+  const float x1 = xb[c1];
+  T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = bias[8 * sub + j];
+    v[j] = fmaf(x0, w[8 * sub + j], v[j]);
+    v[j] = fmaf(x1, w[R + 8 * sub + j], v[j]);
+  }
+  store4(d, v[0], v[1], v[2], v[3]);
+  store4(d + 4, v[4], v[5], v[6], v[7]);
+}
+
 // The sum of a tile's 32 rows in the order both forms of the hop sum use: neighbours first, then pairs of pairs ...
 // (what an xor butterfly over the 32 lanes of a half wave leaves in every lane).
 __device__ __forceinline__ float half_wave_sum(float v) {
@@ -78,13 +130,14 @@ __device__ __forceinline__ float half_wave_sum(float v) {
 // (accumulators start at the bias, k-steps in order).
 // LDS: xch = 32 x (S + 16 / sizeof(T)) x sizeof(T) bytes -- 33 280 for S = 256 in fp32, 16 896 in bf16.
 // ------------------------------------------------------------------------------------------
-template <typename T, int R, int S>
+// SLOTS: `clock` is the pool's table; the workgroup of (slot u, hop i) works only when (i + 1) * hop <= ran(u).
+template <typename T, int R, int S, bool SLOTS = false>
 __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
                                                                   int64_t z_clip_rows, int L, const T* __restrict__ wskip,
                                                                   const float* __restrict__ bs_sum,
                                                                   const T* __restrict__ w1, const float* __restrict__ b1,
                                                                   float* __restrict__ ring, int ring_rows,
-                                                                  const long long* __restrict__ clock, int k, int hop) {
+                                                                  typename When<SLOTS>::type clock, int k, int hop) {
   constexpr int MTW = S / 128;                // 32-channel output tiles per wave
   constexpr int KSL = R / 16;                 // k-steps per layer
   constexpr int KS1 = S / 16;
@@ -93,6 +146,12 @@ __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __rest
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int col = lane & 31, half = lane >> 5;
   const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
+  long long j0_ = 0;
+  if constexpr (SLOTS) {      // (workgroup-uniform, before the first barrier)
+    const SrwnSynthSlot sl = clock[b];
+    if (sl.t < 0 || (i + 1) * hop > slot_ran(sl, k * hop)) return;
+    j0_ = sl.t / hop;
+  }
   const int ks_skip = L * KSL;
   const Frag<T>* ws = reinterpret_cast<const Frag<T>*>(wskip) + (size_t)(wave * MTW) * ks_skip * 64 + lane;
   const Frag<T>* wh = reinterpret_cast<const Frag<T>*>(w1) + (size_t)(wave * MTW) * KS1 * 64 + lane;
@@ -154,7 +213,9 @@ __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __rest
         hsum[mt][q] += half_wave_sum(col < valid ? r1 : 0.0f);
       }
   }
-  const long long j = *clock / hop + i;
+  long long j_;
+  if constexpr (SLOTS) j_ = j0_ + i; else j_ = *clock / hop + i;
+  const long long j = j_;
   float* dst = ring + ((int64_t)b * ring_rows + (int64_t)(j % ring_rows)) * S;
   if (col == 0) {
 #pragma unroll
@@ -169,14 +230,20 @@ __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __rest
 // 2 channels): lane (col, half) reads row t0 + col of channel 2 * w + half, tiles in time order, the tile's rows summed as
 // the head kernel sums them.
 // ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool SLOTS = false>
 __global__ __launch_bounds__(256) void hop_sum_kernel(const T* __restrict__ r1, int64_t r1_clip_rows,
                                                       float* __restrict__ ring, int ring_rows,
-                                                      const long long* __restrict__ clock, int k, int hop, int S) {
+                                                      typename When<SLOTS>::type clock, int k, int hop, int S) {
   const int lane = threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int col = lane & 31, half = lane >> 5;
   const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
-  const long long j = *clock / hop + i;
+  long long j_;
+  if constexpr (SLOTS) {
+    const SrwnSynthSlot sl = clock[b];
+    if (sl.t < 0 || (i + 1) * hop > slot_ran(sl, k * hop)) return;
+    j_ = sl.t / hop + i;
+  } else j_ = *clock / hop + i;
+  const long long j = j_;
   float* dst = ring + ((int64_t)b * ring_rows + (int64_t)(j % ring_rows)) * S;
   const T* src = r1 + ((int64_t)b * r1_clip_rows + (int64_t)i * hop) * S;
   for (int s = 2 * wave + half; s < S; s += 8) {      // (both halves of a wave run the same number of rounds: S is even)
@@ -195,18 +262,27 @@ __global__ __launch_bounds__(256) void hop_sum_kernel(const T* __restrict__ r1, 
 // zeros where no window has filled yet (j < nW - 1).  With `logits`, also mean @ w2 + b2 in srwn_pooled_head's arithmetic.
 // One workgroup per row.
 // ------------------------------------------------------------------------------------------
+// SLOTS: j from the slot's own time; the row is zero too where the hop lies beyond ran(u) (an idle slot's rows).
+template <bool SLOTS = false>
 __global__ __launch_bounds__(256) void window_mean_kernel(const float* __restrict__ ring, int ring_rows,
-                                                          float* __restrict__ mean, const long long* __restrict__ clock,
+                                                          float* __restrict__ mean, typename When<SLOTS>::type clock,
                                                           int k, int hop, int nW, float window, int S,
                                                           const float* __restrict__ w2, const float* __restrict__ b2,
                                                           float* __restrict__ logits, int C, int ldw) {
   __shared__ float m[256];
   const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
-  const long long j = *clock / hop + i;
+  long long j_;
+  bool due = true;
+  if constexpr (SLOTS) {
+    const SrwnSynthSlot sl = clock[b];
+    due = sl.t >= 0 && (i + 1) * hop <= slot_ran(sl, k * hop);
+    j_ = due ? sl.t / hop + i : 0;
+  } else j_ = *clock / hop + i;
+  const long long j = j_;
   const float* rb = ring + (int64_t)b * ring_rows * S;
   for (int s = threadIdx.x; s < S; s += 256) {
     float acc = 0.0f;
-    if (j >= nW - 1)
+    if (due && j >= nW - 1)
       for (int w = 0; w < nW; ++w) acc += rb[(int64_t)((j - nW + 1 + w) % ring_rows) * S + s];
     acc = acc / window;
     m[s] = acc;
@@ -229,12 +305,18 @@ __global__ __launch_bounds__(256) void window_mean_kernel(const float* __restric
 // ------------------------------------------------------------------------------------------
 struct RollEntry { void* buf; long long clip_rows; long long hist; };      // int64 triples, as the host's table holds them
 
-template <typename T, int R>
+// SLOTS: `clock` is the pool's table, the grid has no last block, and slot b rolls by its own ran(b) rows (none: no roll).
+template <typename T, int R, bool SLOTS = false>
 __global__ __launch_bounds__(256) void recog_roll_kernel(const RollEntry* __restrict__ roll, int nroll,
                                                          const float* __restrict__ x, int64_t x_stride,
-                                                         float* __restrict__ carry, long long* __restrict__ clock, int B,
-                                                         int n) {
-  if ((int)blockIdx.x == nroll * B) {
+                                                         float* __restrict__ carry,
+                                                         typename std::conditional<SLOTS, const SrwnSynthSlot*, long long*>::type clock,
+                                                         int B, int n) {
+  if constexpr (SLOTS) {      // (workgroup-uniform, before the first barrier)
+    const SrwnSynthSlot sl = clock[(int)blockIdx.x % B];
+    n = sl.t < 0 ? 0 : slot_ran(sl, n);
+    if (n <= 0) return;
+  } else if ((int)blockIdx.x == nroll * B) {
     for (int b = threadIdx.x; b < B; b += 256) carry[b] = x[(int64_t)b * x_stride + n - 1];
     if (threadIdx.x == 0) *clock = *clock + n;
     return;
@@ -361,7 +443,7 @@ extern "C" int srwn_window_mean(const float* ring, int32_t ring_rows, float* mea
     return set_error(SRWN_E_SHAPE, "window_mean: a ring of %d rows for %d window rows + %d hops per launch - 1", ring_rows, nW, k);
   if (logits && (C < 1 || ldw < C)) return set_error(SRWN_E_SHAPE, "window_mean: C=%d ldw=%d", C, ldw);
   if ((int64_t)B * k > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "window_mean: too many rows");
-  hipLaunchKernelGGL(window_mean_kernel, dim3((unsigned)(B * k)), dim3(256), 0, (hipStream_t)stream, ring, ring_rows, mean,
+  hipLaunchKernelGGL(window_mean_kernel<false>, dim3((unsigned)(B * k)), dim3(256), 0, (hipStream_t)stream, ring, ring_rows, mean,
                      reinterpret_cast<const long long*>(clock), k, hop, nW, (float)window, S, w2, b2, logits, C, ldw);
   return check_launch("window_mean");
 }
@@ -385,4 +467,118 @@ extern "C" int srwn_recog_roll(const int64_t* roll_table, int32_t nroll, const f
   else return set_error(SRWN_E_DTYPE, "recog_roll: dtype %d", dtype);
 #undef SRWN_RR
   return check_launch("recog_roll");
+}
+
+// ------------------------------------------------------------------------------------------
+// The slot forms (classifier pools, srwn.h): the launches above on the pool's table.
+// ------------------------------------------------------------------------------------------
+extern "C" int srwn_recog_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w,
+                                          const float* init_b, void* out, int64_t out_clip_rows, int32_t out_hist,
+                                          int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
+                                          const SrwnSynthSlot* slots, void* stream) {
+  if (!audio_ring || !init_w || !init_b || !out || !slots) return set_error(SRWN_E_NULL, "recog_stream_in_slots: null pointer");
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_stream_in_slots: dilation_channels %d (built: 32, 64)", R);
+  if (capacity < 1 || max_chunk < 1 || out_hist < 0)
+    return set_error(SRWN_E_SHAPE, "recog_stream_in_slots: capacity=%d max_chunk=%d out_hist=%d", capacity, max_chunk, out_hist);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_stream_in_slots: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
+  if ((int64_t)ring_len < (int64_t)max_chunk + 1 || out_clip_rows < (int64_t)out_hist + max_chunk)
+    return set_error(SRWN_E_SHAPE, "recog_stream_in_slots: an audio ring of %d samples for max_chunk + 1 = %lld, %lld buffer "
+                     "rows per slot for %d + %d", ring_len, (long long)max_chunk + 1, (long long)out_clip_rows, out_hist, max_chunk);
+  const int64_t threads = (int64_t)capacity * n * (R / 8);
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16)
+    hipLaunchKernelGGL(recog_stream_in_slots_kernel<bf16_t>, grid, block, 0, st, audio_ring, ring_len, init_w, init_b,
+                       (bf16_t*)out, out_clip_rows, out_hist, capacity, n, R, slots);
+  else if (dtype == SRWN_F32)
+    hipLaunchKernelGGL(recog_stream_in_slots_kernel<float>, grid, block, 0, st, audio_ring, ring_len, init_w, init_b,
+                       (float*)out, out_clip_rows, out_hist, capacity, n, R, slots);
+  else
+    return set_error(SRWN_E_DTYPE, "recog_stream_in_slots: dtype %d", dtype);
+  return check_launch("recog_stream_in_slots");
+}
+
+extern "C" int srwn_pooled_stream_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                             const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                             float* ring, int32_t ring_rows, const SrwnSynthSlot* slots, int32_t capacity,
+                                             int32_t k, int32_t hop, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype,
+                                             void* stream) {
+  if (!z || !wskip || !bs_sum || !w1 || !b1 || !ring || !slots) return set_error(SRWN_E_NULL, "pooled_stream_head_slots: null pointer");
+  if ((R != 32 && R != 64) || (S != 128 && S != 256))
+    return set_error(SRWN_E_UNSUPPORTED, "pooled_stream_head_slots: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", R, S);
+  if (const int rc = hop_args("pooled_stream_head_slots", ring_rows, capacity, k, hop, max_chunk, z_clip_rows)) return rc;
+  if (nlayers < 1 || z_layer_stride < (int64_t)capacity * z_clip_rows * R)
+    return set_error(SRWN_E_SHAPE, "pooled_stream_head_slots: %d layers at a stride of %lld", nlayers, (long long)z_layer_stride);
+  dim3 grid((unsigned)(capacity * k)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define SRWN_PSH(TT, RR, SS)                                                                                            \
+  hipLaunchKernelGGL((pooled_stream_head_kernel<TT, RR, SS, true>), grid, block, 0, st, (const TT*)z, z_layer_stride,   \
+                     z_clip_rows, nlayers, (const TT*)wskip, bs_sum, (const TT*)w1, b1, ring, ring_rows, slots, k, hop)
+#define SRWN_PSH_T(TT)                                       \
+  {                                                          \
+    if (R == 32 && S == 128) SRWN_PSH(TT, 32, 128);          \
+    else if (R == 32) SRWN_PSH(TT, 32, 256);                 \
+    else if (S == 128) SRWN_PSH(TT, 64, 128);                \
+    else SRWN_PSH(TT, 64, 256);                              \
+  }
+  if (dtype == SRWN_BF16) SRWN_PSH_T(bf16_t)
+  else if (dtype == SRWN_F32) SRWN_PSH_T(float)
+  else return set_error(SRWN_E_DTYPE, "pooled_stream_head_slots: dtype %d", dtype);
+#undef SRWN_PSH_T
+#undef SRWN_PSH
+  return check_launch("pooled_stream_head_slots");
+}
+
+extern "C" int srwn_hop_sum_slots(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows,
+                                  const SrwnSynthSlot* slots, int32_t capacity, int32_t k, int32_t hop, int32_t max_chunk,
+                                  int32_t S, int32_t dtype, void* stream) {
+  if (!r1 || !ring || !slots) return set_error(SRWN_E_NULL, "hop_sum_slots: null pointer");
+  if (const int rc = hop_args("hop_sum_slots", ring_rows, capacity, k, hop, max_chunk, r1_clip_rows)) return rc;
+  if (S < 2 || S % 2) return set_error(SRWN_E_SHAPE, "hop_sum_slots: S=%d", S);
+  dim3 grid((unsigned)(capacity * k)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16)
+    hipLaunchKernelGGL((hop_sum_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)r1, r1_clip_rows, ring, ring_rows, slots, k, hop, S);
+  else if (dtype == SRWN_F32)
+    hipLaunchKernelGGL((hop_sum_kernel<float, true>), grid, block, 0, st, (const float*)r1, r1_clip_rows, ring, ring_rows, slots, k, hop, S);
+  else
+    return set_error(SRWN_E_DTYPE, "hop_sum_slots: dtype %d", dtype);
+  return check_launch("hop_sum_slots");
+}
+
+extern "C" int srwn_window_mean_slots(const float* ring, int32_t ring_rows, float* mean, const SrwnSynthSlot* slots,
+                                      int32_t capacity, int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2,
+                                      const float* b2, float* logits, int32_t C, int32_t ldw, void* stream) {
+  if (!ring || !mean || !slots || (logits && (!w2 || !b2))) return set_error(SRWN_E_NULL, "window_mean_slots: null pointer");
+  if (capacity < 1 || k < 1 || hop < 1 || window < hop || window % hop || S < 1 || S > 256)
+    return set_error(SRWN_E_SHAPE, "window_mean_slots: capacity=%d hops=%d hop=%d window=%d S=%d (window a multiple of hop, S <= 256)",
+                     capacity, k, hop, window, S);
+  const int nW = window / hop;
+  if (ring_rows < nW + k - 1)
+    return set_error(SRWN_E_SHAPE, "window_mean_slots: a ring of %d rows for %d window rows + %d hops per launch - 1", ring_rows, nW, k);
+  if (logits && (C < 1 || ldw < C)) return set_error(SRWN_E_SHAPE, "window_mean_slots: C=%d ldw=%d", C, ldw);
+  if ((int64_t)capacity * k > 0x7fffffffLL || (int64_t)k * hop > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "window_mean_slots: too many rows");
+  hipLaunchKernelGGL(window_mean_kernel<true>, dim3((unsigned)(capacity * k)), dim3(256), 0, (hipStream_t)stream, ring,
+                     ring_rows, mean, slots, k, hop, nW, (float)window, S, w2, b2, logits, C, ldw);
+  return check_launch("window_mean_slots");
+}
+
+extern "C" int srwn_recog_roll_slots(const int64_t* roll_table, int32_t nroll, const SrwnSynthSlot* slots, int32_t capacity,
+                                     int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream) {
+  if (!slots || (nroll > 0 && !roll_table)) return set_error(SRWN_E_NULL, "recog_roll_slots: null pointer");
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_roll_slots: dilation_channels %d (built: 32, 64)", R);
+  if (capacity < 1 || nroll < 0 || max_chunk < 1)
+    return set_error(SRWN_E_SHAPE, "recog_roll_slots: capacity=%d boundaries=%d max_chunk=%d", capacity, nroll, max_chunk);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_roll_slots: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
+  if (nroll == 0) return 0;
+  dim3 grid((unsigned)((int64_t)nroll * capacity)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const RollEntry* rt = reinterpret_cast<const RollEntry*>(roll_table);
+#define SRWN_RR(TT, RR) \
+  hipLaunchKernelGGL((recog_roll_kernel<TT, RR, true>), grid, block, 0, st, rt, nroll, (const float*)nullptr, (int64_t)0, (float*)nullptr, slots, capacity, n)
+  if (dtype == SRWN_BF16) { if (R == 32) SRWN_RR(bf16_t, 32); else SRWN_RR(bf16_t, 64); }
+  else if (dtype == SRWN_F32) { if (R == 32) SRWN_RR(float, 32); else SRWN_RR(float, 64); }
+  else return set_error(SRWN_E_DTYPE, "recog_roll_slots: dtype %d", dtype);
+#undef SRWN_RR
+  return check_launch("recog_roll_slots");
 }

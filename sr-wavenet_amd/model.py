@@ -276,6 +276,12 @@ class StreamingClassifier(object):
     def stream(self, batch_size=1):
         return ClassifierStream(self, self._eng.start(batch_size))
 
+    def pool(self, audio_ring=None):
+        """A ``ClassifierPool``: this classifier's ``max_batch`` rows as slots that streams join and leave, each pushing
+        audio of any length at a clock of its own (``recognizer.ClassifierPool``).  audio_ring: samples a slot can hold
+        (default 2 * max_hops * hop + 1).  Ends the current ``ClassifierStream``; ``stream`` and ``classify`` end the pool."""
+        return ClassifierPool(self._eng.pool(audio_ring))
+
 
 class ClassifierStream(object):
     """NumPy face of one running batch of classifier streams (``StreamingClassifier.stream``).  ``t``: samples received
@@ -1253,6 +1259,35 @@ class AudioEncoderPool(_PoolFace):
 
     def step(self, limit=None):
         return {u: f.cpu().numpy() for u, f in self._pool.step(limit).items()}
+
+
+class ClassifierPool(_PoolFace):
+    """NumPy face of a classifier pool (``StreamingClassifier.pool``; recognizer.ClassifierPool).  ``join`` returns slots,
+    ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``step()`` returns ``{slot: probabilities [e, C]}``
+    for every slot whose stream completed window positions (with return_logits a second dict with the pooled logits).  A
+    stream's emissions put together are ``StreamingClassifier.classify`` of its audio alone."""
+
+    def __init__(self, pool):
+        self._pool = pool
+
+    audio_ring = property(lambda self: self._pool.audio_ring)
+    received = property(lambda self: self._pool.received)
+    consumed = property(lambda self: self._pool.consumed)
+    emitted = property(lambda self: self._pool.emitted)
+
+    def audio_room(self, slot):
+        return self._pool.audio_room(int(slot))
+
+    def join(self, n=1, slots=None):
+        return self._pool.join(n, slots)
+
+    def push(self, slots, audio):
+        self._pool.push([int(slots)] if np.isscalar(slots) else slots, _audio_pieces(slots, audio))
+
+    def step(self, return_logits=False):
+        out = self._pool.step(return_logits)
+        host = lambda d: {u: f.cpu().numpy() for u, f in d.items()}
+        return (host(out[0]), host(out[1])) if return_logits else host(out)
 
 
 class ParallelWaveNet(object):

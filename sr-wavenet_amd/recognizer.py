@@ -15,11 +15,15 @@ Per step of k hops: the stream entry (input conv), one ``srwn_residual_group_fwd
 stream form of the group kernels that also stores every layer's z of the chunk's rows), ``srwn_pooled_stream_head`` (skip
 sum, head 1x1 and hop sums in one launch; ``SRWN_RECOG_FUSED=0``: the parity twin, two ``srwn_pw_linear`` calls into
 chunk-sized buffers and ``srwn_hop_sum``), ``srwn_window_mean``, ``srwn_pooled_head`` and the roll.
+
+``StreamClassifier.pool()`` turns the classifier's ``max_batch`` rows into SLOTS (``ClassifierPool``): streams join and
+leave, each pushes audio of any length at a clock of its own, and one step serves every slot that has a whole hop waiting
+with the same launches in their slot forms (srwn.h, srwn_version() 115), on a table the host writes before every step.
 """
 from __future__ import annotations
 
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -28,6 +32,7 @@ from . import kernels as K
 from . import packing as P
 from ._lib import call
 from .engine import Section, WaveNetEngine
+from .slots import SlotTable
 
 # What SRWN_RECOG_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
 RECOG_FUSED_DEFAULT = "1"
@@ -46,6 +51,23 @@ def emissions_due(t_before: int, t_after: int, hop: int, window: int) -> Tuple[i
     lo = max(t_before // hop, nW - 1)
     hi = t_after // hop
     return lo, max(0, hi - lo)
+
+
+def plan_pool_step(received, consumed, active, hop: int, max_hops: int) -> Tuple[int, np.ndarray]:
+    """One step of a classifier pool: (k, hops [capacity]).  hops[u] = min(max_hops, (received[u] - consumed[u]) // hop)
+    whole hops for an active slot and 0 for any other, k = hops.max() the hops of the step's launches (0: nothing to
+    launch).  Pure NumPy: the CPU tests hold it to brute force."""
+    received, consumed = np.asarray(received, np.int64), np.asarray(consumed, np.int64)
+    active = np.asarray(active, bool)
+    hop, max_hops = int(hop), int(max_hops)
+    if hop < 1 or max_hops < 1:
+        raise ValueError("plan_pool_step: hop=%d max_hops=%d" % (hop, max_hops))
+    if received.ndim != 1 or received.shape != consumed.shape or received.shape != active.shape:
+        raise ValueError("plan_pool_step: received, consumed and active are [capacity] each")
+    if np.any(active & ((consumed < 0) | (consumed > received))):
+        raise ValueError("plan_pool_step: a slot has consumed more than it received")
+    hops = np.where(active, np.minimum(max_hops, (received - consumed) // hop), 0).astype(np.int64)
+    return (int(hops.max()) if hops.size else 0), hops
 
 
 def check_hop_window(hop, window):
@@ -221,6 +243,7 @@ class StreamClassifier:
         self._seen: set = set()
         self._serial = 0
         self._state: Optional[RecogState] = None
+        self._pool: Optional["ClassifierPool"] = None
         self.launches_per_step = 4 + len(self.groups) + (1 if self.fused else 3)
 
     def buffer_bytes(self) -> Dict[str, int]:
@@ -242,9 +265,26 @@ class StreamClassifier:
         for b in self.bufs:
             b.zero_()
         self.carry.zero_(); self.clock.zero_(); self.ring.zero_()
+        self._close_pool()
         self._serial += 1
         self._state = RecogState(B, self._serial, torch.zeros((B, 0), dtype=torch.float32, device=self.dev))
         return self._state
+
+    def _close_pool(self):
+        if self._pool is not None:
+            self._pool._open = False
+            self._pool = None
+
+    def pool(self, audio_ring: Optional[int] = None) -> "ClassifierPool":
+        """A ``ClassifierPool`` on this classifier's buffers: its ``max_batch`` rows as slots, each a stream at a clock of
+        its own.  audio_ring: samples a slot's audio ring holds (default 2 * max_chunk + 1, at least max_chunk + 1).  The
+        current ``RecogState`` ends, and an earlier pool; ``start`` ends the pool."""
+        pool = ClassifierPool(self, audio_ring)
+        self._close_pool()
+        self._serial += 1
+        self._state = None
+        self._pool = pool
+        return pool
 
     def _check_state(self, state):
         if state is not self._state or state._serial != self._serial:
@@ -339,3 +379,205 @@ class StreamClassifier:
         hop + 1); a trailing part that does not fill a hop is not heard.  Starts a new state (the current one ends)."""
         x = self._check_audio(audio)
         return self.push(self.start(int(x.shape[0])), x, return_logits)
+
+
+class ClassifierPool(SlotTable):
+    """``StreamClassifier.pool()``: the classifier's ``max_batch`` rows as SLOTS, each holding a stream with its own
+    samples ``received``, samples ``consumed`` by the stack (a multiple of hop) and emissions ``emitted``.  Streams ``join``
+    free slots (history rows zeroed by srwn_flow_stream_reset_slots; the hop-sum ring needs no reset, srwn.h), ``push``
+    audio of any length whenever it arrives (one upload and one srwn_audio_ring_put however many slots are written: a
+    slot's audio lives in its row of a device ring, sample s in column s mod audio_ring), and ``step`` serves every slot
+    that has a whole hop waiting: per pass ``plan_pool_step``, the table [t = consumed, t_end = t + hops * hop] uploaded
+    whole, and the launches of one classifier step in their slot forms -- one hipGraph per k, captured at second use.  The
+    device never advances the table.  A stream's emissions put together equal ``StreamClassifier(max_batch=1).classify``
+    of its audio alone, bit for bit: in any slot, whenever it joined, however its audio was cut, whatever k the steps
+    had and whatever the other slots hold or held before."""
+
+    def __init__(self, owner: StreamClassifier, audio_ring: Optional[int] = None):
+        c = self.c = owner
+        self.capacity, self.hop, self.window, self.max_hops = c.max_batch, c.hop, c.window, c.max_hops
+        self.audio_ring = 2 * c.max_chunk + 1 if audio_ring is None else int(audio_ring)
+        if self.audio_ring < c.max_chunk + 1:
+            raise ValueError("pool: audio_ring %d holds less than max_chunk + 1 = %d samples (a whole step and the sample "
+                             "before it)" % (self.audio_ring, c.max_chunk + 1))
+        if self.capacity * self.audio_ring + 4 * self.capacity > 0x7fffffff:
+            raise ValueError("pool: %d slots of %d samples" % (self.capacity, self.audio_ring))
+        K._need_gpu()
+        cap, dev = self.capacity, c.dev
+        self._received = np.zeros(cap, np.int64)
+        self._consumed = np.zeros(cap, np.int64)
+        self._emitted = np.zeros(cap, np.int64)
+        self._active = np.zeros(cap, bool)
+        self.ring = torch.zeros((cap, self.audio_ring), dtype=torch.float32, device=dev)
+        # one upload per push: [streams | src_offset | first_col | counts] (n each) and the concatenated audio behind them
+        self.stage = torch.zeros(4 * cap + cap * self.audio_ring, dtype=torch.int32, device=dev)
+        self.table = torch.zeros((cap, 2), dtype=torch.int64, device=dev)      # SrwnSynthSlot [t, t_end] per slot
+        self._graphs: Dict[int, object] = {}
+        self._seen: set = set()
+        self._open = True
+        self.launches_per_step = c.launches_per_step      # the same launches in their slot forms (+ the table's upload)
+
+    def buffer_bytes(self) -> Dict[str, int]:
+        """The classifier's device bytes by buffer family with the pool's additions."""
+        nb = lambda ts: int(sum(t.numel() * t.element_size() for t in ts))
+        out = self.c.buffer_bytes()
+        out["pool audio ring"] = nb([self.ring])
+        out["pool stage + table"] = nb([self.stage, self.table])
+        return out
+
+    # ---- inspection
+    received = property(lambda self: self._received.copy(), doc="Samples pushed into each slot's stream so far.")
+    consumed = property(lambda self: self._consumed.copy(), doc="Samples each slot's stack has run (whole hops).")
+    emitted = property(lambda self: self._emitted.copy(), doc="Emissions each slot's stream has returned so far.")
+
+    def _check_open(self):
+        if not self._open:
+            raise ValueError("this pool is closed (the classifier started a batch or opened another pool)")
+
+    def audio_room(self, slot: int) -> int:
+        """Samples a slot can take now: audio_ring - 1 minus what waits for its hop (the - 1 keeps sample consumed - 1, the
+        input conv's tap before the next chunk, alive)."""
+        u, = self._slot_list(slot, "audio_room")
+        return int(self.audio_ring - 1 - (self._received[u] - self._consumed[u]))
+
+    # ---- streams come and go
+    def join(self, n: int = 1, slots=None) -> List[int]:
+        """n streams into free slots (the lowest ones, or `slots`); returns the slots.  A slot starts at sample 0 with
+        zeroed history rows."""
+        self._check_open()
+        slots = self._take_slots(int(n) if slots is None else None, slots)
+        c = self.c
+        ids = torch.tensor(slots, dtype=torch.int32, device=c.dev)
+        call("srwn_flow_stream_reset_slots", c.roll.data_ptr(), c.roll.shape[0], None, 0, 0, ids.data_ptr(), len(slots),
+             self.capacity, c.w.R, K.abi_dtype(c.dt), K._stream())
+        for u in slots:
+            self._received[u] = self._consumed[u] = self._emitted[u] = 0
+            self._active[u] = True
+        return list(slots)
+
+    def leave(self, slots) -> None:
+        """Ends the streams in `slots` where they are (a slot already free stays free) and frees their slots."""
+        self._check_open()
+        for u in self._slot_list(slots, "leave", distinct=True):
+            self._active[u] = False
+
+    def push(self, slots, audio) -> None:
+        """audio[i], 1-D of any length (0 too), behind what slots[i] has received.  Refuses (ValueError, nothing changed) a
+        slot that holds no stream, more than ``audio_room(slot)`` samples and audio that is not floating point.  One
+        host-to-device copy and one srwn_audio_ring_put, whatever the number of slots."""
+        self._check_open()
+        one = not np.ndim(slots)
+        slots = self._slot_list(slots, "push", distinct=True)
+        if one or isinstance(audio, (np.ndarray, torch.Tensor)):
+            audio = [audio]
+        audio = list(audio)
+        if len(audio) != len(slots):
+            raise ValueError("push: %d slots but %d pieces of audio" % (len(slots), len(audio)))
+        xs = []
+        for u, x in zip(slots, audio):
+            if isinstance(x, torch.Tensor):
+                if not x.is_floating_point():
+                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
+                x = x.detach().to("cpu", torch.float32).numpy()
+            else:
+                x = np.asarray(x)
+                if x.dtype.kind != "f":
+                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
+                x = x.astype(np.float32, copy=False)
+            if x.ndim != 1:
+                raise ValueError("push: the audio of a slot is 1-D [samples], got shape %s" % (x.shape,))
+            if not self._active[u]:
+                raise ValueError("push: slot %d holds no stream" % u)
+            if x.shape[0] > self.audio_room(u):
+                raise ValueError("push: %d samples for slot %d, but its ring of %d has room for %d (received %d, consumed "
+                                 "%d)" % (x.shape[0], u, self.audio_ring, self.audio_room(u), self._received[u],
+                                          self._consumed[u]))
+            xs.append(x)
+        pairs = [(u, x) for u, x in zip(slots, xs) if x.shape[0] > 0]
+        if not pairs:
+            return
+        n = len(pairs)
+        counts = np.asarray([x.shape[0] for _, x in pairs], np.int64)
+        us = np.asarray([u for u, _ in pairs], np.int64)
+        host = np.empty(4 * n + int(counts.sum()), np.int32)
+        host[0:n] = us
+        host[n:2 * n] = np.cumsum(counts) - counts
+        host[2 * n:3 * n] = self._received[us] % self.audio_ring
+        host[3 * n:4 * n] = counts
+        host[4 * n:].view(np.float32)[:] = np.concatenate([x for _, x in pairs])
+        self.stage[:host.shape[0]].copy_(torch.from_numpy(host))
+        sp = self.stage.data_ptr()
+        call("srwn_audio_ring_put", self.ring.data_ptr(), self.audio_ring, self.capacity, sp + 16 * n, sp, sp + 4 * n,
+             sp + 8 * n, sp + 12 * n, n, int(counts.max()), K._stream())
+        self._received[us] += counts
+
+    # ---- one step: every whole hop that waits
+    def _launch_step(self, k: int):
+        """The launches of a step of k hops on the table in ``self.table``: ``StreamClassifier._launch_step`` in slot forms."""
+        import ctypes as C_
+        c, w = self.c, self.c.w
+        st, dt, R, S, C, L = K._stream(), K.abi_dtype(c.dt), w.R, w.S, c.max_chunk, w.L
+        n, tb, v, cap = k * c.hop, self.table.data_ptr(), w.view, self.capacity
+        call("srwn_recog_stream_in_slots", self.ring.data_ptr(), self.audio_ring, v("init_w").data_ptr(),
+             v("init_b").data_ptr(), c.bufs[0].data_ptr(), c.hist[0] + C, c.hist[0], cap, n, C, R, dt, tb, st)
+        G = len(c.groups)
+        zstride = cap * C * R
+        for g, (l0, l1) in enumerate(c.groups):
+            last = g + 1 == G
+            out = c.top if last else c.bufs[g + 1]
+            nl = l1 - l0
+            call("srwn_residual_group_fwd_stream_z_slots", c.bufs[g].data_ptr(), c.hist[g] + C, out.data_ptr(),
+                 C if last else c.hist[g + 1] + C, 0 if last else c.hist[g + 1], c.zs[l0].data_ptr(), zstride,
+                 K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
+                 K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
+                 K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
+                 K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
+                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, cap, n, C, R, w.Kw, dt, tb, st)
+        if c.fused:
+            call("srwn_pooled_stream_head_slots", c.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
+                 w.wptr(w.o_w1), v("head_b1").data_ptr(), c.ring.data_ptr(), c.ring_rows, tb, cap, k, c.hop, C, R, S, dt, st)
+        else:      # the twin's two products run over every slot's buffer rows up to the last slot's chunk: the rows of idle
+            # slots and those beyond a slot's ran ride along, and srwn_hop_sum_slots never reads them
+            rows = (cap - 1) * C + n
+            K.pw_linear(c.zs.data_ptr(), R, zstride, R, L * R, w.wptr(w.o_skip), w.bs_sum, c.r0[:rows], S, S, rows,
+                        pro=K.PRO_GATE, epi=K.EPI_RELU)
+            K.pw_linear(c.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), c.r1[:rows], S, S, rows, epi=K.EPI_RELU)
+            call("srwn_hop_sum_slots", c.r1.data_ptr(), C, c.ring.data_ptr(), c.ring_rows, tb, cap, k, c.hop, C, S, dt, st)
+        call("srwn_window_mean_slots", c.ring.data_ptr(), c.ring_rows, c.mean.data_ptr(), tb, cap, k, c.hop, c.window, S,
+             v("head_w2").data_ptr(), v("head_b2").data_ptr(), c.logits.data_ptr(), w.C, w.Cp, st)
+        call("srwn_pooled_head", c.mean.data_ptr(), v("head_w2").data_ptr(), v("head_b2").data_ptr(), None,
+             c.probs.data_ptr(), None, None, None, None, cap * k, S, w.C, w.Cp, st)
+        call("srwn_recog_roll_slots", c.roll.data_ptr(), G, tb, cap, n, C, R, dt, st)
+
+    def step(self, return_logits: bool = False):
+        """Runs while any active slot has a whole hop waiting -> {slot: probabilities [e, C] fp32 on the device} for the
+        slots whose streams completed e > 0 window positions (``emissions_due`` on the slot's own clock); with
+        return_logits (probabilities, logits): a second dict with the pooled logits [e, C] of the same slots.  With nothing
+        due nothing is launched."""
+        self._check_open()
+        c, cap, hop = self.c, self.capacity, self.hop
+        pp, pl = {}, {}
+        while True:
+            k, hops = plan_pool_step(self._received, self._consumed, self._active, hop, self.max_hops)
+            if k == 0:
+                break
+            Cc = c.w.C
+            self.table.copy_(torch.from_numpy(np.stack([self._consumed, self._consumed + hops * hop], 1)))
+            K.run_cached_graph(self._graphs, self._seen, k, c.use_graphs, lambda: self._launch_step(k))
+            probs = logits = None
+            for u in np.flatnonzero(hops):
+                t0, h = int(self._consumed[u]), int(hops[u])
+                first, count = emissions_due(t0, t0 + h * hop, hop, self.window)
+                if count:
+                    if probs is None:      # one copy per pass: the next pass writes the same buffers
+                        probs = c.probs[:cap * k].view(cap, k, Cc).clone()
+                        logits = c.logits[:cap * k].view(cap, k, Cc).clone() if return_logits else None
+                    skip = first - t0 // hop      # hops of this step before the stream's first full window
+                    pp.setdefault(int(u), []).append(probs[u, skip:h])
+                    if return_logits:
+                        pl.setdefault(int(u), []).append(logits[u, skip:h])
+                    self._emitted[u] += count
+            self._consumed += hops * hop
+        cat = lambda p: p[0] if len(p) == 1 else torch.cat(p, dim=0)
+        out = {u: cat(p) for u, p in pp.items()}
+        return (out, {u: cat(p) for u, p in pl.items()}) if return_logits else out
