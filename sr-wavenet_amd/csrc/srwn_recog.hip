@@ -17,15 +17,19 @@
 // batch size and in any row of the batch.
 //
 // The slot forms (classifier pools; srwn.h, srwn_version() 115) are the same kernels on the pool's table of SrwnSynthSlot
-// instead of the clock: slot u is a stream at its own absolute time slots[u].t (a multiple of hop) with ran = clamp(t_end -
-// t, 0, n) rows in this chunk (a multiple of hop too).  The host writes the whole table before every step and no launch
-// modifies it.  What the clock forms take from *clock they take from the slot; a workgroup or thread whose hop or row lies
-// beyond ran returns before it reads or writes anything.  The stream entry reads the audio -- and the sample before the
-// chunk -- from the pool's audio ring, so the slot forms keep no carry.
+// instead of the clock: slot u is a stream at its own absolute time slots[u].t (a multiple of hop) with ran =
+// slot_rows(slots[u], n) rows in this chunk (a multiple of hop too).  The host writes the whole table before every step and
+// no launch modifies it.  What the clock forms take from *clock they take from the slot; a workgroup or thread whose hop or
+// row lies beyond ran returns before it reads or writes anything.  The stream entry reads the audio -- and the sample before
+// the chunk -- from the pool's audio ring, so the slot forms keep no carry.
+// Each pair of entry points is ONE kernel template with a SLOTS flag and ONE host body (`*_impl<SLOTS>`: the checks, the
+// dtype / R / S dispatch and the launch, written once); the ten extern "C" functions at the end only name themselves and
+// pass their arguments on.  ClockArg, slot_rows and RollEntry are srwn_slots.h's, shared with srwn_stream.hip.
 #include <cmath>
 #include <type_traits>
 #include "srwn_common.h"
 #include "srwn_host.h"
+#include "srwn_slots.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -35,14 +39,19 @@ namespace {
 // ------------------------------------------------------------------------------------------
 // stream entry: 8 channels per thread, one row per group of R/8 lanes
 //   v = b; v = fma(x[t-1], w[0], v); v = fma(x[t], w[1], v); round to T          (srwn_causal_conv1d_fwd, shift 0)
-// x[-1] of the chunk is the carry (zero at the stream's start: the conv's zero padding).
+// Clock form: x [B][x_stride] is the chunk's audio, x[-1] of the chunk the carry (zero at the stream's start: the conv's
+// zero padding).  SLOTS: x is the pool's audio ring of x_stride columns per slot; row t < ran(b) of slot b is absolute
+// sample s = slots[b].t + t in column s mod x_stride, x[s - 1] from the ring too (0 at s = 0), no carry.  Only the fetch
+// of the two samples differs.
 // ------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool SLOTS = false>
 __global__ __launch_bounds__(256) void recog_stream_in_kernel(const float* __restrict__ x, int64_t x_stride,
                                                               const float* __restrict__ carry,
                                                               const float* __restrict__ w, const float* __restrict__ bias,
                                                               T* __restrict__ out, int64_t out_clip_rows, int hist, int B,
-                                                              int n, int R) {
+                                                              int n, int R, const SrwnSynthSlot* __restrict__ slots) {
+  // (one argument list for both forms: the clock form is launched with slots = null, the slot form with carry = null,
+  // and neither instantiation reads the other's)
   const int lpr = R / 8;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = idx / lpr;
@@ -50,53 +59,22 @@ __global__ __launch_bounds__(256) void recog_stream_in_kernel(const float* __res
   if (row >= (int64_t)B * n) return;
   const int b = (int)(row / n);
   const int t = (int)(row - (int64_t)b * n);
-  const float* xb = x + (int64_t)b * x_stride;
-  const float x0 = t >= 1 ? xb[t - 1] : carry[b];
-  const float x1 = xb[t];
-  T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    v[j] = bias[8 * sub + j];
-    v[j] = fmaf(x0, w[8 * sub + j], v[j]);
-    v[j] = fmaf(x1, w[R + 8 * sub + j], v[j]);
+  float x0, x1;
+  if constexpr (SLOTS) {
+    const SrwnSynthSlot sl = slots[b];
+    if (sl.t < 0 || t >= slot_rows(sl, n)) return;
+    const int ring_len = (int)x_stride;
+    const float* xb = x + (int64_t)b * ring_len;
+    const long long s = sl.t + t;
+    const int c1 = (int)(s % ring_len);
+    const int c0 = c1 > 0 ? c1 - 1 : ring_len - 1;
+    x0 = s >= 1 ? xb[c0] : 0.0f;
+    x1 = xb[c1];
+  } else {
+    const float* xb = x + (int64_t)b * x_stride;
+    x0 = t >= 1 ? xb[t - 1] : carry[b];
+    x1 = xb[t];
   }
-  store4(d, v[0], v[1], v[2], v[3]);
-  store4(d + 4, v[4], v[5], v[6], v[7]);
-}
-
-// the clock or the table: what a kernel's SLOTS instantiation takes in the place of the clock
-template <bool SLOTS> struct When { typedef typename std::conditional<SLOTS, const SrwnSynthSlot*, const long long*>::type type; };
-
-// rows slot `sl` has in a chunk of n
-__device__ __forceinline__ int slot_ran(const SrwnSynthSlot& sl, int n) {
-  const long long left = sl.t_end - sl.t;
-  return left <= 0 ? 0 : (left < n ? (int)left : n);
-}
-
-// stream entry, slot form: row t < ran(u) of slot u is absolute sample s = slots[u].t + t, read from the audio ring's
-// column s mod ring_len; x[s - 1] from the ring too (0 at s = 0).  The arithmetic is the clock form's.
-template <typename T>
-__global__ __launch_bounds__(256) void recog_stream_in_slots_kernel(const float* __restrict__ ring, int ring_len,
-                                                                    const float* __restrict__ w,
-                                                                    const float* __restrict__ bias, T* __restrict__ out,
-                                                                    int64_t out_clip_rows, int hist, int capacity, int n,
-                                                                    int R, const SrwnSynthSlot* __restrict__ slots) {
-  const int lpr = R / 8;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t row = idx / lpr;
-  const int sub = (int)(idx % lpr);
-  if (row >= (int64_t)capacity * n) return;
-  const int b = (int)(row / n);
-  const int t = (int)(row - (int64_t)b * n);
-  const SrwnSynthSlot sl = slots[b];
-  if (sl.t < 0 || t >= slot_ran(sl, n)) return;
-  const float* xb = ring + (int64_t)b * ring_len;
-  const long long s = sl.t + t;
-  const int c1 = (int)(s % ring_len);
-  const int c0 = c1 > 0 ? c1 - 1 : ring_len - 1;
-  const float x0 = s >= 1 ? xb[c0] : 0.0f;
-  const float x1 = xb[c1];
   T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
   float v[8];
 #pragma unroll
@@ -137,7 +115,7 @@ __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __rest
                                                                   const float* __restrict__ bs_sum,
                                                                   const T* __restrict__ w1, const float* __restrict__ b1,
                                                                   float* __restrict__ ring, int ring_rows,
-                                                                  typename When<SLOTS>::type clock, int k, int hop) {
+                                                                  typename ClockArg<SLOTS>::in clock, int k, int hop) {
   constexpr int MTW = S / 128;                // 32-channel output tiles per wave
   constexpr int KSL = R / 16;                 // k-steps per layer
   constexpr int KS1 = S / 16;
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __rest
   long long j0_ = 0;
   if constexpr (SLOTS) {      // (workgroup-uniform, before the first barrier)
     const SrwnSynthSlot sl = clock[b];
-    if (sl.t < 0 || (i + 1) * hop > slot_ran(sl, k * hop)) return;
+    if (sl.t < 0 || (i + 1) * hop > slot_rows(sl, k * hop)) return;
     j0_ = sl.t / hop;
   }
   const int ks_skip = L * KSL;
@@ -233,14 +211,14 @@ __global__ __launch_bounds__(256) void pooled_stream_head_kernel(const T* __rest
 template <typename T, bool SLOTS = false>
 __global__ __launch_bounds__(256) void hop_sum_kernel(const T* __restrict__ r1, int64_t r1_clip_rows,
                                                       float* __restrict__ ring, int ring_rows,
-                                                      typename When<SLOTS>::type clock, int k, int hop, int S) {
+                                                      typename ClockArg<SLOTS>::in clock, int k, int hop, int S) {
   const int lane = threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int col = lane & 31, half = lane >> 5;
   const int b = (int)blockIdx.x / k, i = (int)blockIdx.x % k;
   long long j_;
   if constexpr (SLOTS) {
     const SrwnSynthSlot sl = clock[b];
-    if (sl.t < 0 || (i + 1) * hop > slot_ran(sl, k * hop)) return;
+    if (sl.t < 0 || (i + 1) * hop > slot_rows(sl, k * hop)) return;
     j_ = sl.t / hop + i;
   } else j_ = *clock / hop + i;
   const long long j = j_;
@@ -265,7 +243,7 @@ __global__ __launch_bounds__(256) void hop_sum_kernel(const T* __restrict__ r1, 
 // SLOTS: j from the slot's own time; the row is zero too where the hop lies beyond ran(u) (an idle slot's rows).
 template <bool SLOTS = false>
 __global__ __launch_bounds__(256) void window_mean_kernel(const float* __restrict__ ring, int ring_rows,
-                                                          float* __restrict__ mean, typename When<SLOTS>::type clock,
+                                                          float* __restrict__ mean, typename ClockArg<SLOTS>::in clock,
                                                           int k, int hop, int nW, float window, int S,
                                                           const float* __restrict__ w2, const float* __restrict__ b2,
                                                           float* __restrict__ logits, int C, int ldw) {
@@ -275,7 +253,7 @@ __global__ __launch_bounds__(256) void window_mean_kernel(const float* __restric
   bool due = true;
   if constexpr (SLOTS) {
     const SrwnSynthSlot sl = clock[b];
-    due = sl.t >= 0 && (i + 1) * hop <= slot_ran(sl, k * hop);
+    due = sl.t >= 0 && (i + 1) * hop <= slot_rows(sl, k * hop);
     j_ = due ? sl.t / hop + i : 0;
   } else j_ = *clock / hop + i;
   const long long j = j_;
@@ -303,18 +281,16 @@ __global__ __launch_bounds__(256) void window_mean_kernel(const float* __restric
 // between), and a row written in one step lies in front of every row a later step reads (srwn_flow_stream_out's roll).
 // The last block: carry[b] = x[b][n - 1] and *clock += n (nothing in this launch reads either).
 // ------------------------------------------------------------------------------------------
-struct RollEntry { void* buf; long long clip_rows; long long hist; };      // int64 triples, as the host's table holds them
-
 // SLOTS: `clock` is the pool's table, the grid has no last block, and slot b rolls by its own ran(b) rows (none: no roll).
+template <bool SLOTS> using RollClock = typename std::conditional<SLOTS, const SrwnSynthSlot*, long long*>::type;
+
 template <typename T, int R, bool SLOTS = false>
 __global__ __launch_bounds__(256) void recog_roll_kernel(const RollEntry* __restrict__ roll, int nroll,
                                                          const float* __restrict__ x, int64_t x_stride,
-                                                         float* __restrict__ carry,
-                                                         typename std::conditional<SLOTS, const SrwnSynthSlot*, long long*>::type clock,
-                                                         int B, int n) {
+                                                         float* __restrict__ carry, RollClock<SLOTS> clock, int B, int n) {
   if constexpr (SLOTS) {      // (workgroup-uniform, before the first barrier)
     const SrwnSynthSlot sl = clock[(int)blockIdx.x % B];
-    n = sl.t < 0 ? 0 : slot_ran(sl, n);
+    n = sl.t < 0 ? 0 : slot_rows(sl, n);
     if (n <= 0) return;
   } else if ((int)blockIdx.x == nroll * B) {
     for (int b = threadIdx.x; b < B; b += 256) carry[b] = x[(int64_t)b * x_stride + n - 1];
@@ -344,34 +320,45 @@ __global__ __launch_bounds__(256) void recog_roll_kernel(const RollEntry* __rest
   }
 }
 
-}  // namespace
 
-extern "C" int srwn_recog_stream_in(const float* x, int64_t x_stride, const float* carry, const float* init_w,
-                                    const float* init_b, void* out, int64_t out_clip_rows, int32_t out_hist, int32_t B,
-                                    int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream) {
-  if (!x || !carry || !init_w || !init_b || !out) return set_error(SRWN_E_NULL, "recog_stream_in: null pointer");
-  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_stream_in: dilation_channels %d (built: 32, 64)", R);
+// ------------------------------------------------------------------------------------------
+// The host bodies: one per pair of entry points.  `who` names the entry point in every message; SLOTS says which form it
+// is, and the clock form's B is then the pool's capacity (named so in the messages: rows_name).
+// ------------------------------------------------------------------------------------------
+// x: the chunk's audio with its carry, or (SLOTS) the pool's audio ring of x_stride samples per slot, without one
+template <bool SLOTS> constexpr const char* rows_name() { return SLOTS ? "capacity" : "B"; }
+
+template <bool SLOTS>
+int recog_stream_in_impl(const char* who, const float* x, int64_t x_stride, const float* carry, const float* init_w,
+                         const float* init_b, void* out, int64_t out_clip_rows, int32_t out_hist, int32_t B, int32_t n,
+                         int32_t max_chunk, int32_t R, int32_t dtype, const SrwnSynthSlot* slots, void* stream) {
+  if (!x || !init_w || !init_b || !out || (SLOTS ? !slots : !carry)) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d (built: 32, 64)", who, R);
   if (B < 1 || max_chunk < 1 || out_hist < 0)
-    return set_error(SRWN_E_SHAPE, "recog_stream_in: B=%d max_chunk=%d out_hist=%d", B, max_chunk, out_hist);
-  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_stream_in: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  if (x_stride < max_chunk || out_clip_rows < (int64_t)out_hist + max_chunk)
-    return set_error(SRWN_E_SHAPE, "recog_stream_in: x stride %lld, %lld buffer rows per stream for %d + %d",
-                     (long long)x_stride, (long long)out_clip_rows, out_hist, max_chunk);
+    return set_error(SRWN_E_SHAPE, "%s: %s=%d max_chunk=%d out_hist=%d", who, rows_name<SLOTS>(), B, max_chunk, out_hist);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "%s: chunk of %d rows (1..max_chunk = %d)", who, n, max_chunk);
+  // (the ring also holds the sample before a whole chunk)
+  if (x_stride < (int64_t)max_chunk + (SLOTS ? 1 : 0) || out_clip_rows < (int64_t)out_hist + max_chunk) {
+    if (SLOTS)
+      return set_error(SRWN_E_SHAPE, "%s: an audio ring of %d samples for max_chunk + 1 = %lld, %lld buffer rows per slot for %d + %d",
+                       who, (int)x_stride, (long long)max_chunk + 1, (long long)out_clip_rows, out_hist, max_chunk);
+    return set_error(SRWN_E_SHAPE, "%s: x stride %lld, %lld buffer rows per stream for %d + %d", who, (long long)x_stride,
+                     (long long)out_clip_rows, out_hist, max_chunk);
+  }
   const int64_t threads = (int64_t)B * n * (R / 8);
   dim3 grid((unsigned)((threads + 255) / 256)), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == SRWN_BF16)
-    hipLaunchKernelGGL(recog_stream_in_kernel<bf16_t>, grid, block, 0, st, x, x_stride, carry, init_w, init_b, (bf16_t*)out,
-                       out_clip_rows, out_hist, B, n, R);
+    hipLaunchKernelGGL((recog_stream_in_kernel<bf16_t, SLOTS>), grid, block, 0, st, x, x_stride, carry, init_w, init_b,
+                       (bf16_t*)out, out_clip_rows, out_hist, B, n, R, slots);
   else if (dtype == SRWN_F32)
-    hipLaunchKernelGGL(recog_stream_in_kernel<float>, grid, block, 0, st, x, x_stride, carry, init_w, init_b, (float*)out,
-                       out_clip_rows, out_hist, B, n, R);
+    hipLaunchKernelGGL((recog_stream_in_kernel<float, SLOTS>), grid, block, 0, st, x, x_stride, carry, init_w, init_b,
+                       (float*)out, out_clip_rows, out_hist, B, n, R, slots);
   else
-    return set_error(SRWN_E_DTYPE, "recog_stream_in: dtype %d", dtype);
-  return check_launch("recog_stream_in");
+    return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+  return check_launch(who);
 }
 
-namespace {
 int hop_args(const char* who, int32_t ring_rows, int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int64_t clip_rows) {
   if (B < 1 || k < 1 || hop < 1 || ring_rows < 1 || max_chunk < 1)
     return set_error(SRWN_E_SHAPE, "%s: B=%d hops=%d hop=%d ring=%d max_chunk=%d", who, B, k, hop, ring_rows, max_chunk);
@@ -381,24 +368,23 @@ int hop_args(const char* who, int32_t ring_rows, int32_t B, int32_t k, int32_t h
   if ((int64_t)B * k > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "%s: too many hops", who);
   return 0;
 }
-}  // namespace
 
-extern "C" int srwn_pooled_stream_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
-                                       const void* wskip, const float* bs_sum, const void* w1, const float* b1,
-                                       float* ring, int32_t ring_rows, const int64_t* clock, int32_t B, int32_t k,
-                                       int32_t hop, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype, void* stream) {
-  if (!z || !wskip || !bs_sum || !w1 || !b1 || !ring || !clock) return set_error(SRWN_E_NULL, "pooled_stream_head: null pointer");
+template <bool SLOTS>
+int pooled_stream_head_impl(const char* who, const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                            const void* wskip, const float* bs_sum, const void* w1, const float* b1, float* ring,
+                            int32_t ring_rows, typename ClockArg<SLOTS>::in clock, int32_t B, int32_t k, int32_t hop,
+                            int32_t max_chunk, int32_t R, int32_t S, int32_t dtype, void* stream) {
+  if (!z || !wskip || !bs_sum || !w1 || !b1 || !ring || !clock) return set_error(SRWN_E_NULL, "%s: null pointer", who);
   if ((R != 32 && R != 64) || (S != 128 && S != 256))
-    return set_error(SRWN_E_UNSUPPORTED, "pooled_stream_head: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", R, S);
-  if (const int rc = hop_args("pooled_stream_head", ring_rows, B, k, hop, max_chunk, z_clip_rows)) return rc;
+    return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
+  if (const int rc = hop_args(who, ring_rows, B, k, hop, max_chunk, z_clip_rows)) return rc;
   if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
-    return set_error(SRWN_E_SHAPE, "pooled_stream_head: %d layers at a stride of %lld", nlayers, (long long)z_layer_stride);
+    return set_error(SRWN_E_SHAPE, "%s: %d layers at a stride of %lld", who, nlayers, (long long)z_layer_stride);
   dim3 grid((unsigned)(B * k)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  const long long* ck = reinterpret_cast<const long long*>(clock);
-#define SRWN_PSH(TT, RR, SS)                                                                                              \
-  hipLaunchKernelGGL((pooled_stream_head_kernel<TT, RR, SS>), grid, block, 0, st, (const TT*)z, z_layer_stride, z_clip_rows, \
-                     nlayers, (const TT*)wskip, bs_sum, (const TT*)w1, b1, ring, ring_rows, ck, k, hop)
+#define SRWN_PSH(TT, RR, SS)                                                                                             \
+  hipLaunchKernelGGL((pooled_stream_head_kernel<TT, RR, SS, SLOTS>), grid, block, 0, st, (const TT*)z, z_layer_stride,    \
+                     z_clip_rows, nlayers, (const TT*)wskip, bs_sum, (const TT*)w1, b1, ring, ring_rows, clock, k, hop)
 #define SRWN_PSH_T(TT)                                       \
   {                                                          \
     if (R == 32 && S == 128) SRWN_PSH(TT, 32, 128);          \
@@ -408,94 +394,102 @@ extern "C" int srwn_pooled_stream_head(const void* z, int64_t z_layer_stride, in
   }
   if (dtype == SRWN_BF16) SRWN_PSH_T(bf16_t)
   else if (dtype == SRWN_F32) SRWN_PSH_T(float)
-  else return set_error(SRWN_E_DTYPE, "pooled_stream_head: dtype %d", dtype);
+  else return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
 #undef SRWN_PSH_T
 #undef SRWN_PSH
-  return check_launch("pooled_stream_head");
+  return check_launch(who);
 }
 
-extern "C" int srwn_hop_sum(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows, const int64_t* clock,
-                            int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int32_t S, int32_t dtype, void* stream) {
-  if (!r1 || !ring || !clock) return set_error(SRWN_E_NULL, "hop_sum: null pointer");
-  if (const int rc = hop_args("hop_sum", ring_rows, B, k, hop, max_chunk, r1_clip_rows)) return rc;
-  if (S < 2 || S % 2) return set_error(SRWN_E_SHAPE, "hop_sum: S=%d", S);
+template <bool SLOTS>
+int hop_sum_impl(const char* who, const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows,
+                 typename ClockArg<SLOTS>::in clock, int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int32_t S,
+                 int32_t dtype, void* stream) {
+  if (!r1 || !ring || !clock) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (const int rc = hop_args(who, ring_rows, B, k, hop, max_chunk, r1_clip_rows)) return rc;
+  if (S < 2 || S % 2) return set_error(SRWN_E_SHAPE, "%s: S=%d", who, S);
   dim3 grid((unsigned)(B * k)), block(256);
   hipStream_t st = (hipStream_t)stream;
-  const long long* ck = reinterpret_cast<const long long*>(clock);
   if (dtype == SRWN_BF16)
-    hipLaunchKernelGGL(hop_sum_kernel<bf16_t>, grid, block, 0, st, (const bf16_t*)r1, r1_clip_rows, ring, ring_rows, ck, k, hop, S);
+    hipLaunchKernelGGL((hop_sum_kernel<bf16_t, SLOTS>), grid, block, 0, st, (const bf16_t*)r1, r1_clip_rows, ring, ring_rows, clock, k, hop, S);
   else if (dtype == SRWN_F32)
-    hipLaunchKernelGGL(hop_sum_kernel<float>, grid, block, 0, st, (const float*)r1, r1_clip_rows, ring, ring_rows, ck, k, hop, S);
+    hipLaunchKernelGGL((hop_sum_kernel<float, SLOTS>), grid, block, 0, st, (const float*)r1, r1_clip_rows, ring, ring_rows, clock, k, hop, S);
   else
-    return set_error(SRWN_E_DTYPE, "hop_sum: dtype %d", dtype);
-  return check_launch("hop_sum");
+    return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+  return check_launch(who);
 }
 
-extern "C" int srwn_window_mean(const float* ring, int32_t ring_rows, float* mean, const int64_t* clock, int32_t B,
-                                int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2,
-                                float* logits, int32_t C, int32_t ldw, void* stream) {
-  if (!ring || !mean || !clock || (logits && (!w2 || !b2))) return set_error(SRWN_E_NULL, "window_mean: null pointer");
+template <bool SLOTS>
+int window_mean_impl(const char* who, const float* ring, int32_t ring_rows, float* mean, typename ClockArg<SLOTS>::in clock,
+                     int32_t B, int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2,
+                     float* logits, int32_t C, int32_t ldw, void* stream) {
+  if (!ring || !mean || !clock || (logits && (!w2 || !b2))) return set_error(SRWN_E_NULL, "%s: null pointer", who);
   if (B < 1 || k < 1 || hop < 1 || window < hop || window % hop || S < 1 || S > 256)
-    return set_error(SRWN_E_SHAPE, "window_mean: B=%d hops=%d hop=%d window=%d S=%d (window a multiple of hop, S <= 256)", B,
-                     k, hop, window, S);
+    return set_error(SRWN_E_SHAPE, "%s: %s=%d hops=%d hop=%d window=%d S=%d (window a multiple of hop, S <= 256)", who,
+                     rows_name<SLOTS>(), B, k, hop, window, S);
   const int nW = window / hop;
   if (ring_rows < nW + k - 1)
-    return set_error(SRWN_E_SHAPE, "window_mean: a ring of %d rows for %d window rows + %d hops per launch - 1", ring_rows, nW, k);
-  if (logits && (C < 1 || ldw < C)) return set_error(SRWN_E_SHAPE, "window_mean: C=%d ldw=%d", C, ldw);
-  if ((int64_t)B * k > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "window_mean: too many rows");
-  hipLaunchKernelGGL(window_mean_kernel<false>, dim3((unsigned)(B * k)), dim3(256), 0, (hipStream_t)stream, ring, ring_rows, mean,
-                     reinterpret_cast<const long long*>(clock), k, hop, nW, (float)window, S, w2, b2, logits, C, ldw);
-  return check_launch("window_mean");
+    return set_error(SRWN_E_SHAPE, "%s: a ring of %d rows for %d window rows + %d hops per launch - 1", who, ring_rows, nW, k);
+  if (logits && (C < 1 || ldw < C)) return set_error(SRWN_E_SHAPE, "%s: C=%d ldw=%d", who, C, ldw);
+  // (SLOTS: the kernel counts a slot's rows in a chunk of k * hop in int32)
+  if ((int64_t)B * k > 0x7fffffffLL || (SLOTS && (int64_t)k * hop > 0x7fffffffLL))
+    return set_error(SRWN_E_SHAPE, "%s: too many rows", who);
+  hipLaunchKernelGGL(window_mean_kernel<SLOTS>, dim3((unsigned)(B * k)), dim3(256), 0, (hipStream_t)stream, ring, ring_rows,
+                     mean, clock, k, hop, nW, (float)window, S, w2, b2, logits, C, ldw);
+  return check_launch(who);
 }
 
-extern "C" int srwn_recog_roll(const int64_t* roll_table, int32_t nroll, const float* x, int64_t x_stride, float* carry,
-                               int64_t* clock, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
-                               void* stream) {
-  if (!x || !carry || !clock || (nroll > 0 && !roll_table)) return set_error(SRWN_E_NULL, "recog_roll: null pointer");
-  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_roll: dilation_channels %d (built: 32, 64)", R);
-  if (B < 1 || nroll < 0 || max_chunk < 1 || x_stride < max_chunk)
-    return set_error(SRWN_E_SHAPE, "recog_roll: B=%d boundaries=%d max_chunk=%d x stride %lld", B, nroll, max_chunk, (long long)x_stride);
-  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_roll: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  static_assert(sizeof(RollEntry) == 24, "the roll table is int64 triples");
-  dim3 grid((unsigned)((int64_t)nroll * B + 1)), block(256);
+// Clock form: x, carry and the clock are renewed by one extra block at the grid's end.  SLOTS: the table in the clock's
+// place, no x and no carry, no last block -- and without boundary buffers no launch at all.
+template <bool SLOTS>
+int recog_roll_impl(const char* who, const int64_t* roll_table, int32_t nroll, const float* x, int64_t x_stride, float* carry,
+                    RollClock<SLOTS> clock, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream) {
+  if (!clock || (nroll > 0 && !roll_table) || (!SLOTS && (!x || !carry))) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d (built: 32, 64)", who, R);
+  if (B < 1 || nroll < 0 || max_chunk < 1 || (!SLOTS && x_stride < max_chunk)) {
+    if (SLOTS) return set_error(SRWN_E_SHAPE, "%s: capacity=%d boundaries=%d max_chunk=%d", who, B, nroll, max_chunk);
+    return set_error(SRWN_E_SHAPE, "%s: B=%d boundaries=%d max_chunk=%d x stride %lld", who, B, nroll, max_chunk, (long long)x_stride);
+  }
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "%s: chunk of %d rows (1..max_chunk = %d)", who, n, max_chunk);
+  if (SLOTS && nroll == 0) return 0;
+  dim3 grid((unsigned)((int64_t)nroll * B + (SLOTS ? 0 : 1))), block(256);
   hipStream_t st = (hipStream_t)stream;
   const RollEntry* rt = reinterpret_cast<const RollEntry*>(roll_table);
-  long long* ck = reinterpret_cast<long long*>(clock);
-#define SRWN_RR(TT, RR) hipLaunchKernelGGL((recog_roll_kernel<TT, RR>), grid, block, 0, st, rt, nroll, x, x_stride, carry, ck, B, n)
+#define SRWN_RR(TT, RR) hipLaunchKernelGGL((recog_roll_kernel<TT, RR, SLOTS>), grid, block, 0, st, rt, nroll, x, x_stride, carry, clock, B, n)
   if (dtype == SRWN_BF16) { if (R == 32) SRWN_RR(bf16_t, 32); else SRWN_RR(bf16_t, 64); }
   else if (dtype == SRWN_F32) { if (R == 32) SRWN_RR(float, 32); else SRWN_RR(float, 64); }
-  else return set_error(SRWN_E_DTYPE, "recog_roll: dtype %d", dtype);
+  else return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
 #undef SRWN_RR
-  return check_launch("recog_roll");
+  return check_launch(who);
 }
 
+const long long* ck(const int64_t* clock) { return reinterpret_cast<const long long*>(clock); }
+
+}  // namespace
+
 // ------------------------------------------------------------------------------------------
-// The slot forms (classifier pools, srwn.h): the launches above on the pool's table.
+// The entry points (srwn.h): each names itself and says which form it is.
 // ------------------------------------------------------------------------------------------
+extern "C" int srwn_recog_stream_in(const float* x, int64_t x_stride, const float* carry, const float* init_w,
+                                    const float* init_b, void* out, int64_t out_clip_rows, int32_t out_hist, int32_t B,
+                                    int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream) {
+  return recog_stream_in_impl<false>("recog_stream_in", x, x_stride, carry, init_w, init_b, out, out_clip_rows, out_hist, B, n,
+                                     max_chunk, R, dtype, nullptr, stream);
+}
+
 extern "C" int srwn_recog_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w,
                                           const float* init_b, void* out, int64_t out_clip_rows, int32_t out_hist,
                                           int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
                                           const SrwnSynthSlot* slots, void* stream) {
-  if (!audio_ring || !init_w || !init_b || !out || !slots) return set_error(SRWN_E_NULL, "recog_stream_in_slots: null pointer");
-  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_stream_in_slots: dilation_channels %d (built: 32, 64)", R);
-  if (capacity < 1 || max_chunk < 1 || out_hist < 0)
-    return set_error(SRWN_E_SHAPE, "recog_stream_in_slots: capacity=%d max_chunk=%d out_hist=%d", capacity, max_chunk, out_hist);
-  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_stream_in_slots: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  if ((int64_t)ring_len < (int64_t)max_chunk + 1 || out_clip_rows < (int64_t)out_hist + max_chunk)
-    return set_error(SRWN_E_SHAPE, "recog_stream_in_slots: an audio ring of %d samples for max_chunk + 1 = %lld, %lld buffer "
-                     "rows per slot for %d + %d", ring_len, (long long)max_chunk + 1, (long long)out_clip_rows, out_hist, max_chunk);
-  const int64_t threads = (int64_t)capacity * n * (R / 8);
-  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SRWN_BF16)
-    hipLaunchKernelGGL(recog_stream_in_slots_kernel<bf16_t>, grid, block, 0, st, audio_ring, ring_len, init_w, init_b,
-                       (bf16_t*)out, out_clip_rows, out_hist, capacity, n, R, slots);
-  else if (dtype == SRWN_F32)
-    hipLaunchKernelGGL(recog_stream_in_slots_kernel<float>, grid, block, 0, st, audio_ring, ring_len, init_w, init_b,
-                       (float*)out, out_clip_rows, out_hist, capacity, n, R, slots);
-  else
-    return set_error(SRWN_E_DTYPE, "recog_stream_in_slots: dtype %d", dtype);
-  return check_launch("recog_stream_in_slots");
+  return recog_stream_in_impl<true>("recog_stream_in_slots", audio_ring, ring_len, nullptr, init_w, init_b, out, out_clip_rows,
+                                    out_hist, capacity, n, max_chunk, R, dtype, slots, stream);
+}
+
+extern "C" int srwn_pooled_stream_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                       const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                       float* ring, int32_t ring_rows, const int64_t* clock, int32_t B, int32_t k,
+                                       int32_t hop, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype, void* stream) {
+  return pooled_stream_head_impl<false>("pooled_stream_head", z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1,
+                                        ring, ring_rows, ck(clock), B, k, hop, max_chunk, R, S, dtype, stream);
 }
 
 extern "C" int srwn_pooled_stream_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
@@ -503,82 +497,45 @@ extern "C" int srwn_pooled_stream_head_slots(const void* z, int64_t z_layer_stri
                                              float* ring, int32_t ring_rows, const SrwnSynthSlot* slots, int32_t capacity,
                                              int32_t k, int32_t hop, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype,
                                              void* stream) {
-  if (!z || !wskip || !bs_sum || !w1 || !b1 || !ring || !slots) return set_error(SRWN_E_NULL, "pooled_stream_head_slots: null pointer");
-  if ((R != 32 && R != 64) || (S != 128 && S != 256))
-    return set_error(SRWN_E_UNSUPPORTED, "pooled_stream_head_slots: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", R, S);
-  if (const int rc = hop_args("pooled_stream_head_slots", ring_rows, capacity, k, hop, max_chunk, z_clip_rows)) return rc;
-  if (nlayers < 1 || z_layer_stride < (int64_t)capacity * z_clip_rows * R)
-    return set_error(SRWN_E_SHAPE, "pooled_stream_head_slots: %d layers at a stride of %lld", nlayers, (long long)z_layer_stride);
-  dim3 grid((unsigned)(capacity * k)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define SRWN_PSH(TT, RR, SS)                                                                                            \
-  hipLaunchKernelGGL((pooled_stream_head_kernel<TT, RR, SS, true>), grid, block, 0, st, (const TT*)z, z_layer_stride,   \
-                     z_clip_rows, nlayers, (const TT*)wskip, bs_sum, (const TT*)w1, b1, ring, ring_rows, slots, k, hop)
-#define SRWN_PSH_T(TT)                                       \
-  {                                                          \
-    if (R == 32 && S == 128) SRWN_PSH(TT, 32, 128);          \
-    else if (R == 32) SRWN_PSH(TT, 32, 256);                 \
-    else if (S == 128) SRWN_PSH(TT, 64, 128);                \
-    else SRWN_PSH(TT, 64, 256);                              \
-  }
-  if (dtype == SRWN_BF16) SRWN_PSH_T(bf16_t)
-  else if (dtype == SRWN_F32) SRWN_PSH_T(float)
-  else return set_error(SRWN_E_DTYPE, "pooled_stream_head_slots: dtype %d", dtype);
-#undef SRWN_PSH_T
-#undef SRWN_PSH
-  return check_launch("pooled_stream_head_slots");
+  return pooled_stream_head_impl<true>("pooled_stream_head_slots", z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1,
+                                       b1, ring, ring_rows, slots, capacity, k, hop, max_chunk, R, S, dtype, stream);
+}
+
+extern "C" int srwn_hop_sum(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows, const int64_t* clock,
+                            int32_t B, int32_t k, int32_t hop, int32_t max_chunk, int32_t S, int32_t dtype, void* stream) {
+  return hop_sum_impl<false>("hop_sum", r1, r1_clip_rows, ring, ring_rows, ck(clock), B, k, hop, max_chunk, S, dtype, stream);
 }
 
 extern "C" int srwn_hop_sum_slots(const void* r1, int64_t r1_clip_rows, float* ring, int32_t ring_rows,
                                   const SrwnSynthSlot* slots, int32_t capacity, int32_t k, int32_t hop, int32_t max_chunk,
                                   int32_t S, int32_t dtype, void* stream) {
-  if (!r1 || !ring || !slots) return set_error(SRWN_E_NULL, "hop_sum_slots: null pointer");
-  if (const int rc = hop_args("hop_sum_slots", ring_rows, capacity, k, hop, max_chunk, r1_clip_rows)) return rc;
-  if (S < 2 || S % 2) return set_error(SRWN_E_SHAPE, "hop_sum_slots: S=%d", S);
-  dim3 grid((unsigned)(capacity * k)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == SRWN_BF16)
-    hipLaunchKernelGGL((hop_sum_kernel<bf16_t, true>), grid, block, 0, st, (const bf16_t*)r1, r1_clip_rows, ring, ring_rows, slots, k, hop, S);
-  else if (dtype == SRWN_F32)
-    hipLaunchKernelGGL((hop_sum_kernel<float, true>), grid, block, 0, st, (const float*)r1, r1_clip_rows, ring, ring_rows, slots, k, hop, S);
-  else
-    return set_error(SRWN_E_DTYPE, "hop_sum_slots: dtype %d", dtype);
-  return check_launch("hop_sum_slots");
+  return hop_sum_impl<true>("hop_sum_slots", r1, r1_clip_rows, ring, ring_rows, slots, capacity, k, hop, max_chunk, S, dtype,
+                            stream);
+}
+
+extern "C" int srwn_window_mean(const float* ring, int32_t ring_rows, float* mean, const int64_t* clock, int32_t B,
+                                int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2,
+                                float* logits, int32_t C, int32_t ldw, void* stream) {
+  return window_mean_impl<false>("window_mean", ring, ring_rows, mean, ck(clock), B, k, hop, window, S, w2, b2, logits, C, ldw,
+                                 stream);
 }
 
 extern "C" int srwn_window_mean_slots(const float* ring, int32_t ring_rows, float* mean, const SrwnSynthSlot* slots,
                                       int32_t capacity, int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2,
                                       const float* b2, float* logits, int32_t C, int32_t ldw, void* stream) {
-  if (!ring || !mean || !slots || (logits && (!w2 || !b2))) return set_error(SRWN_E_NULL, "window_mean_slots: null pointer");
-  if (capacity < 1 || k < 1 || hop < 1 || window < hop || window % hop || S < 1 || S > 256)
-    return set_error(SRWN_E_SHAPE, "window_mean_slots: capacity=%d hops=%d hop=%d window=%d S=%d (window a multiple of hop, S <= 256)",
-                     capacity, k, hop, window, S);
-  const int nW = window / hop;
-  if (ring_rows < nW + k - 1)
-    return set_error(SRWN_E_SHAPE, "window_mean_slots: a ring of %d rows for %d window rows + %d hops per launch - 1", ring_rows, nW, k);
-  if (logits && (C < 1 || ldw < C)) return set_error(SRWN_E_SHAPE, "window_mean_slots: C=%d ldw=%d", C, ldw);
-  if ((int64_t)capacity * k > 0x7fffffffLL || (int64_t)k * hop > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "window_mean_slots: too many rows");
-  hipLaunchKernelGGL(window_mean_kernel<true>, dim3((unsigned)(capacity * k)), dim3(256), 0, (hipStream_t)stream, ring,
-                     ring_rows, mean, slots, k, hop, nW, (float)window, S, w2, b2, logits, C, ldw);
-  return check_launch("window_mean_slots");
+  return window_mean_impl<true>("window_mean_slots", ring, ring_rows, mean, slots, capacity, k, hop, window, S, w2, b2, logits,
+                                C, ldw, stream);
+}
+
+extern "C" int srwn_recog_roll(const int64_t* roll_table, int32_t nroll, const float* x, int64_t x_stride, float* carry,
+                               int64_t* clock, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
+                               void* stream) {
+  return recog_roll_impl<false>("recog_roll", roll_table, nroll, x, x_stride, carry, reinterpret_cast<long long*>(clock), B, n,
+                                max_chunk, R, dtype, stream);
 }
 
 extern "C" int srwn_recog_roll_slots(const int64_t* roll_table, int32_t nroll, const SrwnSynthSlot* slots, int32_t capacity,
                                      int32_t n, int32_t max_chunk, int32_t R, int32_t dtype, void* stream) {
-  if (!slots || (nroll > 0 && !roll_table)) return set_error(SRWN_E_NULL, "recog_roll_slots: null pointer");
-  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "recog_roll_slots: dilation_channels %d (built: 32, 64)", R);
-  if (capacity < 1 || nroll < 0 || max_chunk < 1)
-    return set_error(SRWN_E_SHAPE, "recog_roll_slots: capacity=%d boundaries=%d max_chunk=%d", capacity, nroll, max_chunk);
-  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "recog_roll_slots: chunk of %d rows (1..max_chunk = %d)", n, max_chunk);
-  if (nroll == 0) return 0;
-  dim3 grid((unsigned)((int64_t)nroll * capacity)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const RollEntry* rt = reinterpret_cast<const RollEntry*>(roll_table);
-#define SRWN_RR(TT, RR) \
-  hipLaunchKernelGGL((recog_roll_kernel<TT, RR, true>), grid, block, 0, st, rt, nroll, (const float*)nullptr, (int64_t)0, (float*)nullptr, slots, capacity, n)
-  if (dtype == SRWN_BF16) { if (R == 32) SRWN_RR(bf16_t, 32); else SRWN_RR(bf16_t, 64); }
-  else if (dtype == SRWN_F32) { if (R == 32) SRWN_RR(float, 32); else SRWN_RR(float, 64); }
-  else return set_error(SRWN_E_DTYPE, "recog_roll_slots: dtype %d", dtype);
-#undef SRWN_RR
-  return check_launch("recog_roll_slots");
+  return recog_roll_impl<true>("recog_roll_slots", roll_table, nroll, nullptr, 0, nullptr, slots, capacity, n, max_chunk, R,
+                               dtype, stream);
 }

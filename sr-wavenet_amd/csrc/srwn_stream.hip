@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "srwn_common.h"
 #include "srwn_host.h"
+#include "srwn_slots.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -38,14 +39,8 @@ template <> struct Row8s<float> {
 };
 
 // The slot forms (synthesis pools, srwn.h SrwnSynthSlot) are the same kernels with a template flag: the clock argument
-// becomes the pool's table, slot b's chunk starts at slots[b].t and has ran = clamp(t_end - t, 0, n) rows.  The clock
-// instantiations keep their arguments and their code.
-template <bool SLOTS> struct ClockArg { typedef const long long* __restrict__ in; typedef long long* __restrict__ out; };
-template <> struct ClockArg<true> { typedef const SrwnSynthSlot* __restrict__ in; struct out { SrwnSynthSlot* slots; int* arrive; }; };
-__device__ __forceinline__ int slot_rows(const SrwnSynthSlot s, int n) {
-  const long long left = s.t_end - s.t;
-  return left <= 0 ? 0 : (left < n ? (int)left : n);
-}
+// becomes the pool's table, slot b's chunk starts at slots[b].t and has ran = slot_rows(slots[b], n) rows (ClockArg,
+// slot_rows and the roll's RollEntry: srwn_slots.h).  The clock instantiations keep their arguments and their code.
 
 // ------------------------------------------------------------------------------------------
 // flow entry: 8 channels per thread, one row per group of R/8 lanes
@@ -60,7 +55,7 @@ __global__ __launch_bounds__(256) void flow_stream_in_kernel(const float* __rest
                                                              const T* __restrict__ cond, int cond_frames, int pool,
                                                              int64_t cond_stride, T* __restrict__ out,
                                                              int64_t out_clip_rows, int hist, int B, int n, int R,
-                                                             typename ClockArg<SLOTS>::in clock) {
+                                                             typename ClockArg<SLOTS>::in __restrict__ clock) {
   const int lpr = R / 8;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t row = idx / lpr;
@@ -104,8 +99,6 @@ __global__ __launch_bounds__(256) void flow_stream_in_kernel(const float* __rest
 // [0, hist) (slot form: rows [ran, ran + hist)).  For n < hist the ranges overlap: the block walks them front to back, each step reading all of its rows
 // before it writes any (a barrier between), and a row written in one step lies in front of every row a later step reads.
 // ------------------------------------------------------------------------------------------
-struct RollEntry { void* buf; long long clip_rows; long long hist; };      // int64 triples, as the engine's table holds them
-
 // (SLOTS) slots[b].t += ran(b) for the live slots.  Every workgroup of the exit launch reads the table, so the one that
 // arrives LAST -- after all of them have read -- does the writing: each counts itself in once it is done, the one that
 // finds every other counted puts the counter back to zero for the next launch and advances the table, one thread per
@@ -250,7 +243,7 @@ template <bool SLOTS = false>
 __global__ __launch_bounds__(256) void logistic_noise_kernel(float* __restrict__ noise, int64_t stride,
                                                              const float* __restrict__ temperature,
                                                              const uint64_t* __restrict__ seed,
-                                                             typename ClockArg<SLOTS>::in clock, int B, int n) {
+                                                             typename ClockArg<SLOTS>::in __restrict__ clock, int B, int n) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)B * n) return;
   const int b = (int)(i / n);
@@ -355,7 +348,6 @@ int flow_stream_out_impl(const char* who, const void* h, int64_t top_clip_rows, 
   if (x_stride < max_chunk || top_clip_rows < max_chunk)
     return set_error(SRWN_E_SHAPE, "%s: x stride %lld, top rows %lld < max_chunk %d", who, (long long)x_stride,
                      (long long)top_clip_rows, max_chunk);
-  static_assert(sizeof(RollEntry) == 24, "the roll table is int64 triples");
   const int naff = (int)(((int64_t)B * n + 255) / 256);
   dim3 grid((unsigned)(naff + (int64_t)nroll * B)), block(256);
   hipStream_t st = (hipStream_t)stream;

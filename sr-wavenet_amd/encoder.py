@@ -31,7 +31,7 @@ from . import packing as P
 from . import _lib
 from ._lib import call
 from .engine import Section, StackConfig, WaveNetEngine
-from .slots import SlotTable
+from .audio_ring import AudioRingSlots
 
 # What SRWN_ENC_FUSED means when it is not set (FrameEncoder in bf16): "0" the layer-by-layer twin, "1" the one-launch
 # chain.  Set by measurement: tools/encode_bench.py case (b) at B = 1, pool 512 has the chain at 0.160 ms per push
@@ -739,11 +739,12 @@ class FrameEncoder:
         return EncoderPool(self, audio_ring, max_rows)
 
 
-class EncoderPool(SlotTable):
+class EncoderPool(AudioRingSlots):
     """``FrameEncoder.pool()``: the encoder's ``max_batch`` rows as SLOTS, each holding a stream with its own samples
-    received, frames emitted and end.  Streams ``join`` free slots, ``push`` audio of any length whenever it arrives (one
-    upload and one srwn_audio_ring_put however many slots are written; a slot's audio lives in its row of a device ring,
-    sample s in column s mod audio_ring, and nothing is re-allocated), ``step`` encodes every frame that is due -- of
+    received, frames emitted and end.  Streams ``join`` free slots, ``push`` audio of any length whenever it arrives
+    (``audio_ring.AudioRingSlots``, shared with the classifier pool: one upload and one srwn_audio_ring_put however many
+    slots are written; a slot's audio lives in its row of a device ring, sample s in column s mod audio_ring, and
+    nothing is re-allocated), ``step`` encodes every frame that is due -- of
     every slot, as launches over a LIST of frames (``plan_pool``; srwn_nc_encode_frame_list on the fused path, the same
     plan gathered into windows and run layer by layer otherwise) -- and a stream that was ``finish``ed frees its slot
     with its last frame.  A stream's frames put together equal ``FrameEncoder.encode`` of its audio alone, bit for bit:
@@ -762,20 +763,17 @@ class EncoderPool(SlotTable):
                              % (self.audio_ring, self.window))
         if not 1 <= self.max_rows <= rows:
             raise ValueError("pool: max_rows %d: 1..max_batch * max_frames = %d" % (self.max_rows, rows))
-        if self.capacity * self.audio_ring + 4 * self.capacity > 0x7fffffff:
-            raise ValueError("pool: %d slots of %d samples" % (self.capacity, self.audio_ring))
-        K._need_gpu()
-        cap, dev = self.capacity, fe.w.dev
+        self._alloc_audio_ring()
+        cap = self.capacity
         self._received = np.zeros(cap, np.int64)
         self._emitted = np.zeros(cap, np.int64)
         self._final = np.zeros(cap, bool)
         self._active = np.zeros(cap, bool)
-        self.ring = torch.zeros((cap, self.audio_ring), dtype=torch.float32, device=dev)
-        # one upload per push: [streams | src_offset | first_col | counts] (n each) and the concatenated audio behind them
-        self.stage = torch.zeros(4 * cap + cap * self.audio_ring, dtype=torch.int32, device=dev)
-        self.table = torch.zeros((self.max_rows, 4), dtype=torch.int32, device=dev)      # SrwnEncFrame per item
+        self.table = torch.zeros((self.max_rows, 4), dtype=torch.int32, device=self.dev)      # SrwnEncFrame per item
 
     # ---- inspection
+    dev = property(lambda self: self.fe.w.dev, doc="The encoder's device.")
+
     @property
     def received(self) -> np.ndarray:
         """Samples pushed into each slot's stream so far."""
@@ -814,57 +812,12 @@ class EncoderPool(SlotTable):
         for u in slots:
             self._final[u] = True
 
-    def push(self, slots, audio) -> None:
-        """audio[i], 1-D of any length (0 too), behind what slots[i] has received.  Refuses (ValueError, nothing changed) a
-        slot that holds no stream or was finished, more than ``audio_room(slot)`` samples and audio that is not floating
-        point.  One host-to-device copy and one srwn_audio_ring_put, whatever the number of slots."""
-        one = not np.ndim(slots)
-        slots = self._slot_list(slots, "push", distinct=True)
-        if one or isinstance(audio, (np.ndarray, torch.Tensor)):
-            audio = [audio]
-        audio = list(audio)
-        if len(audio) != len(slots):
-            raise ValueError("push: %d slots but %d pieces of audio" % (len(slots), len(audio)))
-        xs = []
-        for u, x in zip(slots, audio):
-            if isinstance(x, torch.Tensor):
-                if not x.is_floating_point():
-                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
-                x = x.detach().to("cpu", torch.float32).numpy()
-            else:
-                x = np.asarray(x)
-                if x.dtype.kind != "f":
-                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
-                x = x.astype(np.float32, copy=False)
-            if x.ndim != 1:
-                raise ValueError("push: the audio of a slot is 1-D [samples], got shape %s" % (x.shape,))
-            if not self._active[u]:
-                raise ValueError("push: slot %d holds no stream" % u)
-            if self._final[u]:
-                raise ValueError("push: the stream in slot %d was finished" % u)
-            if x.shape[0] > self.audio_room(u):
-                raise ValueError("push: %d samples for slot %d, but its ring of %d has room for %d (received %d, emitted "
-                                 "%d frames)" % (x.shape[0], u, self.audio_ring, self.audio_room(u), self._received[u],
-                                                 self._emitted[u]))
-            xs.append(x)
-        pairs = [(u, x) for u, x in zip(slots, xs) if x.shape[0] > 0]
-        if not pairs:
-            return
-        n = len(pairs)
-        counts = np.asarray([x.shape[0] for _, x in pairs], np.int64)
-        us = np.asarray([u for u, _ in pairs], np.int64)
-        total = int(counts.sum())
-        host = np.empty(4 * n + total, np.int32)
-        host[0:n] = us
-        host[n:2 * n] = np.cumsum(counts) - counts
-        host[2 * n:3 * n] = self._received[us] % self.audio_ring
-        host[3 * n:4 * n] = counts
-        host[4 * n:].view(np.float32)[:] = np.concatenate([x for _, x in pairs])
-        self.stage[:host.shape[0]].copy_(torch.from_numpy(host))
-        sp = self.stage.data_ptr()
-        call("srwn_audio_ring_put", self.ring.data_ptr(), self.audio_ring, self.capacity, sp + 16 * n, sp, sp + 4 * n,
-             sp + 8 * n, sp + 12 * n, n, int(counts.max()), K._stream())
-        self._received[us] += counts
+    def _push_barred(self):
+        """``AudioRingSlots.push``: a finished stream takes no more audio."""
+        return self._final, "push: the stream in slot %d was finished"
+
+    def _room_tail(self, u):
+        return "emitted %d frames" % self._emitted[u]
 
     # ---- one step: every frame that is due
     def _launch(self, items) -> torch.Tensor:

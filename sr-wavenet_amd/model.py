@@ -1233,11 +1233,8 @@ class EncoderStream(object):
         return self._owner._eng.finish(self._st).cpu().numpy()
 
 
-class AudioEncoderPool(_PoolFace):
-    """NumPy face of an encoder pool (``AudioEncoder.pool``; encoder.EncoderPool).  ``join`` returns slots,
-    ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``finish(slots)`` ends streams, ``step()`` returns
-    ``{slot: frames [k, latent]}`` for every slot with new frames and frees the finished slots whose frames are all out.
-    A stream's frames put together are ``AudioEncoder.encode`` of its audio alone."""
+class _AudioPoolFace(_PoolFace):
+    """What the NumPy faces of the pools that take audio share (``self._pool``: an ``audio_ring.AudioRingSlots``)."""
 
     def __init__(self, pool):
         self._pool = pool
@@ -1253,6 +1250,13 @@ class AudioEncoderPool(_PoolFace):
 
     def push(self, slots, audio):
         self._pool.push([int(slots)] if np.isscalar(slots) else slots, _audio_pieces(slots, audio))
+
+
+class AudioEncoderPool(_AudioPoolFace):
+    """NumPy face of an encoder pool (``AudioEncoder.pool``; encoder.EncoderPool).  ``join`` returns slots,
+    ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``finish(slots)`` ends streams, ``step()`` returns
+    ``{slot: frames [k, latent]}`` for every slot with new frames and frees the finished slots whose frames are all out.
+    A stream's frames put together are ``AudioEncoder.encode`` of its audio alone."""
 
     def finish(self, slots):
         self._pool.finish(slots)
@@ -1261,28 +1265,14 @@ class AudioEncoderPool(_PoolFace):
         return {u: f.cpu().numpy() for u, f in self._pool.step(limit).items()}
 
 
-class ClassifierPool(_PoolFace):
+class ClassifierPool(_AudioPoolFace):
     """NumPy face of a classifier pool (``StreamingClassifier.pool``; recognizer.ClassifierPool).  ``join`` returns slots,
     ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``step()`` returns ``{slot: probabilities [e, C]}``
     for every slot whose stream completed window positions (with return_logits a second dict with the pooled logits).  A
     stream's emissions put together are ``StreamingClassifier.classify`` of its audio alone."""
 
-    def __init__(self, pool):
-        self._pool = pool
-
     audio_ring = property(lambda self: self._pool.audio_ring)
-    received = property(lambda self: self._pool.received)
     consumed = property(lambda self: self._pool.consumed)
-    emitted = property(lambda self: self._pool.emitted)
-
-    def audio_room(self, slot):
-        return self._pool.audio_room(int(slot))
-
-    def join(self, n=1, slots=None):
-        return self._pool.join(n, slots)
-
-    def push(self, slots, audio):
-        self._pool.push([int(slots)] if np.isscalar(slots) else slots, _audio_pieces(slots, audio))
 
     def step(self, return_logits=False):
         out = self._pool.step(return_logits)

@@ -19,6 +19,9 @@ chunk-sized buffers and ``srwn_hop_sum``), ``srwn_window_mean``, ``srwn_pooled_h
 ``StreamClassifier.pool()`` turns the classifier's ``max_batch`` rows into SLOTS (``ClassifierPool``): streams join and
 leave, each pushes audio of any length at a clock of its own, and one step serves every slot that has a whole hop waiting
 with the same launches in their slot forms (srwn.h, srwn_version() 115), on a table the host writes before every step.
+There is ONE launch list, ``StreamClassifier._launch_step(B, h, pool=None)``: with a pool it picks the ``_slots`` entry
+points, the pool's table in the clock's place and the pool's audio ring in the place of the staged chunk and its carry.
+The pool's audio ring and its ``push`` are ``audio_ring.AudioRingSlots``, which the encoder pool shares.
 """
 from __future__ import annotations
 
@@ -32,7 +35,7 @@ from . import kernels as K
 from . import packing as P
 from ._lib import call
 from .engine import Section, WaveNetEngine
-from .slots import SlotTable
+from .audio_ring import AudioRingSlots
 
 # What SRWN_RECOG_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
 RECOG_FUSED_DEFAULT = "1"
@@ -303,44 +306,59 @@ class StreamClassifier:
             raise ValueError("audio of %d streams pushed into a state of %d" % (x.shape[0], batch))
         return x
 
-    def _launch_step(self, B: int, h: int):
-        """The launches of a step of h hops (n = h * hop rows) on the audio staged in ``xbuf``."""
+    def _launch_step(self, B: int, h: int, pool: Optional["ClassifierPool"] = None):
+        """The launches of a step of h hops (n = h * hop rows): on the audio staged in ``xbuf`` at the clock, or, with
+        `pool`, the same launches in their slot forms on ``pool.table`` -- B is then the pool's capacity and the audio
+        comes from the pool's ring, which holds the sample before the chunk too (no carry)."""
         import ctypes as C_
         w = self.w
         st, dt, R, S, C, L = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk, w.L
-        n, ck, v = h * self.hop, self.clock.data_ptr(), w.view
-        call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
-             v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt, st)
+        sfx = "" if pool is None else "_slots"
+        n, v = h * self.hop, w.view
+        when = self.clock.data_ptr() if pool is None else pool.table.data_ptr()      # the clock, or the table in its place
+        entry = (self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt)
+        if pool is None:
+            call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
+                 v("init_b").data_ptr(), *entry, st)
+        else:
+            call("srwn_recog_stream_in_slots", pool.ring.data_ptr(), pool.audio_ring, v("init_w").data_ptr(),
+                 v("init_b").data_ptr(), *entry, when, st)
         G = len(self.groups)
         zstride = self.max_batch * C * R
         for g, (l0, l1) in enumerate(self.groups):
             last = g + 1 == G
             out = self.top if last else self.bufs[g + 1]
             nl = l1 - l0
-            call("srwn_residual_group_fwd_stream_z", self.bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
+            call("srwn_residual_group_fwd_stream_z" + sfx, self.bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
                  C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1], self.zs[l0].data_ptr(), zstride,
                  K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
                  K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
                  K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
                  K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, ck, st)
+                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, when, st)
         if self.fused:
-            call("srwn_pooled_stream_head", self.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
-                 w.wptr(w.o_w1), v("head_b1").data_ptr(), self.ring.data_ptr(), self.ring_rows, ck, B, h, self.hop, C, R, S,
+            call("srwn_pooled_stream_head" + sfx, self.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
+                 w.wptr(w.o_w1), v("head_b1").data_ptr(), self.ring.data_ptr(), self.ring_rows, when, B, h, self.hop, C, R, S,
                  dt, st)
         else:      # the training forward's two products (engine.forward: skip_sum, head_1x1) on the buffers' rows, up to
-            # the last stream's chunk: one launch each, so for B > 1 the stale rows between the streams' chunks ride along
+            # the last stream's chunk: one launch each, so the stale rows between the streams' chunks ride along (in a pool
+            # also the rows of idle slots and those beyond a slot's ran), and the hop sum never reads them
             rows = (B - 1) * C + n
             K.pw_linear(self.zs.data_ptr(), R, zstride, R, L * R, w.wptr(w.o_skip), w.bs_sum, self.r0[:rows], S, S, rows,
                         pro=K.PRO_GATE, epi=K.EPI_RELU)
             K.pw_linear(self.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), self.r1[:rows], S, S, rows,
                         epi=K.EPI_RELU)
-            call("srwn_hop_sum", self.r1.data_ptr(), C, self.ring.data_ptr(), self.ring_rows, ck, B, h, self.hop, C, S, dt, st)
-        call("srwn_window_mean", self.ring.data_ptr(), self.ring_rows, self.mean.data_ptr(), ck, B, h, self.hop, self.window,
-             S, v("head_w2").data_ptr(), v("head_b2").data_ptr(), self.logits.data_ptr(), w.C, w.Cp, st)
+            call("srwn_hop_sum" + sfx, self.r1.data_ptr(), C, self.ring.data_ptr(), self.ring_rows, when, B, h, self.hop, C, S,
+                 dt, st)
+        call("srwn_window_mean" + sfx, self.ring.data_ptr(), self.ring_rows, self.mean.data_ptr(), when, B, h, self.hop,
+             self.window, S, v("head_w2").data_ptr(), v("head_b2").data_ptr(), self.logits.data_ptr(), w.C, w.Cp, st)
         call("srwn_pooled_head", self.mean.data_ptr(), v("head_w2").data_ptr(), v("head_b2").data_ptr(), None,
              self.probs.data_ptr(), None, None, None, None, B * h, S, w.C, w.Cp, st)
-        call("srwn_recog_roll", self.roll.data_ptr(), G, self.xbuf.data_ptr(), C, self.carry.data_ptr(), ck, B, n, C, R, dt, st)
+        if pool is None:
+            call("srwn_recog_roll", self.roll.data_ptr(), G, self.xbuf.data_ptr(), C, self.carry.data_ptr(), when, B, n, C, R,
+                 dt, st)
+        else:
+            call("srwn_recog_roll_slots", self.roll.data_ptr(), G, when, B, n, C, R, dt, st)
 
     def push(self, state: RecogState, audio, return_logits: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> probabilities [B, k, C] fp32 of the k window
@@ -381,14 +399,15 @@ class StreamClassifier:
         return self.push(self.start(int(x.shape[0])), x, return_logits)
 
 
-class ClassifierPool(SlotTable):
+class ClassifierPool(AudioRingSlots):
     """``StreamClassifier.pool()``: the classifier's ``max_batch`` rows as SLOTS, each holding a stream with its own
     samples ``received``, samples ``consumed`` by the stack (a multiple of hop) and emissions ``emitted``.  Streams ``join``
     free slots (history rows zeroed by srwn_flow_stream_reset_slots; the hop-sum ring needs no reset, srwn.h), ``push``
     audio of any length whenever it arrives (one upload and one srwn_audio_ring_put however many slots are written: a
     slot's audio lives in its row of a device ring, sample s in column s mod audio_ring), and ``step`` serves every slot
     that has a whole hop waiting: per pass ``plan_pool_step``, the table [t = consumed, t_end = t + hops * hop] uploaded
-    whole, and the launches of one classifier step in their slot forms -- one hipGraph per k, captured at second use.  The
+    whole, and the launches of one classifier step in their slot forms (``StreamClassifier._launch_step`` with this pool)
+    -- one hipGraph per k, captured at second use.  The
     device never advances the table.  A stream's emissions put together equal ``StreamClassifier(max_batch=1).classify``
     of its audio alone, bit for bit: in any slot, whenever it joined, however its audio was cut, whatever k the steps
     had and whatever the other slots hold or held before."""
@@ -400,18 +419,13 @@ class ClassifierPool(SlotTable):
         if self.audio_ring < c.max_chunk + 1:
             raise ValueError("pool: audio_ring %d holds less than max_chunk + 1 = %d samples (a whole step and the sample "
                              "before it)" % (self.audio_ring, c.max_chunk + 1))
-        if self.capacity * self.audio_ring + 4 * self.capacity > 0x7fffffff:
-            raise ValueError("pool: %d slots of %d samples" % (self.capacity, self.audio_ring))
-        K._need_gpu()
-        cap, dev = self.capacity, c.dev
+        self._alloc_audio_ring()
+        cap = self.capacity
         self._received = np.zeros(cap, np.int64)
         self._consumed = np.zeros(cap, np.int64)
         self._emitted = np.zeros(cap, np.int64)
         self._active = np.zeros(cap, bool)
-        self.ring = torch.zeros((cap, self.audio_ring), dtype=torch.float32, device=dev)
-        # one upload per push: [streams | src_offset | first_col | counts] (n each) and the concatenated audio behind them
-        self.stage = torch.zeros(4 * cap + cap * self.audio_ring, dtype=torch.int32, device=dev)
-        self.table = torch.zeros((cap, 2), dtype=torch.int64, device=dev)      # SrwnSynthSlot [t, t_end] per slot
+        self.table = torch.zeros((cap, 2), dtype=torch.int64, device=self.dev)      # SrwnSynthSlot [t, t_end] per slot
         self._graphs: Dict[int, object] = {}
         self._seen: set = set()
         self._open = True
@@ -426,6 +440,7 @@ class ClassifierPool(SlotTable):
         return out
 
     # ---- inspection
+    dev = property(lambda self: self.c.dev, doc="The classifier's device.")
     received = property(lambda self: self._received.copy(), doc="Samples pushed into each slot's stream so far.")
     consumed = property(lambda self: self._consumed.copy(), doc="Samples each slot's stack has run (whole hops).")
     emitted = property(lambda self: self._emitted.copy(), doc="Emissions each slot's stream has returned so far.")
@@ -462,93 +477,14 @@ class ClassifierPool(SlotTable):
             self._active[u] = False
 
     def push(self, slots, audio) -> None:
-        """audio[i], 1-D of any length (0 too), behind what slots[i] has received.  Refuses (ValueError, nothing changed) a
-        slot that holds no stream, more than ``audio_room(slot)`` samples and audio that is not floating point.  One
-        host-to-device copy and one srwn_audio_ring_put, whatever the number of slots."""
+        """``AudioRingSlots.push`` into an open pool: audio[i], 1-D of any length (0 too), behind what slots[i] received."""
         self._check_open()
-        one = not np.ndim(slots)
-        slots = self._slot_list(slots, "push", distinct=True)
-        if one or isinstance(audio, (np.ndarray, torch.Tensor)):
-            audio = [audio]
-        audio = list(audio)
-        if len(audio) != len(slots):
-            raise ValueError("push: %d slots but %d pieces of audio" % (len(slots), len(audio)))
-        xs = []
-        for u, x in zip(slots, audio):
-            if isinstance(x, torch.Tensor):
-                if not x.is_floating_point():
-                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
-                x = x.detach().to("cpu", torch.float32).numpy()
-            else:
-                x = np.asarray(x)
-                if x.dtype.kind != "f":
-                    raise ValueError("push: audio must be floating point, got %s" % x.dtype)
-                x = x.astype(np.float32, copy=False)
-            if x.ndim != 1:
-                raise ValueError("push: the audio of a slot is 1-D [samples], got shape %s" % (x.shape,))
-            if not self._active[u]:
-                raise ValueError("push: slot %d holds no stream" % u)
-            if x.shape[0] > self.audio_room(u):
-                raise ValueError("push: %d samples for slot %d, but its ring of %d has room for %d (received %d, consumed "
-                                 "%d)" % (x.shape[0], u, self.audio_ring, self.audio_room(u), self._received[u],
-                                          self._consumed[u]))
-            xs.append(x)
-        pairs = [(u, x) for u, x in zip(slots, xs) if x.shape[0] > 0]
-        if not pairs:
-            return
-        n = len(pairs)
-        counts = np.asarray([x.shape[0] for _, x in pairs], np.int64)
-        us = np.asarray([u for u, _ in pairs], np.int64)
-        host = np.empty(4 * n + int(counts.sum()), np.int32)
-        host[0:n] = us
-        host[n:2 * n] = np.cumsum(counts) - counts
-        host[2 * n:3 * n] = self._received[us] % self.audio_ring
-        host[3 * n:4 * n] = counts
-        host[4 * n:].view(np.float32)[:] = np.concatenate([x for _, x in pairs])
-        self.stage[:host.shape[0]].copy_(torch.from_numpy(host))
-        sp = self.stage.data_ptr()
-        call("srwn_audio_ring_put", self.ring.data_ptr(), self.audio_ring, self.capacity, sp + 16 * n, sp, sp + 4 * n,
-             sp + 8 * n, sp + 12 * n, n, int(counts.max()), K._stream())
-        self._received[us] += counts
+        super().push(slots, audio)
+
+    def _room_tail(self, u):
+        return "consumed %d" % self._consumed[u]
 
     # ---- one step: every whole hop that waits
-    def _launch_step(self, k: int):
-        """The launches of a step of k hops on the table in ``self.table``: ``StreamClassifier._launch_step`` in slot forms."""
-        import ctypes as C_
-        c, w = self.c, self.c.w
-        st, dt, R, S, C, L = K._stream(), K.abi_dtype(c.dt), w.R, w.S, c.max_chunk, w.L
-        n, tb, v, cap = k * c.hop, self.table.data_ptr(), w.view, self.capacity
-        call("srwn_recog_stream_in_slots", self.ring.data_ptr(), self.audio_ring, v("init_w").data_ptr(),
-             v("init_b").data_ptr(), c.bufs[0].data_ptr(), c.hist[0] + C, c.hist[0], cap, n, C, R, dt, tb, st)
-        G = len(c.groups)
-        zstride = cap * C * R
-        for g, (l0, l1) in enumerate(c.groups):
-            last = g + 1 == G
-            out = c.top if last else c.bufs[g + 1]
-            nl = l1 - l0
-            call("srwn_residual_group_fwd_stream_z_slots", c.bufs[g].data_ptr(), c.hist[g] + C, out.data_ptr(),
-                 C if last else c.hist[g + 1] + C, 0 if last else c.hist[g + 1], c.zs[l0].data_ptr(), zstride,
-                 K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
-                 K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
-                 K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
-                 K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, cap, n, C, R, w.Kw, dt, tb, st)
-        if c.fused:
-            call("srwn_pooled_stream_head_slots", c.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
-                 w.wptr(w.o_w1), v("head_b1").data_ptr(), c.ring.data_ptr(), c.ring_rows, tb, cap, k, c.hop, C, R, S, dt, st)
-        else:      # the twin's two products run over every slot's buffer rows up to the last slot's chunk: the rows of idle
-            # slots and those beyond a slot's ran ride along, and srwn_hop_sum_slots never reads them
-            rows = (cap - 1) * C + n
-            K.pw_linear(c.zs.data_ptr(), R, zstride, R, L * R, w.wptr(w.o_skip), w.bs_sum, c.r0[:rows], S, S, rows,
-                        pro=K.PRO_GATE, epi=K.EPI_RELU)
-            K.pw_linear(c.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), c.r1[:rows], S, S, rows, epi=K.EPI_RELU)
-            call("srwn_hop_sum_slots", c.r1.data_ptr(), C, c.ring.data_ptr(), c.ring_rows, tb, cap, k, c.hop, C, S, dt, st)
-        call("srwn_window_mean_slots", c.ring.data_ptr(), c.ring_rows, c.mean.data_ptr(), tb, cap, k, c.hop, c.window, S,
-             v("head_w2").data_ptr(), v("head_b2").data_ptr(), c.logits.data_ptr(), w.C, w.Cp, st)
-        call("srwn_pooled_head", c.mean.data_ptr(), v("head_w2").data_ptr(), v("head_b2").data_ptr(), None,
-             c.probs.data_ptr(), None, None, None, None, cap * k, S, w.C, w.Cp, st)
-        call("srwn_recog_roll_slots", c.roll.data_ptr(), G, tb, cap, n, C, R, dt, st)
-
     def step(self, return_logits: bool = False):
         """Runs while any active slot has a whole hop waiting -> {slot: probabilities [e, C] fp32 on the device} for the
         slots whose streams completed e > 0 window positions (``emissions_due`` on the slot's own clock); with
@@ -563,7 +499,7 @@ class ClassifierPool(SlotTable):
                 break
             Cc = c.w.C
             self.table.copy_(torch.from_numpy(np.stack([self._consumed, self._consumed + hops * hop], 1)))
-            K.run_cached_graph(self._graphs, self._seen, k, c.use_graphs, lambda: self._launch_step(k))
+            K.run_cached_graph(self._graphs, self._seen, k, c.use_graphs, lambda: c._launch_step(cap, k, self))
             probs = logits = None
             for u in np.flatnonzero(hops):
                 t0, h = int(self._consumed[u]), int(hops[u])

@@ -1,8 +1,10 @@
 """The host bookkeeping every serving pool shares: which slots hold a stream, which are free, how a caller names slots,
 and how one argument becomes one value per stream.  Pure Python and NumPy: no device work, nothing here launches.
 
-* ``SlotTable``  -- the base of ``engine.GenerationPool``, ``student.SynthPool``, ``encoder.EncoderPool`` and
-                    ``model.ResynthesisPool`` (whose ``_active`` is a read-only property computed from its streams'
+* ``SlotTable``  -- the base of ``engine.GenerationPool``, ``student.SynthPool``, ``audio_ring.AudioRingSlots`` (and
+                    through it ``encoder.EncoderPool`` and ``recognizer.ClassifierPool``: the pools that take audio
+                    share their device ring and their ``push`` there, which keeps this module free of device work)
+                    and ``model.ResynthesisPool`` (whose ``_active`` is a read-only property computed from its streams'
                     conditions: it cannot be assigned).
 * ``slot_list``  -- a scalar or a sequence of slots as ints, range-checked (the pools' faces in ``model`` use it too).
 * ``per_stream`` -- None, a scalar or a sequence of n as a list of n.

@@ -1,6 +1,7 @@
 """CPU tests of the classifier pool's host side (recognizer.plan_pool_step, recognizer.ClassifierPool): the step plan
 against brute force, a simulated ragged session through the plan and ``emissions_due``, everything the pool refuses before
-it touches the device, and the audio ring's room.  No GPU: the pools are built without their constructors."""
+it touches the device, the audio ring's room, and what the five slot entry points of the library refuse.  No GPU: the
+pools are built without their constructors, and no call gets as far as a launch."""
 import numpy as np
 import pytest
 
@@ -192,3 +193,87 @@ def test_audio_room_keeps_the_sample_before_the_chunk():
                 assert held[s % ring] == s
             p._consumed[0] = t1
         assert p._received[0] > 20 * ring                            # the ring wrapped many times
+
+
+# ---- the slot forms' refusals ------------------------------------------------------------------------------------------
+E_DTYPE, E_SHAPE, E_NULL, E_UNSUPPORTED = -1, -2, -3, -4
+A = 4096          # a 16-byte aligned stand-in address: nothing is dereferenced on the paths this test takes
+
+
+@pytest.mark.parametrize("binding", ["pybind11", "ctypes"])
+def test_slot_argument_errors_do_not_need_a_gpu(binding):
+    """The five slot entry points refuse what test_recognizer's test_argument_errors_do_not_need_a_gpu has the clock forms
+    refuse, the table in the place of the clock, and what only they can be given wrong; every message names the slot
+    entry."""
+    from tests.test_recognizer import _lib
+    lib = _lib(binding)
+
+    def named(entry):      # the last refusal came from `entry` itself, not from its clock form
+        return lib.srwn_last_error().startswith(entry + b":")
+
+    def head(z=A, zst=2 * 64 * 32, zrows=64, L=3, ring=A, rr=5, slots=A, cap=2, k=2, hop=32, mc=64, R=32, S=128, dt=1):
+        return lib.srwn_pooled_stream_head_slots(z, zst, zrows, L, A, A, A, A, ring, rr, slots, cap, k, hop, mc, R, S, dt, None)
+
+    assert head(z=None) == E_NULL
+    assert head(slots=None) == E_NULL
+    assert head(R=48) == E_UNSUPPORTED
+    assert head(S=192) == E_UNSUPPORTED
+    assert head(k=3) == E_SHAPE                    # 3 hops of 32 rows in a chunk buffer of 64
+    assert head(zrows=32) == E_SHAPE
+    assert head(zst=100) == E_SHAPE
+    assert head(L=0) == E_SHAPE
+    assert head(cap=0) == E_SHAPE
+    assert head(dt=7) == E_DTYPE
+    assert named(b"pooled_stream_head_slots")
+
+    def wmean(ring=A, rr=5, mean=A, slots=A, cap=2, k=2, hop=32, window=128, S=128, logits=None, w2=None):
+        return lib.srwn_window_mean_slots(ring, rr, mean, slots, cap, k, hop, window, S, w2, w2, logits, 12, 32, None)
+
+    assert wmean(ring=None) == E_NULL
+    assert wmean(slots=None) == E_NULL
+    assert wmean(logits=A) == E_NULL               # logits without the last 1x1
+    assert wmean(window=100) == E_SHAPE            # not a multiple of hop
+    assert wmean(hop=0) == E_SHAPE
+    assert wmean(rr=4) == E_SHAPE                  # 4 window rows + 2 hops per launch - 1 = 5
+    assert wmean(S=512) == E_SHAPE
+    assert wmean(cap=0) == E_SHAPE and b"capacity=0" in lib.srwn_last_error()
+    # slot form only: a slot's rows in the chunk are counted in int32, so k * hop must fit (capacity * k does here)
+    assert wmean(cap=1, k=1 << 16, hop=1 << 16, window=1 << 16, rr=1 << 16) == E_SHAPE
+    assert named(b"window_mean_slots")
+
+    def hsum(r1=A, rows=64, slots=A, k=2, hop=32, mc=64, S=128, dt=1):
+        return lib.srwn_hop_sum_slots(r1, rows, A, 5, slots, 2, k, hop, mc, S, dt, None)
+
+    assert hsum(r1=None) == E_NULL
+    assert hsum(slots=None) == E_NULL
+    assert hsum(k=3) == E_SHAPE
+    assert hsum(S=7) == E_SHAPE
+    assert hsum(dt=7) == E_DTYPE
+    assert named(b"hop_sum_slots")
+
+    def entry(ring=A, ring_len=65, rows=31 + 64, hist=31, n=40, mc=64, R=32, dt=1, slots=A):
+        return lib.srwn_recog_stream_in_slots(ring, ring_len, A, A, A, rows, hist, 2, n, mc, R, dt, slots, None)
+
+    assert entry(ring=None) == E_NULL
+    assert entry(slots=None) == E_NULL
+    assert entry(R=48) == E_UNSUPPORTED
+    assert entry(n=65) == E_SHAPE
+    assert entry(n=0) == E_SHAPE
+    assert entry(rows=64) == E_SHAPE
+    assert entry(ring_len=64) == E_SHAPE           # max_chunk samples: no room for the sample before a whole chunk
+    assert b"max_chunk + 1 = 65" in lib.srwn_last_error()
+    assert entry(dt=7) == E_DTYPE
+    assert named(b"recog_stream_in_slots")
+
+    def roll(table=A, nroll=2, n=40, mc=64, R=32, dt=1, slots=A):
+        return lib.srwn_recog_roll_slots(table, nroll, slots, 2, n, mc, R, dt, None)
+
+    assert roll(table=None) == E_NULL
+    assert roll(slots=None) == E_NULL
+    assert roll(R=16) == E_UNSUPPORTED
+    assert roll(n=65) == E_SHAPE
+    assert roll(nroll=-1) == E_SHAPE
+    assert lib.srwn_last_error() == b"recog_roll_slots: capacity=2 boundaries=-1 max_chunk=64"      # (no x, so no x stride)
+    assert roll(dt=7) == E_DTYPE
+    assert named(b"recog_roll_slots")
+    assert roll(nroll=0, table=None) == 0          # no boundary buffers: nothing to roll, nothing launched

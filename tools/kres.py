@@ -33,14 +33,17 @@ def main():
     # (c++filt does not know DF16b = __bf16: demangle with it spelled as a known type)
     dem = subprocess.run(["c++filt"], input="\n".join(r["name"].replace("DF16b", "Dh") for r in rows), capture_output=True,
                          text=True).stdout.replace("_Float16", "bf16").splitlines()
-    print("%-110s %5s %5s %6s %6s %4s %7s" % ("kernel", "VGPR", "AGPR", "vspill", "sspill", "occ", "LDS"))
+    print("%-110s %5s %5s %5s %6s %6s %7s %4s %7s" % ("kernel", "VGPR", "AGPR", "SGPR", "vspill", "sspill", "scratch", "occ",
+                                                      "LDS"))
     for r, d in zip(rows, dem):
         d = re.sub(r"\(anonymous namespace\)::", "", d)
         d = re.sub(r"\(.*\)$", "", d).replace("void ", "")
         if filt and not all(f in d for f in filt):
             continue
-        print("%-110s %5d %5d %6d %6d %4d %7d" % (d[:110], r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("VGPRs Spill", -1),
-                                                  r.get("SGPRs Spill", -1), r.get("Occupancy", -1), r.get("LDS Size", -1)))
+        print("%-110s %5d %5d %5d %6d %6d %7d %4d %7d" % (d[:110], r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("TotalSGPRs", -1),
+                                                          r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1),
+                                                          r.get("ScratchSize", -1), r.get("Occupancy", -1),
+                                                          r.get("LDS Size", -1)))
 
 
 if __name__ == "__main__":
