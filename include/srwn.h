@@ -1317,6 +1317,49 @@ int srwn_window_mean_slots(const float* ring, int32_t ring_rows, float* mean, co
 int srwn_recog_roll_slots(const int64_t* roll_table, int32_t nroll, const SrwnSynthSlot* slots, int32_t capacity, int32_t n,
                           int32_t max_chunk, int32_t R, int32_t dtype, void* stream);
 
+/* ---- streaming likelihood scorer (since srwn_version() 116; csrc/srwn_score.hip): the softmax teacher (class
+ * WaveNetTeacher: createDecoder's stack, model.py:158-196, without conditioning, and the per-sample softmax over mu-law
+ * codes, model.py:100-112) as an inference-only stream that leaves nll[t] = -log p(code[t] | audio[< t]) in nats for every
+ * row of a chunk.  The stack runs through the streaming classifier's launches: srwn_recog_stream_in on the audio DELAYED BY
+ * ONE SAMPLE (x'[0] = the last sample of the chunk before, 0 at the stream's start, x'[1:n] = chunk[:n-1]: with the K = 2
+ * entry conv that is h0[t] = b + w0 a[t-2] + w1 a[t-1], the RightShift of model.py:172 folded into the staging), one
+ * srwn_residual_group_fwd_stream_z per layer group, and srwn_recog_roll.  A chunk is any 1 <= n <= max_chunk rows; a row's
+ * value depends on its own z rows only, so a stream has the same bits however its audio was cut, at any batch size and in
+ * any row of the batch.  R in {32, 64}, S in {128, 256}, 1 <= C <= 256 classes, dtype SRWN_BF16 or SRWN_F32.
+ *
+ *   srwn_stream_score_head  model.py:50-56, the log-softmax and the gather of the target's column in one launch, one
+ *                           workgroup per (stream, 32-row tile of the chunk; the last one masked when n % 32 != 0): the gate
+ *                           c = z sigmoid(z) rebuilt from the stored z as srwn_pw_linear's SRWN_PRO_GATE does, r0 =
+ *                           relu(bs_sum + sum_l Ws_l c_l), r1 = relu(W1 r0 + b1) -- both rounded to dtype where the
+ *                           training forward stores them and exchanged through LDS -- logits = W2 r1 + b2 in fp32 (all
+ *                           three products start at the bias and take their k-steps in order, as srwn_pw_linear does),
+ *                           then per row, over the columns [0, C) ONLY (the padding of the last 32-column tile never enters
+ *                           the max or the sum): m = max, nll = log(sum_c exp(l_c - m)) + m - l[code], 8 lanes per row,
+ *                           lane j on the columns j, j + 8, ... in rising order, the lanes' values joined by an xor
+ *                           butterfly.  z [nlayers][B][z_clip_rows][R] at z_layer_stride, chunk row t of stream b at row b *
+ *                           z_clip_rows + t (what srwn_residual_group_fwd_stream_z stores); wskip: the packed skip image
+ *                           [S/32][nlayers * R / 16] (natural k order, k = l * R + n), w1 the packed head image
+ *                           [S/32][S/16] and w2 the packed image [Cp/32][S/16] of the last 1x1, Cp = 32 * ceil(C / 32), its
+ *                           rows behind C zero, as srwn_pw_linear takes them; b2 [Cp] fp32, zero behind C.  codes
+ *                           [B][out_stride] int32 in [0, C) (a value outside is clamped into it).  Outputs, row t of
+ *                           stream b at b * out_stride + t: nll fp32; best (NULL: not wanted) int32, the argmax column,
+ *                           the lowest one on ties; logits_out (NULL: not wanted) fp32 [B][out_stride][C].  Rows [n,
+ *                           out_stride) of a stream are not touched.  Dynamic LDS: 32 x (S + 16 / sizeof(dtype)) elements
+ *                           of dtype and 32 x 260 fp32 (66 560 bytes for S = 256 in fp32).
+ *   srwn_nll_rows           the parity twin of the head's last step: the same reduction, by the same device routine on the
+ *                           same lane-to-column map, of logits [B][logits_clip_rows][logits_ld] fp32 (logits_ld >= C) that
+ *                           three srwn_pw_linear calls wrote (SRWN_PRO_GATE + SRWN_EPI_RELU over the stored z, SRWN_EPI_RELU,
+ *                           SRWN_EPI_F32): nll, best and logits_out have the bits of srwn_stream_score_head.
+ * Errors: a null pointer (-3; best and logits_out may be NULL), a width that is not built (-4), C outside [1, 256], B < 1, n
+ * < 1 or a chunk or buffer that does not fit (-2), dtype (-1); all before any launch. */
+int srwn_stream_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers, const void* wskip,
+                           const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
+                           const int32_t* codes, float* nll, int32_t* best, float* logits_out, int64_t out_stride,
+                           int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t S, int32_t C, int32_t dtype,
+                           void* stream);
+int srwn_nll_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const int32_t* codes, float* nll,
+                  int32_t* best, float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

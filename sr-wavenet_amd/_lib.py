@@ -262,6 +262,11 @@ SIGNATURES["srwn_pooled_stream_head_slots"] = SIGNATURES["srwn_pooled_stream_hea
 SIGNATURES["srwn_hop_sum_slots"] = SIGNATURES["srwn_hop_sum"]
 SIGNATURES["srwn_window_mean_slots"] = SIGNATURES["srwn_window_mean"]
 SIGNATURES["srwn_recog_roll_slots"] = (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p])
+# streaming likelihood scorer (srwn_version() 116): the one-launch score head over the stored z and its parity twin's
+# last step
+SIGNATURES["srwn_stream_score_head"] = (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32,
+                                                  _i32, _i32, _i32, _i32, _i32, _i32, _p])
+SIGNATURES["srwn_nll_rows"] = (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -1,0 +1,267 @@
+// Streaming likelihood scorer of the softmax teacher (class WaveNetTeacher: createDecoder's stack, model.py:158-196, with the
+// per-sample softmax over mu-law codes, model.py:100-112): nll[t] = -log p(code[t] | audio[< t]) for the rows of a chunk.
+// gfx950 (MI355X) only; MFMA orientation and lane maps: srwn_common.h.  The stack runs through the streaming classifier's
+// entry, group and roll launches (srwn_recog_stream_in on the audio delayed by one sample -- the RightShift --,
+// srwn_residual_group_fwd_stream_z, srwn_recog_roll); here is the head, one launch:
+//   score head     skip sum from the stored z (gate rebuilt as the skip sum's SRWN_PRO_GATE does), relu, head 1x1, relu, last
+//                  1x1, log-softmax and the gather of the target's column, one workgroup per (stream, 32-row tile of the
+//                  chunk): r0, r1 and the logits never reach HBM, one fp32 per sample does
+//   nll rows       the parity twin of the head's last step: the same reduction from a logits buffer that three
+//                  srwn_pw_linear calls wrote
+// Both reduce a row with ONE device routine, row_nll, on the same lane-to-column map, and both forms of the three products
+// start at the bias and take their k-steps in order: the two paths give the same bits.  A row depends on its own z rows
+// only, so a stream has the same bits in any chunking, at any batch size and in any row of the batch.
+#include <cmath>
+#include "srwn_common.h"
+#include "srwn_host.h"
+#include "../../include/srwn.h"
+
+using namespace srwn;
+
+namespace {
+
+constexpr int kRowLanes = 8;                  // lanes that share a row of logits in row_nll
+constexpr int kMaxClasses = 256;
+constexpr int kLogitStride = kMaxClasses + 4; // fp32 elements per row of the LDS logits block (16-byte rows, banks 4 apart)
+
+// ------------------------------------------------------------------------------------------
+// One row of logits -> nll = log(sum_c exp(l[c] - max)) + max - l[code] and the argmax (lowest index on ties), over the
+// columns [0, C) only: what lies behind column C (the padding of the last 32-column tile) is never read.  Called by the 8
+// consecutive lanes of a row's group, all of them, lane `sub` of the group: lane sub owns the columns sub, sub + 8, ... in
+// rising order (its max, then its sum of exp(l - max) in that order), and the lanes' values meet in an xor butterfly
+// (distances 1, 2, 4; fp32 addition commutes, so every lane of the group ends with the same bits).  Returns the same
+// value in all 8 lanes.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float row_nll(const float* logits_row, int C, int code, int sub, int* best) {
+  float m = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int c = sub; c < C; c += kRowLanes) {
+    const float v = logits_row[c];
+    if (v > m) { m = v; bi = c; }             // (strict: the lowest of a lane's equal columns stays)
+  }
+#pragma unroll
+  for (int s = 1; s < kRowLanes; s <<= 1) {
+    const float om = __shfl_xor(m, s, 64);
+    const int ob = __shfl_xor(bi, s, 64);
+    if (om > m || (om == m && ob < bi)) { m = om; bi = ob; }
+  }
+  float sum = 0.0f;
+  for (int c = sub; c < C; c += kRowLanes) sum += expf(logits_row[c] - m);
+#pragma unroll
+  for (int s = 1; s < kRowLanes; s <<= 1) sum += __shfl_xor(sum, s, 64);
+  *best = bi;
+  return logf(sum) + m - logits_row[code];
+}
+
+// What both kernels do with a tile's 32 rows of logits: thread (row = tid / 8, sub = tid % 8) of the workgroup reduces row
+// t0 + row of stream b.  A row beyond the chunk (the last tile) is reduced like the chunk's last row and stores nothing.
+// A code outside [0, C) is clamped into it (srwn_mu_law_encode never writes one).
+__device__ __forceinline__ void reduce_rows(const float* logits_row, int64_t orow, bool live, int C,
+                                            const int32_t* __restrict__ codes, float* __restrict__ nll,
+                                            int32_t* __restrict__ best, float* __restrict__ logits_out, int sub) {
+  int code = codes[orow];
+  code = code < 0 ? 0 : (code >= C ? C - 1 : code);
+  int bi;
+  const float v = row_nll(logits_row, C, code, sub, &bi);
+  if (!live) return;
+  if (sub == 0) {
+    nll[orow] = v;
+    if (best) best[orow] = bi;
+  }
+  if (logits_out)
+    for (int c = sub; c < C; c += kRowLanes) logits_out[orow * C + c] = logits_row[c];
+}
+
+// ------------------------------------------------------------------------------------------
+// score head.  Workgroup = (stream b, tile i of the chunk's ceil(n / 32) tiles), 4 waves; wave w owns the output channels
+// [w * S/4, (w + 1) * S/4) of the first two products and the 32-column tiles w, w + 4 of the logits.  In pooled_stream_head's
+// arithmetic (srwn_recog.hip):
+//   accS = bs_sum + sum_l Ws_l . gate(z_l)      B fragments: 8 channels of one z row per lane (natural k order), the gate
+//                                               on the fragment; A fragments from the packed skip image in L2
+//   r0 = relu(accS) rounded to T -> xch[32][S]  LDS, rows = time: the B operand of the head 1x1 for all four waves
+//   acc1 = b1 + W1 . r0;  r1 = relu(acc1) rounded to T -> xch again, once every wave has read r0 (a barrier)
+//   logits = b2 + W2 . r1 (fp32)  -> lg[32][kLogitStride]      all Cp = 32 * ceil(C / 32) columns; the image's rows behind C
+//                                               and their biases are zero, and row_nll never reads those columns
+//   nll, best = row_nll(lg[row])                8 lanes per row
+// A column of the tile beyond the chunk's last row re-reads that row (as the pooled head masks) and stores nothing.
+// Dynamic LDS: xch = 32 x (S + 16 / sizeof(T)) x sizeof(T) bytes (33 280 for S = 256 in fp32), then lg = 33 280 bytes.
+// ------------------------------------------------------------------------------------------
+template <typename T, int S> constexpr int xch_bytes() { return 32 * RowStage<T>::stride(S) * (int)sizeof(T); }
+constexpr int kLogitBytes = 32 * kLogitStride * (int)sizeof(float);
+
+template <typename T, int R, int S>
+__global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
+                                                                 int64_t z_clip_rows, int L, const T* __restrict__ wskip,
+                                                                 const float* __restrict__ bs_sum,
+                                                                 const T* __restrict__ w1, const float* __restrict__ b1,
+                                                                 const T* __restrict__ w2, const float* __restrict__ b2,
+                                                                 const int32_t* __restrict__ codes,
+                                                                 float* __restrict__ nll, int32_t* __restrict__ best,
+                                                                 float* __restrict__ logits_out, int64_t out_stride, int n,
+                                                                 int ntiles, int C) {
+  constexpr int MTW = S / 128;                // 32-channel output tiles per wave
+  constexpr int KSL = R / 16;                 // k-steps per layer
+  constexpr int KS1 = S / 16;
+  constexpr int LS = RowStage<T>::stride(S);
+  extern __shared__ __attribute__((aligned(16))) char score_lds[];
+  T* xch = reinterpret_cast<T*>(score_lds);
+  float* lg = reinterpret_cast<float*>(score_lds + xch_bytes<T, S>());
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int col = lane & 31, half = lane >> 5;
+  const int b = (int)blockIdx.x / ntiles, t0 = 32 * ((int)blockIdx.x % ntiles);
+  const int valid = n - t0 < 32 ? n - t0 : 32;
+  const int ks_skip = L * KSL;
+  const Frag<T>* ws = reinterpret_cast<const Frag<T>*>(wskip) + (size_t)(wave * MTW) * ks_skip * 64 + lane;
+  const Frag<T>* wh = reinterpret_cast<const Frag<T>*>(w1) + (size_t)(wave * MTW) * KS1 * 64 + lane;
+  const int trow = t0 + (col < valid ? col : valid - 1);      // (a masked column re-reads the chunk's last row)
+  const T* zr = z + ((int64_t)b * z_clip_rows + trow) * R + 8 * half;
+  f32x16 acc[MTW];
+#pragma unroll
+  for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[mt][q] = bs_sum[32 * (wave * MTW + mt) + crow(q, half)];
+  for (int l = 0; l < L; ++l) {
+    Frag<T> bf[KSL];
+#pragma unroll
+    for (int ks = 0; ks < KSL; ++ks) {
+      bf[ks] = load_nat(zr + (int64_t)l * z_layer_stride + 16 * ks);
+      gate_frag<T>(bf[ks]);
+    }
+#pragma unroll
+    for (int ks = 0; ks < KSL; ++ks)
+#pragma unroll
+      for (int mt = 0; mt < MTW; ++mt) mma(acc[mt], ws[((size_t)mt * ks_skip + l * KSL + ks) * 64], bf[ks]);
+  }
+#pragma unroll
+  for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      store4(xch + col * LS + 32 * (wave * MTW + mt) + 8 * g + 4 * half, fmaxf(acc[mt][4 * g], 0.0f),
+             fmaxf(acc[mt][4 * g + 1], 0.0f), fmaxf(acc[mt][4 * g + 2], 0.0f), fmaxf(acc[mt][4 * g + 3], 0.0f));
+  __syncthreads();
+#pragma unroll
+  for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[mt][q] = b1[32 * (wave * MTW + mt) + crow(q, half)];
+#pragma unroll 4
+  for (int ks = 0; ks < KS1; ++ks) {
+    const Frag<T> bf = load_nat(xch + col * LS + 16 * ks + 8 * half);
+#pragma unroll
+    for (int mt = 0; mt < MTW; ++mt) mma(acc[mt], wh[((size_t)mt * KS1 + ks) * 64], bf);
+  }
+  __syncthreads();                            // every wave has read r0: r1 takes its place
+#pragma unroll
+  for (int mt = 0; mt < MTW; ++mt)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      store4(xch + col * LS + 32 * (wave * MTW + mt) + 8 * g + 4 * half, fmaxf(acc[mt][4 * g], 0.0f),
+             fmaxf(acc[mt][4 * g + 1], 0.0f), fmaxf(acc[mt][4 * g + 2], 0.0f), fmaxf(acc[mt][4 * g + 3], 0.0f));
+  __syncthreads();
+  const int ctiles = (C + 31) / 32;
+  for (int mt = wave; mt < ctiles; mt += 4) { // (wave-uniform)
+    const Frag<T>* wl = reinterpret_cast<const Frag<T>*>(w2) + (size_t)mt * KS1 * 64 + lane;
+    f32x16 a2;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) a2[q] = b2[32 * mt + crow(q, half)];
+#pragma unroll 4
+    for (int ks = 0; ks < KS1; ++ks) mma(a2, wl[(size_t)ks * 64], load_nat(xch + col * LS + 16 * ks + 8 * half));
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      store4(lg + col * kLogitStride + 32 * mt + 8 * g + 4 * half, a2[4 * g], a2[4 * g + 1], a2[4 * g + 2], a2[4 * g + 3]);
+  }
+  __syncthreads();
+  const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
+  const bool live = row < valid;
+  const int64_t orow = (int64_t)b * out_stride + t0 + (live ? row : valid - 1);
+  reduce_rows(lg + row * kLogitStride, orow, live, C, codes, nll, best, logits_out, sub);
+}
+
+// ------------------------------------------------------------------------------------------
+// nll rows (parity twin): logits [B][clip_rows][ld] fp32 of the chunk -> nll, best and the copy of the C real columns.
+// The score head's grid and its thread-to-row map, row_nll on the row in HBM.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nll_rows_kernel(const float* __restrict__ logits, int64_t ld, int64_t clip_rows,
+                                                       const int32_t* __restrict__ codes, float* __restrict__ nll,
+                                                       int32_t* __restrict__ best, float* __restrict__ logits_out,
+                                                       int64_t out_stride, int n, int ntiles, int C) {
+  const int b = (int)blockIdx.x / ntiles, t0 = 32 * ((int)blockIdx.x % ntiles);
+  const int valid = n - t0 < 32 ? n - t0 : 32;
+  const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
+  const bool live = row < valid;
+  const int t = t0 + (live ? row : valid - 1);
+  reduce_rows(logits + ((int64_t)b * clip_rows + t) * ld, (int64_t)b * out_stride + t, live, C, codes, nll, best, logits_out,
+              sub);
+}
+
+int rows_args(const char* who, int32_t B, int32_t n, int32_t C, int64_t clip_rows, int64_t out_stride) {
+  if (C < 1 || C > kMaxClasses) return set_error(SRWN_E_SHAPE, "%s: %d classes (1..%d)", who, C, kMaxClasses);
+  if (B < 1 || n < 1) return set_error(SRWN_E_SHAPE, "%s: B=%d, a chunk of %d rows", who, B, n);
+  if (clip_rows < n || out_stride < n)
+    return set_error(SRWN_E_SHAPE, "%s: %d rows in buffers of %lld rows per stream, outputs of %lld", who, n,
+                     (long long)clip_rows, (long long)out_stride);
+  if ((int64_t)B * ((n + 31) / 32) > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "%s: too many tiles", who);
+  return 0;
+}
+
+template <typename T, int R, int S>
+int launch_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int L, const void* wskip,
+                      const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
+                      const int32_t* codes, float* nll, int32_t* best, float* logits_out, int64_t out_stride, int B, int n,
+                      int C, hipStream_t st) {
+  constexpr int sh = xch_bytes<T, S>() + kLogitBytes;
+  const int ntiles = (n + 31) / 32;
+  auto kfn = stream_score_head_kernel<T, R, S>;
+  if (sh > 32768) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
+  hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
+                     (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, codes, nll, best, logits_out, out_stride, n,
+                     ntiles, C);
+  return check_launch("stream_score_head");
+}
+
+}  // namespace
+
+extern "C" int srwn_stream_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                      const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                      const void* w2, const float* b2, const int32_t* codes, float* nll, int32_t* best,
+                                      float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t max_chunk,
+                                      int32_t R, int32_t S, int32_t C, int32_t dtype, void* stream) {
+  const char* who = "stream_score_head";
+  if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !codes || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if ((R != 32 && R != 64) || (S != 128 && S != 256))
+    return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
+  if (max_chunk < 1 || n > max_chunk || z_clip_rows < max_chunk)
+    return set_error(SRWN_E_SHAPE, "%s: a chunk of %d rows in buffers of %lld rows per stream (max_chunk = %d)", who, n,
+                     (long long)z_clip_rows, max_chunk);
+  if (const int rc = rows_args(who, B, n, C, z_clip_rows, out_stride)) return rc;
+  if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
+    return set_error(SRWN_E_SHAPE, "%s: %d layers at a stride of %lld", who, nlayers, (long long)z_layer_stride);
+  hipStream_t st = (hipStream_t)stream;
+#define SRWN_SSH(TT, RR, SS)                                                                                           \
+  return launch_score_head<TT, RR, SS>(z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2, codes, nll, \
+                                       best, logits_out, out_stride, B, n, C, st)
+#define SRWN_SSH_T(TT)                                       \
+  {                                                          \
+    if (R == 32 && S == 128) SRWN_SSH(TT, 32, 128);          \
+    else if (R == 32) SRWN_SSH(TT, 32, 256);                 \
+    else if (S == 128) SRWN_SSH(TT, 64, 128);                \
+    else SRWN_SSH(TT, 64, 256);                              \
+  }
+  if (dtype == SRWN_BF16) SRWN_SSH_T(bf16_t)
+  else if (dtype == SRWN_F32) SRWN_SSH_T(float)
+#undef SRWN_SSH_T
+#undef SRWN_SSH
+  return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+}
+
+extern "C" int srwn_nll_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const int32_t* codes,
+                             float* nll, int32_t* best, float* logits_out, int64_t out_stride, int32_t B, int32_t n,
+                             int32_t C, void* stream) {
+  const char* who = "nll_rows";
+  if (!logits || !codes || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (const int rc = rows_args(who, B, n, C, logits_clip_rows, out_stride)) return rc;
+  if (logits_ld < C) return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d classes", who, (long long)logits_ld, C);
+  const int ntiles = (n + 31) / 32;
+  hipLaunchKernelGGL(nll_rows_kernel, dim3((unsigned)(B * ntiles)), dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
+                     logits_clip_rows, codes, nll, best, logits_out, out_stride, n, ntiles, C);
+  return check_launch(who);
+}

@@ -9,6 +9,8 @@ wrappers, but no TensorFlow: the graph body is the fixed kernel sequence of ``en
                             model.py:100-112); this is the benchmark path.
 * ``WaveNetAutoEncoder`` -- model.py:75-285: non-causal encoder + conditioned mixture-of-logistics decoder
                             (encoder.AutoEncoderEngine), the teacher teacher.py trains.
+* ``StreamingScorer``    -- the softmax teacher's per-sample likelihood on its own (scorer.StreamScorer): any batch, any
+                            length, whole recordings or streams.
 * ``AudioEncoder``       -- that auto-encoder's encoder on its own (encoder.FrameEncoder): any batch, any length,
                             whole clips or streams.
 * ``ParallelWaveNet``    -- model.py:290-656: the IAF student distilled against that frozen teacher
@@ -304,6 +306,74 @@ class ClassifierStream(object):
         return tuple(o.cpu().numpy() for o in out) if return_logits else out.cpu().numpy()
 
 
+class StreamingScorer(object):
+    """The deployable likelihood scorer of the softmax ``WaveNetTeacher`` with a NumPy face: no training engine, no clip
+    length.  ``score(audio [B, T])`` -> nll [B, T] in nats, nll[b, t] = -log p(mu_law_encode(audio)[b, t] | audio[b, < t]),
+    for recordings of any length; ``stream(batch)`` -> a ``ScorerStream`` to ``push`` audio into as it arrives.  A value
+    does not depend on how the audio was cut."""
+
+    def __init__(self, weights, max_batch=1, max_chunk=1600):
+        from .scorer import StreamScorer
+        self._w = weights
+        self._eng = StreamScorer(weights, max_batch=max_batch, max_chunk=max_chunk)
+        self.max_batch, self.max_chunk = self._eng.max_batch, self._eng.max_chunk
+
+    @classmethod
+    def from_checkpoint(cls, logdir, dtype=None, max_batch=1, max_chunk=1600):
+        """A scorer on the variables ``WaveNetTeacher.save`` left in `logdir` (its config.json names the stack; the
+        checkpoint is this package's .pt form or a TensorFlow bundle, read by the reference's variable names)."""
+        import json
+        from types import SimpleNamespace
+        from .recognizer import check_classifier_widths
+        from .scorer import ScorerWeights
+        path = os.path.join(logdir, "config.json")
+        if not os.path.exists(path):
+            raise FileNotFoundError("%s: no config.json (save the teacher with WaveNetTeacher.save)" % logdir)
+        c = json.load(open(path))
+        ScorerWeights.check_config(SimpleNamespace(
+            head_mode="per_timestep" if c.get("head", "softmax") == "softmax" else "mol", gate_mode=c.get("gate_mode", "reference"),
+            cond_channels=(c["latent_channels"] + c["condition_size"]) if c.get("use_encoding") else 0, shift_input=True))
+        check_classifier_widths(c["filter_width"], c["dilation_channels"], c["skip_channels"], "streaming scorer")
+        w = ScorerWeights(c["dilations"], c["dilation_channels"], c["skip_channels"], c["quantization_channels"],
+                          c["filter_width"], dtype or _default_dtype())
+        if not w.load(logdir, c.get("name", "WaveNetTeacher")):
+            raise FileNotFoundError("%s: no checkpoint to restore (WaveNetTeacher.save writes one)" % logdir)
+        return cls(w, max_batch=max_batch, max_chunk=max_chunk)
+
+    @staticmethod
+    def _numpy(out):
+        return tuple(o.cpu().numpy() for o in out) if isinstance(out, tuple) else out.cpu().numpy()
+
+    def score(self, inputs, return_logits=False, return_best=False):
+        """inputs [B, T] -> nll [B, T] (NumPy, nats); with return_logits also the logits [B, T, C], with return_best also
+        the most likely code [B, T]."""
+        return self._numpy(self._eng.score(self._eng._check_audio(inputs), return_logits, return_best))
+
+    def stream(self, batch_size=1):
+        return ScorerStream(self, self._eng.start(batch_size))
+
+
+class ScorerStream(object):
+    """NumPy face of one running batch of scorer streams (``StreamingScorer.stream``).  ``t``: samples scored per
+    stream."""
+
+    def __init__(self, owner, state):
+        self._owner, self._st, self.batch_size = owner, state, state.B
+
+    @property
+    def t(self):
+        return self._st.t
+
+    def push(self, audio, return_logits=False, return_best=False):
+        """audio [B, n], any n >= 0 -> nll [B, n] of exactly those samples."""
+        return self._owner._numpy(self._owner._eng.push(self._st, audio, return_logits, return_best))
+
+    def bits_per_sample(self):
+        """Mean nll of everything pushed so far, in bits, per stream [B] (NaN before the first sample)."""
+        from .scorer import bits_per_sample
+        return np.array([bits_per_sample(v, self._st.t) for v in self._st.nll_sum.cpu().numpy()])
+
+
 class WaveNetTeacher(_EngineOwner):
     """The mu-law softmax teacher of BASELINE.json configs[1-2]: ``createDecoder``'s stack
     (model.py:158-196: RightShift teacher forcing, per-layer conditioning add) with a
@@ -404,6 +474,19 @@ class WaveNetTeacher(_EngineOwner):
         eng = self._stage(inputs, encoding, conditions)
         eng.forward()
         return np.float32(eng.loss.item())
+
+    def scorer(self, max_batch=1, max_chunk=1600):
+        """A ``StreamingScorer`` on a copy of this teacher's current weights: audio of any length in, nll[b, t] = -log
+        p(code[b, t] | audio[b, < t]) in nats out, one number per sample -- the quantity ``loss`` averages, without the
+        training engine.  The unconditioned softmax teacher with the reference gate only."""
+        from .recognizer import check_classifier_widths
+        from .scorer import ScorerWeights
+        ScorerWeights.check_config(self._cfg)
+        check_classifier_widths(self._cfg.filter_width, self._cfg.dilation_channels, self._cfg.skip_channels,
+                                "streaming scorer")
+        if self._primary is None:
+            self._engine(1, self._default_length)
+        return StreamingScorer(ScorerWeights.from_engine(self._primary), max_batch=max_batch, max_chunk=max_chunk)
 
     def generate(self, batch_size, num_samples, mode="sample", seed=0, forced=None, return_logits=False,
                  encoding=None, conditions=None, prompt=None, *, temperature=1.0, top_k=0, top_p=1.0):

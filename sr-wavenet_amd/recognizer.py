@@ -80,29 +80,39 @@ def check_hop_window(hop, window):
         raise ValueError("window %r must be a multiple of hop %r" % (window, hop))
 
 
-def check_classifier_widths(filter_width, dilation_channels, skip_channels):
+def check_classifier_widths(filter_width, dilation_channels, skip_channels, who="streaming classifier"):
     """What the streaming classifier's kernels are built for: refused before anything touches the device."""
     if filter_width != 2:
         raise NotImplementedError("filter_width %d: only 2 is built (reference default, model.py:9)" % filter_width)
     if dilation_channels not in (32, 64) or skip_channels not in (128, 256):
-        raise NotImplementedError("streaming classifier: dilation_channels %d x skip_channels %d; built for {32, 64} x "
-                                  "{128, 256}" % (dilation_channels, skip_channels))
+        raise NotImplementedError("%s: dilation_channels %d x skip_channels %d; built for {32, 64} x "
+                                  "{128, 256}" % (who, dilation_channels, skip_channels))
 
 
-class ClassifierWeights:
-    """The parameters and forward MFMA images of a ``WaveNet`` classifier without the training engine around it: the
-    engine's section layout and reference variable names, no activations, gradients or Adam state.  Built from a
-    ``WaveNet``'s engine (``from_engine``: a copy of its parameters) or filled from a checkpoint directory by the
-    reference's variable names (``load``: this package's .pt form or a TensorFlow bundle)."""
+class StackWeights:
+    """The parameters and forward MFMA images of an unconditioned reference-gate stack with its two head 1x1s, without
+    the training engine around it: the engine's section layout and reference variable names, no activations, gradients
+    or Adam state.  ``ClassifierWeights`` (below) and ``scorer.ScorerWeights`` are its two users; a subclass adds the
+    images its own head needs in ``_pack_head``."""
 
     view = WaveNetEngine.view
     wptr = WaveNetEngine.wptr
     named_tensors = WaveNetEngine.named_tensors
     wavenet, E = False, 0
+    _who = "streaming classifier"
+
+    def _pack_head(self, pk, secs):
+        """Further images behind the ones every user needs (registered on `pk` before it is finalized)."""
+
+    def _copy_engine(self, eng: WaveNetEngine):
+        for name in self.sections:
+            self.view(name).copy_(eng.view(name))
+        self.repack()
+        return self
 
     def __init__(self, dilations, dilation_channels: int = 32, skip_channels: int = 256, output_channels: int = 256,
                  filter_width: int = 2, dtype: torch.dtype = torch.bfloat16, device="cuda"):
-        check_classifier_widths(filter_width, dilation_channels, skip_channels)
+        check_classifier_widths(filter_width, dilation_channels, skip_channels, self._who)
         if not 1 <= int(output_channels) <= 256:
             raise NotImplementedError("output_channels must be in [1, 256]")
         if len(dilations) < 1 or min(int(d) for d in dilations) < 1:
@@ -133,6 +143,7 @@ class ClassifierWeights:
             P.fill_linear(pk, self.o_skip, secs["WS"].offset + l * R * S, R, S, S // 32, L * R // 16,
                           ks_offset=l * R // 16, ks_count=R // 16)
         self.o_w1 = P.pack_linear(pk, secs["head_w1"].offset, S, S, S)
+        self._pack_head(pk, secs)
         pk.finalize()
         self.packer = pk
         self.packed = torch.zeros(max(pk.total, 1), dtype=self.dt, device=self.dev)
@@ -164,6 +175,22 @@ class ClassifierWeights:
         self.params.copy_(host)
         self.repack()
 
+    def load(self, logdir, scope: str = "WaveNet") -> bool:
+        """Fills the parameters from the checkpoint that `logdir`'s state file names (``WaveNet.save`` or the reference's
+        tf.train.Saver wrote it), by the reference's variable names under `scope`."""
+        from .model import _read_state
+        ok = _read_state(logdir, lambda: self.tf_variables(scope))
+        if ok:
+            self.repack()
+        return bool(ok)
+
+
+class ClassifierWeights(StackWeights):
+    """The parameters and forward MFMA images of a ``WaveNet`` classifier without the training engine around it: the
+    engine's section layout and reference variable names, no activations, gradients or Adam state.  Built from a
+    ``WaveNet``'s engine (``from_engine``: a copy of its parameters) or filled from a checkpoint directory by the
+    reference's variable names (``load``: this package's .pt form or a TensorFlow bundle)."""
+
     @classmethod
     def from_engine(cls, eng: WaveNetEngine) -> "ClassifierWeights":
         """A copy of a pooled-head engine's parameters (``WaveNet._engine``); later training does not reach it."""
@@ -175,21 +202,8 @@ class ClassifierWeights:
             raise NotImplementedError("gate_mode %r is not built for the streaming classifier" % (cfg.gate_mode,))
         if cfg.shift_input or cfg.cond_channels:
             raise ValueError("the classifier's stack has no RightShift and no conditioning (model.py:33-62)")
-        w = cls(cfg.dilations, cfg.dilation_channels, cfg.skip_channels, cfg.output_channels, cfg.filter_width, cfg.dtype,
-                eng.dev)
-        for name, s in w.sections.items():
-            w.view(name).copy_(eng.view(name))
-        w.repack()
-        return w
-
-    def load(self, logdir, scope: str = "WaveNet") -> bool:
-        """Fills the parameters from the checkpoint that `logdir`'s state file names (``WaveNet.save`` or the reference's
-        tf.train.Saver wrote it), by the reference's variable names under `scope`."""
-        from .model import _read_state
-        ok = _read_state(logdir, lambda: self.tf_variables(scope))
-        if ok:
-            self.repack()
-        return bool(ok)
+        return cls(cfg.dilations, cfg.dilation_channels, cfg.skip_channels, cfg.output_channels, cfg.filter_width, cfg.dtype,
+                   eng.dev)._copy_engine(eng)
 
 
 class RecogState:
