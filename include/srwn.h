@@ -1209,7 +1209,12 @@ int srwn_mol_sample(const float* logits, int64_t ldl, int32_t M, const float* u1
  *                           every layer of the group for the chunk's own rows (never history or halo rows): chunk row t
  *                           of stream b of layer g at z_out + g * z_layer_stride + ((b * max_chunk) + t) * R, with the
  *                           bits srwn_residual_group_fwd gives that row on the whole clip.  z_layer_stride >= B *
- *                           max_chunk * R elements.  cond_next: NULL, or all entries NULL.
+ *                           max_chunk * R elements.  cond_next, cond_frames, pool_stride and
+ *                           cond_row_stride mean what they mean to srwn_residual_group_fwd_stream (since srwn_version()
+ *                           117; before: NULL only): the conditioning bias of the layer above layer g is added to layer
+ *                           g's output, on the halo rows the launch recomputes too, from the ring row of each row's frame.
+ *                           z is the tanh of a layer's filter conv and is stored for the chunk's own rows only, conditioned
+ *                           or not: a row's z depends on the conditioning through the layer's input alone.
  *   srwn_pooled_stream_head model.py:50-54 and the hop sums of a chunk of k hops in one launch, one workgroup per
  *                           (stream, hop): per 32-row tile of the hop, in time order (the last one masked when hop % 32
  *                           != 0), the gate c = z sigmoid(z) rebuilt from the stored z as srwn_pw_linear's SRWN_PRO_GATE
@@ -1359,6 +1364,43 @@ int srwn_stream_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip
                            void* stream);
 int srwn_nll_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const int32_t* codes, float* nll,
                   int32_t* best, float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t C, void* stream);
+
+/* ---- streaming likelihood scorer of the mixture-of-logistics decoder (since srwn_version() 117; csrc/srwn_score.hip): the
+ * conditioned decoder of class WaveNetAutoEncoder and the mixture-of-logistics WaveNetTeacher (createDecoder, model.py:
+ * 158-196, trained on discretized_mix_logistic_loss, ops.py:124-175) as an inference-only stream that leaves nll[t] = -log
+ * p(audio[t] | audio[< t], encoding) in nats for every row of a chunk.  The stack runs through srwn_flow_stream_in on the
+ * chunk's own audio (RightShift, the K = 2 entry conv and the first layer's conditioning bias at the device clock; its carry
+ * [B][2] = the two samples before the chunk, staged by the caller), one srwn_residual_group_fwd_stream_z per layer group with
+ * cond_next set, and srwn_recog_roll.  The conditioning table is a ring [B * cond_frames][nlayers * R] (dtype), frame q of
+ * stream b in row b * cond_frames + q mod cond_frames, fed by srwn_pw_linear and srwn_cond_ring_scatter; the group launches
+ * recompute their halo rows with their conditioning, so the room rule is the live synthesizer's (110 above): after `fed`
+ * frames a stream at time t has room for max(0, cond_frames - fed + max(t - hist_max, 0) / pool_stride) more, hist_max the
+ * largest history of the plan's groups.  1 <= M <= 16 mixtures: the 4M logits are Cp = 32 or 64 columns.
+ *
+ *   srwn_stream_mol_score_head  srwn_stream_score_head through the logits (one device body serves both kernels: the same
+ *                           workgroups, fragment maps, k order and barriers), logits = W2 r1 + b2 in fp32 in LDS, then per
+ *                           row the mixture-of-logistics negative log-likelihood of the TARGET sample x[b][t] (x [B][x_stride]
+ *                           fp32, the chunk's own audio, not delayed) in srwn_mol_nll_rows' per-mixture arithmetic (the
+ *                           branches on x < -0.999 / x > 0.999 / cdf_delta > 1e-5, max(log_scale, -7), the half bin 1/255,
+ *                           log 127.5): 8 lanes per row, lane j on the mixtures j and j + 8 below M, the log-softmax of the
+ *                           mixture logits and the final log-sum-exp joined by an xor butterfly.  Columns [3M, Cp) are never
+ *                           read by the reduction.  w2: the packed image [Cp/32][S/16] of the last 1x1, rows behind 4M zero;
+ *                           b2 [Cp] fp32.  Outputs, row t of stream b at b * out_stride + t: nll fp32; logits_out (NULL: not
+ *                           wanted) fp32 [B][out_stride][4M].  Rows [n, out_stride) of a stream are not touched.  Dynamic
+ *                           LDS: 32 x (S + 16 / sizeof(dtype)) elements of dtype and 32 x 68 fp32.
+ *   srwn_mol_score_rows     the parity twin of the head's last step: the same reduction, by the same device routine on the
+ *                           same lane-to-mixture map, of logits [B][logits_clip_rows][logits_ld] fp32 (logits_ld >= 4M) that
+ *                           three srwn_pw_linear calls wrote (the last with SRWN_EPI_F32): nll and logits_out have the bits
+ *                           of srwn_stream_mol_score_head.
+ * Errors: a null pointer (-3; logits_out may be NULL), a width that is not built (-4), M outside [1, 16], B < 1, n < 1 or a
+ * chunk or buffer that does not fit (-2), dtype (-1); all before any launch. */
+int srwn_stream_mol_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                               const void* wskip, const float* bs_sum, const void* w1, const float* b1, const void* w2,
+                               const float* b2, const float* x, int64_t x_stride, float* nll, float* logits_out,
+                               int64_t out_stride, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t S, int32_t M,
+                               int32_t dtype, void* stream);
+int srwn_mol_score_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const float* x, int64_t x_stride,
+                        float* nll, float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t M, void* stream);
 
 #ifdef __cplusplus
 }

@@ -267,6 +267,10 @@ SIGNATURES["srwn_recog_roll_slots"] = (C.c_int, [_p, _i32, _p, _i32, _i32, _i32,
 SIGNATURES["srwn_stream_score_head"] = (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i32,
                                                   _i32, _i32, _i32, _i32, _i32, _i32, _p])
 SIGNATURES["srwn_nll_rows"] = (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _i32, _i32, _i32, _p])
+# its mixture-of-logistics form (srwn_version() 117): the target audio [B][x_stride] in the place of the codes, no `best`
+SIGNATURES["srwn_stream_mol_score_head"] = (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64,
+                                                      _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p])
+SIGNATURES["srwn_mol_score_rows"] = (C.c_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

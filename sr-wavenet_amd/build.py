@@ -28,7 +28,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-faile
 # been reused for a pointer (seen on a prototype: HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION).  The build refuses them.
 # Kernels listed here are also held to zero scratch: the contrastive head (csrc/srwn_siamese.hip) and the canonical-gate
 # layer kernels (csrc/srwn_wngate.hip) keep every value in registers or LDS, and the build refuses an object in which they
-# do not.
+# do not.  A name guards every kernel whose mangled name contains it: "stream_score_head_kernel" holds the softmax score
+# head and mol_stream_score_head_kernel, the mixture-of-logistics one, to the same rule.
 NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"], "srwn_siamese.hip": ["contrastive_head_kernel"],
             "srwn_wngate.hip": ["wavenet_layer_fwd_kernel", "wavenet_layer_bwd_kernel"],
             "srwn_ncstream.hip": ["nc_encode_frames_kernel", "nc_encode_frames_kernelINS_10NcListArgs"],

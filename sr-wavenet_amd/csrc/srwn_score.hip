@@ -11,6 +11,12 @@
 // Both reduce a row with ONE device routine, row_nll, on the same lane-to-column map, and both forms of the three products
 // start at the bias and take their k-steps in order: the two paths give the same bits.  A row depends on its own z rows
 // only, so a stream has the same bits in any chunking, at any batch size and in any row of the batch.
+//
+// The conditioned mixture-of-logistics decoder (createDecoder with the encoding, model.py:158-196, trained on
+// discretized_mix_logistic_loss, ops.py:124-175; srwn_version() 117) has the same two forms with another last step:
+//   mol score head   the score head through the logits (ONE device body, score_head_logits, serves both kernels; the 4M
+//                    logits are Cp = 32 or 64 columns in a small LDS block), then row_mol_nll on the undelayed audio
+//   mol score rows   its parity twin, row_mol_nll on a logits buffer in HBM
 #include <cmath>
 #include "srwn_common.h"
 #include "srwn_host.h"
@@ -23,6 +29,8 @@ namespace {
 constexpr int kRowLanes = 8;                  // lanes that share a row of logits in row_nll
 constexpr int kMaxClasses = 256;
 constexpr int kLogitStride = kMaxClasses + 4; // fp32 elements per row of the LDS logits block (16-byte rows, banks 4 apart)
+constexpr int kMaxMixtures = 16;              // 4M <= 64 columns: two 32-column tiles, two mixtures per lane of row_mol_nll
+constexpr int kMolStride = 4 * kMaxMixtures + 4;      // the same rule for the mixture head's LDS logits block
 
 // ------------------------------------------------------------------------------------------
 // One row of logits -> nll = log(sum_c exp(l[c] - max)) + max - l[code] and the argmax (lowest index on ties), over the
@@ -73,6 +81,72 @@ __device__ __forceinline__ void reduce_rows(const float* logits_row, int64_t oro
 }
 
 // ------------------------------------------------------------------------------------------
+// One row of the mixture-of-logistics head: l = (logit_probs [M], means [M], log_scales [M], coeffs [M]) and the target
+// sample xv -> nll = -log_sum_exp_m(log p_m(xv) + log_softmax(logit_probs)_m)  (ops.py:124-175 with sum_all = False), in
+// mol_nll_rows_kernel's per-mixture arithmetic (srwn_ops.hip: the four tf.where branches, the log-scale floor -7, the half
+// bin 1/255, log 127.5).  Called by the 8 lanes of a row's group, lane `sub` of it: lane sub owns the mixtures sub and
+// sub + 8 below M (M <= 16), in that order, and the lanes' values meet in row_nll's xor butterfly (1, 2, 4).  A lane
+// without a mixture brings -inf to a max and nothing to a sum, and never subtracts from its -inf.  The columns from 3M on
+// (the coeffs, unused for one audio channel, and the tile's padding) are never read.  The same value in all 8 lanes.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float mol_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+__device__ __forceinline__ float mol_softplus(float v) { return v > 0.0f ? v + log1pf(expf(-v)) : log1pf(expf(v)); }
+
+// log p_m(xv) of one mixture component (ops.py:147-169)
+__device__ __forceinline__ float mol_component(float xv, float mean, float raw_log_scale) {
+  const float ls = fmaxf(raw_log_scale, -7.0f);
+  const float cx = xv - mean, inv = expf(-ls);
+  const float plus_in = inv * (cx + 1.0f / 255.0f), min_in = inv * (cx - 1.0f / 255.0f), mid_in = inv * cx;
+  const float cdf_delta = mol_sigmoid(plus_in) - mol_sigmoid(min_in);
+  if (xv < -0.999f) return plus_in - mol_softplus(plus_in);
+  if (xv > 0.999f) return -mol_softplus(min_in);
+  if (cdf_delta > 1e-5f) return logf(fmaxf(cdf_delta, 1e-12f));
+  return mid_in - ls - 2.0f * mol_softplus(mid_in) - logf(127.5f);
+}
+
+__device__ __forceinline__ float butterfly_max(float v) {
+#pragma unroll
+  for (int s = 1; s < kRowLanes; s <<= 1) v = fmaxf(v, __shfl_xor(v, s, 64));
+  return v;
+}
+__device__ __forceinline__ float butterfly_sum(float v) {
+#pragma unroll
+  for (int s = 1; s < kRowLanes; s <<= 1) v += __shfl_xor(v, s, 64);
+  return v;
+}
+
+__device__ __forceinline__ float row_mol_nll(const float* l, int M, float xv, int sub) {
+  const bool has0 = sub < M, has1 = sub + kRowLanes < M;
+  const float p0 = has0 ? l[sub] : -INFINITY, p1 = has1 ? l[sub + kRowLanes] : -INFINITY;
+  // log-softmax of the mixture logits (lane 0 always owns mixture 0: the max is finite)
+  const float mp = butterfly_max(fmaxf(p0, p1));
+  float sp = 0.0f;
+  if (has0) sp += expf(p0 - mp);
+  if (has1) sp += expf(p1 - mp);
+  const float lsp = mp + logf(butterfly_sum(sp));
+  float v0 = -INFINITY, v1 = -INFINITY;
+  if (has0) v0 = mol_component(xv, l[M + sub], l[2 * M + sub]) + (p0 - lsp);
+  if (has1) v1 = mol_component(xv, l[M + sub + kRowLanes], l[2 * M + sub + kRowLanes]) + (p1 - lsp);
+  const float best = butterfly_max(fmaxf(v0, v1));
+  float s = 0.0f;
+  if (has0) s += expf(v0 - best);
+  if (has1) s += expf(v1 - best);
+  return -(best + logf(butterfly_sum(s)));
+}
+
+// reduce_rows for the mixture head: thread (row, sub) reduces row t0 + row of stream b on the target sample x[xrow]; a row
+// beyond the chunk is reduced like the chunk's last row and stores nothing.  logits_out takes the 4M real columns.
+__device__ __forceinline__ void reduce_mol_rows(const float* logits_row, int64_t orow, int64_t xrow, bool live, int M,
+                                                const float* __restrict__ x, float* __restrict__ nll,
+                                                float* __restrict__ logits_out, int sub) {
+  const float v = row_mol_nll(logits_row, M, x[xrow], sub);
+  if (!live) return;
+  if (sub == 0) nll[orow] = v;
+  if (logits_out)
+    for (int c = sub; c < 4 * M; c += kRowLanes) logits_out[orow * (4 * M) + c] = logits_row[c];
+}
+
+// ------------------------------------------------------------------------------------------
 // score head.  Workgroup = (stream b, tile i of the chunk's ceil(n / 32) tiles), 4 waves; wave w owns the output channels
 // [w * S/4, (w + 1) * S/4) of the first two products and the 32-column tiles w, w + 4 of the logits.  In pooled_stream_head's
 // arithmetic (srwn_recog.hip):
@@ -89,23 +163,19 @@ __device__ __forceinline__ void reduce_rows(const float* logits_row, int64_t oro
 template <typename T, int S> constexpr int xch_bytes() { return 32 * RowStage<T>::stride(S) * (int)sizeof(T); }
 constexpr int kLogitBytes = 32 * kLogitStride * (int)sizeof(float);
 
-template <typename T, int R, int S>
-__global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
-                                                                 int64_t z_clip_rows, int L, const T* __restrict__ wskip,
-                                                                 const float* __restrict__ bs_sum,
-                                                                 const T* __restrict__ w1, const float* __restrict__ b1,
-                                                                 const T* __restrict__ w2, const float* __restrict__ b2,
-                                                                 const int32_t* __restrict__ codes,
-                                                                 float* __restrict__ nll, int32_t* __restrict__ best,
-                                                                 float* __restrict__ logits_out, int64_t out_stride, int n,
-                                                                 int ntiles, int C) {
+// The body both heads share, through the logits: every thread of the workgroup calls it; afterwards (a barrier inside) lg
+// holds the tile's 32 rows of ctiles * 32 logits at a row stride of LGS floats.  *b_out, *t0_out, *valid_out: the stream,
+// the tile's first chunk row and its rows inside the chunk.
+template <typename T, int R, int S, int LGS>
+__device__ __forceinline__ void score_head_logits(const T* __restrict__ z, int64_t z_layer_stride, int64_t z_clip_rows, int L,
+                                                  const T* __restrict__ wskip, const float* __restrict__ bs_sum,
+                                                  const T* __restrict__ w1, const float* __restrict__ b1,
+                                                  const T* __restrict__ w2, const float* __restrict__ b2, int n, int ntiles,
+                                                  int ctiles, T* xch, float* lg, int* b_out, int* t0_out, int* valid_out) {
   constexpr int MTW = S / 128;                // 32-channel output tiles per wave
   constexpr int KSL = R / 16;                 // k-steps per layer
   constexpr int KS1 = S / 16;
   constexpr int LS = RowStage<T>::stride(S);
-  extern __shared__ __attribute__((aligned(16))) char score_lds[];
-  T* xch = reinterpret_cast<T*>(score_lds);
-  float* lg = reinterpret_cast<float*>(score_lds + xch_bytes<T, S>());
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int col = lane & 31, half = lane >> 5;
   const int b = (int)blockIdx.x / ntiles, t0 = 32 * ((int)blockIdx.x % ntiles);
@@ -157,8 +227,8 @@ __global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restr
       store4(xch + col * LS + 32 * (wave * MTW + mt) + 8 * g + 4 * half, fmaxf(acc[mt][4 * g], 0.0f),
              fmaxf(acc[mt][4 * g + 1], 0.0f), fmaxf(acc[mt][4 * g + 2], 0.0f), fmaxf(acc[mt][4 * g + 3], 0.0f));
   __syncthreads();
-  const int ctiles = (C + 31) / 32;
-  for (int mt = wave; mt < ctiles; mt += 4) { // (wave-uniform)
+  for (int mt = wave; mt < ctiles; mt += 4) { // (wave-uniform; the mixture head's ctiles <= 2: two waves idle here, and k is
+    // NOT split across them -- that would change the summation order and lose the parity twin)
     const Frag<T>* wl = reinterpret_cast<const Frag<T>*>(w2) + (size_t)mt * KS1 * 64 + lane;
     f32x16 a2;
 #pragma unroll
@@ -167,13 +237,62 @@ __global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restr
     for (int ks = 0; ks < KS1; ++ks) mma(a2, wl[(size_t)ks * 64], load_nat(xch + col * LS + 16 * ks + 8 * half));
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-      store4(lg + col * kLogitStride + 32 * mt + 8 * g + 4 * half, a2[4 * g], a2[4 * g + 1], a2[4 * g + 2], a2[4 * g + 3]);
+      store4(lg + col * LGS + 32 * mt + 8 * g + 4 * half, a2[4 * g], a2[4 * g + 1], a2[4 * g + 2], a2[4 * g + 3]);
   }
   __syncthreads();
+  *b_out = b; *t0_out = t0; *valid_out = valid;
+}
+
+template <typename T, int R, int S>
+__global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
+                                                                 int64_t z_clip_rows, int L, const T* __restrict__ wskip,
+                                                                 const float* __restrict__ bs_sum,
+                                                                 const T* __restrict__ w1, const float* __restrict__ b1,
+                                                                 const T* __restrict__ w2, const float* __restrict__ b2,
+                                                                 const int32_t* __restrict__ codes,
+                                                                 float* __restrict__ nll, int32_t* __restrict__ best,
+                                                                 float* __restrict__ logits_out, int64_t out_stride, int n,
+                                                                 int ntiles, int C) {
+  extern __shared__ __attribute__((aligned(16))) char score_lds[];
+  T* xch = reinterpret_cast<T*>(score_lds);
+  float* lg = reinterpret_cast<float*>(score_lds + xch_bytes<T, S>());
+  int b, t0, valid;
+  score_head_logits<T, R, S, kLogitStride>(z, z_layer_stride, z_clip_rows, L, wskip, bs_sum, w1, b1, w2, b2, n, ntiles,
+                                           (C + 31) / 32, xch, lg, &b, &t0, &valid);
   const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
   const bool live = row < valid;
   const int64_t orow = (int64_t)b * out_stride + t0 + (live ? row : valid - 1);
   reduce_rows(lg + row * kLogitStride, orow, live, C, codes, nll, best, logits_out, sub);
+}
+
+// ------------------------------------------------------------------------------------------
+// mol score head: the score head with the mixture-of-logistics reduction.  logits = b2 + W2 . r1 stay fp32 (the means must
+// resolve 1/255 bins) in lg[32][kMolStride]: the Cp / 32 <= 2 column tiles of the 4M logits, waves 0 and 1.  x [B][x_stride]
+// fp32 is the chunk's own audio (the target of row t is x[t], NOT delayed).
+// Dynamic LDS: xch as above, then lg = 32 x 68 x 4 = 8 704 bytes.
+// ------------------------------------------------------------------------------------------
+constexpr int kMolLogitBytes = 32 * kMolStride * (int)sizeof(float);
+
+template <typename T, int R, int S>
+__global__ __launch_bounds__(256) void mol_stream_score_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
+                                                                     int64_t z_clip_rows, int L, const T* __restrict__ wskip,
+                                                                     const float* __restrict__ bs_sum,
+                                                                     const T* __restrict__ w1, const float* __restrict__ b1,
+                                                                     const T* __restrict__ w2, const float* __restrict__ b2,
+                                                                     const float* __restrict__ x, int64_t x_stride,
+                                                                     float* __restrict__ nll, float* __restrict__ logits_out,
+                                                                     int64_t out_stride, int n, int ntiles, int M) {
+  extern __shared__ __attribute__((aligned(16))) char score_lds[];
+  T* xch = reinterpret_cast<T*>(score_lds);
+  float* lg = reinterpret_cast<float*>(score_lds + xch_bytes<T, S>());
+  int b, t0, valid;
+  score_head_logits<T, R, S, kMolStride>(z, z_layer_stride, z_clip_rows, L, wskip, bs_sum, w1, b1, w2, b2, n, ntiles,
+                                         (4 * M + 31) / 32, xch, lg, &b, &t0, &valid);
+  const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
+  const bool live = row < valid;
+  const int t = t0 + (live ? row : valid - 1);
+  reduce_mol_rows(lg + row * kMolStride, (int64_t)b * out_stride + t, (int64_t)b * x_stride + t, live, M, x, nll, logits_out,
+                  sub);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -191,6 +310,20 @@ __global__ __launch_bounds__(256) void nll_rows_kernel(const float* __restrict__
   const int t = t0 + (live ? row : valid - 1);
   reduce_rows(logits + ((int64_t)b * clip_rows + t) * ld, (int64_t)b * out_stride + t, live, C, codes, nll, best, logits_out,
               sub);
+}
+
+// mol score rows (parity twin): nll_rows_kernel's grid and thread-to-row map, row_mol_nll on the row in HBM.
+__global__ __launch_bounds__(256) void mol_score_rows_kernel(const float* __restrict__ logits, int64_t ld, int64_t clip_rows,
+                                                             const float* __restrict__ x, int64_t x_stride,
+                                                             float* __restrict__ nll, float* __restrict__ logits_out,
+                                                             int64_t out_stride, int n, int ntiles, int M) {
+  const int b = (int)blockIdx.x / ntiles, t0 = 32 * ((int)blockIdx.x % ntiles);
+  const int valid = n - t0 < 32 ? n - t0 : 32;
+  const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
+  const bool live = row < valid;
+  const int t = t0 + (live ? row : valid - 1);
+  reduce_mol_rows(logits + ((int64_t)b * clip_rows + t) * ld, (int64_t)b * out_stride + t, (int64_t)b * x_stride + t, live, M,
+                  x, nll, logits_out, sub);
 }
 
 int rows_args(const char* who, int32_t B, int32_t n, int32_t C, int64_t clip_rows, int64_t out_stride) {
@@ -216,6 +349,27 @@ int launch_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows
                      (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, codes, nll, best, logits_out, out_stride, n,
                      ntiles, C);
   return check_launch("stream_score_head");
+}
+
+int mol_rows_args(const char* who, int32_t B, int32_t n, int32_t M, int64_t clip_rows, int64_t x_stride, int64_t out_stride) {
+  if (M < 1 || M > kMaxMixtures) return set_error(SRWN_E_SHAPE, "%s: %d mixtures (1..%d)", who, M, kMaxMixtures);
+  if (x_stride < n) return set_error(SRWN_E_SHAPE, "%s: %d rows of audio at a stride of %lld", who, n, (long long)x_stride);
+  return rows_args(who, B, n, 4 * M, clip_rows, out_stride);
+}
+
+template <typename T, int R, int S>
+int launch_mol_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int L, const void* wskip,
+                          const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
+                          const float* x, int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int B, int n,
+                          int M, hipStream_t st) {
+  constexpr int sh = xch_bytes<T, S>() + kMolLogitBytes;
+  const int ntiles = (n + 31) / 32;
+  auto kfn = mol_stream_score_head_kernel<T, R, S>;
+  if (sh > 32768) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
+  hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
+                     (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, x, x_stride, nll, logits_out, out_stride, n,
+                     ntiles, M);
+  return check_launch("stream_mol_score_head");
 }
 
 }  // namespace
@@ -263,5 +417,51 @@ extern "C" int srwn_nll_rows(const float* logits, int64_t logits_ld, int64_t log
   const int ntiles = (n + 31) / 32;
   hipLaunchKernelGGL(nll_rows_kernel, dim3((unsigned)(B * ntiles)), dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
                      logits_clip_rows, codes, nll, best, logits_out, out_stride, n, ntiles, C);
+  return check_launch(who);
+}
+
+extern "C" int srwn_stream_mol_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                          const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                          const void* w2, const float* b2, const float* x, int64_t x_stride, float* nll,
+                                          float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t max_chunk,
+                                          int32_t R, int32_t S, int32_t M, int32_t dtype, void* stream) {
+  const char* who = "stream_mol_score_head";
+  if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !x || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if ((R != 32 && R != 64) || (S != 128 && S != 256))
+    return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
+  if (max_chunk < 1 || n > max_chunk || z_clip_rows < max_chunk)
+    return set_error(SRWN_E_SHAPE, "%s: a chunk of %d rows in buffers of %lld rows per stream (max_chunk = %d)", who, n,
+                     (long long)z_clip_rows, max_chunk);
+  if (const int rc = mol_rows_args(who, B, n, M, z_clip_rows, x_stride, out_stride)) return rc;
+  if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
+    return set_error(SRWN_E_SHAPE, "%s: %d layers at a stride of %lld", who, nlayers, (long long)z_layer_stride);
+  hipStream_t st = (hipStream_t)stream;
+#define SRWN_MSH(TT, RR, SS)                                                                                              \
+  return launch_mol_score_head<TT, RR, SS>(z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2, x,     \
+                                           x_stride, nll, logits_out, out_stride, B, n, M, st)
+#define SRWN_MSH_T(TT)                                       \
+  {                                                          \
+    if (R == 32 && S == 128) SRWN_MSH(TT, 32, 128);          \
+    else if (R == 32) SRWN_MSH(TT, 32, 256);                 \
+    else if (S == 128) SRWN_MSH(TT, 64, 128);                \
+    else SRWN_MSH(TT, 64, 256);                              \
+  }
+  if (dtype == SRWN_BF16) SRWN_MSH_T(bf16_t)
+  else if (dtype == SRWN_F32) SRWN_MSH_T(float)
+#undef SRWN_MSH_T
+#undef SRWN_MSH
+  return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+}
+
+extern "C" int srwn_mol_score_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const float* x,
+                                   int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int32_t B, int32_t n,
+                                   int32_t M, void* stream) {
+  const char* who = "mol_score_rows";
+  if (!logits || !x || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (const int rc = mol_rows_args(who, B, n, M, logits_clip_rows, x_stride, out_stride)) return rc;
+  if (logits_ld < 4 * M) return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d mixtures", who, (long long)logits_ld, M);
+  const int ntiles = (n + 31) / 32;
+  hipLaunchKernelGGL(mol_score_rows_kernel, dim3((unsigned)(B * ntiles)), dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
+                     logits_clip_rows, x, x_stride, nll, logits_out, out_stride, n, ntiles, M);
   return check_launch(who);
 }

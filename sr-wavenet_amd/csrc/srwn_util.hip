@@ -25,7 +25,7 @@ int check_launch(const char* what) {
 }
 }  // namespace srwn
 
-extern "C" int srwn_version(void) { return 116; }
+extern "C" int srwn_version(void) { return 117; }
 extern "C" const char* srwn_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------------

@@ -374,6 +374,201 @@ class ScorerStream(object):
         return np.array([bits_per_sample(v, self._st.t) for v in self._st.nll_sum.cpu().numpy()])
 
 
+class _MolScorerFace(object):
+    """What ``StreamingMolScorer`` and ``AutoEncoderScorer`` share: a ``scorer.MolStreamScorer`` ``_eng`` on a snapshot of
+    decoder weights ``_w``, and the tiling of clip-level conditions onto encoding frames (``with_conditions``)."""
+
+    def _setup(self, weights, latent_channels, condition_size, max_batch, max_chunk, max_frames):
+        from .scorer import MolStreamScorer
+        self._w = weights
+        self.latent_channels, self.condition_size = int(latent_channels), int(condition_size)
+        self._eng = MolStreamScorer(weights, max_batch=max_batch, max_chunk=max_chunk, max_frames=max_frames)
+        self.max_batch, self.max_chunk, self.max_frames = self._eng.max_batch, self._eng.max_chunk, self._eng.max_frames
+        self.pool_stride, self.conditioned = self._eng.pool, bool(self._eng.E)
+
+    def _conditions(self, batch, conditions):
+        """conditions [B, condition_size] on the device, or None (no device work before the refusals)."""
+        if not self.conditioned:
+            if conditions is not None:
+                raise ValueError("this decoder is not conditioned")
+            return None
+        c = _check_conditions(batch, conditions, self.condition_size, "scorer")
+        return None if c is None else torch.as_tensor(c, device="cuda")
+
+    def _frames(self, encoding, cond):
+        """encoding [B, k, latent] (NumPy or device) -> the conditioning frames [B, k, latent + condition_size] (device)."""
+        e = torch.as_tensor(encoding, dtype=torch.float32)
+        if e.dim() != 3 or e.shape[2] != self.latent_channels:
+            raise ValueError("encoding must be [batch, frames, latent_channels=%d], got %s"
+                             % (self.latent_channels, tuple(e.shape)))
+        e = e.to("cuda")
+        return e if cond is None else _tile_conditions(e, cond)
+
+    def _score(self, inputs, encoding, conditions, return_logits):
+        x = self._eng._check_audio(inputs)
+        enc = None
+        if self.conditioned:
+            if encoding is None:
+                raise ValueError("this decoder is conditioned: pass encoding [batch, samples / pool_stride, %d]"
+                                 % self.latent_channels)
+            enc = self._frames(encoding, self._conditions(int(x.shape[0]), conditions))
+        elif encoding is not None or conditions is not None:
+            raise ValueError("this decoder is not conditioned")
+        out = self._eng.score(x, enc, return_logits)
+        return tuple(o.cpu().numpy() for o in out) if return_logits else out.cpu().numpy()
+
+
+class _MolScoreStreamBase(object):
+    """NumPy face of one running batch of mixture-of-logistics scorer streams.  ``t``: samples scored per stream."""
+
+    def __init__(self, owner, batch_size, conditions):
+        self._owner, self.batch_size = owner, int(batch_size)
+        self._cond = owner._conditions(self.batch_size, conditions)      # (its refusals come before any device work)
+        self._st = owner._eng.start(self.batch_size)
+
+    t = property(lambda self: self._st.t)
+    fed = property(lambda self: self._st.fed)
+
+    def bits_per_sample(self):
+        """Mean nll of everything scored so far, in bits, per stream [B] (NaN before the first sample)."""
+        from .scorer import bits_per_sample
+        return np.array([bits_per_sample(v, self._st.t) for v in self._st.nll_sum.cpu().numpy()])
+
+
+class StreamingMolScorer(_MolScorerFace):
+    """The deployable likelihood scorer of the mixture-of-logistics ``WaveNetTeacher`` (the model the student distils
+    from), conditioned or not, with a NumPy face: ``score(inputs [B, T], encoding, conditions)`` -> nll [B, T] in nats,
+    nll[b, t] = -log p(inputs[b, t] | inputs[b, < t], encoding); ``stream(batch, conditions)`` -> a ``MolScorerStream`` to
+    ``feed`` frames and ``push`` audio into as they arrive.  A value does not depend on how audio and frames were cut."""
+
+    def __init__(self, weights, latent_channels=0, condition_size=0, max_batch=1, max_chunk=1600, max_frames=32):
+        self._setup(weights, latent_channels, condition_size, max_batch, max_chunk, max_frames)
+
+    def score(self, inputs, encoding=None, conditions=None, return_logits=False):
+        """inputs [B, T] (T = frames * pool_stride for a conditioned teacher) -> nll [B, T] (NumPy, nats); with
+        return_logits also the logits [B, T, 4 * num_mixtures]."""
+        return self._score(inputs, encoding, conditions, return_logits)
+
+    def stream(self, batch_size=1, conditions=None):
+        return MolScorerStream(self, batch_size, conditions)
+
+
+class MolScorerStream(_MolScoreStreamBase):
+    """``StreamingMolScorer.stream``: ``feed(encoding [B, k, latent])`` hands every stream its next k <= ``room`` frames,
+    ``push(audio [B, n])`` scores the next n <= ``available`` samples (an unconditioned teacher: any n, nothing to feed)."""
+
+    room = property(lambda self: self._owner._eng.room(self._st))
+    available = property(lambda self: self._owner._eng.available(self._st))
+
+    def feed(self, encoding):
+        if not self._owner.conditioned:
+            raise ValueError("feed: this teacher is not conditioned")
+        self._owner._eng.feed(self._st, self._owner._frames(encoding, self._cond))
+
+    def push(self, audio, return_logits=False):
+        out = self._owner._eng.push(self._st, audio, return_logits)
+        return tuple(o.cpu().numpy() for o in out) if return_logits else out.cpu().numpy()
+
+
+class AutoEncoderScorer(_MolScorerFace):
+    """The whole ``WaveNetAutoEncoder`` as a likelihood meter: an ``AudioEncoder`` (a snapshot of the encoder) feeding a
+    ``scorer.MolStreamScorer`` on a snapshot of the decoder -- audio in, nll[b, t] = -log p(audio[b, t] | audio[b, < t],
+    encode(audio)) in nats out, the number the auto-encoder is trained on, for recordings of any length.  ``score`` scores
+    the (T // pool_stride) * pool_stride samples whose frames exist; ``stream`` does so as the audio arrives, a sample as
+    soon as the encoder has completed its frame, with the same bits however the audio was cut."""
+
+    def __init__(self, encoder, weights, condition_size=0, max_batch=1, max_chunk=1600, max_frames=32):
+        if not isinstance(encoder, AudioEncoder):
+            raise TypeError("AutoEncoderScorer(encoder: AudioEncoder, weights: scorer.MolScorerWeights)")
+        if int(encoder.pool_stride) != int(weights.pool) or weights.E != encoder.latent_channels + int(condition_size):
+            raise ValueError("the encoder gives %d-channel frames per %d samples, the decoder takes %d channels (%d of "
+                             "them conditions) per %d" % (encoder.latent_channels, encoder.pool_stride, weights.E,
+                                                          int(condition_size), weights.pool))
+        self.encoder = encoder
+        self._setup(weights, encoder.latent_channels, condition_size, max_batch, max_chunk, max_frames)
+
+    @classmethod
+    def from_checkpoint(cls, logdir, dtype=None, max_batch=1, max_chunk=1600, max_frames=32):
+        """A scorer on the variables ``WaveNetAutoEncoder.save`` left in `logdir` (its config.json names both halves)."""
+        import json
+        from .scorer import MolScorerWeights
+        path = os.path.join(logdir, "config.json")
+        if not os.path.exists(path):
+            raise FileNotFoundError("%s: no config.json (save the model with WaveNetAutoEncoder.save)" % logdir)
+        c = json.load(open(path))
+        dt = dtype or _default_dtype()
+        enc = AudioEncoder.from_checkpoint(logdir, dtype=dt, max_batch=max_batch, max_frames=max_frames)
+        w = MolScorerWeights(c["dilations"], c["dilation_channels"], c["skip_channels"], c["num_mixtures"],
+                             c["latent_channels"] + c["condition_size"], c["pool_stride"], c["filter_width"], dt)
+        if not w.load(logdir, c.get("name", "WaveNetAutoEncoder") + "/Decoder"):
+            raise FileNotFoundError("%s: no checkpoint to restore (WaveNetAutoEncoder.save writes one)" % logdir)
+        return cls(enc, w, c["condition_size"], max_batch=max_batch, max_chunk=max_chunk, max_frames=max_frames)
+
+    def score_with_encoding(self, inputs, encoding, conditions=None, return_logits=False):
+        """inputs [B, frames * pool_stride], encoding [B, frames, latent_channels] -> nll (NumPy, nats)."""
+        return self._score(inputs, encoding, conditions, return_logits)
+
+    def score(self, inputs, conditions=None, return_logits=False):
+        """inputs [B, T] of any T -> nll [B, (T // pool_stride) * pool_stride] under the encoding of the inputs."""
+        x = self.encoder._check(inputs)
+        enc = self.encoder._eng.encode(torch.as_tensor(x))
+        return self._score(x[:, :int(enc.shape[1]) * self.pool_stride], enc, conditions, return_logits)
+
+    def stream(self, batch_size=1, conditions=None):
+        if not 1 <= int(batch_size) <= min(self.max_batch, self.encoder.max_batch):
+            raise ValueError("batch_size %r: this scorer holds %d streams" % (batch_size, min(self.max_batch, self.encoder.max_batch)))
+        return AutoEncoderScoreStream(self, int(batch_size), conditions)
+
+
+class AutoEncoderScoreStream(_MolScoreStreamBase):
+    """``AutoEncoderScorer.stream``: ``push(audio [B, n])``, any n, returns the nll of every sample whose frame the encoder
+    has completed by now ([B, m], m >= 0); audio that cannot be scored yet waits on the device.  ``finish()`` returns the
+    rest (the encoder's last whole frames, with its clip-end padding) and closes the stream.  ``received``: samples
+    pushed; ``t``: samples scored."""
+
+    def __init__(self, owner, batch_size, conditions):
+        super().__init__(owner, batch_size, conditions)
+        self._enc = owner.encoder._eng.start(self.batch_size)
+        self._backlog = torch.zeros((self.batch_size, 0), dtype=torch.float32, device="cuda")
+
+    received = property(lambda self: self._enc.received)
+
+    def _drain(self, frames):
+        """frames [B, k, latent] (device) into the ring and every sample they allow: feed -> push -> feed while the ring
+        has less room than the frames that are due."""
+        o, st, outs = self._owner, self._st, []
+        eng, k, f0 = o._eng, int(frames.shape[1]), 0
+        while True:
+            if f0 < k:
+                r = min(eng.room(st), k - f0)
+                if r > 0:
+                    eng.feed(st, o._frames(frames[:, f0:f0 + r], self._cond))
+                    f0 += r
+            n = int(eng.available(st))
+            if n <= 0:
+                if f0 < k:      # (cannot happen: max_frames >= live_min_frames leaves room once every sample is scored)
+                    raise RuntimeError("the conditioning ring has no room and no sample to score")
+                break
+            outs.append(eng.push(st, self._backlog[:, :n]))
+            self._backlog = self._backlog[:, n:]
+        if not outs:
+            return np.zeros((self.batch_size, 0), np.float32)
+        return torch.cat(outs, dim=1).cpu().numpy()
+
+    def push(self, audio):
+        if self._enc.closed:
+            raise ValueError("this stream is closed (finish was called)")
+        x = torch.as_tensor(self._owner.encoder._check(audio, self.batch_size))
+        frames = self._owner.encoder._eng.push(self._enc, x)
+        self._backlog = torch.cat([self._backlog, x.to("cuda")], dim=1)
+        return self._drain(frames)
+
+    def finish(self):
+        out = self._drain(self._owner.encoder._eng.finish(self._enc))
+        self._backlog = self._backlog[:, :0]
+        return out
+
+
 class WaveNetTeacher(_EngineOwner):
     """The mu-law softmax teacher of BASELINE.json configs[1-2]: ``createDecoder``'s stack
     (model.py:158-196: RightShift teacher forcing, per-layer conditioning add) with a
@@ -487,6 +682,22 @@ class WaveNetTeacher(_EngineOwner):
         if self._primary is None:
             self._engine(1, self._default_length)
         return StreamingScorer(ScorerWeights.from_engine(self._primary), max_batch=max_batch, max_chunk=max_chunk)
+
+    def mol_scorer(self, max_batch=1, max_chunk=1600, max_frames=32):
+        """A ``StreamingMolScorer`` on a copy of this teacher's current weights, for head="mol" teachers, conditioned
+        (``score(inputs, encoding, conditions)``, frames fed through a ring of ``max_frames``) or not: nll[b, t] = -log
+        p(inputs[b, t] | inputs[b, < t], encoding) in nats -- the quantity ``loss`` sums, without the training engine."""
+        from .recognizer import check_classifier_widths
+        from .scorer import MolScorerWeights
+        MolScorerWeights.check_config(self._cfg)
+        check_classifier_widths(self._cfg.filter_width, self._cfg.dilation_channels, self._cfg.skip_channels,
+                                "streaming scorer")
+        if self._primary is None:
+            self._engine(1, self._default_length)
+        return StreamingMolScorer(MolScorerWeights.from_engine(self._primary),
+                                  self.latent_channels if self.use_encoding else 0,
+                                  self.condition_size if self.use_encoding else 0, max_batch=max_batch,
+                                  max_chunk=max_chunk, max_frames=max_frames)
 
     def generate(self, batch_size, num_samples, mode="sample", seed=0, forced=None, return_logits=False,
                  encoding=None, conditions=None, prompt=None, *, temperature=1.0, top_k=0, top_p=1.0):
@@ -880,6 +1091,18 @@ class WaveNetAutoEncoder(object):
             enc._w.dead[k].copy_(t)
         enc._w.repack()
         return enc
+
+    def scorer(self, max_batch=1, max_chunk=1600, max_frames=32):
+        """An ``AutoEncoderScorer`` on snapshots of this model's encoder (``encoder``) and decoder weights: audio in,
+        nll[b, t] = -log p(audio[b, t] | audio[b, < t], encoding) in nats out, the number ``train`` descends on, for any
+        batch <= max_batch and any length.  Call it again after more training."""
+        from .recognizer import check_classifier_widths
+        from .scorer import MolScorerWeights
+        MolScorerWeights.check_config(self._cfg)
+        check_classifier_widths(self.filter_width, self.dilation_channels, self.skip_channels, "streaming scorer")
+        eng = self._eng or self._engine(1, self.input_size)
+        return AutoEncoderScorer(self.encoder(max_batch, max_frames), MolScorerWeights.from_engine(eng.dec),
+                                 self.condition_size, max_batch=max_batch, max_chunk=max_chunk, max_frames=max_frames)
 
     def reconstruct(self, inputs, conditions=None, seed=None):
         """``self.out`` (model.py:268-273): encode, run the decoder teacher-forced on the same clip, sample."""

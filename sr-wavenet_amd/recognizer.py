@@ -90,10 +90,11 @@ def check_classifier_widths(filter_width, dilation_channels, skip_channels, who=
 
 
 class StackWeights:
-    """The parameters and forward MFMA images of an unconditioned reference-gate stack with its two head 1x1s, without
-    the training engine around it: the engine's section layout and reference variable names, no activations, gradients
-    or Adam state.  ``ClassifierWeights`` (below) and ``scorer.ScorerWeights`` are its two users; a subclass adds the
-    images its own head needs in ``_pack_head``."""
+    """The parameters and forward MFMA images of a reference-gate stack with its two head 1x1s, without the training
+    engine around it: the engine's section layout and reference variable names, no activations, gradients or Adam state.
+    ``ClassifierWeights`` (below), ``scorer.ScorerWeights`` and ``scorer.MolScorerWeights`` are its users; a subclass adds
+    the images its own head needs in ``_pack_head`` and, for a conditioned stack (``E`` > 0), the conditioning sections in
+    ``_more_sections``."""
 
     view = WaveNetEngine.view
     wptr = WaveNetEngine.wptr
@@ -103,6 +104,10 @@ class StackWeights:
 
     def _pack_head(self, pk, secs):
         """Further images behind the ones every user needs (registered on `pk` before it is finalized)."""
+
+    def _more_sections(self):
+        """Further parameter sections (name, shape) behind the ones every user has (a conditioned stack's WC / BC)."""
+        return ()
 
     def _copy_engine(self, eng: WaveNetEngine):
         for name in self.sections:
@@ -127,7 +132,8 @@ class StackWeights:
         off = 0
         for name, shape in (("init_w", (Kw, 1, R)), ("init_b", (R,)), ("WF", (L, Kw, R, R)), ("BF", (L, R)),
                             ("WR", (L, R, R)), ("BR", (L, R)), ("WS", (L, R, S)), ("BS", (L, S)),
-                            ("head_w1", (S, S)), ("head_b1", (S,)), ("head_w2", (S, Cp)), ("head_b2", (Cp,))):
+                            ("head_w1", (S, S)), ("head_b1", (S,)), ("head_w2", (S, Cp)), ("head_b2", (Cp,))) \
+                + tuple(self._more_sections()):
             secs[name] = Section(name, off, shape)
             off += secs[name].numel
         self.sections, self.nparams = secs, off
@@ -168,6 +174,8 @@ class StackWeights:
         put("init_w", sp.init_w); put("init_b", sp.init_b)
         for nm, f in (("WF", "wf"), ("BF", "bf"), ("WR", "wr"), ("BR", "br"), ("WS", "ws"), ("BS", "bs")):
             put(nm, np.stack([getattr(l, f) for l in sp.layers]))
+        if self.E:
+            put("WC", np.stack([l.wc for l in sp.layers])); put("BC", np.stack([l.bc for l in sp.layers]))
         put("head_w1", sp.head_w1); put("head_b1", sp.head_b1)
         w2 = np.zeros((self.S, self.Cp)); w2[:, :self.C] = sp.head_w2
         b2 = np.zeros(self.Cp); b2[:self.C] = sp.head_b2

@@ -16,6 +16,14 @@ The teacher's RightShift (model.py:172) costs no kernel: the stack's input strea
 step stages x'[0] = the sample before the chunk (0 at the stream's start) and x'[1:n] = chunk[:n-1], and the entry conv's
 two taps then read a[t-2] and a[t-1] for row t -- the generator's input conv.  A row depends on absolute time only: a
 stream has the same bits however its audio was cut, at any batch size and in any row of the batch.
+
+``MolStreamScorer`` is the same stream for the conditioned mixture-of-logistics decoder (the ``WaveNetAutoEncoder``'s, and the
+mixture-of-logistics ``WaveNetTeacher``): nll[b, t] = -log p(audio[b, t] | audio[b, < t], encoding) with the audio itself
+as the target.  Its entry is ``srwn_flow_stream_in`` on the chunk as it is (RightShift, entry conv and the first layer's
+conditioning bias at the device clock; its carry, the two samples before the chunk, is staged from the state), its group
+launches carry ``cond_next``, its head is ``srwn_stream_mol_score_head`` (twin: ``srwn_mol_score_rows``), and the encoding
+frames are FED into a conditioning ring while the stream runs (``feed`` / ``room`` / ``available``).  Both scorers share
+``_ScorerBase``: buffers, group plan, graph cache, the cut of a push.
 """
 from __future__ import annotations
 
@@ -31,6 +39,7 @@ from . import packing as P
 from ._lib import call
 from .engine import WaveNetEngine
 from .recognizer import StackWeights
+from .student import live_min_frames, live_room
 
 # What SRWN_SCORE_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
 SCORE_FUSED_DEFAULT = "1"
@@ -61,14 +70,16 @@ class ScorerWeights(StackWeights):
         """What the scorer is built for, on an engine's ``StackConfig``: refused before anything touches the device."""
         if cfg.head_mode == "mol":
             raise NotImplementedError("the streaming scorer is built for the softmax teacher; the mixture-of-logistics "
-                                      "head is not")
+                                      "head is scored by MolStreamScorer (WaveNetTeacher.mol_scorer, "
+                                      "WaveNetAutoEncoder.scorer)")
         if cfg.head_mode != "per_timestep":
             raise ValueError("a streaming scorer needs the per-sample softmax head of WaveNetTeacher (head_mode "
                              "'per_timestep'), this engine has %r" % (cfg.head_mode,))
         if cfg.gate_mode != "reference":
             raise NotImplementedError("gate_mode %r is not built for the streaming scorer" % (cfg.gate_mode,))
         if cfg.cond_channels:
-            raise NotImplementedError("the streaming scorer is not built for the conditioned softmax teacher")
+            raise NotImplementedError("the streaming scorer is not built for the conditioned softmax teacher (the "
+                                      "conditioned mixture-of-logistics decoder: MolStreamScorer)")
         if not cfg.shift_input:
             raise ValueError("the scorer's stack predicts sample t from the samples before it: it needs the teacher's "
                              "RightShift (shift_input)")
@@ -98,12 +109,12 @@ class ScoreState:
         self.nll_sum = torch.zeros(batch, dtype=torch.float64, device=dev)
 
 
-class StreamScorer:
-    """``start`` a batch of streams, then ``push`` audio of any length: nll [B, n] fp32 of exactly the samples pushed,
-    ``score`` for whole recordings.  A step of n rows is one hipGraph per (batch, n, outputs wanted), captured when it is
-    used a second time (SRWN_MODEL_GRAPHS=0: eager launches)."""
+class _ScorerBase:
+    """What ``StreamScorer`` and ``MolStreamScorer`` share: the boundary buffers of the group plan, the stored z, the
+    clock, the roll table, the twin's buffers, the graph cache, the state's serial and the checks of a push.  A subclass
+    allocates the buffers of its own entry and head, and gives ``_new_state`` and ``_reset``."""
 
-    def __init__(self, weights: ScorerWeights, max_batch: int = 1, max_chunk: int = 1600):
+    def __init__(self, weights, max_batch: int = 1, max_chunk: int = 1600):
         if min(int(max_batch), int(max_chunk)) < 1:
             raise ValueError("max_batch and max_chunk must be >= 1")
         K._need_gpu()
@@ -113,16 +124,14 @@ class StreamScorer:
         self.groups = K.group_plan(w.dil, 31, int(os.environ.get("SRWN_GROUP_LAYERS", "8")))
         self.hist = [sum(w.dil[l0:l1]) for l0, l1 in self.groups]
         Bm, C, R, S, L = self.max_batch, self.max_chunk, w.R, w.S, w.L
-        z = lambda *s, dt=self.dt: torch.zeros(s, dtype=dt, device=self.dev)
+        z = self._zeros
         self.bufs = [z(Bm, h + C, R) for h in self.hist]      # [hist rows | chunk rows] per group
         self.top = z(Bm, C, R)                                # the last layer's output: nothing reads it
         self.zs = z(L, Bm, C, R)
-        self.xbuf = z(Bm, C, dt=torch.float32)                # the chunk delayed by one sample
+        self.xbuf = z(Bm, C, dt=torch.float32)                # the chunk as the entry reads it
         self.carry = z(Bm, dt=torch.float32)
         self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        self.codes = z(Bm, C, dt=torch.int32)
         self.nll = z(Bm, C, dt=torch.float32)
-        self.best = z(Bm, C, dt=torch.int32)
         self.logits_out: Optional[torch.Tensor] = None        # [Bm, C, classes] fp32, on the first return_logits
         self.roll = torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs, self.hist)], dtype=torch.int64,
                                  device=self.dev)
@@ -134,20 +143,18 @@ class StreamScorer:
         self._graphs: Dict[tuple, object] = {}
         self._seen: set = set()
         self._serial = 0
-        self._state: Optional[ScoreState] = None
+        self._state = None
         self.launches_per_step = 2 + len(self.groups) + (1 if self.fused else 4)
 
-    def buffer_bytes(self) -> Dict[str, int]:
-        """Device bytes by buffer family (DESIGN's table)."""
-        nb = lambda ts: int(sum(t.numel() * t.element_size() for t in ts if t is not None))
-        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]), "audio": nb([self.xbuf, self.carry, self.codes]),
-               "scores": nb([self.nll, self.best, self.logits_out]), "images": nb([self.w.packed])}
-        if not self.fused:
-            out["twin r0/r1/logits"] = nb([self.r0, self.r1, self.logits32])
-        return out
+    def _zeros(self, *shape, dt=None):
+        return torch.zeros(shape, dtype=self.dt if dt is None else dt, device=self.dev)
+
+    @staticmethod
+    def _nbytes(ts) -> int:
+        return int(sum(t.numel() * t.element_size() for t in ts if t is not None))
 
     # ------------------------------------------------------------------------------------------------
-    def start(self, batch: int = 1) -> ScoreState:
+    def start(self, batch: int = 1):
         """`batch` streams at clock 0: zero history (the conv's zero padding), zero carry, and 0 for the sample before
         the first one (the RightShift's padding)."""
         B = int(batch)
@@ -156,9 +163,13 @@ class StreamScorer:
         for b in self.bufs:
             b.zero_()
         self.carry.zero_(); self.clock.zero_()
+        self._reset()
         self._serial += 1
-        self._state = ScoreState(B, self._serial, self.dev)
+        self._state = self._new_state(B)
         return self._state
+
+    def _reset(self):
+        """What else a new state finds zeroed."""
 
     def _check_state(self, state):
         if state is not self._state or state._serial != self._serial:
@@ -177,46 +188,99 @@ class StreamScorer:
             raise ValueError("audio of %d streams pushed into a state of %d" % (x.shape[0], batch))
         return x
 
-    def _launch_step(self, B: int, n: int, want_logits: bool = False, want_best: bool = False):
-        """The launches of a step of n rows on the delayed audio staged in ``xbuf`` and the targets in ``codes``."""
+    def _launch_groups(self, B: int, n: int, cond=None):
+        """One ``srwn_residual_group_fwd_stream_z`` per layer group.  cond: None, or (table address, frames, pool_stride,
+        row stride in elements) of a conditioning ring [B * frames][L * R]: layer g then adds the bias of layer g + 1."""
         import ctypes as C_
         w = self.w
-        st, dt, R, S, C, L = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk, w.L
-        v, when = w.view, self.clock.data_ptr()
-        call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
-             v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt, st)
+        st, dt, R, C = K._stream(), K.abi_dtype(self.dt), w.R, self.max_chunk
+        v, when, es = w.view, self.clock.data_ptr(), w.packed.element_size()
         G = len(self.groups)
         zstride = self.max_batch * C * R
         for g, (l0, l1) in enumerate(self.groups):
             last = g + 1 == G
             out = self.top if last else self.bufs[g + 1]
             nl = l1 - l0
+            cn, frames, pool, cstride = None, 1, 1, R
+            if cond is not None:
+                table, frames, pool, cstride = cond
+                cn = K._ptr_array([table + (l + 1) * R * es if l + 1 < w.L else None for l in range(l0, l1)])
             call("srwn_residual_group_fwd_stream_z", self.bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
                  C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1], self.zs[l0].data_ptr(), zstride,
                  K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
                  K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
                  K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
                  K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, when, st)
+                 cn, frames, pool, cstride, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, when, st)
+
+    def _head_args(self):
+        """The head's arguments up to the targets: z, the three images and their biases."""
+        w = self.w
+        return (self.zs.data_ptr(), self.max_batch * self.max_chunk * w.R, self.max_chunk, w.L, w.wptr(w.o_skip),
+                w.bs_sum.data_ptr(), w.wptr(w.o_w1), w.view("head_b1").data_ptr(), w.wptr(w.o_w2),
+                w.view("head_b2").data_ptr())
+
+    def _launch_twin_products(self, B: int, n: int):
+        """The training forward's three products (engine.forward: skip_sum, head_1x1 and the last 1x1 in fp32) on the
+        buffers' rows up to the last stream's chunk: one launch each, so the stale rows between the streams' chunks ride
+        along, and the twin's last step never reads them."""
+        w, C = self.w, self.max_chunk
+        R, S, L, v = w.R, w.S, w.L, w.view
+        rows = (B - 1) * C + n
+        K.pw_linear(self.zs.data_ptr(), R, self.max_batch * C * R, R, L * R, w.wptr(w.o_skip), w.bs_sum, self.r0[:rows], S, S,
+                    rows, pro=K.PRO_GATE, epi=K.EPI_RELU)
+        K.pw_linear(self.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), self.r1[:rows], S, S, rows,
+                    epi=K.EPI_RELU)
+        K.pw_linear(self.r1.data_ptr(), S, 0, S, S, w.wptr(w.o_w2), v("head_b2"), self.logits32[:rows], w.Cp, w.Cp,
+                    rows, epi=K.EPI_F32, compute_dtype=self.dt)
+
+    def _launch_roll(self, B: int, n: int):
+        C = self.max_chunk
+        call("srwn_recog_roll", self.roll.data_ptr(), len(self.groups), self.xbuf.data_ptr(), C, self.carry.data_ptr(),
+             self.clock.data_ptr(), B, n, C, self.w.R, K.abi_dtype(self.dt), K._stream())
+
+    def _run_step(self, key: tuple, launch):
+        K.run_cached_graph(self._graphs, self._seen, key, self.use_graphs, launch)
+
+
+class StreamScorer(_ScorerBase):
+    """``start`` a batch of streams, then ``push`` audio of any length: nll [B, n] fp32 of exactly the samples pushed,
+    ``score`` for whole recordings.  A step of n rows is one hipGraph per (batch, n, outputs wanted), captured when it is
+    used a second time (SRWN_MODEL_GRAPHS=0: eager launches)."""
+
+    def __init__(self, weights: ScorerWeights, max_batch: int = 1, max_chunk: int = 1600):
+        super().__init__(weights, max_batch, max_chunk)
+        self.codes = self._zeros(self.max_batch, self.max_chunk, dt=torch.int32)
+        self.best = self._zeros(self.max_batch, self.max_chunk, dt=torch.int32)
+
+    def buffer_bytes(self) -> Dict[str, int]:
+        """Device bytes by buffer family (DESIGN's table)."""
+        nb = self._nbytes
+        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]), "audio": nb([self.xbuf, self.carry, self.codes]),
+               "scores": nb([self.nll, self.best, self.logits_out]), "images": nb([self.w.packed])}
+        if not self.fused:
+            out["twin r0/r1/logits"] = nb([self.r0, self.r1, self.logits32])
+        return out
+
+    def _new_state(self, B: int) -> ScoreState:
+        return ScoreState(B, self._serial, self.dev)
+
+    def _launch_step(self, B: int, n: int, want_logits: bool = False, want_best: bool = False):
+        """The launches of a step of n rows on the delayed audio staged in ``xbuf`` and the targets in ``codes``."""
+        w = self.w
+        st, dt, R, S, C = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk
+        v = w.view
+        call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
+             v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt, st)
+        self._launch_groups(B, n)
         outs = (self.nll.data_ptr(), self.best.data_ptr() if want_best else None,
                 self.logits_out.data_ptr() if want_logits else None, C, B, n)
         if self.fused:
-            call("srwn_stream_score_head", self.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
-                 w.wptr(w.o_w1), v("head_b1").data_ptr(), w.wptr(w.o_w2), v("head_b2").data_ptr(), self.codes.data_ptr(),
-                 *outs, C, R, S, w.C, dt, st)
-        else:      # the training forward's three products (engine.forward: skip_sum, head_1x1 and the last 1x1 in fp32) on
-            # the buffers' rows up to the last stream's chunk: one launch each, so the stale rows between the streams' chunks
-            # ride along, and srwn_nll_rows never reads them
-            rows = (B - 1) * C + n
-            K.pw_linear(self.zs.data_ptr(), R, zstride, R, L * R, w.wptr(w.o_skip), w.bs_sum, self.r0[:rows], S, S, rows,
-                        pro=K.PRO_GATE, epi=K.EPI_RELU)
-            K.pw_linear(self.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), self.r1[:rows], S, S, rows,
-                        epi=K.EPI_RELU)
-            K.pw_linear(self.r1.data_ptr(), S, 0, S, S, w.wptr(w.o_w2), v("head_b2"), self.logits32[:rows], w.Cp, w.Cp,
-                        rows, epi=K.EPI_F32, compute_dtype=self.dt)
+            call("srwn_stream_score_head", *self._head_args(), self.codes.data_ptr(), *outs, C, R, S, w.C, dt, st)
+        else:
+            self._launch_twin_products(B, n)
             call("srwn_nll_rows", self.logits32.data_ptr(), w.Cp, C, self.codes.data_ptr(), *outs, w.C, st)
-        call("srwn_recog_roll", self.roll.data_ptr(), G, self.xbuf.data_ptr(), C, self.carry.data_ptr(), when, B, n, C, R,
-             dt, st)
+        self._launch_roll(B, n)
 
     def push(self, state: ScoreState, audio, return_logits: bool = False, return_best: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> nll [B, n] fp32 (nats) of exactly those
@@ -238,8 +302,7 @@ class StreamScorer:
             self.xbuf[:B, 1:n].copy_(x[:, a:a + n - 1])
             self.codes[:B, :n].copy_(codes[:, a:a + n])
             state._last = x[:, a + n - 1].clone()
-            K.run_cached_graph(self._graphs, self._seen, (B, n, want_logits, want_best), self.use_graphs,
-                               lambda: self._launch_step(B, n, want_logits, want_best))
+            self._run_step((B, n, want_logits, want_best), lambda: self._launch_step(B, n, want_logits, want_best))
             nll[:, a:a + n] = self.nll[:B, :n]
             if want_logits:
                 logits[:, a:a + n] = self.logits_out[:B, :n]
@@ -255,6 +318,274 @@ class StreamScorer:
         one ends)."""
         x = self._check_audio(audio)
         return self.push(self.start(int(x.shape[0])), x, return_logits, return_best)
+
+
+# ---- the conditioned mixture-of-logistics decoder ------------------------------------------------------------------------
+MAX_MIXTURES = 16      # 4M <= 64 logits: the head keeps them in two 32-column tiles, two mixtures per lane of a row
+
+
+def plan_score_pieces(frames: int, pool_stride: int, max_frames: int, hist_max: int) -> List[Tuple[int, int]]:
+    """How ``MolStreamScorer.score`` walks a recording of `frames` encoding frames through a ring of `max_frames`:
+    [(k, n)] in order -- feed k frames (as many as ``student.live_room`` allows, k >= 1), then push the n = fed *
+    pool_stride - t samples they make scorable.  Ends with every frame fed and every sample pushed.  Pure Python: the
+    CPU tests hold it to brute force on a ring model."""
+    frames, pool_stride, max_frames, hist_max = int(frames), int(pool_stride), int(max_frames), int(hist_max)
+    if frames < 0 or pool_stride < 1 or max_frames < live_min_frames(hist_max, pool_stride):
+        raise ValueError("plan_score_pieces: frames=%d pool_stride=%d max_frames=%d (at least %d for a history of %d)"
+                         % (frames, pool_stride, max_frames, live_min_frames(hist_max, pool_stride), hist_max))
+    out, fed, t = [], 0, 0
+    while fed < frames:
+        k = min(live_room(fed, t, hist_max, pool_stride, max_frames), frames - fed)
+        fed += k
+        out.append((k, fed * pool_stride - t))
+        t = fed * pool_stride
+    return out
+
+
+class MolScorerWeights(StackWeights):
+    """The parameters and forward MFMA images of the mixture-of-logistics decoder (createDecoder, model.py:158-196) without
+    the training engine around it: ``ScorerWeights``' layout with output_channels = 4 * num_mixtures (Cp = 32 or 64 rows in
+    the packed last 1x1) and, for cond_channels > 0, the sections WC [L, E, R] / BC [L, R] and the conditioning image of all
+    layers as one [Ep] -> [L * R] product, as the engine packs it.  Built from a decoder engine (``from_engine``: a copy
+    of its parameters: ``WaveNetAutoEncoder``'s decoder, a mixture-of-logistics ``WaveNetTeacher``) or filled from a
+    checkpoint directory by the reference's variable names (``load``)."""
+
+    _who = "streaming scorer"
+
+    def __init__(self, dilations, dilation_channels: int = 32, skip_channels: int = 256, num_mixtures: int = 10,
+                 cond_channels: int = 0, pool_stride: int = 1, filter_width: int = 2, dtype: torch.dtype = torch.bfloat16,
+                 device="cuda"):
+        M, E, pool = int(num_mixtures), int(cond_channels), int(pool_stride)
+        if not 1 <= M <= MAX_MIXTURES:
+            raise NotImplementedError("num_mixtures %d: the streaming scorer's head is built for 1..%d" % (M, MAX_MIXTURES))
+        if E < 0 or pool < 1:
+            raise ValueError("cond_channels %d, pool_stride %d" % (E, pool))
+        self.M, self.E, self.Ep, self.pool = M, E, (E + 15) // 16 * 16, pool if E else 1
+        super().__init__(dilations, dilation_channels, skip_channels, 4 * M, filter_width, dtype, device)
+
+    def _more_sections(self):
+        return (("WC", (self.L, self.E, self.R)), ("BC", (self.L, self.R))) if self.E else ()
+
+    def _pack_head(self, pk, secs):
+        L, R, E, Ep = self.L, self.R, self.E, self.Ep
+        self.o_w2 = P.pack_linear(pk, secs["head_w2"].offset, self.S, self.Cp, self.Cp)
+        self.o_wc = None
+        if E:      # (engine._pack_stack's image: rows = l * R + channel)
+            self.o_wc = pk.reserve(L * R // 32, Ep // 16)
+            for l in range(L):
+                P.fill_linear(pk, self.o_wc + l * (R // 32) * (Ep // 16) * 512, secs["WC"].offset + l * E * R, E, R,
+                              R // 32, Ep // 16)
+
+    def tf_variables(self, scope: str) -> Dict[str, torch.Tensor]:
+        """Reference name -> tensor by the decoder's naming (a conditioning 1x1 in front of every layer's two) when the
+        stack is conditioned; the dead gate variables are left out."""
+        return {k: v for k, v in WaveNetEngine.tf_variables(self, scope, decoder=bool(self.E)).items() if v.is_cuda}
+
+    @staticmethod
+    def check_config(cfg) -> None:
+        """What the mixture-of-logistics scorer is built for, on an engine's ``StackConfig``: refused before anything
+        touches the device."""
+        if cfg.head_mode != "mol":
+            raise ValueError("MolStreamScorer scores the mixture-of-logistics decoder (head_mode 'mol'), this engine has "
+                             "%r (the softmax teacher: StreamScorer)" % (cfg.head_mode,))
+        if cfg.gate_mode != "reference":
+            raise NotImplementedError("gate_mode %r is not built for the streaming scorer" % (cfg.gate_mode,))
+        if not cfg.shift_input:
+            raise ValueError("the scorer's stack predicts sample t from the samples before it: it needs the decoder's "
+                             "RightShift (shift_input)")
+        if cfg.output_channels % 4 or not 1 <= cfg.output_channels // 4 <= MAX_MIXTURES:
+            raise NotImplementedError("output_channels %d: 4 * num_mixtures with 1..%d mixtures"
+                                      % (cfg.output_channels, MAX_MIXTURES))
+
+    @classmethod
+    def from_engine(cls, eng: WaveNetEngine) -> "MolScorerWeights":
+        """A copy of a mixture-of-logistics decoder engine's parameters; later training does not reach it."""
+        cfg = eng.cfg
+        cls.check_config(cfg)
+        return cls(cfg.dilations, cfg.dilation_channels, cfg.skip_channels, cfg.output_channels // 4, cfg.cond_channels,
+                   cfg.pool_stride, cfg.filter_width, cfg.dtype, eng.dev)._copy_engine(eng)
+
+    def load(self, logdir, scope: str = "WaveNetAutoEncoder/Decoder") -> bool:
+        """``StackWeights.load`` under the decoder's scope (``WaveNetAutoEncoder.save`` / ``WaveNetTeacher.save`` or the
+        reference's tf.train.Saver wrote the checkpoint)."""
+        return super().load(logdir, scope)
+
+
+class MolScoreState:
+    """One batch of streams of a ``MolStreamScorer``.  ``t``: samples scored per stream; ``fed``: conditioning frames fed;
+    ``nll_sum``: the sum of every nll returned so far, fp64 [B] on the device."""
+
+    def __init__(self, batch: int, serial: int, dev):
+        self.B, self._serial, self.t, self.fed = batch, serial, 0, 0
+        self._carry = torch.zeros((batch, 2), dtype=torch.float32, device=dev)      # the samples t - 1 and t - 2
+        self.nll_sum = torch.zeros(batch, dtype=torch.float64, device=dev)
+
+
+class MolStreamScorer(_ScorerBase):
+    """``start`` a batch of streams, ``feed`` them encoding frames (a conditioned decoder) and ``push`` audio: nll [B, n]
+    fp32 in nats of exactly the samples pushed, nll[b, t] = -log p(audio[b, t] | audio[b, < t], encoding); ``score`` for
+    whole recordings.  The conditioning table is a ring of ``max_frames`` frames per stream: frame q in row q mod
+    max_frames.  The group launches recompute their halo rows WITH their conditioning, so a chunk at time t still reads the
+    frame of time t - hist_max (hist_max: the largest history of the plan's groups) and the room rule is
+    ``student.live_room``; a ring shorter than ``student.live_min_frames`` would stall and is refused."""
+
+    def __init__(self, weights: MolScorerWeights, max_batch: int = 1, max_chunk: int = 1600, max_frames: int = 32):
+        if min(int(max_batch), int(max_chunk)) < 1:
+            raise ValueError("max_batch and max_chunk must be >= 1")
+        w = weights
+        self.E, self.pool = w.E, w.pool
+        self.hist_max = max(sum(w.dil[l0:l1]) for l0, l1 in self._plan(w)) if w.E else 0
+        self.max_frames = int(max_frames) if w.E else 1
+        if w.E and self.max_frames < live_min_frames(self.hist_max, self.pool):
+            raise ValueError("max_frames %d: a chunk still reads the conditioning of its groups' halo rows, %d samples back; "
+                             "at pool_stride %d the ring needs at least %d frames"
+                             % (self.max_frames, self.hist_max, self.pool, live_min_frames(self.hist_max, self.pool)))
+        super().__init__(w, max_batch, max_chunk)
+        Bm, F, LR = self.max_batch, self.max_frames, (w.L * w.R if w.E else w.R)
+        self.LR = LR
+        self.carry2 = self._zeros(Bm, 2, dt=torch.float32)          # srwn_flow_stream_in's carry, staged before every step
+        self.ring = self._zeros(Bm * F, LR)                          # (unconditioned: one zero row per stream)
+        if w.E:
+            self.stage_in = self._zeros(Bm * F, w.Ep)
+            self.stage_out = self._zeros(Bm * F, LR)
+
+    @staticmethod
+    def _plan(w):
+        return K.group_plan(w.dil, 31, int(os.environ.get("SRWN_GROUP_LAYERS", "8")))
+
+    def buffer_bytes(self) -> Dict[str, int]:
+        """Device bytes by buffer family (DESIGN's table)."""
+        nb = self._nbytes
+        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]),
+               "audio": nb([self.xbuf, self.carry, self.carry2]), "scores": nb([self.nll, self.logits_out]),
+               "conditioning": nb([self.ring] + ([self.stage_in, self.stage_out] if self.E else [])),
+               "images": nb([self.w.packed])}
+        if not self.fused:
+            out["twin r0/r1/logits"] = nb([self.r0, self.r1, self.logits32])
+        return out
+
+    def _new_state(self, B: int) -> MolScoreState:
+        return MolScoreState(B, self._serial, self.dev)
+
+    def _reset(self):
+        self.ring.zero_()
+
+    # ------------------------------------------------------------------------------------------------
+    def room(self, state: MolScoreState) -> int:
+        """Frames that may be fed now (0 for an unconditioned decoder)."""
+        self._check_state(state)
+        return live_room(state.fed, state.t, self.hist_max, self.pool, self.max_frames) if self.E else 0
+
+    def available(self, state: MolScoreState):
+        """Samples that may be pushed now: fed * pool_stride - t; unbounded (inf) without conditioning."""
+        self._check_state(state)
+        return state.fed * self.pool - state.t if self.E else float("inf")
+
+    def feed(self, state: MolScoreState, frames) -> None:
+        """The next k frames of every stream: frames [B, k, cond_channels], a device tensor taken as it is.  Refuses
+        (ValueError, before any device work, state untouched) k > ``room``.  One projection through the conditioning
+        image and ONE srwn_cond_ring_scatter however many streams."""
+        self._check_state(state)
+        if not self.E:
+            raise ValueError("feed: this decoder is not conditioned")
+        fr = torch.as_tensor(frames)
+        B = state.B
+        if fr.dim() != 3 or fr.shape[0] != B or fr.shape[2] != self.E:
+            raise ValueError("feed: frames must be [%d, k, %d], got %s" % (B, self.E, tuple(fr.shape)))
+        k = int(fr.shape[1])
+        room = self.room(state)
+        if k > room:
+            raise ValueError("feed: %d frames, but the ring of %d has room for %d at t = %d with %d fed"
+                             % (k, self.max_frames, room, state.t, state.fed))
+        if k == 0:
+            return
+        w, rows, LR = self.w, B * k, self.LR
+        self.stage_in[:rows, :self.E].copy_(fr.to(device=self.dev, dtype=torch.float32).reshape(rows, self.E))
+        K.pw_linear(self.stage_in.data_ptr(), w.Ep, 0, w.Ep, w.Ep, w.wptr(w.o_wc), w.view("BC").reshape(-1),
+                    self.stage_out[:rows], LR, LR, rows)
+        call("srwn_cond_ring_scatter", self.stage_out.data_ptr(), LR, self.ring.data_ptr(), LR, B, k, state.fed,
+             self.max_frames, LR, K.abi_dtype(self.dt), K._stream())
+        state.fed += k
+
+    def _launch_step(self, B: int, n: int, want_logits: bool = False):
+        """The launches of a step of n rows on the chunk staged in ``xbuf`` (entry input and target) and the two samples
+        before it in ``carry2``."""
+        w = self.w
+        st, dt, R, S, C = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk
+        v, F, LR = w.view, self.max_frames, self.LR
+        call("srwn_flow_stream_in", self.xbuf.data_ptr(), C, self.carry2.data_ptr(), v("init_w").data_ptr(),
+             v("init_b").data_ptr(), self.ring.data_ptr(), F, self.pool, LR, self.bufs[0].data_ptr(), self.hist[0] + C,
+             self.hist[0], B, n, C, R, dt, self.clock.data_ptr(), st)
+        self._launch_groups(B, n, (self.ring.data_ptr(), F, self.pool, LR) if self.E else None)
+        lo = self.logits_out.data_ptr() if want_logits else None
+        if self.fused:
+            call("srwn_stream_mol_score_head", *self._head_args(), self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C, B, n,
+                 C, R, S, w.M, dt, st)
+        else:
+            self._launch_twin_products(B, n)
+            call("srwn_mol_score_rows", self.logits32.data_ptr(), w.Cp, C, self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C,
+                 B, n, w.M, st)
+        self._launch_roll(B, n)
+
+    def push(self, state: MolScoreState, audio, return_logits: bool = False):
+        """The next samples of every stream, audio [B, n] with any n >= 0 -> nll [B, n] fp32 (nats) of exactly those
+        samples (the targets are the audio itself: no mu-law); with return_logits also the logits [B, n, 4M] fp32.  A
+        device tensor is taken as it is.  Refuses (ValueError, state untouched) a wrong rank or batch, and n >
+        ``available``."""
+        self._check_state(state)
+        x = self._check_audio(audio, state.B)
+        B, n_all = state.B, int(x.shape[1])
+        if n_all > self.available(state):
+            raise ValueError("push: %d samples, but the %d frames fed cover %d more at t = %d"
+                             % (n_all, state.fed, self.available(state), state.t))
+        C4 = self.w.C
+        x = x.to(device=self.dev, dtype=torch.float32).contiguous()
+        want_logits = bool(return_logits)
+        if want_logits and self.logits_out is None:
+            self.logits_out = torch.zeros((self.max_batch, self.max_chunk, C4), dtype=torch.float32, device=self.dev)
+        nll = torch.empty((B, n_all), dtype=torch.float32, device=self.dev)
+        logits = torch.empty((B, n_all, C4), dtype=torch.float32, device=self.dev) if want_logits else None
+        for a, n in cut_push(n_all, self.max_chunk):
+            self.xbuf[:B, :n].copy_(x[:, a:a + n])
+            self.carry2[:B].copy_(state._carry)
+            # the next chunk's carry: its samples t - 1 and t - 2
+            before = x[:, a + n - 2] if n >= 2 else state._carry[:, 0]
+            state._carry = torch.stack([x[:, a + n - 1], before], dim=1)
+            self._run_step((B, n, want_logits), lambda: self._launch_step(B, n, want_logits))
+            nll[:, a:a + n] = self.nll[:B, :n]
+            if want_logits:
+                logits[:, a:a + n] = self.logits_out[:B, :n]
+        state.t += n_all
+        state.nll_sum += nll.sum(1, dtype=torch.float64)
+        return (nll, logits) if want_logits else nll
+
+    def score(self, audio, encoding=None, return_logits: bool = False):
+        """Whole recordings audio [B, T] -> nll [B, T] (``push``'s returns).  A conditioned decoder takes encoding [B,
+        frames, cond_channels] with T = frames * pool_stride, fed and pushed in the pieces of ``plan_score_pieces``.
+        Starts a new state (the current one ends)."""
+        x = self._check_audio(audio)
+        B, T = int(x.shape[0]), int(x.shape[1])
+        if not self.E:
+            if encoding is not None:
+                raise ValueError("score: this decoder is not conditioned")
+            return self.push(self.start(B), x, return_logits)
+        if encoding is None:
+            raise ValueError("score: this decoder is conditioned: pass encoding [batch, frames, %d]" % self.E)
+        enc = torch.as_tensor(encoding)
+        if enc.dim() != 3 or enc.shape[0] != B or enc.shape[2] != self.E or int(enc.shape[1]) * self.pool != T:
+            raise ValueError("score: encoding must be [%d, samples / pool_stride = %s, %d], got %s"
+                             % (B, "%d / %d" % (T, self.pool), self.E, tuple(enc.shape)))
+        st = self.start(B)
+        outs, f0, t0 = [], 0, 0
+        for k, n in plan_score_pieces(int(enc.shape[1]), self.pool, self.max_frames, self.hist_max):
+            self.feed(st, enc[:, f0:f0 + k])
+            outs.append(self.push(st, x[:, t0:t0 + n], return_logits))
+            f0, t0 = f0 + k, t0 + n
+        if not outs:
+            outs = [self.push(st, x, return_logits)]
+        if return_logits:
+            return torch.cat([o[0] for o in outs], 1), torch.cat([o[1] for o in outs], 1)
+        return torch.cat(outs, 1)
 
 
 def bits_per_sample(nll_sum: float, samples: int) -> float:
