@@ -336,63 +336,61 @@ int rows_args(const char* who, int32_t B, int32_t n, int32_t C, int64_t clip_row
   return 0;
 }
 
-template <typename T, int R, int S>
-int launch_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int L, const void* wskip,
+// ------------------------------------------------------------------------------------------
+// Host side: one body per pair.  The softmax launches (score head, nll rows) and the mixture launches (mol score head, mol
+// score rows) differ in what a row is scored against and in what the reduction leaves beside nll; HeadRows holds either.
+// ------------------------------------------------------------------------------------------
+struct HeadRows {
+  const int32_t* codes;              // softmax: the targets
+  const float* x; int64_t x_stride;  // mixture: the chunk's own audio
+  float* nll; int32_t* best; float* logits_out; int64_t out_stride;      // (best: softmax only; best, logits_out may be null)
+  int width;                         // C classes, or M mixtures
+  const void* target(bool mol) const { return mol ? (const void*)x : (const void*)codes; }
+};
+
+template <bool MOL>
+int check_rows(const char* who, const HeadRows& r, int32_t B, int32_t n, int64_t clip_rows) {
+  if (MOL && (r.width < 1 || r.width > kMaxMixtures))
+    return set_error(SRWN_E_SHAPE, "%s: %d mixtures (1..%d)", who, r.width, kMaxMixtures);
+  if (MOL && r.x_stride < n)
+    return set_error(SRWN_E_SHAPE, "%s: %d rows of audio at a stride of %lld", who, n, (long long)r.x_stride);
+  return rows_args(who, B, n, MOL ? 4 * r.width : r.width, clip_rows, r.out_stride);
+}
+
+template <bool MOL, typename T, int R, int S>
+int launch_score_head(const char* who, const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int L, const void* wskip,
                       const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
-                      const int32_t* codes, float* nll, int32_t* best, float* logits_out, int64_t out_stride, int B, int n,
-                      int C, hipStream_t st) {
-  constexpr int sh = xch_bytes<T, S>() + kLogitBytes;
+                      const HeadRows& r, int B, int n, hipStream_t st) {
+  constexpr int sh = xch_bytes<T, S>() + (MOL ? kMolLogitBytes : kLogitBytes);
   const int ntiles = (n + 31) / 32;
-  auto kfn = stream_score_head_kernel<T, R, S>;
-  if (sh > 32768) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
-  hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
-                     (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, codes, nll, best, logits_out, out_stride, n,
-                     ntiles, C);
-  return check_launch("stream_score_head");
+  auto launch = [&](auto kfn, auto... rows) {
+    if (sh > 32768) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
+                       (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, rows..., n, ntiles, r.width);
+  };
+  if constexpr (MOL) launch(mol_stream_score_head_kernel<T, R, S>, r.x, r.x_stride, r.nll, r.logits_out, r.out_stride);
+  else launch(stream_score_head_kernel<T, R, S>, r.codes, r.nll, r.best, r.logits_out, r.out_stride);
+  return check_launch(who);
 }
 
-int mol_rows_args(const char* who, int32_t B, int32_t n, int32_t M, int64_t clip_rows, int64_t x_stride, int64_t out_stride) {
-  if (M < 1 || M > kMaxMixtures) return set_error(SRWN_E_SHAPE, "%s: %d mixtures (1..%d)", who, M, kMaxMixtures);
-  if (x_stride < n) return set_error(SRWN_E_SHAPE, "%s: %d rows of audio at a stride of %lld", who, n, (long long)x_stride);
-  return rows_args(who, B, n, 4 * M, clip_rows, out_stride);
-}
-
-template <typename T, int R, int S>
-int launch_mol_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int L, const void* wskip,
-                          const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
-                          const float* x, int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int B, int n,
-                          int M, hipStream_t st) {
-  constexpr int sh = xch_bytes<T, S>() + kMolLogitBytes;
-  const int ntiles = (n + 31) / 32;
-  auto kfn = mol_stream_score_head_kernel<T, R, S>;
-  if (sh > 32768) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
-  hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
-                     (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, x, x_stride, nll, logits_out, out_stride, n,
-                     ntiles, M);
-  return check_launch("stream_mol_score_head");
-}
-
-}  // namespace
-
-extern "C" int srwn_stream_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
-                                      const void* wskip, const float* bs_sum, const void* w1, const float* b1,
-                                      const void* w2, const float* b2, const int32_t* codes, float* nll, int32_t* best,
-                                      float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t max_chunk,
-                                      int32_t R, int32_t S, int32_t C, int32_t dtype, void* stream) {
-  const char* who = "stream_score_head";
-  if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !codes || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+template <bool MOL>
+int score_head_impl(const char* who, const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                    const void* wskip, const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
+                    const HeadRows& r, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype,
+                    void* stream) {
+  if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !r.target(MOL) || !r.nll)
+    return set_error(SRWN_E_NULL, "%s: null pointer", who);
   if ((R != 32 && R != 64) || (S != 128 && S != 256))
     return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
   if (max_chunk < 1 || n > max_chunk || z_clip_rows < max_chunk)
     return set_error(SRWN_E_SHAPE, "%s: a chunk of %d rows in buffers of %lld rows per stream (max_chunk = %d)", who, n,
                      (long long)z_clip_rows, max_chunk);
-  if (const int rc = rows_args(who, B, n, C, z_clip_rows, out_stride)) return rc;
+  if (const int rc = check_rows<MOL>(who, r, B, n, z_clip_rows)) return rc;
   if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
     return set_error(SRWN_E_SHAPE, "%s: %d layers at a stride of %lld", who, nlayers, (long long)z_layer_stride);
-  hipStream_t st = (hipStream_t)stream;
-#define SRWN_SSH(TT, RR, SS)                                                                                           \
-  return launch_score_head<TT, RR, SS>(z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2, codes, nll, \
-                                       best, logits_out, out_stride, B, n, C, st)
+#define SRWN_SSH(TT, RR, SS)                                                                                               \
+  return launch_score_head<MOL, TT, RR, SS>(who, z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2, r, \
+                                            B, n, (hipStream_t)stream)
 #define SRWN_SSH_T(TT)                                       \
   {                                                          \
     if (R == 32 && S == 128) SRWN_SSH(TT, 32, 128);          \
@@ -407,17 +405,42 @@ extern "C" int srwn_stream_score_head(const void* z, int64_t z_layer_stride, int
   return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
 }
 
+template <bool MOL>
+int score_rows_impl(const char* who, const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const HeadRows& r,
+                    int32_t B, int32_t n, void* stream) {
+  if (!logits || !r.target(MOL) || !r.nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (const int rc = check_rows<MOL>(who, r, B, n, logits_clip_rows)) return rc;
+  if (logits_ld < (MOL ? 4 * r.width : r.width))
+    return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d %s", who, (long long)logits_ld, r.width,
+                     MOL ? "mixtures" : "classes");
+  const int ntiles = (n + 31) / 32;
+  const dim3 grid((unsigned)(B * ntiles));
+  if constexpr (MOL)
+    hipLaunchKernelGGL(mol_score_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.x,
+                       r.x_stride, r.nll, r.logits_out, r.out_stride, n, ntiles, r.width);
+  else
+    hipLaunchKernelGGL(nll_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.codes,
+                       r.nll, r.best, r.logits_out, r.out_stride, n, ntiles, r.width);
+  return check_launch(who);
+}
+
+}  // namespace
+
+extern "C" int srwn_stream_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                      const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                      const void* w2, const float* b2, const int32_t* codes, float* nll, int32_t* best,
+                                      float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t max_chunk,
+                                      int32_t R, int32_t S, int32_t C, int32_t dtype, void* stream) {
+  return score_head_impl<false>("stream_score_head", z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2,
+                                HeadRows{codes, nullptr, 0, nll, best, logits_out, out_stride, C}, B, n, max_chunk, R, S,
+                                dtype, stream);
+}
+
 extern "C" int srwn_nll_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const int32_t* codes,
                              float* nll, int32_t* best, float* logits_out, int64_t out_stride, int32_t B, int32_t n,
                              int32_t C, void* stream) {
-  const char* who = "nll_rows";
-  if (!logits || !codes || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
-  if (const int rc = rows_args(who, B, n, C, logits_clip_rows, out_stride)) return rc;
-  if (logits_ld < C) return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d classes", who, (long long)logits_ld, C);
-  const int ntiles = (n + 31) / 32;
-  hipLaunchKernelGGL(nll_rows_kernel, dim3((unsigned)(B * ntiles)), dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
-                     logits_clip_rows, codes, nll, best, logits_out, out_stride, n, ntiles, C);
-  return check_launch(who);
+  return score_rows_impl<false>("nll_rows", logits, logits_ld, logits_clip_rows,
+                                HeadRows{codes, nullptr, 0, nll, best, logits_out, out_stride, C}, B, n, stream);
 }
 
 extern "C" int srwn_stream_mol_score_head(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
@@ -425,43 +448,14 @@ extern "C" int srwn_stream_mol_score_head(const void* z, int64_t z_layer_stride,
                                           const void* w2, const float* b2, const float* x, int64_t x_stride, float* nll,
                                           float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t max_chunk,
                                           int32_t R, int32_t S, int32_t M, int32_t dtype, void* stream) {
-  const char* who = "stream_mol_score_head";
-  if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !x || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
-  if ((R != 32 && R != 64) || (S != 128 && S != 256))
-    return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
-  if (max_chunk < 1 || n > max_chunk || z_clip_rows < max_chunk)
-    return set_error(SRWN_E_SHAPE, "%s: a chunk of %d rows in buffers of %lld rows per stream (max_chunk = %d)", who, n,
-                     (long long)z_clip_rows, max_chunk);
-  if (const int rc = mol_rows_args(who, B, n, M, z_clip_rows, x_stride, out_stride)) return rc;
-  if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
-    return set_error(SRWN_E_SHAPE, "%s: %d layers at a stride of %lld", who, nlayers, (long long)z_layer_stride);
-  hipStream_t st = (hipStream_t)stream;
-#define SRWN_MSH(TT, RR, SS)                                                                                              \
-  return launch_mol_score_head<TT, RR, SS>(z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2, x,     \
-                                           x_stride, nll, logits_out, out_stride, B, n, M, st)
-#define SRWN_MSH_T(TT)                                       \
-  {                                                          \
-    if (R == 32 && S == 128) SRWN_MSH(TT, 32, 128);          \
-    else if (R == 32) SRWN_MSH(TT, 32, 256);                 \
-    else if (S == 128) SRWN_MSH(TT, 64, 128);                \
-    else SRWN_MSH(TT, 64, 256);                              \
-  }
-  if (dtype == SRWN_BF16) SRWN_MSH_T(bf16_t)
-  else if (dtype == SRWN_F32) SRWN_MSH_T(float)
-#undef SRWN_MSH_T
-#undef SRWN_MSH
-  return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+  return score_head_impl<true>("stream_mol_score_head", z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2,
+                               b2, HeadRows{nullptr, x, x_stride, nll, nullptr, logits_out, out_stride, M}, B, n, max_chunk,
+                               R, S, dtype, stream);
 }
 
 extern "C" int srwn_mol_score_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const float* x,
                                    int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int32_t B, int32_t n,
                                    int32_t M, void* stream) {
-  const char* who = "mol_score_rows";
-  if (!logits || !x || !nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
-  if (const int rc = mol_rows_args(who, B, n, M, logits_clip_rows, x_stride, out_stride)) return rc;
-  if (logits_ld < 4 * M) return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d mixtures", who, (long long)logits_ld, M);
-  const int ntiles = (n + 31) / 32;
-  hipLaunchKernelGGL(mol_score_rows_kernel, dim3((unsigned)(B * ntiles)), dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
-                     logits_clip_rows, x, x_stride, nll, logits_out, out_stride, n, ntiles, M);
-  return check_launch(who);
+  return score_rows_impl<true>("mol_score_rows", logits, logits_ld, logits_clip_rows,
+                               HeadRows{nullptr, x, x_stride, nll, nullptr, logits_out, out_stride, M}, B, n, stream);
 }

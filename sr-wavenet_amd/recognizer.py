@@ -11,10 +11,11 @@ yields T - input_size + 1 pooled rows, one per window position.  A stream emits 
 in the state, so the stack only ever advances by whole hops at hop-aligned absolute times: every H_j depends on absolute
 time only, and a stream has the same bits however its audio was cut, at any batch size and in any row of the batch.
 
-Per step of k hops: the stream entry (input conv), one ``srwn_residual_group_fwd_stream_z`` launch per layer group (the
-stream form of the group kernels that also stores every layer's z of the chunk's rows), ``srwn_pooled_stream_head`` (skip
-sum, head 1x1 and hop sums in one launch; ``SRWN_RECOG_FUSED=0``: the parity twin, two ``srwn_pw_linear`` calls into
-chunk-sized buffers and ``srwn_hop_sum``), ``srwn_window_mean``, ``srwn_pooled_head`` and the roll.
+Per step of k hops: the stream entry (input conv), one launch per layer group (``StreamStack.launch_groups`` with stored z:
+the stream form of the group kernels that also stores every layer's z of the chunk's rows), ``srwn_pooled_stream_head``
+(skip sum, head 1x1 and hop sums in one launch; ``SRWN_RECOG_FUSED=0``: the parity twin, two ``srwn_pw_linear`` calls into
+chunk-sized buffers and ``srwn_hop_sum``), ``srwn_window_mean``, ``srwn_pooled_head`` and the roll.  The stack, the staged
+chunk, the clock, the graph cache and a push's checks are ``stream_stack.StreamHost``'s, shared with the scorers.
 
 ``StreamClassifier.pool()`` turns the classifier's ``max_batch`` rows into SLOTS (``ClassifierPool``): streams join and
 leave, each pushes audio of any length at a clock of its own, and one step serves every slot that has a whole hop waiting
@@ -36,6 +37,7 @@ from . import packing as P
 from ._lib import call
 from .engine import Section, WaveNetEngine
 from .audio_ring import AudioRingSlots
+from .stream_stack import StreamHost, nbytes
 
 # What SRWN_RECOG_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
 RECOG_FUSED_DEFAULT = "1"
@@ -227,71 +229,45 @@ class RecogState:
         return int(self._rem.shape[1])
 
 
-class StreamClassifier:
+class StreamClassifier(StreamHost):
     """``start`` a batch of streams, then ``push`` audio of any length: the probabilities [B, k, C] of the k window
     positions that audio completed (k >= 0), ``classify`` for whole recordings.  A step of h hops is one hipGraph per
     (batch, h), captured when it is used a second time (SRWN_MODEL_GRAPHS=0: eager launches)."""
+
+    _noun = "classifier"
 
     def __init__(self, weights: ClassifierWeights, max_batch: int = 1, hop: int = 160, window: int = 16000,
                  max_hops: int = 8):
         check_hop_window(hop, window)
         if min(int(max_batch), int(max_hops)) < 1:
             raise ValueError("max_batch and max_hops must be >= 1")
-        K._need_gpu()
-        w = self.w = weights
-        self.max_batch, self.hop, self.window, self.max_hops = int(max_batch), int(hop), int(window), int(max_hops)
+        self.hop, self.window, self.max_hops = int(hop), int(window), int(max_hops)
         self.nW = self.window // self.hop
-        self.max_chunk = self.max_hops * self.hop
         self.ring_rows = self.nW + self.max_hops - 1      # a step writes max_hops rows before the oldest window is read
-        self.dev, self.dt = w.dev, w.dt
-        self.groups = K.group_plan(w.dil, 31, int(os.environ.get("SRWN_GROUP_LAYERS", "8")))
-        self.hist = [sum(w.dil[l0:l1]) for l0, l1 in self.groups]
-        Bm, C, R, S, L = self.max_batch, self.max_chunk, w.R, w.S, w.L
-        z = lambda *s, dt=self.dt: torch.zeros(s, dtype=dt, device=self.dev)
-        self.bufs = [z(Bm, h + C, R) for h in self.hist]      # [hist rows | chunk rows] per group
-        self.top = z(Bm, C, R)                                # the last layer's output: nothing reads it
-        self.zs = z(L, Bm, C, R)
-        self.xbuf = z(Bm, C, dt=torch.float32)
-        self.carry = z(Bm, dt=torch.float32)
-        self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        self.ring = z(Bm, self.ring_rows, S, dt=torch.float32)
-        self.mean = z(Bm * self.max_hops, S, dt=torch.float32)
+        super().__init__(weights, max_batch, self.max_hops * self.hop,
+                         os.environ.get("SRWN_RECOG_FUSED", RECOG_FUSED_DEFAULT) != "0")
+        w, Bm, z = self.w, self.max_batch, self._zeros
+        self.ring = z(Bm, self.ring_rows, w.S, dt=torch.float32)
+        self.mean = z(Bm * self.max_hops, w.S, dt=torch.float32)
         self.logits = z(Bm * self.max_hops, w.C, dt=torch.float32)
         self.probs = z(Bm * self.max_hops, w.C, dt=torch.float32)
-        self.roll = torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs, self.hist)], dtype=torch.int64,
-                                 device=self.dev)
-        self.fused = os.environ.get("SRWN_RECOG_FUSED", RECOG_FUSED_DEFAULT) != "0"
-        if not self.fused:
-            self.r0, self.r1 = z(Bm * C, S), z(Bm * C, S)
-        self.use_graphs = os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
-        self._graphs: Dict[tuple, object] = {}
-        self._seen: set = set()
-        self._serial = 0
-        self._state: Optional[RecogState] = None
         self._pool: Optional["ClassifierPool"] = None
         self.launches_per_step = 4 + len(self.groups) + (1 if self.fused else 3)
 
     def buffer_bytes(self) -> Dict[str, int]:
         """Device bytes by buffer family (DESIGN's table)."""
-        nb = lambda ts: int(sum(t.numel() * t.element_size() for t in ts))
-        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]), "ring": nb([self.ring]),
-               "audio": nb([self.xbuf, self.carry]), "emissions": nb([self.mean, self.logits, self.probs]),
-               "images": nb([self.w.packed])}
+        out = dict(self.stack.nbytes(), ring=nbytes([self.ring]), audio=nbytes([self.xbuf, self.carry]),
+                   emissions=nbytes([self.mean, self.logits, self.probs]), images=nbytes([self.w.packed]))
         if not self.fused:
-            out["twin r0/r1"] = nb([self.r0, self.r1])
+            out["twin r0/r1"] = nbytes([self.r0, self.r1])
         return out
 
     # ------------------------------------------------------------------------------------------------
     def start(self, batch: int = 1) -> RecogState:
         """`batch` streams at clock 0: zero history (the conv's zero padding), zero carry, empty ring."""
-        B = int(batch)
-        if not 1 <= B <= self.max_batch:
-            raise ValueError("batch %d: this classifier holds max_batch=%d" % (B, self.max_batch))
-        for b in self.bufs:
-            b.zero_()
-        self.carry.zero_(); self.clock.zero_(); self.ring.zero_()
+        B = self._begin(batch)
+        self.ring.zero_()
         self._close_pool()
-        self._serial += 1
         self._state = RecogState(B, self._serial, torch.zeros((B, 0), dtype=torch.float32, device=self.dev))
         return self._state
 
@@ -311,76 +287,37 @@ class StreamClassifier:
         self._pool = pool
         return pool
 
-    def _check_state(self, state):
-        if state is not self._state or state._serial != self._serial:
-            raise ValueError("this state is not the classifier's current one (start() began another)")
-
-    def _check_audio(self, audio, batch=None) -> torch.Tensor:
-        if isinstance(audio, torch.Tensor):
-            x = audio
-        else:
-            x = torch.as_tensor(np.asarray(audio, dtype=np.float32))
-        if x.dim() != 2:
-            raise ValueError("audio must be [batch, samples], got shape %s" % (tuple(x.shape),))
-        if not 1 <= x.shape[0] <= self.max_batch:
-            raise ValueError("batch %d: this classifier holds max_batch=%d" % (x.shape[0], self.max_batch))
-        if batch is not None and x.shape[0] != batch:
-            raise ValueError("audio of %d streams pushed into a state of %d" % (x.shape[0], batch))
-        return x
-
     def _launch_step(self, B: int, h: int, pool: Optional["ClassifierPool"] = None):
         """The launches of a step of h hops (n = h * hop rows): on the audio staged in ``xbuf`` at the clock, or, with
         `pool`, the same launches in their slot forms on ``pool.table`` -- B is then the pool's capacity and the audio
         comes from the pool's ring, which holds the sample before the chunk too (no carry)."""
-        import ctypes as C_
         w = self.w
         st, dt, R, S, C, L = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk, w.L
-        sfx = "" if pool is None else "_slots"
+        slots = pool is not None
+        sfx = "_slots" if slots else ""
         n, v = h * self.hop, w.view
-        when = self.clock.data_ptr() if pool is None else pool.table.data_ptr()      # the clock, or the table in its place
+        when = pool.table.data_ptr() if slots else self.clock.data_ptr()      # the clock, or the table in its place
         entry = (self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt)
-        if pool is None:
-            call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
-                 v("init_b").data_ptr(), *entry, st)
-        else:
+        if slots:
             call("srwn_recog_stream_in_slots", pool.ring.data_ptr(), pool.audio_ring, v("init_w").data_ptr(),
                  v("init_b").data_ptr(), *entry, when, st)
-        G = len(self.groups)
-        zstride = self.max_batch * C * R
-        for g, (l0, l1) in enumerate(self.groups):
-            last = g + 1 == G
-            out = self.top if last else self.bufs[g + 1]
-            nl = l1 - l0
-            call("srwn_residual_group_fwd_stream_z" + sfx, self.bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
-                 C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1], self.zs[l0].data_ptr(), zstride,
-                 K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
-                 K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
-                 K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
-                 K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                 None, 1, 1, R, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, when, st)
+        else:
+            call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
+                 v("init_b").data_ptr(), *entry, st)
+        self.stack.launch_groups(B, n, when, slots)
         if self.fused:
-            call("srwn_pooled_stream_head" + sfx, self.zs.data_ptr(), zstride, C, L, w.wptr(w.o_skip), w.bs_sum.data_ptr(),
-                 w.wptr(w.o_w1), v("head_b1").data_ptr(), self.ring.data_ptr(), self.ring_rows, when, B, h, self.hop, C, R, S,
-                 dt, st)
-        else:      # the training forward's two products (engine.forward: skip_sum, head_1x1) on the buffers' rows, up to
-            # the last stream's chunk: one launch each, so the stale rows between the streams' chunks ride along (in a pool
-            # also the rows of idle slots and those beyond a slot's ran), and the hop sum never reads them
-            rows = (B - 1) * C + n
-            K.pw_linear(self.zs.data_ptr(), R, zstride, R, L * R, w.wptr(w.o_skip), w.bs_sum, self.r0[:rows], S, S, rows,
-                        pro=K.PRO_GATE, epi=K.EPI_RELU)
-            K.pw_linear(self.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), self.r1[:rows], S, S, rows,
-                        epi=K.EPI_RELU)
+            call("srwn_pooled_stream_head" + sfx, self.stack.zs.data_ptr(), self.max_batch * C * R, C, L, w.wptr(w.o_skip),
+                 w.bs_sum.data_ptr(), w.wptr(w.o_w1), v("head_b1").data_ptr(), self.ring.data_ptr(), self.ring_rows, when, B,
+                 h, self.hop, C, R, S, dt, st)
+        else:      # the hop sum never reads the stale rows that ride along in the two products
+            self._launch_twin_products(B, n)
             call("srwn_hop_sum" + sfx, self.r1.data_ptr(), C, self.ring.data_ptr(), self.ring_rows, when, B, h, self.hop, C, S,
                  dt, st)
         call("srwn_window_mean" + sfx, self.ring.data_ptr(), self.ring_rows, self.mean.data_ptr(), when, B, h, self.hop,
              self.window, S, v("head_w2").data_ptr(), v("head_b2").data_ptr(), self.logits.data_ptr(), w.C, w.Cp, st)
         call("srwn_pooled_head", self.mean.data_ptr(), v("head_w2").data_ptr(), v("head_b2").data_ptr(), None,
              self.probs.data_ptr(), None, None, None, None, B * h, S, w.C, w.Cp, st)
-        if pool is None:
-            call("srwn_recog_roll", self.roll.data_ptr(), G, self.xbuf.data_ptr(), C, self.carry.data_ptr(), when, B, n, C, R,
-                 dt, st)
-        else:
-            call("srwn_recog_roll_slots", self.roll.data_ptr(), G, when, B, n, C, R, dt, st)
+        self._launch_roll(B, n, when, slots)
 
     def push(self, state: RecogState, audio, return_logits: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> probabilities [B, k, C] fp32 of the k window
@@ -455,10 +392,9 @@ class ClassifierPool(AudioRingSlots):
 
     def buffer_bytes(self) -> Dict[str, int]:
         """The classifier's device bytes by buffer family with the pool's additions."""
-        nb = lambda ts: int(sum(t.numel() * t.element_size() for t in ts))
         out = self.c.buffer_bytes()
-        out["pool audio ring"] = nb([self.ring])
-        out["pool stage + table"] = nb([self.stage, self.table])
+        out["pool audio ring"] = nbytes([self.ring])
+        out["pool stage + table"] = nbytes([self.stage, self.table])
         return out
 
     # ---- inspection

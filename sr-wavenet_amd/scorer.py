@@ -8,7 +8,7 @@ which is what the teacher is trained on, without the training engine: no fixed (
 [B, T, 256] logits on their way to the host.
 
 Per step of n <= max_chunk samples the launches are the streaming classifier's with another head: the stream entry
-(``srwn_recog_stream_in``), one ``srwn_residual_group_fwd_stream_z`` per layer group, ``srwn_stream_score_head`` (skip sum,
+(``srwn_recog_stream_in``), one launch per layer group (``StreamStack.launch_groups``), ``srwn_stream_score_head`` (skip sum,
 both head 1x1s, log-softmax and the gather of the target's column in one launch; ``SRWN_SCORE_FUSED=0``: the parity twin,
 three ``srwn_pw_linear`` calls into chunk-sized buffers and ``srwn_nll_rows``) and the roll -- one hipGraph per (B, n).
 
@@ -22,8 +22,9 @@ mixture-of-logistics ``WaveNetTeacher``): nll[b, t] = -log p(audio[b, t] | audio
 as the target.  Its entry is ``srwn_flow_stream_in`` on the chunk as it is (RightShift, entry conv and the first layer's
 conditioning bias at the device clock; its carry, the two samples before the chunk, is staged from the state), its group
 launches carry ``cond_next``, its head is ``srwn_stream_mol_score_head`` (twin: ``srwn_mol_score_rows``), and the encoding
-frames are FED into a conditioning ring while the stream runs (``feed`` / ``room`` / ``available``).  Both scorers share
-``_ScorerBase``: buffers, group plan, graph cache, the cut of a push.
+frames are FED into a conditioning ring while the stream runs (``feed`` / ``room`` / ``available``).  The stack, the staged
+chunk, the clock, the graph cache and the checks of a push are ``stream_stack.StreamHost``'s, shared with the classifier;
+``_ScorerBase`` adds what only the scorers have: the nll and logits buffers, ``start`` and the head's common arguments.
 """
 from __future__ import annotations
 
@@ -31,7 +32,6 @@ import math
 import os
 from typing import Dict, List, Optional, Tuple
 
-import numpy as np
 import torch
 
 from . import kernels as K
@@ -39,6 +39,7 @@ from . import packing as P
 from ._lib import call
 from .engine import WaveNetEngine
 from .recognizer import StackWeights
+from .stream_stack import StreamHost, StreamStack, nbytes
 from .student import live_min_frames, live_room
 
 # What SRWN_SCORE_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
@@ -109,135 +110,56 @@ class ScoreState:
         self.nll_sum = torch.zeros(batch, dtype=torch.float64, device=dev)
 
 
-class _ScorerBase:
-    """What ``StreamScorer`` and ``MolStreamScorer`` share: the boundary buffers of the group plan, the stored z, the
-    clock, the roll table, the twin's buffers, the graph cache, the state's serial and the checks of a push.  A subclass
-    allocates the buffers of its own entry and head, and gives ``_new_state`` and ``_reset``."""
+class _ScorerBase(StreamHost):
+    """What ``StreamScorer`` and ``MolStreamScorer`` add to ``StreamHost``: the nll and logits a step leaves, the twin's fp32
+    logits, ``start`` and the head's common arguments.  A subclass allocates the buffers of its own entry and head, and
+    gives ``_new_state`` and ``_reset``."""
+
+    _noun = "scorer"
 
     def __init__(self, weights, max_batch: int = 1, max_chunk: int = 1600):
         if min(int(max_batch), int(max_chunk)) < 1:
             raise ValueError("max_batch and max_chunk must be >= 1")
-        K._need_gpu()
-        w = self.w = weights
-        self.max_batch, self.max_chunk = int(max_batch), int(max_chunk)
-        self.dev, self.dt = w.dev, w.dt
-        self.groups = K.group_plan(w.dil, 31, int(os.environ.get("SRWN_GROUP_LAYERS", "8")))
-        self.hist = [sum(w.dil[l0:l1]) for l0, l1 in self.groups]
-        Bm, C, R, S, L = self.max_batch, self.max_chunk, w.R, w.S, w.L
-        z = self._zeros
-        self.bufs = [z(Bm, h + C, R) for h in self.hist]      # [hist rows | chunk rows] per group
-        self.top = z(Bm, C, R)                                # the last layer's output: nothing reads it
-        self.zs = z(L, Bm, C, R)
-        self.xbuf = z(Bm, C, dt=torch.float32)                # the chunk as the entry reads it
-        self.carry = z(Bm, dt=torch.float32)
-        self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        self.nll = z(Bm, C, dt=torch.float32)
+        super().__init__(weights, max_batch, max_chunk, os.environ.get("SRWN_SCORE_FUSED", SCORE_FUSED_DEFAULT) != "0")
+        Bm, C = self.max_batch, self.max_chunk
+        self.nll = self._zeros(Bm, C, dt=torch.float32)
         self.logits_out: Optional[torch.Tensor] = None        # [Bm, C, classes] fp32, on the first return_logits
-        self.roll = torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs, self.hist)], dtype=torch.int64,
-                                 device=self.dev)
-        self.fused = os.environ.get("SRWN_SCORE_FUSED", SCORE_FUSED_DEFAULT) != "0"
         if not self.fused:
-            self.r0, self.r1 = z(Bm * C, S), z(Bm * C, S)
-            self.logits32 = z(Bm * C, w.Cp, dt=torch.float32)
-        self.use_graphs = os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
-        self._graphs: Dict[tuple, object] = {}
-        self._seen: set = set()
-        self._serial = 0
-        self._state = None
+            self.logits32 = self._zeros(Bm * C, self.w.Cp, dt=torch.float32)
         self.launches_per_step = 2 + len(self.groups) + (1 if self.fused else 4)
 
-    def _zeros(self, *shape, dt=None):
-        return torch.zeros(shape, dtype=self.dt if dt is None else dt, device=self.dev)
-
-    @staticmethod
-    def _nbytes(ts) -> int:
-        return int(sum(t.numel() * t.element_size() for t in ts if t is not None))
+    def _bytes(self, audio, scores, **more) -> Dict[str, int]:
+        """``buffer_bytes`` of a scorer: its audio and score buffers, and further families between those and the images."""
+        out = dict(self.stack.nbytes(), audio=nbytes(audio), scores=nbytes(scores), **more, images=nbytes([self.w.packed]))
+        if not self.fused:
+            out["twin r0/r1/logits"] = nbytes([self.r0, self.r1, self.logits32])
+        return out
 
     # ------------------------------------------------------------------------------------------------
     def start(self, batch: int = 1):
         """`batch` streams at clock 0: zero history (the conv's zero padding), zero carry, and 0 for the sample before
         the first one (the RightShift's padding)."""
-        B = int(batch)
-        if not 1 <= B <= self.max_batch:
-            raise ValueError("batch %d: this scorer holds max_batch=%d" % (B, self.max_batch))
-        for b in self.bufs:
-            b.zero_()
-        self.carry.zero_(); self.clock.zero_()
+        B = self._begin(batch)
         self._reset()
-        self._serial += 1
         self._state = self._new_state(B)
         return self._state
 
     def _reset(self):
         """What else a new state finds zeroed."""
 
-    def _check_state(self, state):
-        if state is not self._state or state._serial != self._serial:
-            raise ValueError("this state is not the scorer's current one (start() began another)")
-
-    def _check_audio(self, audio, batch=None) -> torch.Tensor:
-        if isinstance(audio, torch.Tensor):
-            x = audio
-        else:
-            x = torch.as_tensor(np.asarray(audio, dtype=np.float32))
-        if x.dim() != 2:
-            raise ValueError("audio must be [batch, samples], got shape %s" % (tuple(x.shape),))
-        if not 1 <= x.shape[0] <= self.max_batch:
-            raise ValueError("batch %d: this scorer holds max_batch=%d" % (x.shape[0], self.max_batch))
-        if batch is not None and x.shape[0] != batch:
-            raise ValueError("audio of %d streams pushed into a state of %d" % (x.shape[0], batch))
-        return x
-
-    def _launch_groups(self, B: int, n: int, cond=None):
-        """One ``srwn_residual_group_fwd_stream_z`` per layer group.  cond: None, or (table address, frames, pool_stride,
-        row stride in elements) of a conditioning ring [B * frames][L * R]: layer g then adds the bias of layer g + 1."""
-        import ctypes as C_
-        w = self.w
-        st, dt, R, C = K._stream(), K.abi_dtype(self.dt), w.R, self.max_chunk
-        v, when, es = w.view, self.clock.data_ptr(), w.packed.element_size()
-        G = len(self.groups)
-        zstride = self.max_batch * C * R
-        for g, (l0, l1) in enumerate(self.groups):
-            last = g + 1 == G
-            out = self.top if last else self.bufs[g + 1]
-            nl = l1 - l0
-            cn, frames, pool, cstride = None, 1, 1, R
-            if cond is not None:
-                table, frames, pool, cstride = cond
-                cn = K._ptr_array([table + (l + 1) * R * es if l + 1 < w.L else None for l in range(l0, l1)])
-            call("srwn_residual_group_fwd_stream_z", self.bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
-                 C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1], self.zs[l0].data_ptr(), zstride,
-                 K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
-                 K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
-                 K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
-                 K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                 cn, frames, pool, cstride, (C_.c_int32 * nl)(*w.dil[l0:l1]), nl, B, n, C, R, w.Kw, dt, when, st)
-
     def _head_args(self):
         """The head's arguments up to the targets: z, the three images and their biases."""
         w = self.w
-        return (self.zs.data_ptr(), self.max_batch * self.max_chunk * w.R, self.max_chunk, w.L, w.wptr(w.o_skip),
+        return (self.stack.zs.data_ptr(), self.max_batch * self.max_chunk * w.R, self.max_chunk, w.L, w.wptr(w.o_skip),
                 w.bs_sum.data_ptr(), w.wptr(w.o_w1), w.view("head_b1").data_ptr(), w.wptr(w.o_w2),
                 w.view("head_b2").data_ptr())
 
     def _launch_twin_products(self, B: int, n: int):
-        """The training forward's three products (engine.forward: skip_sum, head_1x1 and the last 1x1 in fp32) on the
-        buffers' rows up to the last stream's chunk: one launch each, so the stale rows between the streams' chunks ride
-        along, and the twin's last step never reads them."""
-        w, C = self.w, self.max_chunk
-        R, S, L, v = w.R, w.S, w.L, w.view
-        rows = (B - 1) * C + n
-        K.pw_linear(self.zs.data_ptr(), R, self.max_batch * C * R, R, L * R, w.wptr(w.o_skip), w.bs_sum, self.r0[:rows], S, S,
-                    rows, pro=K.PRO_GATE, epi=K.EPI_RELU)
-        K.pw_linear(self.r0.data_ptr(), S, 0, S, S, w.wptr(w.o_w1), v("head_b1"), self.r1[:rows], S, S, rows,
-                    epi=K.EPI_RELU)
-        K.pw_linear(self.r1.data_ptr(), S, 0, S, S, w.wptr(w.o_w2), v("head_b2"), self.logits32[:rows], w.Cp, w.Cp,
+        """``StreamHost``'s two products and the training forward's third, the last 1x1 in fp32."""
+        w, S = self.w, self.w.S
+        rows = super()._launch_twin_products(B, n)
+        K.pw_linear(self.r1.data_ptr(), S, 0, S, S, w.wptr(w.o_w2), w.view("head_b2"), self.logits32[:rows], w.Cp, w.Cp,
                     rows, epi=K.EPI_F32, compute_dtype=self.dt)
-
-    def _launch_roll(self, B: int, n: int):
-        C = self.max_chunk
-        call("srwn_recog_roll", self.roll.data_ptr(), len(self.groups), self.xbuf.data_ptr(), C, self.carry.data_ptr(),
-             self.clock.data_ptr(), B, n, C, self.w.R, K.abi_dtype(self.dt), K._stream())
 
     def _run_step(self, key: tuple, launch):
         K.run_cached_graph(self._graphs, self._seen, key, self.use_graphs, launch)
@@ -255,12 +177,7 @@ class StreamScorer(_ScorerBase):
 
     def buffer_bytes(self) -> Dict[str, int]:
         """Device bytes by buffer family (DESIGN's table)."""
-        nb = self._nbytes
-        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]), "audio": nb([self.xbuf, self.carry, self.codes]),
-               "scores": nb([self.nll, self.best, self.logits_out]), "images": nb([self.w.packed])}
-        if not self.fused:
-            out["twin r0/r1/logits"] = nb([self.r0, self.r1, self.logits32])
-        return out
+        return self._bytes([self.xbuf, self.carry, self.codes], [self.nll, self.best, self.logits_out])
 
     def _new_state(self, B: int) -> ScoreState:
         return ScoreState(B, self._serial, self.dev)
@@ -272,7 +189,7 @@ class StreamScorer(_ScorerBase):
         v = w.view
         call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
              v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt, st)
-        self._launch_groups(B, n)
+        self.stack.launch_groups(B, n, self.clock.data_ptr())
         outs = (self.nll.data_ptr(), self.best.data_ptr() if want_best else None,
                 self.logits_out.data_ptr() if want_logits else None, C, B, n)
         if self.fused:
@@ -280,7 +197,7 @@ class StreamScorer(_ScorerBase):
         else:
             self._launch_twin_products(B, n)
             call("srwn_nll_rows", self.logits32.data_ptr(), w.Cp, C, self.codes.data_ptr(), *outs, w.C, st)
-        self._launch_roll(B, n)
+        self._launch_roll(B, n, self.clock.data_ptr())
 
     def push(self, state: ScoreState, audio, return_logits: bool = False, return_best: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> nll [B, n] fp32 (nats) of exactly those
@@ -434,7 +351,7 @@ class MolStreamScorer(_ScorerBase):
             raise ValueError("max_batch and max_chunk must be >= 1")
         w = weights
         self.E, self.pool = w.E, w.pool
-        self.hist_max = max(sum(w.dil[l0:l1]) for l0, l1 in self._plan(w)) if w.E else 0
+        self.hist_max = max(StreamStack.plan(w.dil)[1]) if w.E else 0
         self.max_frames = int(max_frames) if w.E else 1
         if w.E and self.max_frames < live_min_frames(self.hist_max, self.pool):
             raise ValueError("max_frames %d: a chunk still reads the conditioning of its groups' halo rows, %d samples back; "
@@ -449,20 +366,12 @@ class MolStreamScorer(_ScorerBase):
             self.stage_in = self._zeros(Bm * F, w.Ep)
             self.stage_out = self._zeros(Bm * F, LR)
 
-    @staticmethod
-    def _plan(w):
-        return K.group_plan(w.dil, 31, int(os.environ.get("SRWN_GROUP_LAYERS", "8")))
+    _plan = staticmethod(lambda w: StreamStack.plan(w.dil)[0])      # the groups `w`'s stack will have (the tests size rings by it)
 
     def buffer_bytes(self) -> Dict[str, int]:
         """Device bytes by buffer family (DESIGN's table)."""
-        nb = self._nbytes
-        out = {"boundary": nb(self.bufs) + nb([self.top]), "z": nb([self.zs]),
-               "audio": nb([self.xbuf, self.carry, self.carry2]), "scores": nb([self.nll, self.logits_out]),
-               "conditioning": nb([self.ring] + ([self.stage_in, self.stage_out] if self.E else [])),
-               "images": nb([self.w.packed])}
-        if not self.fused:
-            out["twin r0/r1/logits"] = nb([self.r0, self.r1, self.logits32])
-        return out
+        return self._bytes([self.xbuf, self.carry, self.carry2], [self.nll, self.logits_out],
+                           conditioning=nbytes([self.ring] + ([self.stage_in, self.stage_out] if self.E else [])))
 
     def _new_state(self, B: int) -> MolScoreState:
         return MolScoreState(B, self._serial, self.dev)
@@ -512,11 +421,13 @@ class MolStreamScorer(_ScorerBase):
         before it in ``carry2``."""
         w = self.w
         st, dt, R, S, C = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk
-        v, F, LR = w.view, self.max_frames, self.LR
+        v, F, LR, when = w.view, self.max_frames, self.LR, self.clock.data_ptr()
         call("srwn_flow_stream_in", self.xbuf.data_ptr(), C, self.carry2.data_ptr(), v("init_w").data_ptr(),
              v("init_b").data_ptr(), self.ring.data_ptr(), F, self.pool, LR, self.bufs[0].data_ptr(), self.hist[0] + C,
-             self.hist[0], B, n, C, R, dt, self.clock.data_ptr(), st)
-        self._launch_groups(B, n, (self.ring.data_ptr(), F, self.pool, LR) if self.E else None)
+             self.hist[0], B, n, C, R, dt, when, st)
+        # layer l adds the bias of layer l + 1: its R columns of the ring's rows [L * R]
+        above = [self.ring.data_ptr() + (l + 1) * R * self.ring.element_size() if l + 1 < w.L else None for l in range(w.L)]
+        self.stack.launch_groups(B, n, when, cond=(above, F, self.pool, LR) if self.E else None)
         lo = self.logits_out.data_ptr() if want_logits else None
         if self.fused:
             call("srwn_stream_mol_score_head", *self._head_args(), self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C, B, n,
@@ -525,7 +436,7 @@ class MolStreamScorer(_ScorerBase):
             self._launch_twin_products(B, n)
             call("srwn_mol_score_rows", self.logits32.data_ptr(), w.Cp, C, self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C,
                  B, n, w.M, st)
-        self._launch_roll(B, n)
+        self._launch_roll(B, n, when)
 
     def push(self, state: MolScoreState, audio, return_logits: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> nll [B, n] fp32 (nats) of exactly those

@@ -13,10 +13,13 @@ Mirrors ``ParallelWaveNet`` (model.py:290-537):
   update     tf.clip_by_global_norm(grads, 1.0) then Adam (model.py:382-401, the train_fast path student.py:107 uses)
 
 All flows share one flat fp32 parameter / gradient / Adam buffer (one all-reduce, one norm, one update).
+Inference (``FlowSynthesizer``, ``SynthPool``) runs the flows as chunked streams: one ``stream_stack.StreamStack`` per flow
+(group plan, boundary buffers, roll table, group launches) on a shared top buffer and one clock.
 """
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import replace
 from typing import Dict, List, Optional
 
@@ -28,6 +31,7 @@ from . import kernels as K
 from ._lib import call
 from .engine import SQRT_HALF, Section, StackConfig, WaveNetEngine, _Span
 from .slots import SlotTable, per_stream
+from .stream_stack import StreamStack, stream_history_rows      # (the latter for this module's users)
 
 
 class FlowStorage:
@@ -421,17 +425,9 @@ class StudentEngine:
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# Inference: the flows as a chunked stream (csrc/srwn_stream.hip, srwn_residual_group_fwd_stream).  No teacher, no
-# training buffers: per flow the weights, one boundary buffer per layer group and a conditioning table.
+# Inference: the flows as a chunked stream (csrc/srwn_stream.hip).  No teacher, no training buffers: per flow the weights,
+# a StreamStack (one boundary buffer per layer group) and a conditioning table.
 # ----------------------------------------------------------------------------------------------------------------------
-def stream_history_rows(dilations, groups=None) -> List[int]:
-    """Rows of its own input a layer group must keep between two chunks: the sum of its layers' dilations
-    (= stride x halo of the group kernel), for every group of ``srwn_group_plan``'s cut."""
-    dil = [int(d) for d in dilations]
-    groups = K.group_plan(dil, 31, 8) if groups is None else groups
-    return [sum(dil[l0:l1]) for l0, l1 in groups]
-
-
 def live_room(fed: int, t: int, hist_max: int, pool_stride: int, capacity: int) -> int:
     """How many frames a LIVE stream may be fed now.  Its conditioning tables are rings of ``capacity`` frames: frame f
     lives in row f mod capacity.  A chunk starting at time t recomputes the halo rows of group g back to t - hist_g, so
@@ -465,7 +461,8 @@ class FlowWeights:
         self.cfg = cfg
         self.dev = torch.device(device)
         self.dt = cfg.dtype
-        self.L, self.R, self.Kw, self.E = len(cfg.dilations), cfg.dilation_channels, cfg.filter_width, cfg.cond_channels
+        self.dil = [int(d) for d in cfg.dilations]
+        self.L, self.R, self.Kw, self.E = len(self.dil), cfg.dilation_channels, cfg.filter_width, cfg.cond_channels
         self.S = cfg.skip_channels
         self.Ep = (self.E + 15) // 16 * 16
         self.sections = self.layout(cfg)
@@ -542,16 +539,14 @@ class FlowSynthesizer:
         self.cfg, self.F = cfg, int(num_flows)
         self.max_batch, self.max_chunk, self.max_frames = int(max_batch), int(max_chunk), int(max_frames)
         self.dev, self.dt = torch.device(device), cfg.dtype
-        self.dil = [int(d) for d in cfg.dilations]
-        self.L, self.R, self.E, self.pool_stride = len(self.dil), cfg.dilation_channels, cfg.cond_channels, int(cfg.pool_stride)
-        import os as _os
-        self.groups = K.group_plan(self.dil, 31, int(_os.environ.get("SRWN_GROUP_LAYERS", "8")))
-        self.hist = stream_history_rows(self.dil, self.groups)
+        self.L, self.R, self.E, self.pool_stride = len(cfg.dilations), cfg.dilation_channels, cfg.cond_channels, int(cfg.pool_stride)
         self.weights = [FlowWeights(cfg, self.dev) for _ in range(self.F)]
         Bm, C, R = self.max_batch, self.max_chunk, self.R
         z = lambda *s, dt=self.dt: torch.zeros(s, dtype=dt, device=self.dev)
-        self.bufs = [[z(Bm, h + C, R) for h in self.hist] for _ in range(self.F)]      # [hist rows | chunk rows] per group
-        self.top = z(Bm, C, R)                                                        # a flow's last layer, chunk rows only
+        self.top = z(Bm, C, R)                                # every flow's last layer in its turn, chunk rows only
+        self.stacks = [StreamStack(w, Bm, C, store_z=False, top=self.top) for w in self.weights]
+        self.groups, self.hist = self.stacks[0].groups, self.stacks[0].hist
+        self.bufs, self.roll = [sk.bufs for sk in self.stacks], [sk.roll for sk in self.stacks]
         self.rows_c = Bm * self.max_frames
         self.cond_in = z(self.rows_c, self.weights[0].Ep)
         self.cond_all = [z(self.L, self.rows_c, R) for _ in range(self.F)]
@@ -561,15 +556,13 @@ class FlowSynthesizer:
         self.seeds = torch.zeros(Bm, dtype=torch.int64, device=self.dev)
         self.temps = z(Bm, dt=torch.float32)
         self.clock = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        self.roll = [torch.tensor([[b.data_ptr(), h + C, h] for b, h in zip(self.bufs[i], self.hist)], dtype=torch.int64,
-                                  device=self.dev) for i in range(self.F)]
         self.roll_all = torch.cat(self.roll, 0).contiguous()      # every flow's table in one (a pool join resets through it)
         self._graphs: Dict[tuple, object] = {}
         self._seen: set = set()
         self._serial = 0
         self._state: Optional[SynthState] = None
         self._pool: Optional["SynthPool"] = None
-        self.use_graphs = _os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
+        self.use_graphs = os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0"
         self.launches_per_chunk = 1 + self.F * (2 + len(self.groups))
         for w in self.weights:
             w.repack()
@@ -617,8 +610,7 @@ class FlowSynthesizer:
                 call("srwn_pw_linear_ychunks", self.cond_in.data_ptr(), w.Ep, w.Ep, w.wptr(w.o_wc),
                      w.view("BC").reshape(-1).data_ptr(), self.cond_all[i].data_ptr(), self.R, self.R, self.rows_c * self.R,
                      self.L * self.R, self.L * self.R, self.rows_c, K.abi_dtype(self.dt), st)
-            for b in self.bufs[i]:
-                b.zero_()
+            self.stacks[i].reset()
             self.carry[i].zero_()
         self.clock.zero_()
         self._serial += 1
@@ -693,37 +685,24 @@ class FlowSynthesizer:
 
     def _launch_chunk(self, B: int, n: int, device_noise: bool, pool: Optional["SynthPool"] = None):
         """The 1 + F x (2 + G) launches of a chunk.  pool: the slot forms, on the pool's table instead of the clock."""
-        import ctypes as C_
         st, dt, R, C = K._stream(), K.abi_dtype(self.dt), self.R, self.max_chunk
-        sfx = "" if pool is None else "_slots"
-        ck = self.clock.data_ptr() if pool is None else pool.slots.data_ptr()
+        slots = pool is not None
+        sfx = "_slots" if slots else ""
+        ck = pool.slots.data_ptr() if slots else self.clock.data_ptr()
         if device_noise:
             call("srwn_logistic_noise" + sfx, self.xbuf[0].data_ptr(), C, self.temps.data_ptr(), self.seeds.data_ptr(), ck, B, n, st)
-        G = len(self.groups)
         for i, w in enumerate(self.weights):
-            v, bufs = w.view, self.bufs[i]
-            ca = self.cond_all[i]
+            v, ca = w.view, self.cond_all[i]
             call("srwn_flow_stream_in" + sfx, self.xbuf[i].data_ptr(), C, self.carry[i].data_ptr(), v("init_w").data_ptr(),
-                 v("init_b").data_ptr(), ca[0].data_ptr(), self.max_frames, self.pool_stride, R, bufs[0].data_ptr(),
+                 v("init_b").data_ptr(), ca[0].data_ptr(), self.max_frames, self.pool_stride, R, self.bufs[i][0].data_ptr(),
                  self.hist[0] + C, self.hist[0], B, n, C, R, dt, ck, st)
-            for g, (l0, l1) in enumerate(self.groups):
-                last = g + 1 == G
-                out = self.top if last else bufs[g + 1]
-                nl = l1 - l0
-                cond = [ca[l + 1].data_ptr() if l + 1 < self.L else None for l in range(l0, l1)]
-                call("srwn_residual_group_fwd_stream" + sfx, bufs[g].data_ptr(), self.hist[g] + C, out.data_ptr(),
-                     C if last else self.hist[g + 1] + C, 0 if last else self.hist[g + 1],
-                     K._ptr_array([w.wptr(w.o_conv[l]) for l in range(l0, l1)]),
-                     K._ptr_array([w.wptr(w.o_res[l]) for l in range(l0, l1)]),
-                     K._ptr_array([v("BF")[l].data_ptr() for l in range(l0, l1)]),
-                     K._ptr_array([v("BR")[l].data_ptr() for l in range(l0, l1)]),
-                     K._ptr_array(cond), self.max_frames, self.pool_stride, R, (C_.c_int32 * nl)(*self.dil[l0:l1]), nl, B, n, C, R,
-                     self.cfg.filter_width, dt, ck, st)
+            above = [ca[l + 1].data_ptr() if l + 1 < self.L else None for l in range(self.L)]      # layer l adds layer l + 1's
+            self.stacks[i].launch_groups(B, n, ck, slots, (above, self.max_frames, self.pool_stride, R))
             lastf = i + 1 == self.F
-            tail = (ck,) if pool is None else (ck, pool.arrive.data_ptr())
+            tail = (ck, pool.arrive.data_ptr()) if slots else (ck,)
             call("srwn_flow_stream_out" + sfx, self.top.data_ptr(), C, v("flow_w").data_ptr(), v("flow_b").data_ptr(),
                  self.xbuf[i].data_ptr(), self.xbuf[i + 1].data_ptr(), C, self.carry[i].data_ptr(), 1 if lastf else 0,
-                 self.roll[i].data_ptr(), G, B, n, C, R, dt, *tail, 1 if lastf else 0, st)
+                 self.roll[i].data_ptr(), len(self.groups), B, n, C, R, dt, *tail, 1 if lastf else 0, st)
 
     def step(self, state: SynthState, n: int, noise=None) -> torch.Tensor:
         """The next n samples of every stream: [B, n] fp32 in [-1, 1].  noise [B, n]: the first flow's input instead of the
