@@ -1402,6 +1402,52 @@ int srwn_stream_mol_score_head(const void* z, int64_t z_layer_stride, int64_t z_
 int srwn_mol_score_rows(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const float* x, int64_t x_stride,
                         float* nll, float* logits_out, int64_t out_stride, int32_t B, int32_t n, int32_t M, void* stream);
 
+/* ---- scorer pools (since srwn_version() 118; csrc/srwn_score.hip): the launches of the softmax streaming scorer above
+ * (116) for `capacity` SLOTS over one set of buffers, every slot a stream at a clock of its own.  The device table
+ * slots[capacity] of SrwnSynthSlot replaces the clock, with the meaning it has for the classifier pools (115): t is the
+ * absolute time of the slot's next sample (t >= 0), and the slot owns ran(u) = clamp(t_end - t, 0, n) rows of a chunk of n
+ * -- here ANY number of rows, not a multiple of anything.  The HOST writes the whole table before every step (t = the
+ * samples the slot has scored, t_end = t + the samples the step gives it) and no launch modifies it.  A slot with ran = 0
+ * touches nothing.  A step is the entry below, one srwn_residual_group_fwd_stream_z_slots per layer group, the head below
+ * (or the twin: three srwn_pw_linear products over (capacity - 1) * max_chunk + n rows, in which stale rows ride along
+ * and are never read, then srwn_nll_rows_slots) and srwn_recog_roll_slots; a join zeroes the history rows of the joined
+ * slots with srwn_flow_stream_reset_slots (ncarry = 0).  A stream has the bits the clock forms give a batch of one: in any
+ * slot, whenever it joined, however its audio was cut, whatever n the steps had and whatever the other slots hold.  Every
+ * grid depends on (capacity, n) alone, so a captured graph serves every step of its n.
+ *
+ *   srwn_score_stream_in_slots    the pool's entry, one launch over the pool's audio ring [capacity][ring_len] fp32 (sample
+ *                                 s of a slot in column s mod ring_len, the layout srwn_audio_ring_put writes).  For row i <
+ *                                 ran(u) of slot u, s = slots[u].t + i: (a) row out_hist + i of the first boundary buffer
+ *                                 `out` [capacity][out_clip_rows][R] = b + w0 a[s-2] + w1 a[s-1] in srwn_recog_stream_in's
+ *                                 arithmetic and rounding on the delayed audio (the teacher's RightShift folded into the
+ *                                 read: no staged delayed copy, no carry; samples before time 0 read as 0), and (b)
+ *                                 codes[u * codes_stride + i] = the mu-law code of a[s] over C classes, the bits of
+ *                                 srwn_mu_law_encode (one device routine serves both).  ring_len >= max_chunk + 2, so that
+ *                                 a[t-2] is still there beside a whole chunk; codes_stride >= max_chunk.  2 <= C <= 256.
+ *                                 Other rows of out and codes are not touched.
+ *   srwn_stream_score_head_slots  srwn_stream_score_head with one workgroup per (slot u, 32-row tile i < ceil(n / 32)) that
+ *                                 returns before its first barrier when 32 * i >= ran(u) and otherwise runs the clock form's
+ *                                 body (one device body, the SLOTS instantiation of the same kernel template) with ran(u)
+ *                                 in the place of n: a masked last tile re-reads the slot's last own row and stores
+ *                                 nothing.  Rows >= ran(u) of nll, best and logits_out are not touched.
+ *   srwn_nll_rows_slots           the parity twin's last step on the fp32 logits, as srwn_nll_rows is
+ *                                 srwn_stream_score_head's: the same grid and the same early return.
+ * Errors, all before any launch: empty work (capacity * n == 0) is done (0); a null pointer (-3; best and logits_out may be
+ * NULL); a width or a class count that is not built (-4); capacity < 0, n < 0 or a chunk, a buffer or a ring that does
+ * not fit (-2; ring_len < max_chunk + 2 among them); dtype (-1). */
+int srwn_score_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w, const float* init_b, void* out,
+                               int64_t out_clip_rows, int32_t out_hist, int32_t* codes, int64_t codes_stride,
+                               int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t C, int32_t dtype,
+                               const SrwnSynthSlot* slots, void* stream);
+int srwn_stream_score_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                 const void* wskip, const float* bs_sum, const void* w1, const float* b1, const void* w2,
+                                 const float* b2, const int32_t* codes, float* nll, int32_t* best, float* logits_out,
+                                 int64_t out_stride, int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t S,
+                                 int32_t C, int32_t dtype, const SrwnSynthSlot* slots, void* stream);
+int srwn_nll_rows_slots(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const int32_t* codes, float* nll,
+                        int32_t* best, float* logits_out, int64_t out_stride, int32_t capacity, int32_t n, int32_t C,
+                        const SrwnSynthSlot* slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -271,6 +271,12 @@ SIGNATURES["srwn_nll_rows"] = (C.c_int, [_p, _i64, _i64, _p, _p, _p, _p, _i64, _
 SIGNATURES["srwn_stream_mol_score_head"] = (C.c_int, [_p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _i64,
                                                       _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p])
 SIGNATURES["srwn_mol_score_rows"] = (C.c_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _i32, _i32, _i32, _p])
+# scorer pools (srwn_version() 118): the pool's entry (first stack row and target codes from the audio ring, one launch) and
+# the slot forms of the softmax score head and of its twin's last step: the table of SrwnSynthSlot in front of the stream
+SIGNATURES["srwn_score_stream_in_slots"] = (C.c_int, [_p, _i32, _p, _p, _p, _i64, _i32, _p, _i64, _i32, _i32, _i32, _i32, _i32,
+                                                      _i32, _p, _p])
+SIGNATURES["srwn_stream_score_head_slots"] = (C.c_int, SIGNATURES["srwn_stream_score_head"][1][:-1] + [_p, _p])
+SIGNATURES["srwn_nll_rows_slots"] = (C.c_int, SIGNATURES["srwn_nll_rows"][1][:-1] + [_p, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

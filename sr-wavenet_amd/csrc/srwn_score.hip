@@ -17,9 +17,21 @@
 //   mol score head   the score head through the logits (ONE device body, score_head_logits, serves both kernels; the 4M
 //                    logits are Cp = 32 or 64 columns in a small LDS block), then row_mol_nll on the undelayed audio
 //   mol score rows   its parity twin, row_mol_nll on a logits buffer in HBM
+//
+// Scorer pools (srwn.h, srwn_version() 118): the softmax scorer's `capacity` rows as slots on the pool's table of
+// SrwnSynthSlot, each a stream at a clock of its own with ran = slot_rows(slots[u], n) rows in a chunk of n.
+//   pool entry       srwn_score_stream_in_slots: one launch over the pool's audio ring writes the first boundary buffer's
+//                    chunk rows from a[s - 2] and a[s - 1] (the RightShift folded into the read: srwn_recog_stream_in's
+//                    arithmetic on the delayed audio, no staged copy, no carry) AND the target codes mu_law(a[s])
+//                    (srwn_mulaw.h: the routine of srwn_mu_law_encode)
+//   slot forms       of the score head and of nll rows: the SLOTS instantiations of the same kernel templates; a workgroup
+//                    whose tile starts at or behind ran returns before its first barrier, the others run the clock form's
+//                    body with ran in the place of n
 #include <cmath>
 #include "srwn_common.h"
 #include "srwn_host.h"
+#include "srwn_mulaw.h"
+#include "srwn_slots.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -31,6 +43,63 @@ constexpr int kMaxClasses = 256;
 constexpr int kLogitStride = kMaxClasses + 4; // fp32 elements per row of the LDS logits block (16-byte rows, banks 4 apart)
 constexpr int kMaxMixtures = 16;              // 4M <= 64 columns: two 32-column tiles, two mixtures per lane of row_mol_nll
 constexpr int kMolStride = 4 * kMaxMixtures + 4;      // the same rule for the mixture head's LDS logits block
+
+// What a SLOTS instantiation takes behind the clock form's arguments: the pool's table.  The kernels take it as a parameter
+// pack TABLE... that is empty in the clock forms, whose argument lists so stay exactly what they were; the host bodies
+// carry it as a SlotsArg.
+template <bool SLOTS> struct SlotsArg {};
+template <> struct SlotsArg<true> { const SrwnSynthSlot* table; };
+__device__ __forceinline__ const SrwnSynthSlot* table_of(const SrwnSynthSlot* table) { return table; }
+
+// rows slot u has in a chunk of n (a negative clock: none)
+__device__ __forceinline__ int ran_of(const SrwnSynthSlot* table, int u, int n) {
+  const SrwnSynthSlot sl = table[u];
+  return sl.t < 0 ? 0 : slot_rows(sl, n);
+}
+
+// ------------------------------------------------------------------------------------------
+// pool entry: recog_stream_in_kernel's thread map (8 channels per thread, one row per group of R/8 lanes) on the pool's
+// audio ring [capacity][ring_len], sample s of a slot in column s mod ring_len.  Row i < ran(u) of slot u, s = slots[u].t + i:
+//   v = b; v = fma(a[s-2], w[0], v); v = fma(a[s-1], w[1], v); round to T     (srwn_recog_stream_in on the delayed audio;
+//                                                                              samples before time 0 read as 0)
+//   codes[u][i] = mu_law_encode_one(a[s])                                     (the row's first thread)
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void score_stream_in_slots_kernel(const float* __restrict__ ring, int ring_len,
+                                                                    const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, T* __restrict__ out,
+                                                                    int64_t out_clip_rows, int hist,
+                                                                    int32_t* __restrict__ codes, int64_t codes_stride,
+                                                                    int B, int n, int R, float mu, float log1p_mu,
+                                                                    const SrwnSynthSlot* __restrict__ slots) {
+  const int lpr = R / 8;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = idx / lpr;
+  const int sub = (int)(idx % lpr);
+  if (row >= (int64_t)B * n) return;
+  const int b = (int)(row / n);
+  const int t = (int)(row - (int64_t)b * n);
+  const SrwnSynthSlot sl = slots[b];
+  if (sl.t < 0 || t >= slot_rows(sl, n)) return;
+  const float* xb = ring + (int64_t)b * ring_len;
+  const long long s = sl.t + t;
+  const int c2 = (int)(s % ring_len);                          // a[s]; (ring_len >= 3: the two columns before it differ)
+  const int c1 = c2 > 0 ? c2 - 1 : ring_len - 1;
+  const int c0 = c1 > 0 ? c1 - 1 : ring_len - 1;
+  const float x0 = s >= 2 ? xb[c0] : 0.0f;
+  const float x1 = s >= 1 ? xb[c1] : 0.0f;
+  if (sub == 0) codes[(int64_t)b * codes_stride + t] = mu_law_encode_one(xb[c2], mu, log1p_mu);
+  T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    v[j] = bias[8 * sub + j];
+    v[j] = fmaf(x0, w[8 * sub + j], v[j]);
+    v[j] = fmaf(x1, w[R + 8 * sub + j], v[j]);
+  }
+  store4(d, v[0], v[1], v[2], v[3]);
+  store4(d + 4, v[4], v[5], v[6], v[7]);
+}
 
 // ------------------------------------------------------------------------------------------
 // One row of logits -> nll = log(sum_c exp(l[c] - max)) + max - l[code] and the argmax (lowest index on ties), over the
@@ -243,7 +312,9 @@ __device__ __forceinline__ void score_head_logits(const T* __restrict__ z, int64
   *b_out = b; *t0_out = t0; *valid_out = valid;
 }
 
-template <typename T, int R, int S>
+// SLOTS (srwn_stream_score_head_slots): stream b is slot b of the pool's table with ran(b) rows in the place of n; the
+// workgroup of a tile that starts at or behind ran(b) returns here, before the first barrier (workgroup-uniform).
+template <typename T, int R, int S, bool SLOTS = false, typename... TABLE>
 __global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
                                                                  int64_t z_clip_rows, int L, const T* __restrict__ wskip,
                                                                  const float* __restrict__ bs_sum,
@@ -252,7 +323,12 @@ __global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restr
                                                                  const int32_t* __restrict__ codes,
                                                                  float* __restrict__ nll, int32_t* __restrict__ best,
                                                                  float* __restrict__ logits_out, int64_t out_stride, int n,
-                                                                 int ntiles, int C) {
+                                                                 int ntiles, int C, TABLE... table) {
+  static_assert(sizeof...(TABLE) == (SLOTS ? 1 : 0), "the table, in the slot form only");
+  if constexpr (SLOTS) {
+    n = ran_of(table_of(table...), (int)blockIdx.x / ntiles, n);
+    if (32 * ((int)blockIdx.x % ntiles) >= n) return;
+  }
   extern __shared__ __attribute__((aligned(16))) char score_lds[];
   T* xch = reinterpret_cast<T*>(score_lds);
   float* lg = reinterpret_cast<float*>(score_lds + xch_bytes<T, S>());
@@ -299,10 +375,17 @@ __global__ __launch_bounds__(256) void mol_stream_score_head_kernel(const T* __r
 // nll rows (parity twin): logits [B][clip_rows][ld] fp32 of the chunk -> nll, best and the copy of the C real columns.
 // The score head's grid and its thread-to-row map, row_nll on the row in HBM.
 // ------------------------------------------------------------------------------------------
+// SLOTS (srwn_nll_rows_slots): as in the score head.
+template <bool SLOTS = false, typename... TABLE>
 __global__ __launch_bounds__(256) void nll_rows_kernel(const float* __restrict__ logits, int64_t ld, int64_t clip_rows,
                                                        const int32_t* __restrict__ codes, float* __restrict__ nll,
                                                        int32_t* __restrict__ best, float* __restrict__ logits_out,
-                                                       int64_t out_stride, int n, int ntiles, int C) {
+                                                       int64_t out_stride, int n, int ntiles, int C, TABLE... table) {
+  static_assert(sizeof...(TABLE) == (SLOTS ? 1 : 0), "the table, in the slot form only");
+  if constexpr (SLOTS) {
+    n = ran_of(table_of(table...), (int)blockIdx.x / ntiles, n);
+    if (32 * ((int)blockIdx.x % ntiles) >= n) return;
+  }
   const int b = (int)blockIdx.x / ntiles, t0 = 32 * ((int)blockIdx.x % ntiles);
   const int valid = n - t0 < 32 ? n - t0 : 32;
   const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
@@ -357,29 +440,46 @@ int check_rows(const char* who, const HeadRows& r, int32_t B, int32_t n, int64_t
   return rows_args(who, B, n, MOL ? 4 * r.width : r.width, clip_rows, r.out_stride);
 }
 
-template <bool MOL, typename T, int R, int S>
+template <bool MOL, bool SLOTS, typename T, int R, int S>
 int launch_score_head(const char* who, const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int L, const void* wskip,
                       const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
-                      const HeadRows& r, int B, int n, hipStream_t st) {
+                      const HeadRows& r, int B, int n, SlotsArg<SLOTS> slots, hipStream_t st) {
   constexpr int sh = xch_bytes<T, S>() + (MOL ? kMolLogitBytes : kLogitBytes);
   const int ntiles = (n + 31) / 32;
-  auto launch = [&](auto kfn, auto... rows) {
+  auto launch = [&](auto kfn, auto... rows) {      // rows: what the kernel takes behind b2
     if (sh > 32768) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, sh);
     hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
-                       (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, rows..., n, ntiles, r.width);
+                       (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, rows...);
   };
-  if constexpr (MOL) launch(mol_stream_score_head_kernel<T, R, S>, r.x, r.x_stride, r.nll, r.logits_out, r.out_stride);
-  else launch(stream_score_head_kernel<T, R, S>, r.codes, r.nll, r.best, r.logits_out, r.out_stride);
+  if constexpr (MOL)
+    launch(mol_stream_score_head_kernel<T, R, S>, r.x, r.x_stride, r.nll, r.logits_out, r.out_stride, n, ntiles, r.width);
+  else if constexpr (SLOTS)
+    launch(stream_score_head_kernel<T, R, S, true, const SrwnSynthSlot*>, r.codes, r.nll, r.best, r.logits_out, r.out_stride, n,
+           ntiles, r.width, slots.table);
+  else
+    launch(stream_score_head_kernel<T, R, S>, r.codes, r.nll, r.best, r.logits_out, r.out_stride, n, ntiles, r.width);
   return check_launch(who);
 }
 
-template <bool MOL>
+// The slot forms (SLOTS: B is the pool's capacity, `slots` its table) report empty work (capacity * n == 0) as done and a
+// class count that is not built as such (-4), both before anything else of theirs.
+int slot_form_first(const char* who, const SrwnSynthSlot* table, int C) {
+  if (!table) return set_error(SRWN_E_NULL, "%s: null pointer (slots is the pool's device table)", who);
+  if (C < 1 || C > kMaxClasses) return set_error(SRWN_E_UNSUPPORTED, "%s: %d classes (built: 1..%d)", who, C, kMaxClasses);
+  return 0;
+}
+
+template <bool MOL, bool SLOTS = false>
 int score_head_impl(const char* who, const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
                     const void* wskip, const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
                     const HeadRows& r, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype,
-                    void* stream) {
+                    void* stream, SlotsArg<SLOTS> slots = {}) {
+  static_assert(!(MOL && SLOTS), "the slot form is the softmax head's");
+  if (SLOTS && (B == 0 || n == 0)) return 0;
   if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !r.target(MOL) || !r.nll)
     return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if constexpr (SLOTS)
+    if (const int rc = slot_form_first(who, slots.table, r.width)) return rc;
   if ((R != 32 && R != 64) || (S != 128 && S != 256))
     return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
   if (max_chunk < 1 || n > max_chunk || z_clip_rows < max_chunk)
@@ -389,8 +489,8 @@ int score_head_impl(const char* who, const void* z, int64_t z_layer_stride, int6
   if (nlayers < 1 || z_layer_stride < (int64_t)B * z_clip_rows * R)
     return set_error(SRWN_E_SHAPE, "%s: %d layers at a stride of %lld", who, nlayers, (long long)z_layer_stride);
 #define SRWN_SSH(TT, RR, SS)                                                                                               \
-  return launch_score_head<MOL, TT, RR, SS>(who, z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, b2, r, \
-                                            B, n, (hipStream_t)stream)
+  return launch_score_head<MOL, SLOTS, TT, RR, SS>(who, z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1, w2, \
+                                                   b2, r, B, n, slots, (hipStream_t)stream)
 #define SRWN_SSH_T(TT)                                       \
   {                                                          \
     if (R == 32 && S == 128) SRWN_SSH(TT, 32, 128);          \
@@ -405,10 +505,14 @@ int score_head_impl(const char* who, const void* z, int64_t z_layer_stride, int6
   return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
 }
 
-template <bool MOL>
+template <bool MOL, bool SLOTS = false>
 int score_rows_impl(const char* who, const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const HeadRows& r,
-                    int32_t B, int32_t n, void* stream) {
+                    int32_t B, int32_t n, void* stream, SlotsArg<SLOTS> slots = {}) {
+  static_assert(!(MOL && SLOTS), "the slot form is the softmax twin's");
+  if (SLOTS && (B == 0 || n == 0)) return 0;
   if (!logits || !r.target(MOL) || !r.nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if constexpr (SLOTS)
+    if (const int rc = slot_form_first(who, slots.table, r.width)) return rc;
   if (const int rc = check_rows<MOL>(who, r, B, n, logits_clip_rows)) return rc;
   if (logits_ld < (MOL ? 4 * r.width : r.width))
     return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d %s", who, (long long)logits_ld, r.width,
@@ -418,9 +522,43 @@ int score_rows_impl(const char* who, const float* logits, int64_t logits_ld, int
   if constexpr (MOL)
     hipLaunchKernelGGL(mol_score_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.x,
                        r.x_stride, r.nll, r.logits_out, r.out_stride, n, ntiles, r.width);
+  else if constexpr (SLOTS)
+    hipLaunchKernelGGL((nll_rows_kernel<true, const SrwnSynthSlot*>), grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
+                       logits_clip_rows, r.codes, r.nll, r.best, r.logits_out, r.out_stride, n, ntiles, r.width, slots.table);
   else
-    hipLaunchKernelGGL(nll_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.codes,
+    hipLaunchKernelGGL(nll_rows_kernel<>, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.codes,
                        r.nll, r.best, r.logits_out, r.out_stride, n, ntiles, r.width);
+  return check_launch(who);
+}
+
+// The pool entry's host body: srwn_recog_stream_in_slots' checks with the ring one sample longer (a[t - 2]) and the codes.
+int score_stream_in_slots_impl(const char* who, const float* ring, int32_t ring_len, const float* init_w, const float* init_b,
+                               void* out, int64_t out_clip_rows, int32_t out_hist, int32_t* codes, int64_t codes_stride,
+                               int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t C, int32_t dtype,
+                               const SrwnSynthSlot* slots, void* stream) {
+  if (capacity == 0 || n == 0) return 0;
+  if (!ring || !init_w || !init_b || !out || !codes || !slots) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d (built: 32, 64)", who, R);
+  if (C < 2 || C > kMaxClasses) return set_error(SRWN_E_UNSUPPORTED, "%s: %d classes (built: 2..%d)", who, C, kMaxClasses);
+  if (capacity < 1 || max_chunk < 1 || out_hist < 0)
+    return set_error(SRWN_E_SHAPE, "%s: capacity=%d max_chunk=%d out_hist=%d", who, capacity, max_chunk, out_hist);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "%s: chunk of %d rows (1..max_chunk = %d)", who, n, max_chunk);
+  // (the ring also holds the two samples before a whole chunk)
+  if (ring_len < (int64_t)max_chunk + 2 || out_clip_rows < (int64_t)out_hist + max_chunk || codes_stride < max_chunk)
+    return set_error(SRWN_E_SHAPE, "%s: an audio ring of %d samples for max_chunk + 2 = %lld, %lld buffer rows per slot for %d + %d, "
+                     "%lld codes per slot", who, ring_len, (long long)max_chunk + 2, (long long)out_clip_rows, out_hist, max_chunk,
+                     (long long)codes_stride);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+  const int64_t threads = (int64_t)capacity * n * (R / 8);
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const float mu = (float)(C - 1), l1p = (float)log1p((double)mu);      // (srwn_mu_law_encode's constants)
+  if (dtype == SRWN_BF16)
+    hipLaunchKernelGGL(score_stream_in_slots_kernel<bf16_t>, grid, block, 0, st, ring, ring_len, init_w, init_b, (bf16_t*)out,
+                       out_clip_rows, out_hist, codes, codes_stride, capacity, n, R, mu, l1p, slots);
+  else
+    hipLaunchKernelGGL(score_stream_in_slots_kernel<float>, grid, block, 0, st, ring, ring_len, init_w, init_b, (float*)out,
+                       out_clip_rows, out_hist, codes, codes_stride, capacity, n, R, mu, l1p, slots);
   return check_launch(who);
 }
 
@@ -458,4 +596,32 @@ extern "C" int srwn_mol_score_rows(const float* logits, int64_t logits_ld, int64
                                    int32_t M, void* stream) {
   return score_rows_impl<true>("mol_score_rows", logits, logits_ld, logits_clip_rows,
                                HeadRows{nullptr, x, x_stride, nll, nullptr, logits_out, out_stride, M}, B, n, stream);
+}
+
+// ---- scorer pools (srwn.h, srwn_version() 118): each names itself and says which form it is
+extern "C" int srwn_score_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w, const float* init_b,
+                                          void* out, int64_t out_clip_rows, int32_t out_hist, int32_t* codes,
+                                          int64_t codes_stride, int32_t capacity, int32_t n, int32_t max_chunk, int32_t R,
+                                          int32_t C, int32_t dtype, const SrwnSynthSlot* slots, void* stream) {
+  return score_stream_in_slots_impl("score_stream_in_slots", audio_ring, ring_len, init_w, init_b, out, out_clip_rows, out_hist,
+                                    codes, codes_stride, capacity, n, max_chunk, R, C, dtype, slots, stream);
+}
+
+extern "C" int srwn_stream_score_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                            const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                            const void* w2, const float* b2, const int32_t* codes, float* nll, int32_t* best,
+                                            float* logits_out, int64_t out_stride, int32_t capacity, int32_t n,
+                                            int32_t max_chunk, int32_t R, int32_t S, int32_t C, int32_t dtype,
+                                            const SrwnSynthSlot* slots, void* stream) {
+  return score_head_impl<false, true>("stream_score_head_slots", z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1, b1,
+                                      w2, b2, HeadRows{codes, nullptr, 0, nll, best, logits_out, out_stride, C}, capacity, n,
+                                      max_chunk, R, S, dtype, stream, SlotsArg<true>{slots});
+}
+
+extern "C" int srwn_nll_rows_slots(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const int32_t* codes,
+                                   float* nll, int32_t* best, float* logits_out, int64_t out_stride, int32_t capacity,
+                                   int32_t n, int32_t C, const SrwnSynthSlot* slots, void* stream) {
+  return score_rows_impl<false, true>("nll_rows_slots", logits, logits_ld, logits_clip_rows,
+                                      HeadRows{codes, nullptr, 0, nll, best, logits_out, out_stride, C}, capacity, n, stream,
+                                      SlotsArg<true>{slots});
 }

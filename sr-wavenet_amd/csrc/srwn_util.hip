@@ -2,6 +2,7 @@
 // input-conv weight gradient, loss reduction.  gfx950 only.
 #include "srwn_common.h"
 #include "srwn_host.h"
+#include "srwn_mulaw.h"
 #include "../../include/srwn.h"
 
 using namespace srwn;
@@ -25,7 +26,7 @@ int check_launch(const char* what) {
 }
 }  // namespace srwn
 
-extern "C" int srwn_version(void) { return 117; }
+extern "C" int srwn_version(void) { return 118; }
 extern "C" const char* srwn_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------------
@@ -35,14 +36,7 @@ __global__ void mu_law_encode_kernel(const float* __restrict__ audio, int32_t* _
                                      float mu, float log1p_mu) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float a = audio[i];
-  float safe = fminf(fabsf(a), 1.0f);                              // ops.py:88
-  float lm = (float)log1p((double)__fmul_rn(mu, safe));             // correctly rounded f32 log1p
-  float magnitude = __fdiv_rn(lm, log1p_mu);                        // ops.py:89
-  float sgn = (a > 0.0f) ? 1.0f : ((a < 0.0f) ? -1.0f : 0.0f);      // tf.sign
-  float signal = __fmul_rn(sgn, magnitude);                         // ops.py:90
-  float q = __fadd_rn(__fmul_rn(__fdiv_rn(__fadd_rn(signal, 1.0f), 2.0f), mu), 0.5f);  // ops.py:92
-  codes[i] = (int32_t)q;                                            // tf.to_int32 truncates
+  codes[i] = mu_law_encode_one(audio[i], mu, log1p_mu);             // (srwn_mulaw.h: shared with the scorer pool's entry)
 }
 
 __global__ void mu_law_decode_kernel(const int32_t* __restrict__ codes, float* __restrict__ audio, int64_t n,

@@ -352,6 +352,12 @@ class StreamingScorer(object):
     def stream(self, batch_size=1):
         return ScorerStream(self, self._eng.start(batch_size))
 
+    def pool(self, audio_ring=None):
+        """A ``ScorerStreamPool``: this scorer's ``max_batch`` rows as slots that streams join and leave, each pushing audio
+        of any length at a clock of its own (``scorer.ScorerPool``).  audio_ring: samples a slot can hold (default 2 *
+        max_chunk + 2).  Ends the current ``ScorerStream``; ``stream`` and ``score`` end the pool."""
+        return ScorerStreamPool(self._eng.pool(audio_ring))
+
 
 class ScorerStream(object):
     """NumPy face of one running batch of scorer streams (``StreamingScorer.stream``).  ``t``: samples scored per
@@ -1584,6 +1590,26 @@ class ClassifierPool(_AudioPoolFace):
         out = self._pool.step(return_logits)
         host = lambda d: {u: f.cpu().numpy() for u, f in d.items()}
         return (host(out[0]), host(out[1])) if return_logits else host(out)
+
+
+class ScorerStreamPool(_AudioPoolFace):
+    """NumPy face of a scorer pool (``StreamingScorer.pool``; scorer.ScorerPool).  ``join`` returns slots, ``push(slots,
+    audio)`` takes one 1-D array per slot, of any length, ``step()`` returns ``{slot: nll [m]}`` (nats) for every slot whose
+    stream scored m > 0 samples (with return_logits / return_best further dicts, in that order).  A stream's nll put
+    together is ``StreamingScorer.score`` of its audio alone."""
+
+    audio_ring = property(lambda self: self._pool.audio_ring)
+    scored = property(lambda self: self._pool.scored)
+    nll_sum = property(lambda self: self._pool.nll_sum)
+
+    def bits_per_sample(self, slot):
+        """The running mean nll of the stream in `slot`, in bits (NaN before its first sample)."""
+        return self._pool.bits_per_sample(int(slot))
+
+    def step(self, return_logits=False, return_best=False):
+        out = self._pool.step(return_logits, return_best)
+        host = lambda d: {u: f.cpu().numpy() for u, f in d.items()}
+        return tuple(host(d) for d in out) if isinstance(out, tuple) else host(out)
 
 
 class ParallelWaveNet(object):

@@ -17,6 +17,13 @@ step stages x'[0] = the sample before the chunk (0 at the stream's start) and x'
 two taps then read a[t-2] and a[t-1] for row t -- the generator's input conv.  A row depends on absolute time only: a
 stream has the same bits however its audio was cut, at any batch size and in any row of the batch.
 
+``StreamScorer.pool()`` turns the scorer's ``max_batch`` rows into SLOTS (``ScorerPool``): streams join and leave, each
+pushes audio of any length at a clock of its own, and one step scores every sample that waits with the same launches in
+their slot forms (srwn.h, srwn_version() 118) on a table the host writes before every step.  There is ONE launch list,
+``StreamScorer._launch_step(B, n, ..., pool=None)``: with a pool it picks the ``_slots`` entry points and the pool's table in
+the clock's place, and the pool's entry ``srwn_score_stream_in_slots`` reads a[t-2], a[t-1] and the target a[t] straight
+from the pool's audio ring -- no staged delayed copy, no carry, no separate mu-law launch.
+
 ``MolStreamScorer`` is the same stream for the conditioned mixture-of-logistics decoder (the ``WaveNetAutoEncoder``'s, and the
 mixture-of-logistics ``WaveNetTeacher``): nll[b, t] = -log p(audio[b, t] | audio[b, < t], encoding) with the audio itself
 as the target.  Its entry is ``srwn_flow_stream_in`` on the chunk as it is (RightShift, entry conv and the first layer's
@@ -32,11 +39,13 @@ import math
 import os
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import kernels as K
 from . import packing as P
 from ._lib import call
+from .audio_ring import AudioRingSlots
 from .engine import WaveNetEngine
 from .recognizer import StackWeights
 from .stream_stack import StreamHost, StreamStack, nbytes
@@ -44,6 +53,25 @@ from .student import live_min_frames, live_room
 
 # What SRWN_SCORE_FUSED means when it is not set: "1" the one-launch head, "0" the parity twin.
 SCORE_FUSED_DEFAULT = "1"
+
+
+def plan_score_pool_step(received, scored, active, max_chunk: int) -> Tuple[int, np.ndarray]:
+    """One step of a scorer pool: (n, rows [capacity]).  rows[u] = min(received[u] - scored[u], max_chunk) samples for an
+    active slot and 0 for any other; n = 0 when nothing waits, else rows.max() rounded up to a multiple of 32 and capped at
+    max_chunk: the rows of the step's launches, so a pool captures at most ceil(max_chunk / 32) graphs.  The device reads
+    each slot's true row count from the table: n changes no bit.  Pure NumPy: the CPU tests hold it to brute force."""
+    received, scored = np.asarray(received, np.int64), np.asarray(scored, np.int64)
+    active = np.asarray(active, bool)
+    max_chunk = int(max_chunk)
+    if max_chunk < 1:
+        raise ValueError("plan_score_pool_step: max_chunk=%d" % max_chunk)
+    if received.ndim != 1 or received.shape != scored.shape or received.shape != active.shape:
+        raise ValueError("plan_score_pool_step: received, scored and active are [capacity] each")
+    if np.any(active & ((scored < 0) | (scored > received))):
+        raise ValueError("plan_score_pool_step: a slot has scored more than it received")
+    rows = np.where(active, np.minimum(max_chunk, received - scored), 0).astype(np.int64)
+    most = int(rows.max()) if rows.size else 0
+    return min((most + 31) // 32 * 32, max_chunk), rows
 
 
 def cut_push(n: int, max_chunk: int) -> List[Tuple[int, int]]:
@@ -170,10 +198,38 @@ class StreamScorer(_ScorerBase):
     ``score`` for whole recordings.  A step of n rows is one hipGraph per (batch, n, outputs wanted), captured when it is
     used a second time (SRWN_MODEL_GRAPHS=0: eager launches)."""
 
+    _pool: Optional["ScorerPool"] = None
+
     def __init__(self, weights: ScorerWeights, max_batch: int = 1, max_chunk: int = 1600):
         super().__init__(weights, max_batch, max_chunk)
         self.codes = self._zeros(self.max_batch, self.max_chunk, dt=torch.int32)
         self.best = self._zeros(self.max_batch, self.max_chunk, dt=torch.int32)
+
+    def start(self, batch: int = 1):
+        """``_ScorerBase.start``; the pool, if one is open, ends."""
+        st = super().start(batch)
+        self._close_pool()
+        return st
+
+    def _close_pool(self):
+        if self._pool is not None:
+            self._pool._open = False
+            self._pool = None
+
+    def pool(self, audio_ring: Optional[int] = None) -> "ScorerPool":
+        """A ``ScorerPool`` on this scorer's buffers: its ``max_batch`` rows as slots, each a stream at a clock of its own.
+        audio_ring: samples a slot's audio ring holds (default 2 * max_chunk + 2, at least max_chunk + 2).  The current
+        ``ScoreState`` ends, and an earlier pool; ``start`` and ``score`` end the pool."""
+        pool = ScorerPool(self, audio_ring)
+        self._close_pool()
+        self._serial += 1
+        self._state = None
+        self._pool = pool
+        return pool
+
+    def _want_logits(self):
+        if self.logits_out is None:
+            self.logits_out = torch.zeros((self.max_batch, self.max_chunk, self.w.C), dtype=torch.float32, device=self.dev)
 
     def buffer_bytes(self) -> Dict[str, int]:
         """Device bytes by buffer family (DESIGN's table)."""
@@ -182,22 +238,34 @@ class StreamScorer(_ScorerBase):
     def _new_state(self, B: int) -> ScoreState:
         return ScoreState(B, self._serial, self.dev)
 
-    def _launch_step(self, B: int, n: int, want_logits: bool = False, want_best: bool = False):
-        """The launches of a step of n rows on the delayed audio staged in ``xbuf`` and the targets in ``codes``."""
+    def _launch_step(self, B: int, n: int, want_logits: bool = False, want_best: bool = False,
+                     pool: Optional["ScorerPool"] = None):
+        """The launches of a step of n rows: on the delayed audio staged in ``xbuf`` and the targets in ``codes`` at the
+        clock, or, with `pool`, the same launches in their slot forms on ``pool.table`` -- B is then the pool's capacity,
+        and the pool's entry reads the audio ring (the two samples before the chunk too: no staged delayed copy, no carry)
+        and writes ``codes`` itself."""
         w = self.w
         st, dt, R, S, C = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk
         v = w.view
-        call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), v("init_w").data_ptr(),
-             v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0], B, n, C, R, dt, st)
-        self.stack.launch_groups(B, n, self.clock.data_ptr())
+        slots = pool is not None
+        sfx = "_slots" if slots else ""
+        when = pool.table.data_ptr() if slots else self.clock.data_ptr()      # the clock, or the table in its place
+        table = (when,) if slots else ()
+        entry = (v("init_w").data_ptr(), v("init_b").data_ptr(), self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0])
+        if slots:
+            call("srwn_score_stream_in_slots", pool.ring.data_ptr(), pool.audio_ring, *entry, self.codes.data_ptr(), C, B, n, C,
+                 R, w.C, dt, when, st)
+        else:
+            call("srwn_recog_stream_in", self.xbuf.data_ptr(), C, self.carry.data_ptr(), *entry, B, n, C, R, dt, st)
+        self.stack.launch_groups(B, n, when, slots)
         outs = (self.nll.data_ptr(), self.best.data_ptr() if want_best else None,
                 self.logits_out.data_ptr() if want_logits else None, C, B, n)
         if self.fused:
-            call("srwn_stream_score_head", *self._head_args(), self.codes.data_ptr(), *outs, C, R, S, w.C, dt, st)
+            call("srwn_stream_score_head" + sfx, *self._head_args(), self.codes.data_ptr(), *outs, C, R, S, w.C, dt, *table, st)
         else:
             self._launch_twin_products(B, n)
-            call("srwn_nll_rows", self.logits32.data_ptr(), w.Cp, C, self.codes.data_ptr(), *outs, w.C, st)
-        self._launch_roll(B, n, self.clock.data_ptr())
+            call("srwn_nll_rows" + sfx, self.logits32.data_ptr(), w.Cp, C, self.codes.data_ptr(), *outs, w.C, *table, st)
+        self._launch_roll(B, n, when, slots)
 
     def push(self, state: ScoreState, audio, return_logits: bool = False, return_best: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> nll [B, n] fp32 (nats) of exactly those
@@ -208,8 +276,8 @@ class StreamScorer(_ScorerBase):
         x = self._check_audio(audio, state.B).to(device=self.dev, dtype=torch.float32).contiguous()
         B, n_all, Cc = state.B, int(x.shape[1]), self.w.C
         want_logits, want_best = bool(return_logits), bool(return_best)
-        if want_logits and self.logits_out is None:
-            self.logits_out = torch.zeros((self.max_batch, self.max_chunk, Cc), dtype=torch.float32, device=self.dev)
+        if want_logits:
+            self._want_logits()
         nll = torch.empty((B, n_all), dtype=torch.float32, device=self.dev)
         logits = torch.empty((B, n_all, Cc), dtype=torch.float32, device=self.dev) if want_logits else None
         best = torch.empty((B, n_all), dtype=torch.int32, device=self.dev) if want_best else None
@@ -235,6 +303,136 @@ class StreamScorer(_ScorerBase):
         one ends)."""
         x = self._check_audio(audio)
         return self.push(self.start(int(x.shape[0])), x, return_logits, return_best)
+
+
+class ScorerPool(AudioRingSlots):
+    """``StreamScorer.pool()``: the scorer's ``max_batch`` rows as SLOTS, each holding a stream with its own samples
+    ``received`` and samples ``scored``.  Streams ``join`` free slots (history rows zeroed by srwn_flow_stream_reset_slots),
+    ``push`` audio of any length whenever it arrives (``AudioRingSlots.push``: one upload and one srwn_audio_ring_put
+    however many slots are written) and ``step`` scores every sample that waits: per pass ``plan_score_pool_step``, the table
+    [t = scored, t_end = t + rows] uploaded whole, and the launches of one scorer step in their slot forms
+    (``StreamScorer._launch_step`` with this pool) -- one hipGraph per (n, outputs wanted), captured at second use.  A step
+    runs no mu-law launch and makes no delayed copy: the pool's entry reads a[t-2], a[t-1] and the target a[t] from the
+    ring.  The device never advances the table.  A stream's nll put together equals ``StreamScorer(max_batch=1).score`` of its
+    audio alone, bit for bit: in any slot, whenever it joined, however its audio was cut, whatever n the steps had and
+    whatever the other slots hold or held before."""
+
+    def __init__(self, owner: StreamScorer, audio_ring: Optional[int] = None):
+        c = self.c = owner
+        self.capacity, self.max_chunk = c.max_batch, c.max_chunk
+        self.audio_ring = 2 * c.max_chunk + 2 if audio_ring is None else int(audio_ring)
+        if self.audio_ring < c.max_chunk + 2:
+            raise ValueError("pool: audio_ring %d holds less than max_chunk + 2 = %d samples (a whole step and the two "
+                             "samples before it)" % (self.audio_ring, c.max_chunk + 2))
+        self._alloc_audio_ring()
+        cap = self.capacity
+        self._received = np.zeros(cap, np.int64)
+        self._scored = np.zeros(cap, np.int64)
+        self._active = np.zeros(cap, bool)
+        self.table = torch.zeros((cap, 2), dtype=torch.int64, device=self.dev)      # SrwnSynthSlot [t, t_end] per slot
+        self._nll_sum = torch.zeros(cap, dtype=torch.float64, device=self.dev)      # per slot, on the device: no step waits for it
+        self._cols = torch.arange(c.max_chunk, dtype=torch.int64, device=self.dev).unsqueeze(0)
+        self._graphs: Dict[tuple, object] = {}
+        self._seen: set = set()
+        self._open = True
+        self.launches_per_step = c.launches_per_step      # the same launches in their slot forms (+ the table's upload)
+
+    def buffer_bytes(self) -> Dict[str, int]:
+        """The scorer's device bytes by buffer family with the pool's additions."""
+        out = self.c.buffer_bytes()
+        out["pool audio ring"] = nbytes([self.ring])
+        out["pool stage + table"] = nbytes([self.stage, self.table])
+        return out
+
+    # ---- inspection
+    dev = property(lambda self: self.c.dev, doc="The scorer's device.")
+    received = property(lambda self: self._received.copy(), doc="Samples pushed into each slot's stream so far.")
+    scored = property(lambda self: self._scored.copy(), doc="Samples of each slot's stream scored so far.")
+    nll_sum = property(lambda self: self._nll_sum.cpu().numpy().copy(),
+                       doc="The sum of every nll each slot's stream has returned (nats, fp64 [capacity]; 0 at its join).")
+
+    def bits_per_sample(self, slot: int) -> float:
+        """The running mean nll of the stream in `slot`, in bits (NaN before its first sample)."""
+        u, = self._slot_list(slot, "bits_per_sample")
+        return bits_per_sample(float(self._nll_sum[u]), int(self._scored[u]))
+
+    def _check_open(self):
+        if not self._open:
+            raise ValueError("this pool is closed (the scorer started a batch or opened another pool)")
+
+    def audio_room(self, slot: int) -> int:
+        """Samples a slot can take now: audio_ring - 2 minus what waits to be scored (the - 2 keeps the samples scored - 1
+        and scored - 2, the entry conv's taps before the next chunk, alive)."""
+        u, = self._slot_list(slot, "audio_room")
+        return int(self.audio_ring - 2 - (self._received[u] - self._scored[u]))
+
+    # ---- streams come and go
+    def join(self, n: int = 1, slots=None) -> List[int]:
+        """n streams into free slots (the lowest ones, or `slots`); returns the slots.  A slot starts at sample 0 with
+        zeroed history rows and a zero ``nll_sum``."""
+        self._check_open()
+        slots = self._take_slots(int(n) if slots is None else None, slots)
+        c = self.c
+        ids = torch.tensor(slots, dtype=torch.int32, device=c.dev)
+        call("srwn_flow_stream_reset_slots", c.roll.data_ptr(), c.roll.shape[0], None, 0, 0, ids.data_ptr(), len(slots),
+             self.capacity, c.w.R, K.abi_dtype(c.dt), K._stream())
+        self._nll_sum.index_fill_(0, ids.long(), 0.0)
+        for u in slots:
+            self._received[u] = self._scored[u] = 0
+            self._active[u] = True
+        return list(slots)
+
+    def leave(self, slots) -> None:
+        """Ends the streams in `slots` where they are (a slot already free stays free) and frees their slots."""
+        self._check_open()
+        for u in self._slot_list(slots, "leave", distinct=True):
+            self._active[u] = False
+
+    def push(self, slots, audio) -> None:
+        """``AudioRingSlots.push`` into an open pool: audio[i], 1-D of any length (0 too), behind what slots[i] received."""
+        self._check_open()
+        super().push(slots, audio)
+
+    def _room_tail(self, u):
+        return "scored %d" % self._scored[u]
+
+    # ---- one step: every sample that waits
+    def step(self, return_logits: bool = False, return_best: bool = False):
+        """Runs while any active slot has a sample waiting -> {slot: nll [m] fp32 on the device} for the slots whose
+        streams scored m > 0 samples; with return_logits also {slot: logits [m, C]}, with return_best also {slot: the most
+        likely code [m] int32}, in that order (a tuple of dicts).  With nothing waiting nothing is launched."""
+        self._check_open()
+        c, cap = self.c, self.capacity
+        want_logits, want_best = bool(return_logits), bool(return_best)
+        pn, pl, pb = {}, {}, {}
+        while True:
+            n, rows = plan_score_pool_step(self._received, self._scored, self._active, self.max_chunk)
+            if n == 0:
+                break
+            if want_logits:
+                c._want_logits()
+            self.table.copy_(torch.from_numpy(np.stack([self._scored, self._scored + rows], 1)))
+            K.run_cached_graph(self._graphs, self._seen, (n, want_logits, want_best), c.use_graphs,
+                               lambda: c._launch_step(cap, n, want_logits, want_best, self))
+            # one copy per pass: the next pass writes the same buffers
+            nll = c.nll[:cap, :n].clone()
+            logits = c.logits_out[:cap, :n].clone() if want_logits else None
+            best = c.best[:cap, :n].clone() if want_best else None
+            live = self._cols[:, :n] <(self.table[:, 1] - self.table[:, 0]).unsqueeze(1)      # [cap, n]: the slots' own rows
+            self._nll_sum += torch.where(live, nll, 0.0).sum(1, dtype=torch.float64)
+            for u in np.flatnonzero(rows):
+                m = int(rows[u])
+                pn.setdefault(int(u), []).append(nll[u, :m])
+                if want_logits:
+                    pl.setdefault(int(u), []).append(logits[u, :m])
+                if want_best:
+                    pb.setdefault(int(u), []).append(best[u, :m])
+            self._scored += rows
+        cat = lambda p: p[0] if len(p) == 1 else torch.cat(p, dim=0)
+        out = {u: cat(p) for u, p in pn.items()}
+        res = (out,) + (({u: cat(p) for u, p in pl.items()},) if want_logits else ()) \
+            + (({u: cat(p) for u, p in pb.items()},) if want_best else ())
+        return res if len(res) > 1 else out
 
 
 # ---- the conditioned mixture-of-logistics decoder ------------------------------------------------------------------------
