@@ -1448,6 +1448,62 @@ int srwn_nll_rows_slots(const float* logits, int64_t logits_ld, int64_t logits_c
                         int32_t* best, float* logits_out, int64_t out_stride, int32_t capacity, int32_t n, int32_t C,
                         const SrwnSynthSlot* slots, void* stream);
 
+/* ---- mixture-of-logistics scorer pools (since srwn_version() 119; csrc/srwn_score.hip): the launches of the streaming
+ * likelihood scorer of the mixture-of-logistics decoder above (117) for `capacity` SLOTS over one set of buffers, every slot
+ * a stream at a clock of its own AND with a conditioning ring of its own.  The device table slots[capacity] of SrwnSynthSlot
+ * replaces the clock with the meaning it has for the scorer pools (118): t is the absolute time of the slot's next sample
+ * (t >= 0), and the slot owns ran(u) = clamp(t_end - t, 0, n) rows of a chunk of n, any number.  The HOST writes the whole
+ * table before every step (t = the samples the slot has scored, t_end = t + the samples the step gives it: at most what it
+ * has received, and for a conditioned decoder at most fed(u) * pool_stride) and no launch modifies it.  A slot with ran = 0
+ * touches nothing.  A step is the entry below, one srwn_residual_group_fwd_stream_z_slots per layer group with cond_next
+ * set, the head below (or the twin: three srwn_pw_linear products over (capacity - 1) * max_chunk + n rows, in which stale
+ * rows ride along and are never read, then srwn_mol_score_rows_slots) and srwn_recog_roll_slots; a join zeroes the history
+ * rows of the joined slots with srwn_flow_stream_reset_slots (ncarry = 0).  The conditioning table is the ring of 117,
+ * [capacity * cond_frames][nlayers * R]: frame q of slot u in row u * cond_frames + q mod cond_frames, fed by srwn_pw_linear
+ * and srwn_cond_ring_scatter_slots (ragged: any number of frames per slot in one launch) under the room rule of 117 with the
+ * slot's own fed and t.  A join need not clear a slot's ring rows: a stream reads only frames it was fed.  A stream has
+ * the bits the clock forms give a batch of one: in any slot, whenever it joined, however its audio and its frames were cut,
+ * whatever n the steps had and whatever the other slots hold.  Every grid depends on (capacity, n) alone, so a captured
+ * graph serves every step of its n.
+ *
+ *   srwn_mol_score_stream_in_slots    the pool's entry, one launch over the pool's audio ring [capacity][ring_len] fp32
+ *                                     (sample s of a slot in column s mod ring_len, the layout srwn_audio_ring_put writes).
+ *                                     For row i < ran(u) of slot u, s = slots[u].t + i: (a) row out_hist + i of the first
+ *                                     boundary buffer `out` [capacity][out_clip_rows][R] = round(b + w0 a[s-2] + w1 a[s-1])
+ *                                     + cond0 row u * cond_frames + (s / pool_stride) mod cond_frames, rounded again: the
+ *                                     RightShift, the K = 2 entry conv and the first layer's conditioning bias with the bits
+ *                                     srwn_flow_stream_in_slots gives the same row for the same chunk in x, the two samples
+ *                                     before it in carry and the same table (one device routine serves both; samples before
+ *                                     time 0 read as 0; no carry buffer, no staged copy of the chunk), and (b) x_out[u *
+ *                                     x_stride + i] = a[s], the row's target, not delayed, for the head below.  ring_len >=
+ *                                     max_chunk + 2, so that a[s-2] is still there beside a whole chunk; x_stride >=
+ *                                     max_chunk; cond0, cond_frames, pool_stride and cond_row_stride as srwn_flow_stream_in
+ *                                     takes them (an unconditioned decoder passes its one zero row per slot with cond_frames
+ *                                     = 1).  Other rows of out and x_out are not touched.
+ *   srwn_stream_mol_score_head_slots  srwn_stream_mol_score_head with one workgroup per (slot u, 32-row tile i < ceil(n /
+ *                                     32)) that returns before its first barrier when 32 * i >= ran(u) and otherwise runs the
+ *                                     clock form's body (the SLOTS instantiation of the same kernel template) with ran(u) in
+ *                                     the place of n: a masked last tile re-reads the slot's last own row and stores
+ *                                     nothing.  Rows >= ran(u) of nll and logits_out are not touched.
+ *   srwn_mol_score_rows_slots         the parity twin's last step on the fp32 logits, as srwn_mol_score_rows is
+ *                                     srwn_stream_mol_score_head's: the same grid and the same early return.
+ * Errors, all before any launch: empty work (capacity * n == 0) is done (0); a null pointer (-3; logits_out may be NULL); a
+ * width that is not built (-4); M outside [1, 16], capacity < 0, n < 0 or a chunk, a buffer or a ring that does not fit
+ * (-2; ring_len < max_chunk + 2 among them); dtype (-1). */
+int srwn_mol_score_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w, const float* init_b,
+                                   const void* cond0, int32_t cond_frames, int32_t pool_stride, int64_t cond_row_stride,
+                                   void* out, int64_t out_clip_rows, int32_t out_hist, float* x_out, int64_t x_stride,
+                                   int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
+                                   const SrwnSynthSlot* slots, void* stream);
+int srwn_stream_mol_score_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                     const void* wskip, const float* bs_sum, const void* w1, const float* b1, const void* w2,
+                                     const float* b2, const float* x, int64_t x_stride, float* nll, float* logits_out,
+                                     int64_t out_stride, int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t S,
+                                     int32_t M, int32_t dtype, const SrwnSynthSlot* slots, void* stream);
+int srwn_mol_score_rows_slots(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const float* x,
+                              int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int32_t capacity, int32_t n,
+                              int32_t M, const SrwnSynthSlot* slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,12 @@ SIGNATURES["srwn_score_stream_in_slots"] = (C.c_int, [_p, _i32, _p, _p, _p, _i64
                                                       _i32, _p, _p])
 SIGNATURES["srwn_stream_score_head_slots"] = (C.c_int, SIGNATURES["srwn_stream_score_head"][1][:-1] + [_p, _p])
 SIGNATURES["srwn_nll_rows_slots"] = (C.c_int, SIGNATURES["srwn_nll_rows"][1][:-1] + [_p, _p])
+# mixture-of-logistics scorer pools (srwn_version() 119): the pool's entry (first stack row with its conditioning bias and
+# the target samples from the audio ring, one launch) and the slot forms of the mixture head and of its twin's last step
+SIGNATURES["srwn_mol_score_stream_in_slots"] = (C.c_int, [_p, _i32, _p, _p, _p, _i32, _i32, _i64, _p, _i64, _i32, _p, _i64,
+                                                          _i32, _i32, _i32, _i32, _i32, _p, _p])
+SIGNATURES["srwn_stream_mol_score_head_slots"] = (C.c_int, SIGNATURES["srwn_stream_mol_score_head"][1][:-1] + [_p, _p])
+SIGNATURES["srwn_mol_score_rows_slots"] = (C.c_int, SIGNATURES["srwn_mol_score_rows"][1][:-1] + [_p, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -27,8 +27,15 @@
 //   slot forms       of the score head and of nll rows: the SLOTS instantiations of the same kernel templates; a workgroup
 //                    whose tile starts at or behind ran returns before its first barrier, the others run the clock form's
 //                    body with ran in the place of n
+//
+// Mixture-of-logistics scorer pools (srwn.h, srwn_version() 119): the same for the conditioned mixture-of-logistics scorer.
+//   pool entry       srwn_mol_score_stream_in_slots: one launch over the pool's audio ring writes the first boundary buffer's
+//                    chunk rows from a[s - 2], a[s - 1] and the slot's conditioning ring (flow_entry_row, srwn_flow_in.h: the
+//                    routine of srwn_flow_stream_in -- no staged chunk, no carry) AND the targets x_out = a[s]
+//   slot forms       of the mol score head and of mol score rows: the SLOTS instantiations, as above
 #include <cmath>
 #include "srwn_common.h"
+#include "srwn_flow_in.h"
 #include "srwn_host.h"
 #include "srwn_mulaw.h"
 #include "srwn_slots.h"
@@ -99,6 +106,44 @@ __global__ __launch_bounds__(256) void score_stream_in_slots_kernel(const float*
   }
   store4(d, v[0], v[1], v[2], v[3]);
   store4(d + 4, v[4], v[5], v[6], v[7]);
+}
+
+// ------------------------------------------------------------------------------------------
+// mixture-of-logistics pool entry: the thread map above on the same ring.  Row i < ran(u) of slot u, s = slots[u].t + i:
+//   out row = flow_entry_row(a[s-2], a[s-1], cond ring row u * cond_frames + (s / pool) mod cond_frames)
+//                                                                             (srwn_flow_stream_in's arithmetic and bits;
+//                                                                              samples before time 0 read as 0)
+//   x_out[u][i] = a[s]                                                        (the row's first thread: the target, not delayed)
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void mol_score_stream_in_slots_kernel(const float* __restrict__ ring, int ring_len,
+                                                                        const float* __restrict__ w,
+                                                                        const float* __restrict__ bias,
+                                                                        const T* __restrict__ cond, int cond_frames, int pool,
+                                                                        int64_t cond_stride, T* __restrict__ out,
+                                                                        int64_t out_clip_rows, int hist,
+                                                                        float* __restrict__ x_out, int64_t x_stride, int B,
+                                                                        int n, int R,
+                                                                        const SrwnSynthSlot* __restrict__ slots) {
+  const int lpr = R / 8;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t row = idx / lpr;
+  const int sub = (int)(idx % lpr);
+  if (row >= (int64_t)B * n) return;
+  const int b = (int)(row / n);
+  const int t = (int)(row - (int64_t)b * n);
+  const SrwnSynthSlot sl = slots[b];
+  if (sl.t < 0 || t >= slot_rows(sl, n)) return;
+  const float* xb = ring + (int64_t)b * ring_len;
+  const long long s = sl.t + t;
+  const int c2 = (int)(s % ring_len);                          // a[s]; (ring_len >= 3: the two columns before it differ)
+  const int c1 = c2 > 0 ? c2 - 1 : ring_len - 1;
+  const int c0 = c1 > 0 ? c1 - 1 : ring_len - 1;
+  const float x0 = s >= 2 ? xb[c0] : 0.0f;
+  const float x1 = s >= 1 ? xb[c1] : 0.0f;
+  if (sub == 0) x_out[(int64_t)b * x_stride + t] = xb[c2];
+  flow_entry_row<T>(x0, x1, w, bias, cond, cond_frames, pool, cond_stride, b, s,
+                    out, (int64_t)b * out_clip_rows + hist + t, R, sub);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -349,7 +394,8 @@ __global__ __launch_bounds__(256) void stream_score_head_kernel(const T* __restr
 // ------------------------------------------------------------------------------------------
 constexpr int kMolLogitBytes = 32 * kMolStride * (int)sizeof(float);
 
-template <typename T, int R, int S>
+// SLOTS (srwn_stream_mol_score_head_slots): as in the score head.
+template <typename T, int R, int S, bool SLOTS = false, typename... TABLE>
 __global__ __launch_bounds__(256) void mol_stream_score_head_kernel(const T* __restrict__ z, int64_t z_layer_stride,
                                                                      int64_t z_clip_rows, int L, const T* __restrict__ wskip,
                                                                      const float* __restrict__ bs_sum,
@@ -357,7 +403,13 @@ __global__ __launch_bounds__(256) void mol_stream_score_head_kernel(const T* __r
                                                                      const T* __restrict__ w2, const float* __restrict__ b2,
                                                                      const float* __restrict__ x, int64_t x_stride,
                                                                      float* __restrict__ nll, float* __restrict__ logits_out,
-                                                                     int64_t out_stride, int n, int ntiles, int M) {
+                                                                     int64_t out_stride, int n, int ntiles, int M,
+                                                                     TABLE... table) {
+  static_assert(sizeof...(TABLE) == (SLOTS ? 1 : 0), "the table, in the slot form only");
+  if constexpr (SLOTS) {
+    n = ran_of(table_of(table...), (int)blockIdx.x / ntiles, n);
+    if (32 * ((int)blockIdx.x % ntiles) >= n) return;
+  }
   extern __shared__ __attribute__((aligned(16))) char score_lds[];
   T* xch = reinterpret_cast<T*>(score_lds);
   float* lg = reinterpret_cast<float*>(score_lds + xch_bytes<T, S>());
@@ -396,10 +448,18 @@ __global__ __launch_bounds__(256) void nll_rows_kernel(const float* __restrict__
 }
 
 // mol score rows (parity twin): nll_rows_kernel's grid and thread-to-row map, row_mol_nll on the row in HBM.
+// SLOTS (srwn_mol_score_rows_slots): as in the score head.
+template <bool SLOTS = false, typename... TABLE>
 __global__ __launch_bounds__(256) void mol_score_rows_kernel(const float* __restrict__ logits, int64_t ld, int64_t clip_rows,
                                                              const float* __restrict__ x, int64_t x_stride,
                                                              float* __restrict__ nll, float* __restrict__ logits_out,
-                                                             int64_t out_stride, int n, int ntiles, int M) {
+                                                             int64_t out_stride, int n, int ntiles, int M,
+                                                             TABLE... table) {
+  static_assert(sizeof...(TABLE) == (SLOTS ? 1 : 0), "the table, in the slot form only");
+  if constexpr (SLOTS) {
+    n = ran_of(table_of(table...), (int)blockIdx.x / ntiles, n);
+    if (32 * ((int)blockIdx.x % ntiles) >= n) return;
+  }
   const int b = (int)blockIdx.x / ntiles, t0 = 32 * ((int)blockIdx.x % ntiles);
   const int valid = n - t0 < 32 ? n - t0 : 32;
   const int row = (int)threadIdx.x / kRowLanes, sub = (int)threadIdx.x % kRowLanes;
@@ -451,7 +511,10 @@ int launch_score_head(const char* who, const void* z, int64_t z_layer_stride, in
     hipLaunchKernelGGL(kfn, dim3((unsigned)(B * ntiles)), dim3(256), sh, st, (const T*)z, z_layer_stride, z_clip_rows, L,
                        (const T*)wskip, bs_sum, (const T*)w1, b1, (const T*)w2, b2, rows...);
   };
-  if constexpr (MOL)
+  if constexpr (MOL && SLOTS)
+    launch(mol_stream_score_head_kernel<T, R, S, true, const SrwnSynthSlot*>, r.x, r.x_stride, r.nll, r.logits_out, r.out_stride,
+           n, ntiles, r.width, slots.table);
+  else if constexpr (MOL)
     launch(mol_stream_score_head_kernel<T, R, S>, r.x, r.x_stride, r.nll, r.logits_out, r.out_stride, n, ntiles, r.width);
   else if constexpr (SLOTS)
     launch(stream_score_head_kernel<T, R, S, true, const SrwnSynthSlot*>, r.codes, r.nll, r.best, r.logits_out, r.out_stride, n,
@@ -461,11 +524,14 @@ int launch_score_head(const char* who, const void* z, int64_t z_layer_stride, in
   return check_launch(who);
 }
 
-// The slot forms (SLOTS: B is the pool's capacity, `slots` its table) report empty work (capacity * n == 0) as done and a
-// class count that is not built as such (-4), both before anything else of theirs.
+// The slot forms (SLOTS: B is the pool's capacity, `slots` its table) report empty work (capacity * n == 0) as done and, the
+// softmax ones, a class count that is not built as such (-4), both before anything else of theirs.  (The mixture forms
+// leave their mixture count to check_rows: -2, as in the clock forms.)
+template <bool MOL>
 int slot_form_first(const char* who, const SrwnSynthSlot* table, int C) {
   if (!table) return set_error(SRWN_E_NULL, "%s: null pointer (slots is the pool's device table)", who);
-  if (C < 1 || C > kMaxClasses) return set_error(SRWN_E_UNSUPPORTED, "%s: %d classes (built: 1..%d)", who, C, kMaxClasses);
+  if (!MOL && (C < 1 || C > kMaxClasses))
+    return set_error(SRWN_E_UNSUPPORTED, "%s: %d classes (built: 1..%d)", who, C, kMaxClasses);
   return 0;
 }
 
@@ -474,12 +540,11 @@ int score_head_impl(const char* who, const void* z, int64_t z_layer_stride, int6
                     const void* wskip, const float* bs_sum, const void* w1, const float* b1, const void* w2, const float* b2,
                     const HeadRows& r, int32_t B, int32_t n, int32_t max_chunk, int32_t R, int32_t S, int32_t dtype,
                     void* stream, SlotsArg<SLOTS> slots = {}) {
-  static_assert(!(MOL && SLOTS), "the slot form is the softmax head's");
   if (SLOTS && (B == 0 || n == 0)) return 0;
   if (!z || !wskip || !bs_sum || !w1 || !b1 || !w2 || !b2 || !r.target(MOL) || !r.nll)
     return set_error(SRWN_E_NULL, "%s: null pointer", who);
   if constexpr (SLOTS)
-    if (const int rc = slot_form_first(who, slots.table, r.width)) return rc;
+    if (const int rc = slot_form_first<MOL>(who, slots.table, r.width)) return rc;
   if ((R != 32 && R != 64) || (S != 128 && S != 256))
     return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d, skip_channels %d (built: 32 / 64 x 128 / 256)", who, R, S);
   if (max_chunk < 1 || n > max_chunk || z_clip_rows < max_chunk)
@@ -508,19 +573,22 @@ int score_head_impl(const char* who, const void* z, int64_t z_layer_stride, int6
 template <bool MOL, bool SLOTS = false>
 int score_rows_impl(const char* who, const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const HeadRows& r,
                     int32_t B, int32_t n, void* stream, SlotsArg<SLOTS> slots = {}) {
-  static_assert(!(MOL && SLOTS), "the slot form is the softmax twin's");
   if (SLOTS && (B == 0 || n == 0)) return 0;
   if (!logits || !r.target(MOL) || !r.nll) return set_error(SRWN_E_NULL, "%s: null pointer", who);
   if constexpr (SLOTS)
-    if (const int rc = slot_form_first(who, slots.table, r.width)) return rc;
+    if (const int rc = slot_form_first<MOL>(who, slots.table, r.width)) return rc;
   if (const int rc = check_rows<MOL>(who, r, B, n, logits_clip_rows)) return rc;
   if (logits_ld < (MOL ? 4 * r.width : r.width))
     return set_error(SRWN_E_SHAPE, "%s: rows of %lld logits for %d %s", who, (long long)logits_ld, r.width,
                      MOL ? "mixtures" : "classes");
   const int ntiles = (n + 31) / 32;
   const dim3 grid((unsigned)(B * ntiles));
-  if constexpr (MOL)
-    hipLaunchKernelGGL(mol_score_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.x,
+  if constexpr (MOL && SLOTS)
+    hipLaunchKernelGGL((mol_score_rows_kernel<true, const SrwnSynthSlot*>), grid, dim3(256), 0, (hipStream_t)stream, logits,
+                       logits_ld, logits_clip_rows, r.x, r.x_stride, r.nll, r.logits_out, r.out_stride, n, ntiles, r.width,
+                       slots.table);
+  else if constexpr (MOL)
+    hipLaunchKernelGGL(mol_score_rows_kernel<>, grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld, logits_clip_rows, r.x,
                        r.x_stride, r.nll, r.logits_out, r.out_stride, n, ntiles, r.width);
   else if constexpr (SLOTS)
     hipLaunchKernelGGL((nll_rows_kernel<true, const SrwnSynthSlot*>), grid, dim3(256), 0, (hipStream_t)stream, logits, logits_ld,
@@ -559,6 +627,42 @@ int score_stream_in_slots_impl(const char* who, const float* ring, int32_t ring_
   else
     hipLaunchKernelGGL(score_stream_in_slots_kernel<float>, grid, block, 0, st, ring, ring_len, init_w, init_b, (float*)out,
                        out_clip_rows, out_hist, codes, codes_stride, capacity, n, R, mu, l1p, slots);
+  return check_launch(who);
+}
+
+// The mixture pool entry's host body: srwn_flow_stream_in_slots' checks with the ring in the place of the staged chunk and
+// its carry, and the targets.
+int mol_score_stream_in_slots_impl(const char* who, const float* ring, int32_t ring_len, const float* init_w,
+                                   const float* init_b, const void* cond0, int32_t cond_frames, int32_t pool_stride,
+                                   int64_t cond_row_stride, void* out, int64_t out_clip_rows, int32_t out_hist, float* x_out,
+                                   int64_t x_stride, int32_t capacity, int32_t n, int32_t max_chunk, int32_t R, int32_t dtype,
+                                   const SrwnSynthSlot* slots, void* stream) {
+  if (capacity == 0 || n == 0) return 0;
+  if (!ring || !init_w || !init_b || !cond0 || !out || !x_out || !slots) return set_error(SRWN_E_NULL, "%s: null pointer", who);
+  if (R != 32 && R != 64) return set_error(SRWN_E_UNSUPPORTED, "%s: dilation_channels %d (built: 32, 64)", who, R);
+  if (capacity < 1 || max_chunk < 1 || out_hist < 0 || cond_frames < 1 || pool_stride < 1 || cond_row_stride < R ||
+      cond_row_stride % 8)
+    return set_error(SRWN_E_SHAPE, "%s: capacity=%d max_chunk=%d out_hist=%d frames=%d pool=%d cond stride %lld", who, capacity,
+                     max_chunk, out_hist, cond_frames, pool_stride, (long long)cond_row_stride);
+  if (n < 1 || n > max_chunk) return set_error(SRWN_E_SHAPE, "%s: chunk of %d rows (1..max_chunk = %d)", who, n, max_chunk);
+  // (the ring also holds the two samples before a whole chunk)
+  if (ring_len < (int64_t)max_chunk + 2 || out_clip_rows < (int64_t)out_hist + max_chunk || x_stride < max_chunk)
+    return set_error(SRWN_E_SHAPE, "%s: an audio ring of %d samples for max_chunk + 2 = %lld, %lld buffer rows per slot for %d + %d, "
+                     "%lld targets per slot", who, ring_len, (long long)max_chunk + 2, (long long)out_clip_rows, out_hist,
+                     max_chunk, (long long)x_stride);
+  if ((int64_t)capacity * ring_len > 0x7fffffffLL) return set_error(SRWN_E_SHAPE, "%s: %d rings of %d samples", who, capacity, ring_len);
+  if (dtype != SRWN_BF16 && dtype != SRWN_F32) return set_error(SRWN_E_DTYPE, "%s: dtype %d", who, dtype);
+  const int64_t threads = (int64_t)capacity * n * (R / 8);
+  dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == SRWN_BF16)
+    hipLaunchKernelGGL(mol_score_stream_in_slots_kernel<bf16_t>, grid, block, 0, st, ring, ring_len, init_w, init_b,
+                       (const bf16_t*)cond0, cond_frames, pool_stride, cond_row_stride, (bf16_t*)out, out_clip_rows, out_hist,
+                       x_out, x_stride, capacity, n, R, slots);
+  else
+    hipLaunchKernelGGL(mol_score_stream_in_slots_kernel<float>, grid, block, 0, st, ring, ring_len, init_w, init_b,
+                       (const float*)cond0, cond_frames, pool_stride, cond_row_stride, (float*)out, out_clip_rows, out_hist,
+                       x_out, x_stride, capacity, n, R, slots);
   return check_launch(who);
 }
 
@@ -624,4 +728,34 @@ extern "C" int srwn_nll_rows_slots(const float* logits, int64_t logits_ld, int64
   return score_rows_impl<false, true>("nll_rows_slots", logits, logits_ld, logits_clip_rows,
                                       HeadRows{codes, nullptr, 0, nll, best, logits_out, out_stride, C}, capacity, n, stream,
                                       SlotsArg<true>{slots});
+}
+
+// ---- mixture-of-logistics scorer pools (srwn.h, srwn_version() 119)
+extern "C" int srwn_mol_score_stream_in_slots(const float* audio_ring, int32_t ring_len, const float* init_w,
+                                              const float* init_b, const void* cond0, int32_t cond_frames, int32_t pool_stride,
+                                              int64_t cond_row_stride, void* out, int64_t out_clip_rows, int32_t out_hist,
+                                              float* x_out, int64_t x_stride, int32_t capacity, int32_t n, int32_t max_chunk,
+                                              int32_t R, int32_t dtype, const SrwnSynthSlot* slots, void* stream) {
+  return mol_score_stream_in_slots_impl("mol_score_stream_in_slots", audio_ring, ring_len, init_w, init_b, cond0, cond_frames,
+                                        pool_stride, cond_row_stride, out, out_clip_rows, out_hist, x_out, x_stride, capacity, n,
+                                        max_chunk, R, dtype, slots, stream);
+}
+
+extern "C" int srwn_stream_mol_score_head_slots(const void* z, int64_t z_layer_stride, int64_t z_clip_rows, int32_t nlayers,
+                                                const void* wskip, const float* bs_sum, const void* w1, const float* b1,
+                                                const void* w2, const float* b2, const float* x, int64_t x_stride, float* nll,
+                                                float* logits_out, int64_t out_stride, int32_t capacity, int32_t n,
+                                                int32_t max_chunk, int32_t R, int32_t S, int32_t M, int32_t dtype,
+                                                const SrwnSynthSlot* slots, void* stream) {
+  return score_head_impl<true, true>("stream_mol_score_head_slots", z, z_layer_stride, z_clip_rows, nlayers, wskip, bs_sum, w1,
+                                     b1, w2, b2, HeadRows{nullptr, x, x_stride, nll, nullptr, logits_out, out_stride, M},
+                                     capacity, n, max_chunk, R, S, dtype, stream, SlotsArg<true>{slots});
+}
+
+extern "C" int srwn_mol_score_rows_slots(const float* logits, int64_t logits_ld, int64_t logits_clip_rows, const float* x,
+                                         int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int32_t capacity,
+                                         int32_t n, int32_t M, const SrwnSynthSlot* slots, void* stream) {
+  return score_rows_impl<true, true>("mol_score_rows_slots", logits, logits_ld, logits_clip_rows,
+                                     HeadRows{nullptr, x, x_stride, nll, nullptr, logits_out, out_stride, M}, capacity, n, stream,
+                                     SlotsArg<true>{slots});
 }

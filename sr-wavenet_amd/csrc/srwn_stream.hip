@@ -14,6 +14,7 @@
 #include <cmath>
 #include <type_traits>
 #include "srwn_common.h"
+#include "srwn_flow_in.h"
 #include "srwn_host.h"
 #include "srwn_slots.h"
 #include "../../include/srwn.h"
@@ -21,22 +22,6 @@
 using namespace srwn;
 
 namespace {
-
-template <typename T> struct Row8s;
-template <> struct Row8s<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
-    const bf16x8 r = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)r[j];
-  }
-};
-template <> struct Row8s<float> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[8]) {
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-  }
-};
 
 // The slot forms (synthesis pools, srwn.h SrwnSynthSlot) are the same kernels with a template flag: the clock argument
 // becomes the pool's table, slot b's chunk starts at slots[b].t and has ran = slot_rows(slots[b], n) rows (ClockArg,
@@ -74,22 +59,9 @@ __global__ __launch_bounds__(256) void flow_stream_in_kernel(const float* __rest
   const float* xb = x + (int64_t)b * x_stride;
   const float x1 = t >= 1 ? xb[t - 1] : carry[2 * b];
   const float x0 = t >= 2 ? xb[t - 2] : carry[2 * b + (1 - t)];      // t = 1: x[-1] = carry[0]; t = 0: x[-2] = carry[1]
-  // the conditioning table is a ring of cond_frames rows per stream (srwn.h): frame q of the stream lives in row
-  // q mod cond_frames.  A stream that got its whole encoding at the start has q < cond_frames: the identity.
-  const long long tabs = t0 + t;
-  long long f = tabs / pool;
-  if (f >= cond_frames) f %= cond_frames;
-  float c[8];
-  Row8s<T>::load(cond + ((int64_t)b * cond_frames + f) * cond_stride + 8 * sub, c);
-  T* d = out + ((int64_t)b * out_clip_rows + hist + t) * R + 8 * sub;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    float v = bias[8 * sub + j];
-    v = fmaf(x0, w[8 * sub + j], v);
-    v = fmaf(x1, w[R + 8 * sub + j], v);
-    const T vr = (T)v;
-    d[j] = (T)((float)vr + c[j]);
-  }
+  // (the arithmetic, and the frame's row of the conditioning ring: flow_entry_row, shared with the scorer pool's entry)
+  flow_entry_row<T>(x0, x1, w, bias, cond, cond_frames, pool, cond_stride, b, t0 + t,
+                    out, (int64_t)b * out_clip_rows + hist + t, R, sub);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -390,7 +390,7 @@ class _MolScorerFace(object):
         self.latent_channels, self.condition_size = int(latent_channels), int(condition_size)
         self._eng = MolStreamScorer(weights, max_batch=max_batch, max_chunk=max_chunk, max_frames=max_frames)
         self.max_batch, self.max_chunk, self.max_frames = self._eng.max_batch, self._eng.max_chunk, self._eng.max_frames
-        self.pool_stride, self.conditioned = self._eng.pool, bool(self._eng.E)
+        self.pool_stride, self.conditioned = int(self._eng.pool), bool(self._eng.E)
 
     def _conditions(self, batch, conditions):
         """conditions [B, condition_size] on the device, or None (no device work before the refusals)."""
@@ -458,6 +458,12 @@ class StreamingMolScorer(_MolScorerFace):
     def stream(self, batch_size=1, conditions=None):
         return MolScorerStream(self, batch_size, conditions)
 
+    def pool(self, audio_ring=None):
+        """A ``MolScorerStreamPool``: this scorer's ``max_batch`` rows as slots that streams join and leave, each pushing
+        audio and being fed frames at a clock of its own (``scorer.MolScorerPool``).  audio_ring: samples a slot can hold
+        (default 2 * max_chunk + 2).  Ends the current ``MolScorerStream``; ``stream`` and ``score`` end the pool."""
+        return MolScorerStreamPool(self, self._eng.pool(audio_ring))
+
 
 class MolScorerStream(_MolScoreStreamBase):
     """``StreamingMolScorer.stream``: ``feed(encoding [B, k, latent])`` hands every stream its next k <= ``room`` frames,
@@ -524,6 +530,12 @@ class AutoEncoderScorer(_MolScorerFace):
         if not 1 <= int(batch_size) <= min(self.max_batch, self.encoder.max_batch):
             raise ValueError("batch_size %r: this scorer holds %d streams" % (batch_size, min(self.max_batch, self.encoder.max_batch)))
         return AutoEncoderScoreStream(self, int(batch_size), conditions)
+
+    def pool(self, audio_ring=None):
+        """An ``AutoEncoderScorerPool``: an encoder pool feeding a scorer pool, slot by slot, each stream at a clock of its
+        own.  audio_ring: samples a slot of the SCORER half can hold (default: the encoder pool's ring plus max_chunk + 2;
+        at least ``scorer.ae_pool_min_audio_ring``).  Ends the current stream of either half."""
+        return AutoEncoderScorerPool(self, audio_ring)
 
 
 class AutoEncoderScoreStream(_MolScoreStreamBase):
@@ -858,6 +870,15 @@ def _ran_dict(a, ran, slots):
     """A pool step's device rows a [capacity, n] as {slot: its ran[slot] samples} (NumPy) for the `slots` that made some."""
     a = a.cpu().numpy()
     return {u: a[u, :int(ran[u])] for u in slots if ran[u] > 0}
+
+
+def _host_dict(d):
+    """A pool step's {slot: device rows} as {slot: NumPy rows}, with ONE device-to-host copy however many slots."""
+    us = list(d)
+    if len(us) < 2:
+        return {u: d[u].cpu().numpy() for u in us}
+    flat = torch.cat([d[u] for u in us], dim=0).cpu().numpy()
+    return dict(zip(us, np.split(flat, np.cumsum([d[u].shape[0] for u in us])[:-1])))
 
 
 def _audio_pieces(slots, audio):
@@ -1612,6 +1633,65 @@ class ScorerStreamPool(_AudioPoolFace):
         return tuple(host(d) for d in out) if isinstance(out, tuple) else host(out)
 
 
+class MolScorerStreamPool(_AudioPoolFace):
+    """NumPy face of a mixture-of-logistics scorer pool (``StreamingMolScorer.pool``; scorer.MolScorerPool).
+    ``join(conditions, n)`` returns slots (conditions [n, condition_size], one row per stream, tiled onto every frame the
+    stream is fed), ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``feed(slots, encoding)`` one
+    [k, latent_channels] array per slot with k <= ``room(slot)``, ``step()`` returns ``{slot: nll [m]}`` (nats) for every slot
+    whose stream scored m > 0 samples (with return_logits a second dict).  A stream's nll put together is
+    ``StreamingMolScorer.score`` of its audio and encoding alone."""
+
+    def __init__(self, owner, pool):
+        super().__init__(pool)
+        self._owner, self._cond = owner, {}      # slot -> its stream's conditions [1, condition_size] on the device, or None
+
+    audio_ring = property(lambda self: self._pool.audio_ring)
+    scored = property(lambda self: self._pool.scored)
+    fed = property(lambda self: self._pool.fed)
+    nll_sum = property(lambda self: self._pool.nll_sum)
+
+    def join(self, conditions=None, n=1, slots=None):
+        n = int(n) if slots is None else len(slot_list(slots, self.capacity, "join"))
+        c = self._owner._conditions(n, conditions)           # (its refusals come before any device work)
+        slots = self._pool.join(n, slots)
+        for i, u in enumerate(slots):
+            self._cond[u] = None if c is None else c[i:i + 1]
+        return slots
+
+    def leave(self, slots):
+        self._pool.leave(slots)
+        for u in slot_list(slots, self.capacity, "leave"):
+            self._cond.pop(u, None)
+
+    def room(self, slot):
+        return self._pool.room(int(slot))
+
+    def available(self, slot):
+        return self._pool.available(int(slot))
+
+    def bits_per_sample(self, slot):
+        """The running mean nll of the stream in `slot`, in bits (NaN before its first sample)."""
+        return self._pool.bits_per_sample(int(slot))
+
+    def feed(self, slots, encoding):
+        """encoding: one [k, latent_channels] array per slot (one slot: the array itself)."""
+        if not self._owner.conditioned:
+            raise ValueError("feed: this teacher is not conditioned")
+        one = np.isscalar(slots) or (isinstance(encoding, (np.ndarray, torch.Tensor)) and encoding.ndim == 2)
+        us = slot_list(slots, self.capacity, "feed")
+        pieces = [encoding] if one else list(encoding)
+        if len(pieces) != len(us):
+            raise ValueError("feed: %d slots but %d pieces of encoding" % (len(us), len(pieces)))
+        if any(u not in self._cond for u in us):
+            raise ValueError("feed: slots %s do not all hold a stream of this pool" % (us,))
+        self._pool.feed(us, [self._owner._frames(torch.as_tensor(e, dtype=torch.float32)[None], self._cond[u])[0]
+                             for u, e in zip(us, pieces)])
+
+    def step(self, return_logits=False):
+        out = self._pool.step(return_logits)
+        return tuple(_host_dict(d) for d in out) if isinstance(out, tuple) else _host_dict(out)
+
+
 class ParallelWaveNet(object):
     """model.py:290-656 on ``student.StudentEngine``: ``num_flows`` inverse-autoregressive flows distilled against a
     frozen mixture-of-logistics teacher.
@@ -2280,3 +2360,100 @@ class SiameseWaveNet(_EngineOwner):
         eng = self._stage(self._pair(inputs_left, inputs_right))
         eng.forward(with_loss=False)
         return eng.dist.cpu().numpy()
+
+
+class AutoEncoderScorerPool(_ResynthesisPool):
+    """``AutoEncoderScorer.pool()``: an encoder pool ``_enc`` and a ``scorer.MolScorerPool`` ``_mol`` sharing slot ids, with
+    the contract of the resynthesis pools; capacity is the smaller ``max_batch``.  ``join(conditions, n)`` returns slots,
+    ``push(slots, audio)`` takes one 1-D array per slot of any length (at most ``audio_room(slot)``) and writes it into BOTH
+    halves' audio rings (two uploads: the halves keep separate rings), ``finish(slots)`` ends streams, ``leave(slots)``
+    drops them, ``step()`` returns ``{slot: nll [m]}`` (NumPy, nats).  One ``step``: the encoder emits for each slot at most
+    the frames the scorer's conditioning ring has room for (the rest stays audio), the new frames are fed as device
+    tensors with the slot's conditions tiled on, the scorer scores every sample that has its frame, and a slot whose
+    encoder half is finished and fully emitted and whose scorer half has scored all it was fed is freed in both halves.
+    A stream's values put together are ``AutoEncoderScorer(max_batch=1).score(audio)`` of it alone: its first (T //
+    pool_stride) * pool_stride samples; a stream shorter than one frame ends with nothing.
+    The scorer half's audio ring must hold what the ENCODER still needs before it can emit the next frame -- with every
+    fed sample scored that is pool_stride + L + 1 samples beyond emitted * pool_stride, plus the two samples the entry
+    conv carries -- or neither half could move: ``scorer.ae_pool_min_audio_ring``, refused below."""
+
+    _who = "scorer"
+
+    def __init__(self, owner, audio_ring):
+        from .scorer import ae_pool_min_audio_ring
+        enc, mol = owner.encoder._eng, owner._eng
+        need = ae_pool_min_audio_ring(mol.max_chunk, enc.P, enc.L)
+        enc_ring = enc.max_frames * enc.P + enc.L + 1 + enc.P            # (the encoder pool's default)
+        ring = enc_ring + mol.max_chunk + 2 if audio_ring is None else int(audio_ring)
+        if ring < need:
+            raise ValueError("pool: audio_ring %d: the scorer half needs at least %d samples (a step of max_chunk + 2 = %d, "
+                             "and pool_stride + encoder layers + 3 = %d so that the encoder can complete its next frame)"
+                             % (ring, need, mol.max_chunk + 2, enc.P + enc.L + 3))
+        self._owner = owner
+        self.capacity = min(enc.max_batch, mol.max_batch)
+        self._cs = owner.condition_size
+        self._enc = enc.pool()
+        self._mol = mol.pool(ring)
+        self._cond = {}        # slot -> its stream's conditions [1, condition_size] on the device (None without)
+
+    _half = property(lambda self: self._mol)
+    t = property(lambda self: self._mol.scored[:self.capacity], doc="Samples scored so far, per slot.")
+    scored = t
+
+    def audio_room(self, slot):
+        """Samples a slot can take now: the smaller of the two halves' rooms."""
+        return min(self._enc.audio_room(int(slot)), self._mol.audio_room(int(slot)))
+
+    def bits_per_sample(self, slot):
+        """The running mean nll of the stream in `slot`, in bits (NaN before its first sample)."""
+        return self._mol.bits_per_sample(int(slot))
+
+    def join(self, conditions=None, n=1):
+        """n streams into the lowest free slots; conditions [n, condition_size] (one row per stream).  Returns the slots."""
+        n = int(n)
+        self._mol._check_open()
+        slots = self._take_slots(n, None)
+        c = _device_conditions(n, conditions, self._cs, self._who)
+        self._mol.join(slots=slots)
+        self._enc.join(slots=slots)
+        for i, u in enumerate(slots):
+            self._cond[u] = None if c is None else c[i:i + 1]
+        return slots
+
+    def push(self, slots, audio):
+        """Each piece into both halves' rings.  A piece that fits one half only is refused before either is written, as
+        is everything either half refuses."""
+        pieces = _audio_pieces(slots, audio)
+        slots = self._slots(slots, "push")
+        self._mol._check_open()
+        if len(pieces) != len(slots):
+            raise ValueError("push: %d slots but %d pieces of audio" % (len(slots), len(pieces)))
+        for u, x in zip(slots, pieces):
+            if x.ndim == 1 and x.shape[0] > self.audio_room(u):
+                raise ValueError("push: %d samples for slot %d, but its rings have room for %d (encoder half %d, scorer half "
+                                 "%d)" % (x.shape[0], u, self.audio_room(u), self._enc.audio_room(u), self._mol.audio_room(u)))
+        self._enc.push(slots, pieces)      # (its refusals -- a finished stream, a wrong dtype or rank -- come before it writes)
+        self._mol.push(slots, pieces)
+
+    def leave(self, slots):
+        """Ends these streams where they are and frees their slots in both halves."""
+        self._mol._check_open()
+        super().leave(slots)
+
+    def step(self):
+        self._mol._check_open()
+        if not self._cond:
+            return {}
+        enc, mol, P = self._enc, self._mol, self._owner.pool_stride
+        frames = enc.step({u: mol.room(u) for u in enc.active})      # frames that do not fit stay audio
+        if frames:
+            us = sorted(frames)
+            mol.feed(us, [frames[u] if self._cond[u] is None else _tile_conditions(frames[u][None], self._cond[u])[0]
+                          for u in us])
+        out = mol.step()
+        done = [u for u in self._cond if not enc._active[u] and mol._scored[u] == mol._fed[u] * P]
+        if done:                                                     # finished, fully encoded and fully scored
+            mol.leave(done)
+            for u in done:
+                del self._cond[u]
+        return _host_dict(out)

@@ -31,12 +31,23 @@ conditioning bias at the device clock; its carry, the two samples before the chu
 launches carry ``cond_next``, its head is ``srwn_stream_mol_score_head`` (twin: ``srwn_mol_score_rows``), and the encoding
 frames are FED into a conditioning ring while the stream runs (``feed`` / ``room`` / ``available``).  The stack, the staged
 chunk, the clock, the graph cache and the checks of a push are ``stream_stack.StreamHost``'s, shared with the classifier;
-``_ScorerBase`` adds what only the scorers have: the nll and logits buffers, ``start`` and the head's common arguments.
+``_ScorerBase`` adds what only the scorers have: the nll and logits buffers, ``start``, the pool bookkeeping and the head's
+common arguments.
+
+``MolStreamScorer.pool()`` is the same pool for the conditioned decoder (``MolScorerPool``, a ``ScorerPool`` with a
+conditioning ring and a ``fed`` count per slot; srwn.h, srwn_version() 119): ``feed(slots, frames)`` is ragged -- one copy,
+one projection, one ``srwn_cond_ring_scatter_slots`` --, a step scores what has both arrived and got its frame, and
+``MolStreamScorer._launch_step(B, n, want_logits, pool=None)`` is again ONE launch list: with a pool its entry is
+``srwn_mol_score_stream_in_slots`` (a[t-2], a[t-1] and the target a[t] from the pool's audio ring, the first layer's bias
+from the slot's conditioning ring: no staged chunk, no carry), the group launches carry ``cond_next`` in their slot form,
+and the head and the roll are the slot forms.  ``model.AutoEncoderScorerPool`` couples it to an encoder pool;
+``ae_pool_min_audio_ring`` is the smallest scorer-half ring that cannot deadlock that pair.
 """
 from __future__ import annotations
 
 import math
 import os
+import weakref
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -144,6 +155,7 @@ class _ScorerBase(StreamHost):
     gives ``_new_state`` and ``_reset``."""
 
     _noun = "scorer"
+    _pool = None      # the open pool, if any (``pool()``)
 
     def __init__(self, weights, max_batch: int = 1, max_chunk: int = 1600):
         if min(int(max_batch), int(max_chunk)) < 1:
@@ -166,11 +178,26 @@ class _ScorerBase(StreamHost):
     # ------------------------------------------------------------------------------------------------
     def start(self, batch: int = 1):
         """`batch` streams at clock 0: zero history (the conv's zero padding), zero carry, and 0 for the sample before
-        the first one (the RightShift's padding)."""
+        the first one (the RightShift's padding).  The pool, if one is open, ends."""
         B = self._begin(batch)
         self._reset()
         self._state = self._new_state(B)
+        self._close_pool()
         return self._state
+
+    def _close_pool(self):
+        if self._pool is not None:
+            self._pool._open = False
+            self._pool = None
+
+    def _open_pool(self, pool):
+        """`pool` (already built: a refused pool ends nothing) becomes the scorer's one open pool; the current state ends,
+        and an earlier pool."""
+        self._close_pool()
+        self._serial += 1
+        self._state = None
+        self._pool = pool
+        return pool
 
     def _reset(self):
         """What else a new state finds zeroed."""
@@ -198,34 +225,16 @@ class StreamScorer(_ScorerBase):
     ``score`` for whole recordings.  A step of n rows is one hipGraph per (batch, n, outputs wanted), captured when it is
     used a second time (SRWN_MODEL_GRAPHS=0: eager launches)."""
 
-    _pool: Optional["ScorerPool"] = None
-
     def __init__(self, weights: ScorerWeights, max_batch: int = 1, max_chunk: int = 1600):
         super().__init__(weights, max_batch, max_chunk)
         self.codes = self._zeros(self.max_batch, self.max_chunk, dt=torch.int32)
         self.best = self._zeros(self.max_batch, self.max_chunk, dt=torch.int32)
 
-    def start(self, batch: int = 1):
-        """``_ScorerBase.start``; the pool, if one is open, ends."""
-        st = super().start(batch)
-        self._close_pool()
-        return st
-
-    def _close_pool(self):
-        if self._pool is not None:
-            self._pool._open = False
-            self._pool = None
-
     def pool(self, audio_ring: Optional[int] = None) -> "ScorerPool":
         """A ``ScorerPool`` on this scorer's buffers: its ``max_batch`` rows as slots, each a stream at a clock of its own.
         audio_ring: samples a slot's audio ring holds (default 2 * max_chunk + 2, at least max_chunk + 2).  The current
         ``ScoreState`` ends, and an earlier pool; ``start`` and ``score`` end the pool."""
-        pool = ScorerPool(self, audio_ring)
-        self._close_pool()
-        self._serial += 1
-        self._state = None
-        self._pool = pool
-        return pool
+        return self._open_pool(ScorerPool(self, audio_ring))
 
     def _want_logits(self):
         if self.logits_out is None:
@@ -397,42 +406,45 @@ class ScorerPool(AudioRingSlots):
         return "scored %d" % self._scored[u]
 
     # ---- one step: every sample that waits
+    def _plan(self) -> Tuple[int, np.ndarray]:
+        """(n, rows per slot) of the next pass."""
+        return plan_score_pool_step(self._received, self._scored, self._active, self.max_chunk)
+
+    def _step(self, wants: tuple):
+        """``step`` for the outputs `wants` = (logits[, best]) beside nll, bools: the passes while anything waits -> one
+        dict {slot: rows} for nll and one per entry of `wants` that is set."""
+        self._check_open()
+        c, cap = self.c, self.capacity
+        parts = [{} for _ in range(1 + len(wants))]
+        while True:
+            n, rows = self._plan()
+            if n == 0:
+                break
+            if wants[0]:
+                c._want_logits()
+            self.table.copy_(torch.from_numpy(np.stack([self._scored, self._scored + rows], 1)))
+            K.run_cached_graph(self._graphs, self._seen, (n,) + wants, c.use_graphs,
+                               lambda: c._launch_step(cap, n, *wants, pool=self))
+            # one copy per pass: the next pass writes the same buffers
+            bufs = (c.nll, c.logits_out, getattr(c, "best", None))
+            outs = [buf[:cap, :n].clone() if want else None for want, buf in zip((True,) + wants, bufs)]
+            live = self._cols[:, :n] < (self.table[:, 1] - self.table[:, 0]).unsqueeze(1)      # [cap, n]: the slots' own rows
+            self._nll_sum += torch.where(live, outs[0], 0.0).sum(1, dtype=torch.float64)
+            for u in np.flatnonzero(rows):
+                m = int(rows[u])
+                for part, out in zip(parts, outs):
+                    if out is not None:
+                        part.setdefault(int(u), []).append(out[u, :m])
+            self._scored += rows
+        cat = lambda p: p[0] if len(p) == 1 else torch.cat(p, dim=0)
+        res = tuple({u: cat(p) for u, p in part.items()} for part, want in zip(parts, (True,) + wants) if want)
+        return res if len(res) > 1 else res[0]
+
     def step(self, return_logits: bool = False, return_best: bool = False):
         """Runs while any active slot has a sample waiting -> {slot: nll [m] fp32 on the device} for the slots whose
         streams scored m > 0 samples; with return_logits also {slot: logits [m, C]}, with return_best also {slot: the most
         likely code [m] int32}, in that order (a tuple of dicts).  With nothing waiting nothing is launched."""
-        self._check_open()
-        c, cap = self.c, self.capacity
-        want_logits, want_best = bool(return_logits), bool(return_best)
-        pn, pl, pb = {}, {}, {}
-        while True:
-            n, rows = plan_score_pool_step(self._received, self._scored, self._active, self.max_chunk)
-            if n == 0:
-                break
-            if want_logits:
-                c._want_logits()
-            self.table.copy_(torch.from_numpy(np.stack([self._scored, self._scored + rows], 1)))
-            K.run_cached_graph(self._graphs, self._seen, (n, want_logits, want_best), c.use_graphs,
-                               lambda: c._launch_step(cap, n, want_logits, want_best, self))
-            # one copy per pass: the next pass writes the same buffers
-            nll = c.nll[:cap, :n].clone()
-            logits = c.logits_out[:cap, :n].clone() if want_logits else None
-            best = c.best[:cap, :n].clone() if want_best else None
-            live = self._cols[:, :n] <(self.table[:, 1] - self.table[:, 0]).unsqueeze(1)      # [cap, n]: the slots' own rows
-            self._nll_sum += torch.where(live, nll, 0.0).sum(1, dtype=torch.float64)
-            for u in np.flatnonzero(rows):
-                m = int(rows[u])
-                pn.setdefault(int(u), []).append(nll[u, :m])
-                if want_logits:
-                    pl.setdefault(int(u), []).append(logits[u, :m])
-                if want_best:
-                    pb.setdefault(int(u), []).append(best[u, :m])
-            self._scored += rows
-        cat = lambda p: p[0] if len(p) == 1 else torch.cat(p, dim=0)
-        out = {u: cat(p) for u, p in pn.items()}
-        res = (out,) + (({u: cat(p) for u, p in pl.items()},) if want_logits else ()) \
-            + (({u: cat(p) for u, p in pb.items()},) if want_best else ())
-        return res if len(res) > 1 else out
+        return self._step((bool(return_logits), bool(return_best)))
 
 
 # ---- the conditioned mixture-of-logistics decoder ------------------------------------------------------------------------
@@ -536,6 +548,21 @@ class MolScoreState:
         self.nll_sum = torch.zeros(batch, dtype=torch.float64, device=dev)
 
 
+class _PoolStride(int):
+    """What the instance attribute ``MolStreamScorer.pool`` holds.  It has always been the decoder's pool stride, an int, and
+    stays one wherever it is read; called, it is the method ``MolStreamScorer.pool`` that it shadows on the instance:
+    ``scorer.pool(audio_ring)`` opens the scorer's pool, as ``StreamScorer.pool`` does."""
+
+    def __new__(cls, stride, owner):
+        o = super().__new__(cls, stride)
+        o._owner = weakref.ref(owner)
+        return o
+
+    def __call__(self, audio_ring: Optional[int] = None) -> "MolScorerPool":
+        owner = self._owner()
+        return type(owner).pool(owner, audio_ring)
+
+
 class MolStreamScorer(_ScorerBase):
     """``start`` a batch of streams, ``feed`` them encoding frames (a conditioned decoder) and ``push`` audio: nll [B, n]
     fp32 in nats of exactly the samples pushed, nll[b, t] = -log p(audio[b, t] | audio[b, < t], encoding); ``score`` for
@@ -548,7 +575,7 @@ class MolStreamScorer(_ScorerBase):
         if min(int(max_batch), int(max_chunk)) < 1:
             raise ValueError("max_batch and max_chunk must be >= 1")
         w = weights
-        self.E, self.pool = w.E, w.pool
+        self.E, self.pool = w.E, _PoolStride(w.pool, self)
         self.hist_max = max(StreamStack.plan(w.dil)[1]) if w.E else 0
         self.max_frames = int(max_frames) if w.E else 1
         if w.E and self.max_frames < live_min_frames(self.hist_max, self.pool):
@@ -576,6 +603,17 @@ class MolStreamScorer(_ScorerBase):
 
     def _reset(self):
         self.ring.zero_()
+
+    def _want_logits(self):
+        if self.logits_out is None:
+            self.logits_out = torch.zeros((self.max_batch, self.max_chunk, self.w.C), dtype=torch.float32, device=self.dev)
+
+    def pool(self, audio_ring: Optional[int] = None) -> "MolScorerPool":
+        """A ``MolScorerPool`` on this scorer's buffers: its ``max_batch`` rows as slots, each a stream at a clock of its own
+        with a conditioning ring of its own.  audio_ring: samples a slot's audio ring holds (default 2 * max_chunk + 2, at
+        least max_chunk + 2).  The current ``MolScoreState`` ends, and an earlier pool; ``start`` and ``score`` end the
+        pool.  (On an instance the name is also the decoder's pool stride, the int it has always been: ``_PoolStride``.)"""
+        return self._open_pool(MolScorerPool(self, audio_ring))
 
     # ------------------------------------------------------------------------------------------------
     def room(self, state: MolScoreState) -> int:
@@ -614,27 +652,37 @@ class MolStreamScorer(_ScorerBase):
              self.max_frames, LR, K.abi_dtype(self.dt), K._stream())
         state.fed += k
 
-    def _launch_step(self, B: int, n: int, want_logits: bool = False):
-        """The launches of a step of n rows on the chunk staged in ``xbuf`` (entry input and target) and the two samples
-        before it in ``carry2``."""
+    def _launch_step(self, B: int, n: int, want_logits: bool = False, pool: Optional["MolScorerPool"] = None):
+        """The launches of a step of n rows: on the chunk staged in ``xbuf`` (entry input and target) and the two samples
+        before it in ``carry2`` at the clock, or, with `pool`, the same launches in their slot forms on ``pool.table`` -- B
+        is then the pool's capacity, and the pool's entry reads the audio ring (the two samples before the chunk too: no
+        staged chunk, no carry) and writes the targets into ``xbuf`` itself."""
         w = self.w
         st, dt, R, S, C = K._stream(), K.abi_dtype(self.dt), w.R, w.S, self.max_chunk
-        v, F, LR, when = w.view, self.max_frames, self.LR, self.clock.data_ptr()
-        call("srwn_flow_stream_in", self.xbuf.data_ptr(), C, self.carry2.data_ptr(), v("init_w").data_ptr(),
-             v("init_b").data_ptr(), self.ring.data_ptr(), F, self.pool, LR, self.bufs[0].data_ptr(), self.hist[0] + C,
-             self.hist[0], B, n, C, R, dt, when, st)
+        v, F, LR = w.view, self.max_frames, self.LR
+        slots = pool is not None
+        sfx = "_slots" if slots else ""
+        when = pool.table.data_ptr() if slots else self.clock.data_ptr()      # the clock, or the table in its place
+        table = (when,) if slots else ()
+        entry = (v("init_w").data_ptr(), v("init_b").data_ptr(), self.ring.data_ptr(), F, self.pool, LR,
+                 self.bufs[0].data_ptr(), self.hist[0] + C, self.hist[0])
+        if slots:
+            call("srwn_mol_score_stream_in_slots", pool.ring.data_ptr(), pool.audio_ring, *entry, self.xbuf.data_ptr(), C, B,
+                 n, C, R, dt, when, st)
+        else:
+            call("srwn_flow_stream_in", self.xbuf.data_ptr(), C, self.carry2.data_ptr(), *entry, B, n, C, R, dt, when, st)
         # layer l adds the bias of layer l + 1: its R columns of the ring's rows [L * R]
         above = [self.ring.data_ptr() + (l + 1) * R * self.ring.element_size() if l + 1 < w.L else None for l in range(w.L)]
-        self.stack.launch_groups(B, n, when, cond=(above, F, self.pool, LR) if self.E else None)
+        self.stack.launch_groups(B, n, when, slots, cond=(above, F, self.pool, LR) if self.E else None)
         lo = self.logits_out.data_ptr() if want_logits else None
         if self.fused:
-            call("srwn_stream_mol_score_head", *self._head_args(), self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C, B, n,
-                 C, R, S, w.M, dt, st)
+            call("srwn_stream_mol_score_head" + sfx, *self._head_args(), self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C,
+                 B, n, C, R, S, w.M, dt, *table, st)
         else:
             self._launch_twin_products(B, n)
-            call("srwn_mol_score_rows", self.logits32.data_ptr(), w.Cp, C, self.xbuf.data_ptr(), C, self.nll.data_ptr(), lo, C,
-                 B, n, w.M, st)
-        self._launch_roll(B, n, when)
+            call("srwn_mol_score_rows" + sfx, self.logits32.data_ptr(), w.Cp, C, self.xbuf.data_ptr(), C, self.nll.data_ptr(),
+                 lo, C, B, n, w.M, *table, st)
+        self._launch_roll(B, n, when, slots)
 
     def push(self, state: MolScoreState, audio, return_logits: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> nll [B, n] fp32 (nats) of exactly those
@@ -650,8 +698,8 @@ class MolStreamScorer(_ScorerBase):
         C4 = self.w.C
         x = x.to(device=self.dev, dtype=torch.float32).contiguous()
         want_logits = bool(return_logits)
-        if want_logits and self.logits_out is None:
-            self.logits_out = torch.zeros((self.max_batch, self.max_chunk, C4), dtype=torch.float32, device=self.dev)
+        if want_logits:
+            self._want_logits()
         nll = torch.empty((B, n_all), dtype=torch.float32, device=self.dev)
         logits = torch.empty((B, n_all, C4), dtype=torch.float32, device=self.dev) if want_logits else None
         for a, n in cut_push(n_all, self.max_chunk):
@@ -695,6 +743,119 @@ class MolStreamScorer(_ScorerBase):
         if return_logits:
             return torch.cat([o[0] for o in outs], 1), torch.cat([o[1] for o in outs], 1)
         return torch.cat(outs, 1)
+
+
+class MolScorerPool(ScorerPool):
+    """``MolStreamScorer.pool()``: ``ScorerPool`` for the conditioned mixture-of-logistics decoder -- the same slots, audio
+    ring, table, pass loop and graph cache (an ``AudioRingSlots`` like it), plus a CONDITIONING RING per slot: the scorer's
+    ring [max_batch * max_frames] read as ``max_frames`` rows per slot, frame q of slot u in row u * max_frames + q mod
+    max_frames.  Each slot has its own ``fed`` beside ``received`` and ``scored``.  ``feed(slots, frames)`` hands slots
+    their next frames, ragged: one copy into the stage, one srwn_pw_linear over all new rows and one
+    srwn_cond_ring_scatter_slots however many slots and frames, under the room rule ``student.live_room`` on the slot's own
+    fed and scored.  ``step`` scores, per slot, the samples that have both arrived and got their frame: the plan runs on
+    min(received, fed * pool_stride) (an unconditioned decoder: on received alone, it has no feed and room 0).  The
+    launches are ``MolStreamScorer._launch_step`` with this pool: the entry srwn_mol_score_stream_in_slots reads a[t-2],
+    a[t-1] and the target a[t] from the audio ring and the first layer's bias from the slot's conditioning ring, the group
+    launches carry ``cond_next`` in their slot form, then the slot head (or the twin) and the slot roll -- as many launches
+    as a lockstep step.  A stream's nll put together equals ``MolStreamScorer(max_batch=1).score`` of its audio and frames
+    alone, bit for bit: in any slot, whenever it joined, however its audio and frames were cut, whatever n the steps had
+    and whatever the other slots hold or held before."""
+
+    def __init__(self, owner: "MolStreamScorer", audio_ring: Optional[int] = None):
+        super().__init__(owner, audio_ring)
+        self._fed = np.zeros(self.capacity, np.int64)
+        # the feed's destination rows, one upload per feed
+        self._dst = torch.zeros(self.capacity * owner.max_frames, dtype=torch.int32, device=self.dev)
+
+    def buffer_bytes(self) -> Dict[str, int]:
+        """The scorer's device bytes by buffer family with the pool's additions."""
+        out = super().buffer_bytes()
+        out["pool feed rows"] = nbytes([self._dst])
+        return out
+
+    fed = property(lambda self: self._fed.copy(), doc="Conditioning frames fed into each slot's stream so far.")
+
+    def room(self, slot: int) -> int:
+        """Frames slot `slot` may be fed now: ``student.live_room`` on its own fed and scored (0 for an unconditioned
+        decoder)."""
+        u, = self._slot_list(slot, "room")
+        c = self.c
+        return live_room(self._fed[u], self._scored[u], c.hist_max, c.pool, c.max_frames) if c.E else 0
+
+    def available(self, slot: int) -> int:
+        """Samples of slot `slot` the next ``step`` scores: those that have arrived and whose frame was fed."""
+        u, = self._slot_list(slot, "available")
+        return int(self._ready()[u] - self._scored[u])
+
+    def _ready(self) -> np.ndarray:
+        """Per slot, the samples that have arrived and have their conditioning frame."""
+        return np.minimum(self._received, self._fed * self.c.pool) if self.c.E else self._received
+
+    def _plan(self) -> Tuple[int, np.ndarray]:
+        return plan_score_pool_step(self._ready(), self._scored, self._active, self.max_chunk)
+
+    def join(self, n: int = 1, slots=None) -> List[int]:
+        """``ScorerPool.join``; a slot also starts with no frame fed.  The rows of its conditioning ring are NOT zeroed: a
+        stream only reads frames it was fed (a chunk's rows lie below fed * pool_stride, its halo rows before time 0 are
+        the conv's zero padding), so what an earlier stream left there is never read."""
+        slots = super().join(n, slots)
+        self._fed[slots] = 0
+        return slots
+
+    def feed(self, slots, frames) -> None:
+        """The next frames of slots: frames[i] [k_i, cond_channels] for slots[i], ragged (k_i = 0 too); device tensors are
+        taken as they are.  Refuses (ValueError, before any device work, nothing changed) an unconditioned decoder, a slot
+        that holds no stream, a wrong shape and k_i > ``room(slots[i])``.  One copy into the stage, one projection through
+        the conditioning image and ONE srwn_cond_ring_scatter_slots however many slots and frames: row j of slot u goes to
+        ring row u * max_frames + (fed_u + j) mod max_frames."""
+        self._check_open()
+        c = self.c
+        if not c.E:
+            raise ValueError("feed: this decoder is not conditioned")
+        slots = self._slot_list(slots, "feed", distinct=True)
+        if isinstance(frames, (torch.Tensor, np.ndarray)) and frames.ndim == 2:
+            frames = [frames]
+        frames = [f if isinstance(f, torch.Tensor) else torch.as_tensor(np.asarray(f, dtype=np.float32)) for f in frames]
+        if len(frames) != len(slots):
+            raise ValueError("feed: %d slots but %d pieces of frames" % (len(slots), len(frames)))
+        for u, f in zip(slots, frames):
+            if not self._active[u]:
+                raise ValueError("feed: slot %d holds no stream" % u)
+            if f.dim() != 2 or f.shape[1] != c.E:
+                raise ValueError("feed: frames of slot %d must be [k, %d], got %s" % (u, c.E, tuple(f.shape)))
+            if f.shape[0] > self.room(u):
+                raise ValueError("feed: %d frames for slot %d, but its ring of %d has room for %d at t = %d with %d fed"
+                                 % (f.shape[0], u, c.max_frames, self.room(u), self._scored[u], self._fed[u]))
+        pairs = [(u, f) for u, f in zip(slots, frames) if f.shape[0] > 0]
+        if not pairs:
+            return
+        w, F, LR = c.w, c.max_frames, c.LR
+        dst = np.concatenate([u * F + (int(self._fed[u]) + np.arange(f.shape[0])) % F for u, f in pairs]).astype(np.int32)
+        rows = int(dst.shape[0])
+        c.stage_in[:rows, :c.E].copy_(torch.cat([f.to(device=self.dev, dtype=torch.float32) for _, f in pairs], dim=0))
+        K.pw_linear(c.stage_in.data_ptr(), w.Ep, 0, w.Ep, w.Ep, w.wptr(w.o_wc), w.view("BC").reshape(-1),
+                    c.stage_out[:rows], LR, LR, rows)
+        self._dst[:rows].copy_(torch.from_numpy(dst))
+        call("srwn_cond_ring_scatter_slots", c.stage_out.data_ptr(), LR, c.ring.data_ptr(), LR, rows, self._dst.data_ptr(),
+             self.capacity * F, LR, K.abi_dtype(c.dt), K._stream())
+        for u, f in pairs:
+            self._fed[u] += int(f.shape[0])
+
+    def step(self, return_logits: bool = False):
+        """Runs while any active slot has a sample waiting that has its frame -> {slot: nll [m] fp32 on the device} for
+        the slots whose streams scored m > 0 samples; with return_logits a second dict {slot: logits [m, 4M]}.  With
+        nothing to score nothing is launched."""
+        return self._step((bool(return_logits),))
+
+
+def ae_pool_min_audio_ring(max_chunk: int, pool_stride: int, enc_layers: int) -> int:
+    """The smallest audio ring of the scorer half of an encoder + scorer pool pair (``model.AutoEncoderScorerPool``) that
+    cannot deadlock it.  The scorer's ring keeps the samples [scored - 2, received) and a push must fit BOTH halves.  The
+    encoder emits frame e once received >= (e + 1) * pool_stride + enc_layers + 1 (``encoder.plan_frames``); until then no
+    frame is fed and the scorer stands at scored = e * pool_stride at best, so its ring has to take pool_stride +
+    enc_layers + 1 samples beyond that point beside the two carried ones: pool_stride + enc_layers + 3.  And a step reads
+    max_chunk + 2 (``MolScorerPool``).  The larger of the two.  Pure Python: the CPU tests hold it to a ring model."""
+    return max(int(max_chunk) + 2, int(pool_stride) + int(enc_layers) + 3)
 
 
 def bits_per_sample(nll_sum: float, samples: int) -> float:
