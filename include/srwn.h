@@ -1504,6 +1504,50 @@ int srwn_mol_score_rows_slots(const float* logits, int64_t logits_ld, int64_t lo
                               int64_t x_stride, float* nll, float* logits_out, int64_t out_stride, int32_t capacity, int32_t n,
                               int32_t M, const SrwnSynthSlot* slots, void* stream);
 
+/* ---- streaming embedder (since srwn_version() 120; csrc/srwn_embed.hip): a tower of class SiameseWaveNet (model.py:660-797:
+ * class WaveNet's network up to the last 1x1 and the average pool, model.py:689-731) as an inference-only stream that
+ * scores every window position against an enrolled gallery with the reference's distance (model.py:736).  Everything up
+ * to the hop sums is the streaming classifier's (113): srwn_recog_stream_in, srwn_residual_group_fwd_stream_z per layer
+ * group, srwn_pooled_stream_head (or its twin) into the ring [B][ring_rows][S] of hop sums, and srwn_recog_roll last.  The
+ * gallery is gallery [max_gallery][D] fp32 with its row count in DEVICE memory (n_gallery, one int32, clamped to [0,
+ * max_gallery]): every workgroup reads it when it runs, so a captured graph keeps serving after rows were enrolled.
+ *
+ *   srwn_window_embed_match   one launch, one workgroup of 256 threads per row = (stream b, hop i < k of the step), row index
+ *                             b * k + i, j = *clock / hop + i:
+ *                             (a) mean [S] = (sum of the nW = window / hop ring rows that end at hop j, oldest first) / window,
+ *                                 zeros while j < nW - 1 (such a row reads no ring row) -- srwn_window_mean's mean;
+ *                             (b) emb[row][d] = b2[d] + sum_s mean[s] w2[s][d], d < D (w2 [S, ldw] fp32, one fmaf per s in
+ *                                 order): bit for bit what srwn_window_mean writes to `logits` with C = D for the same ring;
+ *                             (c) dist[row][n] = sqrt(1e-8 + sum_d (emb[row][d] - gallery[n][d])^2) for n < N = *n_gallery
+ *                                 (dist [rows][max_gallery]; columns n >= N are not written).  Wave w of the workgroup takes the
+ *                                 rows n = w, w + 4, ...; lane l adds the squares of d = l, l + 64, ... in order and a 64-lane
+ *                                 xor butterfly adds the lanes, as srwn_contrastive_head scores a pair: a distance's bits
+ *                                 depend on the two vectors and D alone, not on k, B, the row or N;
+ *                             (d) nearest[row] = the argmin over n < N, the lowest index on ties, dmin[row] its distance;
+ *                                 N = 0: nearest = -1, dmin = +inf.
+ *                             The mean and the embedding stay in LDS.  ring_rows >= nW + k - 1.
+ *   srwn_window_embed_match_slots
+ *                             the same on a pool's table (115) in the clock's place: row u * k + i from slot u's ring at
+ *                             j = slots[u].t / hop + i; the mean is zero too (and no ring row is read) where (i + 1) * hop >
+ *                             ran(u) -- rows the caller discards.  One device body with the clock form.
+ *   srwn_gallery_match        steps (c) and (d) alone on emb [rows][D] (the device routine of the fused kernel): the last step
+ *                             of the parity twin behind srwn_window_mean(_slots) with logits, and a scorer of stored
+ *                             embeddings.  rows = 0 is done (0).
+ * Limits: S <= 256, 1 <= D <= 256, ldw >= D, 1 <= max_gallery <= 1024.  Errors, all before any launch, as srwn_window_mean
+ * reports them: a null pointer (-3); a size that does not fit (-2: S or D outside [1, 256], ldw < D, max_gallery outside
+ * [1, 1024], B, k or hop < 1, window not a multiple of hop, a ring of fewer than nW + k - 1 rows, rows < 0).  The kernels
+ * are not built per width or dtype (everything here is fp32), so -4 and -1 do not occur. */
+int srwn_window_embed_match(const float* ring, int32_t ring_rows, const int64_t* clock, int32_t B, int32_t k, int32_t hop,
+                            int32_t window, int32_t S, const float* w2, const float* b2, int32_t D, int32_t ldw,
+                            const float* gallery, const int32_t* n_gallery, int32_t max_gallery, float* emb, float* dist,
+                            int32_t* nearest, float* dmin, void* stream);
+int srwn_window_embed_match_slots(const float* ring, int32_t ring_rows, const SrwnSynthSlot* slots, int32_t capacity,
+                                  int32_t k, int32_t hop, int32_t window, int32_t S, const float* w2, const float* b2,
+                                  int32_t D, int32_t ldw, const float* gallery, const int32_t* n_gallery, int32_t max_gallery,
+                                  float* emb, float* dist, int32_t* nearest, float* dmin, void* stream);
+int srwn_gallery_match(const float* emb, int32_t rows, int32_t D, const float* gallery, const int32_t* n_gallery,
+                       int32_t max_gallery, float* dist, int32_t* nearest, float* dmin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

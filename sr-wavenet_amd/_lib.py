@@ -284,6 +284,13 @@ SIGNATURES["srwn_mol_score_stream_in_slots"] = (C.c_int, [_p, _i32, _p, _p, _p, 
 SIGNATURES["srwn_stream_mol_score_head_slots"] = (C.c_int, SIGNATURES["srwn_stream_mol_score_head"][1][:-1] + [_p, _p])
 SIGNATURES["srwn_mol_score_rows_slots"] = (C.c_int, SIGNATURES["srwn_mol_score_rows"][1][:-1] + [_p, _p])
 
+# streaming embedder (srwn_version() 120): window mean, embedding, gallery distances and the nearest row in one launch, its
+# slot form on the pool's table, and the twin's last step (the distances and the nearest row of embeddings that are there)
+SIGNATURES["srwn_window_embed_match"] = (C.c_int, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p, _i32,
+                                                   _p, _p, _p, _p, _p])
+SIGNATURES["srwn_window_embed_match_slots"] = SIGNATURES["srwn_window_embed_match"]
+SIGNATURES["srwn_gallery_match"] = (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p])
+
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded
 

@@ -17,6 +17,8 @@ wrappers, but no TensorFlow: the graph body is the fixed kernel sequence of ``en
                             (student.StudentEngine).
 * ``SiameseWaveNet``     -- model.py:660-797: two weight-sharing WaveNet towers trained on pairs with the contrastive
                             loss (engine head_mode "contrastive": both towers run as one batch).
+* ``StreamingEmbedder``  -- one such tower on its own (embedder.StreamEmbedder): any batch, any length, whole recordings or
+                            streams, every window matched against a gallery of enrolled templates.
 """
 from __future__ import annotations
 
@@ -2360,6 +2362,134 @@ class SiameseWaveNet(_EngineOwner):
         eng = self._stage(self._pair(inputs_left, inputs_right))
         eng.forward(with_loss=False)
         return eng.dist.cpu().numpy()
+
+    def embedder(self, max_batch=1, hop=None, window=None, max_hops=8, max_gallery=64):
+        """A ``StreamingEmbedder`` on a copy of this model's current weights: audio of any length in, the embedding of a
+        window of `window` samples (default input_size) sliding by `hop` (default: the window) out, matched against the
+        templates enrolled with it.  With hop = window = input_size its single embedding of a clip of input_size samples is
+        ``get_embedding``'s."""
+        window = int(self.input_size if window is None else window)
+        hop = window if hop is None else int(hop)
+        from .embedder import EmbedderWeights, check_gallery_size
+        from .recognizer import check_classifier_widths, check_hop_window
+        check_hop_window(hop, window)
+        check_gallery_size(max_gallery)
+        check_classifier_widths(self.filter_width, self.dilation_channels, self.skip_channels, "streaming embedder")
+        if self._primary is None:
+            self._engine(1, self._default_length)
+        return StreamingEmbedder(EmbedderWeights.from_engine(self._primary), max_batch=max_batch, hop=hop, window=window,
+                                 max_hops=max_hops, max_gallery=max_gallery)
+
+
+def _embed_host(r, threshold=None):
+    """An ``embedder.EmbedResult`` of device tensors -> one of NumPy arrays; with a threshold (result, accepted)."""
+    out = type(r)(*(t.cpu().numpy() for t in r))
+    return out if threshold is None else (out, out.distance <= np.float32(threshold))
+
+
+class StreamingEmbedder(object):
+    """The deployable form of a ``SiameseWaveNet`` tower (model.py:689-731) with a NumPy face: no training engine, no clip
+    length, and a gallery of enrolled templates on the device.  ``embed(audio [B, T])`` -> an ``EmbedResult`` (embeddings
+    [B, n_emit, D], nearest [B, n_emit], distance [B, n_emit], distances [B, n_emit, N]) of every window position (j + 1) *
+    hop - window, j >= window / hop - 1, of a recording of any length: the reference's distance (model.py:736) to each of
+    the N enrolled templates, the nearest one's index (-1 with none enrolled) and its distance.  ``enroll(clips [n,
+    window])`` embeds clips with this object's own path and adds them; ``stream(batch)`` -> an ``EmbedderStream`` to
+    ``push`` audio into as it arrives.  A result does not depend on how the audio was cut."""
+
+    def __init__(self, weights, max_batch=1, hop=160, window=16000, max_hops=8, max_gallery=64):
+        from .embedder import StreamEmbedder
+        self._w = weights
+        self._eng = StreamEmbedder(weights, max_batch=max_batch, hop=hop, window=window, max_hops=max_hops,
+                                   max_gallery=max_gallery)
+        e = self._eng
+        self.max_batch, self.hop, self.window, self.max_gallery, self.output_dimensions = (e.max_batch, e.hop, e.window,
+                                                                                           e.max_gallery, e.D)
+
+    @classmethod
+    def from_checkpoint(cls, logdir, dilations, output_dimensions, dilation_channels=32, skip_channels=256, filter_width=2,
+                        name="SiameseWaveNet", dtype=None, max_batch=1, hop=160, window=16000, max_hops=8, max_gallery=64):
+        """An embedder on the variables saved in `logdir` (``SiameseWaveNet.save``'s .pt form or a TensorFlow bundle, by the
+        reference's variable names under `name`/siamese)."""
+        from .embedder import EmbedderWeights, check_gallery_size
+        from .recognizer import check_classifier_widths, check_hop_window
+        check_hop_window(hop, window)
+        check_gallery_size(max_gallery)
+        check_classifier_widths(filter_width, dilation_channels, skip_channels, "streaming embedder")
+        w = EmbedderWeights(dilations, dilation_channels, skip_channels, output_dimensions, filter_width,
+                            dtype or _default_dtype())
+        if not w.load(logdir, name + "/siamese"):
+            raise FileNotFoundError("%s: no checkpoint to restore (SiameseWaveNet.save writes one)" % logdir)
+        return cls(w, max_batch=max_batch, hop=hop, window=window, max_hops=max_hops, max_gallery=max_gallery)
+
+    gallery = property(lambda self: self._eng.gallery.cpu().numpy(), doc="The enrolled templates [N, D].")
+    labels = property(lambda self: self._eng.labels, doc="One label per enrolled template.")
+
+    def embed(self, inputs):
+        """inputs [B, T] -> ``EmbedResult`` (NumPy) of the n_emit = max(0, T // hop - window / hop + 1) window positions."""
+        return _embed_host(self._eng.embed(self._eng._check_audio(inputs)))
+
+    def enroll(self, inputs, labels=None):
+        """Embeds the clips inputs [n, window] (any n, in batches of max_batch) with this object's own path and enrolls
+        the single window of each -> their gallery indices.  Ends the current stream or pool."""
+        x = np.asarray(inputs, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.window:
+            raise ValueError("enroll: inputs must be [n, window = %d], got shape %s" % (self.window, x.shape))
+        labels = None if labels is None else list(labels)
+        if labels is not None and len(labels) != x.shape[0]:
+            raise ValueError("enroll: %d clips but %d labels" % (x.shape[0], len(labels)))
+        if len(self._eng.labels) + x.shape[0] > self.max_gallery:
+            raise ValueError("enroll: %d clips behind the %d enrolled, max_gallery is %d"
+                             % (x.shape[0], len(self._eng.labels), self.max_gallery))
+        if not x.shape[0]:
+            return []
+        e = torch.cat([self._eng.embed(x[i:i + self.max_batch]).embeddings[:, 0]
+                       for i in range(0, x.shape[0], self.max_batch)], 0)
+        return self._eng.enroll(e, labels)
+
+    def enroll_embeddings(self, templates, labels=None):
+        """Enrolls templates [n, D] that are embeddings already -> their gallery indices."""
+        return self._eng.enroll(np.asarray(templates, dtype=np.float32), labels)
+
+    def clear(self):
+        self._eng.clear()
+
+    def stream(self, batch_size=1):
+        return EmbedderStream(self, self._eng.start(batch_size))
+
+    def pool(self, audio_ring=None):
+        """An ``EmbedderStreamPool``: this embedder's ``max_batch`` rows as slots that streams join and leave, each pushing
+        audio of any length at a clock of its own, all matched against this embedder's gallery (``embedder.EmbedderPool``).
+        Ends the current ``EmbedderStream``; ``stream``, ``embed`` and ``enroll`` end the pool."""
+        return EmbedderStreamPool(self._eng.pool(audio_ring))
+
+
+class EmbedderStream(object):
+    """NumPy face of one running batch of embedder streams (``StreamingEmbedder.stream``).  ``t``: samples received per
+    stream; ``emitted``: window positions returned so far."""
+
+    def __init__(self, owner, state):
+        self._owner, self._st, self.batch_size = owner, state, state.B
+
+    t = property(lambda self: self._st.t)
+    emitted = property(lambda self: self._st.emitted)
+
+    def push(self, audio, threshold=None):
+        """audio [B, n], any n >= 0 -> the ``EmbedResult`` [B, e, ..] of the e window positions it completed (e may be 0);
+        with a threshold (result, accepted [B, e] = distance <= threshold)."""
+        return _embed_host(self._owner._eng.push(self._st, audio), threshold)
+
+
+class EmbedderStreamPool(_AudioPoolFace):
+    """NumPy face of an embedder pool (``StreamingEmbedder.pool``; embedder.EmbedderPool).  ``join`` returns slots,
+    ``push(slots, audio)`` takes one 1-D array per slot, of any length, ``step()`` returns ``{slot: EmbedResult [e, ..]}`` for
+    every slot whose stream completed window positions.  A stream's results put together are ``StreamingEmbedder.embed`` of
+    its audio alone under the same gallery."""
+
+    audio_ring = property(lambda self: self._pool.audio_ring)
+    consumed = property(lambda self: self._pool.consumed)
+
+    def step(self, threshold=None):
+        return {u: _embed_host(r, threshold) for u, r in self._pool.step().items()}
 
 
 class AutoEncoderScorerPool(_ResynthesisPool):

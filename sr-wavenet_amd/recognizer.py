@@ -246,12 +246,16 @@ class StreamClassifier(StreamHost):
         self.ring_rows = self.nW + self.max_hops - 1      # a step writes max_hops rows before the oldest window is read
         super().__init__(weights, max_batch, self.max_hops * self.hop,
                          os.environ.get("SRWN_RECOG_FUSED", RECOG_FUSED_DEFAULT) != "0")
-        w, Bm, z = self.w, self.max_batch, self._zeros
-        self.ring = z(Bm, self.ring_rows, w.S, dt=torch.float32)
-        self.mean = z(Bm * self.max_hops, w.S, dt=torch.float32)
-        self.logits = z(Bm * self.max_hops, w.C, dt=torch.float32)
-        self.probs = z(Bm * self.max_hops, w.C, dt=torch.float32)
+        self.ring = self._zeros(self.max_batch, self.ring_rows, self.w.S, dt=torch.float32)
         self._pool: Optional["ClassifierPool"] = None
+        self._alloc_emissions()
+
+    def _alloc_emissions(self):
+        """The buffers ``_launch_emit`` writes, for max_batch * max_hops rows, and the step's launch count."""
+        w, rows, z = self.w, self.max_batch * self.max_hops, self._zeros
+        self.mean = z(rows, w.S, dt=torch.float32)
+        self.logits = z(rows, w.C, dt=torch.float32)
+        self.probs = z(rows, w.C, dt=torch.float32)
         self.launches_per_step = 4 + len(self.groups) + (1 if self.fused else 3)
 
     def buffer_bytes(self) -> Dict[str, int]:
@@ -280,12 +284,15 @@ class StreamClassifier(StreamHost):
         """A ``ClassifierPool`` on this classifier's buffers: its ``max_batch`` rows as slots, each a stream at a clock of
         its own.  audio_ring: samples a slot's audio ring holds (default 2 * max_chunk + 1, at least max_chunk + 1).  The
         current ``RecogState`` ends, and an earlier pool; ``start`` ends the pool."""
-        pool = ClassifierPool(self, audio_ring)
+        pool = self._new_pool(audio_ring)
         self._close_pool()
         self._serial += 1
         self._state = None
         self._pool = pool
         return pool
+
+    def _new_pool(self, audio_ring):
+        return ClassifierPool(self, audio_ring)
 
     def _launch_step(self, B: int, h: int, pool: Optional["ClassifierPool"] = None):
         """The launches of a step of h hops (n = h * hop rows): on the audio staged in ``xbuf`` at the clock, or, with
@@ -313,11 +320,18 @@ class StreamClassifier(StreamHost):
             self._launch_twin_products(B, n)
             call("srwn_hop_sum" + sfx, self.r1.data_ptr(), C, self.ring.data_ptr(), self.ring_rows, when, B, h, self.hop, C, S,
                  dt, st)
-        call("srwn_window_mean" + sfx, self.ring.data_ptr(), self.ring_rows, self.mean.data_ptr(), when, B, h, self.hop,
-             self.window, S, v("head_w2").data_ptr(), v("head_b2").data_ptr(), self.logits.data_ptr(), w.C, w.Cp, st)
-        call("srwn_pooled_head", self.mean.data_ptr(), v("head_w2").data_ptr(), v("head_b2").data_ptr(), None,
-             self.probs.data_ptr(), None, None, None, None, B * h, S, w.C, w.Cp, st)
+        self._launch_emit(B, h, when, sfx)
         self._launch_roll(B, n, when, slots)
+
+    def _launch_emit(self, B: int, h: int, when: int, sfx: str):
+        """What a step makes of the hop sums (between the head and the roll): the window means with their pooled logits,
+        then the probabilities.  when, sfx: the clock and "", or a pool's table and "_slots"."""
+        w, st = self.w, K._stream()
+        w2, b2 = w.view("head_w2").data_ptr(), w.view("head_b2").data_ptr()
+        call("srwn_window_mean" + sfx, self.ring.data_ptr(), self.ring_rows, self.mean.data_ptr(), when, B, h, self.hop,
+             self.window, w.S, w2, b2, self.logits.data_ptr(), w.C, w.Cp, st)
+        call("srwn_pooled_head", self.mean.data_ptr(), w2, b2, None, self.probs.data_ptr(), None, None, None, None, B * h,
+             w.S, w.C, w.Cp, st)
 
     def push(self, state: RecogState, audio, return_logits: bool = False):
         """The next samples of every stream, audio [B, n] with any n >= 0 -> probabilities [B, k, C] fp32 of the k window
@@ -443,35 +457,44 @@ class ClassifierPool(AudioRingSlots):
         return "consumed %d" % self._consumed[u]
 
     # ---- one step: every whole hop that waits
+    def _passes(self):
+        """The passes of a ``step``, while any active slot has a whole hop waiting: per pass ``plan_pool_step``, the table
+        uploaded whole and the launches of one classifier step of k hops in their slot forms; yields (k, [(slot, lo, hi)])
+        -- the emission rows [lo, hi) of the pass's k that each slot's stream completed (``emissions_due`` on the slot's own
+        clock; slots with none are left out) -- and moves the slots' clocks on once the caller has taken them."""
+        self._check_open()
+        c, cap, hop = self.c, self.capacity, self.hop
+        while True:
+            k, hops = plan_pool_step(self._received, self._consumed, self._active, hop, self.max_hops)
+            if k == 0:
+                return
+            self.table.copy_(torch.from_numpy(np.stack([self._consumed, self._consumed + hops * hop], 1)))
+            K.run_cached_graph(self._graphs, self._seen, k, c.use_graphs, lambda: c._launch_step(cap, k, self))
+            due = []
+            for u in np.flatnonzero(hops):
+                t0, h = int(self._consumed[u]), int(hops[u])
+                first, count = emissions_due(t0, t0 + h * hop, hop, self.window)
+                if count:      # (first - t0 // hop: hops of this step before the stream's first full window)
+                    due.append((int(u), first - t0 // hop, h))
+                    self._emitted[u] += count
+            yield k, due
+            self._consumed += hops * hop
+
     def step(self, return_logits: bool = False):
         """Runs while any active slot has a whole hop waiting -> {slot: probabilities [e, C] fp32 on the device} for the
         slots whose streams completed e > 0 window positions (``emissions_due`` on the slot's own clock); with
         return_logits (probabilities, logits): a second dict with the pooled logits [e, C] of the same slots.  With nothing
         due nothing is launched."""
-        self._check_open()
-        c, cap, hop = self.c, self.capacity, self.hop
         pp, pl = {}, {}
-        while True:
-            k, hops = plan_pool_step(self._received, self._consumed, self._active, hop, self.max_hops)
-            if k == 0:
-                break
-            Cc = c.w.C
-            self.table.copy_(torch.from_numpy(np.stack([self._consumed, self._consumed + hops * hop], 1)))
-            K.run_cached_graph(self._graphs, self._seen, k, c.use_graphs, lambda: c._launch_step(cap, k, self))
-            probs = logits = None
-            for u in np.flatnonzero(hops):
-                t0, h = int(self._consumed[u]), int(hops[u])
-                first, count = emissions_due(t0, t0 + h * hop, hop, self.window)
-                if count:
-                    if probs is None:      # one copy per pass: the next pass writes the same buffers
-                        probs = c.probs[:cap * k].view(cap, k, Cc).clone()
-                        logits = c.logits[:cap * k].view(cap, k, Cc).clone() if return_logits else None
-                    skip = first - t0 // hop      # hops of this step before the stream's first full window
-                    pp.setdefault(int(u), []).append(probs[u, skip:h])
-                    if return_logits:
-                        pl.setdefault(int(u), []).append(logits[u, skip:h])
-                    self._emitted[u] += count
-            self._consumed += hops * hop
+        for k, due in self._passes():
+            if due:      # one copy per pass: the next pass writes the same buffers
+                c, cap, Cc = self.c, self.capacity, self.c.w.C
+                probs = c.probs[:cap * k].view(cap, k, Cc).clone()
+                logits = c.logits[:cap * k].view(cap, k, Cc).clone() if return_logits else None
+            for u, lo, hi in due:
+                pp.setdefault(u, []).append(probs[u, lo:hi])
+                if return_logits:
+                    pl.setdefault(u, []).append(logits[u, lo:hi])
         cat = lambda p: p[0] if len(p) == 1 else torch.cat(p, dim=0)
         out = {u: cat(p) for u, p in pp.items()}
         return (out, {u: cat(p) for u, p in pl.items()}) if return_logits else out
