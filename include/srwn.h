@@ -1548,6 +1548,38 @@ int srwn_window_embed_match_slots(const float* ring, int32_t ring_rows, const Sr
 int srwn_gallery_match(const float* emb, int32_t rows, int32_t D, const float* gallery, const int32_t* n_gallery,
                        int32_t max_gallery, float* dist, int32_t* nearest, float* dmin, void* stream);
 
+/* ---- student flow inversion (since srwn_version() 121; csrc/srwn_flow_inv.hip): one inverse-autoregressive flow of class
+ * ParallelWaveNet (createFlow, model.py:456-487) run backwards, audio -> noise.  The flow computes
+ *   x_out[t] = x_in[t] * exp(p0[t]) + p1[t],   (p0, p1)[t] = flow_b + relu(stack(RightShift(x_in), encoding)[t]) . flow_w,
+ * where the stack reads x_in[< t] only, so given x_out = y the input is recovered one step at a time:
+ *   h0[t]   = init_b + init_w[0] * x_in[t-2] + init_w[1] * x_in[t-1]   from the RECOVERED samples (zeros before the clip),
+ *             rounded to the activation type, then layer 0's conditioning bias is added (srwn_flow_stream_in's rounding);
+ *   layers  the L conditioned layers of the reference gate over rings of the last d_l + 1 layer inputs, with the
+ *           arithmetic, the ring writes, the zero tap before the clip starts and the conditioning frame
+ *           min(t / pool_stride, cond_frames - 1) of the conditioned generator (srwn_generate_mol); no skip path;
+ *   head    (p0, p1) = flow_b + relu(x_L[t] rounded to the activation type) . flow_w in fp32 (srwn_flow_affine_fwd);
+ *   inverse x_in[t] = (y[t] - p1) * expf(-p0).
+ * One launch inverts ONE flow over the steps [t0, t0 + nsteps) of B streams; a student of F flows is F dependent launches,
+ * the last flow first, each reading the x_in the launch before wrote.  sum_f p0_f[t] is log |d audio / d noise| at t.
+ *   wcr     per layer [srwn conv image, last tap permuted | residual image] (the generators' layer images, without skip)
+ *   flow_w  [R][2] fp32, flow_b [2] fp32 (srwn_flow_affine_fwd's w2 / b2); bias_f, bias_r [L][R]; init_w [2][R]; init_b [R]
+ *   ring    srwn_generate_ring_elems(dilations, nlayers, R) elements per group of 32 streams, zero at t0 = 0
+ *   y, x_in [B][Tout] fp32, prm [B][Tout][2] fp32 or NULL: rows j < nsteps <= Tout are the launch's own (as in
+ *           srwn_generate_resume); y and x_in may not overlap
+ *   cond    the conditioning biases: cb_l of stream u and frame f at element l * cond_layer_stride +
+ *           (u * cond_frames + f) * cond_ld, R values of the activation type (cond_ld >= R)
+ *   carry   float [B][2] = (x_in[t0-1], x_in[t0-2]) in, (x_in[t0+n-1], x_in[t0+n-2]) out; NULL = zeros in, nothing
+ *           written (only with t0 = 0).  Any cut of a run into launches gives the bits of one launch.
+ * Errors, all before any launch: B = 0 or nsteps = 0 is done (0); B, nsteps or t0 < 0, nsteps > Tout, nlayers outside
+ * [1, 64], a dilation < 1, cond_frames or pool_stride < 1, cond_ld < R, cond_frames * pool_stride < t0 + nsteps, or layer
+ * constants that do not fit the LDS of a workgroup (-2); a null pointer other than prm, or a NULL carry with t0 > 0 (-3);
+ * R not 32 or 64, K not 2 (-4); a dtype other than SRWN_BF16 / SRWN_F32 (-1). */
+int srwn_flow_invert(const void* wcr, const float* bias_f, const float* bias_r, const float* init_w, const float* init_b,
+                     const float* flow_w, const float* flow_b, void* ring, const float* y, float* x_in, float* prm,
+                     const int32_t* dilations, int32_t nlayers, int32_t B, int32_t Tout, int32_t nsteps, int32_t R, int32_t K,
+                     const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
+                     int64_t cond_layer_stride, int32_t dtype, void* stream, int32_t t0, float* carry);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,9 @@ SIGNATURES["srwn_window_embed_match"] = (C.c_int, [_p, _i32, _p, _i32, _i32, _i3
                                                    _p, _p, _p, _p, _p])
 SIGNATURES["srwn_window_embed_match_slots"] = SIGNATURES["srwn_window_embed_match"]
 SIGNATURES["srwn_gallery_match"] = (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p])
+# student flow inversion (srwn_version() 121): one flow run backwards over [t0, t0 + nsteps), in the resume form
+SIGNATURES["srwn_flow_invert"] = (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32,
+                                            _p, _i32, _i32, _i64, _i64, _i32, _p, _i32, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -1821,6 +1821,21 @@ class ParallelWaveNet(object):
         syn._eng.repack()
         return syn
 
+    def inverter(self, max_batch=1):
+        """A ``StudentInverter`` with this model's hyper-parameters and a COPY of its current flow parameters (a
+        snapshot, as ``synthesizer``): audio -> noise and the student's exact log-likelihood of held-out audio."""
+        inv = StudentInverter(self.dilations, self.num_flows, filter_width=self.filter_width,
+                              dilation_channels=self.dilation_channels, latent_channels=self.latent_channels,
+                              condition_size=self.condition_size, pool_stride=self.pool_stride, name=self._name,
+                              dtype=self._flow_cfg.dtype, max_batch=max_batch)
+        if self._primary is None:
+            self._engine(1, self.input_size)
+        for w, f in zip(inv._eng.weights, self._primary.flows):
+            w.params.copy_(f.params)
+            w.repack()
+        inv._eng.repack()
+        return inv
+
     # --- checkpointing (model.py:540-567) ---------------------------------------------------------------
     def load(self, sess, logdir):
         if self._teacher_dir is not None and self._teacher is not None:
@@ -1958,6 +1973,8 @@ class StudentSynthesizer(object):
         nz = None
         if noise is not None:
             nz = torch.as_tensor(np.asarray(noise, dtype=np.float32))
+            if tuple(nz.shape) == (B, T, 1):      # (what StudentInverter.invert returns)
+                nz = nz[:, :, 0]
             if tuple(nz.shape) != (B, T):
                 raise ValueError("noise must be [%d, %d] (= frames * pool_stride)" % (B, T))
             nz = nz.to("cuda")
@@ -1974,7 +1991,8 @@ class StudentSynthesizer(object):
     def synthesize(self, encoding, conditions=None, seed=0, temperature=1.0, noise=None):
         """encoding [B, frames, latent_channels] -> audio [B, frames * pool_stride, 1] in [-1, 1] (model.py:535), made in
         chunks of max_chunk.  seed / temperature: scalars or one per stream (a scalar seed s: stream b draws with s + b);
-        noise [B, T]: the logistic noise itself (``ParallelWaveNet.generate``'s `inputs`)."""
+        noise [B, T] (or [B, T, 1], as ``StudentInverter.invert`` returns it): the logistic noise itself
+        (``ParallelWaveNet.generate``'s `inputs`)."""
         st, nz, B, T = self._begin(encoding, conditions, seed, temperature, noise)
         out = torch.cat(list(self._chunks(st, nz, T, self.max_chunk)), dim=1)
         return out.view(B, T, 1).cpu().numpy()
@@ -2000,6 +2018,136 @@ class StudentSynthesizer(object):
         [batch, condition_size] are tiled onto every fed frame.  It ends a running ``stream`` or pool, like ``synthesize``."""
         K._need_gpu()
         return LiveSynthesis(self, int(batch), conditions, seed, temperature)
+
+    def inverter(self, max_batch=None):
+        """A ``StudentInverter`` on this synthesizer's own flow weights (one snapshot serves both directions):
+        ``synth.synthesize(encoding, conditions, noise=inv.invert(x, encoding, conditions))`` is the round trip."""
+        return StudentInverter(self.dilations, self.num_flows, filter_width=self.filter_width,
+                               dilation_channels=self.dilation_channels, latent_channels=self.latent_channels,
+                               condition_size=self.condition_size, pool_stride=self.pool_stride, name=self._name,
+                               dtype=self._eng.dt, max_batch=self.max_batch if max_batch is None else max_batch,
+                               _share=self._eng)
+
+
+class StudentInverter(object):
+    """The reverse direction of the student (``student.FlowInverter``): audio in, out the logistic noise that the flows of
+    a trained ``ParallelWaveNet`` (model.py:456-535) turn into it, and its exact log-likelihood under the student,
+    nll[b, t] = -log logistic(z[b, t]; 0, 1) + sum over the flows of their log scales at t (nats).  The inverse of an
+    autoregressive flow is sequential: one persistent launch per flow and chunk steps through the samples.
+
+    The audio is taken as the flows' UNCLIPPED output: samples that the student clipped at +-1 (model.py:535) do not
+    invert to the noise that made them.  ``load`` reads what ``ParallelWaveNet.save`` wrote."""
+
+    def __init__(self, dilations, num_flows, filter_width=2, dilation_channels=32, latent_channels=16, condition_size=0,
+                 pool_stride=512, name="ParallelWaveNet", dtype=None, max_batch=1, gate_mode="reference", _share=None):
+        from .student import FlowInverter
+        self.dilations, self.num_flows = list(dilations), int(num_flows)
+        self.filter_width, self.dilation_channels = filter_width, dilation_channels
+        self.latent_channels, self.condition_size, self.pool_stride = latent_channels, condition_size, pool_stride
+        self._name, self.max_batch = name, int(max_batch)
+        cfg = StackConfig(dilations=list(dilations), filter_width=filter_width, dilation_channels=dilation_channels,
+                          cond_channels=latent_channels + condition_size, pool_stride=pool_stride,
+                          dtype=dtype or _default_dtype(), gate_mode=gate_mode)
+        if _share is None:
+            self._eng = FlowInverter(cfg, num_flows, max_batch=max_batch)
+        else:      # a FlowSynthesizer: its weights
+            self._eng = FlowInverter(cfg, num_flows, max_batch=max_batch, device=_share.dev, weights=_share.weights)
+
+    @property
+    def network_params(self):
+        out = {}
+        for i, w in enumerate(self._eng.weights):
+            out.update(w.tf_variables("%s/Flow%d/Flow%d" % (self._name, i, i)))           # model.py:417,468,510
+        return out
+
+    def load(self, logdir):
+        ok = _read_state(logdir, lambda: self.network_params)
+        if ok:
+            for w in self._eng.weights:
+                w.repack()
+            self._eng.repack()
+        return ok
+
+    @classmethod
+    def from_checkpoint(cls, logdir, dilations, num_flows, **kwargs):
+        """An inverter on the flows saved in `logdir` (``ParallelWaveNet.save``); the hyper-parameters are the
+        constructor's (the student's checkpoint holds variables only)."""
+        inv = cls(dilations, num_flows, **kwargs)
+        if not inv.load(logdir):
+            raise FileNotFoundError("%s: no student checkpoint (ParallelWaveNet.save writes one)" % logdir)
+        return inv
+
+    # ------------------------------------------------------------------------------------------------
+    def _cond(self, encoding, conditions):
+        """encoding [B, frames, latent] (+ conditions [B, condition_size]) -> encoding_w_condition as a host tensor; every
+        refusal, no device work."""
+        enc = np.asarray(encoding, dtype=np.float32)
+        if enc.ndim != 3 or enc.shape[2] != self.latent_channels:
+            raise ValueError("encoding must be [batch, frames, latent_channels=%d]" % self.latent_channels)
+        B = int(enc.shape[0])
+        if not 1 <= B <= self.max_batch or enc.shape[1] < 1:
+            raise ValueError("encoding of %d streams x %d frames: this inverter was built for max_batch=%d"
+                             % (B, enc.shape[1], self.max_batch))
+        c = _check_conditions(B, conditions, self.condition_size, "student")
+        e = torch.as_tensor(enc)
+        return e if c is None else _tile_conditions(e, torch.as_tensor(c))
+
+    def _audio(self, audio, batch, length=None):
+        x = np.asarray(audio, dtype=np.float32)
+        if x.ndim == 3 and x.shape[2] == 1:
+            x = x[:, :, 0]
+        if x.ndim != 2 or x.shape[0] != batch or (length is not None and x.shape[1] != length):
+            raise ValueError("audio must be [%d, %s], got %s" % (batch, "n" if length is None else length, np.shape(audio)))
+        return x
+
+    def _invert(self, audio, encoding, conditions):
+        from .student import logistic_nll
+        e = self._cond(encoding, conditions)
+        x = self._audio(audio, e.shape[0], e.shape[1] * self.pool_stride)
+        z, ls = self._eng.invert(torch.as_tensor(x), e.contiguous())
+        return z, logistic_nll(z, ls)
+
+    def invert(self, audio, encoding, conditions=None):
+        """audio [B, T = frames * pool_stride] (or [B, T, 1]) -> noise [B, T, 1], ``ParallelWaveNet.generate``'s `inputs`."""
+        z, _ = self._invert(audio, encoding, conditions)
+        return z.view(z.shape[0], -1, 1).cpu().numpy()
+
+    def log_likelihood(self, audio, encoding, conditions=None):
+        """-log p(audio[b, t] | audio[b, < t], encoding) under the student, [B, T] in nats."""
+        return self._invert(audio, encoding, conditions)[1].cpu().numpy()
+
+    def stream(self, encoding, conditions=None):
+        """An ``InversionStream`` over the encoding: ``push`` audio chunk by chunk; chunking never changes a bit."""
+        e = self._cond(encoding, conditions)
+        return InversionStream(self, self._eng.start(e.contiguous()))
+
+
+class InversionStream(object):
+    """NumPy face of one running batch of inversion streams (``StudentInverter.stream``).  ``t``: samples inverted per
+    stream."""
+
+    def __init__(self, owner, state):
+        self._owner, self._st, self.batch_size = owner, state, state.B
+        self._nll_sum = np.zeros(state.B, np.float64)
+
+    @property
+    def t(self):
+        return self._st.t
+
+    def push(self, audio):
+        """audio [B, n] -> (noise [B, n], nll [B, n]) of exactly those samples.  A push past frames * pool_stride is
+        refused (ValueError) and leaves the stream where it was."""
+        from .student import logistic_nll
+        x = self._owner._audio(audio, self._st.B)
+        z, ls = self._owner._eng.step(self._st, torch.as_tensor(x))
+        nll = logistic_nll(z, ls).cpu().numpy()
+        self._nll_sum += nll.sum(1, dtype=np.float64)
+        return z.cpu().numpy(), nll
+
+    def bits_per_sample(self):
+        """Mean nll of everything pushed so far, in bits, per stream [B] (NaN before the first sample)."""
+        from .scorer import bits_per_sample
+        return np.array([bits_per_sample(v, self._st.t) for v in self._nll_sum])
 
 
 class LiveSynthesis(_LiveStream):

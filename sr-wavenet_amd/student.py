@@ -505,6 +505,155 @@ class FlowWeights:
         self._pk.idx = None
 
 
+def _check_flow_cfg(flow_cfg: StackConfig):
+    """What the flows' inference classes refuse about a configuration, before any device work."""
+    if not flow_cfg.cond_channels:
+        raise ValueError("a flow is conditioned on the encoding (model.py:431): cond_channels > 0")
+    if flow_cfg.gate_mode != "reference":
+        raise NotImplementedError("gate_mode %r is not built for the flows of ParallelWaveNet" % (flow_cfg.gate_mode,))
+    if flow_cfg.filter_width != 2 or flow_cfg.dilation_channels not in (32, 64):
+        raise NotImplementedError("flows: filter_width 2 and dilation_channels 32 / 64 are built")
+
+
+def logistic_nll(noise: torch.Tensor, log_scale: torch.Tensor) -> torch.Tensor:
+    """-log p(audio[t] | audio[< t]) in nats, from the two outputs of a ``FlowInverter``: the logistic(0, 1) base density
+    of the student's noise (student.py:104) at z, -log f(z) = |z| + 2 log(1 + exp(-|z|)), plus log |d audio / d z| =
+    the sum of the flows' log scales."""
+    a = noise.abs()
+    return a + 2.0 * torch.log1p(torch.exp(-a)) + log_scale
+
+
+class InvertState:
+    """One batch of streams of a ``FlowInverter`` (which holds the device side: an inverter serves one state at a time).
+    ``t``: samples inverted so far; ``limit`` = frames * pool_stride."""
+
+    def __init__(self, batch: int, frames: int, limit: int, serial: int, cond_all):
+        self.B, self.frames, self.limit, self.t, self._serial = batch, frames, limit, 0, serial
+        self.cond_all = cond_all      # per flow [L, B * frames, R]: cb of every layer and frame
+
+
+class FlowInverter:
+    """``num_flows`` flows (model.py:456-487) run backwards: audio in, the noise that makes it and log |d audio / d noise|
+    out.  A flow's inverse is sequential (x_in[t] needs the stack's output on the recovered x_in[< t]), so a chunk costs one
+    launch of csrc/srwn_flow_inv.hip per flow, the last flow first, each a persistent kernel that steps through the chunk
+    on the queue-cached layer rings of the generators.  ``start`` a batch of streams on their encodings, then ``step`` it
+    chunk by chunk; any cut into chunks gives the bits of one call.  weights: the ``FlowWeights`` to serve (a
+    ``FlowSynthesizer``'s own: ``FlowSynthesizer.inverter``); default: new ones."""
+
+    def __init__(self, flow_cfg: StackConfig, num_flows: int, max_batch: int = 1, device="cuda", weights=None):
+        _check_flow_cfg(flow_cfg)
+        if min(int(num_flows), int(max_batch)) < 1:
+            raise ValueError("num_flows and max_batch must be >= 1")
+        K._need_gpu()
+        from . import _lib, packing as P
+        import ctypes
+        cfg = replace(flow_cfg, head_mode="flow", shift_input=True, output_channels=2)
+        self.cfg, self.F, self.max_batch = cfg, int(num_flows), int(max_batch)
+        self.dev, self.dt = torch.device(device), cfg.dtype
+        self.L, self.R, self.E, self.pool_stride = len(cfg.dilations), cfg.dilation_channels, cfg.cond_channels, int(cfg.pool_stride)
+        self.weights = list(weights) if weights is not None else [FlowWeights(cfg, self.dev) for _ in range(self.F)]
+        if len(self.weights) != self.F:
+            raise ValueError("%d FlowWeights for %d flows" % (len(self.weights), self.F))
+        L, R, Kw = self.L, self.R, cfg.filter_width
+        self._dil = (ctypes.c_int32 * L)(*[int(d) for d in cfg.dilations])
+        # generation-order images, per layer [conv (last tap permuted) | residual] back to back (packing.pack_conv_gen)
+        sec = self.weights[0].sections
+        self._pk = K.Packer(self.dev)
+        for l in range(L):
+            P.pack_conv_gen(self._pk, sec["WF"].offset + l * Kw * R * R, Kw, R)
+            P.pack_res(self._pk, sec["WR"].offset + l * R * R, R)
+        z = lambda *s, dt=self.dt: torch.zeros(s, dtype=dt, device=self.dev)
+        self.images = [z(self._pk.total) for _ in range(self.F)]
+        self.groups = (self.max_batch + 31) // 32
+        relems = int(_lib.load().srwn_generate_ring_elems(self._dil, L, R))
+        self.rings = [z(self.groups * relems) for _ in range(self.F)]
+        self.carry_all = z(self.F, self.max_batch, 2, dt=torch.float32)
+        self._serial = 0
+        self._state: Optional[InvertState] = None
+        if weights is None:
+            for w in self.weights:
+                w.repack()
+        self.repack()
+
+    def repack(self):
+        """The generation-order images from the weights' current parameters (after a load, or when the synthesizer that
+        shares the weights was given new ones)."""
+        self._pk.finalize()
+        for w, img in zip(self.weights, self.images):
+            self._pk.gather(w.params, img)
+        torch.cuda.current_stream().synchronize()
+        self._pk.idx = None
+
+    # ------------------------------------------------------------------------------------------------
+    def _check_cond(self, cond) -> torch.Tensor:
+        cond = torch.as_tensor(cond, dtype=torch.float32)
+        if cond.dim() != 3 or cond.shape[2] != self.E:
+            raise ValueError("cond must be [batch, frames, %d], got %s" % (self.E, tuple(cond.shape)))
+        if not 1 <= cond.shape[0] <= self.max_batch or cond.shape[1] < 1:
+            raise ValueError("cond: %d streams x %d frames; this inverter holds max_batch=%d"
+                             % (cond.shape[0], cond.shape[1], self.max_batch))
+        return cond
+
+    def start(self, cond) -> InvertState:
+        """cond [B <= max_batch, frames, E] (encoding_w_condition) -> a state at clock 0: zero rings, zero carries."""
+        cond = self._check_cond(cond)
+        B, frames = int(cond.shape[0]), int(cond.shape[1])
+        rows, st = B * frames, K._stream()
+        Ep = self.weights[0].Ep
+        cin = torch.zeros((rows, Ep), dtype=self.dt, device=self.dev)
+        cin[:, :self.E].copy_(cond.reshape(rows, self.E).to(self.dev))
+        cond_all = []
+        for w, ring in zip(self.weights, self.rings):      # cb of every layer and frame (model.py:180), as FlowSynthesizer.start
+            ca = torch.empty((self.L, rows, self.R), dtype=self.dt, device=self.dev)
+            call("srwn_pw_linear_ychunks", cin.data_ptr(), Ep, Ep, w.wptr(w.o_wc), w.view("BC").reshape(-1).data_ptr(),
+                 ca.data_ptr(), self.R, self.R, rows * self.R, self.L * self.R, self.L * self.R, rows, K.abi_dtype(self.dt), st)
+            cond_all.append(ca)
+            ring.zero_()
+        self.carry_all.zero_()
+        self._serial += 1
+        self._state = InvertState(B, frames, frames * self.pool_stride, self._serial, cond_all)
+        return self._state
+
+    def step(self, state: InvertState, audio, want_params: bool = False):
+        """The next n samples of every stream: audio [B, n] (taken as the flows' unclipped output) -> (noise [B, n],
+        log_scale [B, n] = the sum over the flows of p0) fp32; want_params: also (prm, x_in), per flow the [B, n, 2]
+        parameters and the [B, n] recovered input.  Refuses (ValueError, state untouched) a state that is not the current
+        one and steps past frames * pool_stride."""
+        if state is not self._state or state._serial != self._serial:
+            raise ValueError("this state is not the inverter's current one (start() began another)")
+        y = torch.as_tensor(audio, dtype=torch.float32)
+        if y.dim() != 2 or y.shape[0] != state.B:
+            raise ValueError("audio must be [%d, n], got %s" % (state.B, tuple(y.shape)))
+        B, n = state.B, int(y.shape[1])
+        if state.t + n > state.limit:
+            raise ValueError("chunk of %d samples at %d: the encoding ends at frames * pool_stride = %d"
+                             % (n, state.t, state.limit))
+        y = y.to(self.dev).contiguous()
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=self.dev)
+        xs, prms = [None] * self.F, [None] * self.F
+        st, dt = K._stream(), K.abi_dtype(self.dt)
+        for i in range(self.F - 1, -1, -1):      # the last flow first; each reads what the launch before recovered
+            w, ca = self.weights[i], state.cond_all[i]
+            v = w.view
+            xs[i], prms[i] = z(B, n), z(B, n, 2)
+            call("srwn_flow_invert", self.images[i].data_ptr(), v("BF").data_ptr(), v("BR").data_ptr(),
+                 v("init_w").data_ptr(), v("init_b").data_ptr(), v("flow_w").data_ptr(), v("flow_b").data_ptr(),
+                 self.rings[i].data_ptr(), y.data_ptr(), xs[i].data_ptr(), prms[i].data_ptr(), self._dil, self.L, B, n, n,
+                 self.R, self.cfg.filter_width, ca.data_ptr(), state.frames, self.pool_stride, self.R,
+                 ca.shape[1] * self.R, dt, st, state.t, self.carry_all[i].data_ptr())
+            y = xs[i]
+        state.t += n
+        log_scale = prms[0][:, :, 0].clone()
+        for p in prms[1:]:
+            log_scale += p[:, :, 0]
+        return (xs[0], log_scale, prms, xs) if want_params else (xs[0], log_scale)
+
+    def invert(self, audio, cond, want_params: bool = False):
+        """``start(cond)`` and one ``step`` over the whole of audio [B, T]."""
+        cond = self._check_cond(cond)
+        return self.step(self.start(cond), audio, want_params)
+
+
 class SynthState:
     """One batch of streams of a ``FlowSynthesizer`` (which holds the device side: a synthesizer serves one state at a
     time).  ``t``: samples made so far; ``limit`` = frames * pool_stride.  A ``live`` state is fed its frames while it runs
@@ -527,12 +676,7 @@ class FlowSynthesizer:
     def __init__(self, flow_cfg: StackConfig, num_flows: int, max_batch: int = 1, max_chunk: int = 1600,
                  max_frames: int = 32, device="cuda"):
         K._need_gpu()
-        if not flow_cfg.cond_channels:
-            raise ValueError("a flow is conditioned on the encoding (model.py:431): cond_channels > 0")
-        if flow_cfg.gate_mode != "reference":
-            raise NotImplementedError("gate_mode %r is not built for the flows of ParallelWaveNet" % (flow_cfg.gate_mode,))
-        if flow_cfg.filter_width != 2 or flow_cfg.dilation_channels not in (32, 64):
-            raise NotImplementedError("flows: filter_width 2 and dilation_channels 32 / 64 are built")
+        _check_flow_cfg(flow_cfg)
         if min(int(num_flows), int(max_batch), int(max_chunk), int(max_frames)) < 1:
             raise ValueError("num_flows, max_batch, max_chunk and max_frames must be >= 1")
         cfg = replace(flow_cfg, head_mode="flow", shift_input=True, output_channels=2)
@@ -570,6 +714,12 @@ class FlowSynthesizer:
     def repack(self):
         for w in self.weights:
             w.repack()
+
+    def inverter(self, max_batch: Optional[int] = None) -> "FlowInverter":
+        """A ``FlowInverter`` on this synthesizer's own ``FlowWeights``: both directions serve one snapshot (after new
+        parameters and ``repack`` here, call the inverter's ``repack`` too)."""
+        return FlowInverter(self.cfg, self.F, max_batch=self.max_batch if max_batch is None else max_batch,
+                            device=self.dev, weights=self.weights)
 
     # ------------------------------------------------------------------------------------------------
     def start(self, cond, seeds=0, temperature=1.0, live=False, batch=None) -> SynthState:
