@@ -4,6 +4,8 @@ MI355X implementation: same model calls, no TensorFlow session, no plotting.
 
   python examples/teacher.py --teacher runs/teacher --steps 200                    # synthetic waves (simple_audio)
   python examples/teacher.py --teacher runs/teacher --tfrecord nsynth.tfrecord     # NSynth clips (nsynth.py)
+  python examples/teacher.py --teacher runs/teacher --tfrecord nsynth.tfrecord --device-data
+                                            # the clips loaded onto the device once, every batch drawn there (dataset.py)
 """
 import argparse
 import os
@@ -30,6 +32,9 @@ def main(argv=None):
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--print-steps", type=int, default=50)
     p.add_argument("--layers", type=int, default=30)
+    p.add_argument("--device-data", action="store_true",
+                   help="keep the clips on the device and draw every batch inside the training step (model.fit)")
+    p.add_argument("--device-clips", type=int, default=256, help="--device-data without --tfrecord: synthetic waves to hold")
     a = p.parse_args(argv)
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     data = NsynthDataReader(a.tfrecord, a.batch_size, a.num_samples, audio_max_length=a.audio_max_length) if a.tfrecord else None
@@ -37,6 +42,8 @@ def main(argv=None):
                                  latent_channels=a.latent_channels, skip_channels=128, pool_stride=a.pool_stride,
                                  learning_rate=1e-4)                                     # teacher.py:61
     teacher.load(a.teacher)
+    if a.device_data:
+        return fit_loop(a, teacher)
     loss = None
     for step in range(a.steps):
         x = data.next()[0] if data else generate_wave_batch(a.batch_size, a.num_samples)[0].astype(np.float32)
@@ -45,6 +52,30 @@ def main(argv=None):
             regen = teacher.reconstruct(x, None); enc = teacher.encode(x, None)           # teacher.py:83-84
             print(step, float(loss), "reconstruction rms %.3f" % float(np.sqrt(np.mean(regen ** 2))), "encoding", enc.shape, flush=True)
         teacher.save(a.teacher, step, force=False)                                        # once per minute, teacher.py:110
+    teacher.save(a.teacher, a.steps - 1, force=True)
+    return float(loss)
+
+
+def fit_loop(a, teacher):
+    """--device-data: the TFRecord file (or a block of synthetic waves) is loaded onto the device once; the steps between
+    two prints are one ``fit`` call -- graph replays with no upload, one host wait for the losses."""
+    import importlib
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    if a.tfrecord:
+        data = D.DeviceDataset.from_tfrecord(a.tfrecord, a.audio_max_length, label_key=None)
+    else:
+        data = D.DeviceDataset(generate_wave_batch(a.device_clips, a.num_samples)[0].astype(np.float32))
+    sampler = data.sampler(a.batch_size, a.num_samples, seed=0)
+    print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)
+    loss, step = None, 0
+    while step < a.steps:
+        n = min(a.print_steps, a.steps - step)
+        loss = teacher.fit(sampler, n)[-1]
+        step += n
+        x = data.audio[sampler.indices.long(), :a.num_samples].cpu().numpy()      # the last batch drawn ("head" crop)
+        regen = teacher.reconstruct(x, None); enc = teacher.encode(x, None)
+        print(step - 1, float(loss), "reconstruction rms %.3f" % float(np.sqrt(np.mean(regen ** 2))), "encoding", enc.shape, flush=True)
+        teacher.save(a.teacher, step - 1, force=False)
     teacher.save(a.teacher, a.steps - 1, force=True)
     return float(loss)
 

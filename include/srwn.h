@@ -1580,6 +1580,39 @@ int srwn_flow_invert(const void* wcr, const float* bias_f, const float* bias_r, 
                      const void* cond, int32_t cond_frames, int32_t pool_stride, int64_t cond_ld,
                      int64_t cond_layer_stride, int32_t dtype, void* stream, int32_t t0, float* carry);
 
+/* ---- device-resident datasets (since srwn_version() 122; csrc/srwn_data.hip): the two launches that a BatchSampler
+ * (sr-wavenet_amd/dataset.py) puts around the training step, inside its hipGraph.  The clips stay on the device; a replay
+ * needs no upload and no host wait.
+ *   state   int64 [2] = {seed, step} in device memory.  srwn_batch_draw only reads it; srwn_step_log ticks `step`, as
+ *           srwn_adam_step ticks its own counter.
+ * srwn_batch_draw draws the B records of the step and writes what the engines' set_inputs writes from a host batch.  Row b
+ * is position p = (step * world + rank) * B + b of the sample sequence: epoch e = p / num_clips, place i = p % num_clips,
+ * record perm(seed, e)(i) (shuffle != 0: a keyed bijection on [0, num_clips) -- four alternating Feistel rounds on the next
+ * power of two, keyed by the splitmix64 finaliser of the samplers' uniforms, cycle-walked back into range) or i; crop 0 takes
+ * samples [0, T) of the clip (tf.slice, nsynth.py:31), crop 1 an offset uniform on [0, clip_len - T] drawn from (seed, p).
+ * dataset.draw_plan states the same function in Python.
+ *   clips    [num_clips][clip_len] fp32;  labels [num_clips] int32, or NULL without one-hot rows
+ *   audio0   [B][T] fp32: the cropped rows;  audio1 the same rows once more, or NULL (the auto-encoder's second buffer)
+ *   codes    [B][T] int32 or NULL: the rows' mu-law codes at quantization_channels, with the bits of srwn_mu_law_encode
+ *   onehot   NULL, or a matrix of onehot_dtype (SRWN_F32 / SRWN_BF16) with onehot_ld elements per row: rows
+ *            [b * onehot_rows, (b + 1) * onehot_rows) get, in columns [onehot_col0, onehot_col0 + num_classes), the one-hot
+ *            row of record b's label -- all zeros for a label outside [0, num_classes), as tf.one_hot; other columns are
+ *            not touched.  (The classifier: onehot_rows 1, column 0, fp32 [B][C]; the auto-encoder: the frames of a clip,
+ *            behind the latent columns of the decoder's conditioning input.)
+ *   indices  [B] int32: the records drawn
+ * Errors, all before any launch: B = 0 or T = 0 is done (0); a null clips, state, audio0 or indices, or one-hot rows without
+ * labels (-3); num_clips or clip_len < 1, T > clip_len, B > 65535, rank outside [0, world), a crop other than 0 / 1,
+ * quantization_channels < 2 with codes, one-hot columns that do not fit onehot_ld, a buffer that is not 4-byte aligned (-2);
+ * a one-hot dtype other than SRWN_F32 / SRWN_BF16 (-1).
+ * srwn_step_log is the step's last launch: log[step % capacity] = loss[0], then step += 1 (one thread).  The tick is here
+ * because every workgroup of srwn_batch_draw reads `step`.  Errors: a null pointer (-3), capacity < 1 (-2). */
+int srwn_batch_draw(const float* clips, const int32_t* labels, int32_t num_clips, int64_t clip_len, const int64_t* state,
+                    int32_t B, int32_t T, int32_t shuffle, int32_t crop, int32_t rank, int32_t world, float* audio0,
+                    float* audio1, int32_t* codes, int32_t quantization_channels, void* onehot, int64_t onehot_ld,
+                    int32_t onehot_rows, int32_t onehot_col0, int32_t num_classes, int32_t onehot_dtype, int32_t* indices,
+                    void* stream);
+int srwn_step_log(const float* loss, float* log, int32_t capacity, int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -294,6 +294,11 @@ SIGNATURES["srwn_gallery_match"] = (C.c_int, [_p, _i32, _i32, _p, _p, _i32, _p, 
 SIGNATURES["srwn_flow_invert"] = (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32,
                                             _p, _i32, _i32, _i64, _i64, _i32, _p, _i32, _p])
 
+# device-resident datasets (srwn_version() 122): the draw and the log launch around a training step fed by a BatchSampler
+SIGNATURES["srwn_batch_draw"] = (C.c_int, [_p, _p, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p,
+                                           _i64, _i32, _i32, _i32, _i32, _p, _p])
+SIGNATURES["srwn_step_log"] = (C.c_int, [_p, _p, _i32, _p, _p])
+
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded
 

@@ -52,6 +52,96 @@ def _train_step(eng):
     return out
 
 
+def _fit_part(eng, sampler, dest, part):
+    """The launches of one ``fit`` step on either side of the gradient all-reduce: 0 = {draw, forward, backward},
+    1 = {Adam, re-pack, log}.  Between the sampler's two launches this is ``train_step``'s own sequence."""
+    if part == 0:
+        sampler.draw(**dest)
+        if hasattr(eng, "dec"):          # the auto-encoder pair (encoder.AutoEncoderEngine)
+            eng.forward()
+        else:
+            eng.forward(defer_loss=True)
+        eng.backward()
+    else:
+        eng.optimizer_step()
+        sampler.log_step(eng.loss)
+
+
+def _fit(eng, sampler, steps, dest):
+    """``steps`` training steps of an engine fed by a ``dataset.BatchSampler``: every batch is drawn on the device by the
+    step's first launch (``dest``: where ``BatchSampler.draw`` writes what ``set_inputs`` would) and the loss is logged
+    by its last, so a run of steps needs no upload and no host wait -- the host waits once per ``log_capacity`` steps to
+    drain the loss ring.  Capture follows ``_train_step``'s rule: two eager steps of this (engine, sampler) pair, then
+    hipGraphs of its own (the graphs of ``train(x)`` are not touched); SRWN_MODEL_GRAPHS=0 keeps eager launches.
+    Returns every step's loss, float32 [steps]."""
+    steps = int(steps)
+    if steps < 0:
+        raise ValueError("steps %d" % steps)
+    st = getattr(eng, "_fit_state", None)
+    if st is None or st["sampler"] is not sampler:
+        st = eng._fit_state = {"sampler": sampler, "eager": 0, "graphs": None, "failed": False}
+    world = eng.dec.world if hasattr(eng, "dec") else eng.world
+    out = np.empty(steps, np.float32)
+    done = 0
+    while done < steps:
+        n = min(steps - done, sampler.log_capacity)
+        step0 = sampler.step
+        for _ in range(n):
+            if st["graphs"] is not None:
+                st["graphs"][0].replay()
+                if len(st["graphs"]) > 1:
+                    eng.allreduce_grads()
+                    st["graphs"][1].replay()
+            else:
+                _fit_part(eng, sampler, dest, 0)
+                eng.allreduce_grads()
+                _fit_part(eng, sampler, dest, 1)
+                st["eager"] += 1
+                if st["eager"] >= 2 and os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0" and not st["failed"]:
+                    try:
+                        st["graphs"] = _fit_capture(eng, sampler, dest, world)
+                    except Exception as e:   # keep training with eager launches, say why once
+                        st["failed"] = True
+                        print("hipGraph capture failed (%s); continuing with eager launches" % e)
+            sampler.step += 1
+        out[done:done + n] = sampler.losses(step0, n)          # the host waits here
+        done += n
+    return out
+
+
+def _fit_capture(eng, sampler, dest, world):
+    """The ``fit`` step as one hipGraph, or with several ranks as two with the all-reduce left between them (see
+    ``WaveNetEngine.capture_graphs``).  Capturing launches nothing: the device step does not tick."""
+    import gc
+    torch.cuda.synchronize()
+    gc.collect()        # (a collection inside a capture may destroy hipGraphs mid-capture: kernels.run_cached_graph)
+    g0 = torch.cuda.CUDAGraph()
+    if world == 1 and os.environ.get("SRWN_FORCE_DIST") != "1":
+        with torch.cuda.graph(g0):
+            _fit_part(eng, sampler, dest, 0)
+            _fit_part(eng, sampler, dest, 1)
+        graphs = [g0]
+    else:
+        with torch.cuda.graph(g0):
+            _fit_part(eng, sampler, dest, 0)
+        g1 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g1, pool=g0.pool()):
+            _fit_part(eng, sampler, dest, 1)
+        graphs = [g0, g1]
+    torch.cuda.synchronize()
+    return graphs
+
+
+def _fit_labels(sampler, width, who, what):
+    """The dataset of `sampler` must hold labels of `width` classes (their one-hot rows are `who`'s `what`)."""
+    d = sampler.dataset
+    if d.labels is None:
+        raise ValueError("%s.fit: the dataset holds no labels; their one-hot rows are the %s" % (who, what))
+    if d.num_classes != int(width):
+        raise ValueError("%s.fit: the dataset has num_classes=%d, the model's %s are %d wide"
+                         % (who, d.num_classes, what, int(width)))
+
+
 def _default_dtype():
     return torch.float32 if os.environ.get("SRWN_DTYPE", "bf16").lower() in ("f32", "fp32", "float32") else torch.bfloat16
 
@@ -223,6 +313,16 @@ class WaveNet(_EngineOwner):
         eng = self._stage(inputs, targets)
         _train_step(eng)
         return np.float32(eng.loss.item())
+
+    def fit(self, sampler, steps):
+        """``steps`` training steps on batches a ``dataset.BatchSampler`` draws on the device (the labels' one-hot rows
+        are the targets); returns every step's loss, float32 [steps].  See ``_fit``."""
+        if sampler.num_samples != self.input_size:
+            raise ValueError("inputs have %d samples, the model was built for input_size=%d"
+                             % (sampler.num_samples, self.input_size))
+        _fit_labels(sampler, self.output_size, "WaveNet", "targets")
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        return _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels))
 
     def predict(self, inputs):
         eng = self._stage(inputs)
@@ -681,6 +781,19 @@ class WaveNetTeacher(_EngineOwner):
         _train_step(eng)
         return np.float32(eng.loss.item())
 
+    def fit(self, sampler, steps):
+        """``steps`` training steps on batches a ``dataset.BatchSampler`` draws on the device (with the softmax head the
+        draw writes the mu-law targets too); returns every step's loss, float32 [steps].  See ``_fit``.  The unconditioned
+        teacher only: a conditioned teacher's encoding comes from another model."""
+        if self.use_encoding:
+            raise NotImplementedError("WaveNetTeacher.fit: this teacher was built with use_encoding=True and its encoding "
+                                      "comes from another model; feed it with train(inputs, encoding, conditions)")
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        dest = dict(audio=eng.audio)
+        if self.head == "softmax":
+            dest.update(codes=eng.targets, quantization_channels=self.quantization_channels)
+        return _fit(eng, sampler, steps, dest)
+
     def get_logits(self, inputs, encoding=None, conditions=None):
         eng = self._stage(inputs, encoding, conditions)
         return eng.forward(want_logits=True).cpu().numpy()
@@ -1102,6 +1215,18 @@ class WaveNetAutoEncoder(object):
         eng = self._stage(inputs, conditions)
         _train_step(eng)
         return np.float32(eng.loss.item())
+
+    def fit(self, sampler, steps):
+        """``steps`` training steps on batches a ``dataset.BatchSampler`` draws on the device; with condition_size > 0
+        the labels' one-hot rows are the conditions.  Returns every step's loss, float32 [steps].  See ``_fit``."""
+        if self.condition_size > 0:
+            _fit_labels(sampler, self.condition_size, "WaveNetAutoEncoder", "conditions")
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        d = eng.dec
+        dest = dict(audio=eng.enc.x, audio2=d.audio)
+        if self.condition_size > 0:
+            dest.update(onehot=d.cond_in, onehot_rows=d.frames, onehot_col0=self.latent_channels)
+        return _fit(eng, sampler, steps, dest)
 
     def encode(self, inputs, conditions=None):
         eng = self._stage(inputs, conditions)
@@ -1875,6 +2000,10 @@ class ParallelWaveNet(object):
         logs = sum(f.prm[:, 0].view(eng.B, eng.T).sum(1) for f in eng.flows)
         return (logs + 2.0 * eng.T).double().cpu().numpy()
 
+    def fit(self, sampler, steps):
+        raise NotImplementedError("ParallelWaveNet.fit: a student step needs noise and teacher passes beside the clips; "
+                                  "feed it with train(sess, inputs, truth, encoding, conditions)")
+
     def train_fast(self, sess, inputs, truth, encoding, conditions=None):
         """One distillation step (model.py:634-642): returns (loss, power_loss)."""
         eng = self._stage(inputs, truth, encoding, conditions)
@@ -2491,6 +2620,10 @@ class SiameseWaveNet(_EngineOwner):
 
     def save(self, sess, logdir, global_step, force=False, fmt=None):
         return super().save(logdir, global_step, force, fmt)
+
+    def fit(self, sampler, steps):
+        raise NotImplementedError("SiameseWaveNet.fit: a step needs pairs of clips and their labels; feed it with "
+                                  "train(sess, inputs_left, inputs_right, labels)")
 
     def train(self, sess, inputs_left, inputs_right, labels):
         x = self._pair(inputs_left, inputs_right)
