@@ -4,6 +4,7 @@
 
   python examples/siamese.py --train --logdir runs/siamese --steps 1000
   python examples/siamese.py --test --logdir runs/siamese
+  python examples/siamese.py --train --logdir runs/siamese --steps 1000 --device-data
 """
 import argparse
 import os
@@ -29,15 +30,26 @@ def main(argv=None):
     p.add_argument("--num-samples", type=int, default=5120)
     p.add_argument("--print-steps", type=int, default=100)
     p.add_argument("--seed", type=int, default=None, help="seed of the wave generator (default: unseeded)")
+    p.add_argument("--layers", type=int, default=30)
+    p.add_argument("--device-data", action="store_true",
+                   help="--train on pairs drawn on the device from a labelled set held there (model.fit)")
+    p.add_argument("--tfrecord", type=str, default=None, help="--device-data: an NSynth TFRecord file, labelled by --label-key")
+    p.add_argument("--audio-max-length", type=int, default=16000)
+    p.add_argument("--label-key", type=str, default="instrument_family")
+    p.add_argument("--num-classes", type=int, default=11)
+    p.add_argument("--device-clips", type=int, default=256,
+                   help="--device-data without --tfrecord: generated waves to hold, labelled by wave shape")
     a = p.parse_args(argv)
     rng = np.random.RandomState(a.seed) if a.seed is not None else None
-    dilations = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3
+    dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     network = SiameseWaveNet(input_size=a.num_samples, output_dimensions=2, dilations=dilations, skip_channels=128,
                              learning_rate=1e-4)                                             # siamese.py:44
     sess = None                                                                               # accepted and ignored
     network.load(sess, a.logdir)
     loss = None
-    if a.train:
+    if a.train and a.device_data:
+        loss = fit_loop(a, network, rng)
+    elif a.train:
         global_step = a.start
         for global_step in range(a.start, a.steps):
             pairs = [(generate_random_wave(a.num_samples, rng=rng), generate_random_wave(a.num_samples, rng=rng))
@@ -58,6 +70,35 @@ def main(argv=None):
             embedding2 = network.get_embedding(sess, [x2])
             print(embedding1, embedding2, (y1 == y2).all(), embedding1.shape, flush=True)
     return None if loss is None else float(loss)
+
+
+def fit_loop(a, network, rng):
+    """--device-data: a labelled set of recordings -- the TFRecord file with its --label-key feature, or a fixed set of
+    generated waves labelled by wave shape -- is loaded onto the device once; every step draws its pairs there ("same
+    class" for half of them) and the steps between two prints are one ``fit`` call."""
+    import importlib
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    if a.tfrecord:
+        data = D.DeviceDataset.from_tfrecord(a.tfrecord, a.audio_max_length, label_key=a.label_key,
+                                             num_classes=a.num_classes)
+    else:
+        waves = [generate_random_wave(a.num_samples, rng=rng) for _ in range(a.device_clips)]
+        data = D.DeviceDataset(np.array([w for w, _ in waves], dtype=np.float32),
+                               np.array([int(np.argmax(y)) for _, y in waves]), 4)
+    sampler = data.pair_sampler(a.batch_size, a.num_samples, seed=0)
+    sampler.seek(a.start)
+    print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)
+    loss, step = None, a.start
+    while step < a.steps:
+        n = min(a.print_steps, a.steps - step)
+        losses, distance = network.fit(sampler, n)
+        step += n
+        loss = losses[-1]
+        print(step - 1, loss, distance[-1], sampler.y.cpu().numpy(), flush=True)
+        network.save(None, a.logdir, step - 1, force=False)
+    if loss is not None:
+        network.save(None, a.logdir, step - 1, force=True)
+    return loss
 
 
 if __name__ == "__main__":

@@ -3,6 +3,7 @@
 teacher, draw logistic noise, ``train_fast``; same model calls, no TensorFlow session, no plotting.
 
   python examples/student.py --teacher runs/teacher --student runs/student --steps 200
+  python examples/student.py --teacher runs/teacher --student runs/student --steps 200 --device-data
 """
 import argparse
 import os
@@ -31,6 +32,9 @@ def main(argv=None):
     p.add_argument("--print-steps", type=int, default=50)
     p.add_argument("--layers", type=int, default=30)
     p.add_argument("--flows", type=int, default=4)
+    p.add_argument("--device-data", action="store_true",
+                   help="keep the clips on the device; draw clips and noise and run the teacher's encoder inside the step (model.fit)")
+    p.add_argument("--device-clips", type=int, default=256, help="--device-data without --tfrecord: synthetic waves to hold")
     a = p.parse_args(argv)
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     data = NsynthDataReader(a.tfrecord, a.batch_size, a.num_samples, audio_max_length=a.audio_max_length) if a.tfrecord else None
@@ -40,6 +44,8 @@ def main(argv=None):
                               gamma=1.0, learning_rate=1e-4)                              # student.py:82
     sess = None                                                                           # accepted and ignored
     student.load(sess, a.student)
+    if a.device_data:
+        return fit_loop(a, student)
     rng = np.random.default_rng(0)
     loss = None
     for step in range(a.steps):
@@ -52,6 +58,31 @@ def main(argv=None):
             print("Step: {:6d} | Entropy: {} | Power Loss: {:.4f} | Total Loss: {:.4f}".format(step, entropy, power_loss, loss), flush=True)
         student.save(sess, a.student, step, force=False)
     student.save(sess, a.student, a.steps - 1, force=True)
+    return float(loss)
+
+
+def fit_loop(a, student):
+    """--device-data: the TFRecord file (or a block of synthetic waves) is loaded onto the device once; the steps between
+    two prints are one ``fit`` call -- graph replays that draw the clips and the noise, encode with the frozen teacher and
+    log the losses on the device; the host waits once per call."""
+    import importlib
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    if a.tfrecord:
+        data = D.DeviceDataset.from_tfrecord(a.tfrecord, a.audio_max_length, label_key=None)
+    else:
+        data = D.DeviceDataset(generate_wave_batch(a.device_clips, a.num_samples)[0].astype(np.float32))
+    sampler = data.distill_sampler(a.batch_size, a.num_samples, seed=0)
+    print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)
+    loss, step = None, 0
+    while step < a.steps:
+        n = min(a.print_steps, a.steps - step)
+        losses, power = student.fit(sampler, n)
+        step += n
+        loss = losses[-1]
+        entropy = sampler.entropies(sampler.step - 1, 1)[0]
+        print("Step: {:6d} | Entropy: {} | Power Loss: {:.4f} | Total Loss: {:.4f}".format(step - 1, entropy, power[-1], loss), flush=True)
+        student.save(None, a.student, step - 1, force=False)
+    student.save(None, a.student, a.steps - 1, force=True)
     return float(loss)
 
 

@@ -1613,6 +1613,66 @@ int srwn_batch_draw(const float* clips, const int32_t* labels, int32_t num_clips
                     void* stream);
 int srwn_step_log(const float* loss, float* log, int32_t capacity, int64_t* state, void* stream);
 
+/* ---- device-resident training for the student and the twin towers (since srwn_version() 123; csrc/srwn_draw.hip): the
+ * launches a DistillSampler and a PairSampler (sr-wavenet_amd/dataset.py) put around a training step, inside its hipGraph.
+ * The rules of the block above hold: `state` is int64 [2] = {seed, step} in device memory, the draws only read it and the
+ * log launches tick `step`; rows are positions p = (step * world + rank) * B + b of the sample sequence, their records and
+ * crop offsets are srwn_batch_draw's (dataset.draw_plan); every argument is checked before any launch.
+ * srwn_distill_draw is the student step's first launch.
+ *   audio0   [B][T] fp32: the cropped rows;  audio1, audio2 the same rows again, or NULL (the teacher encoder's input,
+ *            StudentEngine.truth and the teacher decoder's audio)
+ *   noise    [B][T] fp32 or NULL: temperature * (log u - log(1 - u)), u = (k + 1/2) / 2^23, with the 23-bit values k of
+ *            dataset.noise_plan: row b has the seed s_b = mix64((seed ^ NOISE_SALT) + GOLDEN * (p + 1)) and entry j the
+ *            bits mix64(s_b + GOLDEN * (j + 1)) >> 41 -- what srwn_logistic_noise draws for seed[b] = s_b at clock 0, by
+ *            that kernel's evaluation and its rule for temperature 0
+ *   cond_tables  a DEVICE array of num_tables (0..64) addresses of matrices of cond_dtype (SRWN_F32 / SRWN_BF16) with
+ *            cond_ld elements per row (the teacher decoder's cond_in and every flow's): in each, rows [b * cond_rows,
+ *            (b + 1) * cond_rows) get, in columns [cond_col0, cond_col0 + num_classes), the one-hot row of record b's label
+ *            by srwn_batch_draw's tf.one_hot rule; other columns are not touched.  num_tables 0: no one-hot rows.
+ *   indices  [B] int32: the records drawn
+ * Errors: B = 0 or T = 0 is done (0); a null clips, state, audio0 or indices, or one-hot rows without labels or tables
+ * (-3); num_clips or clip_len < 1, T > clip_len, B > 65535, rank outside [0, world), a crop other than 0 / 1, num_tables
+ * outside [0, 64], one-hot columns that do not fit cond_ld, a buffer that is not 4-byte aligned (-2); a one-hot dtype other
+ * than SRWN_F32 / SRWN_BF16 (-1).
+ * srwn_cond_scatter writes enc [rows][latent] fp32 (EncoderStack.forward's encoding) into columns [0, latent) of the same
+ * num_tables matrices, converted to cond_dtype (bf16: round to nearest even) -- the bits of cond_in[:, :latent].copy_(enc);
+ * columns >= latent are not touched.  One launch.  Errors: nothing to do is done (0); a null pointer (-3); negative sizes,
+ * cond_ld < latent, num_tables > 64 (-2); the dtype (-1).
+ * srwn_distill_log is the student step's last launch (one thread): in double and in this order, every operation rounded
+ * once, entropy = logs[0] + 2 n and loss = (beta * ce[0] - alpha * entropy + power[0]) / loss_div -- the arithmetic of
+ * StudentEngine.losses() -- then loss_log[s] = (float)loss, power_log[s] = power[0], entropy_log[s] = (float)entropy at
+ * s = step % capacity, then step += 1.  Errors: a null pointer (-3); capacity < 1, n < 0, loss_div 0 or NaN (-2).
+ * srwn_pair_draw is the twins' first launch (dataset.pair_plan).  The left clip of pair b is the draw's record and offset
+ * of position p.  With c its label, m the records of class c, q its place inside the class block of `order`: the coin
+ * same = (h1 >> 32) < same_threshold (= floor(p_same * 2^32)), overridden where only one outcome exists (m = 1: different;
+ * num_clips = m: same; num_clips = 1: the record itself); same: k = ((h2 >> 32) (m - 1)) >> 32, k += (k >= q), right =
+ * order[class_start[c] + k]; different: k = ((h2 >> 32) (num_clips - m)) >> 32, right = order[k < class_start[c] ? k : k +
+ * m]; h1, h2 and the right crop offset's h3 = mix64((seed ^ salt) + GOLDEN * (p + 1)) with the three PAIR salts.
+ *   order [num_clips] int32: the stable argsort of the labels;  place [num_clips]: its inverse;  class_start
+ *   [num_classes + 1]: where each class begins in `order`.  Every label must lie in [0, num_classes).
+ *   audio [2P][T] fp32: the left clips in rows [0, P), the right ones in [P, 2P);  y [P] fp32: 1 where the labels agree,
+ *   else 0 (model.py:747-749);  left, right [P] int32 and y_log [P] fp32: the draw, for the sampler.
+ * Errors: P = 0 or T = 0 is done (0); a null pointer (-3); the draw's shape errors, P > 32767, num_classes < 1,
+ * same_threshold outside [0, 2^32] (-2).
+ * srwn_pair_log is the twins' last launch (one workgroup): loss_log[s] = loss[0] and dist_log[s][0..P) = dist[0..P) at
+ * s = step % capacity, then step += 1.  Errors: a null pointer (-3); capacity or P < 1 (-2). */
+int srwn_distill_draw(const float* clips, const int32_t* labels, int32_t num_clips, int64_t clip_len, const int64_t* state,
+                      int32_t B, int32_t T, int32_t shuffle, int32_t crop, int32_t rank, int32_t world, float* audio0,
+                      float* audio1, float* audio2, float* noise, float temperature, const int64_t* cond_tables,
+                      int32_t num_tables, int64_t cond_ld, int32_t cond_rows, int32_t cond_col0, int32_t num_classes,
+                      int32_t cond_dtype, int32_t* indices, void* stream);
+int srwn_cond_scatter(const float* enc, int64_t rows, int32_t latent, const int64_t* cond_tables, int32_t num_tables,
+                      int64_t cond_ld, int32_t cond_dtype, void* stream);
+int srwn_distill_log(const float* ce, const float* power, const float* logs, double alpha, double beta, int64_t n,
+                     double loss_div, float* loss_log, float* power_log, float* entropy_log, int32_t capacity,
+                     int64_t* state, void* stream);
+int srwn_pair_draw(const float* clips, const int32_t* labels, const int32_t* order, const int32_t* place,
+                   const int32_t* class_start, int32_t num_classes, int32_t num_clips, int64_t clip_len, const int64_t* state,
+                   int32_t P, int32_t T, int64_t same_threshold, int32_t shuffle, int32_t crop, int32_t rank, int32_t world,
+                   float* audio, float* y, int32_t* left, int32_t* right, float* y_log, void* stream);
+int srwn_pair_log(const float* loss, const float* dist, int32_t P, float* loss_log, float* dist_log, int32_t capacity,
+                  int64_t* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ F32, BF16 = 0, 1
 PRO_NONE, PRO_GATE = 0, 1
 EPI_NONE, EPI_RELU, EPI_MASK, EPI_F32 = 0, 1, 2, 4
 
-_p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_p, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 
 class SrwnGenSlot(C.Structure):
@@ -298,6 +298,14 @@ SIGNATURES["srwn_flow_invert"] = (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, 
 SIGNATURES["srwn_batch_draw"] = (C.c_int, [_p, _p, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p,
                                            _i64, _i32, _i32, _i32, _i32, _p, _p])
 SIGNATURES["srwn_step_log"] = (C.c_int, [_p, _p, _i32, _p, _p])
+# device-resident training for the student and the twins (srwn_version() 123): a DistillSampler's and a PairSampler's launches
+SIGNATURES["srwn_distill_draw"] = (C.c_int, [_p, _p, _i32, _i64, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _f32,
+                                             _p, _i32, _i64, _i32, _i32, _i32, _i32, _p, _p])
+SIGNATURES["srwn_cond_scatter"] = (C.c_int, [_p, _i64, _i32, _p, _i32, _i64, _i32, _p])
+SIGNATURES["srwn_distill_log"] = (C.c_int, [_p, _p, _p, _f64, _f64, _i64, _f64, _p, _p, _p, _i32, _p, _p])
+SIGNATURES["srwn_pair_draw"] = (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
+                                          _p, _p, _p, _p, _p, _p])
+SIGNATURES["srwn_pair_log"] = (C.c_int, [_p, _p, _i32, _p, _p, _i32, _p, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

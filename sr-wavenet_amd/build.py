@@ -19,7 +19,7 @@ PYB_SRC = os.path.join(CSRC, "srwn_pybind.cpp")   # generated from _lib.SIGNATUR
 PYB_NAME = "_srwn_pyb"
 IO_SOURCES = ["srwn_tfrecord.cpp"]
 CXX = os.environ.get("CXX", "g++")
-SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_ncstream.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip", "srwn_wngate.hip", "srwn_stream.hip", "srwn_recog.hip", "srwn_score.hip", "srwn_embed.hip", "srwn_flow_inv.hip", "srwn_data.hip"]
+SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_ncstream.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip", "srwn_wngate.hip", "srwn_stream.hip", "srwn_recog.hip", "srwn_score.hip", "srwn_embed.hip", "srwn_flow_inv.hip", "srwn_data.hip", "srwn_draw.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed", "-ffp-contract=on"]
 # Kernels that fetch REGISTER operands with loads the compiler does not see (inline asm, hand-counted waits) must not
@@ -204,7 +204,7 @@ def pybind_source() -> str:
     import ctypes as C
     L = _signatures()
     kinds = {C.c_void_p: ("std::uintptr_t", "P{%s}"), C.c_int32: ("int32_t", "%s"), C.c_int64: ("int64_t", "%s"),
-             C.c_float: ("float", "%s"), C.c_uint64: ("uint64_t", "%s"), C.c_int: ("int", "%s")}
+             C.c_float: ("float", "%s"), C.c_double: ("double", "%s"), C.c_uint64: ("uint64_t", "%s"), C.c_int: ("int", "%s")}
     out = ["// GENERATED by sr-wavenet_amd/build.py (pybind_source) from _lib.SIGNATURES -- do not edit.",
            "// The thin pybind11 module over the C-ABI of include/srwn.h: pointers as integers, scalars as declared.",
            "#include <pybind11/pybind11.h>", "#include <cstdint>", '#include "../../include/srwn.h"', "namespace py = pybind11;",

@@ -13,6 +13,11 @@ boundaries (nsynth.py:39-45), and every epoch is a fresh keyed permutation of th
 buffer of 10 000 records is NOT reproduced: TensorFlow's shuffle order is not reproducible either (see nsynth.py's
 docstring), and a permutation of the whole set is the stronger shuffle.
 
+Two more samplers feed the models whose step needs more than clips (csrc/srwn_draw.hip): a ``DistillSampler`` draws the
+student's clips, its logistic noise (``noise_plan``) and the labels' one-hot rows into every conditioning input, and logs
+loss, power loss and entropy; a ``PairSampler`` draws "same class" / "different class" pairs of a labelled set
+(``pair_plan``) for the twin towers and logs the loss and the pairs' distances.
+
 Storage is fp32 only: int16 or bf16 clip storage is out of scope.
 """
 from __future__ import annotations
@@ -24,6 +29,10 @@ import numpy as np
 _MASK = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 _CROP_SALT = 0x63726F706F666673
+NOISE_SALT = 0x6E6F697365726F77        # the rows' noise seeds
+PAIR_SALT = 0x70616972636F696E         # the pairs' coins ...
+PAIR_PICK_SALT = 0x706169727069636B    # ... their right records
+PAIR_CROP_SALT = 0x7061697263726F70    # ... and the right clips' crop offsets
 _ROUNDS = 4
 CROPS = {"head": 0, "random": 1}
 MAX_BATCH = 65535          # rows of one draw (the launch's second grid dimension)
@@ -77,6 +86,109 @@ def draw_plan(seed: int, step: int, batch_size: int, n: int, clip_len: int, num_
             h = _mix64((seed ^ _CROP_SALT) + _GOLDEN * (p + 1))
             off[b] = ((h >> 32) * (clip_len - num_samples + 1)) >> 32
     return idx, off
+
+
+def noise_rows(seed: int, step: int, batch_size: int, rank: int = 0, world: int = 1) -> np.ndarray:
+    """The seeds s_b of the step's noise rows, uint64 [B]: ``_mix64((seed ^ NOISE_SALT) + _GOLDEN * (p + 1))`` at the
+    row's position p = (step * world + rank) * B + b."""
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d of %d" % (rank, world))
+    seed &= _MASK
+    return np.array([_mix64((seed ^ NOISE_SALT) + _GOLDEN * ((step * world + rank) * batch_size + b + 1))
+                     for b in range(batch_size)], dtype=np.uint64)
+
+
+def noise_plan(seed: int, step: int, batch_size: int, num_samples: int, rank: int = 0, world: int = 1) -> np.ndarray:
+    """The 23-bit values k of the step's logistic noise, uint32 [B, T]: ``k[b, j] = _mix64(s_b + _GOLDEN * (j + 1)) >> 41``
+    with the row seeds of ``noise_rows`` -- what ``srwn_logistic_noise`` draws for ``seed[b] = s_b`` at clock 0.  The
+    noise is ``temperature * (log u - log(1 - u))`` at ``u = (k + 1/2) / 2^23``, by that kernel's own evaluation
+    (``srwn_logistic_from_bits``)."""
+    if batch_size < 1 or num_samples < 1:
+        raise ValueError("noise_plan: batch_size %d, num_samples %d" % (batch_size, num_samples))
+    rows = noise_rows(seed, step, batch_size, rank, world)
+    # splitmix64 over whole rows in uint64 arithmetic (wraps as the masks of _mix64 do)
+    j = np.arange(1, num_samples + 1, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        x = rows[:, None] + np.uint64(_GOLDEN) * j[None, :]
+        x ^= x >> np.uint64(30); x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27); x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return (x >> np.uint64(41)).astype(np.uint32)
+
+
+def class_index(labels, num_classes: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(order [N] int32, place [N] int32, start [num_classes + 1] int32)``: the stable argsort of the labels, its inverse
+    and where each class begins in it.  Every label must lie in [0, num_classes)."""
+    lab = np.asarray(labels).astype(np.int64).reshape(-1)
+    if int(num_classes) < 1:
+        raise ValueError("num_classes %d: at least 1" % int(num_classes))
+    if lab.size < 1:
+        raise ValueError("the dataset is empty")
+    if lab.min() < 0 or lab.max() >= int(num_classes):
+        raise ValueError("pairs need every label inside [0, %d); got labels from %d to %d"
+                         % (int(num_classes), int(lab.min()), int(lab.max())))
+    order = np.argsort(lab, kind="stable").astype(np.int32)
+    place = np.empty_like(order)
+    place[order] = np.arange(lab.size, dtype=np.int32)
+    start = np.concatenate([[0], np.cumsum(np.bincount(lab, minlength=int(num_classes)))]).astype(np.int32)
+    return order, place, start
+
+
+def same_threshold(p_same: float) -> int:
+    """floor(p_same * 2^32): the coin of a pair says "same" where its 32 bits lie below it."""
+    if not 0.0 <= float(p_same) <= 1.0:
+        raise ValueError("p_same %r: a probability" % (p_same,))
+    return int(float(p_same) * 4294967296.0)
+
+
+def pair_plan(seed: int, step: int, pairs: int, labels, num_classes: int, clip_len: int, num_samples: int,
+              p_same: float = 0.5, shuffle: bool = True, crop: str = "head", rank: int = 0, world: int = 1):
+    """The pairs of ``step``: ``(left [P] int32, right [P] int32, off_left [P] int64, off_right [P] int64, y [P]
+    float32)``.  The left side is ``draw_plan``'s record and offset of position p = (step * world + rank) * P + b.  With c
+    its label, m the records of class c, N all records and q the left record's place inside its class block of the stable
+    argsort ``order`` of the labels: the coin ``same = (h1 >> 32) < floor(p_same * 2^32)`` is overridden where only one
+    outcome exists (m == 1: different; N == m: same; N == 1: the record with itself).  Same: ``k = ((h2 >> 32) * (m - 1))
+    >> 32``, ``k += (k >= q)`` (never the clip itself), right = ``order[start[c] + k]``.  Different: ``k = ((h2 >> 32) *
+    (N - m)) >> 32``, right = ``order[k if k < start[c] else k + m]``.  h1, h2 and (crop "random") the right offset's h3
+    are ``_mix64((seed ^ salt) + _GOLDEN * (p + 1))`` with PAIR_SALT, PAIR_PICK_SALT and PAIR_CROP_SALT; the offset
+    follows ``draw_plan``'s formula.  y = 1.0 where the labels agree, else 0.0 (the reference's convention,
+    model.py:747-749)."""
+    lab = np.asarray(labels).astype(np.int64).reshape(-1)
+    order, place, start = class_index(lab, num_classes)
+    n = int(lab.size)
+    left, off_left = draw_plan(seed, step, pairs, n, clip_len, num_samples, shuffle, crop, rank, world)
+    thr = same_threshold(p_same)
+    seed &= _MASK
+    right = np.empty(pairs, np.int32)
+    off_right = np.zeros(pairs, np.int64)
+    for b in range(pairs):
+        p = (step * world + rank) * pairs + b
+        rec = int(left[b])
+        c = int(lab[rec])
+        s0 = int(start[c])
+        m = int(start[c + 1]) - s0
+        q = int(place[rec]) - s0
+        h1 = _mix64((seed ^ PAIR_SALT) + _GOLDEN * (p + 1))
+        h2 = _mix64((seed ^ PAIR_PICK_SALT) + _GOLDEN * (p + 1)) >> 32
+        same = (h1 >> 32) < thr
+        if m == 1:
+            same = False
+        if n == m:
+            same = True
+        if n == 1:
+            right[b] = rec
+        elif same:
+            k = (h2 * (m - 1)) >> 32
+            k += k >= q
+            right[b] = order[s0 + k]
+        else:
+            k = (h2 * (n - m)) >> 32
+            right[b] = order[k if k < s0 else k + m]
+        if CROPS[crop]:
+            h3 = _mix64((seed ^ PAIR_CROP_SALT) + _GOLDEN * (p + 1))
+            off_right[b] = ((h3 >> 32) * (clip_len - num_samples + 1)) >> 32
+    y = (lab[left] == lab[right]).astype(np.float32)
+    return left, right, off_left, off_right, y
 
 
 def _check_draw(batch_size, n, clip_len, num_samples, crop, rank, world):
@@ -168,6 +280,32 @@ class DeviceDataset(object):
     def sampler(self, batch_size, num_samples, seed=0, shuffle=True, crop="head", rank=0, world=1, log_capacity=1024):
         return BatchSampler(self, batch_size, num_samples, seed, shuffle, crop, rank, world, log_capacity)
 
+    def distill_sampler(self, batch_size, num_samples, seed=0, shuffle=True, crop="head", temperature=1.0, rank=0, world=1,
+                        log_capacity=1024):
+        """The draws of a student's distillation run (``ParallelWaveNet.fit``): clips, logistic noise, one-hot rows."""
+        return DistillSampler(self, batch_size, num_samples, seed, shuffle, crop, temperature, rank, world, log_capacity)
+
+    def pair_sampler(self, pairs, num_samples, seed=0, p_same=0.5, shuffle=True, crop="head", rank=0, world=1,
+                     log_capacity=1024):
+        """The draws of a twin-tower run (``SiameseWaveNet.fit``): `pairs` pairs of clips per step, "same class" with
+        probability `p_same`.  Needs labels, every one inside [0, num_classes)."""
+        return PairSampler(self, pairs, num_samples, seed, p_same, shuffle, crop, rank, world, log_capacity)
+
+    def class_index(self):
+        """``class_index`` of the labels as device tensors (order, place, start), built and uploaded on first use."""
+        if getattr(self, "_class_index", None) is None:
+            import torch
+            self._class_index = tuple(torch.as_tensor(a).to(self.device)
+                                      for a in class_index(self._host_labels(), self.num_classes))
+        return self._class_index
+
+    def _host_labels(self) -> np.ndarray:
+        if self.labels is None:
+            raise ValueError("this dataset holds no labels")
+        if getattr(self, "_labels_host", None) is None:
+            self._labels_host = self.labels.cpu().numpy()
+        return self._labels_host
+
 
 def _is_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
@@ -245,9 +383,183 @@ class BatchSampler(object):
         K.call("srwn_step_log", K._chk(loss, "loss", torch.float32, (1,)), self.log.data_ptr(), self.log_capacity,
                self.state.data_ptr(), K._stream())
 
+    # ---- what ``fit`` asks of a sampler: its log launch for an engine, and the logged steps as arrays --------------------
+    def log_engine(self, eng):
+        self.log_step(eng.loss)
+
+    def results(self, step0: int, count: int):
+        return (self.losses(step0, count),)
+
     def losses(self, step0: int, count: int) -> np.ndarray:
         """The losses of steps [step0, step0 + count) from the ring (count <= log_capacity): the host waits here."""
         if not 0 <= count <= self.log_capacity:
             raise ValueError("the ring holds %d losses, asked for %d" % (self.log_capacity, count))
         ring = self.log.cpu().numpy()
         return ring[(step0 + np.arange(count)) % self.log_capacity].astype(np.float32)
+
+
+class DistillSampler(BatchSampler):
+    """The draws of a student's distillation run.  Beside a ``BatchSampler``'s state it owns the rings of the power loss
+    and the entropy; ``temperature`` scales the noise.  ``draw`` is ``srwn_distill_draw`` (the clips into up to three
+    buffers, the noise, the one-hot rows into every conditioning input), ``scatter`` is ``srwn_cond_scatter`` (the
+    teacher's encoding into the same inputs), ``log_engine`` is ``srwn_distill_log``."""
+
+    def __init__(self, dataset, batch_size, num_samples, seed=0, shuffle=True, crop="head", temperature=1.0, rank=0,
+                 world=1, log_capacity=1024):
+        if not np.isfinite(float(temperature)) or float(temperature) < 0.0:
+            raise ValueError("temperature %r: finite and not negative" % (temperature,))
+        BatchSampler.__init__(self, dataset, batch_size, num_samples, seed, shuffle, crop, rank, world, log_capacity)
+        import torch
+        self.temperature = float(temperature)
+        self.power_log = torch.zeros_like(self.log)
+        self.entropy_log = torch.zeros_like(self.log)
+        self._tables = None      # (the tensors, their addresses on the device)
+
+    def noise_plan(self, step: Optional[int] = None) -> np.ndarray:
+        """``noise_plan`` of `step` (default: the next one) for this sampler."""
+        return noise_plan(self.seed, self.step if step is None else int(step), self.batch_size, self.num_samples,
+                          self.rank, self.world)
+
+    def noise_rows(self, step: Optional[int] = None) -> np.ndarray:
+        return noise_rows(self.seed, self.step if step is None else int(step), self.batch_size, self.rank, self.world)
+
+    def _table_addresses(self, tables):
+        import torch
+        tables = list(tables)
+        if self._tables is None or len(self._tables[0]) != len(tables) or \
+                any(a is not b for a, b in zip(self._tables[0], tables)):
+            t0 = tables[0]
+            for t in tables:
+                if t.ndim != 2 or t.shape != t0.shape or t.dtype != t0.dtype or not t.is_contiguous():
+                    raise NotImplementedError("the conditioning inputs of one step must share shape and dtype: %s %s, %s %s"
+                                              % (tuple(t0.shape), t0.dtype, tuple(t.shape), t.dtype))
+            if len(tables) > 64:
+                raise ValueError("%d conditioning inputs: at most 64" % len(tables))
+            addr = torch.tensor([t.data_ptr() for t in tables], dtype=torch.int64, device=self.dataset.device)
+            self._tables = (tables, addr)
+        return self._tables[1]
+
+    def draw(self, audio, audio2=None, audio3=None, noise=None, tables=None, rows=1, col0=0):
+        """srwn_distill_draw on the current stream: the step's rows into `audio` (and `audio2`, `audio3`: [B, T] fp32), its
+        noise times ``temperature`` into `noise` and, with `tables` (matrices [B * rows, ld] of one dtype), the labels'
+        one-hot rows into columns [col0, col0 + num_classes) of each.  Reads the device step; does not tick it."""
+        import torch
+        from . import kernels as K
+        d, B, T = self.dataset, self.batch_size, self.num_samples
+        pa = K._chk(audio, "audio", torch.float32, (B, T))
+        pa2 = K._opt(audio2, "audio2", torch.float32, (B, T))
+        pa3 = K._opt(audio3, "audio3", torch.float32, (B, T))
+        pn = K._opt(noise, "noise", torch.float32, (B, T))
+        pt, nt, ld, dt = None, 0, 0, 0
+        if tables:
+            if d.labels is None:
+                raise ValueError("this dataset holds no labels")
+            pt, nt = self._table_addresses(tables).data_ptr(), len(tables)
+            t0 = tables[0]
+            if t0.shape[0] != B * int(rows) or int(col0) < 0 or int(col0) + d.num_classes > t0.shape[1]:
+                raise ValueError("tables: shape %s, expected [%d, >= %d]"
+                                 % (tuple(t0.shape), B * int(rows), int(col0) + d.num_classes))
+            ld, dt = int(t0.shape[1]), K.abi_dtype(t0.dtype)
+        K.call("srwn_distill_draw", d.audio.data_ptr(), None if d.labels is None else d.labels.data_ptr(), len(d),
+               d.clip_len, self.state.data_ptr(), B, T, int(self.shuffle), CROPS[self.crop], self.rank, self.world, pa, pa2,
+               pa3, pn, self.temperature, pt, nt, ld, int(rows), int(col0), d.num_classes, dt, self.indices.data_ptr(),
+               K._stream())
+
+    def scatter(self, enc, tables):
+        """srwn_cond_scatter on the current stream: `enc` [rows, latent] fp32 into columns [0, latent) of every table, in
+        the tables' dtype -- the bits of ``table[:, :latent].copy_(enc)``."""
+        import torch
+        from . import kernels as K
+        pe = K._chk(enc, "enc", torch.float32)
+        t0 = tables[0]
+        addr = self._table_addresses(tables)
+        if enc.ndim != 2 or enc.shape[0] != t0.shape[0] or enc.shape[1] > t0.shape[1]:
+            raise ValueError("enc: shape %s against tables %s" % (tuple(enc.shape), tuple(t0.shape)))
+        K.call("srwn_cond_scatter", pe, int(enc.shape[0]), int(enc.shape[1]), addr.data_ptr(), len(tables),
+               int(t0.shape[1]), K.abi_dtype(t0.dtype), K._stream())
+
+    def log_engine(self, eng):
+        """srwn_distill_log on the current stream, for a ``student.StudentEngine``: loss, power loss and entropy of the step
+        into the three rings (``StudentEngine.losses()``'s arithmetic on the device), then the device step ticks."""
+        from . import kernels as K
+        K.call("srwn_distill_log", eng.ce.data_ptr(), eng.power.data_ptr(), eng.logs.data_ptr(), float(eng.alpha),
+               float(eng.beta), int(eng.N), float(eng.loss_div), self.log.data_ptr(), self.power_log.data_ptr(),
+               self.entropy_log.data_ptr(), self.log_capacity, self.state.data_ptr(), K._stream())
+
+    def _ring(self, ring, step0, count):
+        if not 0 <= count <= self.log_capacity:
+            raise ValueError("the ring holds %d steps, asked for %d" % (self.log_capacity, count))
+        return ring.cpu().numpy()[(step0 + np.arange(count)) % self.log_capacity].astype(np.float32)
+
+    def power_losses(self, step0: int, count: int) -> np.ndarray:
+        return self._ring(self.power_log, step0, count)
+
+    def entropies(self, step0: int, count: int) -> np.ndarray:
+        return self._ring(self.entropy_log, step0, count)
+
+    def results(self, step0: int, count: int):
+        return self.losses(step0, count), self.power_losses(step0, count)
+
+
+class PairSampler(BatchSampler):
+    """The draws of a twin-tower run on a labelled ``DeviceDataset``: ``pairs`` pairs per step, "same class" with
+    probability ``p_same`` (``pair_plan``).  ``batch_size`` is the number of pairs.  Beside the loss ring it owns the
+    ``[log_capacity, pairs]`` distance ring and the left indices (``indices``), right indices and y of the last draw."""
+
+    def __init__(self, dataset, pairs, num_samples, seed=0, p_same=0.5, shuffle=True, crop="head", rank=0, world=1,
+                 log_capacity=1024):
+        if dataset.labels is None:
+            raise ValueError("pair_sampler: the dataset holds no labels; pairs are drawn by class")
+        self.same_threshold = same_threshold(p_same)
+        if int(pairs) > 32767:
+            raise ValueError("pairs %d: at most 32767" % int(pairs))
+        _check_draw(int(pairs), len(dataset), dataset.clip_len, int(num_samples), crop, int(rank), int(world))
+        if int(log_capacity) < 1:
+            raise ValueError("log_capacity %d: at least 1" % int(log_capacity))
+        self._index = dataset.class_index()          # (refuses labels outside the classes)
+        BatchSampler.__init__(self, dataset, pairs, num_samples, seed, shuffle, crop, rank, world, log_capacity)
+        import torch
+        dev = dataset.device
+        self.pairs, self.p_same = int(pairs), float(p_same)
+        self.right = torch.zeros(self.pairs, dtype=torch.int32, device=dev)
+        self.y = torch.zeros(self.pairs, dtype=torch.float32, device=dev)
+        self.dist_log = torch.zeros((self.log_capacity, self.pairs), dtype=torch.float32, device=dev)
+
+    def pair_plan(self, step: Optional[int] = None):
+        """``pair_plan`` of `step` (default: the next one) for this sampler."""
+        d = self.dataset
+        return pair_plan(self.seed, self.step if step is None else int(step), self.pairs, d._host_labels(), d.num_classes,
+                         d.clip_len, self.num_samples, self.p_same, self.shuffle, self.crop, self.rank, self.world)
+
+    def draw(self, audio, labels):
+        """srwn_pair_draw on the current stream: the left clips into rows [0, P) and the right ones into rows [P, 2P) of
+        `audio` ([2P, T] fp32), y into `labels` ([P] fp32); the draw's indices and y into ``indices``, ``right``, ``y``."""
+        import torch
+        from . import kernels as K
+        d, P, T = self.dataset, self.pairs, self.num_samples
+        order, place, start = self._index
+        K.call("srwn_pair_draw", d.audio.data_ptr(), d.labels.data_ptr(), order.data_ptr(), place.data_ptr(),
+               start.data_ptr(), d.num_classes, len(d), d.clip_len, self.state.data_ptr(), P, T, self.same_threshold,
+               int(self.shuffle), CROPS[self.crop], self.rank, self.world, K._chk(audio, "audio", torch.float32, (2 * P, T)),
+               K._chk(labels, "labels", torch.float32, (P,)), self.indices.data_ptr(), self.right.data_ptr(),
+               self.y.data_ptr(), K._stream())
+
+    def log_pairs(self, loss, dist):
+        """srwn_pair_log on the current stream: the loss and the P distances into their rings, then the step ticks."""
+        import torch
+        from . import kernels as K
+        K.call("srwn_pair_log", K._chk(loss, "loss", torch.float32, (1,)), K._chk(dist, "dist", torch.float32, (self.pairs,)),
+               self.pairs, self.log.data_ptr(), self.dist_log.data_ptr(), self.log_capacity, self.state.data_ptr(),
+               K._stream())
+
+    def log_engine(self, eng):
+        self.log_pairs(eng.loss, eng.dist)
+
+    def distances(self, step0: int, count: int) -> np.ndarray:
+        """The distances [count, P] of steps [step0, step0 + count) from the ring (count <= log_capacity)."""
+        if not 0 <= count <= self.log_capacity:
+            raise ValueError("the ring holds %d steps, asked for %d" % (self.log_capacity, count))
+        return self.dist_log.cpu().numpy()[(step0 + np.arange(count)) % self.log_capacity].astype(np.float32)
+
+    def results(self, step0: int, count: int):
+        return self.losses(step0, count), self.distances(step0, count)

@@ -52,28 +52,32 @@ def _train_step(eng):
     return out
 
 
-def _fit_part(eng, sampler, dest, part):
+def _fit_part(eng, sampler, dest, part, between=None):
     """The launches of one ``fit`` step on either side of the gradient all-reduce: 0 = {draw, forward, backward},
-    1 = {Adam, re-pack, log}.  Between the sampler's two launches this is ``train_step``'s own sequence."""
+    1 = {Adam, re-pack, log}.  Between the sampler's two launches this is ``train_step``'s own sequence; `between`
+    (the student: the teacher encoder's forward pass and the scatter of its encoding) runs right behind the draw."""
     if part == 0:
         sampler.draw(**dest)
-        if hasattr(eng, "dec"):          # the auto-encoder pair (encoder.AutoEncoderEngine)
-            eng.forward()
-        else:
+        if between is not None:
+            between()
+        if isinstance(eng, WaveNetEngine):
             eng.forward(defer_loss=True)
+        else:                            # the auto-encoder pair (encoder.AutoEncoderEngine), the student (StudentEngine)
+            eng.forward()
         eng.backward()
     else:
         eng.optimizer_step()
-        sampler.log_step(eng.loss)
+        sampler.log_engine(eng)
 
 
-def _fit(eng, sampler, steps, dest):
-    """``steps`` training steps of an engine fed by a ``dataset.BatchSampler``: every batch is drawn on the device by the
-    step's first launch (``dest``: where ``BatchSampler.draw`` writes what ``set_inputs`` would) and the loss is logged
-    by its last, so a run of steps needs no upload and no host wait -- the host waits once per ``log_capacity`` steps to
-    drain the loss ring.  Capture follows ``_train_step``'s rule: two eager steps of this (engine, sampler) pair, then
-    hipGraphs of its own (the graphs of ``train(x)`` are not touched); SRWN_MODEL_GRAPHS=0 keeps eager launches.
-    Returns every step's loss, float32 [steps]."""
+def _fit(eng, sampler, steps, dest, between=None):
+    """``steps`` training steps of an engine fed by a sampler of dataset.py: every batch is drawn on the device by the
+    step's first launch (``dest``: where the sampler's ``draw`` writes what ``set_inputs`` would) and the step is logged
+    by its last (the sampler's ``log_engine``), so a run of steps needs no upload and no host wait -- the host waits once
+    per ``log_capacity`` steps to drain the rings.  Capture follows ``_train_step``'s rule: two eager steps of this
+    (engine, sampler) pair, then hipGraphs of its own (the graphs of ``train(x)`` are not touched); SRWN_MODEL_GRAPHS=0
+    keeps eager launches.  Returns what the sampler's ``results`` gives for every step, one array per logged quantity:
+    the loss, float32 [steps], first."""
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps %d" % steps)
@@ -81,7 +85,7 @@ def _fit(eng, sampler, steps, dest):
     if st is None or st["sampler"] is not sampler:
         st = eng._fit_state = {"sampler": sampler, "eager": 0, "graphs": None, "failed": False}
     world = eng.dec.world if hasattr(eng, "dec") else eng.world
-    out = np.empty(steps, np.float32)
+    pieces = []
     done = 0
     while done < steps:
         n = min(steps - done, sampler.log_capacity)
@@ -93,23 +97,25 @@ def _fit(eng, sampler, steps, dest):
                     eng.allreduce_grads()
                     st["graphs"][1].replay()
             else:
-                _fit_part(eng, sampler, dest, 0)
+                _fit_part(eng, sampler, dest, 0, between)
                 eng.allreduce_grads()
-                _fit_part(eng, sampler, dest, 1)
+                _fit_part(eng, sampler, dest, 1, between)
                 st["eager"] += 1
                 if st["eager"] >= 2 and os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0" and not st["failed"]:
                     try:
-                        st["graphs"] = _fit_capture(eng, sampler, dest, world)
+                        st["graphs"] = _fit_capture(eng, sampler, dest, world, between)
                     except Exception as e:   # keep training with eager launches, say why once
                         st["failed"] = True
                         print("hipGraph capture failed (%s); continuing with eager launches" % e)
             sampler.step += 1
-        out[done:done + n] = sampler.losses(step0, n)          # the host waits here
+        pieces.append(sampler.results(step0, n))               # the host waits here
         done += n
-    return out
+    if not pieces:
+        pieces.append(sampler.results(sampler.step, 0))
+    return tuple(np.concatenate([p[i] for p in pieces], axis=0) for i in range(len(pieces[0])))
 
 
-def _fit_capture(eng, sampler, dest, world):
+def _fit_capture(eng, sampler, dest, world, between=None):
     """The ``fit`` step as one hipGraph, or with several ranks as two with the all-reduce left between them (see
     ``WaveNetEngine.capture_graphs``).  Capturing launches nothing: the device step does not tick."""
     import gc
@@ -118,15 +124,15 @@ def _fit_capture(eng, sampler, dest, world):
     g0 = torch.cuda.CUDAGraph()
     if world == 1 and os.environ.get("SRWN_FORCE_DIST") != "1":
         with torch.cuda.graph(g0):
-            _fit_part(eng, sampler, dest, 0)
-            _fit_part(eng, sampler, dest, 1)
+            _fit_part(eng, sampler, dest, 0, between)
+            _fit_part(eng, sampler, dest, 1, between)
         graphs = [g0]
     else:
         with torch.cuda.graph(g0):
-            _fit_part(eng, sampler, dest, 0)
+            _fit_part(eng, sampler, dest, 0, between)
         g1 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1, pool=g0.pool()):
-            _fit_part(eng, sampler, dest, 1)
+            _fit_part(eng, sampler, dest, 1, between)
         graphs = [g0, g1]
     torch.cuda.synchronize()
     return graphs
@@ -322,7 +328,7 @@ class WaveNet(_EngineOwner):
                              % (sampler.num_samples, self.input_size))
         _fit_labels(sampler, self.output_size, "WaveNet", "targets")
         eng = self._engine(sampler.batch_size, sampler.num_samples)
-        return _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels))
+        return _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels))[0]
 
     def predict(self, inputs):
         eng = self._stage(inputs)
@@ -792,7 +798,7 @@ class WaveNetTeacher(_EngineOwner):
         dest = dict(audio=eng.audio)
         if self.head == "softmax":
             dest.update(codes=eng.targets, quantization_channels=self.quantization_channels)
-        return _fit(eng, sampler, steps, dest)
+        return _fit(eng, sampler, steps, dest)[0]
 
     def get_logits(self, inputs, encoding=None, conditions=None):
         eng = self._stage(inputs, encoding, conditions)
@@ -1226,7 +1232,7 @@ class WaveNetAutoEncoder(object):
         dest = dict(audio=eng.enc.x, audio2=d.audio)
         if self.condition_size > 0:
             dest.update(onehot=d.cond_in, onehot_rows=d.frames, onehot_col0=self.latent_channels)
-        return _fit(eng, sampler, steps, dest)
+        return _fit(eng, sampler, steps, dest)[0]
 
     def encode(self, inputs, conditions=None):
         eng = self._stage(inputs, conditions)
@@ -2001,8 +2007,31 @@ class ParallelWaveNet(object):
         return (logs + 2.0 * eng.T).double().cpu().numpy()
 
     def fit(self, sampler, steps):
-        raise NotImplementedError("ParallelWaveNet.fit: a student step needs noise and teacher passes beside the clips; "
-                                  "feed it with train(sess, inputs, truth, encoding, conditions)")
+        """``steps`` distillation steps (``train_fast``'s) on batches a ``dataset.DistillSampler`` draws on the device:
+        clips, logistic noise and -- with condition_size > 0 -- the labels' one-hot rows; the frozen teacher's encoder
+        runs inside the step and its encoding goes straight into the conditioning inputs.  The teacher must be a
+        ``WaveNetAutoEncoder`` (object or directory).  Returns (loss [steps], power_loss [steps]), float32; the entropies
+        are in the sampler's ring (``sampler.entropies``).  See ``_fit``."""
+        from .dataset import DistillSampler
+        if not isinstance(sampler, DistillSampler):
+            raise NotImplementedError("ParallelWaveNet.fit: a student step needs noise and teacher passes beside the clips; "
+                                      "feed it with train(sess, inputs, truth, encoding, conditions)")
+        if self._teacher is not None and not isinstance(self._teacher, WaveNetAutoEncoder):
+            raise NotImplementedError("ParallelWaveNet.fit runs the teacher's encoder inside the step: build the student "
+                                      "on a WaveNetAutoEncoder teacher (a decoder-only teacher has no encoder)")
+        if self.condition_size > 0:
+            _fit_labels(sampler, self.condition_size, "ParallelWaveNet", "conditions")
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        enc, tch = self._teacher._engine(eng.B, eng.T).enc, eng.teacher
+        tables = [tch.cond_in] + [f.cond_in for f in eng.flows]
+        dest = dict(audio=enc.x, audio2=eng.truth, audio3=tch.audio, noise=eng.noise)
+        if self.condition_size > 0:
+            dest.update(tables=tables, rows=tch.frames, col0=self.latent_channels)
+
+        def between():      # the teacher's encoding of the clips, into the latent columns of every conditioning input
+            enc.forward()
+            sampler.scatter(enc.enc, tables)
+        return _fit(eng, sampler, steps, dest, between)
 
     def train_fast(self, sess, inputs, truth, encoding, conditions=None):
         """One distillation step (model.py:634-642): returns (loss, power_loss)."""
@@ -2622,8 +2651,17 @@ class SiameseWaveNet(_EngineOwner):
         return super().save(logdir, global_step, force, fmt)
 
     def fit(self, sampler, steps):
-        raise NotImplementedError("SiameseWaveNet.fit: a step needs pairs of clips and their labels; feed it with "
-                                  "train(sess, inputs_left, inputs_right, labels)")
+        """``steps`` training steps (``train``'s) on the pairs a ``dataset.PairSampler`` draws on the device from a
+        labelled set of recordings.  Returns (loss [steps], distance [steps, P]), float32.  See ``_fit``."""
+        from .dataset import PairSampler
+        if not isinstance(sampler, PairSampler):
+            raise NotImplementedError("SiameseWaveNet.fit: a step needs pairs of clips and their labels; feed it with "
+                                      "train(sess, inputs_left, inputs_right, labels)")
+        if sampler.num_samples != self.input_size:
+            raise ValueError("SiameseWaveNet.fit: the sampler draws %d samples, the model was built for input_size=%d"
+                             % (sampler.num_samples, self.input_size))
+        eng = self._engine(2 * sampler.pairs, sampler.num_samples)
+        return _fit(eng, sampler, steps, dict(audio=eng.audio, labels=eng.labels))
 
     def train(self, sess, inputs_left, inputs_right, labels):
         x = self._pair(inputs_left, inputs_right)

@@ -13,7 +13,21 @@ auto-encoder (30 layers, S = 128, 5 mixtures, bf16, batch 4 x 4096).  Millisecon
                     alternating fresh processes, --rounds each
 
 (c) - (d) is what the draw and the log launch cost; (a) and (b) show what the host loop around the step costs.
-usage: python tools/fit_bench.py [--steps 200] [--reps 3] [--records 64] [--only teacher|autoencoder]
+
+Three more legs, for the models whose host loops do the most per step (--only student | twins_small | twins_wide; none of
+them runs by default): the student at bench.py's student shape (4 flows x 30 layers, R = 64, a 30-layer MoL-10
+auto-encoder teacher, bf16, batch 8 x 16000) and the twins at tools/siamese_bench.py's two shapes.  For each:
+
+  (a) host loop     the example driver's loop on host arrays (a pool of 16, cycled): examples/student.py's encode, NumPy
+                    logistic noise, train_fast; examples/siamese.py's train on pairs
+  (b) fit           model.fit(sampler, steps) with a DistillSampler / PairSampler on a DeviceDataset
+  (c) staged engine the captured step of the same engine replayed on the inputs of the last host step
+  (e) student only: the teacher encoder's forward pass alone, as a graph -- (b) runs it inside the step, (c) does not
+
+(a) - (c) is what the host loop costs above the step itself; (b) - (c) what the launches of the samplers (and, for the
+student, the teacher's encoder inside the step) cost.
+usage: python tools/fit_bench.py [--steps 200] [--reps 3] [--records 64]
+                                 [--only teacher|autoencoder|student|twins_small|twins_wide]
                                  [--parent-lib ab/libsrwn_parent.so --parent-root ab/parent]"""
 import argparse
 import importlib
@@ -31,6 +45,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIL = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3
 CLIP = 16000
 SHAPES = {"teacher": (8, 16000), "autoencoder": (4, 4096)}
+EXTRA = {"student": (8, 16000), "twins_small": (1, 5120), "twins_wide": (8, 16000)}     # batch (pairs) x samples
 
 
 def make_model(M, shape):
@@ -121,6 +136,93 @@ def model_paths(a, shape):
     return out
 
 
+def make_student(M):
+    """bench.py's student shape on the model API: the frozen teacher is an auto-encoder, so that it can encode."""
+    t = M.WaveNetAutoEncoder(16000, 0, 10, DIL, dilation_channels=64, skip_channels=256, latent_channels=16, pool_stride=125)
+    return M.ParallelWaveNet(16000, 0, DIL, t, num_flows=4, dilation_channels=64, skip_channels=256, latent_channels=16,
+                             pool_stride=125, alpha=1.0, beta=1.0, gamma=1e-3, learning_rate=1e-4)
+
+
+def make_twins(M, shape):
+    R, S = (32, 128) if shape == "twins_small" else (64, 256)
+    return M.SiameseWaveNet(EXTRA[shape][1], 2, DIL, dilation_channels=R, skip_channels=S, learning_rate=1e-4)
+
+
+def extra_paths(a, shape):
+    """(a), (b), (c) of the student and the twins: {key: (best, spread)}."""
+    import gc
+    import torch
+    M = importlib.import_module("sr-wavenet_amd.model")
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    SA = importlib.import_module("sr-wavenet_amd.simple_audio")
+    B, T = EXTRA[shape]
+    rng = np.random.default_rng(1)
+    out = {}
+    if shape == "student":
+        clips = make_clips(a.records)
+        labels = None
+        m = make_student(M)
+        pool = [np.ascontiguousarray(clips[rng.integers(0, a.records, B), :T]) for _ in range(16)]
+
+        def host(n):
+            for i in range(n):
+                x = pool[i % 16]
+                enc = m.encode(None, x, None)
+                noise = rng.logistic(0, 1, (B, T)).astype(np.float32)
+                m.train_fast(None, noise, x, enc, None)
+        eng = lambda: m._engine(B, T)
+    else:
+        gen = np.random.RandomState(0)
+        waves = [SA.generate_random_wave(T, rng=gen) for _ in range(a.records)]
+        clips = np.array([w for w, _ in waves], dtype=np.float32)
+        labels = np.array([int(np.argmax(y)) for _, y in waves])
+        m = make_twins(M, shape)
+        pool = []
+        for _ in range(16):
+            l, r = rng.integers(0, a.records, B), rng.integers(0, a.records, B)
+            pool.append((clips[l], clips[r], (labels[l] == labels[r]).astype(np.float32)))
+
+        def host(n):
+            for i in range(n):
+                m.train(None, *pool[i % 16])
+        eng = lambda: m._engine(2 * B, T)
+    host(a.warmup)
+    out["a"] = regions(host, a.steps, a.reps)
+    e = eng()
+
+    def staged(n):
+        for _ in range(n):
+            e.train_step_graphed()
+    staged(a.warmup)
+    out["c"] = regions(staged, a.steps, a.reps)
+    if shape == "student":      # what (b) runs inside the step and (c) does not: the teacher encoder's forward pass, as a graph
+        enc = m._teacher._engine(B, T).enc
+        enc.forward()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            enc.forward()
+
+        def encode(n):
+            for _ in range(n):
+                g.replay()
+        encode(a.warmup)
+        out["e"] = regions(encode, a.steps, a.reps)
+        del g, enc
+    del m, e
+    gc.collect()
+    torch.cuda.empty_cache()
+    if shape == "student":
+        m = make_student(M)
+        s = D.DeviceDataset(clips).distill_sampler(B, T, seed=0)
+    else:
+        m = make_twins(M, shape)
+        s = D.DeviceDataset(clips, labels, 4).pair_sampler(B, T, seed=0)
+    m.fit(s, a.warmup)
+    out["b"] = regions(lambda n: m.fit(s, n), a.steps, a.reps)
+    return out
+
+
 def staged_child(a):
     """(d) in this process: bench.py's path on the package under --pkg-root."""
     sys.path.insert(0, a.pkg_root)
@@ -177,7 +279,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--records", type=int, default=64, help="clips of 16000 floats in the data set and the generated file")
-    ap.add_argument("--only", default=None, choices=list(SHAPES))
+    ap.add_argument("--only", default=None, choices=list(SHAPES) + list(EXTRA))
     ap.add_argument("--parent-lib", default=None, help="another build of libsrwn.so (relative to the repository) for (d)")
     ap.add_argument("--parent-root", default=None, help="the package that library belongs to (relative to the repository)")
     ap.add_argument("--child", dest="only_shape", default=None, choices=list(SHAPES), help=argparse.SUPPRESS)
@@ -188,6 +290,18 @@ def main():
     if bool(a.parent_lib) != bool(a.parent_root):
         sys.exit("--parent-lib and --parent-root go together")
     sys.path.insert(0, ROOT)
+    if a.only in EXTRA:
+        B, T = EXTRA[a.only]
+        print("== %s, %d x %d, bf16: ms per step, best of %d regions of %d steps (spread)" % (a.only, B, T, a.reps, a.steps),
+              flush=True)
+        res = extra_paths(a, a.only)
+        for key, name in (("a", "(a) the example's host loop"), ("b", "(b) fit"), ("c", "(c) staged engine replays")):
+            print("   %-32s %.4f (%.4f)" % (name, *res[key]), flush=True)
+        if "e" in res:
+            print("   %-32s %.4f (%.4f)" % ("(e) teacher encoder forward alone", *res["e"]), flush=True)
+        print("   (a) - (c) = %+.4f ms   (b) - (c) = %+.4f ms" % (res["a"][0] - res["c"][0], res["b"][0] - res["c"][0]),
+              flush=True)
+        return
     for shape in ([a.only] if a.only else list(SHAPES)):
         B, T = SHAPES[shape]
         print("== %s, batch %d x %d, bf16: ms per step, best of %d regions of %d steps (spread)" % (shape, B, T, a.reps, a.steps),
