@@ -1673,6 +1673,29 @@ int srwn_pair_draw(const float* clips, const int32_t* labels, const int32_t* ord
 int srwn_pair_log(const float* loss, const float* dist, int32_t P, float* loss_log, float* dist_log, int32_t capacity,
                   int64_t* state, void* stream);
 
+/* ---- device-resident evaluation (since srwn_version() 124; csrc/srwn_eval.hip): the launch an EvalSampler
+ * (sr-wavenet_amd/dataset.py) puts behind the classifier's forward pass when it sweeps a held-out set once, inside the
+ * sweep's hipGraph.  The draw in front is srwn_batch_draw with shuffle 0, which only reads the state; this launch ticks it.
+ *   state    int64 [3] = {seed, step, sweep} in device memory
+ *   probs    [B][C] fp32: the pooled head's posteriors of the step's rows;  indices [B] int32: the draw's records
+ *   labels   [num_clips] int32, every one inside [0, C)
+ *   pred, rank_out [sweep_capacity][num_clips] int32;  nll [sweep_capacity][num_clips] fp32;
+ *   confusion [sweep_capacity][C][C] int32 (label, then prediction);  seen [sweep_capacity] int32: the result slots
+ * Row b of the step is position p = (step * world + rank) * B + b and is valid where p < num_clips (its record is p: one
+ * sweep of ceil(num_clips / (B * world)) steps visits every record once across the ranks).  For every valid row the launch
+ * writes, in slot sweep % sweep_capacity and at the row's record: pred, the first maximum of the row (`>` over rising
+ * class index: on equal values the lower index); rank_out, the number of classes that come before the label's class in
+ * that order (a greater probability, or an equal one at a lower index), so rank_out = 0 exactly where pred = label;
+ * nll = (float)(-log((double)probs[label])), +inf for a probability of 0.  It adds 1 to confusion[label][pred] and to seen
+ * with integer atomic adds.  At step 0 it first clears the slot's confusion and seen.  Invalid rows write nothing; records
+ * the sweep has not reached keep what they held.  Last it ticks: step += 1, and where step reaches the sweep's steps,
+ * step = 0 and sweep += 1.  One workgroup.  dataset.sweep_plan states the order in Python.
+ * Errors, all before any launch: a null pointer (-3); C outside [1, 256], B < 1, num_clips < 1, rank outside [0, world),
+ * sweep_capacity < 1 (-2). */
+int srwn_eval_classes(const float* probs, const int32_t* indices, const int32_t* labels, int64_t* state, int32_t num_clips,
+                      int32_t B, int32_t C, int32_t rank, int32_t world, int32_t sweep_capacity, int32_t* pred,
+                      int32_t* rank_out, float* nll, int32_t* confusion, int32_t* seen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -306,6 +306,8 @@ SIGNATURES["srwn_distill_log"] = (C.c_int, [_p, _p, _p, _f64, _f64, _i64, _f64, 
 SIGNATURES["srwn_pair_draw"] = (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _i32, _i32, _i64, _i32, _i32, _i32, _i32,
                                           _p, _p, _p, _p, _p, _p])
 SIGNATURES["srwn_pair_log"] = (C.c_int, [_p, _p, _i32, _p, _p, _i32, _p, _p])
+# device-resident evaluation (srwn_version() 124): an EvalSampler's launch behind the classifier's forward pass
+SIGNATURES["srwn_eval_classes"] = (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -18,6 +18,12 @@ student's clips, its logistic noise (``noise_plan``) and the labels' one-hot row
 loss, power loss and entropy; a ``PairSampler`` draws "same class" / "different class" pairs of a labelled set
 (``pair_plan``) for the twin towers and logs the loss and the pairs' distances.
 
+Held-out evaluation runs the same way (csrc/srwn_eval.hip): an ``EvalSampler`` sweeps a labelled set once, in order
+(``sweep_plan``: the last step may be ragged), its draw is ``srwn_batch_draw`` and the launch behind the forward pass,
+``srwn_eval_classes``, turns the step's posteriors into predicted classes, ranks, per-clip NLL and confusion counts in one
+of ``sweep_capacity`` result slots on the device and ticks the state ``{seed, step, sweep}``; ``WaveNet.evaluate`` and
+``WaveNet.fit(..., validate=...)`` (model.py) read the slots into ``EvalResult``s.
+
 Storage is fp32 only: int16 or bf16 clip storage is out of scope.
 """
 from __future__ import annotations
@@ -86,6 +92,34 @@ def draw_plan(seed: int, step: int, batch_size: int, n: int, clip_len: int, num_
             h = _mix64((seed ^ _CROP_SALT) + _GOLDEN * (p + 1))
             off[b] = ((h >> 32) * (clip_len - num_samples + 1)) >> 32
     return idx, off
+
+
+def sweep_steps(n: int, batch_size: int, world: int = 1) -> int:
+    """The steps of one sweep over `n` records: ceil(n / (batch_size * world))."""
+    n, batch_size, world = int(n), int(batch_size), int(world)
+    if n < 1:
+        raise ValueError("the dataset is empty")
+    if batch_size < 1 or world < 1:
+        raise ValueError("sweep_steps: batch_size %d, world %d" % (batch_size, world))
+    return -(-n // (batch_size * world))
+
+
+def sweep_plan(step: int, batch_size: int, n: int, rank: int = 0, world: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """The batch of step `step` of a sweep that visits every record once: ``(indices [B] int32, valid [B] bool)``.  Row b is
+    position p = (step * world + rank) * B + b; it is valid where p < n and its record is p % n -- ``draw_plan``'s record
+    without shuffling, so ``srwn_batch_draw`` is the sweep's draw and the rows of the ragged tail read inside the set.
+    ``sweep_steps(n, B, world)`` steps of all ranks hold every record exactly once among their valid rows."""
+    step, batch_size, n, rank, world = int(step), int(batch_size), int(n), int(rank), int(world)
+    if n < 1:
+        raise ValueError("the dataset is empty")
+    if not 1 <= batch_size <= MAX_BATCH:
+        raise ValueError("batch_size %d: at least 1, at most %d" % (batch_size, MAX_BATCH))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d of %d" % (rank, world))
+    if step < 0:
+        raise ValueError("step %d" % step)
+    p = (step * world + rank) * batch_size + np.arange(batch_size, dtype=np.int64)
+    return (p % n).astype(np.int32), p < n
 
 
 def noise_rows(seed: int, step: int, batch_size: int, rank: int = 0, world: int = 1) -> np.ndarray:
@@ -290,6 +324,12 @@ class DeviceDataset(object):
         """The draws of a twin-tower run (``SiameseWaveNet.fit``): `pairs` pairs of clips per step, "same class" with
         probability `p_same`.  Needs labels, every one inside [0, num_classes)."""
         return PairSampler(self, pairs, num_samples, seed, p_same, shuffle, crop, rank, world, log_capacity)
+
+    def eval_sampler(self, batch_size, num_samples, crop="head", seed=0, rank=0, world=1, top_k=5, sweep_capacity=16):
+        """The sweeps of a held-out evaluation (``WaveNet.evaluate``, ``WaveNet.fit(..., validate=...)``): every record once
+        per sweep, in order, `batch_size` per step with a ragged last step; the results of the last `sweep_capacity` sweeps
+        stay on the device.  Needs labels, every one inside [0, num_classes), and at most 256 classes."""
+        return EvalSampler(self, batch_size, num_samples, crop, seed, rank, world, top_k, sweep_capacity)
 
     def class_index(self):
         """``class_index`` of the labels as device tensors (order, place, start), built and uploaded on first use."""
@@ -563,3 +603,119 @@ class PairSampler(BatchSampler):
 
     def results(self, step0: int, count: int):
         return self.losses(step0, count), self.distances(step0, count)
+
+
+MAX_EVAL_CLASSES = 256     # srwn_eval_classes: a wave per row, four classes per lane
+
+
+class EvalResult(object):
+    """One sweep of a labelled set through a classifier, as NumPy arrays on the host.
+
+    ``pred``, ``rank`` (int32 [N]) and ``nll`` (float32 [N]) per record: the predicted class, the number of classes that
+    come before the label's class (0 = correct; top-k accuracy is ``mean(rank < k)``) and -log p(label).  ``confusion``
+    int32 [C, C] counts (label, prediction) and ``seen`` the records counted.  ``owned`` bool [N] marks the records this
+    rank swept -- all of them with world = 1; elsewhere ``pred`` and ``rank`` are -1 and ``nll`` is NaN.  ``accuracy``,
+    ``top_k_accuracy`` (at ``top_k``) and ``mean_nll`` (a float64 sum on the host) are over the owned records;
+    ``per_class`` int64 [C, 2] holds (correct, total) per class, the counts train.py:94-113 prints.  ``step`` is the
+    training step the sweep was taken at, or None."""
+
+    def __init__(self, pred, rank, nll, confusion, seen, owned, top_k, step=None):
+        self.pred, self.rank, self.nll, self.confusion = pred, rank, nll, confusion
+        self.seen, self.owned, self.top_k, self.step = int(seen), owned, int(top_k), step
+        n = max(self.seen, 1)
+        self.accuracy = float(np.trace(confusion)) / n
+        self.top_k_accuracy = float(np.count_nonzero(rank[owned] < self.top_k)) / n
+        self.mean_nll = float(nll[owned].astype(np.float64).sum()) / n
+        self.per_class = np.stack([np.diag(confusion), confusion.sum(axis=1)], axis=1).astype(np.int64)
+
+    def __repr__(self):
+        return "EvalResult(step=%r, seen=%d, accuracy=%.4f, top_%d_accuracy=%.4f, mean_nll=%.4f)" % (
+            self.step, self.seen, self.accuracy, self.top_k, self.top_k_accuracy, self.mean_nll)
+
+
+class EvalSampler(BatchSampler):
+    """The sweeps of a held-out evaluation on a labelled ``DeviceDataset`` (``sweep_plan``).  A ``BatchSampler`` without
+    shuffling that owns the device state ``{seed, step, sweep}`` (int64 [3]) and ``sweep_capacity`` result slots, each
+    ``pred [N]`` int32, ``rank [N]`` int32, ``nll [N]`` float32, ``confusion [C, C]`` int32 and ``seen`` int32: sweep k
+    lands in slot k % sweep_capacity.  Its draw is ``srwn_batch_draw``; the launch behind the forward pass,
+    ``srwn_eval_classes`` (``classify``), writes the slot and ticks the state."""
+
+    def __init__(self, dataset, batch_size, num_samples, crop="head", seed=0, rank=0, world=1, top_k=5, sweep_capacity=16):
+        if dataset.labels is None:
+            raise ValueError("eval_sampler: the dataset holds no labels; an evaluation counts predictions against them")
+        C_ = int(dataset.num_classes)
+        if C_ > MAX_EVAL_CLASSES:
+            raise ValueError("eval_sampler: num_classes %d: at most %d" % (C_, MAX_EVAL_CLASSES))
+        if int(top_k) < 1:
+            raise ValueError("top_k %d: at least 1" % int(top_k))
+        if int(sweep_capacity) < 1:
+            raise ValueError("sweep_capacity %d: at least 1" % int(sweep_capacity))
+        _check_draw(int(batch_size), len(dataset), dataset.clip_len, int(num_samples), crop, int(rank), int(world))
+        class_index(dataset._host_labels(), C_)              # (refuses labels outside the classes)
+        BatchSampler.__init__(self, dataset, batch_size, num_samples, seed, False, crop, rank, world, 1)
+        import torch
+        dev, n = dataset.device, len(dataset)
+        self.top_k, self.sweep_capacity = int(top_k), int(sweep_capacity)
+        self.sweep_steps = sweep_steps(n, self.batch_size, self.world)
+        self.state = torch.tensor([int(self.state[0]), 0, 0], dtype=torch.int64, device=dev)
+        self.pred = torch.zeros((self.sweep_capacity, n), dtype=torch.int32, device=dev)
+        self.rank_of_label = torch.zeros((self.sweep_capacity, n), dtype=torch.int32, device=dev)
+        self.nll = torch.zeros((self.sweep_capacity, n), dtype=torch.float32, device=dev)
+        self.confusion = torch.zeros((self.sweep_capacity, C_, C_), dtype=torch.int32, device=dev)
+        self.seen = torch.zeros(self.sweep_capacity, dtype=torch.int32, device=dev)
+        self.sweep = 0           # the host's copy of the device's sweep counter: sweeps launched so far
+
+    def plan(self, step: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """``sweep_plan`` of `step` (default: the next one) for this sampler."""
+        return sweep_plan(self.step if step is None else int(step), self.batch_size, len(self.dataset), self.rank,
+                          self.world)
+
+    def owned(self) -> np.ndarray:
+        """bool [N]: the records this rank's sweep visits."""
+        own = np.zeros(len(self.dataset), bool)
+        for s in range(self.sweep_steps):
+            idx, valid = self.plan(s)
+            own[idx[valid]] = True
+        return own
+
+    def seek(self, step: int) -> None:
+        """Continues the current sweep at `step` (0: starts it over): sets the device's step and the host's."""
+        if not 0 <= int(step) < self.sweep_steps:
+            raise ValueError("step %d of a sweep of %d" % (int(step), self.sweep_steps))
+        self.state[1:2].fill_(int(step))
+        self.step = int(step)
+
+    def log_step(self, loss):
+        raise TypeError("an EvalSampler logs no loss: its last launch is srwn_eval_classes (pass it to evaluate(), or to "
+                        "fit(..., validate=(sampler, every)))")
+
+    def classify(self, probs):
+        """srwn_eval_classes on the current stream: the step's valid rows of `probs` ([B, C] fp32) into the slot of the
+        device's sweep, then the device state ticks."""
+        import torch
+        from . import kernels as K
+        d, B = self.dataset, self.batch_size
+        K.call("srwn_eval_classes", K._chk(probs, "probs", torch.float32, (B, d.num_classes)), self.indices.data_ptr(),
+               d.labels.data_ptr(), self.state.data_ptr(), len(d), B, d.num_classes, self.rank, self.world,
+               self.sweep_capacity, self.pred.data_ptr(), self.rank_of_label.data_ptr(), self.nll.data_ptr(),
+               self.confusion.data_ptr(), self.seen.data_ptr(), K._stream())
+
+    def stepped(self) -> None:
+        """The host's copy of the tick of one ``classify`` launch (or one replay of a graph that holds it)."""
+        self.step += 1
+        if self.step >= self.sweep_steps:
+            self.step = 0
+            self.sweep += 1
+
+    def result(self, sweep: int, step=None) -> "EvalResult":
+        """Sweep number `sweep` (one of the last ``sweep_capacity`` completed) from its slot: the host waits here."""
+        sweep = int(sweep)
+        if not max(0, self.sweep - self.sweep_capacity) <= sweep < self.sweep:
+            raise ValueError("sweep %d: the slots hold sweeps [%d, %d)"
+                             % (sweep, max(0, self.sweep - self.sweep_capacity), self.sweep))
+        k = sweep % self.sweep_capacity
+        own = self.owned()
+        pred = np.where(own, self.pred[k].cpu().numpy(), np.int32(-1)).astype(np.int32)
+        rank = np.where(own, self.rank_of_label[k].cpu().numpy(), np.int32(-1)).astype(np.int32)
+        nll = np.where(own, self.nll[k].cpu().numpy(), np.float32(np.nan)).astype(np.float32)
+        return EvalResult(pred, rank, nll, self.confusion[k].cpu().numpy(), int(self.seen[k].item()), own, self.top_k, step)

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .dataset import EvalResult  # noqa: F401  (what evaluate() returns)
 from .engine import StackConfig, WaveNetEngine
 from .slots import SlotTable, per_stream, slot_list
 
@@ -70,14 +71,15 @@ def _fit_part(eng, sampler, dest, part, between=None):
         sampler.log_engine(eng)
 
 
-def _fit(eng, sampler, steps, dest, between=None):
+def _fit(eng, sampler, steps, dest, between=None, after_step=None):
     """``steps`` training steps of an engine fed by a sampler of dataset.py: every batch is drawn on the device by the
     step's first launch (``dest``: where the sampler's ``draw`` writes what ``set_inputs`` would) and the step is logged
     by its last (the sampler's ``log_engine``), so a run of steps needs no upload and no host wait -- the host waits once
     per ``log_capacity`` steps to drain the rings.  Capture follows ``_train_step``'s rule: two eager steps of this
     (engine, sampler) pair, then hipGraphs of its own (the graphs of ``train(x)`` are not touched); SRWN_MODEL_GRAPHS=0
     keeps eager launches.  Returns what the sampler's ``results`` gives for every step, one array per logged quantity:
-    the loss, float32 [steps], first."""
+    the loss, float32 [steps], first.  `after_step` (validation) is called behind every step, once the sampler's count has
+    ticked; what it enqueues runs between this step's launches and the next one's."""
     steps = int(steps)
     if steps < 0:
         raise ValueError("steps %d" % steps)
@@ -108,6 +110,8 @@ def _fit(eng, sampler, steps, dest, between=None):
                         st["failed"] = True
                         print("hipGraph capture failed (%s); continuing with eager launches" % e)
             sampler.step += 1
+            if after_step is not None:       # (validation: a sweep of another sampler enqueued behind this step)
+                after_step()
         pieces.append(sampler.results(step0, n))               # the host waits here
         done += n
     if not pieces:
@@ -146,6 +150,102 @@ def _fit_labels(sampler, width, who, what):
     if d.num_classes != int(width):
         raise ValueError("%s.fit: the dataset has num_classes=%d, the model's %s are %d wide"
                          % (who, d.num_classes, what, int(width)))
+
+
+def _sweep_steps(eng, sampler, step, count, tick):
+    """`count` forward-only steps of an engine fed by a sampler, enqueued without a host wait: `step()` is the launch
+    sequence {draw, forward, the sampler's last launch} and `tick()` the host's copy of what that last launch does to the
+    device state.  Capture follows ``_fit``'s rule with a state of its own: two eager steps of this (engine, sampler) pair,
+    then one hipGraph that is replayed (the graphs of ``fit`` and ``train`` are not touched); SRWN_MODEL_GRAPHS=0 keeps
+    eager launches."""
+    st = getattr(eng, "_eval_state", None)
+    if st is None or st["sampler"] is not sampler:
+        st = eng._eval_state = {"sampler": sampler, "eager": 0, "graph": None, "failed": False}
+    for _ in range(count):
+        if st["graph"] is not None:
+            st["graph"].replay()
+        else:
+            step()
+            st["eager"] += 1
+            if st["eager"] >= 2 and os.environ.get("SRWN_MODEL_GRAPHS", "1") != "0" and not st["failed"]:
+                try:
+                    import gc
+                    torch.cuda.synchronize()
+                    gc.collect()    # (a collection inside a capture may destroy hipGraphs mid-capture: see _fit_capture)
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):       # capturing launches nothing: the device state does not tick
+                        step()
+                    torch.cuda.synchronize()
+                    st["graph"] = g
+                except Exception as e:   # keep sweeping with eager launches, say why once
+                    st["failed"] = True
+                    print("hipGraph capture failed (%s); continuing with eager launches" % e)
+        tick()
+
+
+def _eval_sweep(eng, ev):
+    """One sweep of an ``EvalSampler`` through a pooled-head engine, enqueued: ``sweep_steps`` steps of {srwn_batch_draw
+    into the engine's audio, the forward pass without loss or weight-gradient tiles, srwn_eval_classes}.  The sweep lands
+    in slot ``(ev.sweep - 1) % sweep_capacity`` once this returns; nothing waits for it here."""
+    def step():
+        ev.draw(audio=eng.audio)
+        eng.forward(with_loss=False, train=False)
+        ev.classify(eng.probs)
+    ev.seek(0)
+    _sweep_steps(eng, ev, step, ev.sweep_steps, ev.stepped)
+
+
+def _evaluate_losses(eng, sampler, dest, who):
+    """The forward-only loss of every step of one sweep of a plain, non-shuffled ``BatchSampler``, float32 [steps]: the
+    launches of ``loss(batch)`` between the sampler's draw and its ``srwn_step_log``.  The host waits once per
+    ``log_capacity`` steps."""
+    def step():
+        sampler.draw(**dest)
+        eng.forward()
+        sampler.log_engine(eng)
+
+    def tick():
+        sampler.step += 1
+    steps = _loss_sweep_steps(sampler, who)
+    sampler.seek(0)
+    pieces, done = [], 0
+    while done < steps:
+        n = min(steps - done, sampler.log_capacity)
+        _sweep_steps(eng, sampler, step, n, tick)
+        pieces.append(sampler.losses(done, n))                  # the host waits here
+        done += n
+    return np.concatenate(pieces)
+
+
+def _loss_sweep_steps(sampler, who):
+    """The steps of ``_evaluate_losses``, or the reason why `sampler` cannot drive it."""
+    from .dataset import BatchSampler
+    if type(sampler) is not BatchSampler:
+        raise TypeError("%s.evaluate takes a plain dataset.BatchSampler (dataset.sampler(..., shuffle=False)), got %s"
+                        % (who, type(sampler).__name__))
+    if sampler.shuffle:
+        raise ValueError("%s.evaluate: the sampler shuffles; a sweep visits the records in order (shuffle=False)" % who)
+    n, per = len(sampler.dataset), sampler.batch_size * sampler.world
+    if n % per:
+        raise ValueError("%s.evaluate: %d clips are no multiple of batch_size * world = %d; this model's loss kernel gives "
+                         "one number per batch, so a ragged last step would count wrapped-around clips twice (the "
+                         "streaming scorers give per-sample likelihoods of any clip)" % (who, n, per))
+    return n // per
+
+
+def _check_validate(validate):
+    """``validate=(eval_sampler, every)`` of ``WaveNet.fit``, checked before any device work."""
+    from .dataset import EvalSampler
+    try:
+        ev, every = validate
+    except (TypeError, ValueError):
+        raise ValueError("validate must be (eval_sampler, every), got %r" % (validate,))
+    if not isinstance(ev, EvalSampler):
+        raise TypeError("validate: the first entry must be a dataset.EvalSampler (dataset.eval_sampler(...)), got %s"
+                        % type(ev).__name__)
+    if int(every) < 1:
+        raise ValueError("validate: every %d: at least 1" % int(every))
+    return ev, int(every)
 
 
 def _default_dtype():
@@ -320,15 +420,73 @@ class WaveNet(_EngineOwner):
         _train_step(eng)
         return np.float32(eng.loss.item())
 
-    def fit(self, sampler, steps):
+    def fit(self, sampler, steps, validate=None):
         """``steps`` training steps on batches a ``dataset.BatchSampler`` draws on the device (the labels' one-hot rows
-        are the targets); returns every step's loss, float32 [steps].  See ``_fit``."""
+        are the targets); returns every step's loss, float32 [steps].  See ``_fit``.
+
+        ``validate=(eval_sampler, every)``: one sweep of a ``dataset.EvalSampler`` (``evaluate``'s) is enqueued behind
+        every training step whose count -- ``sampler.step`` after the step -- is a multiple of `every`, as replays of a
+        graph of its own between the training graph's.  Each sweep lands in the next of the sampler's result slots, so
+        the host does not wait per sweep: the slots are read when ``sweep_capacity`` of them are full and at the end.
+        Returns ``(losses, [EvalResult, ...])`` then, every result with the ``step`` it was taken at.  The training run's
+        bits are the ones without validation."""
+        from .dataset import EvalSampler
+        if isinstance(sampler, EvalSampler):
+            raise TypeError("WaveNet.fit: an EvalSampler sweeps a held-out set; train on dataset.sampler(...)")
         if sampler.num_samples != self.input_size:
             raise ValueError("inputs have %d samples, the model was built for input_size=%d"
                              % (sampler.num_samples, self.input_size))
         _fit_labels(sampler, self.output_size, "WaveNet", "targets")
+        if validate is None:
+            eng = self._engine(sampler.batch_size, sampler.num_samples)
+            return _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels))[0]
+        ev, every = _check_validate(validate)
+        self._check_eval(ev)
         eng = self._engine(sampler.batch_size, sampler.num_samples)
-        return _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels))[0]
+        eng_v = self._engine(ev.batch_size, ev.num_samples)
+        results, pending = [], []            # pending: (sweep number, training step) of the sweeps still in their slots
+
+        def drain():                         # the host waits here
+            results.extend(ev.result(k, s) for k, s in pending)
+            del pending[:]
+
+        def after_step():
+            if sampler.step % every == 0:
+                if len(pending) >= ev.sweep_capacity:
+                    drain()
+                _eval_sweep(eng_v, ev)
+                pending.append((ev.sweep - 1, sampler.step))
+
+        losses = _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels), after_step=after_step)[0]
+        drain()
+        return losses, results
+
+    def _check_eval(self, ev):
+        from .dataset import EvalSampler
+        if not isinstance(ev, EvalSampler):
+            raise TypeError("WaveNet.evaluate takes a dataset.EvalSampler (dataset.eval_sampler(...)), got %s"
+                            % type(ev).__name__)
+        if ev.num_samples != self.input_size:
+            raise ValueError("inputs have %d samples, the model was built for input_size=%d"
+                             % (ev.num_samples, self.input_size))
+        if ev.dataset.num_classes != int(self.output_size):
+            raise ValueError("WaveNet.evaluate: the dataset has num_classes=%d, the model's posteriors are %d wide"
+                             % (ev.dataset.num_classes, int(self.output_size)))
+
+    def evaluate(self, eval_sampler, step=None):
+        """One sweep of a labelled held-out set on the device -- the reference driver's test mode (train.py:90-120)
+        without its loop of uploads and downloads: ``sweep_steps`` steps of {draw, forward pass, ``srwn_eval_classes``},
+        the host waits once at the end.  Returns an ``EvalResult`` (dataset.py): per record the predicted class, the rank
+        of the label's class and -log p(label); the confusion matrix, accuracy, top-k accuracy, mean NLL and per-class
+        (correct, total).  The sampler's batch size may differ from the training one: the engine of that shape runs on
+        the model's current parameters, as ``predict`` does.  Nothing else changes: the parameters, the Adam moments,
+        the optimizer's step and a training sampler's state keep their bits.  With world > 1 this rank sweeps and returns
+        its own share (``EvalResult.owned``); merging -- adding ``confusion``, taking each record from the rank that saw
+        it -- is the caller's."""
+        self._check_eval(eval_sampler)
+        eng = self._engine(eval_sampler.batch_size, eval_sampler.num_samples)
+        _eval_sweep(eng, eval_sampler)
+        return eval_sampler.result(eval_sampler.sweep - 1, step)          # the host waits here
 
     def predict(self, inputs):
         eng = self._stage(inputs)
@@ -800,6 +958,23 @@ class WaveNetTeacher(_EngineOwner):
             dest.update(codes=eng.targets, quantization_channels=self.quantization_channels)
         return _fit(eng, sampler, steps, dest)[0]
 
+    def evaluate(self, sampler):
+        """The forward-only loss -- ``loss(batch)`` -- of every step of one sweep over the sampler's dataset, float32
+        [len(dataset) / (batch_size * world)] in the steps' order, with one host wait per ``log_capacity`` steps.  The loss
+        kernel gives a batch mean (softmax) or sum (mixture of logistics), not per-clip values, so `sampler` is a plain
+        ``dataset.sampler(..., shuffle=False)`` whose batches divide the set.  Per-sample held-out likelihoods of any
+        clip exist already: the streaming scorers (``scorer()``, ``mol_scorer()``).  No parameter changes.  The
+        unconditioned teacher only, as ``fit``."""
+        if self.use_encoding:
+            raise NotImplementedError("WaveNetTeacher.evaluate: this teacher was built with use_encoding=True and its "
+                                      "encoding comes from another model; use loss(inputs, encoding, conditions)")
+        _loss_sweep_steps(sampler, "WaveNetTeacher")
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        dest = dict(audio=eng.audio)
+        if self.head == "softmax":
+            dest.update(codes=eng.targets, quantization_channels=self.quantization_channels)
+        return _evaluate_losses(eng, sampler, dest, "WaveNetTeacher")
+
     def get_logits(self, inputs, encoding=None, conditions=None):
         eng = self._stage(inputs, encoding, conditions)
         return eng.forward(want_logits=True).cpu().numpy()
@@ -1233,6 +1408,22 @@ class WaveNetAutoEncoder(object):
         if self.condition_size > 0:
             dest.update(onehot=d.cond_in, onehot_rows=d.frames, onehot_col0=self.latent_channels)
         return _fit(eng, sampler, steps, dest)[0]
+
+    def evaluate(self, sampler):
+        """The forward-only loss of every step of one sweep over the sampler's dataset, float32 [len(dataset) /
+        (batch_size * world)] in the steps' order; with condition_size > 0 the labels' one-hot rows are the conditions.
+        The mixture-of-logistics loss kernel gives one number per batch, so `sampler` is a plain ``dataset.sampler(...,
+        shuffle=False)`` whose batches divide the set.  Per-sample held-out likelihoods of any clip exist already: the
+        streaming scorer (``scorer()``).  No parameter changes."""
+        _loss_sweep_steps(sampler, "WaveNetAutoEncoder")
+        if self.condition_size > 0:
+            _fit_labels(sampler, self.condition_size, "WaveNetAutoEncoder", "conditions")
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        d = eng.dec
+        dest = dict(audio=eng.enc.x, audio2=d.audio)
+        if self.condition_size > 0:
+            dest.update(onehot=d.cond_in, onehot_rows=d.frames, onehot_col0=self.latent_channels)
+        return _evaluate_losses(eng, sampler, dest, "WaveNetAutoEncoder")
 
     def encode(self, inputs, conditions=None):
         eng = self._stage(inputs, conditions)
