@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Parallel driver to the reference's siamese.py: random wave pairs, label 1 when both clips use the same wave shapes,
-``SiameseWaveNet.train``; same model calls, no TensorFlow session, no plotting.  ``--test`` prints embeddings.
+``SiameseWaveNet.train``; same model calls, no TensorFlow session, no plotting.  ``--test`` prints embeddings; with
+``--device-data`` it sweeps a labelled held-out set on the device and prints what a verification model is judged by.
 
   python examples/siamese.py --train --logdir runs/siamese --steps 1000
   python examples/siamese.py --test --logdir runs/siamese
   python examples/siamese.py --train --logdir runs/siamese --steps 1000 --device-data
+  python examples/siamese.py --test --logdir runs/siamese --device-data --test-clips 1024
 """
 import argparse
 import os
@@ -39,6 +41,10 @@ def main(argv=None):
     p.add_argument("--num-classes", type=int, default=11)
     p.add_argument("--device-clips", type=int, default=256,
                    help="--device-data without --tfrecord: generated waves to hold, labelled by wave shape")
+    p.add_argument("--test-clips", type=int, default=256,
+                   help="--test --device-data without --tfrecord: generated waves of the held-out set")
+    p.add_argument("--eval-batch-size", type=int, default=8, help="--test --device-data: clips per step of the sweep")
+    p.add_argument("--bins", type=int, default=512, help="--test --device-data: bins of the distance histograms")
     a = p.parse_args(argv)
     rng = np.random.RandomState(a.seed) if a.seed is not None else None
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
@@ -62,7 +68,9 @@ def main(argv=None):
                 print(global_step, loss, distance, labels, flush=True)
             network.save(sess, a.logdir, global_step, force=False)                         # once per minute
         network.save(sess, a.logdir, global_step, force=True)
-    if a.test:
+    if a.test and a.device_data:
+        test_sweep(a, network, rng)
+    elif a.test:
         for _ in range(10):
             x1, y1 = generate_random_wave(a.num_samples, rng=rng)
             x2, y2 = generate_random_wave(a.num_samples, rng=rng)
@@ -72,19 +80,38 @@ def main(argv=None):
     return None if loss is None else float(loss)
 
 
+def labelled_set(a, clips, rng, limit=None):
+    """The TFRecord file with its --label-key feature, or `clips` generated waves labelled by wave shape, on the device."""
+    import importlib
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    if a.tfrecord:
+        return D.DeviceDataset.from_tfrecord(a.tfrecord, a.audio_max_length, label_key=a.label_key,
+                                             num_classes=a.num_classes, limit=limit)
+    waves = [generate_random_wave(a.num_samples, rng=rng) for _ in range(clips)]
+    return D.DeviceDataset(np.array([w for w, _ in waves], dtype=np.float32),
+                           np.array([int(np.argmax(y)) for _, y in waves]), 4)
+
+
+def test_sweep(a, network, rng):
+    """--test --device-data: one sweep of a labelled held-out set through a tower and one launch over all its pairs
+    (``SiameseWaveNet.evaluate``): nearest-neighbour accuracy, recall@k, equal error rate, AUC."""
+    import importlib
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    data = labelled_set(a, a.test_clips, rng, limit=D.MAX_EMBED_RECORDS)
+    res = network.evaluate(data.embed_sampler(a.eval_batch_size, a.num_samples, bins=a.bins))
+    far, frr = res.far_frr(res.eer_threshold) if np.isfinite(res.eer_threshold) else (float("nan"), float("nan"))
+    print("Held-out: %d clips | pairs: %d same, %d different" % (res.seen, res.hist_same.sum(), res.hist_diff.sum()))
+    print("1-NN accuracy: %.4f | recall@5: %.4f | recall@10: %.4f" % (res.nn_accuracy, res.recall_at(5), res.recall_at(10)))
+    print("EER: %.4f at distance %.4f (FAR %.4f, FRR %.4f) | AUC: %.4f" % (res.eer, res.eer_threshold, far, frr, res.auc),
+          flush=True)
+    return res
+
+
 def fit_loop(a, network, rng):
     """--device-data: a labelled set of recordings -- the TFRecord file with its --label-key feature, or a fixed set of
     generated waves labelled by wave shape -- is loaded onto the device once; every step draws its pairs there ("same
     class" for half of them) and the steps between two prints are one ``fit`` call."""
-    import importlib
-    D = importlib.import_module("sr-wavenet_amd.dataset")
-    if a.tfrecord:
-        data = D.DeviceDataset.from_tfrecord(a.tfrecord, a.audio_max_length, label_key=a.label_key,
-                                             num_classes=a.num_classes)
-    else:
-        waves = [generate_random_wave(a.num_samples, rng=rng) for _ in range(a.device_clips)]
-        data = D.DeviceDataset(np.array([w for w, _ in waves], dtype=np.float32),
-                               np.array([int(np.argmax(y)) for _, y in waves]), 4)
+    data = labelled_set(a, a.device_clips, rng)
     sampler = data.pair_sampler(a.batch_size, a.num_samples, seed=0)
     sampler.seek(a.start)
     print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)

@@ -1696,6 +1696,36 @@ int srwn_eval_classes(const float* probs, const int32_t* indices, const int32_t*
                       int32_t B, int32_t C, int32_t rank, int32_t world, int32_t sweep_capacity, int32_t* pred,
                       int32_t* rank_out, float* nll, int32_t* confusion, int32_t* seen, void* stream);
 
+/* ---- device-resident evaluation of an embedding model (since srwn_version() 125; csrc/srwn_pair_eval.hip): the two launches
+ * an EmbedSampler (sr-wavenet_amd/dataset.py) adds to a tower's forward pass when it sweeps a labelled held-out set: one
+ * behind every step's forward pass, one behind the sweep's last step over all pairs of records.
+ *   state      int64 [3] = {seed, step, sweep} in device memory, ticked as srwn_eval_classes ticks it
+ *   slots_emb  [sweep_capacity][num_clips][D] fp32;  seen [sweep_capacity] int32;  labels [num_clips] int32
+ *   nearest, same_nearest, rank_same [sweep_capacity][num_clips] int32;  nearest_dist, same_dist the same in fp32
+ *   hist_same, hist_diff [sweep_capacity][bins] int64;  dist NULL or [num_clips][num_clips] fp32
+ * srwn_embed_collect: row b of the step is position p = (step * world + rank) * B + b, valid where p < num_clips.  The launch
+ * copies every valid row of emb [B][D] to record indices[b] of slot sweep % sweep_capacity, adds their number to the slot's
+ * seen (from 0 at step 0) and ticks: step += 1, and where step reaches ceil(num_clips / (B * world)), step = 0 and
+ * sweep += 1.  Invalid rows write nothing.  One workgroup.
+ * srwn_pair_sweep: over the records of slot (sweep - 1) % sweep_capacity, the sweep just completed (nothing before the
+ * first).  d(i, j) = sqrtf(1e-8f + ss) with the bits of srwn_contrastive_head and srwn_gallery_match: lane l of a 64-lane
+ * wave forms ss_l by fmaf(df, df, ss) over k = l, l + 64, ... from 0, an xor butterfly 32, 16, 8, 4, 2, 1 adds the lanes;
+ * dist[i][j] = d(i, j) for every i and j, the diagonal included.  a comes before b iff d_a < d_b, or d_a == d_b and a < b.
+ * Per record i over j != i: nearest and nearest_dist are the first j and its distance (-1 and +inf for one record);
+ * same_nearest and same_dist the first j with labels[j] == labels[i] (-1 and +inf without one); rank_same the number of j of
+ * another label that come before same_nearest, -1 without one.  Over i < j: bin = min(bins - 1, (int)(d * scale)) is counted
+ * in hist_same or hist_diff by the labels; a product that is not below bins, NaN included, goes to the last bin.  The entry
+ * point clears the slot's two histograms with a one-workgroup launch in front of the row launch (one workgroup per
+ * record), which adds its LDS counts to them with 64-bit integer atomic adds: no result depends on an execution order.
+ * Errors, all before any launch: a null pointer other than dist (-3); D outside [1, 1024], num_clips outside [1, 4096],
+ * B < 1, rank outside [0, world), sweep_capacity < 1, bins outside [1, 4096], a scale that is not finite and above 0 (-2). */
+int srwn_embed_collect(const float* emb, const int32_t* indices, int64_t* state, int32_t num_clips, int32_t B, int32_t D,
+                       int32_t rank, int32_t world, int32_t sweep_capacity, float* slots_emb, int32_t* seen, void* stream);
+int srwn_pair_sweep(const float* slots_emb, const int32_t* labels, const int64_t* state, int32_t num_clips, int32_t D,
+                    int32_t sweep_capacity, int32_t bins, float scale, int32_t* nearest, int32_t* same_nearest,
+                    int32_t* rank_same, float* nearest_dist, float* same_dist, int64_t* hist_same, int64_t* hist_diff,
+                    float* dist, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

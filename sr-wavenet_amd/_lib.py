@@ -308,6 +308,10 @@ SIGNATURES["srwn_pair_draw"] = (C.c_int, [_p, _p, _p, _p, _p, _i32, _i32, _i64, 
 SIGNATURES["srwn_pair_log"] = (C.c_int, [_p, _p, _i32, _p, _p, _i32, _p, _p])
 # device-resident evaluation (srwn_version() 124): an EvalSampler's launch behind the classifier's forward pass
 SIGNATURES["srwn_eval_classes"] = (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p])
+# device-resident evaluation of an embedding model (srwn_version() 125): an EmbedSampler's launch behind a tower's forward
+# pass, and the all-pairs launch behind a sweep's last step
+SIGNATURES["srwn_embed_collect"] = (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p])
+SIGNATURES["srwn_pair_sweep"] = (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p])
 
 _lib = None
 BINDING = None      # "pybind11" or "ctypes" once loaded

@@ -24,6 +24,12 @@ Held-out evaluation runs the same way (csrc/srwn_eval.hip): an ``EvalSampler`` s
 of ``sweep_capacity`` result slots on the device and ticks the state ``{seed, step, sweep}``; ``WaveNet.evaluate`` and
 ``WaveNet.fit(..., validate=...)`` (model.py) read the slots into ``EvalResult``s.
 
+An embedding model is judged over all pairs of the held-out set (csrc/srwn_pair_eval.hip): an ``EmbedSampler`` sweeps the
+set the same way, ``srwn_embed_collect`` behind the tower's forward pass gathers the embeddings in a result slot, and one
+``srwn_pair_sweep`` behind the sweep's last step turns the slot's N x N distances into nearest neighbours, the rank of the
+nearest record of the same label and the two distance histograms; ``SiameseWaveNet.evaluate`` and ``SiameseWaveNet.fit(...,
+validate=...)`` read the slots into ``PairEvalResult``s (nearest-neighbour accuracy, recall@k, FAR / FRR, EER, AUC).
+
 Storage is fp32 only: int16 or bf16 clip storage is out of scope.
 """
 from __future__ import annotations
@@ -330,6 +336,15 @@ class DeviceDataset(object):
         per sweep, in order, `batch_size` per step with a ragged last step; the results of the last `sweep_capacity` sweeps
         stay on the device.  Needs labels, every one inside [0, num_classes), and at most 256 classes."""
         return EvalSampler(self, batch_size, num_samples, crop, seed, rank, world, top_k, sweep_capacity)
+
+    def embed_sampler(self, batch_size, num_samples, crop="head", seed=0, bins=512, d_max=None, sweep_capacity=4, rank=0,
+                      world=1):
+        """The sweeps of a held-out evaluation of an embedding model (``SiameseWaveNet.evaluate``,
+        ``SiameseWaveNet.fit(..., validate=...)``): every record once per sweep, in order, then one launch over all pairs
+        of records; the results of the last `sweep_capacity` sweeps stay on the device.  `bins` histogram bins over
+        [0, `d_max`] (None: twice the model's margin).  Needs labels, every one inside [0, num_classes), at most
+        ``MAX_EMBED_RECORDS`` records and world = 1."""
+        return EmbedSampler(self, batch_size, num_samples, crop, seed, bins, d_max, sweep_capacity, rank, world)
 
     def class_index(self):
         """``class_index`` of the labels as device tensors (order, place, start), built and uploaded on first use."""
@@ -719,3 +734,213 @@ class EvalSampler(BatchSampler):
         rank = np.where(own, self.rank_of_label[k].cpu().numpy(), np.int32(-1)).astype(np.int32)
         nll = np.where(own, self.nll[k].cpu().numpy(), np.float32(np.nan)).astype(np.float32)
         return EvalResult(pred, rank, nll, self.confusion[k].cpu().numpy(), int(self.seen[k].item()), own, self.top_k, step)
+
+
+MAX_EMBED_RECORDS = 4096   # srwn_pair_sweep: a workgroup per record keeps the record's row of distances in LDS
+MAX_EMBED_BINS = 4096      # ... and two histograms of `bins` counters
+MAX_EMBED_DIM = 1024       # ... and the record's own embedding
+
+
+class PairEvalResult(object):
+    """One sweep of a labelled set through an embedding model and over all its pairs, as NumPy arrays on the host.
+
+    ``emb`` float32 [N, D]; per record i over the other records j in the order (distance, index): ``nearest`` and
+    ``nearest_dist`` (the first j), ``same_nearest`` and ``same_dist`` (the first j of i's label; -1 and +inf without one)
+    and ``rank_same`` (the records of another label in front of ``same_nearest``; -1 without one) -- ``rank_same == 0`` is a
+    correct 1-NN classification.  ``hist_same`` / ``hist_diff`` int64 [bins] count the pairs i < j of one label / of two
+    labels by ``bin = min(bins - 1, int(d * fp32(bins / d_max)))``.  ``labels`` int32 [N], ``seen`` the records collected,
+    ``step`` the training step the sweep was taken at or None, ``distances`` the whole [N, N] matrix or None.
+
+    Every metric is derived from the integers in float64.  Thresholds lie on the bin edges ``edge(k) = (k + 1) * d_max /
+    bins`` for k = -1 .. bins - 1: at edge k a pair is accepted as "same" iff its bin <= k, so edge -1 accepts nothing and
+    edge bins - 1 everything (the last bin also holds the pairs beyond d_max).  A rate over an empty set of pairs is NaN,
+    and so are ``eer``, ``eer_threshold`` and ``auc`` then."""
+
+    def __init__(self, emb, nearest, nearest_dist, same_nearest, same_dist, rank_same, hist_same, hist_diff, seen, labels,
+                 bins, d_max, step=None, distances=None):
+        self.emb, self.nearest, self.nearest_dist = emb, nearest, nearest_dist
+        self.same_nearest, self.same_dist, self.rank_same = same_nearest, same_dist, rank_same
+        self.hist_same, self.hist_diff = np.asarray(hist_same, np.int64), np.asarray(hist_diff, np.int64)
+        self.seen, self.labels, self.bins, self.d_max = int(seen), labels, int(bins), float(d_max)
+        self.step, self.distances = step, distances
+        self.nn_accuracy = self.recall_at(1)
+        far, frr = self.rates()
+        if np.isnan(far).any() or np.isnan(frr).any():
+            self.eer = self.eer_threshold = self.auc = float("nan")
+        else:
+            k = int(np.argmin(np.abs(far - frr)))            # (the first minimum: the lowest edge)
+            self.eer = float((far[k] + frr[k]) / 2.0)
+            self.eer_threshold = self.edge(k - 1)
+            tpr = 1.0 - frr
+            self.auc = float(np.sum((far[1:] - far[:-1]) * (tpr[1:] + tpr[:-1]) / 2.0))
+
+    def edge(self, k: int) -> float:
+        """The threshold of bin edge k in [-1, bins - 1]."""
+        return (int(k) + 1) * self.d_max / self.bins
+
+    def rates(self):
+        """``(FAR, FRR)``, float64 [bins + 1]: entry k + 1 is at edge k, from edge -1 (accept nothing: 0, 1) to edge
+        bins - 1 (accept everything: 1, 0)."""
+        same, diff = self.hist_same.astype(np.float64), self.hist_diff.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            far = np.concatenate([[0.0], np.cumsum(diff)]) / diff.sum()
+            frr = (same.sum() - np.concatenate([[0.0], np.cumsum(same)])) / same.sum()
+        return far, frr
+
+    def far_frr(self, threshold: float):
+        """``(FAR, FRR)`` at a threshold on a bin edge."""
+        x = float(threshold) * self.bins / self.d_max
+        k = int(round(x)) - 1
+        if not -1 <= k <= self.bins - 1 or abs(x - (k + 1)) > 1e-9 * max(1.0, abs(x)):
+            raise ValueError("threshold %r: thresholds lie on the bin edges (k + 1) * %r / %d, k in [-1, %d]"
+                             % (threshold, self.d_max, self.bins, self.bins - 1))
+        far, frr = self.rates()
+        return float(far[k + 1]), float(frr[k + 1])
+
+    def recall_at(self, k: int) -> float:
+        """``mean(0 <= rank_same < k)`` over all records: a record without a partner of its label counts as a miss."""
+        r = self.rank_same
+        return float(np.count_nonzero((r >= 0) & (r < int(k)))) / max(int(r.shape[0]), 1)
+
+    def __repr__(self):
+        return "PairEvalResult(step=%r, seen=%d, nn_accuracy=%.4f, eer=%.4f at %.4f, auc=%.4f)" % (
+            self.step, self.seen, self.nn_accuracy, self.eer, self.eer_threshold, self.auc)
+
+
+class EmbedSampler(BatchSampler):
+    """The sweeps of a held-out evaluation of an embedding model on a labelled ``DeviceDataset`` (``sweep_plan``).  A
+    ``BatchSampler`` without shuffling that owns the device state ``{seed, step, sweep}`` (int64 [3]) and ``sweep_capacity``
+    result slots, each ``emb [N, D]`` fp32, ``nearest``, ``same_nearest``, ``rank_same`` int32 [N], ``nearest_dist``,
+    ``same_dist`` fp32 [N], ``hist_same``, ``hist_diff`` int64 [bins] and ``seen`` int32: sweep k lands in slot
+    k % sweep_capacity.  Its draw is ``srwn_batch_draw``; the launch behind the forward pass, ``srwn_embed_collect``
+    (``collect``), fills the slot's embeddings and ticks the state; ``srwn_pair_sweep`` (``pair_sweep``) behind a sweep's last
+    step fills the rest from all pairs.  D and, with ``d_max=None``, the histograms' range (twice the margin) come from the
+    model that first runs the sampler (``bind``).  At most ``MAX_EMBED_RECORDS`` records; world = 1 only."""
+
+    def __init__(self, dataset, batch_size, num_samples, crop="head", seed=0, bins=512, d_max=None, sweep_capacity=4, rank=0,
+                 world=1):
+        if dataset.labels is None:
+            raise ValueError("embed_sampler: the dataset holds no labels; the pairs are counted by them")
+        if int(world) > 1:
+            raise ValueError("embed_sampler: world %d: the all-pairs pass needs every rank's embeddings, and a rank collects "
+                             "only its own share of the records (an all-gather of embeddings is not built): world = 1"
+                             % int(world))
+        if not 1 <= int(bins) <= MAX_EMBED_BINS:
+            raise ValueError("bins %d: at least 1, at most %d" % (int(bins), MAX_EMBED_BINS))
+        if d_max is not None and not (np.isfinite(float(d_max)) and float(d_max) > 0.0):
+            raise ValueError("d_max %r: finite and above 0" % (d_max,))
+        if int(sweep_capacity) < 1:
+            raise ValueError("sweep_capacity %d: at least 1" % int(sweep_capacity))
+        if len(dataset) > MAX_EMBED_RECORDS:
+            raise ValueError("embed_sampler: %d records: at most %d (a record's row of distances stays in one workgroup's "
+                             "LDS)" % (len(dataset), MAX_EMBED_RECORDS))
+        _check_draw(int(batch_size), len(dataset), dataset.clip_len, int(num_samples), crop, int(rank), int(world))
+        class_index(dataset._host_labels(), int(dataset.num_classes))      # (refuses labels outside the classes)
+        BatchSampler.__init__(self, dataset, batch_size, num_samples, seed, False, crop, rank, world, 1)
+        import torch
+        dev, n = dataset.device, len(dataset)
+        self.bins, self.d_max, self.sweep_capacity = int(bins), None if d_max is None else float(d_max), int(sweep_capacity)
+        self.sweep_steps = sweep_steps(n, self.batch_size, self.world)
+        self.state = torch.tensor([int(self.state[0]), 0, 0], dtype=torch.int64, device=dev)
+        cap = self.sweep_capacity
+        self.dim = None          # D, once a model has bound the sampler
+        self.emb = None
+        self.nearest = torch.zeros((cap, n), dtype=torch.int32, device=dev)
+        self.same_nearest = torch.zeros((cap, n), dtype=torch.int32, device=dev)
+        self.rank_same = torch.zeros((cap, n), dtype=torch.int32, device=dev)
+        self.nearest_dist = torch.zeros((cap, n), dtype=torch.float32, device=dev)
+        self.same_dist = torch.zeros((cap, n), dtype=torch.float32, device=dev)
+        self.hist_same = torch.zeros((cap, self.bins), dtype=torch.int64, device=dev)
+        self.hist_diff = torch.zeros((cap, self.bins), dtype=torch.int64, device=dev)
+        self.seen = torch.zeros(cap, dtype=torch.int32, device=dev)
+        self.dist = None         # [N, N], allocated by the first sweep that asks for the matrix
+        self.sweep = 0           # the host's copy of the device's sweep counter: sweeps launched so far
+
+    def bind(self, dim: int, d_max_default: float) -> None:
+        """What the model supplies when it first runs the sampler: the embedding's dimensions (the slots' ``emb`` are
+        allocated here) and, where the sampler was built with ``d_max=None``, the histograms' range."""
+        dim = int(dim)
+        if not 1 <= dim <= MAX_EMBED_DIM:
+            raise ValueError("embed_sampler: %d embedding dimensions: at least 1, at most %d" % (dim, MAX_EMBED_DIM))
+        if self.dim is not None and self.dim != dim:
+            raise ValueError("embed_sampler: bound to %d embedding dimensions, the model has %d" % (self.dim, dim))
+        if self.d_max is None:
+            if not (np.isfinite(float(d_max_default)) and float(d_max_default) > 0.0):
+                raise ValueError("d_max %r: finite and above 0" % (d_max_default,))
+            self.d_max = float(d_max_default)
+        if self.dim is None:
+            import torch
+            self.dim = dim
+            self.emb = torch.zeros((self.sweep_capacity, len(self.dataset), dim), dtype=torch.float32,
+                                   device=self.dataset.device)
+
+    @property
+    def scale(self) -> np.float32:
+        """fp32(bins / d_max): what ``srwn_pair_sweep`` multiplies a distance by."""
+        if self.d_max is None:
+            raise ValueError("embed_sampler: d_max is not set yet (the model supplies 2 * margin when it first runs the sampler)")
+        return np.float32(self.bins / self.d_max)
+
+    def plan(self, step: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """``sweep_plan`` of `step` (default: the next one) for this sampler."""
+        return sweep_plan(self.step if step is None else int(step), self.batch_size, len(self.dataset), self.rank,
+                          self.world)
+
+    def seek(self, step: int) -> None:
+        """Continues the current sweep at `step` (0: starts it over): sets the device's step and the host's."""
+        if not 0 <= int(step) < self.sweep_steps:
+            raise ValueError("step %d of a sweep of %d" % (int(step), self.sweep_steps))
+        self.state[1:2].fill_(int(step))
+        self.step = int(step)
+
+    def log_step(self, loss):
+        raise TypeError("an EmbedSampler logs no loss: its last launch is srwn_embed_collect (pass it to "
+                        "SiameseWaveNet.evaluate(), or to fit(..., validate=(sampler, every)))")
+
+    def collect(self, emb):
+        """srwn_embed_collect on the current stream: the step's valid rows of `emb` ([B, D] fp32) into the slot of the
+        device's sweep, then the device state ticks."""
+        import torch
+        from . import kernels as K
+        d, B = self.dataset, self.batch_size
+        if self.emb is None:
+            raise ValueError("embed_sampler: not bound to a model yet (bind)")
+        K.call("srwn_embed_collect", K._chk(emb, "emb", torch.float32, (B, self.dim)), self.indices.data_ptr(),
+               self.state.data_ptr(), len(d), B, self.dim, self.rank, self.world, self.sweep_capacity, self.emb.data_ptr(),
+               self.seen.data_ptr(), K._stream())
+
+    def stepped(self) -> None:
+        """The host's copy of the tick of one ``collect`` launch (or one replay of a graph that holds it)."""
+        self.step += 1
+        if self.step >= self.sweep_steps:
+            self.step = 0
+            self.sweep += 1
+
+    def pair_sweep(self, distances: bool = False):
+        """srwn_pair_sweep on the current stream, over the slot of the sweep the device has just completed; with
+        `distances` the whole matrix goes to ``self.dist`` [N, N]."""
+        import torch
+        from . import kernels as K
+        d, n = self.dataset, len(self.dataset)
+        if self.emb is None:
+            raise ValueError("embed_sampler: not bound to a model yet (bind)")
+        if distances and self.dist is None:
+            self.dist = torch.zeros((n, n), dtype=torch.float32, device=d.device)
+        K.call("srwn_pair_sweep", self.emb.data_ptr(), d.labels.data_ptr(), self.state.data_ptr(), n, self.dim,
+               self.sweep_capacity, self.bins, float(self.scale), self.nearest.data_ptr(), self.same_nearest.data_ptr(),
+               self.rank_same.data_ptr(), self.nearest_dist.data_ptr(), self.same_dist.data_ptr(), self.hist_same.data_ptr(),
+               self.hist_diff.data_ptr(), self.dist.data_ptr() if distances else None, K._stream())
+
+    def result(self, sweep: int, step=None, distances: bool = False) -> "PairEvalResult":
+        """Sweep number `sweep` (one of the last ``sweep_capacity`` completed) from its slot: the host waits here.  With
+        `distances` the matrix of the last ``pair_sweep(distances=True)`` goes along."""
+        sweep = int(sweep)
+        if not max(0, self.sweep - self.sweep_capacity) <= sweep < self.sweep:
+            raise ValueError("sweep %d: the slots hold sweeps [%d, %d)"
+                             % (sweep, max(0, self.sweep - self.sweep_capacity), self.sweep))
+        k = sweep % self.sweep_capacity
+        host = lambda t: t[k].cpu().numpy()
+        return PairEvalResult(host(self.emb), host(self.nearest), host(self.nearest_dist), host(self.same_nearest),
+                              host(self.same_dist), host(self.rank_same), host(self.hist_same), host(self.hist_diff),
+                              int(self.seen[k].item()), self.dataset._host_labels().astype(np.int32), self.bins, self.d_max,
+                              step, self.dist.cpu().numpy() if distances and self.dist is not None else None)

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .dataset import EvalResult  # noqa: F401  (what evaluate() returns)
+from .dataset import EvalResult, PairEvalResult  # noqa: F401  (what the evaluate() methods return)
 from .engine import StackConfig, WaveNetEngine
 from .slots import SlotTable, per_stream, slot_list
 
@@ -217,12 +217,12 @@ def _evaluate_losses(eng, sampler, dest, who):
     return np.concatenate(pieces)
 
 
-def _loss_sweep_steps(sampler, who):
-    """The steps of ``_evaluate_losses``, or the reason why `sampler` cannot drive it."""
+def _loss_sweep_steps(sampler, who, kind=None, how="a plain dataset.BatchSampler (dataset.sampler(..., shuffle=False))"):
+    """The steps of ``_evaluate_losses``, or the reason why `sampler` cannot drive it.  `kind`: the sampler class the
+    model's step is fed by (default: a plain ``BatchSampler``), `how` its name in the refusal."""
     from .dataset import BatchSampler
-    if type(sampler) is not BatchSampler:
-        raise TypeError("%s.evaluate takes a plain dataset.BatchSampler (dataset.sampler(..., shuffle=False)), got %s"
-                        % (who, type(sampler).__name__))
+    if type(sampler) is not (kind or BatchSampler):
+        raise TypeError("%s.evaluate takes %s, got %s" % (who, how, type(sampler).__name__))
     if sampler.shuffle:
         raise ValueError("%s.evaluate: the sampler shuffles; a sweep visits the records in order (shuffle=False)" % who)
     n, per = len(sampler.dataset), sampler.batch_size * sampler.world
@@ -233,16 +233,16 @@ def _loss_sweep_steps(sampler, who):
     return n // per
 
 
-def _check_validate(validate):
-    """``validate=(eval_sampler, every)`` of ``WaveNet.fit``, checked before any device work."""
+def _check_validate(validate, kind=None, how="a dataset.EvalSampler (dataset.eval_sampler(...))"):
+    """``validate=(eval_sampler, every)`` of ``WaveNet.fit`` (`kind`, `how`: the sampler class of another model's
+    sweeps and its name in the refusal), checked before any device work."""
     from .dataset import EvalSampler
     try:
         ev, every = validate
     except (TypeError, ValueError):
         raise ValueError("validate must be (eval_sampler, every), got %r" % (validate,))
-    if not isinstance(ev, EvalSampler):
-        raise TypeError("validate: the first entry must be a dataset.EvalSampler (dataset.eval_sampler(...)), got %s"
-                        % type(ev).__name__)
+    if not isinstance(ev, kind or EvalSampler):
+        raise TypeError("validate: the first entry must be %s, got %s" % (how, type(ev).__name__))
     if int(every) < 1:
         raise ValueError("validate: every %d: at least 1" % int(every))
     return ev, int(every)
@@ -2224,6 +2224,54 @@ class ParallelWaveNet(object):
             sampler.scatter(enc.enc, tables)
         return _fit(eng, sampler, steps, dest, between)
 
+    def evaluate(self, sampler):
+        """The forward-only ``(loss, power_loss, entropy)`` of every batch of one sweep of a held-out set, float32
+        [steps] each: a step is ``fit``'s without the backward pass and the update -- {``srwn_distill_draw``, the teacher
+        encoder's forward pass and ``srwn_cond_scatter``, the student's forward pass, ``srwn_distill_log``} -- replayed
+        from a graph of its own; the noise is the sampler's ``noise_plan`` and the conditions are as in ``fit``.  Takes a
+        ``dataset.DistillSampler`` built with ``shuffle=False`` whose set is a multiple of batch_size * world (the losses
+        are one number per batch).  The host waits once per ``log_capacity`` steps.  Nothing else changes: the flows'
+        parameters, their Adam moments, the optimizer's step, the frozen teacher and a training sampler's state keep their
+        bits."""
+        from .dataset import DistillSampler
+        steps = _loss_sweep_steps(sampler, "ParallelWaveNet", DistillSampler,
+                                  "a dataset.DistillSampler (dataset.distill_sampler(..., shuffle=False))")
+        if self._teacher is not None and not isinstance(self._teacher, WaveNetAutoEncoder):
+            raise NotImplementedError("ParallelWaveNet.evaluate runs the teacher's encoder inside the step: build the "
+                                      "student on a WaveNetAutoEncoder teacher (a decoder-only teacher has no encoder)")
+        if self.condition_size > 0:
+            d = sampler.dataset
+            if d.labels is None:
+                raise ValueError("ParallelWaveNet.evaluate: the dataset holds no labels; their one-hot rows are the "
+                                 "conditions")
+            if d.num_classes != int(self.condition_size):
+                raise ValueError("ParallelWaveNet.evaluate: the dataset has num_classes=%d, the model's conditions are %d "
+                                 "wide" % (d.num_classes, int(self.condition_size)))
+        eng = self._engine(sampler.batch_size, sampler.num_samples)
+        enc, tch = self._teacher._engine(eng.B, eng.T).enc, eng.teacher
+        tables = [tch.cond_in] + [f.cond_in for f in eng.flows]
+        dest = dict(audio=enc.x, audio2=eng.truth, audio3=tch.audio, noise=eng.noise)
+        if self.condition_size > 0:
+            dest.update(tables=tables, rows=tch.frames, col0=self.latent_channels)
+
+        def step():
+            sampler.draw(**dest)
+            enc.forward()
+            sampler.scatter(enc.enc, tables)
+            eng.forward()
+            sampler.log_engine(eng)
+
+        def tick():
+            sampler.step += 1
+        sampler.seek(0)
+        pieces, done = [], 0
+        while done < steps:
+            n = min(steps - done, sampler.log_capacity)
+            _sweep_steps(eng, sampler, step, n, tick)
+            pieces.append((sampler.losses(done, n), sampler.power_losses(done, n), sampler.entropies(done, n)))   # waits
+            done += n
+        return tuple(np.concatenate([p[i] for p in pieces]) for i in range(3))
+
     def train_fast(self, sess, inputs, truth, encoding, conditions=None):
         """One distillation step (model.py:634-642): returns (loss, power_loss)."""
         eng = self._stage(inputs, truth, encoding, conditions)
@@ -2841,18 +2889,85 @@ class SiameseWaveNet(_EngineOwner):
     def save(self, sess, logdir, global_step, force=False, fmt=None):
         return super().save(logdir, global_step, force, fmt)
 
-    def fit(self, sampler, steps):
+    def fit(self, sampler, steps, validate=None):
         """``steps`` training steps (``train``'s) on the pairs a ``dataset.PairSampler`` draws on the device from a
-        labelled set of recordings.  Returns (loss [steps], distance [steps, P]), float32.  See ``_fit``."""
-        from .dataset import PairSampler
+        labelled set of recordings.  Returns (loss [steps], distance [steps, P]), float32.  See ``_fit``.
+
+        ``validate=(embed_sampler, every)``: one sweep of a ``dataset.EmbedSampler`` (``evaluate``'s) is enqueued behind
+        every training step whose count -- ``sampler.step`` after the step -- is a multiple of `every`, with the contract
+        of ``WaveNet.fit``'s ``validate``: each sweep lands in the next of the sampler's result slots, the slots are read
+        when ``sweep_capacity`` of them are full and at the end, and the training run's bits are the ones without
+        validation.  Returns ``(loss, distance, [PairEvalResult, ...])`` then, every result with the ``step`` it was
+        taken at."""
+        from .dataset import EmbedSampler, PairSampler
         if not isinstance(sampler, PairSampler):
             raise NotImplementedError("SiameseWaveNet.fit: a step needs pairs of clips and their labels; feed it with "
                                       "train(sess, inputs_left, inputs_right, labels)")
         if sampler.num_samples != self.input_size:
             raise ValueError("SiameseWaveNet.fit: the sampler draws %d samples, the model was built for input_size=%d"
                              % (sampler.num_samples, self.input_size))
+        if validate is None:
+            eng = self._engine(2 * sampler.pairs, sampler.num_samples)
+            return _fit(eng, sampler, steps, dict(audio=eng.audio, labels=eng.labels))
+        es, every = _check_validate(validate, EmbedSampler, "a dataset.EmbedSampler (dataset.embed_sampler(...))")
+        self._check_embed(es)
         eng = self._engine(2 * sampler.pairs, sampler.num_samples)
-        return _fit(eng, sampler, steps, dict(audio=eng.audio, labels=eng.labels))
+        eng_v = self._engine(es.batch_size, es.num_samples)
+        results, pending = [], []            # pending: (sweep number, training step) of the sweeps still in their slots
+
+        def drain():                         # the host waits here
+            results.extend(es.result(k, s) for k, s in pending)
+            del pending[:]
+
+        def after_step():
+            if sampler.step % every == 0:
+                if len(pending) >= es.sweep_capacity:
+                    drain()
+                self._embed_sweep(eng_v, es)
+                pending.append((es.sweep - 1, sampler.step))
+
+        loss, dist = _fit(eng, sampler, steps, dict(audio=eng.audio, labels=eng.labels), after_step=after_step)
+        drain()
+        return loss, dist, results
+
+    def _check_embed(self, es):
+        """An ``EmbedSampler`` this model can sweep; binds it to the embedding's width and, without a d_max of its own, to
+        a histogram range of twice the margin (beyond the margin a pair of two labels costs nothing)."""
+        from .dataset import EmbedSampler
+        if not isinstance(es, EmbedSampler):
+            raise TypeError("SiameseWaveNet.evaluate takes a dataset.EmbedSampler (dataset.embed_sampler(...)), got %s"
+                            % type(es).__name__)
+        if es.num_samples != self.input_size:
+            raise ValueError("SiameseWaveNet.evaluate: the sampler draws %d samples, the model was built for input_size=%d"
+                             % (es.num_samples, self.input_size))
+        es.bind(self.output_dimensions, 2.0 * float(self.margin))
+
+    @staticmethod
+    def _embed_sweep(eng, es, distances=False):
+        """One sweep of an ``EmbedSampler`` through a tower, enqueued: ``sweep_steps`` steps of {srwn_batch_draw into the
+        engine's audio, ``get_embedding``'s forward pass -- no pairs, no loss --, srwn_embed_collect}, then srwn_pair_sweep
+        over the slot ``(es.sweep - 1) % sweep_capacity``.  Nothing waits for it here."""
+        def step():
+            es.draw(audio=eng.audio)
+            eng.forward(with_loss=False)
+            es.collect(eng.emb)
+        es.seek(0)
+        _sweep_steps(eng, es, step, es.sweep_steps, es.stepped)
+        es.pair_sweep(distances)
+
+    def evaluate(self, embed_sampler, step=None, distances=False):
+        """One sweep of a labelled held-out set on the device and one launch over all its pairs: ``sweep_steps`` replays of
+        {draw, the tower's forward pass, ``srwn_embed_collect``}, ``srwn_pair_sweep``, then the host waits once.  Returns a
+        ``PairEvalResult`` (dataset.py): the embeddings, per record the nearest record, the nearest one of its label and
+        the rank of that one among the records of other labels, the distance histograms of the pairs of one label and of
+        two, and from them nearest-neighbour accuracy, recall@k, FAR / FRR at the bin edges, EER and AUC; with
+        `distances` the [N, N] matrix too.  The sampler's batch size is any (the engine of that shape runs on the model's
+        current parameters, as ``get_embedding`` does).  Nothing else changes: the parameters, the Adam moments, the
+        optimizer's step and a training sampler's state keep their bits."""
+        self._check_embed(embed_sampler)
+        eng = self._engine(embed_sampler.batch_size, embed_sampler.num_samples)
+        self._embed_sweep(eng, embed_sampler, bool(distances))
+        return embed_sampler.result(embed_sampler.sweep - 1, step, bool(distances))      # the host waits here
 
     def train(self, sess, inputs_left, inputs_right, labels):
         x = self._pair(inputs_left, inputs_right)
