@@ -58,22 +58,26 @@ def main(argv=None):
     p.add_argument("--validation-clips", type=int, default=64)
     p.add_argument("--validate-every", type=int, default=100, help="--device-data: training steps between two sweeps")
     p.add_argument("--eval-batch-size", type=int, default=8)
+    import importlib
+    O = importlib.import_module("sr-wavenet_amd.optim")
+    O.add_control_flags(p, validate=True)
     a = p.parse_args(argv)
     rng = np.random.RandomState(a.seed) if a.seed is not None else None
     num_classes = len(WORDS)
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 2)[:a.layers]
     network = WaveNet(a.num_samples, num_classes, dilations, dilation_channels=32, skip_channels=128,
                       output_channels=num_classes, learning_rate=0.001)                     # train.py:39
+    if a.train:
+        O.apply_control_flags(network, a, 0.001, a.steps)
     network.load(a.logdir)
     D = None
     if a.device_data:
-        import importlib
         D = importlib.import_module("sr-wavenet_amd.dataset")
     if a.train and a.device_data:
         fit_loop(a, network, D, rng)
     elif a.train:
-        global_step = 0
-        for global_step in range(a.steps):
+        global_step = first = network.training_step() if a.resume and network.load_training_state(a.logdir) else 0
+        for global_step in range(first, a.steps):
             x, labels = make_set(a.batch_size, a.num_samples, rng)
             y = np.eye(num_classes, dtype=np.float32)[labels]
             loss = network.train(x, y)
@@ -81,8 +85,11 @@ def main(argv=None):
                 probs = network.predict(x)[:, 0, :]
                 print("Step: {:6d} | Loss: {:.4f} | Correct Pred: {:.4f} | Real: {} | Predicted: {}".format(
                     global_step, loss, np.sum(y * probs), WORDS[labels[0]], WORDS[int(np.argmax(probs[0]))]), flush=True)
-            network.save(a.logdir, global_step, force=False)                              # once per minute
+            if network.save(a.logdir, global_step, force=False) and a.resume:             # once per minute
+                network.save_training_state(a.logdir, global_step)
         network.save(a.logdir, global_step, force=True)
+        if a.resume:
+            network.save_training_state(a.logdir, global_step)
     if a.test:
         x, labels = make_set(a.test_clips, a.num_samples, rng)
         if a.device_data:
@@ -111,6 +118,9 @@ def fit_loop(a, network, D, rng):
     print("%d + %d clips of %d samples on the device (%.1f MB)" % (len(train), len(held), train.clip_len,
                                                                   (train.nbytes + held.nbytes) / 1e6), flush=True)
     step = 0
+    if a.resume and network.load_training_state(a.logdir, sampler=sampler):
+        step = sampler.step                          # the sampler continues its sequence where the saved run stopped
+    first = step
     while step < a.steps:
         n = min(a.print_steps, a.steps - step)
         losses, sweeps = network.fit(sampler, n, validate=(validation, a.validate_every))
@@ -119,9 +129,12 @@ def fit_loop(a, network, D, rng):
         for r in sweeps:
             print("Step: {:6d} | Validation: {:d} of {:d} | % Correct: {:.3f} | NLL: {:.4f}".format(
                 r.step, int(np.trace(r.confusion)), r.seen, r.accuracy, r.mean_nll), flush=True)
-        network.save(a.logdir, step - 1, force=False)
-    if step:
+        if network.save(a.logdir, step - 1, force=False) and a.resume:
+            network.save_training_state(a.logdir, step - 1, sampler=sampler)
+    if step > first or (step and not a.resume):
         network.save(a.logdir, step - 1, force=True)
+        if a.resume:
+            network.save_training_state(a.logdir, step - 1, sampler=sampler)
 
 
 if __name__ == "__main__":

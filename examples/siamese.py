@@ -45,17 +45,24 @@ def main(argv=None):
                    help="--test --device-data without --tfrecord: generated waves of the held-out set")
     p.add_argument("--eval-batch-size", type=int, default=8, help="--test --device-data: clips per step of the sweep")
     p.add_argument("--bins", type=int, default=512, help="--test --device-data: bins of the distance histograms")
+    import importlib
+    O = importlib.import_module("sr-wavenet_amd.optim")
+    O.add_control_flags(p)
     a = p.parse_args(argv)
     rng = np.random.RandomState(a.seed) if a.seed is not None else None
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     network = SiameseWaveNet(input_size=a.num_samples, output_dimensions=2, dilations=dilations, skip_channels=128,
                              learning_rate=1e-4)                                             # siamese.py:44
     sess = None                                                                               # accepted and ignored
+    if a.train:
+        O.apply_control_flags(network, a, 1e-4, a.steps)
     network.load(sess, a.logdir)
     loss = None
     if a.train and a.device_data:
         loss = fit_loop(a, network, rng)
     elif a.train:
+        if a.resume and network.load_training_state(a.logdir):
+            a.start = network.training_step()
         global_step = a.start
         for global_step in range(a.start, a.steps):
             pairs = [(generate_random_wave(a.num_samples, rng=rng), generate_random_wave(a.num_samples, rng=rng))
@@ -66,8 +73,11 @@ def main(argv=None):
             loss, distance = network.train(sess, x1, x2, labels)
             if global_step % a.print_steps == 0:
                 print(global_step, loss, distance, labels, flush=True)
-            network.save(sess, a.logdir, global_step, force=False)                         # once per minute
+            if network.save(sess, a.logdir, global_step, force=False) and a.resume:        # once per minute
+                network.save_training_state(a.logdir, global_step)
         network.save(sess, a.logdir, global_step, force=True)
+        if a.resume:
+            network.save_training_state(a.logdir, global_step)
     if a.test and a.device_data:
         test_sweep(a, network, rng)
     elif a.test:
@@ -114,6 +124,8 @@ def fit_loop(a, network, rng):
     data = labelled_set(a, a.device_clips, rng)
     sampler = data.pair_sampler(a.batch_size, a.num_samples, seed=0)
     sampler.seek(a.start)
+    if a.resume and network.load_training_state(a.logdir, sampler=sampler):
+        a.start = sampler.step                       # the sampler continues its sequence where the saved run stopped
     print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)
     loss, step = None, a.start
     while step < a.steps:
@@ -122,9 +134,12 @@ def fit_loop(a, network, rng):
         step += n
         loss = losses[-1]
         print(step - 1, loss, distance[-1], sampler.y.cpu().numpy(), flush=True)
-        network.save(None, a.logdir, step - 1, force=False)
+        if network.save(None, a.logdir, step - 1, force=False) and a.resume:
+            network.save_training_state(a.logdir, step - 1, sampler=sampler)
     if loss is not None:
         network.save(None, a.logdir, step - 1, force=True)
+        if a.resume:
+            network.save_training_state(a.logdir, step - 1, sampler=sampler)
     return loss
 
 

@@ -35,6 +35,9 @@ def main(argv=None):
     p.add_argument("--device-data", action="store_true",
                    help="keep the clips on the device; draw clips and noise and run the teacher's encoder inside the step (model.fit)")
     p.add_argument("--device-clips", type=int, default=256, help="--device-data without --tfrecord: synthetic waves to hold")
+    import importlib
+    O = importlib.import_module("sr-wavenet_amd.optim")
+    O.add_control_flags(p)
     a = p.parse_args(argv)
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     data = NsynthDataReader(a.tfrecord, a.batch_size, a.num_samples, audio_max_length=a.audio_max_length) if a.tfrecord else None
@@ -43,12 +46,14 @@ def main(argv=None):
                               latent_channels=a.latent_channels, pool_stride=a.pool_stride, alpha=1.0, beta=1.0,
                               gamma=1.0, learning_rate=1e-4)                              # student.py:82
     sess = None                                                                           # accepted and ignored
+    O.apply_control_flags(student, a, 1e-4, a.steps)
     student.load(sess, a.student)
     if a.device_data:
         return fit_loop(a, student)
     rng = np.random.default_rng(0)
     loss = None
-    for step in range(a.steps):
+    first = student.training_step() if a.resume and student.load_training_state(a.student) else 0
+    for step in range(first, a.steps):
         x = data.next()[0] if data else generate_wave_batch(a.batch_size, a.num_samples)[0].astype(np.float32)
         encoding = student.encode(sess, x, None)                                          # student.py:95
         noise = rng.logistic(0, 1, (a.batch_size, a.num_samples)).astype(np.float32)      # student.py:100
@@ -56,9 +61,12 @@ def main(argv=None):
         if step % a.print_steps == 0:
             entropy = student.getEntropy_fast(sess, noise, encoding, None)
             print("Step: {:6d} | Entropy: {} | Power Loss: {:.4f} | Total Loss: {:.4f}".format(step, entropy, power_loss, loss), flush=True)
-        student.save(sess, a.student, step, force=False)
+        if student.save(sess, a.student, step, force=False) and a.resume:
+            student.save_training_state(a.student, step)
     student.save(sess, a.student, a.steps - 1, force=True)
-    return float(loss)
+    if a.resume:
+        student.save_training_state(a.student, a.steps - 1)
+    return None if loss is None else float(loss)
 
 
 def fit_loop(a, student):
@@ -74,6 +82,8 @@ def fit_loop(a, student):
     sampler = data.distill_sampler(a.batch_size, a.num_samples, seed=0)
     print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)
     loss, step = None, 0
+    if a.resume and student.load_training_state(a.student, sampler=sampler):
+        step = sampler.step                          # the sampler continues its sequence where the saved run stopped
     while step < a.steps:
         n = min(a.print_steps, a.steps - step)
         losses, power = student.fit(sampler, n)
@@ -81,9 +91,12 @@ def fit_loop(a, student):
         loss = losses[-1]
         entropy = sampler.entropies(sampler.step - 1, 1)[0]
         print("Step: {:6d} | Entropy: {} | Power Loss: {:.4f} | Total Loss: {:.4f}".format(step - 1, entropy, power[-1], loss), flush=True)
-        student.save(None, a.student, step - 1, force=False)
+        if student.save(None, a.student, step - 1, force=False) and a.resume:
+            student.save_training_state(a.student, step - 1, sampler=sampler)
     student.save(None, a.student, a.steps - 1, force=True)
-    return float(loss)
+    if a.resume:
+        student.save_training_state(a.student, a.steps - 1, sampler=sampler)
+    return None if loss is None else float(loss)
 
 
 if __name__ == "__main__":

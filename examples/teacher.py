@@ -35,25 +35,33 @@ def main(argv=None):
     p.add_argument("--device-data", action="store_true",
                    help="keep the clips on the device and draw every batch inside the training step (model.fit)")
     p.add_argument("--device-clips", type=int, default=256, help="--device-data without --tfrecord: synthetic waves to hold")
+    import importlib
+    O = importlib.import_module("sr-wavenet_amd.optim")
+    O.add_control_flags(p)
     a = p.parse_args(argv)
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     data = NsynthDataReader(a.tfrecord, a.batch_size, a.num_samples, audio_max_length=a.audio_max_length) if a.tfrecord else None
     teacher = WaveNetAutoEncoder(input_size=a.num_samples, condition_size=0, num_mixtures=5, dilations=dilations,
                                  latent_channels=a.latent_channels, skip_channels=128, pool_stride=a.pool_stride,
                                  learning_rate=1e-4)                                     # teacher.py:61
+    O.apply_control_flags(teacher, a, 1e-4, a.steps)
     teacher.load(a.teacher)
     if a.device_data:
         return fit_loop(a, teacher)
     loss = None
-    for step in range(a.steps):
+    first = teacher.training_step() if a.resume and teacher.load_training_state(a.teacher) else 0
+    for step in range(first, a.steps):
         x = data.next()[0] if data else generate_wave_batch(a.batch_size, a.num_samples)[0].astype(np.float32)
         loss = teacher.train(x, None)                                                     # teacher.py:78
         if step % a.print_steps == 0:
             regen = teacher.reconstruct(x, None); enc = teacher.encode(x, None)           # teacher.py:83-84
             print(step, float(loss), "reconstruction rms %.3f" % float(np.sqrt(np.mean(regen ** 2))), "encoding", enc.shape, flush=True)
-        teacher.save(a.teacher, step, force=False)                                        # once per minute, teacher.py:110
+        if teacher.save(a.teacher, step, force=False) and a.resume:                       # once per minute, teacher.py:110
+            teacher.save_training_state(a.teacher, step)
     teacher.save(a.teacher, a.steps - 1, force=True)
-    return float(loss)
+    if a.resume:
+        teacher.save_training_state(a.teacher, a.steps - 1)
+    return None if loss is None else float(loss)
 
 
 def fit_loop(a, teacher):
@@ -68,6 +76,8 @@ def fit_loop(a, teacher):
     sampler = data.sampler(a.batch_size, a.num_samples, seed=0)
     print("%d clips of %d samples on the device (%.1f MB)" % (len(data), data.clip_len, data.nbytes / 1e6), flush=True)
     loss, step = None, 0
+    if a.resume and teacher.load_training_state(a.teacher, sampler=sampler):
+        step = sampler.step                          # the sampler continues its sequence where the saved run stopped
     while step < a.steps:
         n = min(a.print_steps, a.steps - step)
         loss = teacher.fit(sampler, n)[-1]
@@ -75,9 +85,12 @@ def fit_loop(a, teacher):
         x = data.audio[sampler.indices.long(), :a.num_samples].cpu().numpy()      # the last batch drawn ("head" crop)
         regen = teacher.reconstruct(x, None); enc = teacher.encode(x, None)
         print(step - 1, float(loss), "reconstruction rms %.3f" % float(np.sqrt(np.mean(regen ** 2))), "encoding", enc.shape, flush=True)
-        teacher.save(a.teacher, step - 1, force=False)
+        if teacher.save(a.teacher, step - 1, force=False) and a.resume:
+            teacher.save_training_state(a.teacher, step - 1, sampler=sampler)
     teacher.save(a.teacher, a.steps - 1, force=True)
-    return float(loss)
+    if a.resume:
+        teacher.save_training_state(a.teacher, a.steps - 1, sampler=sampler)
+    return None if loss is None else float(loss)
 
 
 if __name__ == "__main__":

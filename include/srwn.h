@@ -1726,6 +1726,28 @@ int srwn_pair_sweep(const float* slots_emb, const int32_t* labels, const int64_t
                     int32_t* rank_same, float* nearest_dist, float* same_dist, int64_t* hist_same, int64_t* hist_diff,
                     float* dist, void* stream);
 
+/* ---- training controls (since srwn_version() 126; csrc/srwn_opt.hip): the update of srwn_adam_step / srwn_adam_step_scaled
+ * with the learning rate read from a device table, the clip factor from device memory and an exponential moving average of
+ * the parameters kept in the same pass.
+ *   ctl           float32 [H][2] = {lr, ema_decay} per step, in device memory
+ *   ctl_len       int32 [1] in device memory: H.  The launch reads it, so a table and a length rewritten in place steer a
+ *                 captured graph without a new capture.  H is held to [1, ctl_capacity]
+ *   ctl_capacity  the rows allocated behind ctl (host): no row at or past it is ever read
+ *   ema           NULL, or float32 [n]: the shadow
+ *   grad_scale_dev NULL, or the clip factor of srwn_clip_scale: g = grads * (grad_scale * grad_scale_dev[0])
+ *   tick          as for srwn_adam_step_scaled; t below is the count after the tick (the count itself where tick = 0)
+ * Rule, with row = min(t - 1, H - 1) (0 where t = 0):
+ *   lr_t = (float)((double)ctl[row][0] * sqrt(1 - b2^t) / (1 - b1^t));
+ *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  params -= lr_t * m / (sqrt(v) + eps)      (the bits of srwn_adam_step at
+ *   lr = ctl[row][0])
+ *   and where ema is given, tf's assign_moving_average on the parameter just written, as three separately rounded fp32
+ *   operations in this order:  s = 1.0f - ctl[row][1];  diff = ema - params;  p = s * diff;  ema = ema - p
+ * params, m and v do not depend on whether ema is given.  Errors, before any launch: a null params, grads, m, v, step, ctl
+ * or ctl_len (-3); n < 0 or ctl_capacity < 1 (-2).  n == 0 returns 0. */
+int srwn_adam_step_ctl(float* params, const float* grads, float* m, float* v, float* ema, int64_t n, int64_t* step,
+                       const float* ctl, const int32_t* ctl_len, int32_t ctl_capacity, float beta1, float beta2, float eps,
+                       float grad_scale, const float* grad_scale_dev, int32_t tick, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -312,9 +312,11 @@ SIGNATURES["srwn_eval_classes"] = (C.c_int, [_p, _p, _p, _p, _i32, _i32, _i32, _
 # pass, and the all-pairs launch behind a sweep's last step
 SIGNATURES["srwn_embed_collect"] = (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p])
 SIGNATURES["srwn_pair_sweep"] = (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p])
+# training controls (srwn_version() 126): the Adam update with lr and EMA decay from a device table, the shadow in the same pass
+SIGNATURES["srwn_adam_step_ctl"] = (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _i32, _p])
 
 _lib = None
-BINDING = None      # "pybind11" or "ctypes" once loaded
+BINDING = None     # "pybind11" or "ctypes" once loaded
 
 
 def signature_hash() -> str:

@@ -368,7 +368,10 @@ def _is_tensor(x) -> bool:
 
 class BatchSampler(object):
     """The draws of one training run on a ``DeviceDataset``.  Owns the device state ``{seed, step}`` (int64 [2]), the
-    loss ring of ``log_capacity`` floats and the ``[batch_size]`` int32 indices of the last draw."""
+    loss ring of ``log_capacity`` floats and the ``[batch_size]`` int32 indices of the last draw.  A draw is a function of
+    ``(seed, step)`` alone, so a resumed sampler continues its sequence: ``seek(step)`` on a sampler built with the saved
+    seed -- what a model's ``load_training_state(logdir, sampler=...)`` does -- draws the batches the stopped run would
+    have drawn next."""
 
     def __init__(self, dataset, batch_size, num_samples, seed=0, shuffle=True, crop="head", rank=0, world=1,
                  log_capacity=1024):

@@ -30,7 +30,7 @@ from . import kernels as K
 from . import packing as P
 from . import _lib
 from ._lib import call
-from .engine import Section, StackConfig, WaveNetEngine
+from .engine import OptControls, Section, StackConfig, WaveNetEngine, adam_update, swap_with_ema
 from .audio_ring import AudioRingSlots
 
 # What SRWN_ENC_FUSED means when it is not set (FrameEncoder in bf16): "0" the layer-by-layer twin, "1" the one-launch
@@ -210,6 +210,8 @@ class EncoderStack(_EncoderParams):
         self.rows_c = self.B * self.frames
         self.EC, self.S, self.lat, self.Kw = encoder_channels, skip_channels, latent_channels, filter_width
         self.dt, self.dev, self.lr = dtype, torch.device(device), learning_rate
+        self.ctl = OptControls()      # training controls (optim.TrainControls) of this parameter buffer
+        self.ctl.engines.add(self)
         self._build_params(seed)
         self._build_packing()
         self._alloc()
@@ -226,10 +228,12 @@ class EncoderStack(_EncoderParams):
     def init_parameters(self, seed: int):
         self._init_host(seed)
         self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
+        self.ctl.reset_ema(self.params)
 
     def load_oracle_params(self, ep):
         self._oracle_host(ep)
         self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
+        self.ctl.reset_ema(self.params)
         self.repack()
 
     # -- MFMA weight images --------------------------------------------------------------------------
@@ -410,8 +414,36 @@ class EncoderStack(_EncoderParams):
         K.init_conv_wgrad(self.xr, self.dpre[0].view(B, T, EC), v("nc_w", g).reshape(-1), v("nc_b", g), Kw,
                           -(Kw - 1) + (Kw - 1) // 2, self.ic_ws)
 
-    def optimizer_step(self, grad_scale: float = 1.0):
-        K.adam_step(self.params, self.grads, self.adam_m, self.adam_v, self.adam_step, self.lr, grad_scale=grad_scale)
+    def optimizer_step(self, grad_scale: float = 1.0, joint_clip: bool = False):
+        self._adam_update(grad_scale, joint_clip)
+        self.repack()
+
+    def _adam_update(self, grad_scale: float, joint_clip: bool = False):
+        """As ``WaveNetEngine._adam_update``: srwn_adam_step without controls; with them [srwn_sumsq -> srwn_clip_scale ->]
+        srwn_adam_step_ctl, the two clip launches left to the owner of a joint norm (`joint_clip`)."""
+        c = self.ctl
+        if c.controls is not None and c.clip is not None:
+            if not joint_clip:
+                K.sumsq(self.grads, c.sq_parts)
+                K.clip_scale(c.sq_parts, c.controls.clip_norm, grad_scale, c.clip)
+            grad_scale = 1.0
+        adam_update(c, self.params, self.grads, self.adam_m, self.adam_v, self.adam_step, self.lr, grad_scale, c.clip)
+
+    # -- training controls (optim.py), as WaveNetEngine's -------------------------------------------------
+    @property
+    def clip(self):
+        return self.ctl.clip
+
+    @property
+    def ema(self):
+        return self.ctl.ema
+
+    def set_controls(self, controls):
+        if self.ctl.set(controls, self.params):
+            self.ctl.drop_graphs()
+
+    def swap_ema(self):
+        swap_with_ema(self.ctl, self.params)
         self.repack()
 
 
@@ -432,6 +464,8 @@ class AutoEncoderEngine:
         self.lat, self.cs = latent_channels, condition_size
         self.denc = torch.zeros((self.enc.rows_c, self.lat), dtype=torch.float32, device=self.dec.dev)
         self.loss = self.dec.loss
+        self._sq_parts = None      # training controls with clipping: the partials of ONE norm over both gradient buffers
+        self.dec.ctl.engines.add(self)      # (the graphs of train / fit hang on this object)
 
     def set_inputs(self, inputs: torch.Tensor, conditions: Optional[torch.Tensor] = None):
         d = self.dec
@@ -473,8 +507,39 @@ class AutoEncoderEngine:
         dp.allreduce_sum_(self.enc.grads, self.dec.pg)
 
     def optimizer_step(self):
-        self.dec.optimizer_step()      # the mixture loss is a SUM over batch and time: shard gradients add
-        self.enc.optimizer_step(1.0)
+        d, e = self.dec, self.enc
+        joint = d.ctl.controls is not None and d.ctl.clip is not None
+        if joint:       # tf.clip_by_global_norm over the encoder's and the decoder's gradients: one norm, one factor
+            pd = K.sumsq_partials(d.nparams)
+            K.sumsq(d.grads, self._sq_parts[:pd])
+            K.sumsq(e.grads, self._sq_parts[pd:])
+            K.clip_scale(self._sq_parts, d.ctl.controls.clip_norm, 1.0, d.ctl.clip)
+        d._adam_update(joint)      # the mixture loss is a SUM over batch and time: shard gradients add
+        d.repack()
+        e.optimizer_step(1.0, joint)
+
+    # -- training controls (optim.py): both buffers follow one table; each keeps its step counter and its shadow ------
+    @property
+    def clip(self):
+        return self.dec.ctl.clip
+
+    def set_controls(self, controls):
+        d, e = self.dec, self.enc
+        drop = d.ctl.set(controls, d.params)
+        drop = e.ctl.set(controls, e.params) or drop
+        if controls is not None and controls.clip_norm is not None:
+            if self._sq_parts is None:
+                self._sq_parts = torch.zeros(K.sumsq_partials(d.nparams) + K.sumsq_partials(e.nparams),
+                                             dtype=torch.float32, device=d.dev)
+            e.ctl.clip = d.ctl.clip
+        else:
+            self._sq_parts = None
+        if drop:
+            d.ctl.drop_graphs()
+
+    def swap_ema(self):
+        self.dec.swap_ema()
+        self.enc.swap_ema()
 
     def train_step(self):
         self.forward()

@@ -70,6 +70,90 @@ class Section:
         self.numel = int(np.prod(shape))
 
 
+class OptControls:
+    """The device side of ``optim.TrainControls`` for one flat parameter buffer, shared by every engine that shares the
+    buffer (``share_from``): the control table float32 [capacity, 2] = {lr, ema_decay} and its length int32 [1] that
+    ``srwn_adam_step_ctl`` reads, the EMA shadow (flat fp32 like ``params``) with the scratch buffer of its swap, the
+    partials of the gradient norm and ``clip`` float32 [2] = {last clip factor, last norm}.  ``controls is None``: no
+    controls, the optimizer runs the launches it ran before there were any."""
+
+    def __init__(self):
+        import weakref
+        self.controls = None
+        self.table = self.length = self.ema = self.scratch = self.sq_parts = self.clip = None
+        self.swapped = False
+        self.engines = weakref.WeakSet()      # whose captured graphs hold the launch list these controls decide
+
+    def set(self, controls, params: torch.Tensor) -> bool:
+        """Installs `controls` (or None).  The same features and bound within the allocated table: the table and its length are
+        rewritten in place, captured graphs follow them, returns False.  Anything else re-allocates and returns True:
+        the launch list has changed.  The shadow is set to the parameters when the EMA is switched on and kept while it
+        stays on."""
+        if self.swapped:
+            raise RuntimeError("set_controls inside ema_weights(): the parameters and the EMA shadow are swapped")
+        old = self.controls
+        if controls is None:
+            self.controls = None
+            self.table = self.length = self.ema = self.scratch = self.sq_parts = self.clip = None
+            return old is not None
+        tab = torch.from_numpy(controls.table())
+        if old is not None and old.features == controls.features and old.clip_norm == controls.clip_norm and \
+                controls.horizon <= self.table.shape[0]:      # (clip_norm is a host scalar of srwn_clip_scale)
+            self.table[:controls.horizon].copy_(tab)
+            self.length.fill_(controls.horizon)
+            self.controls = controls
+            return False
+        dev = params.device
+        self.table, self.length = tab.to(dev), torch.full((1,), controls.horizon, dtype=torch.int32, device=dev)
+        clip, ema = controls.features
+        self.clip = torch.zeros(2, dtype=torch.float32, device=dev) if clip else None
+        self.sq_parts = torch.zeros(K.sumsq_partials(params.numel()), dtype=torch.float32, device=dev) if clip else None
+        if ema and self.ema is None:
+            self.ema, self.scratch = params.clone(), torch.empty_like(params)
+        elif not ema:
+            self.ema = self.scratch = None
+        self.controls = controls
+        return True
+
+    def reset_ema(self, params: torch.Tensor):
+        """The shadow follows parameters that were set from outside (load, init_parameters)."""
+        if self.ema is not None:
+            if self.swapped:
+                raise RuntimeError("the parameters were replaced inside ema_weights()")
+            self.ema.copy_(params)
+
+    def drop_graphs(self):
+        for e in list(self.engines):
+            e._graph_ready, e._fit_state = False, None
+
+
+def adam_update(ctl: OptControls, params, grads, m, v, step, lr: float, grad_scale: float = 1.0, scale_dev=None):
+    """The one update launch every optimizer of the package goes through.  No controls: srwn_adam_step at the fixed rate
+    `lr` (srwn_adam_step_scaled where the gradient scale `scale_dev` is on the device), the launches from before there
+    were controls.  Controls: srwn_adam_step_ctl -- the step's learning rate and EMA decay from the device table, the
+    gradient scale ``grad_scale * scale_dev[0]``, the EMA shadow in the same pass."""
+    if ctl.controls is None:
+        if scale_dev is None:
+            K.adam_step(params, grads, m, v, step, lr, grad_scale=grad_scale)
+        else:
+            K.adam_step_scaled(params, grads, m, v, step, lr, scale_dev, True)
+        return
+    if ctl.swapped:
+        raise RuntimeError("optimizer_step inside ema_weights(): the parameters and the EMA shadow are swapped")
+    K.adam_step_ctl(params, grads, m, v, step, ctl.table, ctl.length, ema=ctl.ema, scale_dev=scale_dev, tick=True,
+                    grad_scale=grad_scale)
+
+
+def swap_with_ema(ctl: OptControls, params):
+    """Exchanges the CONTENTS of `params` and the shadow through the scratch buffer: three copies on the current stream."""
+    if ctl.ema is None:
+        raise ValueError("swap_ema: no EMA weights (set_controls with an ema_decay)")
+    ctl.scratch.copy_(params)
+    params.copy_(ctl.ema)
+    ctl.ema.copy_(ctl.scratch)
+    ctl.swapped = not ctl.swapped
+
+
 def _os_environ_flag(name: str, default: bool) -> bool:
     import os
     return os.environ.get(name, "1" if default else "0") != "0"
@@ -613,6 +697,9 @@ class WaveNetEngine:
                 setattr(self, a, getattr(share_from, a))
             if self.E:
                 self.o_wc = share_from.o_wc
+        # training controls (optim.TrainControls): one holder per parameter buffer, shared like the Adam state
+        self.ctl = share_from.ctl if share_from is not None else OptControls()
+        self.ctl.engines.add(self)
         self._alloc_buffers()
         self.repack()
 
@@ -694,6 +781,7 @@ class WaveNetEngine:
         if not self.wavenet:
             self.dead_gate["WG"].copy_(wg)
         self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
+        self._reset_ema()
 
     def load_oracle_params(self, sp):
         """Copies an oracle ``StackParams`` (tests) into the flat buffer."""
@@ -717,6 +805,7 @@ class WaveNetEngine:
         put("head_w2", w2); put("head_b2", b2)
         self.params.copy_(host)
         self.adam_m.zero_(); self.adam_v.zero_(); self.adam_step.zero_()
+        self._reset_ema()
         self.repack()
 
     def named_tensors(self, buf: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
@@ -1634,11 +1723,59 @@ class WaveNetEngine:
         dp.allreduce_sum_(self.grads, self.pg)
 
     def optimizer_step(self):
+        self._adam_update()
+        self.repack()
+
+    def _adam_update(self, joint_clip: bool = False):
+        """The update launches.  No controls: srwn_adam_step at the configured rate.  Controls (``set_controls``):
+        [srwn_sumsq -> srwn_clip_scale ->] srwn_adam_step_ctl.  `joint_clip`: the owner of several buffers has left the
+        clip factor of their joint norm in ``self.clip`` already (encoder.AutoEncoderEngine)."""
         # mean losses: mean of shard gradients; the mixture-of-logistics loss is a SUM over batch and time
         # (ops.py:173-174), so shard gradients simply add
-        K.adam_step(self.params, self.grads, self.adam_m, self.adam_v, self.adam_step, self.cfg.learning_rate,
-                    grad_scale=1.0 if self.mol else 1.0 / self.world)
+        grad_scale = 1.0 if self.mol else 1.0 / self.world
+        c = self.ctl
+        if c.controls is not None and c.clip is not None:
+            if not joint_clip:      # the norm of the gradient Adam would use: behind the 1 / world of a mean loss
+                K.sumsq(self.grads, c.sq_parts)
+                K.clip_scale(c.sq_parts, c.controls.clip_norm, grad_scale, c.clip)
+            grad_scale = 1.0
+        adam_update(c, self.params, self.grads, self.adam_m, self.adam_v, self.adam_step, self.cfg.learning_rate,
+                    grad_scale, c.clip)
+
+    # ------------------------------------------------------------------------------------------
+    # training controls: learning-rate table, gradient clipping, EMA weights (optim.py)
+    # ------------------------------------------------------------------------------------------
+    @property
+    def clip(self) -> Optional[torch.Tensor]:
+        """float32 [2] on the device: the last step's clip factor (times the loss's 1 / world) and gradient norm; None
+        without clipping."""
+        return self.ctl.clip
+
+    @property
+    def ema(self) -> Optional[torch.Tensor]:
+        """The EMA shadow, flat fp32 like ``params`` (None without one).  Inside ``swap_ema`` it holds the raw weights."""
+        return self.ctl.ema
+
+    def set_controls(self, controls):
+        """Installs an ``optim.TrainControls`` (None: back to the fixed rate) for this engine and every engine sharing its
+        parameters.  The same features (clipping on / off and its bound, EMA on / off), a horizon inside the allocated table:
+        the table and its length are rewritten in place and captured graphs follow.  Any other change drops the captured graphs
+        of ``train`` and ``fit``; the usual rule captures them again."""
+        if self.ctl.set(controls, self.params):
+            self.ctl.drop_graphs()
+
+    def _reset_ema(self):
+        ctl = getattr(self, "ctl", None)      # (init_parameters runs before the holder exists)
+        if ctl is not None:
+            ctl.reset_ema(self.params)
+
+    def swap_ema(self):
+        """Exchanges the CONTENTS of ``params`` and the EMA shadow (the kernels read biases through views of ``params``,
+        so the pointers stay) through one scratch buffer, then rebuilds the weight images.  Three copies and two gathers
+        on the current stream: capturable.  Twice is the identity."""
+        swap_with_ema(self.ctl, self.params)
         self.repack()
+        self._repack_generation()
 
     def _allreduce_bucket_a(self):
         """Skip + head gradients: issued while the lower part of the backward pass runs."""

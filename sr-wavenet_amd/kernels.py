@@ -890,3 +890,24 @@ def adam_step_scaled(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor,
     _chk(step, "step", torch.int64, (1,)); _chk(scale_dev, "scale_dev", torch.float32)
     call("srwn_adam_step_scaled", params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(), n, step.data_ptr(),
          float(lr), float(beta1), float(beta2), float(eps), scale_dev.data_ptr(), int(bool(tick)), _stream())
+
+
+def adam_step_ctl(params: torch.Tensor, grads: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: torch.Tensor,
+                  ctl: torch.Tensor, ctl_len: torch.Tensor, ema: Optional[torch.Tensor] = None,
+                  scale_dev: Optional[torch.Tensor] = None, tick: bool = True, grad_scale: float = 1.0,
+                  beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """The Adam update under training controls (srwn_adam_step_ctl): lr and EMA decay of the step from row
+    min(t - 1, H - 1) of ``ctl`` float32 [capacity, 2], H from ``ctl_len`` int32 [1] (held to [1, capacity]); the gradient
+    scale is ``grad_scale * scale_dev[0]``; ``ema`` (the shadow) is updated in the same pass."""
+    n = params.numel()
+    for t, nm in ((params, "params"), (grads, "grads"), (m, "m"), (v, "v")):
+        _chk(t, nm, torch.float32, (n,))
+    _chk(step, "step", torch.int64, (1,))
+    _chk(ctl, "ctl", torch.float32); _chk(ctl_len, "ctl_len", torch.int32, (1,))
+    if ctl.dim() != 2 or ctl.shape[1] != 2 or ctl.shape[0] < 1:
+        raise ValueError("adam_step_ctl: ctl must be [H, 2] with H >= 1, got %s" % (tuple(ctl.shape),))
+    pe = _opt(ema, "ema", torch.float32, (n,))
+    ps = None if scale_dev is None else _chk(scale_dev, "scale_dev", torch.float32)
+    call("srwn_adam_step_ctl", params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(), pe, n, step.data_ptr(),
+         ctl.data_ptr(), ctl_len.data_ptr(), int(ctl.shape[0]), float(beta1), float(beta2), float(eps), float(grad_scale),
+         ps, int(bool(tick)), _stream())

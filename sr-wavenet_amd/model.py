@@ -320,7 +320,8 @@ def _read_state(logdir, params_fn):
         return False
     params = params_fn()
     if tfc.is_bundle(path):
-        arrays = tfc.read_bundle(path, names=list(params))       # Adam slots and counters in the file are ignored
+        arrays = tfc.read_bundle(path, names=list(params))       # Adam slots and counters in a TF bundle are ignored
+        #                                                            (this package's own: save_/load_training_state)
         get = lambda k: torch.from_numpy(arrays[k])
     else:
         state = torch.load(path, weights_only=True)
@@ -333,7 +334,154 @@ def _read_state(logdir, params_fn):
     return True
 
 
-class _EngineOwner:
+# --- training controls (optim.py) ----------------------------------------------------------------------------------
+class _TrainingControls:
+    """What the five trainable models share: ``set_training_controls``, ``ema_weights``, ``save_training_state`` /
+    ``load_training_state``.  A model says where its optimizers live: ``_control_engine()`` -- the engine whose
+    ``set_controls`` / ``swap_ema`` reach every parameter buffer of the model (built on first use) -- and
+    ``_optimizers()``, name -> (engine, params, m, v, step, controls holder)."""
+    _controls = None          # the optim.TrainControls in force (class defaults: objects made without __init__ have none)
+    _in_ema = False
+
+    def set_training_controls(self, schedule=None, horizon=None, clip_norm=None, ema_decay=None, ema_warmup=True,
+                              validate_ema=False):
+        """Learning-rate schedule, gradient clipping and EMA weights for ``train`` and ``fit``, for every engine of the model,
+        present and future.  `schedule`: a schedule of ``optim`` (or any ``f(step) -> lr`` of the 0-based step, or a
+        number); None keeps the constructor's learning_rate, constant.  `horizon`: the steps the device table holds (later
+        steps keep its last row; default 1).  `clip_norm`: tf.clip_by_global_norm's bound.  `ema_decay` in [0, 1): keep an
+        exponential moving average of the weights (`ema_warmup`: tf's ``min(decay, (1 + t) / (10 + t))``), which
+        ``ema_weights()`` serves and, with `validate_ema`, the sweeps of ``fit(..., validate=...)`` judge.  Calling it with
+        no argument removes the controls.  The same features within the allocated horizon rewrite the device table in
+        place and captured graphs follow; anything else captures ``train`` and ``fit`` again."""
+        from .optim import TrainControls
+        if self._in_ema:
+            raise RuntimeError("set_training_controls inside ema_weights()")
+        if schedule is None and horizon is None and clip_norm is None and ema_decay is None:
+            controls = None
+            if validate_ema:
+                raise ValueError("validate_ema needs ema_decay")
+        else:
+            controls = TrainControls(self._learning_rate() if schedule is None else schedule,
+                                     1 if horizon is None else horizon, clip_norm, ema_decay, ema_warmup, validate_ema)
+        self._controls = controls
+        eng = self._control_engine(build=False)
+        if eng is not None:
+            eng.set_controls(controls)
+        return controls
+
+    def _apply_controls(self, eng):
+        """A model's first engine, just built: the controls set before it existed."""
+        if self._controls is not None:
+            eng.set_controls(self._controls)
+
+    def _refuse_in_ema(self, what):
+        if self._in_ema:
+            raise RuntimeError("%s inside ema_weights(): the parameters hold the averaged weights; leave the context to "
+                               "train" % what)
+
+    def _validate_ema(self):
+        return self._controls is not None and self._controls.validate_ema
+
+    def ema_weights(self):
+        """A context in which the model's parameters ARE the averaged weights: ``swap_ema()`` on entry and again on exit.
+        Everything that reads the parameters inside it -- predict, evaluate, generate, stream, generation_pool, encode,
+        reconstruct, get_embedding, save, and the snapshots recognizer(), embedder(), synthesizer(), inverter(), scorer()
+        take -- serves the average; ``train`` / ``fit`` raise RuntimeError.  ValueError without an EMA."""
+        if self._controls is None or self._controls.ema_decay is None:
+            raise ValueError("ema_weights: this model keeps no EMA weights (set_training_controls(ema_decay=...))")
+        if self._in_ema:
+            raise RuntimeError("ema_weights: already inside the context")
+        return _EmaContext(self)
+
+    def training_step(self) -> int:
+        """Adam's step count (of the model's first optimizer): the steps trained so far, where a resumed run goes on."""
+        return int(next(iter(self._optimizers().values()))[4].item())
+
+    # --- optimizer state next to the checkpoint ------------------------------------------------------------
+    def save_training_state(self, logdir, global_step, sampler=None):
+        """What ``save`` leaves out and a resumed run needs: Adam's m, v and step of every optimizer of the model, the EMA
+        shadow, the controls' scalar settings and -- given a sampler -- its {seed, step}, as ``train_state-N.pt`` named in
+        a ``train_state`` file the way ``checkpoint`` names the weights.  ``save`` and its files do not change."""
+        self._refuse_in_ema("save_training_state")
+        opts = {}
+        for name, (eng, params, m, v, step, ctl) in self._optimizers().items():
+            opts[name] = {"m": m.detach().cpu().clone(), "v": v.detach().cpu().clone(), "step": int(step.item()),
+                          "ema": None if ctl.ema is None else ctl.ema.detach().cpu().clone()}
+        state = {"optimizers": opts, "controls": None if self._controls is None else self._controls.scalars(),
+                 "sampler": None if sampler is None else {"seed": int(sampler.seed), "step": int(sampler.step)}}
+        os.makedirs(logdir, exist_ok=True)
+        name = "train_state-%d.pt" % int(global_step)
+        torch.save(state, os.path.join(logdir, name))
+        with open(os.path.join(logdir, "train_state"), "w") as f:
+            f.write('train_state_path: "%s"\n' % name)
+
+    def load_training_state(self, logdir, sampler=None):
+        """Restores what ``save_training_state`` wrote; after ``load`` it resumes the run exactly -- call
+        ``set_training_controls`` first as the saved run did (a schedule is code: the file holds the scalar settings and
+        checks clip_norm, ema_decay and ema_warmup; the horizon may grow).  Given a sampler built like the saved one, it continues its sequence at the saved step.  Returns
+        False without a state file; ValueError where shapes or settings do not match."""
+        self._refuse_in_ema("load_training_state")
+        idx = os.path.join(logdir, "train_state")
+        if not os.path.exists(idx):
+            return False
+        import re
+        m_ = re.search(r'train_state_path: "([^"]+)"', open(idx).read())
+        path = os.path.join(logdir, m_.group(1)) if m_ else None
+        if path is None or not os.path.exists(path):
+            print("Could not find training state at %s" % path)
+            return False
+        state = torch.load(path, weights_only=True)
+        have = None if self._controls is None else self._controls.scalars()
+        # (what shapes the state: clipping and the shadow.  A resumed run may extend its horizon or judge other weights.)
+        drop = lambda c: None if c is None else {k: v for k, v in c.items() if k not in ("validate_ema", "horizon")}
+        if drop(state["controls"]) != drop(have):
+            raise ValueError("the training state was saved under controls %r, this model has %r: call "
+                             "set_training_controls as the saved run did" % (state["controls"], have))
+        opts = self._optimizers()
+        if set(opts) != set(state["optimizers"]):
+            raise ValueError("the training state holds optimizers %s, the model has %s"
+                             % (sorted(state["optimizers"]), sorted(opts)))
+        for name, (eng, params, m, v, step, ctl) in opts.items():       # check everything before anything is written
+            o = state["optimizers"][name]
+            for k, dst in (("m", m), ("v", v), ("ema", ctl.ema)):
+                if (o[k] is None) != (dst is None) or (dst is not None and tuple(o[k].shape) != tuple(dst.shape)):
+                    raise ValueError("training state %s.%s has shape %s, the model's is %s"
+                                     % (name, k, None if o[k] is None else tuple(o[k].shape),
+                                        None if dst is None else tuple(dst.shape)))
+        if sampler is not None:
+            if state["sampler"] is None:
+                raise ValueError("the training state holds no sampler state")
+            if int(state["sampler"]["seed"]) != int(sampler.seed):
+                raise ValueError("the training state's sampler was seeded %d, this one %d"
+                                 % (state["sampler"]["seed"], sampler.seed))
+        for name, (eng, params, m, v, step, ctl) in opts.items():
+            o = state["optimizers"][name]
+            m.copy_(o["m"]); v.copy_(o["v"]); step.fill_(int(o["step"]))
+            if ctl.ema is not None:
+                ctl.ema.copy_(o["ema"])
+        if sampler is not None:
+            sampler.seek(int(state["sampler"]["step"]))
+        return True
+
+
+class _EmaContext:
+    def __init__(self, model):
+        self.model = model
+
+    def __enter__(self):
+        m = self.model
+        m._control_engine().swap_ema()
+        m._in_ema = True
+        return m
+
+    def __exit__(self, *exc):
+        m = self.model
+        m._control_engine().swap_ema()
+        m._in_ema = False
+        return False
+
+
+class _EngineOwner(_TrainingControls):
     """Builds one engine per (batch, length) seen, all sharing the same parameters."""
 
     def _setup(self, cfg: StackConfig, seed: int):
@@ -351,8 +499,22 @@ class _EngineOwner:
             eng = WaveNetEngine(self._cfg, B, T, "cuda", seed=self._seed, share_from=self._primary)
             if self._primary is None:
                 self._primary = eng
+                self._apply_controls(eng)
             self._engines[key] = eng
         return eng
+
+    def _learning_rate(self):
+        return self._cfg.learning_rate
+
+    def _control_engine(self, build=True):
+        """The first engine: its controls, EMA shadow and weight images are shared by every other (``share_from``)."""
+        if self._primary is None and build:
+            self._engine(1, self._default_length)
+        return self._primary
+
+    def _optimizers(self):
+        e = self._control_engine()
+        return {"stack": (e, e.params, e.adam_m, e.adam_v, e.adam_step, e.ctl)}
 
     @property
     def network_params(self):
@@ -372,6 +534,7 @@ class _EngineOwner:
     def load(self, logdir):
         ok = _read_state(logdir, lambda: self.network_params)
         if ok:
+            self._primary._reset_ema()      # (an EMA shadow restarts from the loaded weights: load_training_state has the saved one)
             self._primary.repack()
             print("Restoring previous session")
         return ok
@@ -416,6 +579,7 @@ class WaveNet(_EngineOwner):
         return eng
 
     def train(self, inputs, targets):
+        self._refuse_in_ema("train")
         eng = self._stage(inputs, targets)
         _train_step(eng)
         return np.float32(eng.loss.item())
@@ -429,8 +593,10 @@ class WaveNet(_EngineOwner):
         graph of its own between the training graph's.  Each sweep lands in the next of the sampler's result slots, so
         the host does not wait per sweep: the slots are read when ``sweep_capacity`` of them are full and at the end.
         Returns ``(losses, [EvalResult, ...])`` then, every result with the ``step`` it was taken at.  The training run's
-        bits are the ones without validation."""
+        bits are the ones without validation.  Under ``set_training_controls(..., validate_ema=True)`` every sweep runs on
+        the EMA weights (``swap_ema`` in front of it and behind it, enqueued like the sweep itself)."""
         from .dataset import EvalSampler
+        self._refuse_in_ema("fit")
         if isinstance(sampler, EvalSampler):
             raise TypeError("WaveNet.fit: an EvalSampler sweeps a held-out set; train on dataset.sampler(...)")
         if sampler.num_samples != self.input_size:
@@ -454,7 +620,11 @@ class WaveNet(_EngineOwner):
             if sampler.step % every == 0:
                 if len(pending) >= ev.sweep_capacity:
                     drain()
+                if self._validate_ema():         # the sweep judges the averaged weights: swapped in and out on its stream
+                    eng.swap_ema()
                 _eval_sweep(eng_v, ev)
+                if self._validate_ema():
+                    eng.swap_ema()
                 pending.append((ev.sweep - 1, sampler.step))
 
         losses = _fit(eng, sampler, steps, dict(audio=eng.audio, onehot=eng.labels), after_step=after_step)[0]
@@ -941,6 +1111,7 @@ class WaveNetTeacher(_EngineOwner):
         return eng
 
     def train(self, inputs, encoding=None, conditions=None):
+        self._refuse_in_ema("train")
         eng = self._stage(inputs, encoding, conditions)
         _train_step(eng)
         return np.float32(eng.loss.item())
@@ -949,6 +1120,7 @@ class WaveNetTeacher(_EngineOwner):
         """``steps`` training steps on batches a ``dataset.BatchSampler`` draws on the device (with the softmax head the
         draw writes the mu-law targets too); returns every step's loss, float32 [steps].  See ``_fit``.  The unconditioned
         teacher only: a conditioned teacher's encoding comes from another model."""
+        self._refuse_in_ema("fit")
         if self.use_encoding:
             raise NotImplementedError("WaveNetTeacher.fit: this teacher was built with use_encoding=True and its encoding "
                                       "comes from another model; feed it with train(inputs, encoding, conditions)")
@@ -1270,7 +1442,7 @@ class GenerationPool(_PoolFace):
         return _ran_dict(a, ran, range(self._pool.capacity))
 
 
-class WaveNetAutoEncoder(object):
+class WaveNetAutoEncoder(_TrainingControls):
     """model.py:75-285 on ``encoder.AutoEncoderEngine``: the non-causal encoder (ResidualDilationLayerNC chain,
     skip sum -> latent 1x1 -> average pool) and the conditioned mixture-of-logistics decoder, trained jointly on
     ``discretized_mix_logistic_loss(inputs, logits)`` (model.py:103,114,116).
@@ -1314,6 +1486,7 @@ class WaveNetAutoEncoder(object):
         if self._eng is None:
             self._eng = AutoEncoderEngine(self._cfg, B, T, self.encoder_channels, self.latent_channels,
                                           self.condition_size, "cuda", seed=self._seed)
+            self._apply_controls(self._eng)
         elif (self._eng.B, self._eng.T) != (int(B), int(T)):
             raise NotImplementedError("WaveNetAutoEncoder: one (batch, length) per model object for now; built for "
                                       "%s, got %s" % ((self._eng.B, self._eng.T), (B, T)))
@@ -1356,6 +1529,19 @@ class WaveNetAutoEncoder(object):
              out.data_ptr(), d.N, torch.cuda.current_stream().cuda_stream)
         return out.view(eng.B, eng.T).cpu().numpy()
 
+    def _learning_rate(self):
+        return self._cfg.learning_rate
+
+    def _control_engine(self, build=True):
+        if self._eng is None and build:
+            self._engine(1, self.input_size)
+        return self._eng
+
+    def _optimizers(self):
+        """The decoder's and the encoder's: two buffers, two step counters, two shadows."""
+        eng = self._control_engine()
+        return {k: (e, e.params, e.adam_m, e.adam_v, e.adam_step, e.ctl) for k, e in (("decoder", eng.dec), ("encoder", eng.enc))}
+
     @property
     def network_params(self):
         eng = self._eng or self._engine(1, self.input_size)
@@ -1377,6 +1563,7 @@ class WaveNetAutoEncoder(object):
     def load(self, logdir):
         ok = _read_state(logdir, lambda: self.network_params)
         if ok:
+            self._eng.enc.ctl.reset_ema(self._eng.enc.params); self._eng.dec._reset_ema()
             self._eng.enc.repack(); self._eng.dec.repack()
             print("Restoring previous session")
         return ok
@@ -1393,6 +1580,7 @@ class WaveNetAutoEncoder(object):
         return m
 
     def train(self, inputs, conditions=None):
+        self._refuse_in_ema("train")
         eng = self._stage(inputs, conditions)
         _train_step(eng)
         return np.float32(eng.loss.item())
@@ -1400,6 +1588,7 @@ class WaveNetAutoEncoder(object):
     def fit(self, sampler, steps):
         """``steps`` training steps on batches a ``dataset.BatchSampler`` draws on the device; with condition_size > 0
         the labels' one-hot rows are the conditions.  Returns every step's loss, float32 [steps].  See ``_fit``."""
+        self._refuse_in_ema("fit")
         if self.condition_size > 0:
             _fit_labels(sampler, self.condition_size, "WaveNetAutoEncoder", "conditions")
         eng = self._engine(sampler.batch_size, sampler.num_samples)
@@ -2016,7 +2205,7 @@ class MolScorerStreamPool(_AudioPoolFace):
         return tuple(_host_dict(d) for d in out) if isinstance(out, tuple) else _host_dict(out)
 
 
-class ParallelWaveNet(object):
+class ParallelWaveNet(_TrainingControls):
     """model.py:290-656 on ``student.StudentEngine``: ``num_flows`` inverse-autoregressive flows distilled against a
     frozen mixture-of-logistics teacher.
 
@@ -2101,7 +2290,20 @@ class ParallelWaveNet(object):
                                 self.num_flows, alpha=a, beta=b, gamma=g, learning_rate=self._lr, seed=self._seed)
             self._primary = eng
             self._engines[key] = eng
+            self._apply_controls(eng)
         return eng
+
+    def _learning_rate(self):
+        return self._lr
+
+    def _control_engine(self, build=True):
+        if self._primary is None and build:
+            self._engine(1, self.input_size)
+        return self._primary
+
+    def _optimizers(self):
+        st = self._control_engine().storage
+        return {"flows": (self._primary, st.params, st.adam_m, st.adam_v, st.adam_step, self._primary.ctl)}
 
     def _stage(self, inputs, truth, encoding, conditions):
         z = torch.as_tensor(np.asarray(inputs, dtype=np.float32), device="cuda")
@@ -2164,6 +2366,7 @@ class ParallelWaveNet(object):
             self._teacher.load(self._teacher_dir)                                         # model.py:543-544
         ok = _read_state(logdir, lambda: self.network_params)
         if ok:
+            self._primary.ctl.reset_ema(self._primary.storage.params)
             for f in self._primary.flows:
                 f.repack()
             print("Restoring previous session")
@@ -2204,6 +2407,7 @@ class ParallelWaveNet(object):
         ``WaveNetAutoEncoder`` (object or directory).  Returns (loss [steps], power_loss [steps]), float32; the entropies
         are in the sampler's ring (``sampler.entropies``).  See ``_fit``."""
         from .dataset import DistillSampler
+        self._refuse_in_ema("fit")
         if not isinstance(sampler, DistillSampler):
             raise NotImplementedError("ParallelWaveNet.fit: a student step needs noise and teacher passes beside the clips; "
                                       "feed it with train(sess, inputs, truth, encoding, conditions)")
@@ -2274,6 +2478,7 @@ class ParallelWaveNet(object):
 
     def train_fast(self, sess, inputs, truth, encoding, conditions=None):
         """One distillation step (model.py:634-642): returns (loss, power_loss)."""
+        self._refuse_in_ema("train_fast")
         eng = self._stage(inputs, truth, encoding, conditions)
         _train_step(eng)
         l = eng.losses()
@@ -2282,6 +2487,7 @@ class ParallelWaveNet(object):
     def train(self, sess, inputs, truth, encoding, conditions=None):
         """The slow path (model.py:599-632): per-noise-row gradients, each clipped to norm 1, then averaged and
         applied; returns (mean loss, mean power loss).  student.py:107 trains with ``train_fast``."""
+        self._refuse_in_ema("train")
         eng = self._stage(inputs, truth, encoding, conditions)
         l, p = eng.train_per_sample()
         return np.float32(l), np.float32(p)
@@ -2900,6 +3106,7 @@ class SiameseWaveNet(_EngineOwner):
         validation.  Returns ``(loss, distance, [PairEvalResult, ...])`` then, every result with the ``step`` it was
         taken at."""
         from .dataset import EmbedSampler, PairSampler
+        self._refuse_in_ema("fit")
         if not isinstance(sampler, PairSampler):
             raise NotImplementedError("SiameseWaveNet.fit: a step needs pairs of clips and their labels; feed it with "
                                       "train(sess, inputs_left, inputs_right, labels)")
@@ -2923,7 +3130,11 @@ class SiameseWaveNet(_EngineOwner):
             if sampler.step % every == 0:
                 if len(pending) >= es.sweep_capacity:
                     drain()
+                if self._validate_ema():         # as WaveNet.fit: the sweep judges the averaged weights
+                    eng.swap_ema()
                 self._embed_sweep(eng_v, es)
+                if self._validate_ema():
+                    eng.swap_ema()
                 pending.append((es.sweep - 1, sampler.step))
 
         loss, dist = _fit(eng, sampler, steps, dict(audio=eng.audio, labels=eng.labels), after_step=after_step)
@@ -2970,6 +3181,7 @@ class SiameseWaveNet(_EngineOwner):
         return embed_sampler.result(embed_sampler.sweep - 1, step, bool(distances))      # the host waits here
 
     def train(self, sess, inputs_left, inputs_right, labels):
+        self._refuse_in_ema("train")
         x = self._pair(inputs_left, inputs_right)
         y = np.asarray(labels, dtype=np.float32).reshape(-1)
         if y.shape[0] != x.shape[0] // 2:

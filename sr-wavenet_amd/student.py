@@ -29,7 +29,7 @@ import torch
 from . import dp
 from . import kernels as K
 from ._lib import call
-from .engine import SQRT_HALF, Section, StackConfig, WaveNetEngine, _Span
+from .engine import SQRT_HALF, OptControls, Section, StackConfig, WaveNetEngine, _Span, adam_update, swap_with_ema
 from .slots import SlotTable, per_stream
 from .stream_stack import StreamStack, stream_history_rows      # (the latter for this module's users)
 
@@ -272,6 +272,8 @@ class StudentEngine:
         self.F = int(num_flows)
         per = FlowStack.param_count(replace(flow_cfg, head_mode="flow"))
         self.storage = FlowStorage(per * self.F, self.dev)
+        self.ctl = OptControls()      # training controls (optim.TrainControls) of the flows' one parameter buffer
+        self.ctl.engines.add(self)
         self.flows: List[FlowStack] = [FlowStack(flow_cfg, self.B, self.T, device=self.dev, seed=seed + 101 * i,
                                                  storage=self.storage, slot=i) for i in range(self.F)]
         B, T, N = self.B, self.T, self.N
@@ -361,8 +363,35 @@ class StudentEngine:
         parallelism the flat buffer holds the SUM of the ranks' (loss / local B) gradients -> mean, then clip."""
         st = self.storage
         K.sumsq(st.grads, self.sq_parts)
-        K.clip_scale(self.sq_parts, 1.0, 1.0 / self.world, self.clip)
-        K.adam_step_scaled(st.params, st.grads, st.adam_m, st.adam_v, st.adam_step, self.lr, self.clip, True)
+        K.clip_scale(self.sq_parts, self._clip_norm(), 1.0 / self.world, self.clip)
+        self._adam_update(1.0, self.clip)
+        for f in self.flows:
+            f.repack()
+
+    def _adam_update(self, grad_scale, scale_dev):
+        """The update launch of both training paths: srwn_adam_step(_scaled) at the fixed rate without controls,
+        srwn_adam_step_ctl with them (``engine.adam_update``)."""
+        st = self.storage
+        adam_update(self.ctl, st.params, st.grads, st.adam_m, st.adam_v, st.adam_step, self.lr, grad_scale, scale_dev)
+
+    def _clip_norm(self) -> float:
+        """The reference clips at 1.0 (model.py:385); controls with a clip_norm replace it."""
+        c = self.ctl.controls
+        return 1.0 if c is None or c.clip_norm is None else c.clip_norm
+
+    # -- training controls (optim.py) ----------------------------------------------------------------------
+    @property
+    def ema(self):
+        return self.ctl.ema
+
+    def set_controls(self, controls):
+        """As ``WaveNetEngine.set_controls``, for the flows' shared buffer.  The student always clips (``self.clip``
+        holds the factor and the norm): `clip_norm` None keeps the reference's 1.0, so clipping is no feature here."""
+        if self.ctl.set(controls, self.storage.params):
+            self.ctl.drop_graphs()
+
+    def swap_ema(self):
+        swap_with_ema(self.ctl, self.storage.params)
         for f in self.flows:
             f.repack()
 
@@ -392,7 +421,7 @@ class StudentEngine:
                 self.forward()
                 self.backward()
                 K.sumsq(st.grads, self.sq_parts)
-                K.clip_scale(self.sq_parts, 1.0, 1.0, self.clip)
+                K.clip_scale(self.sq_parts, self._clip_norm(), 1.0, self.clip)
                 call("srwn_axpy_dev", self._acc.data_ptr(), st.grads.data_ptr(), self.clip.data_ptr(), 1.0 / self.B,
                      st.grads.numel(), K._stream())
                 l = self.losses()
@@ -402,7 +431,7 @@ class StudentEngine:
             self.noise.copy_(self._noise_all)
         st.grads.copy_(self._acc)
         self.allreduce_grads()
-        K.adam_step(st.params, st.grads, st.adam_m, st.adam_v, st.adam_step, self.lr, grad_scale=1.0 / self.world)
+        self._adam_update(1.0 / self.world, None)
         for f in self.flows:
             f.repack()
         return float(np.mean(losses)), float(np.mean(powers))
