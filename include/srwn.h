@@ -84,7 +84,9 @@ int srwn_causal_conv1d_fwd(const float* x, const float* w, const float* bias, vo
  * workspace of srwn_init_conv_wgrad_partials(B,T,R,K) floats; result written (not accumulated).
  * gw = gb = NULL: only the per-slab partials are written -- partials[slab][(K+1)*R] = [gw | gb] of each slab of rows,
  * srwn_init_conv_wgrad_partials / ((K+1)*R) slabs -- for the caller to sum (the training step does it as one more job
- * of its srwn_reduce_partials_multi launch instead of a launch of its own). */
+ * of its srwn_reduce_partials_multi launch instead of a launch of its own).
+ * R in {32, 64, 128}; K <= 7: the first stage's reduction buffer takes 8192*(K+1) bytes of LDS whatever R, 64 KiB at
+ * K = 7.  K = 8 passes the shape check and is refused as SRWN_E_UNSUPPORTED at every R; K > 8: SRWN_E_SHAPE. */
 int64_t srwn_init_conv_wgrad_partials(int32_t B, int32_t T, int32_t R, int32_t K);
 int srwn_init_conv_wgrad(const float* audio, const void* g, float* partials, float* gw, float* gb, int32_t B,
                          int32_t T, int32_t R, int32_t K, int32_t shift, int32_t dtype, void* stream);

@@ -2,7 +2,8 @@
 
 Nothing in the reference pins these results: parity is "unpinned by the reference" and anchored on
 oracle (i) (NumPy fp64, np.fft STFT) == oracle (ii) (torch autograd, DFT-matrix STFT) -- tests/test_oracle.py.
-fp32 mode meets 1e-3 relative; bf16 rounds every stored activation and is judged loosely."""
+fp32 mode meets 1e-3 relative; bf16 rounds every stored activation and is judged loosely.
+The student's own kernels are held entry by entry, on exact designs, by tests/test_gpu_flow_entries.py."""
 import math
 
 import numpy as np
