@@ -523,6 +523,10 @@ class AutoEncoderEngine:
     def clip(self):
         return self.dec.ctl.clip
 
+    @property
+    def world(self):
+        return self.dec.world
+
     def set_controls(self, controls):
         d, e = self.dec, self.enc
         drop = d.ctl.set(controls, d.params)

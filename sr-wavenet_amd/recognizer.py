@@ -188,7 +188,7 @@ class StackWeights:
     def load(self, logdir, scope: str = "WaveNet") -> bool:
         """Fills the parameters from the checkpoint that `logdir`'s state file names (``WaveNet.save`` or the reference's
         tf.train.Saver wrote it), by the reference's variable names under `scope`."""
-        from .model import _read_state
+        from .training import _read_state
         ok = _read_state(logdir, lambda: self.tf_variables(scope))
         if ok:
             self.repack()

@@ -278,6 +278,44 @@ def test_train_and_fit_mix_on_one_model(host_fp32):
     _same(_params(m), host_fp32["p10"])
 
 
+def _three_ways(rounds=4):
+    """`rounds` rounds of {train(x) on a host batch, fit(sampler, 1), evaluate(eval_sampler)} on one classifier, all three
+    on its engine of shape (B, 64): (model, engine, train losses, fit losses, the EvalResults' arrays, parameters)."""
+    D = sub("dataset")
+    m, clips = _classifier(), _clips()
+    s = _sampler("classifier")
+    ev = D.DeviceDataset(clips, np.abs(LABELS) % NC, NC).eval_sampler(B, 64)
+    trained, fitted, swept = [], [], []
+    for r in range(rounds):
+        idx = (np.arange(B) + r) % N
+        trained.append(m.train(clips[idx, :64], _onehot(LABELS[idx], NC)))
+        fitted.append(m.fit(s, 1))
+        res = m.evaluate(ev)
+        swept.append([np.asarray(a) for a in (res.pred, res.rank, res.nll, res.confusion, res.owned)])
+    return (m, m._engine(B, 64), np.array(trained, np.float32), np.concatenate(fitted), swept, _params(m))
+
+
+def test_train_fit_and_evaluate_capture_each_their_own(monkeypatch):
+    """train(x), fit and evaluate interleaved on one engine: each counts its own two eager steps and captures graphs of its
+    own behind them, and every loss, every sweep's arrays and the final parameters are those of the same rounds under
+    SRWN_MODEL_GRAPHS=0, bit for bit."""
+    m, eng, trained, fitted, swept, params = _three_ways()
+    assert eng._graph_ready is True
+    assert eng._fit_state["graphs"] is not None and len(eng._fit_state["graphs"]) == 1
+    assert eng._eval_state["graph"] is not None
+    monkeypatch.setenv("SRWN_MODEL_GRAPHS", "0")
+    m0, eng0, trained0, fitted0, swept0, params0 = _three_ways()
+    assert not getattr(eng0, "_graph_ready", False)
+    assert eng0._fit_state["graphs"] is None and eng0._eval_state["graph"] is None
+    print("train", trained.tolist(), trained0.tolist(), "fit", fitted.tolist(), fitted0.tolist())
+    assert np.array_equal(trained.view(np.uint32), trained0.view(np.uint32))
+    assert fitted.shape == (4,) and np.array_equal(fitted.view(np.uint32), fitted0.view(np.uint32))
+    for got, want in zip(swept, swept0):
+        for a, b in zip(got, want):
+            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+    _same(params, params0)
+
+
 def test_fit_refuses_what_the_model_does_not_accept():
     m = _classifier()
     with pytest.raises(ValueError, match="holds no labels"):
