@@ -10,7 +10,8 @@ examples/siamese.py labels them; no TensorFlow session, no recordings on disk.
 Without ``--device-data`` this is train.py's host loop: ``train(x, y)`` per batch, ``predict(x)`` per test clip.  With it
 the training set and the test set are loaded onto the device once: the steps between two prints are one ``fit`` call that
 also sweeps a validation set every ``--validate-every`` steps (``fit(..., validate=...)``), and ``--test`` is one
-``evaluate`` call."""
+``evaluate`` call.  ``--shift``, ``--gain``, ``--noise``, ``--noise-prob`` and ``--noise-volume`` augment the training draws
+there (``dataset.Augment``); the validation and test sets are never augmented."""
 import argparse
 import os
 import sys
@@ -61,7 +62,10 @@ def main(argv=None):
     import importlib
     O = importlib.import_module("sr-wavenet_amd.optim")
     O.add_control_flags(p, validate=True)
+    DS = importlib.import_module("sr-wavenet_amd.dataset")
+    DS.add_augment_flags(p)
     a = p.parse_args(argv)
+    a.augment = DS.augment_from_flags(a, a.device_data)         # (refuses the flags without --device-data)
     rng = np.random.RandomState(a.seed) if a.seed is not None else None
     num_classes = len(WORDS)
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 2)[:a.layers]
@@ -113,7 +117,7 @@ def fit_loop(a, network, D, rng):
     of its own."""
     train = D.DeviceDataset(*make_set(a.device_clips, a.num_samples, rng), len(WORDS))
     held = D.DeviceDataset(*make_set(a.validation_clips, a.num_samples, rng), len(WORDS))
-    sampler = train.sampler(a.batch_size, a.num_samples, seed=0)
+    sampler = train.sampler(a.batch_size, a.num_samples, seed=0, augment=a.augment)     # (the held-out sets stay plain)
     validation = held.eval_sampler(a.eval_batch_size, a.num_samples)
     print("%d + %d clips of %d samples on the device (%.1f MB)" % (len(train), len(held), train.clip_len,
                                                                   (train.nbytes + held.nbytes) / 1e6), flush=True)

@@ -7,6 +7,10 @@
   python examples/siamese.py --test --logdir runs/siamese
   python examples/siamese.py --train --logdir runs/siamese --steps 1000 --device-data
   python examples/siamese.py --test --logdir runs/siamese --device-data --test-clips 1024
+  python examples/siamese.py --train --logdir runs/siamese --steps 1000 --device-data --shift 100 --gain 0.7:1.3
+
+``--shift``, ``--gain``, ``--noise``, ``--noise-prob`` and ``--noise-volume`` augment the pairs drawn with ``--device-data``
+(``dataset.Augment``): the two clips of a pair independently, so two views of one recording differ.
 """
 import argparse
 import os
@@ -48,7 +52,10 @@ def main(argv=None):
     import importlib
     O = importlib.import_module("sr-wavenet_amd.optim")
     O.add_control_flags(p)
+    DS = importlib.import_module("sr-wavenet_amd.dataset")
+    DS.add_augment_flags(p)
     a = p.parse_args(argv)
+    a.augment = DS.augment_from_flags(a, a.device_data)         # (refuses the flags without --device-data)
     rng = np.random.RandomState(a.seed) if a.seed is not None else None
     dilations = ([1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3)[:a.layers]
     network = SiameseWaveNet(input_size=a.num_samples, output_dimensions=2, dilations=dilations, skip_channels=128,
@@ -122,7 +129,7 @@ def fit_loop(a, network, rng):
     generated waves labelled by wave shape -- is loaded onto the device once; every step draws its pairs there ("same
     class" for half of them) and the steps between two prints are one ``fit`` call."""
     data = labelled_set(a, a.device_clips, rng)
-    sampler = data.pair_sampler(a.batch_size, a.num_samples, seed=0)
+    sampler = data.pair_sampler(a.batch_size, a.num_samples, seed=0, augment=a.augment)   # (two views of a pair differ)
     sampler.seek(a.start)
     if a.resume and network.load_training_state(a.logdir, sampler=sampler):
         a.start = sampler.step                       # the sampler continues its sequence where the saved run stopped

@@ -1750,6 +1750,42 @@ int srwn_adam_step_ctl(float* params, const float* grads, float* m, float* v, fl
                        const float* ctl, const int32_t* ctl_len, int32_t ctl_capacity, float beta1, float beta2, float eps,
                        float grad_scale, const float* grad_scale_dev, int32_t tick, void* stream);
 
+/* ---- augmented draws (since srwn_version() 127; csrc/srwn_augment.hip): srwn_batch_draw and srwn_pair_draw with a random
+ * time shift, a random gain and a background recording mixed in at a random volume, in the same one launch.  Everything the
+ * plain entries say holds -- the state is only read, the records and crop offsets are dataset.draw_plan's and
+ * dataset.pair_plan's, the outputs are the same buffers -- and the arguments in front of the augmentation block are theirs.
+ *   max_shift        S: the shift is uniform on [-S, S], 0 <= S < T
+ *   gain_lo, gain_hi, volume_lo, volume_hi   linear amplitude ranges, finite, 0 <= lo <= hi
+ *   noise            NULL, or [noise_clips][noise_len] fp32 background recordings, noise_len >= T;  noise_clips 0: none
+ *   noise_threshold  floor(noise_prob * 2^32): a row is mixed where its coin's 32 bits lie below it (and there is noise)
+ * Row b (srwn_pair_draw_aug: pair b, side 0 its left clip and side 1 its right one; srwn_batch_draw_aug: side 0) at position
+ * p takes six draws h = mix64((seed ^ salt) + GOLDEN * (2 p + side + 1)), one salt per quantity (dataset.augment_plan):
+ *   shift = (((h >> 32) (2 S + 1)) >> 32) - S;   gain = lo + u (hi - lo) with u = (float)(h >> 40) * 2^-24 (exact), the
+ *   subtraction, the product and the sum each rounded to fp32;   mix = (h >> 32) < noise_threshold;   noise record
+ *   ((h >> 32) noise_clips) >> 32;   noise offset ((h >> 32) (noise_len - T + 1)) >> 32;   volume as gain.
+ * With row[0..T) the cropped clip, the sample rule (dataset.augment_rows) is
+ *   xs[j] = row[j - shift] where 0 <= j - shift < T, else +0;   n[j] = noise[record][offset + j] and v = volume where the
+ *   row is mixed, else n[j] = +0 and v = +0;   y[j] = fp32(fp32(gain * xs[j]) + fp32(v * n[j])), no fused multiply-add;
+ *   then y < -1 ? -1 : (y > 1 ? 1 : y), so a NaN passes.  Subnormal products are kept.
+ * audio0, audio1 and the mu-law codes (srwn_pair_draw_aug: audio) all hold y; one-hot rows, indices, y, left, right and y_log
+ * are the plain entries'.
+ * Errors, all before any launch: the plain entry's, and max_shift outside [0, T), a range with a negative end, lo > hi or a
+ * value that is not finite, noise_clips < 0, noise_len < T with noise_clips > 0, noise_threshold outside [0, 2^32], a noise
+ * pointer that is not 4-byte aligned (-2); noise_clips > 0 with a null noise (-3). */
+int srwn_batch_draw_aug(const float* clips, const int32_t* labels, int32_t num_clips, int64_t clip_len, const int64_t* state,
+                        int32_t B, int32_t T, int32_t shuffle, int32_t crop, int32_t rank, int32_t world, float* audio0,
+                        float* audio1, int32_t* codes, int32_t quantization_channels, void* onehot, int64_t onehot_ld,
+                        int32_t onehot_rows, int32_t onehot_col0, int32_t num_classes, int32_t onehot_dtype,
+                        int32_t* indices, int32_t max_shift, float gain_lo, float gain_hi, const float* noise,
+                        int32_t noise_clips, int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi,
+                        void* stream);
+int srwn_pair_draw_aug(const float* clips, const int32_t* labels, const int32_t* order, const int32_t* place,
+                       const int32_t* class_start, int32_t num_classes, int32_t num_clips, int64_t clip_len,
+                       const int64_t* state, int32_t P, int32_t T, int64_t same_threshold, int32_t shuffle, int32_t crop,
+                       int32_t rank, int32_t world, float* audio, float* y, int32_t* left, int32_t* right, float* y_log,
+                       int32_t max_shift, float gain_lo, float gain_hi, const float* noise, int32_t noise_clips,
+                       int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

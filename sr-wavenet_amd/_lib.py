@@ -314,6 +314,11 @@ SIGNATURES["srwn_embed_collect"] = (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32
 SIGNATURES["srwn_pair_sweep"] = (C.c_int, [_p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p])
 # training controls (srwn_version() 126): the Adam update with lr and EMA decay from a device table, the shadow in the same pass
 SIGNATURES["srwn_adam_step_ctl"] = (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _i32, _f32, _f32, _f32, _f32, _p, _i32, _p])
+# augmented draws (srwn_version() 127): the two draws with the augmentation block behind their own arguments -- shift bound,
+# gain range, the noise set's pointer, count and clip length, the coin threshold, volume range
+_AUG = [_i32, _f32, _f32, _p, _i32, _i64, _i64, _f32, _f32]
+SIGNATURES["srwn_batch_draw_aug"] = (C.c_int, SIGNATURES["srwn_batch_draw"][1][:-1] + _AUG + [_p])
+SIGNATURES["srwn_pair_draw_aug"] = (C.c_int, SIGNATURES["srwn_pair_draw"][1][:-1] + _AUG + [_p])
 
 _lib = None
 BINDING = None     # "pybind11" or "ctypes" once loaded

@@ -17,6 +17,7 @@
 // the others read.  Rows are written as srwn_batch_draw writes them: a scalar head up to the destination's 16-byte
 // boundary, 16-byte stores and a scalar tail, a row longer than kDrawSpan split over several workgroups.
 #include "srwn_common.h"
+#include "srwn_draw_common.h"
 #include "srwn_host.h"
 #include "../../include/srwn.h"
 
@@ -24,43 +25,7 @@ using namespace srwn;
 
 namespace {
 
-constexpr int kDrawThreads = 256;
-constexpr int kDrawPerThread = 16;                                // samples per thread and pass: 4096 per workgroup
-constexpr int kDrawSpan = kDrawThreads * kDrawPerThread;
-constexpr int kFeistelRounds = 4;
-constexpr unsigned long long kGolden = 0x9E3779B97F4A7C15ull;
-constexpr unsigned long long kCropSalt = 0x63726F706F666673ull;       // dataset._CROP_SALT (srwn_batch_draw's)
 constexpr unsigned long long kNoiseSalt = 0x6E6F697365726F77ull;      // dataset.NOISE_SALT
-constexpr unsigned long long kPairSalt = 0x70616972636F696Eull;       // dataset.PAIR_SALT: the coin
-constexpr unsigned long long kPairPickSalt = 0x706169727069636Bull;   // dataset.PAIR_PICK_SALT: the right record
-constexpr unsigned long long kPairCropSalt = 0x7061697263726F70ull;   // dataset.PAIR_CROP_SALT: the right crop offset
-
-// the splitmix64 finaliser gen_uniform (srwn_gen_ring.h) keys its draws with
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-  return x;
-}
-
-// perm(seed, e)(i) of csrc/srwn_data.hip (dataset.permute): a keyed bijection on [0, N), cycle-walked Feistel rounds; the
-// walk is bounded by the domain size 2^k
-__device__ __forceinline__ unsigned feistel_perm(unsigned long long seed, unsigned long long e, unsigned i, unsigned N) {
-  if (N <= 1u) return 0u;
-  const int k = 32 - __clz((int)(N - 1u));
-  const unsigned long long ekey = mix64(seed + kGolden * (e + 1ull));
-  unsigned x = i;
-  for (unsigned long long walk = 0; walk < (1ull << k); ++walk) {
-    int a = k / 2, b = k - a;                                     // x = (L : a bits, R : b bits)
-#pragma unroll
-    for (int r = 0; r < kFeistelRounds; ++r) {
-      const unsigned L = x >> b, R = x & ((1u << b) - 1u);
-      const unsigned f = (unsigned)mix64(ekey + kGolden * ((unsigned long long)R * kFeistelRounds + r + 1ull));
-      x = (R << a) | (L ^ (f & ((1u << a) - 1u)));
-      const int t = a; a = b; b = t;
-    }
-    if (x < N) return x;
-  }
-  return i;                                                       // (not reached; inside [0, N) whatever happens)
-}
 
 // log u - log(1 - u) at u = (k + 1/2) / 2^23: the evaluation of csrc/srwn_stream.hip's logistic_of_bits23, operation for
 // operation (srwn_logistic_noise and srwn_logistic_from_bits give these bits)
@@ -72,41 +37,9 @@ __device__ __forceinline__ float logistic_of_bits23(uint32_t k) {
   return d < 0.0f ? -l : l;
 }
 
-// position p of the sample sequence -> its record and crop offset (dataset.draw_plan)
-struct Pick { unsigned rec; int64_t off; };
-__device__ __forceinline__ Pick draw_pick(unsigned long long seed, unsigned long long p, int N, int shuffle, int crop,
-                                          int64_t clip_len, int T) {
-  const unsigned long long e = p / (unsigned long long)N;
-  const unsigned i = (unsigned)(p % (unsigned long long)N);
-  Pick k;
-  k.rec = shuffle ? feistel_perm(seed, e, i, (unsigned)N) : i;
-  k.off = 0;
-  if (crop) {                                                     // uniform on [0, clip_len - T]
-    const unsigned long long h = mix64((seed ^ kCropSalt) + kGolden * (p + 1ull));
-    k.off = (int64_t)(((h >> 32) * (unsigned long long)(clip_len - T + 1)) >> 32);
-  }
-  return k;
-}
-
-// one row of T fp32 values dst[j] = src[j], this workgroup's share [j0, j1): head, 16-byte body, tail (srwn_data.hip)
+// one row of T fp32 values dst[j] = src[j], this workgroup's share [j0, j1): the row writer of srwn_draw_common.h
 __device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* __restrict__ src, int j0, int j1) {
-  // first element of the share whose destination sits on a 16-byte boundary (dst is 4-byte aligned)
-  const int mis = (int)(((uintptr_t)(dst + j0) >> 2) & 3);
-  int jb = j0 + ((4 - mis) & 3);
-  if (jb > j1) jb = j1;
-  const int nvec = (j1 - jb) / 4;
-  const int je = jb + 4 * nvec;
-  const int tid = (int)threadIdx.x;
-  if (tid < jb - j0) dst[j0 + tid] = src[j0 + tid];                             // head: at most 3 elements
-  const bool src_aligned = (((uintptr_t)(src + jb)) & 15) == 0;
-  for (int v = tid; v < nvec; v += kDrawThreads) {
-    const int j = jb + 4 * v;
-    f32x4 x;
-    if (src_aligned) x = *reinterpret_cast<const f32x4*>(src + j);
-    else x = f32x4{src[j], src[j + 1], src[j + 2], src[j + 3]};
-    *reinterpret_cast<f32x4*>(dst + j) = x;
-  }
-  if (tid < j1 - je) dst[je + tid] = src[je + tid];                             // tail: at most 3 elements
+  draw_row(dst, src, j0, j1, [](float x) { return x; });
 }
 
 __device__ __forceinline__ void put(void* table, int dtype, int64_t o, float v) {
@@ -189,14 +122,6 @@ __global__ void distill_log_kernel(const float* __restrict__ ce, const float* __
   state[1] = (int64_t)(step + 1ull);
 }
 
-struct PairArgs {
-  const float* clips; const int32_t* labels; const int32_t* order; const int32_t* place; const int32_t* start;
-  const int64_t* state;
-  float* audio; float* y; int32_t* left; int32_t* right; float* y_log;
-  int64_t clip_len; unsigned long long threshold;
-  int32_t N, P, T, shuffle, crop, rank, world, num_classes;
-};
-
 __global__ __launch_bounds__(kDrawThreads) void pair_draw_kernel(const PairArgs a) {
   const int row = (int)blockIdx.y;                                // [0, P): the left clips; [P, 2P): the right ones
   const int b = row < a.P ? row : row - a.P;
@@ -257,16 +182,6 @@ __global__ __launch_bounds__(256) void pair_log_kernel(const float* __restrict__
     loss_log[slot] = loss[0];
     state[1] = (int64_t)(step + 1ull);                            // ... and one writes it after
   }
-}
-
-int check_draw(const char* who, const float* clips, int32_t num_clips, int64_t clip_len, const int64_t* state, int32_t B,
-               int32_t T, int32_t crop, int32_t rank, int32_t world) {
-  if (num_clips < 1 || clip_len < 1 || B < 0 || T < 0 || (int64_t)T > clip_len || clip_len - T >= (1ll << 32))
-    return set_error(SRWN_E_SHAPE, "%s: %d clips of %lld samples, B=%d T=%d", who, num_clips, (long long)clip_len, B, T);
-  if (world < 1 || rank < 0 || rank >= world) return set_error(SRWN_E_SHAPE, "%s: rank %d of %d", who, rank, world);
-  if (crop != 0 && crop != 1) return set_error(SRWN_E_SHAPE, "%s: crop %d (0 head, 1 random)", who, crop);
-  if (!clips || !state) return set_error(SRWN_E_NULL, "%s: null pointer", who);
-  return 0;
 }
 
 }  // namespace
@@ -336,21 +251,10 @@ extern "C" int srwn_pair_draw(const float* clips, const int32_t* labels, const i
                               int32_t T, int64_t same_threshold, int32_t shuffle, int32_t crop, int32_t rank, int32_t world,
                               float* audio, float* y, int32_t* left, int32_t* right, float* y_log, void* stream) {
   if (P == 0 || T == 0) return 0;
-  if (int rc = check_draw("pair_draw", clips, num_clips, clip_len, state, P, T, crop, rank, world)) return rc;
-  if (num_classes < 1) return set_error(SRWN_E_SHAPE, "pair_draw: %d classes", num_classes);
-  if (P > 32767) return set_error(SRWN_E_SHAPE, "pair_draw: P=%d (at most 32767 pairs per draw)", P);
-  if (same_threshold < 0 || same_threshold > (1ll << 32))
-    return set_error(SRWN_E_SHAPE, "pair_draw: same_threshold %lld outside [0, 2^32]", (long long)same_threshold);
-  if (!labels || !order || !place || !class_start || !audio || !y || !left || !right || !y_log)
-    return set_error(SRWN_E_NULL, "pair_draw: null pointer");
-  if (((uintptr_t)clips | (uintptr_t)audio) & 3)
-    return set_error(SRWN_E_SHAPE, "pair_draw: the fp32 buffers must be 4-byte aligned");
   PairArgs a;
-  a.clips = clips; a.labels = labels; a.order = order; a.place = place; a.start = class_start; a.state = state;
-  a.audio = audio; a.y = y; a.left = left; a.right = right; a.y_log = y_log;
-  a.clip_len = clip_len; a.threshold = (unsigned long long)same_threshold;
-  a.N = num_clips; a.P = P; a.T = T; a.shuffle = shuffle != 0; a.crop = crop; a.rank = rank; a.world = world;
-  a.num_classes = num_classes;
+  if (int rc = check_pair_draw("pair_draw", clips, labels, order, place, class_start, num_classes, num_clips, clip_len, state, P,
+                               T, same_threshold, shuffle, crop, rank, world, audio, y, left, right, y_log, &a))
+    return rc;
   dim3 grid((unsigned)((T + kDrawSpan - 1) / kDrawSpan), (unsigned)(2 * P));
   hipLaunchKernelGGL(pair_draw_kernel, grid, dim3(kDrawThreads), 0, (hipStream_t)stream, a);
   return check_launch("pair_draw");

@@ -30,10 +30,17 @@ set the same way, ``srwn_embed_collect`` behind the tower's forward pass gathers
 nearest record of the same label and the two distance histograms; ``SiameseWaveNet.evaluate`` and ``SiameseWaveNet.fit(...,
 validate=...)`` read the slots into ``PairEvalResult``s (nearest-neighbour accuracy, recall@k, FAR / FRR, EER, AUC).
 
+A ``BatchSampler`` or a ``PairSampler`` built with ``augment=Augment(...)`` draws augmented rows (csrc/srwn_augment.hip):
+a random time shift with zero fill, a random gain and a background clip of another ``DeviceDataset`` mixed in at a random
+volume, per row and per step, in the draw launch itself.  ``augment_plan`` states the row's draws and ``augment_rows`` the
+sample rule; the kernels give their bits.  A ``PairSampler`` augments the two clips of a pair as two sides of one position,
+so two views of one record differ.  Evaluation sweeps are not augmented.
+
 Storage is fp32 only: int16 or bf16 clip storage is out of scope.
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import numpy as np
@@ -45,6 +52,12 @@ NOISE_SALT = 0x6E6F697365726F77        # the rows' noise seeds
 PAIR_SALT = 0x70616972636F696E         # the pairs' coins ...
 PAIR_PICK_SALT = 0x706169727069636B    # ... their right records
 PAIR_CROP_SALT = 0x7061697263726F70    # ... and the right clips' crop offsets
+AUG_SHIFT_SALT = 0x6175677368696674     # an augmented row's shift ...
+AUG_GAIN_SALT = 0x6175676761696E21      # ... its gain
+AUG_COIN_SALT = 0x617567636F696E21      # ... whether noise is mixed in
+AUG_PICK_SALT = 0x6175677069636B21      # ... the noise record
+AUG_OFFSET_SALT = 0x6175676F66667374    # ... where its window starts
+AUG_VOLUME_SALT = 0x617567766F6C2121    # ... and its volume
 _ROUNDS = 4
 CROPS = {"head": 0, "random": 1}
 MAX_BATCH = 65535          # rows of one draw (the launch's second grid dimension)
@@ -317,8 +330,11 @@ class DeviceDataset(object):
         """Device bytes of the clips and the labels."""
         return self.audio.numel() * 4 + (0 if self.labels is None else self.labels.numel() * 4)
 
-    def sampler(self, batch_size, num_samples, seed=0, shuffle=True, crop="head", rank=0, world=1, log_capacity=1024):
-        return BatchSampler(self, batch_size, num_samples, seed, shuffle, crop, rank, world, log_capacity)
+    def sampler(self, batch_size, num_samples, seed=0, shuffle=True, crop="head", rank=0, world=1, log_capacity=1024,
+                augment=None):
+        """The draws of a training run (``fit`` of the classifier, the teacher, the auto-encoder); with `augment` (an
+        ``Augment``) every drawn row is shifted, scaled and mixed with noise in the draw launch."""
+        return BatchSampler(self, batch_size, num_samples, seed, shuffle, crop, rank, world, log_capacity, augment)
 
     def distill_sampler(self, batch_size, num_samples, seed=0, shuffle=True, crop="head", temperature=1.0, rank=0, world=1,
                         log_capacity=1024):
@@ -326,10 +342,11 @@ class DeviceDataset(object):
         return DistillSampler(self, batch_size, num_samples, seed, shuffle, crop, temperature, rank, world, log_capacity)
 
     def pair_sampler(self, pairs, num_samples, seed=0, p_same=0.5, shuffle=True, crop="head", rank=0, world=1,
-                     log_capacity=1024):
+                     log_capacity=1024, augment=None):
         """The draws of a twin-tower run (``SiameseWaveNet.fit``): `pairs` pairs of clips per step, "same class" with
-        probability `p_same`.  Needs labels, every one inside [0, num_classes)."""
-        return PairSampler(self, pairs, num_samples, seed, p_same, shuffle, crop, rank, world, log_capacity)
+        probability `p_same`.  Needs labels, every one inside [0, num_classes).  With `augment` (an ``Augment``) the two
+        clips of a pair are augmented independently."""
+        return PairSampler(self, pairs, num_samples, seed, p_same, shuffle, crop, rank, world, log_capacity, augment)
 
     def eval_sampler(self, batch_size, num_samples, crop="head", seed=0, rank=0, world=1, top_k=5, sweep_capacity=16):
         """The sweeps of a held-out evaluation (``WaveNet.evaluate``, ``WaveNet.fit(..., validate=...)``): every record once
@@ -362,6 +379,188 @@ class DeviceDataset(object):
         return self._labels_host
 
 
+def _amplitude_range(r, name) -> Tuple[float, float]:
+    try:
+        lo, hi = (float(v) for v in r)
+    except (TypeError, ValueError):
+        raise ValueError("%s %r: a range (lo, hi)" % (name, r))
+    with np.errstate(over="ignore"):             # (a value beyond fp32's range is not finite where the kernel reads it)
+        finite = np.isfinite(np.float32(lo)) and np.isfinite(np.float32(hi))
+    if not (finite and 0.0 <= lo <= hi):
+        raise ValueError("%s %r: finite linear amplitudes, 0 <= lo <= hi" % (name, r))
+    return lo, hi
+
+
+class Augment(object):
+    """What an augmenting sampler does to every drawn row, immutable: a shift uniform on [-shift, shift] samples with zero
+    fill, a gain uniform on ``gain`` and, with probability ``noise_prob``, a window of a clip of the ``DeviceDataset``
+    ``noise`` (its labels are unused) added at a volume uniform on ``noise_volume``.  Amplitudes are linear.  The defaults
+    change nothing but the sign of a zero (``augment_rows``)."""
+    __slots__ = ("shift", "gain", "noise", "noise_prob", "noise_volume", "noise_threshold")
+
+    def __init__(self, shift=0, gain=(1.0, 1.0), noise=None, noise_prob=0.0, noise_volume=(0.0, 0.0)):
+        if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 0 <= int(shift) < 1 << 31:
+            raise ValueError("shift %r: a number of samples, at least 0" % (shift,))
+        if noise is not None and not isinstance(noise, DeviceDataset):
+            raise TypeError("noise must be a DeviceDataset of background clips, got %s" % type(noise).__name__)
+        set_ = object.__setattr__
+        set_(self, "shift", int(shift))
+        set_(self, "gain", _amplitude_range(gain, "gain"))
+        set_(self, "noise_volume", _amplitude_range(noise_volume, "noise_volume"))
+        try:
+            set_(self, "noise_threshold", same_threshold(noise_prob))
+        except (TypeError, ValueError):
+            raise ValueError("noise_prob %r: a probability" % (noise_prob,))
+        if noise is None and self.noise_threshold:
+            raise ValueError("noise_prob %r without noise: pass the background clips as noise=DeviceDataset(...)"
+                             % (noise_prob,))
+        set_(self, "noise", noise)
+        set_(self, "noise_prob", float(noise_prob))
+
+    def __setattr__(self, name, value=None):
+        raise AttributeError("an Augment is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self):
+        return "Augment(shift=%d, gain=%r, noise=%s, noise_prob=%r, noise_volume=%r)" % (
+            self.shift, self.gain, "None" if self.noise is None else "<%d clips>" % len(self.noise), self.noise_prob,
+            self.noise_volume)
+
+    def check(self, dataset, num_samples: int) -> None:
+        """What only a sampler knows: the shift stays inside the row, the noise lives beside the clips and covers a row."""
+        if self.shift >= int(num_samples):
+            raise ValueError("augment: shift %d: below num_samples %d" % (self.shift, int(num_samples)))
+        if self.noise is not None:
+            if str(self.noise.device) != str(dataset.device):
+                raise ValueError("augment: the noise is on %s, the clips are on %s" % (self.noise.device, dataset.device))
+            if self.noise.clip_len < int(num_samples):
+                raise ValueError("augment: noise clips of %d samples are shorter than num_samples %d"
+                                 % (self.noise.clip_len, int(num_samples)))
+
+
+AugmentPlan = namedtuple("AugmentPlan", "shift gain mix noise_index noise_offset volume")
+
+
+def _amplitude(h: int, lo: float, hi: float) -> np.float32:
+    """lo + u (hi - lo) at u = float32(h >> 40) * 2^-24 (exact): the subtraction, the product and the sum round to fp32."""
+    u = np.float32(h >> 40) * np.float32(2.0 ** -24)
+    lo, hi = np.float32(lo), np.float32(hi)
+    return np.float32(lo + np.float32(u * np.float32(hi - lo)))
+
+
+def augment_plan(seed: int, step: int, batch_size: int, num_samples: int, augment: "Augment", noise_n: int, noise_len: int,
+                 rank: int = 0, world: int = 1, side: int = 0) -> "AugmentPlan":
+    """The augmentation of the rows of ``step``: ``(shift [B] int32, gain [B] float32, mix [B] bool, noise_index [B] int32,
+    noise_offset [B] int64, volume [B] float32)``.  Row b is ``draw_plan``'s position p = (step * world + rank) * B + b;
+    every quantity has a draw of its own, ``_mix64((seed ^ SALT) + _GOLDEN * (2 * p + side + 1))`` with the six AUG salts,
+    so ranks, steps, rows and the two sides of a pair never share one.  shift = ``((h >> 32) * (2 S + 1)) >> 32`` minus S;
+    gain and volume are ``_amplitude`` of their ranges; mix says the coin ``h >> 32`` lies below ``floor(noise_prob * 2^32)``
+    (never without noise clips: `noise_n` 0); the noise record is uniform on [0, noise_n) and its window starts at an
+    offset uniform on [0, noise_len - num_samples], both by ``((h >> 32) * range) >> 32``.  `side`: 0 for a ``BatchSampler``
+    and the left clip of a pair, 1 for the right clip."""
+    batch_size, num_samples, noise_n, noise_len = int(batch_size), int(num_samples), int(noise_n), int(noise_len)
+    if not isinstance(augment, Augment):
+        raise TypeError("augment must be an Augment, got %s" % type(augment).__name__)
+    if not 1 <= batch_size <= MAX_BATCH:
+        raise ValueError("batch_size %d: at least 1, at most %d" % (batch_size, MAX_BATCH))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d of %d" % (rank, world))
+    if side not in (0, 1):
+        raise ValueError("side %r: 0 or 1" % (side,))
+    if not augment.shift < num_samples:
+        raise ValueError("augment: shift %d: below num_samples %d" % (augment.shift, num_samples))
+    if noise_n < 0 or (noise_n > 0 and noise_len < num_samples):
+        raise ValueError("augment_plan: %d noise clips of %d samples, num_samples %d" % (noise_n, noise_len, num_samples))
+    seed &= _MASK
+    S = augment.shift
+    plan = AugmentPlan(np.zeros(batch_size, np.int32), np.zeros(batch_size, np.float32), np.zeros(batch_size, bool),
+                       np.zeros(batch_size, np.int32), np.zeros(batch_size, np.int64), np.zeros(batch_size, np.float32))
+    for b in range(batch_size):
+        p = (step * world + rank) * batch_size + b
+        h = lambda salt: _mix64((seed ^ salt) + _GOLDEN * (2 * p + side + 1))
+        plan.shift[b] = (((h(AUG_SHIFT_SALT) >> 32) * (2 * S + 1)) >> 32) - S
+        plan.gain[b] = _amplitude(h(AUG_GAIN_SALT), *augment.gain)
+        plan.volume[b] = _amplitude(h(AUG_VOLUME_SALT), *augment.noise_volume)
+        if noise_n > 0:
+            plan.mix[b] = (h(AUG_COIN_SALT) >> 32) < augment.noise_threshold
+            plan.noise_index[b] = ((h(AUG_PICK_SALT) >> 32) * noise_n) >> 32
+            plan.noise_offset[b] = ((h(AUG_OFFSET_SALT) >> 32) * (noise_len - num_samples + 1)) >> 32
+    return plan
+
+
+def augment_rows(rows, plan: "AugmentPlan", noise_clips=None) -> np.ndarray:
+    """The sample rule on the cropped rows ``[B, T]``, in fp32: ``xs[j] = rows[j - shift]`` inside the row and +0 outside
+    (TensorFlow speech_commands' time shift with zero fill, inside the crop window); ``n[j] = noise_clips[noise_index,
+    noise_offset + j]`` and v = volume where ``mix``, else n = +0 and v = +0; ``y = fp32(fp32(gain * xs) + fp32(v * n))``,
+    then ``y < -1 ? -1 : (y > 1 ? 1 : y)`` (a NaN passes).  The sum is formed with mixing off too, so a zero has one sign
+    whatever the plan: -0.0 only where both products are -0.0.  Every destination of a draw holds y."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim != 2 or x.shape[0] != plan.shift.shape[0]:
+        raise ValueError("rows must be [%d, T], got %s" % (plan.shift.shape[0], tuple(x.shape)))
+    B, T = x.shape
+    if plan.mix.any():
+        if noise_clips is None:
+            raise ValueError("the plan mixes noise into %d rows: pass the noise clips" % int(plan.mix.sum()))
+        noise_clips = np.asarray(noise_clips, dtype=np.float32)
+    out = np.empty_like(x)
+    j = np.arange(T)
+    for b in range(B):
+        k = j - int(plan.shift[b])
+        inside = (k >= 0) & (k < T)
+        xs = np.where(inside, x[b, np.clip(k, 0, T - 1)], np.float32(0.0)).astype(np.float32)
+        if plan.mix[b]:
+            o = int(plan.noise_offset[b])
+            n, v = noise_clips[int(plan.noise_index[b]), o:o + T], np.float32(plan.volume[b])
+        else:
+            n, v = np.zeros(T, np.float32), np.float32(0.0)
+        with np.errstate(all="ignore"):
+            y = (np.float32(plan.gain[b]) * xs).astype(np.float32) + (v * n).astype(np.float32)
+        out[b] = np.where(y < np.float32(-1.0), np.float32(-1.0), np.where(y > np.float32(1.0), np.float32(1.0), y))
+    return out
+
+
+def add_augment_flags(parser) -> None:
+    """The drivers' augmentation flags (examples/classifier.py, examples/siamese.py); ``augment_from_flags`` reads them."""
+    g = parser.add_argument_group("augmentation (--device-data)")
+    g.add_argument("--shift", type=int, default=0, metavar="N", help="shift every drawn clip by up to N samples, zero fill")
+    g.add_argument("--gain", type=str, default=None, metavar="LO:HI", help="scale every drawn clip by a gain uniform on [LO, HI]")
+    g.add_argument("--noise", type=str, default=None, metavar="FILE.npy", help="background clips to mix in: an [M, len] array")
+    g.add_argument("--noise-prob", type=float, default=0.0, metavar="P", help="mix noise into a drawn clip with probability P")
+    g.add_argument("--noise-volume", type=str, default=None, metavar="LO:HI", help="volume of the noise, uniform on [LO, HI]")
+
+
+def _flag_range(text, name):
+    try:
+        lo, hi = (float(v) for v in text.split(":"))
+    except ValueError:
+        raise SystemExit("--%s %r: LO:HI" % (name, text))
+    return lo, hi
+
+
+def augment_from_flags(args, device_data: bool, device="cuda") -> Optional["Augment"]:
+    """The ``Augment`` the flags of ``add_augment_flags`` ask for, or None when none of them is set.  They act in the draw
+    launch, so without --device-data they are refused here, not ignored.  The noise file is uploaded once."""
+    asked = [f for f, on in (("--shift", args.shift != 0), ("--gain", args.gain is not None), ("--noise", args.noise is not None),
+                             ("--noise-prob", args.noise_prob != 0.0), ("--noise-volume", args.noise_volume is not None)) if on]
+    if not asked:
+        return None
+    if not device_data:
+        raise SystemExit("%s: augmentation happens where the batch is drawn on the device; add --device-data"
+                         % ", ".join(asked))
+    noise = None
+    if args.noise is not None:
+        clips = np.load(args.noise)
+        if clips.ndim != 2:
+            raise SystemExit("--noise %s: an [M, len] array of background clips, got shape %s" % (args.noise, clips.shape))
+        noise = DeviceDataset(clips.astype(np.float32), device=device)
+    try:
+        return Augment(args.shift, (1.0, 1.0) if args.gain is None else _flag_range(args.gain, "gain"), noise,
+                       args.noise_prob, (0.0, 0.0) if args.noise_volume is None else _flag_range(args.noise_volume, "noise-volume"))
+    except (TypeError, ValueError) as e:
+        raise SystemExit("augmentation flags: %s" % e)
+
+
 def _is_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
@@ -373,12 +572,19 @@ class BatchSampler(object):
     seed -- what a model's ``load_training_state(logdir, sampler=...)`` does -- draws the batches the stopped run would
     have drawn next."""
 
+    augment = None           # an Augment, or None: the plain draw (class default: objects made without __init__ have none)
+
     def __init__(self, dataset, batch_size, num_samples, seed=0, shuffle=True, crop="head", rank=0, world=1,
-                 log_capacity=1024):
+                 log_capacity=1024, augment=None):
         batch_size, num_samples, rank, world = int(batch_size), int(num_samples), int(rank), int(world)
         _check_draw(batch_size, len(dataset), dataset.clip_len, num_samples, crop, rank, world)
         if int(log_capacity) < 1:
             raise ValueError("log_capacity %d: at least 1" % int(log_capacity))
+        if augment is not None:
+            if not isinstance(augment, Augment):
+                raise TypeError("augment must be an Augment, got %s" % type(augment).__name__)
+            augment.check(dataset, num_samples)
+        self.augment = augment
         import torch
         self.dataset, self.batch_size, self.num_samples = dataset, batch_size, num_samples
         self.seed, self.shuffle, self.crop, self.rank, self.world = int(seed) & _MASK, bool(shuffle), crop, rank, world
@@ -396,6 +602,22 @@ class BatchSampler(object):
         return draw_plan(self.seed, self.step if step is None else int(step), self.batch_size, len(d), d.clip_len,
                          self.num_samples, self.shuffle, self.crop, self.rank, self.world)
 
+    def augment_plan(self, step: Optional[int] = None, side: int = 0) -> "AugmentPlan":
+        """``augment_plan`` of `step` (default: the next one) for this sampler's ``augment``."""
+        if self.augment is None:
+            raise ValueError("this sampler does not augment (it was built with augment=None)")
+        nz = self.augment.noise
+        return augment_plan(self.seed, self.step if step is None else int(step), self.batch_size, self.num_samples,
+                            self.augment, 0 if nz is None else len(nz), 0 if nz is None else nz.clip_len, self.rank,
+                            self.world, side)
+
+    def _augment_args(self):
+        """The augmentation block of the ``_aug`` entries (srwn.h), behind the plain draw's arguments."""
+        a = self.augment
+        nz = a.noise
+        return (a.shift, a.gain[0], a.gain[1], None if nz is None else nz.audio.data_ptr(), 0 if nz is None else len(nz),
+                0 if nz is None else nz.clip_len, a.noise_threshold, a.noise_volume[0], a.noise_volume[1])
+
     def seek(self, step: int) -> None:
         """Continues the sequence at `step` (a run resumed from a checkpoint): sets the device counter and the host's."""
         if int(step) < 0:
@@ -405,7 +627,7 @@ class BatchSampler(object):
 
     # ---- the two launches ------------------------------------------------------------------------------------------
     def draw(self, audio, audio2=None, codes=None, quantization_channels=0, onehot=None, onehot_rows=1, onehot_col0=0):
-        """srwn_batch_draw on the current stream: the step's rows into `audio` ([B, T] fp32; `audio2` the same once
+        """srwn_batch_draw (with an ``Augment``: srwn_batch_draw_aug) on the current stream: the step's rows into `audio` ([B, T] fp32; `audio2` the same once
         more), their mu-law codes into `codes` (int32, B * T), the labels' one-hot rows into columns [onehot_col0,
         onehot_col0 + num_classes) of `onehot` ([B * onehot_rows, ld], fp32 or bf16) and the indices into
         ``self.indices``.  Reads the device step; does not tick it (``log`` does)."""
@@ -429,10 +651,14 @@ class BatchSampler(object):
                 raise ValueError("onehot: shape %s, expected [%d, >= %d]"
                                  % (tuple(onehot.shape), B * int(onehot_rows), int(onehot_col0) + d.num_classes))
             ld, odt = int(onehot.shape[1]), K.abi_dtype(onehot.dtype)
-        K.call("srwn_batch_draw", d.audio.data_ptr(), None if d.labels is None else d.labels.data_ptr(), len(d),
-               d.clip_len, self.state.data_ptr(), B, T, int(self.shuffle), CROPS[self.crop], self.rank, self.world, pa, pa2,
-               pc, int(quantization_channels), po, ld, int(onehot_rows), int(onehot_col0), d.num_classes, odt,
-               self.indices.data_ptr(), K._stream())
+        args = (d.audio.data_ptr(), None if d.labels is None else d.labels.data_ptr(), len(d),
+                d.clip_len, self.state.data_ptr(), B, T, int(self.shuffle), CROPS[self.crop], self.rank, self.world, pa, pa2,
+                pc, int(quantization_channels), po, ld, int(onehot_rows), int(onehot_col0), d.num_classes, odt,
+                self.indices.data_ptr())
+        if self.augment is None:
+            K.call("srwn_batch_draw", *args, K._stream())
+        else:                                # the same rows through dataset.augment_rows, audio, audio2 and codes alike
+            K.call("srwn_batch_draw_aug", *args, *self._augment_args(), K._stream())
 
     def log_step(self, loss):
         """srwn_step_log on the current stream: ``log[step % log_capacity] = loss``, then the device step ticks."""
@@ -565,7 +791,7 @@ class PairSampler(BatchSampler):
     ``[log_capacity, pairs]`` distance ring and the left indices (``indices``), right indices and y of the last draw."""
 
     def __init__(self, dataset, pairs, num_samples, seed=0, p_same=0.5, shuffle=True, crop="head", rank=0, world=1,
-                 log_capacity=1024):
+                 log_capacity=1024, augment=None):
         if dataset.labels is None:
             raise ValueError("pair_sampler: the dataset holds no labels; pairs are drawn by class")
         self.same_threshold = same_threshold(p_same)
@@ -574,8 +800,12 @@ class PairSampler(BatchSampler):
         _check_draw(int(pairs), len(dataset), dataset.clip_len, int(num_samples), crop, int(rank), int(world))
         if int(log_capacity) < 1:
             raise ValueError("log_capacity %d: at least 1" % int(log_capacity))
+        if augment is not None:
+            if not isinstance(augment, Augment):
+                raise TypeError("augment must be an Augment, got %s" % type(augment).__name__)
+            augment.check(dataset, num_samples)
         self._index = dataset.class_index()          # (refuses labels outside the classes)
-        BatchSampler.__init__(self, dataset, pairs, num_samples, seed, shuffle, crop, rank, world, log_capacity)
+        BatchSampler.__init__(self, dataset, pairs, num_samples, seed, shuffle, crop, rank, world, log_capacity, augment)
         import torch
         dev = dataset.device
         self.pairs, self.p_same = int(pairs), float(p_same)
@@ -589,18 +819,27 @@ class PairSampler(BatchSampler):
         return pair_plan(self.seed, self.step if step is None else int(step), self.pairs, d._host_labels(), d.num_classes,
                          d.clip_len, self.num_samples, self.p_same, self.shuffle, self.crop, self.rank, self.world)
 
+    def augment_plan(self, step: Optional[int] = None):
+        """``(left, right)``: ``augment_plan`` of `step` (default: the next one) for the pairs' left clips (side 0) and
+        right clips (side 1)."""
+        return BatchSampler.augment_plan(self, step, 0), BatchSampler.augment_plan(self, step, 1)
+
     def draw(self, audio, labels):
-        """srwn_pair_draw on the current stream: the left clips into rows [0, P) and the right ones into rows [P, 2P) of
+        """srwn_pair_draw (with an ``Augment``: srwn_pair_draw_aug) on the current stream: the left clips into rows [0, P) and the right ones into rows [P, 2P) of
         `audio` ([2P, T] fp32), y into `labels` ([P] fp32); the draw's indices and y into ``indices``, ``right``, ``y``."""
         import torch
         from . import kernels as K
         d, P, T = self.dataset, self.pairs, self.num_samples
         order, place, start = self._index
-        K.call("srwn_pair_draw", d.audio.data_ptr(), d.labels.data_ptr(), order.data_ptr(), place.data_ptr(),
-               start.data_ptr(), d.num_classes, len(d), d.clip_len, self.state.data_ptr(), P, T, self.same_threshold,
-               int(self.shuffle), CROPS[self.crop], self.rank, self.world, K._chk(audio, "audio", torch.float32, (2 * P, T)),
-               K._chk(labels, "labels", torch.float32, (P,)), self.indices.data_ptr(), self.right.data_ptr(),
-               self.y.data_ptr(), K._stream())
+        args = (d.audio.data_ptr(), d.labels.data_ptr(), order.data_ptr(), place.data_ptr(),
+                start.data_ptr(), d.num_classes, len(d), d.clip_len, self.state.data_ptr(), P, T, self.same_threshold,
+                int(self.shuffle), CROPS[self.crop], self.rank, self.world, K._chk(audio, "audio", torch.float32, (2 * P, T)),
+                K._chk(labels, "labels", torch.float32, (P,)), self.indices.data_ptr(), self.right.data_ptr(),
+                self.y.data_ptr())
+        if self.augment is None:
+            K.call("srwn_pair_draw", *args, K._stream())
+        else:
+            K.call("srwn_pair_draw_aug", *args, *self._augment_args(), K._stream())
 
     def log_pairs(self, loss, dist):
         """srwn_pair_log on the current stream: the loss and the P distances into their rings, then the step ticks."""

@@ -42,7 +42,7 @@ from .serving import (  # noqa: F401
 )
 from .training import (  # noqa: F401
     _captured_step, _sampler_state, _train_step, _fit_part, _fit, _fit_capture, _fit_validated, _fit_labels,
-    _sweep_steps, _eval_sweep, _evaluate_losses, _loss_sweep_steps, _check_validate, _write_state, _read_state,
+    _sweep_steps, _eval_sweep, _evaluate_losses, _loss_sweep_steps, _refuse_augment, _check_validate, _write_state, _read_state,
     _TrainingControls, _EmaContext,
 )
 
@@ -169,6 +169,7 @@ class WaveNet(_EngineOwner):
         if not isinstance(ev, EvalSampler):
             raise TypeError("WaveNet.evaluate takes a dataset.EvalSampler (dataset.eval_sampler(...)), got %s"
                             % type(ev).__name__)
+        _refuse_augment(ev, "WaveNet")
         if ev.num_samples != self.input_size:
             raise ValueError("inputs have %d samples, the model was built for input_size=%d"
                              % (ev.num_samples, self.input_size))
@@ -1170,6 +1171,7 @@ class SiameseWaveNet(_EngineOwner):
         if not isinstance(es, EmbedSampler):
             raise TypeError("SiameseWaveNet.evaluate takes a dataset.EmbedSampler (dataset.embed_sampler(...)), got %s"
                             % type(es).__name__)
+        _refuse_augment(es, "SiameseWaveNet")
         if es.num_samples != self.input_size:
             raise ValueError("SiameseWaveNet.evaluate: the sampler draws %d samples, the model was built for input_size=%d"
                              % (es.num_samples, self.input_size))

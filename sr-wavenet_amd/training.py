@@ -238,6 +238,7 @@ def _loss_sweep_steps(sampler, who, kind=None, how="a plain dataset.BatchSampler
     from .dataset import BatchSampler
     if type(sampler) is not (kind or BatchSampler):
         raise TypeError("%s.evaluate takes %s, got %s" % (who, how, type(sampler).__name__))
+    _refuse_augment(sampler, who)
     if sampler.shuffle:
         raise ValueError("%s.evaluate: the sampler shuffles; a sweep visits the records in order (shuffle=False)" % who)
     n, per = len(sampler.dataset), sampler.batch_size * sampler.world
@@ -246,6 +247,13 @@ def _loss_sweep_steps(sampler, who, kind=None, how="a plain dataset.BatchSampler
                          "one number per batch, so a ragged last step would count wrapped-around clips twice (the "
                          "streaming scorers give per-sample likelihoods of any clip)" % (who, n, per))
     return n // per
+
+
+def _refuse_augment(sampler, who):
+    """A held-out sweep is not augmented: ``evaluate`` refuses a sampler that carries an ``Augment``."""
+    if getattr(sampler, "augment", None) is not None:
+        raise ValueError("%s.evaluate: the sampler augments its rows; a held-out sweep is not augmented (build it with "
+                         "augment=None)" % who)
 
 
 def _check_validate(validate, kind=None, how="a dataset.EvalSampler (dataset.eval_sampler(...))"):

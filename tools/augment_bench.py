@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""What augmenting the drawn batch costs on one MI355X: the draw launch alone, and a whole ``fit`` step.
+
+Launches, at 8 x 16000 out of 64 clips of 16000 (crop "head") into one audio buffer and the codes -- microseconds per launch
+of ``srwn_batch_draw`` against ``srwn_batch_draw_aug`` with a shift only (+-1600), a gain only (0.7 .. 1.3) and all three
+(the shift, the gain, 8 noise clips of 16000 + 4000 samples mixed into every row at 0.1 .. 0.5):
+
+  warm   a hipGraph of --launches launches of one draw replayed: best of --reps replays, per launch
+  cold   the same replay right after a 512 MiB buffer has been rewritten, so that clips and noise come from HBM again
+
+Steps, for the config-2 teacher (30 layers, R = 64, S = 256, softmax, bf16, batch 8 x 16000) and examples/classifier.py's
+network (20 layers, 32 / 128 channels, 4 classes, batch --classifier-batch x 16384) -- milliseconds per step, best of
+--reps regions of --steps steps with the spread (tools/fit_bench.py's regions), after a warm-up that includes the capture:
+
+  (a) fit            model.fit(sampler, steps), no augmentation
+  (b) fit, augmented the same with augment=Augment(all three)
+  (c) host loop      dataset.augment_rows in NumPy over the plans' rows, then model.train(x)
+
+usage: python tools/augment_bench.py [--steps 100] [--reps 3] [--only launches|teacher|classifier]"""
+import argparse
+import importlib
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DIL = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3
+RECORDS, NOISE_CLIPS, NOISE_EXTRA = 64, 8, 4000
+
+
+def make_clips(n, length, seed=0):
+    rng = np.random.default_rng(seed)
+    t = np.arange(length, dtype=np.float32)[None, :]
+    return (0.5 * np.sin(t * rng.uniform(0.01, 0.3, (n, 1))) + 0.05 * rng.standard_normal((n, length))).astype(np.float32)
+
+
+def settings(D, T, noise):
+    return {"shift only": D.Augment(shift=T // 10), "gain only": D.Augment(gain=(0.7, 1.3)),
+            "all three": D.Augment(shift=T // 10, gain=(0.7, 1.3), noise=noise, noise_prob=1.0, noise_volume=(0.1, 0.5))}
+
+
+def regions(run, steps, reps):
+    """ms per step of `reps` regions of `steps` steps: (best, spread)."""
+    import torch
+    v = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(steps)
+        torch.cuda.synchronize()
+        v.append((time.perf_counter() - t0) / steps * 1e3)
+    return min(v), max(v) - min(v)
+
+
+def launches(a):
+    import torch
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    B, T = 8, 16000
+    data = D.DeviceDataset(make_clips(RECORDS, T))
+    noise = D.DeviceDataset(make_clips(NOISE_CLIPS, T + NOISE_EXTRA, seed=1))
+    audio = torch.zeros((B, T), device="cuda")
+    codes = torch.zeros(B * T, dtype=torch.int32, device="cuda")
+    flush = torch.zeros(512 << 18, device="cuda")                   # 512 MiB: more than the caches hold
+    print("== draw launches, %d x %d: us per launch, best of %d (spread); warm = %d launches per replay" % (B, T, a.reps, a.launches))
+    cases = [("srwn_batch_draw", None)] + [("srwn_batch_draw_aug, " + k, v) for k, v in settings(D, T, noise).items()]
+    for name, aug in cases:
+        s = data.sampler(B, T, seed=0, augment=aug)
+        s.draw(audio, codes=codes, quantization_channels=256)
+        torch.cuda.synchronize()
+        many, one = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with torch.cuda.graph(many):
+            for _ in range(a.launches):
+                s.draw(audio, codes=codes, quantization_channels=256)
+        with torch.cuda.graph(one):
+            s.draw(audio, codes=codes, quantization_channels=256)
+        many.replay()
+        warm = regions(lambda n: many.replay(), 1, a.reps)
+        cold = []
+        for _ in range(a.reps):
+            flush.add_(1.0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            one.replay()
+            torch.cuda.synchronize()
+            cold.append((time.perf_counter() - t0) * 1e6)
+        print("   %-36s warm %8.2f (%.2f)   cold, with the replay's own launch cost %8.2f (%.2f)"
+              % (name, warm[0] * 1e3 / a.launches, warm[1] * 1e3 / a.launches, min(cold), max(cold) - min(cold)), flush=True)
+
+
+def steps(a, kind):
+    import gc
+    import torch
+    M = importlib.import_module("sr-wavenet_amd.model")
+    D = importlib.import_module("sr-wavenet_amd.dataset")
+    if kind == "teacher":
+        B, T, classes = 8, 16000, 0
+        make = lambda: M.WaveNetTeacher(T, 0, DIL, dilation_channels=64, skip_channels=256, quantization_channels=256)
+    else:
+        B, T, classes = a.classifier_batch, 16384, 4
+        make = lambda: M.WaveNet(T, classes, DIL[:20], dilation_channels=32, skip_channels=128, output_channels=classes,
+                                 learning_rate=0.001)                                        # examples/classifier.py
+    clips = make_clips(RECORDS, T)
+    nz = make_clips(NOISE_CLIPS, T + NOISE_EXTRA, seed=1)
+    labels = (np.arange(RECORDS) % classes) if classes else None
+    data = D.DeviceDataset(clips, labels, classes)
+    aug = settings(D, T, D.DeviceDataset(nz))["all three"]
+    print("== %s, batch %d x %d: ms per step, best of %d regions of %d steps (spread)" % (kind, B, T, a.reps, a.steps), flush=True)
+    out = {}
+    for key, augment in (("a", None), ("b", aug)):
+        m = make()
+        s = data.sampler(B, T, seed=0, augment=augment)
+        m.fit(s, a.warmup)
+        out[key] = regions(lambda n: m.fit(s, n), a.steps, a.reps)
+        del m, s
+        gc.collect()
+        torch.cuda.empty_cache()
+    m = make()
+    eye = np.eye(max(classes, 1), dtype=np.float32)
+    st = [0]
+
+    def host(n):
+        for _ in range(n):
+            idx, off = D.draw_plan(0, st[0], B, RECORDS, T, T)
+            plan = D.augment_plan(0, st[0], B, T, aug, NOISE_CLIPS, T + NOISE_EXTRA)
+            x = D.augment_rows(clips[idx], plan, nz)
+            m.train(x, eye[labels[idx]]) if classes else m.train(x)
+            st[0] += 1
+    host(a.warmup)
+    out["c"] = regions(host, a.steps, a.reps)
+    for key, name in (("a", "(a) fit"), ("b", "(b) fit, augmented"), ("c", "(c) host loop: augment_rows, train(x)")):
+        print("   %-40s %.4f (%.4f)" % (name, *out[key]), flush=True)
+    print("   (b) - (a) = %+.4f ms   (c) - (b) = %+.4f ms" % (out["b"][0] - out["a"][0], out["c"][0] - out["b"][0]), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--classifier-batch", type=int, default=1, help="examples/classifier.py's default")
+    ap.add_argument("--only", default=None, choices=["launches", "teacher", "classifier"])
+    a = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    for what in ([a.only] if a.only else ["launches", "teacher", "classifier"]):
+        launches(a) if what == "launches" else steps(a, what)
+
+
+if __name__ == "__main__":
+    main()
