@@ -11,7 +11,8 @@ Without ``--device-data`` this is train.py's host loop: ``train(x, y)`` per batc
 the training set and the test set are loaded onto the device once: the steps between two prints are one ``fit`` call that
 also sweeps a validation set every ``--validate-every`` steps (``fit(..., validate=...)``), and ``--test`` is one
 ``evaluate`` call.  ``--shift``, ``--gain``, ``--noise``, ``--noise-prob`` and ``--noise-volume`` augment the training draws
-there (``dataset.Augment``); the validation and test sets are never augmented."""
+there (``dataset.Augment``), and ``--speed LO:HI`` (with ``--resample-taps``) resamples every drawn clip by a random factor,
+tempo and pitch together; the validation and test sets are never augmented."""
 import argparse
 import os
 import sys

@@ -10,7 +10,8 @@
   python examples/siamese.py --train --logdir runs/siamese --steps 1000 --device-data --shift 100 --gain 0.7:1.3
 
 ``--shift``, ``--gain``, ``--noise``, ``--noise-prob`` and ``--noise-volume`` augment the pairs drawn with ``--device-data``
-(``dataset.Augment``): the two clips of a pair independently, so two views of one recording differ.
+(``dataset.Augment``): the two clips of a pair independently, so two views of one recording differ.  ``--speed LO:HI``
+(with ``--resample-taps``) resamples each clip by a random factor of its own, tempo and pitch together.
 """
 import argparse
 import os

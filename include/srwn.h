@@ -1786,6 +1786,39 @@ int srwn_pair_draw_aug(const float* clips, const int32_t* labels, const int32_t*
                        int32_t max_shift, float gain_lo, float gain_hi, const float* noise, int32_t noise_clips,
                        int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi, void* stream);
 
+/* ---- speed perturbation in the augmented draws (since srwn_version() 128; csrc/srwn_resample.hip): srwn_batch_draw_aug and
+ * srwn_pair_draw_aug with every row resampled by a factor of its own, y(j) = x(j * s), before shift, gain, noise and clamp act
+ * on it -- tempo and pitch move together, by 12 log2(s) semitones.  Everything the _aug entries say holds, and the arguments
+ * in front of the resampling block are theirs.
+ *   table            [SRWN_RESAMPLE_PHASES][taps] fp32, the polyphase low-pass dataset.resample_table states: tap k of phase
+ *                    f sits k - (taps / 2 - 1) - f / SRWN_RESAMPLE_PHASES samples from the position.  Only read.
+ *   taps             even, 2 .. 64
+ *   step_lo, step_hi speeds as fixed-point steps with 24 fraction bits, round(s * 2^24): 2^23 <= step_lo <= step_hi <= 2^25
+ * The row takes a seventh draw h = mix64((seed ^ salt) + GOLDEN * (2 p + side + 1)) (dataset.speed_plan; the other six do not
+ * move): step = step_lo + (((h >> 32) (step_hi - step_lo + 1)) >> 32).  With row[0..T) the cropped clip and +0 outside it
+ * (the record's samples beyond the crop window are never read), q = jj * step as an unsigned 64-bit integer, i = q >> 24 and
+ * f = (q >> (24 - log2 SRWN_RESAMPLE_PHASES)) & (SRWN_RESAMPLE_PHASES - 1), the resampled row (dataset.resample_rows) is
+ *   r[jj] = the sum over k = 0 .. taps - 1, in that order from +0, of fp32(table[f][k] * row[i - (taps / 2 - 1) + k]),
+ * every product and every partial sum rounded to fp32, no fused multiply-add.  The _aug entries' sample rule then reads r
+ * where it reads row: xs[j] = r[j - shift] where 0 <= j - shift < T, else +0.  All audio outputs and the codes hold y.
+ * Errors, all before any launch: the _aug entry's, and taps odd or outside [2, 64], step_lo > step_hi, a step outside
+ * [2^23, 2^25], a table that is not 4-byte aligned (-2); a null table (-3). */
+#define SRWN_RESAMPLE_PHASES 4096
+int srwn_batch_draw_warp(const float* clips, const int32_t* labels, int32_t num_clips, int64_t clip_len, const int64_t* state,
+                         int32_t B, int32_t T, int32_t shuffle, int32_t crop, int32_t rank, int32_t world, float* audio0,
+                         float* audio1, int32_t* codes, int32_t quantization_channels, void* onehot, int64_t onehot_ld,
+                         int32_t onehot_rows, int32_t onehot_col0, int32_t num_classes, int32_t onehot_dtype,
+                         int32_t* indices, int32_t max_shift, float gain_lo, float gain_hi, const float* noise,
+                         int32_t noise_clips, int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi,
+                         const float* table, int32_t taps, int32_t step_lo, int32_t step_hi, void* stream);
+int srwn_pair_draw_warp(const float* clips, const int32_t* labels, const int32_t* order, const int32_t* place,
+                        const int32_t* class_start, int32_t num_classes, int32_t num_clips, int64_t clip_len,
+                        const int64_t* state, int32_t P, int32_t T, int64_t same_threshold, int32_t shuffle, int32_t crop,
+                        int32_t rank, int32_t world, float* audio, float* y, int32_t* left, int32_t* right, float* y_log,
+                        int32_t max_shift, float gain_lo, float gain_hi, const float* noise, int32_t noise_clips,
+                        int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi, const float* table,
+                        int32_t taps, int32_t step_lo, int32_t step_hi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -319,6 +319,11 @@ SIGNATURES["srwn_adam_step_ctl"] = (C.c_int, [_p, _p, _p, _p, _p, _i64, _p, _p, 
 _AUG = [_i32, _f32, _f32, _p, _i32, _i64, _i64, _f32, _f32]
 SIGNATURES["srwn_batch_draw_aug"] = (C.c_int, SIGNATURES["srwn_batch_draw"][1][:-1] + _AUG + [_p])
 SIGNATURES["srwn_pair_draw_aug"] = (C.c_int, SIGNATURES["srwn_pair_draw"][1][:-1] + _AUG + [_p])
+# speed perturbation (srwn_version() 128): the augmented draws with the resampling block behind the augmentation block --
+# the polyphase table, its taps, the fixed-point step range
+_WARP = [_p, _i32, _i32, _i32]
+SIGNATURES["srwn_batch_draw_warp"] = (C.c_int, SIGNATURES["srwn_batch_draw_aug"][1][:-1] + _WARP + [_p])
+SIGNATURES["srwn_pair_draw_warp"] = (C.c_int, SIGNATURES["srwn_pair_draw_aug"][1][:-1] + _WARP + [_p])
 
 _lib = None
 BINDING = None     # "pybind11" or "ctypes" once loaded

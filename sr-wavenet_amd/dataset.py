@@ -36,6 +36,11 @@ volume, per row and per step, in the draw launch itself.  ``augment_plan`` state
 sample rule; the kernels give their bits.  A ``PairSampler`` augments the two clips of a pair as two sides of one position,
 so two views of one record differ.  Evaluation sweeps are not augmented.
 
+``Augment(speed=(lo, hi))`` adds speed perturbation in front of that rule (csrc/srwn_resample.hip): every row is resampled
+by a factor of its own near 1, ``y(j) = x(j * s)``, through a windowed-sinc polyphase table -- tempo and pitch move
+together, by ``12 log2(s)`` semitones.  ``speed_plan`` states the row's fixed-point step, ``resample_table`` the filter and
+``resample_rows`` the sample rule; shift, gain, noise and clamp then act on the resampled row.
+
 Storage is fp32 only: int16 or bf16 clip storage is out of scope.
 """
 from __future__ import annotations
@@ -58,6 +63,11 @@ AUG_COIN_SALT = 0x617567636F696E21      # ... whether noise is mixed in
 AUG_PICK_SALT = 0x6175677069636B21      # ... the noise record
 AUG_OFFSET_SALT = 0x6175676F66667374    # ... where its window starts
 AUG_VOLUME_SALT = 0x617567766F6C2121    # ... and its volume
+AUG_SPEED_SALT = 0x6175677370656564     # ... and the step it is resampled at
+SPEED_BITS = 24            # a speed is a fixed-point step with this many fraction bits: step = round(s * 2^24)
+SPEED_ONE = 1 << SPEED_BITS
+RESAMPLE_PHASES = 4096     # phases of the polyphase table (SRWN_RESAMPLE_PHASES in srwn.h); a power of two
+RESAMPLE_BETA = 7.0        # its Kaiser window (DESIGN section 5f says why these two)
 _ROUNDS = 4
 CROPS = {"head": 0, "random": 1}
 MAX_BATCH = 65535          # rows of one draw (the launch's second grid dimension)
@@ -395,10 +405,17 @@ class Augment(object):
     """What an augmenting sampler does to every drawn row, immutable: a shift uniform on [-shift, shift] samples with zero
     fill, a gain uniform on ``gain`` and, with probability ``noise_prob``, a window of a clip of the ``DeviceDataset``
     ``noise`` (its labels are unused) added at a volume uniform on ``noise_volume``.  Amplitudes are linear.  The defaults
-    change nothing but the sign of a zero (``augment_rows``)."""
-    __slots__ = ("shift", "gain", "noise", "noise_prob", "noise_volume", "noise_threshold")
+    change nothing but the sign of a zero (``augment_rows``).
 
-    def __init__(self, shift=0, gain=(1.0, 1.0), noise=None, noise_prob=0.0, noise_volume=(0.0, 0.0)):
+    ``speed=(lo, hi)``, 0.5 <= lo <= hi <= 2: before all that the row is resampled by a factor s of its own, ``y(j) =
+    x(j * s)`` -- s > 1 plays faster and higher, by ``12 log2(s)`` semitones, and the content ends at T / s -- through a
+    windowed-sinc table of ``taps`` taps (even, 2 .. 64) per phase, cut off for the fastest speed (``resample_table``).
+    The row's step is uniform on the fixed-point steps ``[step_lo, step_hi] = round(speed * 2^24)`` (``speed_plan``)."""
+    __slots__ = ("shift", "gain", "noise", "noise_prob", "noise_volume", "noise_threshold", "speed", "taps", "step_lo",
+                 "step_hi")
+
+    def __init__(self, shift=0, gain=(1.0, 1.0), noise=None, noise_prob=0.0, noise_volume=(0.0, 0.0), speed=(1.0, 1.0),
+                 taps=16):
         if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 0 <= int(shift) < 1 << 31:
             raise ValueError("shift %r: a number of samples, at least 0" % (shift,))
         if noise is not None and not isinstance(noise, DeviceDataset):
@@ -416,6 +433,18 @@ class Augment(object):
                              % (noise_prob,))
         set_(self, "noise", noise)
         set_(self, "noise_prob", float(noise_prob))
+        try:
+            lo, hi = (float(v) for v in speed)
+        except (TypeError, ValueError):
+            raise ValueError("speed %r: a range (lo, hi)" % (speed,))
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0.5 <= lo <= hi <= 2.0):
+            raise ValueError("speed %r: finite factors, 0.5 <= lo <= hi <= 2" % (speed,))
+        if isinstance(taps, bool) or not isinstance(taps, (int, np.integer)) or not 2 <= int(taps) <= 64 or int(taps) % 2:
+            raise ValueError("taps %r: an even number of taps, 2 to 64" % (taps,))
+        set_(self, "speed", (lo, hi))
+        set_(self, "taps", int(taps))
+        set_(self, "step_lo", int(round(lo * SPEED_ONE)))
+        set_(self, "step_hi", int(round(hi * SPEED_ONE)))
 
     def __setattr__(self, name, value=None):
         raise AttributeError("an Augment is immutable")
@@ -423,9 +452,23 @@ class Augment(object):
     __delattr__ = __setattr__
 
     def __repr__(self):
-        return "Augment(shift=%d, gain=%r, noise=%s, noise_prob=%r, noise_volume=%r)" % (
+        return "Augment(shift=%d, gain=%r, noise=%s, noise_prob=%r, noise_volume=%r%s)" % (
             self.shift, self.gain, "None" if self.noise is None else "<%d clips>" % len(self.noise), self.noise_prob,
-            self.noise_volume)
+            self.noise_volume, ", speed=%r, taps=%d" % (self.speed, self.taps) if self.resamples else "")
+
+    @property
+    def resamples(self) -> bool:
+        """Whether a draw resamples its rows: any speed but exactly (1, 1) (then the draw is the ``_aug`` entry's)."""
+        return (self.step_lo, self.step_hi) != (SPEED_ONE, SPEED_ONE)
+
+    @property
+    def cutoff(self) -> float:
+        """The table's cutoff as a fraction of Nyquist: ``min(1, 1 / hi)``, so the fastest speed folds nothing back."""
+        return min(1.0, 1.0 / self.speed[1])
+
+    def table(self) -> np.ndarray:
+        """``resample_table(cutoff, taps)``: the one table of this Augment."""
+        return resample_table(self.cutoff, self.taps)
 
     def check(self, dataset, num_samples: int) -> None:
         """What only a sampler knows: the shift stays inside the row, the noise lives beside the clips and covers a row."""
@@ -520,6 +563,97 @@ def augment_rows(rows, plan: "AugmentPlan", noise_clips=None) -> np.ndarray:
     return out
 
 
+def speed_plan(seed: int, step: int, batch_size: int, augment: "Augment", rank: int = 0, world: int = 1,
+               side: int = 0) -> np.ndarray:
+    """The fixed-point resampling steps of the rows of ``step``, int64 [B]: row b at ``draw_plan``'s position p draws
+    ``h = _mix64((seed ^ AUG_SPEED_SALT) + _GOLDEN * (2 * p + side + 1))`` -- the key of ``augment_plan``'s six draws under
+    a seventh salt, so none of them moves -- and its step is ``step_lo + (((h >> 32) * (step_hi - step_lo + 1)) >> 32)``,
+    uniform on the integers [step_lo, step_hi].  A step q means speed q / 2^24: no float decides a position."""
+    batch_size = int(batch_size)
+    if not isinstance(augment, Augment):
+        raise TypeError("augment must be an Augment, got %s" % type(augment).__name__)
+    if not 1 <= batch_size <= MAX_BATCH:
+        raise ValueError("batch_size %d: at least 1, at most %d" % (batch_size, MAX_BATCH))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d of %d" % (rank, world))
+    if side not in (0, 1):
+        raise ValueError("side %r: 0 or 1" % (side,))
+    seed &= _MASK
+    lo_q, hi_q = augment.step_lo, augment.step_hi
+    out = np.empty(batch_size, np.int64)
+    for b in range(batch_size):
+        p = (step * world + rank) * batch_size + b
+        h = _mix64((seed ^ AUG_SPEED_SALT) + _GOLDEN * (2 * p + side + 1))
+        out[b] = lo_q + (((h >> 32) * (hi_q - lo_q + 1)) >> 32)
+    return out
+
+
+_TABLES = {}
+
+
+def resample_table(cutoff: float, taps: int) -> np.ndarray:
+    """The polyphase low-pass of ``resample_rows``, float32 [RESAMPLE_PHASES, taps], read-only.  Tap k of phase f sits at
+    distance ``d = k - (taps / 2 - 1) - f / RESAMPLE_PHASES`` samples from the position and weighs ``cutoff * sinc(cutoff *
+    d)`` under a Kaiser window of ``RESAMPLE_BETA`` over |d| <= taps / 2, in float64; every phase row is then divided by
+    its sum (a constant passes unchanged at any phase) and rounded once to float32.  `cutoff` is a fraction of Nyquist in
+    (0, 1]; at 1 phase 0 is written as the exact unit impulse (its sinc has its zeros on the other taps up to rounding)."""
+    cutoff, taps = float(cutoff), int(taps)
+    if not 0.0 < cutoff <= 1.0:
+        raise ValueError("cutoff %r: a fraction of Nyquist in (0, 1]" % (cutoff,))
+    if not 2 <= taps <= 64 or taps % 2:
+        raise ValueError("taps %r: an even number of taps, 2 to 64" % (taps,))
+    if (cutoff, taps) not in _TABLES:
+        half = taps // 2
+        d = (np.arange(taps, dtype=np.float64) - (half - 1))[None, :] - \
+            (np.arange(RESAMPLE_PHASES, dtype=np.float64) / RESAMPLE_PHASES)[:, None]
+        w = np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(0.0, 1.0 - (d / half) ** 2))) / np.i0(RESAMPLE_BETA)
+        h = cutoff * np.sinc(cutoff * d) * w
+        h /= h.sum(axis=1, keepdims=True)
+        if cutoff == 1.0:
+            h[0] = 0.0
+            h[0, half - 1] = 1.0
+        t = h.astype(np.float32)
+        t.setflags(write=False)
+        _TABLES[(cutoff, taps)] = t
+    return _TABLES[(cutoff, taps)]
+
+
+def resample_rows(rows, steps, table) -> np.ndarray:
+    """The resampling rule on the cropped rows ``[B, T]``, in fp32 with integer positions.  With P = RESAMPLE_PHASES and
+    ``q = j * steps[b]`` (an unsigned 64-bit integer): ``i = q >> 24`` is the source sample at or before the position and
+    ``f = (q >> (24 - log2 P)) & (P - 1)`` the phase, selected by floor.  ``r[j]`` is accumulated in tap order k = 0 ..
+    taps - 1 from +0.0: ``acc = fp32(acc + fp32(table[f, k] * x[i - (taps / 2 - 1) + k]))``, every operation rounded
+    separately, with x = +0.0 outside [0, T) of the row -- samples of the record beyond the crop window are never read.
+    The position is anchored at the row's first sample: r[0] filters around x[0], and a row played faster ends at T / s
+    with zeros behind (kws_streaming's resample, then pad or crop at the end)."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+    table = np.asarray(table, dtype=np.float32)
+    if x.ndim != 2 or x.shape[0] != steps.shape[0]:
+        raise ValueError("rows must be [%d, T], got %s" % (steps.shape[0], tuple(x.shape)))
+    if table.ndim != 2 or table.shape[0] != RESAMPLE_PHASES or table.shape[1] % 2 or not 2 <= table.shape[1] <= 64:
+        raise ValueError("table must be [%d, taps], got %s" % (RESAMPLE_PHASES, tuple(table.shape)))
+    if steps.min() < SPEED_ONE // 2 or steps.max() > 2 * SPEED_ONE:
+        raise ValueError("steps outside [2^23, 2^25]")
+    B, T = x.shape
+    taps = table.shape[1]
+    shift = SPEED_BITS - (RESAMPLE_PHASES.bit_length() - 1)
+    out = np.empty_like(x)
+    j = np.arange(T, dtype=np.uint64)
+    for b in range(B):
+        q = j * np.uint64(steps[b])
+        i = (q >> np.uint64(SPEED_BITS)).astype(np.int64)
+        f = ((q >> np.uint64(shift)) & np.uint64(RESAMPLE_PHASES - 1)).astype(np.int64)
+        acc = np.zeros(T, np.float32)
+        with np.errstate(all="ignore"):
+            for k in range(taps):
+                at = i - (taps // 2 - 1) + k
+                xk = np.where((at >= 0) & (at < T), x[b, np.clip(at, 0, T - 1)], np.float32(0.0)).astype(np.float32)
+                acc = (acc + (table[f, k] * xk).astype(np.float32)).astype(np.float32)
+        out[b] = acc
+    return out
+
+
 def add_augment_flags(parser) -> None:
     """The drivers' augmentation flags (examples/classifier.py, examples/siamese.py); ``augment_from_flags`` reads them."""
     g = parser.add_argument_group("augmentation (--device-data)")
@@ -528,6 +662,9 @@ def add_augment_flags(parser) -> None:
     g.add_argument("--noise", type=str, default=None, metavar="FILE.npy", help="background clips to mix in: an [M, len] array")
     g.add_argument("--noise-prob", type=float, default=0.0, metavar="P", help="mix noise into a drawn clip with probability P")
     g.add_argument("--noise-volume", type=str, default=None, metavar="LO:HI", help="volume of the noise, uniform on [LO, HI]")
+    g.add_argument("--speed", type=str, default=None, metavar="LO:HI",
+                   help="resample every drawn clip by a factor uniform on [LO, HI] within [0.5, 2]: tempo and pitch together")
+    g.add_argument("--resample-taps", type=int, default=None, metavar="N", help="taps of the resampling filter (even, 2..64; 16)")
 
 
 def _flag_range(text, name):
@@ -542,7 +679,9 @@ def augment_from_flags(args, device_data: bool, device="cuda") -> Optional["Augm
     """The ``Augment`` the flags of ``add_augment_flags`` ask for, or None when none of them is set.  They act in the draw
     launch, so without --device-data they are refused here, not ignored.  The noise file is uploaded once."""
     asked = [f for f, on in (("--shift", args.shift != 0), ("--gain", args.gain is not None), ("--noise", args.noise is not None),
-                             ("--noise-prob", args.noise_prob != 0.0), ("--noise-volume", args.noise_volume is not None)) if on]
+                             ("--noise-prob", args.noise_prob != 0.0), ("--noise-volume", args.noise_volume is not None),
+                             ("--speed", getattr(args, "speed", None) is not None),
+                             ("--resample-taps", getattr(args, "resample_taps", None) is not None)) if on]
     if not asked:
         return None
     if not device_data:
@@ -556,7 +695,9 @@ def augment_from_flags(args, device_data: bool, device="cuda") -> Optional["Augm
         noise = DeviceDataset(clips.astype(np.float32), device=device)
     try:
         return Augment(args.shift, (1.0, 1.0) if args.gain is None else _flag_range(args.gain, "gain"), noise,
-                       args.noise_prob, (0.0, 0.0) if args.noise_volume is None else _flag_range(args.noise_volume, "noise-volume"))
+                       args.noise_prob, (0.0, 0.0) if args.noise_volume is None else _flag_range(args.noise_volume, "noise-volume"),
+                       (1.0, 1.0) if getattr(args, "speed", None) is None else _flag_range(args.speed, "speed"),
+                       16 if getattr(args, "resample_taps", None) is None else args.resample_taps)
     except (TypeError, ValueError) as e:
         raise SystemExit("augmentation flags: %s" % e)
 
@@ -573,6 +714,7 @@ class BatchSampler(object):
     have drawn next."""
 
     augment = None           # an Augment, or None: the plain draw (class default: objects made without __init__ have none)
+    _resample_dev = None     # the Augment's resampling table on the clips' device, uploaded by the first draw that needs it
 
     def __init__(self, dataset, batch_size, num_samples, seed=0, shuffle=True, crop="head", rank=0, world=1,
                  log_capacity=1024, augment=None):
@@ -618,6 +760,21 @@ class BatchSampler(object):
         return (a.shift, a.gain[0], a.gain[1], None if nz is None else nz.audio.data_ptr(), 0 if nz is None else len(nz),
                 0 if nz is None else nz.clip_len, a.noise_threshold, a.noise_volume[0], a.noise_volume[1])
 
+    def speed_plan(self, step: Optional[int] = None, side: int = 0) -> np.ndarray:
+        """``speed_plan`` of `step` (default: the next one) for this sampler's ``augment``."""
+        if self.augment is None:
+            raise ValueError("this sampler does not augment (it was built with augment=None)")
+        return speed_plan(self.seed, self.step if step is None else int(step), self.batch_size, self.augment, self.rank,
+                          self.world, side)
+
+    def _resample_args(self):
+        """The resampling block of the ``_warp`` entries (srwn.h), behind the augmentation block."""
+        a = self.augment
+        if self._resample_dev is None:
+            import torch
+            self._resample_dev = torch.as_tensor(a.table().copy()).to(self.dataset.device)    # (the cached one is read-only)
+        return (self._resample_dev.data_ptr(), a.taps, a.step_lo, a.step_hi)
+
     def seek(self, step: int) -> None:
         """Continues the sequence at `step` (a run resumed from a checkpoint): sets the device counter and the host's."""
         if int(step) < 0:
@@ -657,8 +814,10 @@ class BatchSampler(object):
                 self.indices.data_ptr())
         if self.augment is None:
             K.call("srwn_batch_draw", *args, K._stream())
-        else:                                # the same rows through dataset.augment_rows, audio, audio2 and codes alike
+        elif not self.augment.resamples:     # the same rows through dataset.augment_rows, audio, audio2 and codes alike
             K.call("srwn_batch_draw_aug", *args, *self._augment_args(), K._stream())
+        else:                                # ... through dataset.resample_rows first
+            K.call("srwn_batch_draw_warp", *args, *self._augment_args(), *self._resample_args(), K._stream())
 
     def log_step(self, loss):
         """srwn_step_log on the current stream: ``log[step % log_capacity] = loss``, then the device step ticks."""
@@ -824,6 +983,12 @@ class PairSampler(BatchSampler):
         right clips (side 1)."""
         return BatchSampler.augment_plan(self, step, 0), BatchSampler.augment_plan(self, step, 1)
 
+    def speed_plan(self, step: Optional[int] = None, side: Optional[int] = None):
+        """``speed_plan`` of `step` (default: the next one): ``(left, right)``, or one `side` of the pairs."""
+        if side is None:
+            return BatchSampler.speed_plan(self, step, 0), BatchSampler.speed_plan(self, step, 1)
+        return BatchSampler.speed_plan(self, step, side)
+
     def draw(self, audio, labels):
         """srwn_pair_draw (with an ``Augment``: srwn_pair_draw_aug) on the current stream: the left clips into rows [0, P) and the right ones into rows [P, 2P) of
         `audio` ([2P, T] fp32), y into `labels` ([P] fp32); the draw's indices and y into ``indices``, ``right``, ``y``."""
@@ -838,8 +1003,10 @@ class PairSampler(BatchSampler):
                 self.y.data_ptr())
         if self.augment is None:
             K.call("srwn_pair_draw", *args, K._stream())
-        else:
+        elif not self.augment.resamples:
             K.call("srwn_pair_draw_aug", *args, *self._augment_args(), K._stream())
+        else:
+            K.call("srwn_pair_draw_warp", *args, *self._augment_args(), *self._resample_args(), K._stream())
 
     def log_pairs(self, loss, dist):
         """srwn_pair_log on the current stream: the loss and the P distances into their rings, then the step ticks."""

@@ -3,7 +3,8 @@
 
 Launches, at 8 x 16000 out of 64 clips of 16000 (crop "head") into one audio buffer and the codes -- microseconds per launch
 of ``srwn_batch_draw`` against ``srwn_batch_draw_aug`` with a shift only (+-1600), a gain only (0.7 .. 1.3) and all three
-(the shift, the gain, 8 noise clips of 16000 + 4000 samples mixed into every row at 0.1 .. 0.5):
+(the shift, the gain, 8 noise clips of 16000 + 4000 samples mixed into every row at 0.1 .. 0.5), and against
+``srwn_batch_draw_warp`` with a speed only (0.9 .. 1.1, 16 taps) and with all three behind it:
 
   warm   a hipGraph of --launches launches of one draw replayed: best of --reps replays, per launch
   cold   the same replay right after a 512 MiB buffer has been rewritten, so that clips and noise come from HBM again
@@ -15,6 +16,8 @@ network (20 layers, 32 / 128 channels, 4 classes, batch --classifier-batch x 163
   (a) fit            model.fit(sampler, steps), no augmentation
   (b) fit, augmented the same with augment=Augment(all three)
   (c) host loop      dataset.augment_rows in NumPy over the plans' rows, then model.train(x)
+  (d) fit, resampled (b) with speed=(0.9, 1.1): the draw is srwn_batch_draw_warp
+  (e) host loop      dataset.resample_rows, then dataset.augment_rows, then model.train(x)
 
 usage: python tools/augment_bench.py [--steps 100] [--reps 3] [--only launches|teacher|classifier]"""
 import argparse
@@ -28,6 +31,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIL = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512] * 3
 RECORDS, NOISE_CLIPS, NOISE_EXTRA = 64, 8, 4000
+SPEED = (0.9, 1.1)
 
 
 def make_clips(n, length, seed=0):
@@ -38,7 +42,10 @@ def make_clips(n, length, seed=0):
 
 def settings(D, T, noise):
     return {"shift only": D.Augment(shift=T // 10), "gain only": D.Augment(gain=(0.7, 1.3)),
-            "all three": D.Augment(shift=T // 10, gain=(0.7, 1.3), noise=noise, noise_prob=1.0, noise_volume=(0.1, 0.5))}
+            "all three": D.Augment(shift=T // 10, gain=(0.7, 1.3), noise=noise, noise_prob=1.0, noise_volume=(0.1, 0.5)),
+            "speed only": D.Augment(speed=SPEED),
+            "speed, all three": D.Augment(shift=T // 10, gain=(0.7, 1.3), noise=noise, noise_prob=1.0, noise_volume=(0.1, 0.5),
+                                          speed=SPEED)}
 
 
 def regions(run, steps, reps):
@@ -64,7 +71,8 @@ def launches(a):
     codes = torch.zeros(B * T, dtype=torch.int32, device="cuda")
     flush = torch.zeros(512 << 18, device="cuda")                   # 512 MiB: more than the caches hold
     print("== draw launches, %d x %d: us per launch, best of %d (spread); warm = %d launches per replay" % (B, T, a.reps, a.launches))
-    cases = [("srwn_batch_draw", None)] + [("srwn_batch_draw_aug, " + k, v) for k, v in settings(D, T, noise).items()]
+    cases = [("srwn_batch_draw", None)] + [("srwn_batch_draw_%s, %s" % ("warp" if v.resamples else "aug", k), v)
+                                           for k, v in settings(D, T, noise).items()]
     for name, aug in cases:
         s = data.sampler(B, T, seed=0, augment=aug)
         s.draw(audio, codes=codes, quantization_channels=256)
@@ -106,9 +114,10 @@ def steps(a, kind):
     labels = (np.arange(RECORDS) % classes) if classes else None
     data = D.DeviceDataset(clips, labels, classes)
     aug = settings(D, T, D.DeviceDataset(nz))["all three"]
+    warp = settings(D, T, aug.noise)["speed, all three"]
     print("== %s, batch %d x %d: ms per step, best of %d regions of %d steps (spread)" % (kind, B, T, a.reps, a.steps), flush=True)
     out = {}
-    for key, augment in (("a", None), ("b", aug)):
+    for key, augment in (("a", None), ("b", aug), ("d", warp)):
         m = make()
         s = data.sampler(B, T, seed=0, augment=augment)
         m.fit(s, a.warmup)
@@ -120,18 +129,25 @@ def steps(a, kind):
     eye = np.eye(max(classes, 1), dtype=np.float32)
     st = [0]
 
-    def host(n):
+    def host(n, resample=False):
         for _ in range(n):
             idx, off = D.draw_plan(0, st[0], B, RECORDS, T, T)
             plan = D.augment_plan(0, st[0], B, T, aug, NOISE_CLIPS, T + NOISE_EXTRA)
-            x = D.augment_rows(clips[idx], plan, nz)
+            x = clips[idx]
+            if resample:
+                x = D.resample_rows(x, D.speed_plan(0, st[0], B, warp), warp.table())
+            x = D.augment_rows(x, plan, nz)
             m.train(x, eye[labels[idx]]) if classes else m.train(x)
             st[0] += 1
     host(a.warmup)
     out["c"] = regions(host, a.steps, a.reps)
-    for key, name in (("a", "(a) fit"), ("b", "(b) fit, augmented"), ("c", "(c) host loop: augment_rows, train(x)")):
-        print("   %-40s %.4f (%.4f)" % (name, *out[key]), flush=True)
-    print("   (b) - (a) = %+.4f ms   (c) - (b) = %+.4f ms" % (out["b"][0] - out["a"][0], out["c"][0] - out["b"][0]), flush=True)
+    out["e"] = regions(lambda n: host(n, True), a.steps, a.reps)
+    for key, name in (("a", "(a) fit"), ("b", "(b) fit, augmented"), ("c", "(c) host loop: augment_rows, train(x)"),
+                      ("d", "(d) fit, resampled and augmented"), ("e", "(e) host loop: resample_rows, augment_rows, train(x)")):
+        print("   %-52s %.4f (%.4f)" % (name, *out[key]), flush=True)
+    print("   (b) - (a) = %+.4f ms   (c) - (b) = %+.4f ms   (d) - (a) = %+.4f ms   (e) - (d) = %+.4f ms"
+          % (out["b"][0] - out["a"][0], out["c"][0] - out["b"][0], out["d"][0] - out["a"][0], out["e"][0] - out["d"][0]),
+          flush=True)
 
 
 def main():
