@@ -12,7 +12,9 @@ the training set and the test set are loaded onto the device once: the steps bet
 also sweeps a validation set every ``--validate-every`` steps (``fit(..., validate=...)``), and ``--test`` is one
 ``evaluate`` call.  ``--shift``, ``--gain``, ``--noise``, ``--noise-prob`` and ``--noise-volume`` augment the training draws
 there (``dataset.Augment``), and ``--speed LO:HI`` (with ``--resample-taps``) resamples every drawn clip by a random factor,
-tempo and pitch together; the validation and test sets are never augmented."""
+tempo and pitch together; ``--rir FILE.npy`` with ``--rir-prob P`` convolves a drawn clip with one of the file's room
+impulse responses (``dataset.prepare_rirs``, ``dataset.synthetic_rirs``).  The validation and test sets are never
+augmented."""
 import argparse
 import os
 import sys

@@ -12,6 +12,8 @@
 ``--shift``, ``--gain``, ``--noise``, ``--noise-prob`` and ``--noise-volume`` augment the pairs drawn with ``--device-data``
 (``dataset.Augment``): the two clips of a pair independently, so two views of one recording differ.  ``--speed LO:HI``
 (with ``--resample-taps``) resamples each clip by a random factor of its own, tempo and pitch together.
+``--rir FILE.npy`` with ``--rir-prob P`` reverberates each clip with a room impulse response of its own: two views of one
+recording then differ the way two rooms do.
 """
 import argparse
 import os

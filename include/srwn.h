@@ -1819,6 +1819,42 @@ int srwn_pair_draw_warp(const float* clips, const int32_t* labels, const int32_t
                         int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi, const float* table,
                         int32_t taps, int32_t step_lo, int32_t step_hi, void* stream);
 
+/* ---- room reverberation in the augmented draws (since srwn_version() 129; csrc/srwn_room.hip): srwn_batch_draw_warp and
+ * srwn_pair_draw_warp with a row convolved with a room impulse response between resampling and shift, gain, noise and clamp.
+ * Everything the _warp entries say holds, and the arguments in front of the room block are theirs, with one addition:
+ * table == NULL with taps == 0 and step_lo == step_hi == 2^24 means "no resampling" -- the row is the cropped clip, as in the
+ * _aug entries (through the table, phase 0 would turn a -0.0 into +0.0).
+ *   rir              [rir_clips][rir_len] fp32, the impulse responses.  Only read.
+ *   rir_clips        >= 1
+ *   rir_len          K, 1 .. SRWN_ROOM_MAX_TAPS
+ *   rir_threshold    floor(reverb_prob * 2^32), in [0, 2^32]
+ * The row takes an eighth and a ninth draw h = mix64((seed ^ salt) + GOLDEN * (2 p + side + 1)) (dataset.reverb_plan; the
+ * other seven do not move): it is reverberated where (h_coin >> 32) < rir_threshold, with the response
+ * ((h_pick >> 32) rir_clips) >> 32.  With r[0..T) the resampled (or cropped) row and +0 outside it, and h that response,
+ *   e[jj] = the sum over k = 0 .. K - 1, in that order from +0, of fp32(h[k] * r[jj - k]),
+ * every product and every partial sum rounded to fp32, no fused multiply-add, subnormals kept (dataset.reverb_rows): the
+ * tail beyond T is cut.  The sample rule then reads e where it reads r: xs[j] = e[j - shift] where 0 <= j - shift < T, else
+ * +0; the noise is added dry.  A row whose coin is off has the bits the _warp (or, without a table, the _aug) entry gives it.
+ * Errors, all before any launch: the _aug and _warp entries' (a null table with taps or another step: -3), and rir_clips < 1,
+ * rir_len outside [1, SRWN_ROOM_MAX_TAPS], rir_threshold outside [0, 2^32], rir not 4-byte aligned (-2); a null rir (-3). */
+#define SRWN_ROOM_MAX_TAPS 8192
+int srwn_batch_draw_room(const float* clips, const int32_t* labels, int32_t num_clips, int64_t clip_len, const int64_t* state,
+                         int32_t B, int32_t T, int32_t shuffle, int32_t crop, int32_t rank, int32_t world, float* audio0,
+                         float* audio1, int32_t* codes, int32_t quantization_channels, void* onehot, int64_t onehot_ld,
+                         int32_t onehot_rows, int32_t onehot_col0, int32_t num_classes, int32_t onehot_dtype,
+                         int32_t* indices, int32_t max_shift, float gain_lo, float gain_hi, const float* noise,
+                         int32_t noise_clips, int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi,
+                         const float* table, int32_t taps, int32_t step_lo, int32_t step_hi, const float* rir,
+                         int32_t rir_clips, int32_t rir_len, int64_t rir_threshold, void* stream);
+int srwn_pair_draw_room(const float* clips, const int32_t* labels, const int32_t* order, const int32_t* place,
+                        const int32_t* class_start, int32_t num_classes, int32_t num_clips, int64_t clip_len,
+                        const int64_t* state, int32_t P, int32_t T, int64_t same_threshold, int32_t shuffle, int32_t crop,
+                        int32_t rank, int32_t world, float* audio, float* y, int32_t* left, int32_t* right, float* y_log,
+                        int32_t max_shift, float gain_lo, float gain_hi, const float* noise, int32_t noise_clips,
+                        int64_t noise_len, int64_t noise_threshold, float volume_lo, float volume_hi, const float* table,
+                        int32_t taps, int32_t step_lo, int32_t step_hi, const float* rir, int32_t rir_clips,
+                        int32_t rir_len, int64_t rir_threshold, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -324,6 +324,11 @@ SIGNATURES["srwn_pair_draw_aug"] = (C.c_int, SIGNATURES["srwn_pair_draw"][1][:-1
 _WARP = [_p, _i32, _i32, _i32]
 SIGNATURES["srwn_batch_draw_warp"] = (C.c_int, SIGNATURES["srwn_batch_draw_aug"][1][:-1] + _WARP + [_p])
 SIGNATURES["srwn_pair_draw_warp"] = (C.c_int, SIGNATURES["srwn_pair_draw_aug"][1][:-1] + _WARP + [_p])
+# room reverberation (srwn_version() 129): the resampling draws with the room block behind the resampling block -- the
+# impulse responses, their count, their taps, the coin's threshold
+_ROOM = [_p, _i32, _i32, _i64]
+SIGNATURES["srwn_batch_draw_room"] = (C.c_int, SIGNATURES["srwn_batch_draw_warp"][1][:-1] + _ROOM + [_p])
+SIGNATURES["srwn_pair_draw_room"] = (C.c_int, SIGNATURES["srwn_pair_draw_warp"][1][:-1] + _ROOM + [_p])
 
 _lib = None
 BINDING = None     # "pybind11" or "ctypes" once loaded

@@ -19,7 +19,7 @@ PYB_SRC = os.path.join(CSRC, "srwn_pybind.cpp")   # generated from _lib.SIGNATUR
 PYB_NAME = "_srwn_pyb"
 IO_SOURCES = ["srwn_tfrecord.cpp"]
 CXX = os.environ.get("CXX", "g++")
-SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_ncstream.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip", "srwn_wngate.hip", "srwn_stream.hip", "srwn_recog.hip", "srwn_score.hip", "srwn_embed.hip", "srwn_flow_inv.hip", "srwn_data.hip", "srwn_draw.hip", "srwn_augment.hip", "srwn_resample.hip", "srwn_eval.hip", "srwn_pair_eval.hip"]
+SOURCES = ["srwn_util.hip", "srwn_fwd.hip", "srwn_bwd.hip", "srwn_opt.hip", "srwn_pool.hip", "srwn_gemm.hip", "srwn_wgrad2.hip", "srwn_gen.hip", "srwn_gen16.hip", "srwn_flow.hip", "srwn_enc.hip", "srwn_nc.hip", "srwn_ncstream.hip", "srwn_group.hip", "srwn_wgradt.hip", "srwn_ops.hip", "srwn_head.hip", "srwn_siamese.hip", "srwn_wngate.hip", "srwn_stream.hip", "srwn_recog.hip", "srwn_score.hip", "srwn_embed.hip", "srwn_flow_inv.hip", "srwn_data.hip", "srwn_draw.hip", "srwn_augment.hip", "srwn_resample.hip", "srwn_room.hip", "srwn_eval.hip", "srwn_pair_eval.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-pass-failed", "-ffp-contract=on"]
 # Kernels that fetch REGISTER operands with loads the compiler does not see (inline asm, hand-counted waits) must not
@@ -35,7 +35,8 @@ NO_SPILL = {"srwn_wgradt.hip": ["wgrad_skip_wt_kernel"], "srwn_siamese.hip": ["c
             "srwn_ncstream.hip": ["nc_encode_frames_kernel", "nc_encode_frames_kernelINS_10NcListArgs"],
             "srwn_recog.hip": ["pooled_stream_head_kernel"], "srwn_score.hip": ["stream_score_head_kernel"],
             "srwn_embed.hip": ["window_embed_match_kernel", "gallery_match_kernel"],
-            "srwn_pair_eval.hip": ["embed_collect_kernel", "pair_sweep_kernel"]}
+            "srwn_pair_eval.hip": ["embed_collect_kernel", "pair_sweep_kernel"],
+            "srwn_room.hip": ["batch_draw_room_kernel", "pair_draw_room_kernel"]}
 
 
 def _deps():

@@ -1,4 +1,4 @@
-// What the augmenting draw launches share (csrc/srwn_augment.hip, csrc/srwn_resample.hip): a row's draws as
+// What the augmenting draw launches share (csrc/srwn_augment.hip, csrc/srwn_resample.hip, csrc/srwn_room.hip): a row's draws as
 // dataset.augment_plan states them, the sample rule's mix and clamp (dataset.augment_rows), the right record of a pair
 // (dataset.pair_plan) and the host-side check of the augmentation block, so that a row has one plan wherever it is drawn.
 #pragma once

@@ -26,7 +26,7 @@ int check_launch(const char* what) {
 }
 }  // namespace srwn
 
-extern "C" int srwn_version(void) { return 128; }
+extern "C" int srwn_version(void) { return 129; }
 extern "C" const char* srwn_last_error(void) { return g_err; }
 
 // ------------------------------------------------------------------------------------------

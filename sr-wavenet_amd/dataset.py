@@ -64,10 +64,13 @@ AUG_PICK_SALT = 0x6175677069636B21      # ... the noise record
 AUG_OFFSET_SALT = 0x6175676F66667374    # ... where its window starts
 AUG_VOLUME_SALT = 0x617567766F6C2121    # ... and its volume
 AUG_SPEED_SALT = 0x6175677370656564     # ... and the step it is resampled at
+AUG_RIR_COIN_SALT = 0x61756772636F696E  # ... whether it is reverberated ("augrcoin")
+AUG_RIR_PICK_SALT = 0x617567727069636B  # ... and with which room response ("augrpick")
 SPEED_BITS = 24            # a speed is a fixed-point step with this many fraction bits: step = round(s * 2^24)
 SPEED_ONE = 1 << SPEED_BITS
 RESAMPLE_PHASES = 4096     # phases of the polyphase table (SRWN_RESAMPLE_PHASES in srwn.h); a power of two
 RESAMPLE_BETA = 7.0        # its Kaiser window (DESIGN section 5f says why these two)
+ROOM_MAX_TAPS = 8192       # taps of a room impulse response (SRWN_ROOM_MAX_TAPS in srwn.h): 0.51 s at 16 kHz
 _ROUNDS = 4
 CROPS = {"head": 0, "random": 1}
 MAX_BATCH = 65535          # rows of one draw (the launch's second grid dimension)
@@ -410,12 +413,17 @@ class Augment(object):
     ``speed=(lo, hi)``, 0.5 <= lo <= hi <= 2: before all that the row is resampled by a factor s of its own, ``y(j) =
     x(j * s)`` -- s > 1 plays faster and higher, by ``12 log2(s)`` semitones, and the content ends at T / s -- through a
     windowed-sinc table of ``taps`` taps (even, 2 .. 64) per phase, cut off for the fastest speed (``resample_table``).
-    The row's step is uniform on the fixed-point steps ``[step_lo, step_hi] = round(speed * 2^24)`` (``speed_plan``)."""
+    The row's step is uniform on the fixed-point steps ``[step_lo, step_hi] = round(speed * 2^24)`` (``speed_plan``).
+
+    ``reverb``, a ``DeviceDataset`` whose clips are room impulse responses ``[M, K]``, K at most ``ROOM_MAX_TAPS`` (its
+    labels are unused): with probability ``reverb_prob`` the resampled row is convolved with one of them, cut at the row's
+    length (``reverb_plan``, ``reverb_rows``), before shift, gain and noise -- the noise is added dry.  ``prepare_rirs``
+    brings measured responses into the form a draw wants; ``synthetic_rirs`` makes some up."""
     __slots__ = ("shift", "gain", "noise", "noise_prob", "noise_volume", "noise_threshold", "speed", "taps", "step_lo",
-                 "step_hi")
+                 "step_hi", "reverb", "reverb_prob", "reverb_threshold")
 
     def __init__(self, shift=0, gain=(1.0, 1.0), noise=None, noise_prob=0.0, noise_volume=(0.0, 0.0), speed=(1.0, 1.0),
-                 taps=16):
+                 taps=16, reverb=None, reverb_prob=0.0):
         if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 0 <= int(shift) < 1 << 31:
             raise ValueError("shift %r: a number of samples, at least 0" % (shift,))
         if noise is not None and not isinstance(noise, DeviceDataset):
@@ -445,6 +453,17 @@ class Augment(object):
         set_(self, "taps", int(taps))
         set_(self, "step_lo", int(round(lo * SPEED_ONE)))
         set_(self, "step_hi", int(round(hi * SPEED_ONE)))
+        if reverb is not None and not isinstance(reverb, DeviceDataset):
+            raise TypeError("reverb must be a DeviceDataset of room impulse responses, got %s" % type(reverb).__name__)
+        try:
+            set_(self, "reverb_threshold", same_threshold(reverb_prob))
+        except (TypeError, ValueError):
+            raise ValueError("reverb_prob %r: a probability" % (reverb_prob,))
+        if reverb is None and self.reverb_threshold:
+            raise ValueError("reverb_prob %r without reverb: pass the room impulse responses as reverb=DeviceDataset(...)"
+                             % (reverb_prob,))
+        set_(self, "reverb", reverb)
+        set_(self, "reverb_prob", float(reverb_prob))
 
     def __setattr__(self, name, value=None):
         raise AttributeError("an Augment is immutable")
@@ -452,14 +471,22 @@ class Augment(object):
     __delattr__ = __setattr__
 
     def __repr__(self):
-        return "Augment(shift=%d, gain=%r, noise=%s, noise_prob=%r, noise_volume=%r%s)" % (
+        return "Augment(shift=%d, gain=%r, noise=%s, noise_prob=%r, noise_volume=%r%s%s)" % (
             self.shift, self.gain, "None" if self.noise is None else "<%d clips>" % len(self.noise), self.noise_prob,
-            self.noise_volume, ", speed=%r, taps=%d" % (self.speed, self.taps) if self.resamples else "")
+            self.noise_volume, ", speed=%r, taps=%d" % (self.speed, self.taps) if self.resamples else "",
+            ", reverb=<%d responses of %d taps>, reverb_prob=%r" % (len(self.reverb), self.reverb.clip_len, self.reverb_prob)
+            if self.reverberates else "")
 
     @property
     def resamples(self) -> bool:
         """Whether a draw resamples its rows: any speed but exactly (1, 1) (then the draw is the ``_aug`` entry's)."""
         return (self.step_lo, self.step_hi) != (SPEED_ONE, SPEED_ONE)
+
+    @property
+    def reverberates(self) -> bool:
+        """Whether a draw may reverberate a row: there are responses and the probability is not zero (then the draw is the
+        ``_room`` entry's; otherwise it is the entry it was without the two keywords)."""
+        return self.reverb is not None and self.reverb_threshold != 0
 
     @property
     def cutoff(self) -> float:
@@ -471,7 +498,8 @@ class Augment(object):
         return resample_table(self.cutoff, self.taps)
 
     def check(self, dataset, num_samples: int) -> None:
-        """What only a sampler knows: the shift stays inside the row, the noise lives beside the clips and covers a row."""
+        """What only a sampler knows: the shift stays inside the row, the noise lives beside the clips and covers a row,
+        the room responses live there too, are short enough for the kernel and finite (one reduction on the device)."""
         if self.shift >= int(num_samples):
             raise ValueError("augment: shift %d: below num_samples %d" % (self.shift, int(num_samples)))
         if self.noise is not None:
@@ -480,6 +508,15 @@ class Augment(object):
             if self.noise.clip_len < int(num_samples):
                 raise ValueError("augment: noise clips of %d samples are shorter than num_samples %d"
                                  % (self.noise.clip_len, int(num_samples)))
+        if self.reverb is not None:
+            if str(self.reverb.device) != str(dataset.device):
+                raise ValueError("augment: the room responses are on %s, the clips are on %s"
+                                 % (self.reverb.device, dataset.device))
+            if not 1 <= self.reverb.clip_len <= ROOM_MAX_TAPS:
+                raise ValueError("augment: room responses of %d taps: 1 to %d" % (self.reverb.clip_len, ROOM_MAX_TAPS))
+            import torch
+            if not bool(torch.isfinite(self.reverb.audio).all()):
+                raise ValueError("augment: the room responses hold a tap that is not finite")
 
 
 AugmentPlan = namedtuple("AugmentPlan", "shift gain mix noise_index noise_offset volume")
@@ -654,6 +691,106 @@ def resample_rows(rows, steps, table) -> np.ndarray:
     return out
 
 
+ReverbPlan = namedtuple("ReverbPlan", "apply index")
+
+
+def reverb_plan(seed: int, step: int, batch_size: int, augment: "Augment", rir_n: int, rank: int = 0, world: int = 1,
+                side: int = 0) -> "ReverbPlan":
+    """The reverberation of the rows of ``step``: ``(apply [B] bool, index [B] int32)``.  Row b at ``draw_plan``'s position
+    p takes two more draws under the key of the other seven, ``h = _mix64((seed ^ SALT) + _GOLDEN * (2 * p + side + 1))``
+    with ``AUG_RIR_COIN_SALT`` and ``AUG_RIR_PICK_SALT``, so none of those moves: ``apply = (h_coin >> 32) <
+    floor(reverb_prob * 2^32)`` (never without responses: `rir_n` 0) and ``index = ((h_pick >> 32) * rir_n) >> 32``, uniform
+    on [0, rir_n)."""
+    batch_size, rir_n = int(batch_size), int(rir_n)
+    if not isinstance(augment, Augment):
+        raise TypeError("augment must be an Augment, got %s" % type(augment).__name__)
+    if not 1 <= batch_size <= MAX_BATCH:
+        raise ValueError("batch_size %d: at least 1, at most %d" % (batch_size, MAX_BATCH))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError("rank %d of %d" % (rank, world))
+    if side not in (0, 1):
+        raise ValueError("side %r: 0 or 1" % (side,))
+    if rir_n < 0:
+        raise ValueError("reverb_plan: %d room responses" % rir_n)
+    seed &= _MASK
+    plan = ReverbPlan(np.zeros(batch_size, bool), np.zeros(batch_size, np.int32))
+    for b in range(batch_size):
+        p = (step * world + rank) * batch_size + b
+        h = lambda salt: _mix64((seed ^ salt) + _GOLDEN * (2 * p + side + 1))
+        if rir_n > 0:
+            plan.apply[b] = (h(AUG_RIR_COIN_SALT) >> 32) < augment.reverb_threshold
+            plan.index[b] = ((h(AUG_RIR_PICK_SALT) >> 32) * rir_n) >> 32
+    return plan
+
+
+def reverb_rows(rows, plan: "ReverbPlan", rirs) -> np.ndarray:
+    """The reverberation rule on the (cropped, resampled) rows ``[B, T]``, in fp32.  Where ``plan.apply[b]``, with ``h =
+    rirs[plan.index[b]]`` of K taps: ``e[j]`` is accumulated in tap order k = 0 .. K - 1 from +0.0, ``acc = fp32(acc +
+    fp32(h[k] * r[j - k]))``, every product and every sum rounded separately, with r = +0.0 outside [0, T) -- the record
+    before the crop window is never read -- and the tail beyond T is cut.  Elsewhere the row passes untouched, bit for bit.
+    In-order sums are the rule because NumPy can state them: a pairwise or fused sum has other bits."""
+    x = np.ascontiguousarray(rows, dtype=np.float32)
+    if x.ndim != 2 or x.shape[0] != plan.apply.shape[0]:
+        raise ValueError("rows must be [%d, T], got %s" % (plan.apply.shape[0], tuple(x.shape)))
+    out = x.copy()
+    if not plan.apply.any():
+        return out
+    rirs = np.asarray(rirs, dtype=np.float32)
+    if rirs.ndim != 2 or not 1 <= rirs.shape[1] <= ROOM_MAX_TAPS:
+        raise ValueError("rirs must be [M, K] with 1 <= K <= %d, got %s" % (ROOM_MAX_TAPS, tuple(rirs.shape)))
+    B, T = x.shape
+    K = rirs.shape[1]
+    for b in np.nonzero(plan.apply)[0]:
+        h = rirs[int(plan.index[b])]
+        padded = np.concatenate([np.zeros(K - 1, np.float32), x[b]])       # padded[K - 1 + i] = r[i]
+        acc = np.zeros(T, np.float32)
+        with np.errstate(all="ignore"):
+            for k in range(K):
+                acc = (acc + (h[k] * padded[K - 1 - k:K - 1 - k + T]).astype(np.float32)).astype(np.float32)
+        out[b] = acc
+    return out
+
+
+def prepare_rirs(rirs, length: int) -> np.ndarray:
+    """Measured room impulse responses ``[M, any]`` (or one, ``[any]``) as a draw wants them, float32 ``[M, length]``,
+    computed in float64: what precedes each response's largest |tap| -- the direct path -- is dropped, so reverberation
+    does not delay the signal; the rest is cut or zero-padded to `length` and scaled to unit energy, so it does not change
+    the level of white input.  A response with a tap that is not finite, or with none that is not zero, is refused."""
+    h = np.atleast_2d(np.asarray(rirs, dtype=np.float64))
+    length = int(length)
+    if h.ndim != 2 or h.shape[1] < 1:
+        raise ValueError("rirs must be [M, taps], got %s" % (tuple(np.shape(rirs)),))
+    if not 1 <= length <= ROOM_MAX_TAPS:
+        raise ValueError("length %d: 1 to %d taps" % (length, ROOM_MAX_TAPS))
+    out = np.zeros((h.shape[0], length), np.float64)
+    for m in range(h.shape[0]):
+        if not np.isfinite(h[m]).all():
+            raise ValueError("response %d holds a tap that is not finite" % m)
+        if not h[m].any():
+            raise ValueError("response %d is all zero" % m)
+        d = h[m, int(np.argmax(np.abs(h[m]))):][:length]
+        out[m, :d.shape[0]] = d / np.sqrt(np.sum(d * d))
+    return out.astype(np.float32)
+
+
+def synthetic_rirs(n: int, length: int, rt60=(0.2, 0.6), sample_rate: int = 16000, seed: int = 0) -> np.ndarray:
+    """`n` made-up room responses, float32 ``[n, length]``: seeded Gaussian noise under ``exp(-6.908 t / rt60)`` -- the
+    energy falls by 60 dB in rt60 seconds -- with rt60 uniform on the range and a unit first tap (the direct path), passed
+    through ``prepare_rirs``.  For the drivers, the benchmarks and the tests; a real corpus goes through ``prepare_rirs``."""
+    n, length = int(n), int(length)
+    try:
+        lo, hi = (float(v) for v in rt60)
+    except (TypeError, ValueError):
+        raise ValueError("rt60 %r: a range (lo, hi) of seconds" % (rt60,))
+    if n < 1 or not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi) or sample_rate <= 0:
+        raise ValueError("synthetic_rirs: n=%d, rt60=%r, sample_rate=%r" % (n, rt60, sample_rate))
+    rng = np.random.default_rng(seed)
+    t = np.arange(length, dtype=np.float64) / float(sample_rate)
+    h = rng.standard_normal((n, length)) * np.exp(-6.908 * t[None, :] / rng.uniform(lo, hi, (n, 1)))
+    h[:, 0] = 1.0
+    return prepare_rirs(h, length)
+
+
 def add_augment_flags(parser) -> None:
     """The drivers' augmentation flags (examples/classifier.py, examples/siamese.py); ``augment_from_flags`` reads them."""
     g = parser.add_argument_group("augmentation (--device-data)")
@@ -665,6 +802,9 @@ def add_augment_flags(parser) -> None:
     g.add_argument("--speed", type=str, default=None, metavar="LO:HI",
                    help="resample every drawn clip by a factor uniform on [LO, HI] within [0.5, 2]: tempo and pitch together")
     g.add_argument("--resample-taps", type=int, default=None, metavar="N", help="taps of the resampling filter (even, 2..64; 16)")
+    g.add_argument("--rir", type=str, default=None, metavar="FILE.npy",
+                   help="room impulse responses to reverberate with: an [M, K] array, K <= %d (dataset.prepare_rirs)" % ROOM_MAX_TAPS)
+    g.add_argument("--rir-prob", type=float, default=0.0, metavar="P", help="reverberate a drawn clip with probability P")
 
 
 def _flag_range(text, name):
@@ -681,7 +821,9 @@ def augment_from_flags(args, device_data: bool, device="cuda") -> Optional["Augm
     asked = [f for f, on in (("--shift", args.shift != 0), ("--gain", args.gain is not None), ("--noise", args.noise is not None),
                              ("--noise-prob", args.noise_prob != 0.0), ("--noise-volume", args.noise_volume is not None),
                              ("--speed", getattr(args, "speed", None) is not None),
-                             ("--resample-taps", getattr(args, "resample_taps", None) is not None)) if on]
+                             ("--resample-taps", getattr(args, "resample_taps", None) is not None),
+                             ("--rir", getattr(args, "rir", None) is not None),
+                             ("--rir-prob", getattr(args, "rir_prob", 0.0) != 0.0)) if on]
     if not asked:
         return None
     if not device_data:
@@ -693,11 +835,18 @@ def augment_from_flags(args, device_data: bool, device="cuda") -> Optional["Augm
         if clips.ndim != 2:
             raise SystemExit("--noise %s: an [M, len] array of background clips, got shape %s" % (args.noise, clips.shape))
         noise = DeviceDataset(clips.astype(np.float32), device=device)
+    reverb = None
+    if getattr(args, "rir", None) is not None:
+        rirs = np.load(args.rir)
+        if rirs.ndim != 2:
+            raise SystemExit("--rir %s: an [M, K] array of room impulse responses, got shape %s" % (args.rir, rirs.shape))
+        reverb = DeviceDataset(rirs.astype(np.float32), device=device)
     try:
         return Augment(args.shift, (1.0, 1.0) if args.gain is None else _flag_range(args.gain, "gain"), noise,
                        args.noise_prob, (0.0, 0.0) if args.noise_volume is None else _flag_range(args.noise_volume, "noise-volume"),
                        (1.0, 1.0) if getattr(args, "speed", None) is None else _flag_range(args.speed, "speed"),
-                       16 if getattr(args, "resample_taps", None) is None else args.resample_taps)
+                       16 if getattr(args, "resample_taps", None) is None else args.resample_taps, reverb,
+                       getattr(args, "rir_prob", 0.0))
     except (TypeError, ValueError) as e:
         raise SystemExit("augmentation flags: %s" % e)
 
@@ -775,6 +924,23 @@ class BatchSampler(object):
             self._resample_dev = torch.as_tensor(a.table().copy()).to(self.dataset.device)    # (the cached one is read-only)
         return (self._resample_dev.data_ptr(), a.taps, a.step_lo, a.step_hi)
 
+    def reverb_plan(self, step: Optional[int] = None, side: int = 0) -> "ReverbPlan":
+        """``reverb_plan`` of `step` (default: the next one) for this sampler's ``augment``."""
+        if self.augment is None:
+            raise ValueError("this sampler does not augment (it was built with augment=None)")
+        rv = self.augment.reverb
+        return reverb_plan(self.seed, self.step if step is None else int(step), self.batch_size, self.augment,
+                           0 if rv is None else len(rv), self.rank, self.world, side)
+
+    def _room_args(self):
+        """The resampling block and the room block of the ``_room`` entries (srwn.h), behind the augmentation block: a
+        null table where the speed is (1, 1) -- through the table, phase 0 would turn -0.0 into +0.0.  Uploads nothing:
+        the responses live in their ``DeviceDataset``."""
+        a = self.augment
+        rv = a.reverb
+        warp = self._resample_args() if a.resamples else (None, 0, SPEED_ONE, SPEED_ONE)
+        return warp + (rv.audio.data_ptr(), len(rv), rv.clip_len, a.reverb_threshold)
+
     def seek(self, step: int) -> None:
         """Continues the sequence at `step` (a run resumed from a checkpoint): sets the device counter and the host's."""
         if int(step) < 0:
@@ -814,6 +980,8 @@ class BatchSampler(object):
                 self.indices.data_ptr())
         if self.augment is None:
             K.call("srwn_batch_draw", *args, K._stream())
+        elif self.augment.reverberates:      # ... and, where the row's coin says so, through dataset.reverb_rows
+            K.call("srwn_batch_draw_room", *args, *self._augment_args(), *self._room_args(), K._stream())
         elif not self.augment.resamples:     # the same rows through dataset.augment_rows, audio, audio2 and codes alike
             K.call("srwn_batch_draw_aug", *args, *self._augment_args(), K._stream())
         else:                                # ... through dataset.resample_rows first
@@ -989,6 +1157,12 @@ class PairSampler(BatchSampler):
             return BatchSampler.speed_plan(self, step, 0), BatchSampler.speed_plan(self, step, 1)
         return BatchSampler.speed_plan(self, step, side)
 
+    def reverb_plan(self, step: Optional[int] = None, side: Optional[int] = None):
+        """``reverb_plan`` of `step` (default: the next one): ``(left, right)``, or one `side` of the pairs."""
+        if side is None:
+            return BatchSampler.reverb_plan(self, step, 0), BatchSampler.reverb_plan(self, step, 1)
+        return BatchSampler.reverb_plan(self, step, side)
+
     def draw(self, audio, labels):
         """srwn_pair_draw (with an ``Augment``: srwn_pair_draw_aug) on the current stream: the left clips into rows [0, P) and the right ones into rows [P, 2P) of
         `audio` ([2P, T] fp32), y into `labels` ([P] fp32); the draw's indices and y into ``indices``, ``right``, ``y``."""
@@ -1003,6 +1177,8 @@ class PairSampler(BatchSampler):
                 self.y.data_ptr())
         if self.augment is None:
             K.call("srwn_pair_draw", *args, K._stream())
+        elif self.augment.reverberates:
+            K.call("srwn_pair_draw_room", *args, *self._augment_args(), *self._room_args(), K._stream())
         elif not self.augment.resamples:
             K.call("srwn_pair_draw_aug", *args, *self._augment_args(), K._stream())
         else:
